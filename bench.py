@@ -2,7 +2,7 @@
 """bench.py -- BASELINE.json metric: audio frames/s (and per-frame logit max-abs-err vs the CPU
 reference) on the named frame shape.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -21,7 +21,13 @@ the same steps keep running untimed for --settle seconds (default 0.6): the in-f
 the power controller needs ~0.3 s to pull the shader clock down to what it then sustains, so a timed region entered cold is
 measured at a clock the job does not keep (`settle` on the line; `sustained` = the same regime over >= 2 s).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up (W steps, then --settle seconds of the same steps untimed), times the K steps, writes the last
+timed step's logits if --dump-outputs DIR is given (DIR/logits.npy, float32; inputs and weights are seeded, so two builds compare
+output for output) and prints the line: metric, value, unit, ms_per_step, dtype, config, settle, stages, ranks,
+in_flight_batch_latency_ms.  Everything else -- every extra measurement below and the check that the in-flight outputs equal a
+single call's -- runs only with --full (the --no-* options then drop single legs of it).
+
+Extra objects on the JSON line (--full):
   roofline     -- the kernel with the largest share of a step's kernel time (rocprofv3 --kernel-trace --stats of the step submitted
                   alone: profiles/r05_bench_sequential_kernel_stats.csv), lstm_rec16h_kernel: ALGORITHMIC f32-equivalent FLOP of one
                   launch (2 x 4H x H per frame, direction and layer) / its launch duration MEASURED WITH THE GPU TO
@@ -113,6 +119,13 @@ def main():
     ap.add_argument("--reproducible", action="store_true",
                     help="with --rec-tile 0: every rank runs the recurrent form the library would pick for the GLOBAL batch "
                          "(uvad_recurrent_tile_for(world x batch)), so an utterance gets the same bits for every N")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra measurements and checks after the timed steps: roofline (launches alone on the GPU), clocks, "
+                         "sustained / sequential / all_f32 / f32_gemm / three_products, SincNet, reference shape, CPU baseline and logit "
+                         "errors, in-flight outputs vs a single call (a plain run times the K steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (the per-frame logits) as "
+                         "DIR/logits.npy (float32)")
     ap.add_argument("--scatter", action="store_true",
                     help="extra measurement (N > 1): root-resident PCM scattered to the ranks (RCCL over xGMI) on a side stream, "
                          "double-buffered against the compute; reported as the extra object 'scatter', never in 'value'")
@@ -194,7 +207,7 @@ def main():
         r.set_timing(live_events)
     acc = {"fbank": 0.0, "proj": 0.0, "recurrent": 0.0, "head": 0.0, "total": 0.0}
     n_acc = 0
-    sampler = start_sampler(dev) if rank == 0 else None
+    sampler = start_sampler(dev) if rank == 0 and args.full else None
     torch.cuda.synchronize(dev)
     udist.barrier()
     t0 = time.perf_counter()
@@ -227,14 +240,19 @@ def main():
         n_acc += 1
     for r in rts:
         r.set_timing(False)
-    # Outside the timed region: every step processed the same batch, so the logits of the last n_fly steps (one per slot, all
-    # produced while the others were in flight) must equal, bit for bit, what one call alone produces.  Concurrent kernels
-    # corrupting each other would show here (tools/pipe_check.py is the longer version of this check).
-    alone = rts[0].forward(pcm, want_probs=False)[0]
-    torch.cuda.synchronize(dev)
-    n_wrong = sum(int(not torch.equal(p.result()[0], alone)) for p in recent)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, recent[-1], rank, world)
+    n_wrong = 0
+    if args.full:
+        # Outside the timed region: every step processed the same batch, so the logits of the last n_fly steps (one per slot, all
+        # produced while the others were in flight) must equal, bit for bit, what one call alone produces.  Concurrent kernels
+        # corrupting each other would show here (tools/pipe_check.py is the longer version of this check).
+        alone = rts[0].forward(pcm, want_probs=False)[0]
+        torch.cuda.synchronize(dev)
+        n_wrong = sum(int(not torch.equal(p.result()[0], alone)) for p in recent)
+        del alone
     lat = sorted(p.elapsed_ms() for p in all_steps)
-    del recent, alone, all_steps
+    del recent, all_steps
     # what every rank actually did (the first real N > 1 run proves RCCL saw N ranks, and a rank whose stream probe settled for fewer
     # steps in flight -- RCCL's own streams share the 16 hardware queues -- shows here instead of silently halving the rate)
     per_rank = udist.all_gather_floats([float(rank), float(n_fly), B * T * args.steps / elapsed, elapsed, float(dev.index or 0)],
@@ -277,11 +295,13 @@ def main():
     for k in stage:
         stage[k]["note"] = "HIP-event time inside the timed region: stretched by the other in-flight steps' kernels; not a kernel figure"
 
-    # ---- roofline: every duration in it is measured with the GPU to itself (alone_on_gpu), never inside the in-flight region.
-    alone = alone_on_gpu(rts[0], dev, pcm, args.rec_tile)
-    n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
     step_ms = elapsed / args.steps * 1e3
-    roofline = build_roofline(alone, B, T, rec_tile, n_cu, step_ms, n_fly, clocks)
+    roofline = None
+    if args.full:
+        # ---- roofline: every duration in it is measured with the GPU to itself (alone_on_gpu), never inside the in-flight region.
+        alone = alone_on_gpu(rts[0], dev, pcm, args.rec_tile)
+        n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
+        roofline = build_roofline(alone, B, T, rec_tile, n_cu, step_ms, n_fly, clocks)
 
     out = {
         "metric": "audio frames/sec (log-mel + PyanNet2 VAD forward); per-frame logit max-abs-err vs CPU ref",
@@ -300,10 +320,13 @@ def main():
         "settle": {"seconds": args.settle, "untimed_steps": settle_steps,
                    "what": "the same in-flight steps run untimed between the W warm-up steps and the timed region, so that the K timed steps see the "
                            "shader clock the regime sustains at the socket's power limit, not the idle-start clock"},
-        "roofline": roofline, "stages": stage,
+        "stages": stage,
         "classifier_f32_equivalent_TFLOPs": frames_step * (proj_f + rec_f + head_f) / (step_ms * 1e-3) / 1e12,
     }
-    out["in_flight_outputs_identical_to_single_call"] = n_wrong == 0
+    if roofline is not None:
+        out["roofline"] = roofline
+    if args.full:
+        out["in_flight_outputs_identical_to_single_call"] = n_wrong == 0
     out["ranks"] = {"ranks_seen": len(per_rank), "backend": udist.backend_name(),
                     "per_rank": [{"rank": int(r[0]), "steps_in_flight": int(r[1]), "value": r[2], "seconds": r[3], "cuda_device": int(r[4])} for r in per_rank],
                     "what": "all-gather over the process group after the timed region: each rank's own frames/s over its own elapsed time "
@@ -316,7 +339,7 @@ def main():
                                          "what": "device time of ONE batch (first kernel allowed to start -> last kernel done) while the other "
                                                  f"{n_fly - 1} steps share the GPU; sequential.ms_per_step is the same batch alone"}
 
-    if n_fly > 1 and not args.no_sequential:
+    if args.full and n_fly > 1 and not args.no_sequential:
         out["sustained"] = sustained_leg(pipe, dev, pcm, world, rank, seconds=2.2, step_ms=step_ms)
         out["sequential"] = sequential_latency(rts[0], dev, pcm, min(args.steps, 10), world, args.rec_tile)
         out["all_f32"] = all_f32_leg(pipe, dev, pcm, world, args.rec_tile)
@@ -331,11 +354,11 @@ def main():
                                          "matrix work is time; logit error of this mode: logit_err_three_product_mode")
     if args.scatter:
         out["scatter"] = scatter_leg(rt, dev, B, S, rank, world, min(args.steps, 10))
-    if rank == 0 and world == 1 and not args.no_sincnet:
+    if args.full and rank == 0 and world == 1 and not args.no_sincnet:
         out["pyannet_sincnet"] = sincnet_throughput(dev)
-    if rank == 0 and world == 1 and not args.no_reference_shape:
+    if args.full and rank == 0 and world == 1 and not args.no_reference_shape:
         out["reference_shape"] = reference_shape_leg(dev, with_cpu=not args.no_cpu_baseline)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out.update(cpu_baseline_and_error(model, rt, pcm, dev))
     if rank == 0:
         bad = fracs_above_one(out)
@@ -348,6 +371,25 @@ def main():
 
 
 P2Q_ACTIVE = True   # set from runtime.p2_on_fp8() once the model is finalized
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, pending, rank, world):
+    """--dump-outputs: what the timed path hands its caller, from the last timed step -- the per-frame logits (B x T, float32; the
+    probabilities are not requested by the timed path) -- as <path>/logits.npy (logits_rank<r>.npy per rank when N > 1).  Above
+    64 MB in all a fixed, seeded sample of utterances is written instead, their row indices beside it (logits_rows.npy, float64)."""
+    import numpy as np
+    logits = pending.result()[0]
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    B = logits.shape[0]
+    keep = max(1, min(B, DUMP_MAX_BYTES // world // max(1, logits[0].numel() * 4 + 8)))
+    if keep < B:
+        rows = torch.randperm(B, generator=torch.Generator().manual_seed(20251015))[:keep].sort().values
+        np.save(os.path.join(path, f"logits_rows{tag}.npy"), rows.numpy().astype(np.float64))
+        logits = logits[rows.to(logits.device)]
+    np.save(os.path.join(path, f"logits{tag}.npy"), logits.float().cpu().numpy())
+    log(f"last timed step's logits {tuple(logits.shape)} written to {os.path.join(path, f'logits{tag}.npy')}")
 
 
 def fracs_above_one(obj, path=""):

@@ -543,6 +543,39 @@ def test_bench_two_ranks_on_one_gpu_gloo_rehearsal(launcher):
     print(f"2-rank rehearsal ({launcher}):", {k: d[k] for k in ("value", "ms_per_step")}, sc)
 
 
+def test_bench_plain_run_dumps_the_last_timed_steps_logits(tmp_path):
+    """A plain `bench.py` run (no --full): the line carries the headline keys and none of the extra legs, `steps` is --steps, and
+    --dump-outputs writes the last timed step's logits -- bit for bit what one call of the bench's recurrent form returns for the
+    same seeded PCM and weights."""
+    import json, os, subprocess, sys
+    import uvad_amd
+    from uvad_amd.synth import synth_pcm_device
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B = 32
+    out_dir = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B),
+                        "--settle", "0.05", "--dump-outputs", str(out_dir)], cwd=root, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - B * 1000 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    for k in ("roofline", "sustained", "sequential", "all_f32", "pyannet_sincnet", "reference_shape", "cpu_baseline", "clocks_during_timed_region"):
+        assert k not in d, k
+    got = np.load(out_dir / "logits.npy")
+    assert got.dtype == np.float32 and got.shape == (B, 1000)
+    dev = torch.device("cuda:0")
+    m = _cfg2_model(dev, 4.0)
+    rt = m.runtime(dev)
+    rt.set_recurrent_tile(16)
+    want = m.forward_waveform(synth_pcm_device(B, 160000, seed=42, device=dev))[0].cpu().numpy()
+    rt.set_recurrent_tile(0)
+    assert np.array_equal(got, want), float(np.abs(got - want).max())
+
+
 @pytest.mark.parametrize("mode", ["f16p", "f16p3"])
 def test_bench_regime_outputs_identical_to_single_calls(mode):
     """The headline regime checked for CORRECTNESS, not speed: twelve steps of the cfg-2 batch in flight on twelve hardware queues with

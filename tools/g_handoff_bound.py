@@ -82,7 +82,7 @@ def run():
     for rep in range(2):          # alternating: the boxes' clocks drift
         for name, env in settings:
             e = dict(os.environ, **env)
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_lib.py"), lib, "--steps", "200", "--warmup", "3", "--no-cpu-baseline", "--no-sincnet",
+            p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_lib.py"), lib, "--steps", "200", "--warmup", "3", "--full", "--no-cpu-baseline", "--no-sincnet",
                                 "--no-sequential", "--no-reference-shape"], env=e, capture_output=True, text=True, timeout=600)
             line = [l for l in p.stdout.splitlines() if l.startswith("{")]
             if not line:

@@ -18,7 +18,7 @@ run_pass() {   # name, counters...
     if [ $rc -ne 0 ]; then echo "[profile] pass $name failed with rc $rc (unknown counter?): see $OUT/$name.log; continuing"; tail -3 "$OUT/$name.log"; fi
 }
 echo "[profile] kernel stats"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 $REPO/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-sincnet --no-reference-shape "$@" > "$OUT/stats.log" 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 $REPO/bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-sincnet --no-reference-shape "$@" > "$OUT/stats.log" 2>&1
 echo "[profile] kernel stats of the step submitted alone (throughput recurrence)"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/seqstats" -- python3 $REPO/bench.py --steps 5 --warmup 2 --settle 0 --in-flight 1 --rec-tile 16 --no-cpu-baseline --no-sincnet --no-sequential --no-reference-shape > "$OUT/seqstats.log" 2>&1
 run_pass fetch FETCH_SIZE
