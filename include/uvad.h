@@ -41,7 +41,7 @@ extern "C" {
 #define UVAD_E_WORKSPACE   -4
 #define UVAD_E_UNSUPPORTED -5
 
-#define UVAD_ABI_VERSION 4
+#define UVAD_ABI_VERSION 5
 
 typedef struct uvad_ctx uvad_ctx; /* opaque */
 
@@ -224,6 +224,15 @@ int uvad_sincnet(uvad_ctx *, const float *d_wav, int B, int64_t S, float *d_feat
 /* Replaces: PyanNet.forward (PyanNet.py:162-195): uvad_sincnet + uvad_classify; d_logits / d_probs [B][frames]. */
 int uvad_forward_wav(uvad_ctx *, const float *d_wav, int B, int64_t S, float *d_logits, float *d_probs,
                      void *d_workspace, size_t ws_bytes, void *stream);
+
+/* uvad_sincnet / uvad_forward_wav from 16-bit PCM as read from a wav file: samples are read as q / 32768 (as uvad_fbank_i16), straight
+ * from d_wav by the waveform kernels (no conversion pass, no f32 copy).  Same workspace (uvad_sincnet_workspace_bytes), same form
+ * selection (uvad_get_sincnet_form), asynchronous and capturable like the f32 calls; the results are the f32 calls' bits on q / 32768
+ * for S < 2^23 samples per row (the waveform statistics are summed exactly, csrc/sincnet.hip). */
+int uvad_sincnet_i16(uvad_ctx *, const int16_t *d_wav, int B, int64_t S, float *d_feats, void *d_workspace,
+                     size_t ws_bytes, void *stream);
+int uvad_forward_wav_i16(uvad_ctx *, const int16_t *d_wav, int B, int64_t S, float *d_logits, float *d_probs,
+                         void *d_workspace, size_t ws_bytes, void *stream);
 
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;

@@ -9,7 +9,7 @@ LIB_PATH = os.path.join(_HERE, "libuvad.so")
 
 UVAD_OK = 0
 ERR_NAMES = {-1: "UVAD_E_ARG", -2: "UVAD_E_HIP", -3: "UVAD_E_STATE", -4: "UVAD_E_WORKSPACE", -5: "UVAD_E_UNSUPPORTED"}
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 class FbankCfg(C.Structure):
@@ -59,6 +59,9 @@ SIGNATURES = {
     "uvad_sincnet": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_forward_wav": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_sincnet_i16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_forward_wav_i16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_get_taps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uvad_stream_state_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "uvad_stream_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),

@@ -1,7 +1,7 @@
 // sincnet.hip -- SincNet front end of PyanNet (reference: src/models/blocks/sincnet.py:33-103, called from
 // PyanNet.forward, src/models/segmentation/PyanNet.py:177).  waveform (B, S) -> features (B, frames, 60):
 //
-//   wav_norm1d (InstanceNorm1d(1))                                   -> wav_stats_kernel   (scale, shift per b)
+//   wav_norm1d (InstanceNorm1d(1))                                   -> wav_stats_kernel   (scale, shift per b; int16: wav_stats_i16_kernel)
 //   sinc filter bank conv (80 x 251, stride 10), |.|, MaxPool1d(3)   -> conv_pool_kernel<3, true>
 //   InstanceNorm1d(80) + leaky_relu                                  -> norm_finalize_kernel (scale, shift per (b, c)),
 //                                                                       applied when the NEXT conv stages its input
@@ -19,6 +19,8 @@
 // bias, |.|, the 3:1 max pool and the per-tile (sum, M2) statistics the instance norm of the next stage
 // needs -- written as per-tile partials and reduced in tile order, so results do not depend on scheduling.
 #include "uvad_internal.h"
+
+#include <type_traits>
 
 namespace uvad {
 
@@ -80,8 +82,67 @@ __global__ __launch_bounds__(1024) void wav_stats_kernel(const float *wav, long 
     }
 }
 
-template <int NT, bool CIN1, int EPT, int WAVES>
+// The same statistics of int16 samples read as q / 32768 (wav ingest, uvad_sincnet_i16 / uvad_forward_wav_i16): the raw integers are summed
+// exactly in int64 and scaled once.  The f32 kernel's double sums of q / 32768 are exact as well, in any order, while S < 2^23 (524 s per
+// row): every term of the sum is a multiple of 2^-15 and every square a multiple of 2^-30, each of magnitude <= 1, so a 53-bit significand
+// holds every partial sum.  Both kernels therefore reach the same (s, ss) and, through the same closing arithmetic, (scale, shift) that are
+// bit-identical to the f32 call on q.float() / 32768 for S < 2^23; longer rows get the exact statistics here.
+__global__ __launch_bounds__(1024) void wav_stats_i16_kernel(const int16_t *wav, long long S, long long row_stride, const float *gamma,
+                                                             const float *beta, float eps, float *scale, float *shift) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int16_t *x = wav + (size_t)b * row_stride;
+    long long s = 0, ss = 0;
+    long long i0 = 0;
+    if ((reinterpret_cast<uintptr_t>(x) & 15) == 0) {   // 16-byte loads (8 samples)
+        const long long n8 = S >> 3;
+        for (long long i = tid; i < n8; i += 1024) {
+            const int4 v = reinterpret_cast<const int4 *>(x)[i];
+            const int w[4] = {v.x, v.y, v.z, v.w};
+            int cs = 0;
+            unsigned long long css = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int lo = (int)(int16_t)(w[k] & 0xffff), hi = w[k] >> 16;   // little endian: sample 2k in the low half
+                cs += lo + hi;
+                css += (unsigned)(lo * lo) + (unsigned)(hi * hi);               // <= 2^31 per pair
+            }
+            s += cs;
+            ss += (long long)css;
+        }
+        i0 = n8 << 3;
+    }
+    for (long long i = i0 + tid; i < S; i += 1024) {
+        const int v = x[i];
+        s += v;
+        ss += (long long)(v * v);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { s += __shfl_xor(s, o); ss += __shfl_xor(ss, o); }
+    __shared__ long long red[2][16];
+    if ((tid & 63) == 0) { red[0][tid >> 6] = s; red[1][tid >> 6] = ss; }
+    __syncthreads();
+    if (tid == 0) {
+        s = 0; ss = 0;
+        for (int w = 0; w < 16; ++w) { s += red[0][w]; ss += red[1][w]; }
+        const double sd = (double)s * 0x1p-15, ssd = (double)ss * 0x1p-30;   // exact while |s| < 2^53, ss < 2^53 (S < 2^23)
+        const double mean = sd / (double)S;
+        double var = ssd / (double)S - mean * mean;
+        if (var < 0.0) var = 0.0;
+        const double sc = (double)gamma[0] / sqrt(var + (double)eps);
+        scale[b] = (float)sc;
+        shift[b] = (float)((double)beta[0] - mean * sc);
+    }
+}
+
+// a waveform sample as the stages stage it: f32 as given, int16 scaled by 2^-15 (exact: the f32 value of q / 32768)
+__device__ __forceinline__ float wav_sample(float v) { return v; }
+__device__ __forceinline__ float wav_sample(int16_t v) { return (float)v * 0x1p-15f; }
+
+// I16: the single-channel stage reads the waveform as int16 (a.in_i16), converted in the prefetch with wav_sample
+template <int NT, bool CIN1, int EPT, int WAVES, bool I16 = false>
 __global__ __launch_bounds__(WAVES * 64) void conv_pool_kernel(SincConvArgs a) {
+    static_assert(CIN1 || !I16, "int16 input is the waveform: single-channel stage only");
+    using Tin = typename std::conditional<I16, int16_t, float>::type;
     constexpr int NW = NT * 32;
     constexpr int NTHR = WAVES * 64;
     constexpr int CTW = WAVES * 32;            // conv positions computed per tile (one 32-row MFMA block per wave)
@@ -126,16 +187,18 @@ __global__ __launch_bounds__(WAVES * 64) void conv_pool_kernel(SincConvArgs a) {
     const int ci0 = tid / XW, xs0 = tid - ci0 * XW;
     const int qstep = NTHR / XW, rstep = NTHR - qstep * XW;
     float pre[EPT];
+    const Tin *in_base;
+    if constexpr (I16) in_base = a.in_i16; else in_base = a.in;
 #define UVAD_SN_PREFETCH(g_)                                                               \
     {   /* 32-bit element offsets from the utterance's (wave-uniform) base: one address VGPR per load */ \
         const int b_ = (int)((g_) / a.ntiles), tile_ = (int)((g_) - (long long)b_ * a.ntiles); \
-        const float *inb_ = a.in + (size_t)b_ * a.in_bstride;                              \
+        const Tin *inb_ = in_base + (size_t)b_ * a.in_bstride;                             \
         const int x0_ = tile_ * TA * a.stride;                                             \
         int x_ = xs0;                                                                      \
         unsigned off_ = (unsigned)ci0 * (unsigned)a.Lin + (unsigned)(x0_ + xs0);           \
         _Pragma("unroll") for (int e = 0; e < EPT; ++e) {                                  \
             const bool ok_ = tid + NTHR * e < nelem && x0_ + x_ < a.Lin;                   \
-            pre[e] = inb_[ok_ ? off_ : 0u];                                                \
+            pre[e] = wav_sample(inb_[ok_ ? off_ : 0u]);                                    \
             x_ += rstep; off_ += (unsigned)qstep * (unsigned)a.Lin + (unsigned)rstep;      \
             if (x_ >= XW) { x_ -= XW; off_ += (unsigned)(a.Lin - XW); }                    \
         }                                                                                  \
@@ -363,6 +426,12 @@ hipError_t launch_wav_stats(const float *wav, int B, long long S, long long row_
     return hipGetLastError();
 }
 
+hipError_t launch_wav_stats(const int16_t *wav, int B, long long S, long long row_stride, const float *gamma, const float *beta, float eps,
+                            float *scale, float *shift, hipStream_t s) {
+    hipLaunchKernelGGL(wav_stats_i16_kernel, dim3(B), dim3(1024), 0, s, wav, S, row_stride, gamma, beta, eps, scale, shift);
+    return hipGetLastError();
+}
+
 hipError_t launch_sinc_conv(const SincConvArgs &a, hipStream_t s) {
     const int NT = (a.Cout + 31) / 32;
     if (NT != 2 && NT != 3) return hipErrorInvalidValue;
@@ -377,17 +446,21 @@ hipError_t launch_sinc_conv(const SincConvArgs &a, hipStream_t s) {
     const bool cin1 = a.Cin == 1;
     const int ept = sinc_conv_ept(a, plan.waves);
     if (ept > 48 || (cin1 && ept > 8)) return hipErrorInvalidValue;   // uvad_sincnet_configure rejects these geometries
-#define UVAD_SINC_LAUNCH(NT_, C1_, EPT_, W_)                                                                               \
+    if (a.in_i16 && !cin1) return hipErrorInvalidValue;               // int16 is the waveform: the single-channel stage only
+    const bool i16 = a.in_i16 != nullptr;
+#define UVAD_SINC_LAUNCH_T(NT_, C1_, EPT_, W_, I16_)                                                                       \
     {                                                                                                                      \
-        auto k = conv_pool_kernel<NT_, C1_, EPT_, W_>;                                                                     \
+        auto k = conv_pool_kernel<NT_, C1_, EPT_, W_, I16_>;                                                               \
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         if (e != hipSuccess) return e;                                                                                     \
         hipLaunchKernelGGL(k, grid, block, lds, s, a);                                                                     \
     }
+#define UVAD_SINC_LAUNCH(NT_, C1_, EPT_, W_) UVAD_SINC_LAUNCH_T(NT_, C1_, EPT_, W_, false)
+#define UVAD_SINC_LAUNCH1(NT_, W_) { if (i16) UVAD_SINC_LAUNCH_T(NT_, true, 8, W_, true) else UVAD_SINC_LAUNCH_T(NT_, true, 8, W_, false) }
     if (cin1 && plan.waves == 8) {
-        if (NT == 3) UVAD_SINC_LAUNCH(3, true, 8, 8) else UVAD_SINC_LAUNCH(2, true, 8, 8)
+        if (NT == 3) UVAD_SINC_LAUNCH1(3, 8) else UVAD_SINC_LAUNCH1(2, 8)
     } else if (cin1) {
-        if (NT == 3) UVAD_SINC_LAUNCH(3, true, 8, 3) else UVAD_SINC_LAUNCH(2, true, 8, 3)
+        if (NT == 3) UVAD_SINC_LAUNCH1(3, 3) else UVAD_SINC_LAUNCH1(2, 3)
     } else if (plan.waves == 4) {
         if (ept <= 32) { if (NT == 3) UVAD_SINC_LAUNCH(3, false, 32, 4) else UVAD_SINC_LAUNCH(2, false, 32, 4) }
         else { if (NT == 3) UVAD_SINC_LAUNCH(3, false, 48, 4) else UVAD_SINC_LAUNCH(2, false, 48, 4) }
@@ -396,7 +469,9 @@ hipError_t launch_sinc_conv(const SincConvArgs &a, hipStream_t s) {
     } else {
         if (NT == 3) UVAD_SINC_LAUNCH(3, false, 48, 3) else UVAD_SINC_LAUNCH(2, false, 48, 3)
     }
+#undef UVAD_SINC_LAUNCH1
 #undef UVAD_SINC_LAUNCH
+#undef UVAD_SINC_LAUNCH_T
     return hipGetLastError();
 }
 

@@ -74,8 +74,11 @@ __device__ __forceinline__ void split2(float v, _Float16 &hi, _Float16 &lo) {
     lo = (_Float16)((v - (float)hi) * 2048.0f);
 }
 
-template <int ST>
+// I16 (stage 1 only): the waveform is int16 (a.in_i16); a chunk of 8 samples is one 16-byte load, kept raw in registers until the staging
+// converts it as (float)q * 2^-15 -- exactly the f32 value of q / 32768, so the staged f16 planes are the f32 call's bits.
+template <int ST, bool I16 = false>
 __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
+    static_assert(ST == 1 || !I16, "int16 input is the waveform: stage 1 only");
     using S = Stage<ST>;
     constexpr int KS = S::KS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -133,6 +136,7 @@ __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
     constexpr int SIN_CST = Stage<ST == 1 ? 2 : ST>::IN_CST, SU = SIN_CST / 4, RPP = 256 / SU, THR = RPP * SU, SROWS = Stage<ST == 1 ? 2 : ST>::ROWS;
     constexpr int NPRE = ST == 1 ? 4 : (SROWS + RPP - 1) / RPP;
     float4 pre[NPRE];
+    int4 pre16[2];                 // I16: chunks tid and 256 + tid as raw samples
     // Stages 2 / 3: where the window of tile gi starts and how many of its rows exist; pf_load(i) fetches this thread's unit of pass i.  Every
     // load is UNCONDITIONAL (a thread past THR, a row past the window or past the utterance re-reads unit 0: stage() ignores it / stages zeros),
     // so a load is one address select and one instruction, and the loads of the NEXT tile can be issued one at a time between the k-steps of the
@@ -155,7 +159,28 @@ __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
     auto pf_slot = [](int i) { return (i * NGROUP * (KS - 1)) / NPRE; };
     auto prefetch = [&](long long gi) __attribute__((always_inline)) {
         const int b = (int)(gi / a.ntiles), tile = (int)(gi - (long long)b * a.ntiles);
-        if constexpr (ST == 1) {
+        if constexpr (ST == 1 && I16) {
+            const int16_t *src = a.in_i16 + (size_t)b * a.in_bstride;
+            const long long x0s = (long long)tile * (TILE_POS * 10);
+            const bool vec = (reinterpret_cast<uintptr_t>(src) & 15) == 0;   // (the tile origin is a multiple of 1920 samples = 3840 bytes)
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int c = tid + 256 * r;
+                const long long x = x0s + 8 * c;
+                int4 v = make_int4(0, 0, 0, 0);
+                if (c < S::WIN / 8) {
+                    if (vec && x + 8 <= a.Lin) {
+                        v = *reinterpret_cast<const int4 *>(src + x);
+                    } else {   // unaligned row or the row's end: samples past it read as 0 (int16 has no NaN; stage() zeroes them by position)
+                        int e[8];
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) e[k] = x + k < a.Lin ? (int)(unsigned short)src[x + k] : 0;
+                        v = make_int4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
+                    }
+                }
+                pre16[r] = v;
+            }
+        } else if constexpr (ST == 1) {
             const float *src = a.in + (size_t)b * a.in_bstride;
             const long long x0s = (long long)tile * (TILE_POS * 10);
             const bool vec = (reinterpret_cast<uintptr_t>(src) & 15) == 0;   // (the tile origin is a multiple of 1920 samples)
@@ -193,7 +218,19 @@ __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
             for (int r = 0; r < 2; ++r) {
                 const int c = tid + 256 * r;
                 if (c < S::WIN / 8) {
-                    const float e[8] = {pre[2 * r].x, pre[2 * r].y, pre[2 * r].z, pre[2 * r].w, pre[2 * r + 1].x, pre[2 * r + 1].y, pre[2 * r + 1].z, pre[2 * r + 1].w};
+                    float e[8];
+                    if constexpr (I16) {
+                        const int w[4] = {pre16[r].x, pre16[r].y, pre16[r].z, pre16[r].w};
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {   // little endian: sample 2k in the low half
+                            e[2 * k] = (float)(int)(int16_t)(w[k] & 0xffff) * 0x1p-15f;
+                            e[2 * k + 1] = (float)(w[k] >> 16) * 0x1p-15f;
+                        }
+                    } else {
+                        const float f[8] = {pre[2 * r].x, pre[2 * r].y, pre[2 * r].z, pre[2 * r].w, pre[2 * r + 1].x, pre[2 * r + 1].y, pre[2 * r + 1].z, pre[2 * r + 1].w};
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) e[k] = f[k];
+                    }
                     _Float16 h[8], l[8];
 #pragma unroll
                     for (int k = 0; k < 8; ++k) {
@@ -565,14 +602,16 @@ hipError_t launch_sinc_conv_f16p(int stage, const SincF16Args &a, hipStream_t s)
     if (total <= 0) return hipSuccess;
     const int ncu = a.n_cu > 0 ? a.n_cu : 256;
     const dim3 grid((unsigned)(total < ncu ? total : ncu)), block(256);
-#define UVAD_SF_LAUNCH(ST_)                                                                                                          \
+#define UVAD_SF_LAUNCH(ST_, I16_)                                                                                                    \
     {                                                                                                                                \
-        auto k = sinc_conv_f16p_kernel<ST_>;                                                                                         \
+        auto k = sinc_conv_f16p_kernel<ST_, I16_>;                                                                                   \
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, Stage<ST_>::LDS_BYTES); \
         if (e != hipSuccess) return e;                                                                                               \
         hipLaunchKernelGGL(k, grid, block, Stage<ST_>::LDS_BYTES, s, a);                                                             \
     }
-    if (stage == 0) UVAD_SF_LAUNCH(1) else if (stage == 1) UVAD_SF_LAUNCH(2) else if (stage == 2) UVAD_SF_LAUNCH(3) else return hipErrorInvalidValue;
+    if (a.in_i16 && stage != 0) return hipErrorInvalidValue;   // int16 is the waveform: stage 0 only
+    if (stage == 0 && a.in_i16) UVAD_SF_LAUNCH(1, true) else if (stage == 0) UVAD_SF_LAUNCH(1, false)
+    else if (stage == 1) UVAD_SF_LAUNCH(2, false) else if (stage == 2) UVAD_SF_LAUNCH(3, false) else return hipErrorInvalidValue;
 #undef UVAD_SF_LAUNCH
     return hipGetLastError();
 }

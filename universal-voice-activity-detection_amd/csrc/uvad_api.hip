@@ -789,7 +789,9 @@ size_t uvad_sincnet_workspace_bytes(const uvad_ctx *c, int B, int64_t S) {
     return sinc_carve(c, B, S).total;
 }
 
-static int sincnet_impl(uvad_ctx *c, const float *d_wav, int B, int64_t S, float *d_feats, void *ws, size_t ws_bytes, hipStream_t s) {
+// d_wav: f32, or int16 read as q / 32768 (is_i16): the waveform kernels (statistics, the first conv stage of either form) read it as
+// given -- no conversion pass, no f32 copy -- and everything after the first stage is the same for both sample types.
+static int sincnet_impl(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64_t S, float *d_feats, void *ws, size_t ws_bytes, hipStream_t s) {
     if (!c->has_sinc) return fail(c, UVAD_E_STATE, "uvad_sincnet: uvad_sincnet_configure has not been called");
     if (!c->finalized || !c->sinc_ready) return fail(c, UVAD_E_STATE, "uvad_sincnet: SincNet tensors not set / uvad_finalize not called");
     const SincLayout l = sinc_carve(c, B, S);
@@ -799,8 +801,10 @@ static int sincnet_impl(uvad_ctx *c, const float *d_wav, int B, int64_t S, float
     char *base = reinterpret_cast<char *>(ws);
     const uvad_sincnet_cfg &q = c->sc;
     float *s0 = reinterpret_cast<float *>(base + l.off_s0);
-    HIPCHK(c, launch_wav_stats(d_wav, B, S, S, c->sn_wav_g, c->sn_wav_b, q.eps, s0, s0 + B, s));
-    const float *in = d_wav, *in_scale = s0, *in_shift = s0 + B;
+    const int16_t *wav16 = is_i16 ? static_cast<const int16_t *>(d_wav) : nullptr;
+    if (wav16) HIPCHK(c, launch_wav_stats(wav16, B, S, S, c->sn_wav_g, c->sn_wav_b, q.eps, s0, s0 + B, s));
+    else HIPCHK(c, launch_wav_stats(static_cast<const float *>(d_wav), B, S, S, c->sn_wav_g, c->sn_wav_b, q.eps, s0, s0 + B, s));
+    const float *in = wav16 ? nullptr : static_cast<const float *>(d_wav), *in_scale = s0, *in_shift = s0 + B;
     // Split-f16 form (GEMM modes 1 / 3) when the geometry is the reference's and every stage input provably fits the f16 range: an
     // instance-normalised value is at most sqrt(L - 1) in magnitude, so |gamma| * sqrt(L) + |beta| bounds what the staging converts.
     bool f16 = l.f16 && c->sinc_f16 && (c->gemm_mode == 1 || c->gemm_mode == 3);
@@ -813,7 +817,7 @@ static int sincnet_impl(uvad_ctx *c, const float *d_wav, int B, int64_t S, float
             float *part = reinterpret_cast<float *>(base + l.off_part[i]);
             float *sc = reinterpret_cast<float *>(base + l.off_sc[i]);
             SincF16Args a{};
-            a.in = in; a.in_bstride = S; a.Lin = (int)l.Lin[i];
+            a.in = in; a.in_i16 = i == 0 ? wav16 : nullptr; a.in_bstride = S; a.Lin = (int)l.Lin[i];
             a.in_scale = in_scale; a.in_shift = in_shift; a.n_in = l.Cin[i]; a.slope = q.leaky_slope;
             a.Wfrag = c->sn_wfrag[i]; a.wscale = c->sn_wscale[i]; a.bias = c->sn_bias16[i];
             a.Lpool = (int)l.Lpool[i]; a.ntiles = l.ntiles16[i];
@@ -831,7 +835,7 @@ static int sincnet_impl(uvad_ctx *c, const float *d_wav, int B, int64_t S, float
         float *part = reinterpret_cast<float *>(base + l.off_part[i]);
         float *sc = reinterpret_cast<float *>(base + l.off_sc[i]);
         SincConvArgs a{};
-        a.in = in; a.in_bstride = (long long)l.Cin[i] * l.Lin[i]; a.Cin = l.Cin[i]; a.Lin = (int)l.Lin[i];
+        a.in = in; a.in_i16 = i == 0 ? wav16 : nullptr; a.in_bstride = (long long)l.Cin[i] * l.Lin[i]; a.Cin = l.Cin[i]; a.Lin = (int)l.Lin[i];
         a.in_scale = in_scale; a.in_shift = in_shift; a.in_lrelu = i > 0; a.slope = q.leaky_slope;
         a.Wt2 = c->sn_wt[i]; a.bias = c->sn_bias[i];
         a.Kw = l.Kw[i]; a.stride = l.stride[i]; a.Ktot = l.Cin[i] * l.Kw[i]; a.Kp = (a.Ktot + 7) / 8 * 8; a.Cout = l.Cout[i]; a.do_abs = i == 0;
@@ -846,19 +850,26 @@ static int sincnet_impl(uvad_ctx *c, const float *d_wav, int B, int64_t S, float
     return UVAD_OK;
 }
 
-int uvad_sincnet(uvad_ctx *c, const float *d_wav, int B, int64_t S, float *d_feats, void *ws, size_t ws_bytes, void *stream) {
+static int sincnet_entry(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64_t S, float *d_feats, void *ws, size_t ws_bytes, void *stream) {
     if (!c) return UVAD_E_ARG;
     if (!d_wav || !d_feats || B <= 0 || S <= 0 || !ws) return fail(c, UVAD_E_ARG, "uvad_sincnet: bad argument");
     HIPCHK(c, hipSetDevice(c->device));
-    return sincnet_impl(c, d_wav, B, S, d_feats, ws, ws_bytes, (hipStream_t)stream);
+    return sincnet_impl(c, d_wav, is_i16, B, S, d_feats, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int uvad_sincnet(uvad_ctx *c, const float *d_wav, int B, int64_t S, float *d_feats, void *ws, size_t ws_bytes, void *stream) {
+    return sincnet_entry(c, d_wav, 0, B, S, d_feats, ws, ws_bytes, stream);
+}
+int uvad_sincnet_i16(uvad_ctx *c, const int16_t *d_wav, int B, int64_t S, float *d_feats, void *ws, size_t ws_bytes, void *stream) {
+    return sincnet_entry(c, d_wav, 1, B, S, d_feats, ws, ws_bytes, stream);
 }
 
 static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float *d_logits, float *d_probs,
                          void *ws, size_t ws_bytes, hipStream_t s, bool record_start, bool check_range,
                          const StreamState *ss, int ld_out, bool feats_in_planes, const FbankArgs *fused_fb);
 
-int uvad_forward_wav(uvad_ctx *c, const float *d_wav, int B, int64_t S, float *d_logits, float *d_probs,
-                     void *ws, size_t ws_bytes, void *stream) {
+static int forward_wav_impl(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64_t S, float *d_logits, float *d_probs,
+                            void *ws, size_t ws_bytes, void *stream) {
     if (!c) return UVAD_E_ARG;
     if (!d_wav || B <= 0 || S <= 0 || !ws) return fail(c, UVAD_E_ARG, "uvad_forward_wav: bad argument");
     if (!c->has_sinc) return fail(c, UVAD_E_STATE, "uvad_forward_wav: uvad_sincnet_configure has not been called");
@@ -873,9 +884,18 @@ int uvad_forward_wav(uvad_ctx *c, const float *d_wav, int B, int64_t S, float *d
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(c, hipSetDevice(c->device));
     if (c->timing) HIPCHK(c, hipEventRecord(c->ev[0], s));
-    int r = sincnet_impl(c, d_wav, B, S, feats, base + w.total, ws_bytes - w.total, s);
+    int r = sincnet_impl(c, d_wav, is_i16, B, S, feats, base + w.total, ws_bytes - w.total, s);
     if (r) return r;
     return classify_impl(c, feats, B, (int)T, d_logits, d_probs, ws, w.total, s, false, true, nullptr, 0, false, nullptr);
+}
+
+int uvad_forward_wav(uvad_ctx *c, const float *d_wav, int B, int64_t S, float *d_logits, float *d_probs,
+                     void *ws, size_t ws_bytes, void *stream) {
+    return forward_wav_impl(c, d_wav, 0, B, S, d_logits, d_probs, ws, ws_bytes, stream);
+}
+int uvad_forward_wav_i16(uvad_ctx *c, const int16_t *d_wav, int B, int64_t S, float *d_logits, float *d_probs,
+                         void *ws, size_t ws_bytes, void *stream) {
+    return forward_wav_impl(c, d_wav, 1, B, S, d_logits, d_probs, ws, ws_bytes, stream);
 }
 
 int64_t uvad_num_frames(const uvad_ctx *c, int64_t S) {

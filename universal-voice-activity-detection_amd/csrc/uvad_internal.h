@@ -241,6 +241,7 @@ void pack_fc_image(const float *w /*[128][128], torch nn.Linear.weight*/, float 
 // ---- sincnet.hip: SincNet front end of PyanNet (conv + |.| + maxpool(3) + instance-norm statistics) ----------
 struct SincConvArgs {
     const float *in; long long in_bstride; int Cin, Lin;   // in[b*in_bstride + ci*Lin + x]
+    const int16_t *in_i16;                                 // single-channel stage only: the waveform as int16 (read as q / 32768), else null
     const float *in_scale, *in_shift;                      // [B][Cin]: x*scale + shift applied while staging (previous norm)
     int in_lrelu; float slope;                             // then leaky_relu (layers after the first)
     const float *Wt2;                                      // [Kp][NW]: W^T, zero padded (NW = 32*ceil(Cout/32))
@@ -254,6 +255,8 @@ struct SincConvArgs {
 };
 hipError_t launch_wav_stats(const float *wav, int B, long long S, long long row_stride, const float *gamma, const float *beta, float eps,
                             float *scale, float *shift, hipStream_t s);
+hipError_t launch_wav_stats(const int16_t *wav, int B, long long S, long long row_stride, const float *gamma, const float *beta, float eps,
+                            float *scale, float *shift, hipStream_t s);   // int16 samples read as q / 32768
 struct SincConvPlan { int waves, pt, phases; };            // waves per workgroup, pooled outputs per tile, statistics groups per tile
 SincConvPlan sinc_conv_plan(const SincConvArgs &a);        // needs Cin, Cout, Kw, stride, Kp
 hipError_t launch_sinc_conv(const SincConvArgs &a, hipStream_t s);
@@ -267,6 +270,7 @@ hipError_t launch_sinc_out(const float *P, const float *scale, const float *shif
 // ---- sincnet_f16p.hip: the same three stages on the f16 matrix cores (f32-equivalent split arithmetic), channel-minor intermediates ----
 struct SincF16Args {
     const float *in; long long in_bstride; int Lin;        // stage 0: in[b * in_bstride + x] (the waveform); stages 1, 2: in[(b * Lin + x) * cst_in + c]
+    const int16_t *in_i16;                                 // stage 0 only: the waveform as int16 (read as q / 32768; `in` unused), else null
     const float *in_scale, *in_shift; int n_in;            // [B][n_in]: x * scale + shift applied while staging (n_in = 1, or the real channel count)
     float slope;                                           // leaky_relu of the previous stage (stages 1, 2)
     const unsigned short *Wfrag; float wscale;             // sinc_f16p_pack_weights

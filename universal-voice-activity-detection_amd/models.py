@@ -168,12 +168,14 @@ class PyanNet(PyanNet2):
 
     @torch.no_grad()
     def forward(self, waveforms: torch.Tensor) -> torch.Tensor:
-        """(batch, channel, samples) -> (batch, frames, 1) speech probabilities."""
+        """(batch, channel, samples) -> (batch, frames, 1) speech probabilities.  f32 samples, or int16 as read from a wav file (read as
+        q / 32768 by uvad_forward_wav_i16, no conversion on the host)."""
         _, probs = self.forward_logits(waveforms, want_logits=False)
         return probs.unsqueeze(-1)
 
     @torch.no_grad()
     def forward_logits(self, waveforms: torch.Tensor, want_logits=True):
+        """(batch, [channel = 1,] samples) f32 or int16 -> (logits, probs), both (batch, frames); int16 is passed through unconverted."""
         self._require_gpu(waveforms, "waveforms")
         if waveforms.dim() == 3:
             assert waveforms.shape[1] == 1, f"Only single channel is supported. You have {waveforms.shape[1]}"

@@ -1,4 +1,4 @@
-"""ForwardPipeline: keep several uvad_forward calls in flight.
+"""ForwardPipeline: keep several uvad_forward (PyanNet2 with a FbankConfig) or uvad_forward_wav (PyanNet) calls in flight.
 
 Why: the recurrence of one batch is a serial chain of 4 x T steps that cannot use the chip -- at B = 256 its latency form
 occupies 128 of the 256 CUs for 5.3 ms, its throughput form (recurrent_tile=16) 32 CUs for 7.4 ms.  Independent batches
@@ -16,6 +16,7 @@ from typing import List, Optional
 
 import torch
 
+from .models import PyanNet
 from .runtime import VadRuntime
 
 
@@ -45,15 +46,20 @@ class ForwardPipeline:
     MAX_STREAM_TRIES = 48
 
     def __init__(self, model, device, depth: int = 2, recurrent_tile: int = 0):
-        """model: a built uvad_amd.PyanNet2 with attach_fbank(...) done (weights are copied into every slot).
+        """model: a built uvad_amd.PyanNet2 with attach_fbank(...) done, or a built uvad_amd.PyanNet (SincNet front end: the slots
+        run uvad_forward_wav[_i16] on raw waveforms); weights are copied into every slot.
         recurrent_tile: 0 = the library's per-call choice (fastest single call), 16 = the throughput form of the recurrence
         (16 sequences per workgroup: ~3.5x fewer CU-cycles per sequence than the latency form, so more of the chip is free
         for the other slots' kernels; a single call gets slower), 4 = the latency form."""
-        if getattr(model, "_fbank_cfg", None) is None:
+        self.wav = isinstance(model, PyanNet)
+        if not self.wav and getattr(model, "_fbank_cfg", None) is None:
             raise RuntimeError("attach_fbank(FbankConfig(...)) first: the pipeline runs the fused PCM -> logits path")
         self.device = torch.device(device)
         self.depth = max(1, int(depth))
         cfg = {"encoding_dim": model.encoding_dim, "lstm": model.hparams.lstm, "linear": model.hparams.linear}
+        # PyanNet: the SincNet stage in every slot, loaded with the materialised filter bank (PyanNet._flat_state_dict)
+        extra = {"sincnet": model.sincnet.config()} if self.wav else {"fbank": model._fbank_cfg}
+        sd = model._flat_state_dict() if self.wav else model.state_dict()
         self.runtimes: List[VadRuntime] = []
         self.streams: Optional[List[torch.cuda.Stream]] = None
         self.streams_tried = 0
@@ -61,9 +67,9 @@ class ForwardPipeline:
         self._active = self.depth
         try:   # every slot holds a weights copy and (later) a workspace: a failure while building slot k must not leave 0..k-1 behind
             for _ in range(self.depth):
-                r = VadRuntime(device=self.device, fbank=model._fbank_cfg, model=cfg)
+                r = VadRuntime(device=self.device, model=cfg, **extra)
                 self.runtimes.append(r)
-                r.load_state_dict(model.state_dict())
+                r.load_state_dict(sd)
                 if recurrent_tile:
                     r.set_recurrent_tile(recurrent_tile)
                 if self.depth > 1:
@@ -97,7 +103,8 @@ class ForwardPipeline:
 
     # ------------------------------------------------------------------ use
     def submit(self, pcm: torch.Tensor, want_logits: bool = True, want_probs: bool = False, timed: bool = False) -> Pending:
-        """pcm (B, S) f32 on the device, ready on the CURRENT stream.  Returns at once; the step runs on the next slot's stream.
+        """pcm (B, S) f32, or int16 read as q / 32768, on the device, ready on the CURRENT stream.  Returns at once; the step runs on the
+        next slot's stream (VadRuntime.forward, or forward_wav for a PyanNet).
         timed: bracket the step with timing events on its own stream (Pending.elapsed_ms)."""
         i = self._k % self._active
         self._k += 1
@@ -108,7 +115,8 @@ class ForwardPipeline:
             if timed:
                 start = torch.cuda.Event(enable_timing=True)
                 start.record(s)
-            logits, probs = self.runtimes[i].forward(pcm, want_logits=want_logits, want_probs=want_probs)
+            run = self.runtimes[i].forward_wav if self.wav else self.runtimes[i].forward
+            logits, probs = run(pcm, want_logits=want_logits, want_probs=want_probs)
             ev = torch.cuda.Event(enable_timing=timed)
             ev.record(s)
         pcm.record_stream(s)

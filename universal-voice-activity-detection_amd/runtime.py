@@ -181,27 +181,38 @@ class VadRuntime:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
 
+    def _dev_wav(self, wav: "torch.Tensor"):
+        """(contiguous wav on the device, True if int16): int16 goes to the _i16 entries unconverted, anything else as f32."""
+        if torch.is_tensor(wav) and wav.dtype == torch.int16:
+            if wav.device != self.device:
+                raise RuntimeError(f"wav must be a tensor on {self.device} (got {wav.device})")
+            return wav.contiguous(), True
+        return self._dev_f32(wav, "wav"), False
+
     def sincnet(self, wav: "torch.Tensor") -> "torch.Tensor":
-        """wav (B,S) f32 on the GPU -> SincNet features (B, frames, c3)."""
+        """wav (B,S) f32, or int16 as read from a wav file (samples read as q / 32768, the same signal as uvad_fbank_i16 / forward()
+        take: the f32 call on q.float() / 32768 gives the same bits), on the GPU -> SincNet features (B, frames, c3)."""
         if self._sn_c is None:
             raise RuntimeError("this runtime was created without a SincNet configuration")
         with torch.cuda.device(self.device):
-            wav = self._dev_f32(wav, "wav")
+            wav, i16 = self._dev_wav(wav)
             B, S = wav.shape
             T = self.sincnet_num_frames(S)
             if T <= 0:
                 raise ValueError(f"{S} samples are too short for one SincNet frame")
             ws = self._wav_ws(B, S, T, False)
             feats = torch.empty((B, T, self._sn_c.c3), dtype=torch.float32, device=self.device)
-            self._check(self.lib.uvad_sincnet(self.ctx, wav.data_ptr(), B, S, feats.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+            fn = self.lib.uvad_sincnet_i16 if i16 else self.lib.uvad_sincnet
+            self._check(fn(self.ctx, wav.data_ptr(), B, S, feats.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
             return feats
 
     def forward_wav(self, wav: "torch.Tensor", want_logits=True, want_probs=True):
-        """wav (B,S) f32 on the GPU -> (logits, probs) of PyanNet (SincNet -> LSTM stack -> head)."""
+        """wav (B,S) f32, or int16 read as q / 32768 (as in sincnet()), on the GPU -> (logits, probs) of PyanNet (SincNet -> LSTM stack ->
+        head); int16 runs uvad_forward_wav_i16."""
         if self._sn_c is None:
             raise RuntimeError("this runtime was created without a SincNet configuration")
         with torch.cuda.device(self.device):
-            wav = self._dev_f32(wav, "wav")
+            wav, i16 = self._dev_wav(wav)
             B, S = wav.shape
             T = self.sincnet_num_frames(S)
             if T <= 0:
@@ -209,10 +220,11 @@ class VadRuntime:
             ws = self._wav_ws(B, S, T, True)
             logits = torch.empty((B, T), dtype=torch.float32, device=self.device) if want_logits else None
             probs = torch.empty((B, T), dtype=torch.float32, device=self.device) if want_probs else None
-            self._check(self.lib.uvad_forward_wav(self.ctx, wav.data_ptr(), B, S,
-                                                  logits.data_ptr() if want_logits else None,
-                                                  probs.data_ptr() if want_probs else None,
-                                                  ws.data_ptr(), ws.numel(), self._stream()))
+            fn = self.lib.uvad_forward_wav_i16 if i16 else self.lib.uvad_forward_wav
+            self._check(fn(self.ctx, wav.data_ptr(), B, S,
+                           logits.data_ptr() if want_logits else None,
+                           probs.data_ptr() if want_probs else None,
+                           ws.data_ptr(), ws.numel(), self._stream()))
             self._last_bt = (B, T)
             return logits, probs
 

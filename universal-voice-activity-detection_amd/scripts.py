@@ -17,8 +17,8 @@ Cut geometry (``window_seconds``, default = the reference's 5.0):
   window -- an explicit option, not the default).
 
 Every batch goes through the fused hot path: PCM (int16 straight from the wav file, or f32) ->
-``uvad_forward[_i16]`` (features stay in the workspace) -> ``uvad_median_filter`` -> ``uvad_label_runs``;
-several batches are kept in flight with ``ForwardPipeline`` when there is more than one."""
+``uvad_forward[_i16]`` (features stay in the workspace; SincNet: ``uvad_forward_wav[_i16]``) -> ``uvad_median_filter`` ->
+``uvad_label_runs``; several batches are kept in flight with ``ForwardPipeline`` when there is more than one."""
 import json
 import math
 import os
@@ -150,7 +150,7 @@ def predict_vad(**kwargs):
 
     rt = net.runtime(device)
     pipe = None
-    if not sincnet and len(batches) > 1:   # kept tails (n < W) take the unfused branch below
+    if len(batches) > 1:   # log-mel: kept tails (n < W) take the unfused branch below; SincNet: every batch, tails padded first
         pipe = open_pipeline(net, device, min(3, len(batches)))
 
     def stack(group):
@@ -162,11 +162,15 @@ def predict_vad(**kwargs):
     for group in batches:
         n = pieces[group[0]][2]
         x = stack(group)
-        if sincnet:   # (batch, samples); the model consumes raw audio, channel axis added as in vad_engine.py:252-255
-            xf = x.float() / 32768.0 if x.dtype == torch.int16 else x
+        if sincnet:   # (batch, samples), int16 from a wav file as it is (uvad_forward_wav_i16 reads q / 32768); the model consumes raw audio
             if W is not None and n < W:   # a kept tail: the recipe pads the AUDIO cut to the window (.pad(duration=5.0)), so every cut gives 293 frames
-                xf = torch.nn.functional.pad(xf, (0, W - n))
-            probs = model(xf.unsqueeze(1)).squeeze(-1)
+                xp = x.new_zeros((x.shape[0], W))   # (zero samples in either type)
+                xp[:, :n] = x
+                x = xp
+            if pipe is not None:
+                pending.append((group, pipe.submit(x, want_logits=False, want_probs=True)))
+                continue
+            probs = model(x.unsqueeze(1)).squeeze(-1)   # channel axis added as in vad_engine.py:252-255
         elif W is not None and n < W:
             # a kept tail (3 s < length < 5 s): features of the samples that exist, then lhotse's padding frames up to the
             # window's frame count, then the classifier (the reference pads FEATURES, not audio)
