@@ -72,7 +72,7 @@ typedef struct {
     int bidirectional; /* lstm.bidirectional: 1 */
     int lin_hidden;    /* linear.hidden_size: 128 */
     int lin_layers;    /* linear.num_layers: 2 */
-    float leaky_slope; /* F.leaky_relu default 0.01 (PyanNet2.py:185) */
+    float leaky_slope; /* F.leaky_relu default 0.01 (PyanNet2.py:185); any finite value (NaN / inf: UVAD_E_ARG from uvad_create) */
 } uvad_model_cfg;
 
 /* ABI version of the loaded library (== UVAD_ABI_VERSION of the header it was built from). */
@@ -195,8 +195,8 @@ typedef struct {
     int kernel_size;   /* 251 */
     int c2, k2;        /* Conv1d(80, 60, 5) */
     int c3, k3;        /* Conv1d(60, 60, 5); c3 must equal the classifier's encoding_dim */
-    float leaky_slope; /* F.leaky_relu default 0.01 */
-    float eps;         /* InstanceNorm1d eps 1e-5 */
+    float leaky_slope; /* F.leaky_relu default 0.01; any finite value (NaN / inf: UVAD_E_ARG).  A slope > 1 runs the exact-f32 stages */
+    float eps;         /* InstanceNorm1d eps 1e-5 of all four norms; finite and >= 0 (else UVAD_E_ARG) */
 } uvad_sincnet_cfg;
 
 /* Replaces: SincNet.__init__ (sincnet.py:33-70).  Adds the stage to a context created with a model
@@ -258,10 +258,10 @@ int uvad_forward_wav_i16(uvad_ctx *, const int16_t *d_wav, int B, int64_t S, flo
  *      differ in the last bits.
  * The SincNet front end (uvad_sincnet, uvad_forward_wav) follows the same selector: modes 1 and 3 run its three convolution stages on
  * the f16 matrix cores with the split arithmetic of mode 1 (exact three-plane weights in registers, sincnet_f16p.hip) when the geometry
- * is the reference's (sinc bank of 80 filters x <= 256 taps at stride 10; Conv1d(80 -> <= 64, 5); Conv1d(<= 64 -> <= 64, 5)) and every
- * stage input provably fits the f16 range (|gamma| * sqrt(length) + |beta| < 60000 for the instance norm in front of it); modes 0 and 2,
- * other geometries and inputs outside that bound run the exact-f32 stages (v_mfma_f32_32x32x2_f32, sincnet.hip).  uvad_get_sincnet_form
- * tells which.
+ * is the reference's (sinc bank of 80 filters x <= 256 taps at stride 10; Conv1d(80 -> <= 64, 5); Conv1d(<= 64 -> <= 64, 5)), the leaky
+ * slope is <= 1 and every stage input provably fits the f16 range ((|gamma| * sqrt(length) + |beta|) x max(1, |slope|) < 60000 for the
+ * instance norm and leaky_relu in front of it); modes 0 and 2, other geometries, slopes and inputs outside that bound run the exact-f32
+ * stages (v_mfma_f32_32x32x2_f32, sincnet.hip).  uvad_get_sincnet_form tells which.
  * All are held to the same 1e-4 logit bound by the tests.  Replaces nothing in the reference (torch picks its GEMM). */
 int uvad_set_gemm_mode(uvad_ctx *, int mode);
 /* What the most recent uvad_sincnet / uvad_forward_wav call of this context ran: 1 = the split-f16 stages, 0 = the exact-f32 stages

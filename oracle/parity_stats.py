@@ -29,22 +29,23 @@ def truth_logits(state_dict, feats, encoding_dim, hidden=128, num_layers=4, bidi
 
 @torch.no_grad()
 def truth_sincnet(front, wav, chunk=32):
-    """front: a torch_ref.TorchSincNet (f32 parameters); wav (B, S) f32.  Returns (B, frames, 60) float64 tensor: every
-    operator of TorchSincNet.forward on double tensors (conv1d / max_pool1d / instance_norm / leaky_relu in float64)."""
+    """front: a torch_ref.TorchSincNet (f32 parameters, any geometry / leaky slope / eps); wav (B, S) f32.  Returns (B, frames, c3)
+    float64 tensor: every operator of TorchSincNet.forward on double tensors (conv1d / max_pool1d / instance_norm / leaky_relu in float64)."""
     import torch.nn.functional as F
-    filt = tr.sinc_filters(front.low_hz_, front.band_hz_).double().unsqueeze(1)        # the f32 filter bank, cast
+    filt = front.filters().double().unsqueeze(1)                                       # the f32 filter bank, cast
     p = {k: v.detach().double() for k, v in front.state_dict().items()}
+    slope, eps = front.leaky_slope, front.eps
     out = []
     wav = torch.as_tensor(wav)
     for i in range(0, wav.shape[0], chunk):
         x = wav[i:i + chunk].double().unsqueeze(1)
-        x = F.instance_norm(x, weight=p["wav_norm1d.weight"], bias=p["wav_norm1d.bias"], eps=front.wav_norm1d.eps)
+        x = F.instance_norm(x, weight=p["wav_norm1d.weight"], bias=p["wav_norm1d.bias"], eps=eps)
         x = torch.abs(F.conv1d(x, filt, stride=front.stride))
-        x = F.leaky_relu(F.instance_norm(F.max_pool1d(x, 3, 3), weight=p["norm1d.0.weight"], bias=p["norm1d.0.bias"], eps=front.norm1d[0].eps))
+        x = F.leaky_relu(F.instance_norm(F.max_pool1d(x, 3, 3), weight=p["norm1d.0.weight"], bias=p["norm1d.0.bias"], eps=eps), slope)
         for j in range(2):
             x = F.conv1d(x, p[f"conv1d.{j}.weight"], p[f"conv1d.{j}.bias"])
             x = F.leaky_relu(F.instance_norm(F.max_pool1d(x, 3, 3), weight=p[f"norm1d.{j + 1}.weight"], bias=p[f"norm1d.{j + 1}.bias"],
-                                             eps=front.norm1d[j + 1].eps))
+                                             eps=eps), slope)
         out.append(x.transpose(1, 2).contiguous())
     return torch.cat(out)
 

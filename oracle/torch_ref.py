@@ -192,36 +192,65 @@ def sincnet_num_frames(S, stride=10):
 
 
 class TorchSincNet(nn.Module):
-    """sincnet.py:33-103 on stock torch modules; the sinc layer is a conv1d with the materialised filter bank."""
+    """sincnet.py:33-103 on stock torch modules; the sinc layer is a conv1d with the materialised filter bank.
 
-    def __init__(self, stride=10):
+    The defaults are the reference's geometry (stride 10, 80 x 251 sinc bank, Conv1d(80, 60, 5), Conv1d(60, 60, 5), leaky slope 0.01,
+    eps 1e-5); the other arguments span what uvad_sincnet_configure accepts.  An odd kernel_size materialises the sinc bank from the
+    learnable band edges (low_hz_, band_hz_); an even one (which ParamSincFB cannot build) carries the bank itself as ``filters_``."""
+
+    def __init__(self, stride=10, n_filters=80, kernel_size=251, c2=60, k2=5, c3=60, k3=5, leaky_slope=0.01, eps=1e-5):
         super().__init__()
-        self.stride = stride
-        self.wav_norm1d = nn.InstanceNorm1d(1, affine=True)
-        low, band = sinc_init_params()
-        self.low_hz_ = nn.Parameter(low)
-        self.band_hz_ = nn.Parameter(band)
-        self.norm1d = nn.ModuleList([nn.InstanceNorm1d(80, affine=True), nn.InstanceNorm1d(60, affine=True), nn.InstanceNorm1d(60, affine=True)])
-        self.conv1d = nn.ModuleList([nn.Conv1d(80, 60, 5), nn.Conv1d(60, 60, 5)])   # conv1d.1 / conv1d.2 of the reference
+        self.stride, self.n_filters, self.kernel_size = stride, n_filters, kernel_size
+        self.c2, self.k2, self.c3, self.k3 = c2, k2, c3, k3
+        self.leaky_slope, self.eps = leaky_slope, eps
+        self.wav_norm1d = nn.InstanceNorm1d(1, affine=True, eps=eps)
+        if kernel_size % 2:
+            low, band = sinc_init_params(n_filters)
+            self.low_hz_ = nn.Parameter(low)
+            self.band_hz_ = nn.Parameter(band)
+        else:
+            self.filters_ = nn.Parameter(torch.zeros(n_filters, kernel_size))
+        self.norm1d = nn.ModuleList([nn.InstanceNorm1d(c, affine=True, eps=eps) for c in (n_filters, c2, c3)])
+        self.conv1d = nn.ModuleList([nn.Conv1d(n_filters, c2, k2), nn.Conv1d(c2, c3, k3)])   # conv1d.1 / conv1d.2 of the reference
+
+    def config(self):
+        """The uvad_sincnet_cfg of this front end (VadRuntime's ``sincnet=`` argument)."""
+        return {"stride": self.stride, "n_filters": self.n_filters, "kernel_size": self.kernel_size, "c2": self.c2, "k2": self.k2,
+                "c3": self.c3, "k3": self.k3, "leaky_slope": self.leaky_slope, "eps": self.eps}
+
+    def filters(self):
+        """(n_filters, kernel_size) f32: the bank the first stage convolves with."""
+        if self.kernel_size % 2:
+            return sinc_filters(self.low_hz_, self.band_hz_, self.kernel_size)
+        return self.filters_.detach().float()
+
+    def num_frames(self, S):
+        n = S
+        for kw, st in ((self.kernel_size, self.stride), (self.k2, 1), (self.k3, 1)):
+            n = ((n - kw) // st + 1 if n >= kw else 0) // 3
+        return n
 
     @torch.no_grad()
-    def forward(self, wav):   # (B, 1, S) -> (B, 60, frames)
+    def forward(self, wav):   # (B, 1, S) -> (B, c3, frames)
         x = self.wav_norm1d(wav)
-        x = F.conv1d(x, sinc_filters(self.low_hz_, self.band_hz_).unsqueeze(1), stride=self.stride)
+        x = F.conv1d(x, self.filters().unsqueeze(1), stride=self.stride)
         x = torch.abs(x)
-        x = F.leaky_relu(self.norm1d[0](F.max_pool1d(x, 3, 3)))
-        x = F.leaky_relu(self.norm1d[1](F.max_pool1d(self.conv1d[0](x), 3, 3)))
-        x = F.leaky_relu(self.norm1d[2](F.max_pool1d(self.conv1d[1](x), 3, 3)))
+        x = F.leaky_relu(self.norm1d[0](F.max_pool1d(x, 3, 3)), self.leaky_slope)
+        x = F.leaky_relu(self.norm1d[1](F.max_pool1d(self.conv1d[0](x), 3, 3)), self.leaky_slope)
+        x = F.leaky_relu(self.norm1d[2](F.max_pool1d(self.conv1d[1](x), 3, 3)), self.leaky_slope)
         return x
 
 
-def seeded_sincnet(seed=99):
+def seeded_sincnet(seed=99, **cfg):
+    """A TorchSincNet(**cfg) with seeded parameters (defaults: the reference geometry, the draws of every earlier release)."""
     g = torch.Generator().manual_seed(seed)
-    m = TorchSincNet()
+    m = TorchSincNet(**cfg)
     with torch.no_grad():
         for name, p in m.named_parameters():
             if name in ("low_hz_", "band_hz_"):
                 p.mul_(1.0 + 0.05 * (torch.rand(p.shape, generator=g) - 0.5))       # perturb the mel initialisation
+            elif name == "filters_":
+                p.copy_((torch.rand(p.shape, generator=g) * 2 - 1) / math.sqrt(p.shape[1]))
             elif "norm" in name and name.endswith("weight"):
                 p.copy_(1.0 + 0.2 * (torch.rand(p.shape, generator=g) - 0.5))
             elif "norm" in name:
@@ -229,3 +258,23 @@ def seeded_sincnet(seed=99):
             else:
                 p.copy_((torch.rand(p.shape, generator=g) * 2 - 1) / math.sqrt(p.shape[1] * p.shape[2] if p.dim() == 3 else 300.0))
     return m.eval()
+
+
+def sincnet_runtime_state_dict(front, classifier_sd=None, seed=None, scale=2.0, **classifier):
+    """The tensors VadRuntime.load_state_dict takes for a PyanNet with this front end: the materialised bank as
+    ``sincnet.conv1d.0.filters``, the norms and convs under their reference names (conv1d.{1,2}), plus the classifier's --
+    ``classifier_sd`` as given, or seeded_state_dict(front.c3, seed=seed, scale=scale, **classifier) when a seed is given."""
+    fsd = front.state_dict()
+    if classifier_sd is None and seed is not None:
+        classifier_sd = seeded_state_dict(front.c3, seed=seed, scale=scale, **classifier)
+    sd = dict(classifier_sd or {})
+    sd["sincnet.conv1d.0.filters"] = front.filters().detach().clone()
+    for k in ("wav_norm1d.weight", "wav_norm1d.bias"):
+        sd["sincnet." + k] = fsd[k]
+    for i in range(3):
+        for p in ("weight", "bias"):
+            sd[f"sincnet.norm1d.{i}.{p}"] = fsd[f"norm1d.{i}.{p}"]
+    for i in range(2):
+        for p in ("weight", "bias"):
+            sd[f"sincnet.conv1d.{i + 1}.{p}"] = fsd[f"conv1d.{i}.{p}"]
+    return sd

@@ -192,3 +192,63 @@ def test_c_oracle_handles_wide_feed_forward_and_input():
         ref = tr.TorchPyanNet2(F, H, L, bi, lin_h, lin_l)
         ref.load_state_dict(sd)
         assert np.abs(ref(feats)[0].numpy() - want).max() < 1e-5
+
+
+def test_parametric_sincnet_truth_keeps_the_reference_point_and_matches_a_stock_f32_stack():
+    """oracle.parity_stats.truth_sincnet reads geometry, leaky slope and eps from the TorchSincNet it is given.  At the default
+    arguments it is bit for bit the reference-point evaluation (restated here as it was written for that point only); at two
+    other geometries -- an even (seeded, not sinc) filter bank, and c3 != 60 with other taps / stride / slope / eps -- it agrees
+    with an independent f32 stack of stock nn.Conv1d / nn.MaxPool1d / nn.InstanceNorm1d / F.leaky_relu modules."""
+    import torch.nn as nn
+    import torch.nn.functional as F
+    from oracle import parity_stats as ps
+
+    def reference_point_truth(front, wav):
+        filt = tr.sinc_filters(front.low_hz_, front.band_hz_).double().unsqueeze(1)
+        p = {k: v.detach().double() for k, v in front.state_dict().items()}
+        x = wav.double().unsqueeze(1)
+        x = F.instance_norm(x, weight=p["wav_norm1d.weight"], bias=p["wav_norm1d.bias"], eps=1e-5)
+        x = torch.abs(F.conv1d(x, filt, stride=10))
+        x = F.leaky_relu(F.instance_norm(F.max_pool1d(x, 3, 3), weight=p["norm1d.0.weight"], bias=p["norm1d.0.bias"], eps=1e-5))
+        for j in range(2):
+            x = F.conv1d(x, p[f"conv1d.{j}.weight"], p[f"conv1d.{j}.bias"])
+            x = F.leaky_relu(F.instance_norm(F.max_pool1d(x, 3, 3), weight=p[f"norm1d.{j + 1}.weight"], bias=p[f"norm1d.{j + 1}.bias"], eps=1e-5))
+        return x.transpose(1, 2).contiguous()
+
+    wav = torch.from_numpy(tr.synth_pcm(3, 9001, seed=17))
+    front = tr.seeded_sincnet(99)
+    assert front.config() == {"stride": 10, "n_filters": 80, "kernel_size": 251, "c2": 60, "k2": 5, "c3": 60, "k3": 5,
+                              "leaky_slope": 0.01, "eps": 1e-5}
+    got = ps.truth_sincnet(front, wav)
+    assert got.dtype == torch.float64 and got.shape == (3, tr.sincnet_num_frames(9001), 60) == (3, front.num_frames(9001), 60)
+    assert torch.equal(got, reference_point_truth(front, wav))
+
+    for cfg in (dict(stride=3, n_filters=64, kernel_size=128, c2=48, k2=4, c3=44, k3=7, leaky_slope=-0.2, eps=1e-3),
+                dict(stride=1, n_filters=34, kernel_size=33, c2=96, k2=3, c3=68, k3=9, leaky_slope=2.5, eps=1.0)):
+        front = tr.seeded_sincnet(7, **cfg)
+        assert front.config() == cfg
+        sd = tr.sincnet_runtime_state_dict(front, seed=3)
+        assert sd["sincnet.conv1d.0.filters"].shape == (cfg["n_filters"], cfg["kernel_size"])
+        assert sd["sincnet.conv1d.2.weight"].shape == (cfg["c3"], cfg["c2"], cfg["k3"]) and sd["lstm.weight_ih_l0"].shape[1] == cfg["c3"]
+        truth = ps.truth_sincnet(front, wav)
+        # the independent f32 stack: stock modules, weights copied in
+        conv0 = nn.Conv1d(1, cfg["n_filters"], cfg["kernel_size"], stride=cfg["stride"], bias=False)
+        conv0.weight.data.copy_(front.filters().unsqueeze(1))
+        convs = [nn.Conv1d(front.n_filters, cfg["c2"], cfg["k2"]), nn.Conv1d(cfg["c2"], cfg["c3"], cfg["k3"])]
+        for c, src in zip(convs, front.conv1d):
+            c.load_state_dict(src.state_dict())
+        norms = [nn.InstanceNorm1d(n, affine=True, eps=cfg["eps"]) for n in (1, cfg["n_filters"], cfg["c2"], cfg["c3"])]
+        norms[0].load_state_dict(front.wav_norm1d.state_dict())
+        for n, src in zip(norms[1:], front.norm1d):
+            n.load_state_dict(src.state_dict())
+        pool = nn.MaxPool1d(3, stride=3)
+        with torch.no_grad():
+            x = torch.abs(conv0(norms[0](wav.unsqueeze(1))))
+            x = F.leaky_relu(norms[1](pool(x)), cfg["leaky_slope"])
+            x = F.leaky_relu(norms[2](pool(convs[0](x))), cfg["leaky_slope"])
+            x = F.leaky_relu(norms[3](pool(convs[1](x))), cfg["leaky_slope"])
+        want = x.transpose(1, 2)
+        assert truth.shape == want.shape == (3, front.num_frames(9001), cfg["c3"]) and truth.shape[1] >= 8
+        err = float((truth - want.double()).abs().max())
+        print(f"{cfg}: float64 truth vs stock f32 stack {err:.2e}")
+        assert err < 1e-5

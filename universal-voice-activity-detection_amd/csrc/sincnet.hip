@@ -437,7 +437,9 @@ hipError_t launch_sinc_conv(const SincConvArgs &a, hipStream_t s) {
     if (NT != 2 && NT != 3) return hipErrorInvalidValue;
     const SincConvPlan plan = sinc_conv_plan(a);
     if (a.ntiles != (a.Lpool + plan.pt - 1) / plan.pt) return hipErrorInvalidValue;   // the caller sized the partials with the same plan
-    const size_t lds = sinc_conv_lds_bytes(a, NT, plan.waves);
+    // the dynamic part only: sinc_conv_lds_bytes counts the static (scale, shift) table too, and the kernel's total (dynamic + static) is
+    // what must fit the 160 KiB (requesting the whole figure as dynamic LDS failed the launch of stages within 768 bytes of the limit)
+    const size_t lds = sinc_conv_lds_bytes(a, NT, plan.waves) - 96 * sizeof(float2);
     // persistent workgroups, one per CU (the LDS-resident filter matrix allows no more), each walking a contiguous
     // range of the (utterance, tile) pairs
     const long long total = (long long)a.B * a.ntiles;

@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
                     _Float16 h[4], l[4];
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const float t = __builtin_fmaxf(e[k], e[k] * a.slope);   // leaky_relu of the previous stage (0 <= slope < 1; NaN stays NaN)
+                        const float t = __builtin_fmaxf(e[k], e[k] * a.slope);   // leaky_relu of the previous stage for any slope <= 1 (sincnet_impl gates larger ones off; NaN stays NaN)
                         split2(t, h[k], l[k]);
                     }
                     uint2 ph, pl;

@@ -150,6 +150,7 @@ int fail(uvad_ctx *c, int code, const std::string &msg) {
     return code;
 }
 int hip_fail(uvad_ctx *c, hipError_t e, const char *what) {
+    (void)hipGetLastError();   // reported here: a failed launch or attribute call must not resurface in the next call's hipGetLastError
     return fail(c, UVAD_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 #define HIPCHK(c, call)                                        \
@@ -330,6 +331,7 @@ int uvad_create(int device, const uvad_fbank_cfg *fb, const uvad_model_cfg *mode
             return fail(c, UVAD_E_UNSUPPORTED, "encoding_dim must be a positive multiple of 4");
         if (model->num_layers < 1 || model->lin_layers < 0 || (model->lin_layers > 0 && (model->lin_hidden < 4 || model->lin_hidden % 4)))
             return fail(c, UVAD_E_ARG, "bad model configuration");
+        if (!std::isfinite(model->leaky_slope)) return fail(c, UVAD_E_ARG, "model leaky_slope must be finite");
     }
     for (auto &ev : c->ev) HIPCHK(c, hipEventCreate(&ev));
     return UVAD_OK;
@@ -755,6 +757,9 @@ int uvad_sincnet_configure(uvad_ctx *c, const uvad_sincnet_cfg *q) {
     if (!c->has_model) return fail(c, UVAD_E_STATE, "uvad_sincnet_configure: context was created without a model configuration");
     if (q->stride < 1 || q->kernel_size < 3 || q->k2 < 3 || q->k3 < 3 || q->n_filters < 1 || q->c2 < 1 || q->c3 < 1)
         return fail(c, UVAD_E_ARG, "bad SincNet configuration");
+    if (!std::isfinite(q->leaky_slope)) return fail(c, UVAD_E_ARG, "SincNet leaky_slope must be finite");
+    // eps >= 0 keeps an instance-normalised value within sqrt(L - 1) in magnitude: the bound the split-f16 range guard rests on
+    if (!std::isfinite(q->eps) || q->eps < 0.0f) return fail(c, UVAD_E_ARG, "SincNet eps must be finite and >= 0");
     const int cout[3] = {q->n_filters, q->c2, q->c3};
     if ((q->n_filters & 1) || (q->c2 & 1)) return fail(c, UVAD_E_UNSUPPORTED, "SincNet input channel counts of the conv stages must be even");
     for (int i = 0; i < 3; ++i)
@@ -806,10 +811,13 @@ static int sincnet_impl(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64
     else HIPCHK(c, launch_wav_stats(static_cast<const float *>(d_wav), B, S, S, c->sn_wav_g, c->sn_wav_b, q.eps, s0, s0 + B, s));
     const float *in = wav16 ? nullptr : static_cast<const float *>(d_wav), *in_scale = s0, *in_shift = s0 + B;
     // Split-f16 form (GEMM modes 1 / 3) when the geometry is the reference's and every stage input provably fits the f16 range: an
-    // instance-normalised value is at most sqrt(L - 1) in magnitude, so |gamma| * sqrt(L) + |beta| bounds what the staging converts.
-    bool f16 = l.f16 && c->sinc_f16 && (c->gemm_mode == 1 || c->gemm_mode == 3);
+    // instance-normalised value is at most sqrt(L - 1) in magnitude, so |gamma| * sqrt(L) + |beta| bounds what the staging converts, and
+    // the leaky_relu in front of stages 2 and 3 scales that by at most max(1, |slope|).  The staging of those stages applies leaky_relu
+    // as max(e, e * slope), which is leaky_relu only for slope <= 1: a larger slope runs the exact-f32 stages.
+    bool f16 = l.f16 && c->sinc_f16 && (c->gemm_mode == 1 || c->gemm_mode == 3) && q.leaky_slope <= 1.0f;
+    const double act = std::fmax(1.0, std::fabs((double)q.leaky_slope));
     for (int i = 0; i < 3 && f16; ++i)
-        if (!(c->sn_in_gmax[i] * std::sqrt((double)l.Lin[i]) + c->sn_in_bmax[i] < 60000.0)) f16 = false;
+        if (!((c->sn_in_gmax[i] * std::sqrt((double)l.Lin[i]) + c->sn_in_bmax[i]) * (i > 0 ? act : 1.0) < 60000.0)) f16 = false;
     c->sinc_f16_used = f16;
     if (f16) {
         for (int i = 0; i < 3; ++i) {
