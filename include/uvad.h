@@ -18,7 +18,7 @@
  *     allocates or frees caller tensors.  It owns only the weights / tables inside uvad_ctx.
  *   - compute calls are ASYNCHRONOUS on `stream` (a hipStream_t passed as void*; NULL = the
  *     default stream) and perform no allocation or synchronisation => hipGraph-capturable
- *     (exception: uvad_stream_step, see there).  Every call makes the context's device current
+ *     (exceptions: uvad_stream_step and uvad_window_step, see there).  Every call makes the context's device current
  *     (hipSetDevice) before it enqueues, so a multi-GPU process may interleave contexts freely.
  *   - one ctx per (device, model); a ctx is NOT thread-safe (the reference drives the model
  *     from a single thread: Trainer(devices=1), src/scripts/predict.py:79-85).
@@ -165,6 +165,39 @@ int uvad_stream_step(uvad_ctx *, const float *d_pcm_chunk, int B, int chunk, voi
                      float *d_logits, int ld_logits, void *d_workspace, size_t ws_bytes, void *stream);
 int uvad_stream_peek(const uvad_ctx *, const void *d_state, int chunk, int *k, int64_t *offset, int *parity, int *first);
 int uvad_stream_advance(uvad_ctx *, void *d_state, int chunk);
+
+/* Windowed streaming: any model uvad_classify runs -- bidirectional included, which uvad_stream_* refuses -- served live by
+ * re-running it from zero state over a sliding window, the reference's inference semantic (5 s windows, each from zero state,
+ * src/datasets/ami/utils.py:107,163; the reference itself has no streaming).  B feeds advance in lockstep, `chunk` samples per step;
+ * uvad_window_reset configures a window of `window` = W frames and a look-ahead of `lookahead` = L frames (0 <= L < W, and every step
+ * needs L + chunk / frame_shift + 1 <= W, else UVAD_E_ARG).
+ *   Features: the framing of uvad_stream_step (snip_edges = 0, first chunk reflected on the left).  Frame t is transformed ONCE, when
+ *   its last sample arrives, into a per-feed ring of W frames in d_state, so a window's features are slices of the continuous feature
+ *   stream: frame t equals uvad_fbank of the whole signal at t to fp32 rounding.  This is the one deliberate difference from the
+ *   reference, which frames every cut anew: only the reflected edge frames of a reference cut differ.
+ *   Emission: after a step let e be the number of complete frames.  The step emits frames [f0, e - L) (f0 = what earlier steps emitted;
+ *   none while e <= L) and returns their number k >= 0.  The logit of each emitted frame t is row t of the model run from zero state
+ *   over the window [max(0, e - W), e) (the prefix [0, e) during the warm-up e < W).  Streams are open-ended: the last L frames are
+ *   never emitted and there is no right-edge reflection.  For a causal model with L = 0 the warm-up steps equal uvad_stream_step.
+ *   Outputs: d_logits / d_probs [B][ld_out] (row b, columns 0 .. k - 1; either may be NULL, not both).
+ * A step enqueues the feature stage for the new frames only, one kernel that writes the window from the ring straight into the first
+ * projection's operand, the classifier at (B, Tw = min(e, W)) -- with time chunks off (uvad_get_time_chunks() is 1 afterwards) -- and a
+ * gather of the emitted rows.  It never allocates, frees or synchronises, warm-up included.  Host-side counters decide the launch
+ * arguments (as for uvad_stream_step); once the window is full the ring position and frame count are read from the device, so two
+ * steps with the same replay_key (uvad_window_peek; -1 during the warm-up) and the same buffers enqueue identical work: a graph
+ * captured around one replays for the other, followed by uvad_window_advance, which moves the counters as the step would and
+ * returns its k.  For a chunk that is a multiple of frame_shift a group settles into two keys (the PCM-tail parity); otherwise into
+ * a number bounded by the chunk / frame_shift cycle.
+ * uvad_window_features (debug tap) copies the current window's features [B][Tw][n_mels] (as the last step classified them) to
+ * d_feats and sets *Tw; d_feats = NULL only sets *Tw. */
+size_t uvad_window_state_bytes(const uvad_ctx *, int B, int window);
+size_t uvad_window_workspace_bytes(const uvad_ctx *, int B, int chunk, int window);
+int uvad_window_reset(uvad_ctx *, void *d_state, int B, int window, int lookahead, void *stream);
+int uvad_window_step(uvad_ctx *, const float *d_pcm_chunk, int B, int chunk, void *d_state,
+                     float *d_logits, float *d_probs, int ld_out, void *d_workspace, size_t ws_bytes, void *stream);
+int uvad_window_peek(const uvad_ctx *, const void *d_state, int chunk, int *k, int64_t *replay_key);
+int uvad_window_advance(uvad_ctx *, void *d_state, int chunk);
+int uvad_window_features(uvad_ctx *, const void *d_state, int B, float *d_feats, int *Tw, void *stream);
 
 /* Replaces: median_filter (src/utils/helper.py:66-97) as used by VadModel.predict_step
  * (vad_engine.py:204-211): threshold 0.5 then odd `kernel`-tap median, zero padded edges.

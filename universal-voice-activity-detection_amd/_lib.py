@@ -71,6 +71,14 @@ SIGNATURES = {
     "uvad_stream_peek": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int),
                                    C.POINTER(C.c_int)]),
     "uvad_stream_advance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "uvad_window_state_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "uvad_window_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "uvad_window_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "uvad_window_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_window_peek": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "uvad_window_advance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "uvad_window_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "uvad_median_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "uvad_label_runs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uvad_der_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -106,7 +114,11 @@ def load():
             "`make -C universal-voice-activity-detection_amd/csrc`. There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise RuntimeError(f"libuvad.so does not export {name}: it was built from an older source tree; rebuild the library "
+                               "(`make -C universal-voice-activity-detection_amd/csrc`)") from None
         fn.restype = res
         fn.argtypes = args
     got = lib.uvad_abi_version()

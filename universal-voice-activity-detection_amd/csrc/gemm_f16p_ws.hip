@@ -380,7 +380,7 @@ hipError_t launch_gemm_f16p_ws(const GemmArgs &a, unsigned *counters, int n_cu, 
         for (int d = 0; d < a.ws_dirs; ++d)
             if (a.ws_off[d] < 0 || a.ws_len[d] < 0 || a.ws_len[d] > mt) return hipErrorInvalidValue;
     }
-    hipError_t e = hipMemsetAsync(counters, 0, gemm_f16p_ws_counter_bytes(), s);
+    hipError_t e = launch_zero_counters(counters, (int)(gemm_f16p_ws_counter_bytes() / sizeof(unsigned)), s);
     if (e != hipSuccess) return e;
     // one workgroup per CU; every (group, column tile) pair must own at least one workgroup: a multiple of 8 * nt
     const int per = GROUPS * nt;

@@ -155,6 +155,10 @@ __global__ __launch_bounds__(256) void runs_kernel(const uint8_t *labels, int B,
 }
 
 // busy-waits `ticks` of the constant 100 MHz counter (s_memrealtime), one wave: the stream-overlap probe's "long" kernel
+__global__ __launch_bounds__(256) void zero_counters_kernel(unsigned *p, int n) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) atomicExch(p + i, 0u);
+}
+
 __global__ __launch_bounds__(64) void spin_kernel(unsigned long long ticks, unsigned long long *sink) {
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
     unsigned long long t = t0;
@@ -205,6 +209,12 @@ hipError_t launch_median(const float *probs, int B, int T, int kernel, uint8_t *
     const long long n = (long long)B * T;
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(median_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, s, probs, B, T, kernel / 2, labels);
+    return hipGetLastError();
+}
+
+hipError_t launch_zero_counters(unsigned *p, int n, hipStream_t s) {
+    if (!p || n <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(zero_counters_kernel, dim3((n + 255) / 256), dim3(256), 0, s, p, n);
     return hipGetLastError();
 }
 

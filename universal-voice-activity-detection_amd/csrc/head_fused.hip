@@ -325,7 +325,7 @@ bool head_fused_supported(int K1, int lin_hidden, int lin_layers, long long M, i
 
 hipError_t launch_head_fused(const HeadArgs &a, int n_cu, hipStream_t s) {
     if (!a.Yh || !a.Yl || !a.W1 || !a.W2 || !a.b1 || !a.b2 || !a.wc || !a.bc || !a.counter || a.M <= 0) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(a.counter, 0, sizeof(unsigned), s);
+    hipError_t e = launch_zero_counters(a.counter, 1, s);
     if (e != hipSuccess) return e;
     const int mt = (int)((a.M + TM - 1) / TM);
     const int ncu = n_cu > 0 ? n_cu : 256;

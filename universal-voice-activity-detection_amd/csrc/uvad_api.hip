@@ -87,9 +87,11 @@ constexpr int SIDE_RETRY_AFTER = 256;       // calls after which a caller stream
 
 struct StreamCounters { int64_t n_samples = 0, n_frames = 0, n_steps = 0; };
 struct StreamState { float *h = nullptr, *c = nullptr; size_t layer_stride = 0; };
+struct WindowGroup { StreamCounters sc; int B = 0, W = 0, L = 0; };
 
 struct uvad_ctx {
     std::map<void *, StreamCounters> streams;   // host mirror of the lock-step stream groups, keyed by d_state
+    std::map<void *, WindowGroup> windows;      // ... and of the windowed stream groups (uvad_window_*)
     int device = 0, n_cu = 256;
     bool has_fb = false, has_model = false, finalized = false, tables_set = false;
     uvad_fbank_cfg fb{};
@@ -1455,6 +1457,22 @@ StreamPlan stream_plan(const uvad_ctx *c, const StreamCounters &sc, int chunk) {
     p.offset = p.k > 0 ? sc.n_frames * sh - n_left - (n_prev - L) : 0;   // offset of the first new frame inside a staging row (tail = L samples)
     return p;
 }
+// The feature stage of a step with p.k > 0 frames: VIRTUAL rows [tail (frame_len samples) | chunk] read from p.offset on (FbankArgs::vs_*);
+// the kernel also writes the next tail.  Output pointers (feats / planes) are the caller's.
+FbankArgs stream_fbank_args(const uvad_ctx *c, const float *d_pcm_chunk, int B, int chunk, const StreamPlan &p, const float *staging,
+                            const float *tail_in, float *tail_out) {
+    const int L = c->fb.frame_len, sh = c->fb.frame_shift;
+    FbankArgs fa{};
+    fa.pcm = staging + p.offset; fa.pcm_is_i16 = 0; fa.B = B; fa.S = (int64_t)(L + chunk) - p.offset; fa.T = p.k;
+    fa.vs_chunk = d_pcm_chunk; fa.vs_tail_in = tail_in; fa.vs_tail_out = tail_out;
+    fa.vs_tail = L; fa.vs_chunk_len = chunk; fa.vs_first = p.first; fa.vs_n_left = (L - sh) / 2; fa.vs_offset = (int)p.offset;
+    fa.row_stride = L + chunk;
+    fa.frame_len = L; fa.frame_shift = sh; fa.n_mels = c->fb.n_mels;
+    fa.preemph = c->fb.preemph; fa.log_floor = c->fb.log_floor; fa.remove_dc = c->fb.remove_dc; fa.snip_edges = 1;
+    fa.tab.window = c->d_window; fa.tab.mel_start = c->d_mel_start; fa.tab.mel_len = c->d_mel_len;
+    fa.tab.mel_w = c->d_mel_w; fa.tab.mel_wt = c->d_mel_wt; fa.tab.mel_stride = c->mel_stride; fa.tab.tw512 = c->d_tw512; fa.tab.nyquist = c->mel_nyquist;
+    return fa;
+}
 }  // namespace
 }  // extern "C++"
 
@@ -1513,19 +1531,12 @@ int uvad_stream_step(uvad_ctx *c, const float *d_pcm_chunk, int B, int chunk, vo
     sc.n_steps += 1;
     if (k <= 0) return 0;
     if (k > ld_logits) return fail(c, UVAD_E_ARG, "ld_logits smaller than the number of new frames");
-    const int64_t o = plan.offset;   // >= 0
     sc.n_frames += k;
     void *cws = wsb + staging_bytes;
     const WsLayout w = carve(c, B, k);
     float *feats = reinterpret_cast<float *>(reinterpret_cast<char *>(cws) + w.off_feats);
-    FbankArgs fa{};
-    fa.pcm = staging + o; fa.pcm_is_i16 = 0; fa.B = B; fa.S = (int64_t)(S.tail + chunk) - o; fa.T = k;
-    fa.vs_chunk = d_pcm_chunk; fa.vs_tail_in = reinterpret_cast<const float *>(st + S.off_tail[par]);
-    fa.vs_tail_out = reinterpret_cast<float *>(st + S.off_tail[par ^ 1]);
-    fa.vs_tail = S.tail; fa.vs_chunk_len = chunk; fa.vs_first = plan.first; fa.vs_n_left = n_left; fa.vs_offset = (int)o;
-    fa.row_stride = S.tail + chunk;
-    fa.frame_len = L; fa.frame_shift = sh; fa.n_mels = c->fb.n_mels;
-    fa.preemph = c->fb.preemph; fa.log_floor = c->fb.log_floor; fa.remove_dc = c->fb.remove_dc; fa.snip_edges = 1;
+    FbankArgs fa = stream_fbank_args(c, d_pcm_chunk, B, chunk, plan, staging, reinterpret_cast<const float *>(st + S.off_tail[par]),
+                                     reinterpret_cast<float *>(st + S.off_tail[par ^ 1]));
     fa.feats = feats;
     // as in uvad_forward: features straight into the first projection's operand planes -- unless the one-launch stack runs (f32 features)
     const bool planes = c->gemm_mode >= 1 && c->f16_ok && !stream_uses_stack(c, k);
@@ -1534,8 +1545,6 @@ int uvad_stream_step(uvad_ctx *c, const float *d_pcm_chunk, int B, int chunk, vo
         fa.plane_lo = fa.plane_hi + plane_rows(w.M) * (size_t)w.Fp;
         fa.plane_w = w.Fp;
     }
-    fa.tab.window = c->d_window; fa.tab.mel_start = c->d_mel_start; fa.tab.mel_len = c->d_mel_len;
-    fa.tab.mel_w = c->d_mel_w; fa.tab.mel_wt = c->d_mel_wt; fa.tab.mel_stride = c->mel_stride; fa.tab.tw512 = c->d_tw512; fa.tab.nyquist = c->mel_nyquist;
     // One launch for the whole step when the stack kernel also takes the head and the feature stage fits beside it (lstm_stack.hip)
     const bool fuse_fb = !planes && stream_uses_stack(c, k) && stream_head_in_stack(c) && lstm_stack_fb_lds_bytes(fa, k) > 0;
     if (!fuse_fb) HIPCHK(c, launch_fbank(fa, s));
@@ -1568,6 +1577,204 @@ int uvad_stream_advance(uvad_ctx *c, void *d_state, int chunk) {
     sc.n_steps += 1;
     sc.n_frames += p.k;
     return p.k;
+}
+
+// ---- windowed streaming ------------------------------------------------------------------------
+// state layout (bytes, 256-aligned blocks): tail[2][B][frame_len] f32 (ping-pong, as the stream) | ring [B][W][n_mels] f32 |
+// ctr[2] int64 (frames complete: ctr[parity] before a step, ctr[parity ^ 1] after it)
+// workspace: staging [B][frame_len + chunk] (steps without frames) | new frames [B][kmax][n_mels] | logits, probs [B][W] | classifier
+//            workspace of (B, W) (carve() grows with T, so it holds every warm-up window too)
+extern "C++" {
+namespace {
+struct WindowLayout {
+    size_t off_tail[2] = {0, 0}, off_ring = 0, off_ctr = 0, total = 0;
+};
+WindowLayout window_layout(const uvad_ctx *c, int B, int W) {
+    WindowLayout L;
+    size_t o = 0;
+    for (int i = 0; i < 2; ++i) { L.off_tail[i] = o; o += align_up((size_t)B * c->fb.frame_len * sizeof(float)); }
+    L.off_ring = o; o += align_up((size_t)B * W * c->fb.n_mels * sizeof(float));
+    L.off_ctr = o; o += align_up(2 * sizeof(long long));
+    L.total = o;
+    return L;
+}
+struct WindowWs {
+    size_t off_new = 0, off_logits = 0, off_probs = 0, off_cls = 0, total = 0;
+};
+WindowWs window_ws(const uvad_ctx *c, int B, int chunk, int W) {
+    WindowWs w;
+    size_t o = align_up((size_t)B * (c->fb.frame_len + chunk) * sizeof(float));
+    w.off_new = o; o += align_up((size_t)B * stream_max_frames(c, chunk) * c->fb.n_mels * sizeof(float));
+    w.off_logits = o; o += align_up((size_t)B * W * sizeof(float));
+    w.off_probs = o; o += align_up((size_t)B * W * sizeof(float));
+    w.off_cls = o; o += carve(c, B, W).total;
+    w.total = o;
+    return w;
+}
+// What the next step of a window group does: the stream's plan for the feature stage (k new frames), the window [e - Tw, e) it
+// classifies and the rows [r0, r0 + n_emit) of that window it emits (frames [max(0, e_prev - L), max(0, e - L))).
+struct WindowPlan { StreamPlan fp; int64_t e = 0; int Tw = 0, r0 = 0, n_emit = 0; int64_t key = -1; };
+WindowPlan window_plan(const uvad_ctx *c, const WindowGroup &g, int chunk) {
+    WindowPlan p;
+    p.fp = stream_plan(c, g.sc, chunk);
+    const int64_t e_prev = g.sc.n_frames;
+    p.e = e_prev + p.fp.k;
+    p.Tw = (int)std::min<int64_t>(p.e, g.W);
+    const int64_t f0 = std::max<int64_t>(0, e_prev - g.L), f1 = std::max<int64_t>(0, p.e - g.L);
+    p.n_emit = (int)(f1 - f0);
+    p.r0 = (int)(f0 - (p.e - p.Tw));
+    // Once the window is full, everything that moves from step to step is read from the device (ring position, counter); what the launch
+    // arguments still carry is k, the staging offset and the parity (Tw = W, r0 = W - L - k, n_emit = k follow from them)
+    if (!p.fp.first && p.e >= g.W) p.key = ((int64_t)p.fp.k << 32) | (p.fp.offset << 1) | p.fp.parity;
+    return p;
+}
+void window_advance(WindowGroup &g, const WindowPlan &p) {
+    g.sc.n_samples = p.fp.n_after;
+    g.sc.n_steps += 1;
+    g.sc.n_frames = p.e;
+}
+int window_check_cfg(uvad_ctx *c, const char *who) {
+    if (!c->has_fb || !c->has_model) return fail(c, UVAD_E_STATE, std::string(who) + ": needs both a fbank and a model configuration");
+    if (c->fb.snip_edges) return fail(c, UVAD_E_UNSUPPORTED, std::string(who) + ": the centred (snip_edges = 0) framing only");
+    if (c->fb.n_mels != c->mc.in_dim) return fail(c, UVAD_E_ARG, std::string(who) + ": n_mels != encoding_dim");
+    return UVAD_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+size_t uvad_window_state_bytes(const uvad_ctx *c, int B, int window) {
+    if (!c || !c->has_fb || !c->has_model || B <= 0 || window < 1) return 0;
+    return window_layout(c, B, window).total;
+}
+
+size_t uvad_window_workspace_bytes(const uvad_ctx *c, int B, int chunk, int window) {
+    if (!c || !c->has_fb || !c->has_model || B <= 0 || chunk <= 0 || window < 1) return 0;
+    return window_ws(c, B, chunk, window).total;
+}
+
+int uvad_window_reset(uvad_ctx *c, void *d_state, int B, int window, int lookahead, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_state || B <= 0) return fail(c, UVAD_E_ARG, "uvad_window_reset: bad argument");
+    if (window < 1) return fail(c, UVAD_E_ARG, "uvad_window_reset: window must be >= 1 frame");
+    if (lookahead < 0 || lookahead >= window) return fail(c, UVAD_E_ARG, "uvad_window_reset: need 0 <= lookahead < window");
+    if (int r = window_check_cfg(c, "uvad_window_reset")) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemsetAsync(d_state, 0, window_layout(c, B, window).total, (hipStream_t)stream));
+    WindowGroup g;
+    g.B = B; g.W = window; g.L = lookahead;
+    c->windows[d_state] = g;
+    return UVAD_OK;
+}
+
+int uvad_window_step(uvad_ctx *c, const float *d_pcm_chunk, int B, int chunk, void *d_state, float *d_logits, float *d_probs, int ld_out,
+                     void *ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_pcm_chunk || !d_state || (!d_logits && !d_probs) || !ws || B <= 0 || chunk <= 0)
+        return fail(c, UVAD_E_ARG, "uvad_window_step: bad argument");
+    if (!c->finalized || !c->tables_set) return fail(c, UVAD_E_STATE, "uvad_window_step: context not ready (tables / weights)");
+    if (int r = window_check_cfg(c, "uvad_window_step")) return r;
+    auto it = c->windows.find(d_state);
+    if (it == c->windows.end()) return fail(c, UVAD_E_STATE, "uvad_window_step: call uvad_window_reset on this state first");
+    WindowGroup &g = it->second;
+    if (B != g.B) return fail(c, UVAD_E_ARG, "uvad_window_step: B differs from the one the state was reset with");
+    const int L = c->fb.frame_len, sh = c->fb.frame_shift, n_left = (L - sh) / 2, F = c->fb.n_mels;
+    const int kmax = stream_max_frames(c, chunk);
+    if ((int64_t)g.L + kmax > g.W)
+        return fail(c, UVAD_E_ARG, "uvad_window_step: lookahead + chunk / frame_shift + 1 = " + std::to_string(g.L + kmax) + " frames exceeds the window of " +
+                                       std::to_string(g.W));
+    if (g.sc.n_samples == 0 && chunk < n_left) return fail(c, UVAD_E_ARG, "first chunk must hold at least (frame_len - shift)/2 samples");
+    const WindowWs wl = window_ws(c, B, chunk, g.W);
+    if (ws_bytes < wl.total) return fail(c, UVAD_E_WORKSPACE, "window workspace too small: need " + std::to_string(wl.total) + " bytes");
+    const WindowPlan p = window_plan(c, g, chunk);
+    if (p.n_emit > ld_out) return fail(c, UVAD_E_ARG, "uvad_window_step: ld_out smaller than the number of emitted frames");
+    const WindowLayout SL = window_layout(c, B, g.W);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    char *st = reinterpret_cast<char *>(d_state);
+    char *wsb = reinterpret_cast<char *>(ws);
+    float *staging = reinterpret_cast<float *>(wsb);
+    const int par = p.fp.parity, k = p.fp.k;
+    const float *tail_in = reinterpret_cast<const float *>(st + SL.off_tail[par]);
+    float *tail_out = reinterpret_cast<float *>(st + SL.off_tail[par ^ 1]);
+    long long *ctr = reinterpret_cast<long long *>(st + SL.off_ctr);
+    c->chunks_used = 1;
+    if (k <= 0) {   // no frame completes: carry the tail and the frame count over to the other parity
+        HIPCHK(c, launch_stream_stage(d_pcm_chunk, B, chunk, L, n_left, p.fp.first, tail_in, tail_out, staging, s));
+        HIPCHK(c, launch_window_carry(ctr + par, ctr + (par ^ 1), s));
+        window_advance(g, p);
+        return 0;
+    }
+    // the k new frames, computed once
+    float *newf = reinterpret_cast<float *>(wsb + wl.off_new);
+    FbankArgs fa = stream_fbank_args(c, d_pcm_chunk, B, chunk, p.fp, staging, tail_in, tail_out);
+    fa.feats = newf;
+    HIPCHK(c, launch_fbank(fa, s));
+    // the window into the first projection's operand, as uvad_forward's feature kernel writes it
+    char *cws = wsb + wl.off_cls;
+    const WsLayout w = carve(c, B, p.Tw);
+    const bool planes = c->gemm_mode >= 1 && c->f16_ok;
+    float *feats = reinterpret_cast<float *>(cws + w.off_feats);
+    WindowArgs a{};
+    a.newf = newf; a.ring = reinterpret_cast<float *>(st + SL.off_ring); a.ctr_in = ctr + par; a.ctr_out = ctr + (par ^ 1);
+    a.B = B; a.R = g.W; a.F = F; a.k = k; a.Tw = p.Tw;
+    a.planes = planes; a.Fp = w.Fp; a.tiles = w.tiles;
+    a.xh = reinterpret_cast<unsigned short *>(cws + w.off_fplanes); a.xl = a.xh + plane_rows(w.M) * (size_t)w.Fp;
+    a.out = feats;
+    HIPCHK(c, launch_window_assemble(a, s));
+    window_advance(g, p);
+    if (p.n_emit <= 0) return 0;
+    float *lg = reinterpret_cast<float *>(wsb + wl.off_logits), *pr = reinterpret_cast<float *>(wsb + wl.off_probs);
+    // the classifier at (B, Tw), time chunks off: a new T every warm-up step would churn the chunk-plan cache, whose eviction synchronises
+    const bool timing = c->timing;
+    const int chunk_mode = c->chunk_mode;
+    c->timing = false;
+    c->chunk_mode = 1;
+    const int r = classify_impl(c, feats, B, p.Tw, d_logits ? lg : nullptr, d_probs ? pr : nullptr, cws, wl.total - wl.off_cls, s, false, false,
+                                nullptr, 0, planes, nullptr);
+    c->timing = timing;
+    c->chunk_mode = chunk_mode;
+    if (r) return r;
+    HIPCHK(c, launch_window_emit(lg, pr, B, p.Tw, p.r0, p.n_emit, d_logits, d_probs, ld_out, s));
+    return p.n_emit;
+}
+
+int uvad_window_peek(const uvad_ctx *c, const void *d_state, int chunk, int *k, int64_t *replay_key) {
+    if (!c || !d_state || chunk <= 0 || !k || !replay_key) return UVAD_E_ARG;
+    auto it = c->windows.find(const_cast<void *>(d_state));
+    if (it == c->windows.end() || !c->has_fb) return UVAD_E_STATE;
+    const WindowPlan p = window_plan(c, it->second, chunk);
+    *k = p.n_emit;
+    *replay_key = p.key;
+    return UVAD_OK;
+}
+
+int uvad_window_advance(uvad_ctx *c, void *d_state, int chunk) {
+    if (!c || !d_state || chunk <= 0) return UVAD_E_ARG;
+    auto it = c->windows.find(d_state);
+    if (it == c->windows.end() || !c->has_fb) return fail(c, UVAD_E_STATE, "uvad_window_advance: call uvad_window_reset on this state first");
+    const WindowPlan p = window_plan(c, it->second, chunk);
+    window_advance(it->second, p);
+    return p.n_emit;
+}
+
+int uvad_window_features(uvad_ctx *c, const void *d_state, int B, float *d_feats, int *Tw, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_state || !Tw || B <= 0) return fail(c, UVAD_E_ARG, "uvad_window_features: bad argument");
+    auto it = c->windows.find(const_cast<void *>(d_state));
+    if (it == c->windows.end()) return fail(c, UVAD_E_STATE, "uvad_window_features: call uvad_window_reset on this state first");
+    const WindowGroup &g = it->second;
+    if (B != g.B) return fail(c, UVAD_E_ARG, "uvad_window_features: B differs from the one the state was reset with");
+    *Tw = (int)std::min<int64_t>(g.sc.n_frames, g.W);
+    if (!d_feats || *Tw == 0) return UVAD_OK;
+    const WindowLayout SL = window_layout(c, B, g.W);
+    const char *st = reinterpret_cast<const char *>(d_state);
+    HIPCHK(c, hipSetDevice(c->device));
+    WindowArgs a{};
+    a.ring = reinterpret_cast<float *>(const_cast<char *>(st) + SL.off_ring);
+    a.ctr_in = reinterpret_cast<const long long *>(st + SL.off_ctr) + (g.sc.n_steps & 1);
+    a.B = B; a.R = g.W; a.F = c->fb.n_mels; a.k = 0; a.Tw = *Tw; a.out = d_feats;
+    HIPCHK(c, launch_window_assemble(a, (hipStream_t)stream));
+    return UVAD_OK;
 }
 
 int uvad_median_filter(uvad_ctx *c, const float *d_probs, int B, int T, int kernel, uint8_t *d_labels, void *stream) {

@@ -147,6 +147,12 @@ hipError_t launch_runs(const uint8_t *labels, int B, int T, int max_runs, int *r
 // per-row {false alarm, missed detection} frame counts of 0/1 label rows
 hipError_t launch_der(const uint8_t *pred, const uint8_t *gt, int B, int T, uint32_t *counts, hipStream_t s);
 
+// zero n words of tile-queue counters with device-scope atomic exchanges: the operations the persistent kernels count with
+// (gemm_f16p_ws_kernel, head_fused_kernel), so the reset and the counting meet at the same coherence point.  Used instead of
+// hipMemsetAsync, whose blit node in a replayed hipGraph was not always seen by the next kernel's atomics (the head then found its
+// queue exhausted and left its logits unwritten)
+hipError_t launch_zero_counters(unsigned *p, int n, hipStream_t s);
+
 // one wave that busy-waits `ticks` of the 100 MHz constant clock, then (optionally) stores the waited ticks
 hipError_t launch_spin(unsigned long long ticks, unsigned long long *sink, hipStream_t s);
 
@@ -206,6 +212,24 @@ size_t fbank_lds_bytes(const FbankArgs &a);
 // new tail = last `tail` samples of staging
 hipError_t launch_stream_stage(const float *chunk_pcm, int B, int chunk, int tail, int n_left, int first_step,
                                const float *tail_in, float *tail_out, float *staging, hipStream_t s);
+
+// ---- window_stream.hip: the feature ring of the windowed stream (uvad_window_step) -------------------------------------------
+// The window [e - Tw, e) of every feed, e = *ctr_in + k read on the device, from the ring [B][R][F] (frame t in slot t % R) and the k
+// new frames newf [B][k][F] (committed to their slots on the way) -> the f16 planes of the first projection (planes: split_features_kernel's
+// layout, Fp columns, tiles * Tw * SEQ_TILE tile-major rows, padding sequences zero) or canonical f32 rows out [B][Tw][F].  ctr_out
+// (optional) receives e.  k = 0, ctr_out = nullptr: a read-only copy of the window (the debug tap).
+struct WindowArgs {
+    const float *newf; float *ring; const long long *ctr_in; long long *ctr_out;
+    int B, R, F, k, Tw;
+    int planes; unsigned short *xh, *xl; int Fp, tiles;
+    float *out;
+};
+hipError_t launch_window_assemble(const WindowArgs &a, hipStream_t s);
+// a step that completes no frame: *ctr_out = *ctr_in (a kernel, not a copy node: see launch_zero_counters)
+hipError_t launch_window_carry(const long long *ctr_in, long long *ctr_out, hipStream_t s);
+// logits / probs [b][j] (row stride ld_out) = logits_in / probs_in [b][r0 + j] (row stride Tw), j < n; either output may be nullptr
+hipError_t launch_window_emit(const float *logits_in, const float *probs_in, int B, int Tw, int r0, int n, float *logits, float *probs,
+                              int ld_out, hipStream_t s);
 
 // ---- lstm_stack.hip: every layer of a causal (one-direction, H = 128) stack for T <= LSTM_STACK_TMAX new frames in ONE launch, carried
 //      (h, c) updated in place: the streaming step (uvad_stream_step).  Exact f32.

@@ -17,6 +17,31 @@ def _model_cfg(encoding_dim: int, lstm: dict, linear: dict, leaky_slope: float =
                          int(linear.get("num_layers", 0)), float(leaky_slope))
 
 
+def window_step_plan(samples: int, frames: int, chunk: int, window: int, lookahead: int, frame_len: int = 400, frame_shift: int = 160):
+    """One step of a windowed stream group (uvad_window_step, include/uvad.h) from its counters (samples received, frames complete)
+    -> (samples, frames, (k, window_lo, window_hi, emit_lo, emit_hi)) after the step.  Frame t spans samples
+    [t * shift - n_left, t * shift - n_left + frame_len), n_left = (frame_len - shift) // 2; the model runs over frames
+    [window_lo, window_hi) and the step emits frames [emit_lo, emit_hi), k = emit_hi - emit_lo of them."""
+    n_left = (frame_len - frame_shift) // 2
+    if samples == 0 and chunk < n_left:
+        raise ValueError(f"the first chunk must hold at least (frame_len - shift) / 2 = {n_left} samples")
+    if lookahead < 0 or lookahead + chunk // frame_shift + 1 > window:
+        raise ValueError(f"need 0 <= lookahead and lookahead + chunk // frame_shift + 1 <= window (got {lookahead}, {chunk}, {window})")
+    n = samples + chunk
+    e = max(frames, (n + n_left - frame_len) // frame_shift + 1) if n + n_left - frame_len >= 0 else frames
+    lo, hi = max(0, frames - lookahead), max(0, e - lookahead)
+    return n, e, (hi - lo, max(0, e - window), e, lo, hi)
+
+
+def window_schedule(steps: int, chunk: int, window: int, lookahead: int = 0, frame_len: int = 400, frame_shift: int = 160):
+    """[(k, window_lo, window_hi, emit_lo, emit_hi)] for `steps` steps of `chunk` samples of a windowed stream group (window_step_plan)."""
+    out, n, e = [], 0, 0
+    for _ in range(steps):
+        n, e, row = window_step_plan(n, e, chunk, window, lookahead, frame_len, frame_shift)
+        out.append(row)
+    return out
+
+
 class VadRuntime:
     def __init__(self, device, fbank: Optional[FbankConfig] = None, model: Optional[dict] = None, sincnet: Optional[dict] = None):
         """model: {"encoding_dim": int, "lstm": {...merged defaults...}, "linear": {...}} or None.
@@ -317,6 +342,85 @@ class VadRuntime:
             if k < 0:
                 self._check(k)
             return out[:, :k]
+
+    # ------------------------------------------------------------------ windowed streaming (any model, bidirectional included)
+    def window_stream_open(self, B: int, chunk: int, window: int = 500, lookahead: int = 0, graphs: bool = False):
+        """Allocate and reset a windowed stream group (uvad_window_reset): B lock-step feeds of `chunk` samples per step, the model
+        run from zero state over the last `window` frames, frames emitted `lookahead` frames behind the newest complete one.
+        graphs: once the window is full, capture each distinct step (uvad_window_peek's replay key) into a hipGraph and replay it."""
+        with torch.cuda.device(self.device):
+            nbytes = int(self.lib.uvad_window_state_bytes(self.ctx, B, window))
+            if nbytes == 0:
+                raise RuntimeError("windowed streaming needs a runtime built with both a FbankConfig and a model, and window >= 1")
+            state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._check(self.lib.uvad_window_reset(self.ctx, state.data_ptr(), B, window, lookahead, self._stream()))
+            ws = torch.empty(int(self.lib.uvad_window_workspace_bytes(self.ctx, B, chunk, window)), dtype=torch.uint8, device=self.device)
+            kmax = chunk // self._fb_c.frame_shift + 1
+            return {"state": state, "ws": ws, "B": B, "chunk": chunk, "window": window, "lookahead": lookahead, "samples": 0, "frames": 0,
+                    "out": torch.empty((B, kmax), dtype=torch.float32, device=self.device),
+                    "in": torch.empty((B, chunk), dtype=torch.float32, device=self.device),
+                    "graphs": {} if graphs else None, "weights_gen": getattr(self, "_weights_gen", 0)}
+
+    def window_stream_step(self, st, pcm_chunk: "torch.Tensor") -> "torch.Tensor":
+        """pcm_chunk (B, chunk) f32 on the GPU -> logits (B, k) of the k frames this step emits (window_step_plan; a view of a buffer
+        that the next step overwrites).  With window_stream_open(graphs=True) warm-up steps are enqueued kernel by kernel and the
+        steady-state ones replay one hipGraph per replay key, then move the counters with uvad_window_advance."""
+        with torch.cuda.device(self.device):
+            pcm_chunk = self._dev_f32(pcm_chunk, "pcm_chunk")
+            if tuple(pcm_chunk.shape) != (st["B"], st["chunk"]):
+                raise ValueError(f"expected a ({st['B']}, {st['chunk']}) chunk, got {tuple(pcm_chunk.shape)}")
+            n, e, (k_want, *_) = window_step_plan(st["samples"], st["frames"], st["chunk"], st["window"], st["lookahead"],
+                                                  self._fb_c.frame_len, self._fb_c.frame_shift)
+            out = st["out"]
+
+            def enqueue(src):
+                return self.lib.uvad_window_step(self.ctx, src.data_ptr(), st["B"], st["chunk"], st["state"].data_ptr(), out.data_ptr(),
+                                                 None, out.shape[1], st["ws"].data_ptr(), st["ws"].numel(), self._stream())
+
+            graphs = st.get("graphs")
+            if graphs is not None and st.get("weights_gen") != getattr(self, "_weights_gen", 0):
+                graphs.clear()           # captured before a weight hot-swap: their kernel nodes point at freed buffers
+                st["weights_gen"] = getattr(self, "_weights_gen", 0)
+            key = -1
+            if graphs is not None:
+                kk, rk = C.c_int(), C.c_int64()
+                self._check(self.lib.uvad_window_peek(self.ctx, st["state"].data_ptr(), st["chunk"], C.byref(kk), C.byref(rk)))
+                key = rk.value
+            if key < 0:
+                k = enqueue(pcm_chunk)
+            else:
+                st["in"].copy_(pcm_chunk)                    # the graphs read their input from a fixed buffer
+                g = graphs.get(key)
+                if g is None:
+                    cur = torch.cuda.current_stream(self.device)
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):                # capture: the step's launches are recorded, not run; its counters advance
+                        k = enqueue(st["in"])
+                    if k < 0:
+                        self._check(k)
+                    graphs[key] = g
+                    torch.cuda.current_stream(self.device).wait_stream(cur)
+                    g.replay()                               # now run it
+                else:
+                    g.replay()
+                    k = self.lib.uvad_window_advance(self.ctx, st["state"].data_ptr(), st["chunk"])
+            if k < 0:
+                self._check(k)
+            if k != k_want:
+                raise RuntimeError(f"uvad_window_step emitted {k} frames, the schedule says {k_want}")
+            st["samples"], st["frames"] = n, e
+            return out[:, :k]
+
+    def window_features(self, st) -> "torch.Tensor":
+        """The features (B, Tw, n_mels) of the window the last window_stream_step classified (debug tap, uvad_window_features)."""
+        with torch.cuda.device(self.device):
+            tw = C.c_int()
+            self._check(self.lib.uvad_window_features(self.ctx, st["state"].data_ptr(), st["B"], None, C.byref(tw), self._stream()))
+            feats = torch.empty((st["B"], tw.value, self._fb_c.n_mels), dtype=torch.float32, device=self.device)
+            if tw.value:
+                self._check(self.lib.uvad_window_features(self.ctx, st["state"].data_ptr(), st["B"], feats.data_ptr(), C.byref(tw),
+                                                          self._stream()))
+            return feats
 
     def set_gemm_mode(self, mode: str):
         """"f32": exact f32 MFMA; "f16p": split-f16 on the f16 matrix cores (default: the weight-stationary kernel for the large
