@@ -199,6 +199,39 @@ int uvad_window_peek(const uvad_ctx *, const void *d_state, int chunk, int *k, i
 int uvad_window_advance(uvad_ctx *, void *d_state, int chunk);
 int uvad_window_features(uvad_ctx *, const void *d_state, int B, float *d_feats, int *Tw, void *stream);
 
+/* Variable-length batches (what torch users know as pack_padded_sequence semantics for nn.LSTM).  Row b of a [B][T] batch holds
+ * len_b valid frames; for a bidirectional model padding is no substitute (the backward direction would start in the padding and run
+ * through it), so these calls carry the lengths down to the recurrence.
+ *   - Lengths live in DEVICE memory: int32 [B] frames (d_lens) or int64 [B] samples (d_nsamp).  They are read on the device and clamped
+ *     to [0, T] (resp. [0, S]), so a call stays enqueue-only and hipGraph-capturable, and one captured graph serves any lengths <= T.
+ *   - Every output of row b at frame t < len_b equals the model run on that row's first len_b frames alone (from zero state in both
+ *     directions).  For GEMM modes 0 and 2 and a pinned recurrent tile (uvad_set_recurrent_tile) the bits are those of uvad_classify on
+ *     the row alone at T = len_b; modes 1 and 3 pick their projection / head kernels by launch size and agree to rounding.
+ *   - Input frames t >= len_b and PCM samples >= S_b are NEVER read: NaN, Inf or 1e30 there changes no output bit, and they cannot trip
+ *     the f16 range check of uvad_classify (the padding of the classifier's operand is zero).
+ *   - Outputs at t >= len_b are exactly 0.0f, logits and probabilities; labels there are 0 and runs never extend past len_b.
+ *   - PCM: row b has T_b = uvad_num_frames(S_b) frames, framed with the right-edge reflection at S_b: frame t < T_b is bit-identical to
+ *     uvad_fbank on pcm[b, :S_b] alone.  Outputs are [B][T], T = uvad_num_frames(S).
+ *   - A lens call runs with time chunks off (uvad_get_time_chunks() is 1 afterwards).  The recurrence of a workgroup runs as many steps
+ *     as its longest sequence; the GEMMs still run over all T rows.
+ *   - Workspace: uvad_workspace_bytes(B, T) as for the dense calls.  d_lens / d_nsamp == NULL: UVAD_E_ARG; a missing table or model:
+ *     UVAD_E_STATE. */
+int uvad_classify_lens(uvad_ctx *, const float *d_feats, int B, int T, const int32_t *d_lens, float *d_logits, float *d_probs,
+                       void *d_workspace, size_t ws_bytes, void *stream);
+int uvad_forward_lens(uvad_ctx *, const float *d_pcm, int B, int64_t S, const int64_t *d_nsamp, float *d_logits, float *d_probs,
+                      void *d_workspace, size_t ws_bytes, void *stream);
+int uvad_forward_lens_i16(uvad_ctx *, const int16_t *d_pcm, int B, int64_t S, const int64_t *d_nsamp, float *d_logits, float *d_probs,
+                          void *d_workspace, size_t ws_bytes, void *stream);
+/* d_feats [B][T][n_mels], T = uvad_num_frames(S); rows past T_b are written as zero */
+int uvad_fbank_lens(uvad_ctx *, const float *d_pcm, int B, int64_t S, const int64_t *d_nsamp, float *d_feats, void *stream);
+int uvad_fbank_lens_i16(uvad_ctx *, const int16_t *d_pcm, int B, int64_t S, const int64_t *d_nsamp, float *d_feats, void *stream);
+/* uvad_median_filter / uvad_label_runs on each row's prefix [0, len_b): the median is scipy medfilt of the prefix with zero padding at
+ * both of its ends; a run open at the end of the prefix closes at len_b */
+int uvad_median_filter_lens(uvad_ctx *, const float *d_probs, int B, int T, const int32_t *d_lens, int kernel, uint8_t *d_labels,
+                            void *stream);
+int uvad_label_runs_lens(uvad_ctx *, const uint8_t *d_labels, int B, int T, const int32_t *d_lens, int max_runs, int32_t *d_runs,
+                         int32_t *d_counts, void *stream);
+
 /* Replaces: median_filter (src/utils/helper.py:66-97) as used by VadModel.predict_step
  * (vad_engine.py:204-211): threshold 0.5 then odd `kernel`-tap median, zero padded edges.
  * d_probs [B][T] -> d_labels [B][T] uint8 (0/1). */

@@ -48,6 +48,9 @@ def load_config() -> ConfigDict:
     # padded to the window; window_seconds = None runs whole recordings in one pass instead (not what the reference does)
     cfg.window_seconds = 5.0
     cfg.min_window_seconds = 3.0
+    # with window_seconds = None: recordings of different lengths share a batch (sorted by length, padded size within max_duration),
+    # each row classified on its own length (uvad_forward_lens); False runs recordings of equal length together only
+    cfg.ragged_batches = False
 
     cfg.experiments_dir = os.environ.get("UVAD_EXPERIMENTS_DIR", "experiments")
     cfg.load_checkpoint = False

@@ -52,7 +52,9 @@ __device__ __forceinline__ float pcm_at(const void *row, int64_t i) {
 
 
 // NORMAL_FLOOR: the energy floor is a normal float (chosen by launch_fbank from FbankArgs::log_floor; see fbp::log_floored)
-template <bool I16, bool NORMAL_FLOOR>
+// LENS (FbankArgs::nsamp): row b holds S_b = clamp(nsamp[b], 0, S) samples and T_b = its frame count; it is framed and reflected at S_b
+// exactly as a row of S_b samples alone (samples >= S_b are never read) and its frames t >= T_b are written as zero.
+template <bool I16, bool NORMAL_FLOOR, bool LENS>
 __global__ __launch_bounds__(256, UVAD_FB_MINWAVES) void fbank_kernel(FbankArgs a, const float2 *__restrict__ tw512) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int L = a.frame_len, sh = a.frame_shift, F = a.n_mels;
@@ -66,9 +68,9 @@ __global__ __launch_bounds__(256, UVAD_FB_MINWAVES) void fbank_kernel(FbankArgs 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.y;
     const int64_t t0 = (int64_t)blockIdx.x * FR_WG;
-    const int nfr = (int)((a.T - t0) < FR_WG ? (a.T - t0) : FR_WG);
+    const int nfr_all = (int)((a.T - t0) < FR_WG ? (a.T - t0) : FR_WG);
     if (b >= a.B) {   // plane output only (the grid covers whole sequence tiles): rows of a padding sequence read as zero
-        for (int i = tid; i < nfr * a.plane_w; i += 256) {
+        for (int i = tid; i < nfr_all * a.plane_w; i += 256) {
             const size_t row = ((size_t)(b >> 2) * a.T + (size_t)(t0 + i / a.plane_w)) * SEQ_TILE + (b & 3);
             const size_t o = plane_index(row, i % a.plane_w, a.plane_w);
             a.plane_hi[o] = 0;
@@ -76,6 +78,31 @@ __global__ __launch_bounds__(256, UVAD_FB_MINWAVES) void fbank_kernel(FbankArgs 
         }
         return;
     }
+    int64_t Sb = a.S, Tb = a.T;   // (LENS) this row's samples and frames
+    if constexpr (LENS) {
+        Sb = a.nsamp[b];
+        Sb = Sb < 0 ? 0 : Sb > a.S ? a.S : Sb;
+        Tb = a.snip_edges ? (Sb < L ? 0 : 1 + (Sb - L) / sh) : (Sb + sh / 2) / sh;
+        const int64_t tz = Tb > t0 ? Tb : t0;   // frames [tz, t0 + nfr_all) of this workgroup are padding: zero rows
+        const int nz = (int)(t0 + nfr_all - tz);
+        if (nz > 0) {
+            const int wz = a.plane_hi ? a.plane_w : F;
+            for (int i = tid; i < nz * wz; i += 256) {
+                const int64_t t = tz + i / wz;
+                const int col = i % wz;
+                if (a.plane_hi) {
+                    const size_t o = plane_index(((size_t)(b >> 2) * a.T + (size_t)t) * SEQ_TILE + (b & 3), col, a.plane_w);
+                    a.plane_hi[o] = 0;
+                    a.plane_lo[o] = 0;
+                } else {
+                    a.feats[((size_t)b * a.T + t) * F + col] = 0.0f;
+                }
+            }
+        }
+        if (t0 >= Tb) return;   // workgroup-uniform, before any barrier
+    }
+    const int nfr = LENS ? (int)(Tb - t0 < nfr_all ? Tb - t0 : nfr_all) : nfr_all;
+    const int64_t S = LENS ? Sb : a.S;
     const int n_left = a.snip_edges ? 0 : (L - sh) / 2;
     const int64_t s0 = t0 * sh - n_left;
     const int need = (nfr - 1) * sh + L;
@@ -103,7 +130,7 @@ __global__ __launch_bounds__(256, UVAD_FB_MINWAVES) void fbank_kernel(FbankArgs 
     // A tile that lies wholly inside the row, on an aligned address, needs none of the per-lane range / alignment tests below: one
     // workgroup-uniform decision (scalar arithmetic) instead of four 64-bit compares per 16-byte piece.  All but the first and last
     // tiles of a row are of this kind.
-    const bool interior = !virt && s0 >= 0 && s0 + (int64_t)((need + 3) & ~3) <= a.S &&
+    const bool interior = !virt && s0 >= 0 && s0 + (int64_t)((need + 3) & ~3) <= S &&
                           ((I16 ? reinterpret_cast<uintptr_t>(reinterpret_cast<const int16_t *>(xrow) + s0) & 7
                                 : reinterpret_cast<uintptr_t>(reinterpret_cast<const float *>(xrow) + s0) & 15) == 0);
     for (int base = 0; base < need; base += ST_IT * 1024) {
@@ -114,7 +141,7 @@ __global__ __launch_bounds__(256, UVAD_FB_MINWAVES) void fbank_kernel(FbankArgs 
             const int64_t g = s0 + i;
             v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (i < need) {
-                bool fast = interior || (!virt && g >= 0 && g + 3 < a.S);
+                bool fast = interior || (!virt && g >= 0 && g + 3 < S);
                 if (I16) {
                     const int16_t *p = reinterpret_cast<const int16_t *>(xrow) + g;
                     fast = interior || (fast && (reinterpret_cast<uintptr_t>(p) & 7) == 0);
@@ -134,9 +161,9 @@ __global__ __launch_bounds__(256, UVAD_FB_MINWAVES) void fbank_kernel(FbankArgs 
                     for (int e = 0; e < 4; ++e) {
                         int64_t idx = g + e;
                         if (idx < 0) idx = -idx - 1;
-                        if (idx >= a.S) idx = 2 * a.S - 1 - idx;
+                        if (idx >= S) idx = 2 * S - 1 - idx;
                         if (idx < 0) idx = 0;
-                        if (idx >= a.S) idx = a.S - 1;
+                        if (idx >= S) idx = S - 1;
                         e4[e] = virt ? vs_abs((int)idx + a.vs_offset) : pcm_at<I16>(xrow, idx);
                     }
                     v[it] = make_float4(e4[0], e4[1], e4[2], e4[3]);
@@ -227,6 +254,21 @@ __global__ __launch_bounds__(256) void stream_stage_kernel(const float *chunk_pc
     }
 }
 
+// per-row frame counts of rows of clamp(nsamp[b], 0, S) samples (uvad_num_frames on the device): the lengths uvad_forward_lens classifies
+__global__ __launch_bounds__(256) void frames_of_kernel(const int64_t *nsamp, int B, int64_t S, int L, int sh, int snip, int *frames) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int64_t v = nsamp[b];
+    v = v < 0 ? 0 : v > S ? S : v;
+    frames[b] = (int)(snip ? (v < L ? 0 : 1 + (v - L) / sh) : (v + sh / 2) / sh);
+}
+
+hipError_t launch_frames_of(const int64_t *nsamp, int B, int64_t S, int frame_len, int frame_shift, int snip_edges, int *frames, hipStream_t s) {
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(frames_of_kernel, dim3((B + 255) / 256), dim3(256), 0, s, nsamp, B, S, frame_len, frame_shift, snip_edges, frames);
+    return hipGetLastError();
+}
+
 size_t fbank_lds_bytes(const FbankArgs &a) {
     const size_t raw_pad = (size_t)((((FR_WG - 1) * a.frame_shift + a.frame_len) + 3) & ~3);
     const size_t melw_pad = mel_image_floats(a.tab.mel_stride, a.n_mels);
@@ -253,8 +295,11 @@ hipError_t launch_fbank(const FbankArgs &a, hipStream_t s) {
     const dim3 grid((unsigned)((a.T + FR_WG - 1) / FR_WG), rows);
     const float2 *tw = reinterpret_cast<const float2 *>(a.tab.tw512);
     const bool normal_floor = a.log_floor >= 1.17549435e-38f;   // FLT_MIN
-    const void *fn = a.pcm_is_i16 ? (normal_floor ? (const void *)fbank_kernel<true, true> : (const void *)fbank_kernel<true, false>)
-                                  : (normal_floor ? (const void *)fbank_kernel<false, true> : (const void *)fbank_kernel<false, false>);
+    if (a.nsamp && a.vs_chunk) return hipErrorInvalidValue;   // per-row lengths are for whole rows, not streaming steps
+    const void *fn = a.nsamp ? (a.pcm_is_i16 ? (normal_floor ? (const void *)fbank_kernel<true, true, true> : (const void *)fbank_kernel<true, false, true>)
+                                             : (normal_floor ? (const void *)fbank_kernel<false, true, true> : (const void *)fbank_kernel<false, false, true>))
+                   : a.pcm_is_i16 ? (normal_floor ? (const void *)fbank_kernel<true, true, false> : (const void *)fbank_kernel<true, false, false>)
+                                  : (normal_floor ? (const void *)fbank_kernel<false, true, false> : (const void *)fbank_kernel<false, false, false>);
     if (lds > 48 * 1024) {
         const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;

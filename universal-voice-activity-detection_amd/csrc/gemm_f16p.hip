@@ -316,7 +316,30 @@ __global__ __launch_bounds__(256) void split_features_kernel(const float *x, int
     if (flag && __builtin_amdgcn_ballot_w64(bad) != 0 && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
 }
 
+// Canonical f32 features [B][T][F] -> the same with the frames t >= len_b = clamp(lens[b], 0, T) of every row written as zero and NEVER
+// read (uvad_classify_lens): the split, its range check and the exact-f32 projection then see zero padding, so whatever the caller left
+// there (NaN, 1e30) cannot reach a valid row or the device flag.
+__global__ __launch_bounds__(256) void mask_features_kernel(const float *x, int B, int T, int F, const int *lens, float *out) {
+    const long long n = (long long)B * T * F;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const long long bt = i / F;
+        const int b = (int)(bt / T), t = (int)(bt - (long long)b * T);
+        const int v = lens[b], len = v < 0 ? 0 : v > T ? T : v;
+        out[i] = t < len ? x[i] : 0.0f;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_mask_features(const float *x, int B, int T, int F, const int *lens, float *out, hipStream_t s) {
+    const long long n = (long long)B * T * F;
+    if (n <= 0) return hipSuccess;
+    if (!lens) return hipErrorInvalidValue;
+    const long long want = (n + 255) / 256;
+    const int grid = (int)(want > 4096 ? 4096 : want);
+    hipLaunchKernelGGL(mask_features_kernel, dim3(grid), dim3(256), 0, s, x, B, T, F, lens, out);
+    return hipGetLastError();
+}
 
 int gemm_f16p_padded_k(int K) { return (K + 31) / 32 * 32; }
 

@@ -154,6 +154,71 @@ __global__ __launch_bounds__(256) void runs_kernel(const uint8_t *labels, int B,
     }
 }
 
+// ---- per-row lengths (the *_lens entry points): row b is valid at frames t < len_b = clamp(lens[b], 0, T) --------------------------
+__device__ __forceinline__ int row_len(const int *lens, int b, int T) {
+    const int v = lens[b];
+    return v < 0 ? 0 : v > T ? T : v;
+}
+
+// outputs [B][ld] at frames len_b <= t < T written as exactly 0 (the classifier kernels wrote every frame; their padding values are not
+// results).  Either pointer may be nullptr.
+__global__ __launch_bounds__(256) void lens_fill_kernel(float *logits, float *probs, int B, int T, int ld, const int *lens) {
+    const long long n = (long long)B * T;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / T), t = (int)(i - (long long)b * T);
+        if (t < row_len(lens, b, T)) continue;
+        const size_t o = (size_t)b * ld + t;
+        if (logits) logits[o] = 0.0f;
+        if (probs) probs[o] = 0.0f;
+    }
+}
+
+// median_kernel on the prefix [0, len_b) of every row (zero padded at both of ITS ends, as scipy medfilt of the prefix alone); labels at
+// t >= len_b are 0 and probabilities there are never read
+__global__ __launch_bounds__(256) void median_lens_kernel(const float *probs, int B, int T, int half, uint8_t *labels, const int *lens) {
+    const long long n = (long long)B * T;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int t = (int)(i % T), b = (int)(i / T);
+    const int Tb = row_len(lens, b, T);
+    const float *p = probs + (i - t);
+    int ones = 0;
+    if (t < Tb)
+        for (int d = -half; d <= half; ++d) {
+            const int u = t + d;
+            if (u >= 0 && u < Tb) ones += !(p[u] < 0.5f);
+        }
+    labels[i] = ones > half ? 1 : 0;
+}
+
+// runs_kernel on the prefix [0, len_b) of every row (row stride T): a run open at the end closes at len_b, never later
+__global__ __launch_bounds__(256) void runs_lens_kernel(const uint8_t *labels, int B, int T, int max_runs, int *runs, int *counts, const int *lens) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.x * 4 + wave;
+    if (b >= B) return;
+    const int Tb = row_len(lens, b, T);
+    const uint8_t *p = labels + (size_t)b * T;
+    int *r = runs + (size_t)b * max_runs * 2;
+    const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    int n_start = 0, n_stop = 0;
+    for (int t0 = 0; t0 < Tb; t0 += 64) {
+        const int t = t0 + lane;
+        const bool in = t < Tb;
+        const unsigned cur = in ? (p[t] & 1u) : 0u;
+        const unsigned prev = (in && t > 0) ? (p[t - 1] & 1u) : 0u;
+        const bool is_start = in && cur && !prev, is_stop = in && !cur && prev;
+        const unsigned long long ms = __ballot(is_start), me = __ballot(is_stop);
+        if (is_start) { const int i = n_start + __popcll(ms & below); if (i < max_runs) r[2 * i] = t; }
+        if (is_stop) { const int i = n_stop + __popcll(me & below); if (i < max_runs) r[2 * i + 1] = t; }
+        n_start += __popcll(ms);
+        n_stop += __popcll(me);
+    }
+    if (lane == 0) {
+        if (n_start > n_stop && n_stop < max_runs) r[2 * n_stop + 1] = Tb;
+        counts[b] = n_start;
+    }
+}
+
 // busy-waits `ticks` of the constant 100 MHz counter (s_memrealtime), one wave: the stream-overlap probe's "long" kernel
 __global__ __launch_bounds__(256) void zero_counters_kernel(unsigned *p, int n) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) atomicExch(p + i, 0u);
@@ -209,6 +274,31 @@ hipError_t launch_median(const float *probs, int B, int T, int kernel, uint8_t *
     const long long n = (long long)B * T;
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(median_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, s, probs, B, T, kernel / 2, labels);
+    return hipGetLastError();
+}
+
+hipError_t launch_lens_fill(float *logits, float *probs, int B, int T, int ld, const int *lens, hipStream_t s) {
+    const long long n = (long long)B * T;
+    if (n <= 0 || (!logits && !probs)) return hipSuccess;
+    if (!lens || ld < T) return hipErrorInvalidValue;
+    long long g = (n + 255) / 256;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(lens_fill_kernel, dim3((int)g), dim3(256), 0, s, logits, probs, B, T, ld, lens);
+    return hipGetLastError();
+}
+
+hipError_t launch_median_lens(const float *probs, int B, int T, int kernel, uint8_t *labels, const int *lens, hipStream_t s) {
+    const long long n = (long long)B * T;
+    if (n <= 0) return hipSuccess;
+    if (!lens) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(median_lens_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, s, probs, B, T, kernel / 2, labels, lens);
+    return hipGetLastError();
+}
+
+hipError_t launch_runs_lens(const uint8_t *labels, int B, int T, int max_runs, int *runs, int *counts, const int *lens, hipStream_t s) {
+    if (B <= 0 || T <= 0) return hipSuccess;
+    if (!lens) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(runs_lens_kernel, dim3((B + 3) / 4), dim3(256), 0, s, labels, B, T, max_runs, runs, counts, lens);
     return hipGetLastError();
 }
 

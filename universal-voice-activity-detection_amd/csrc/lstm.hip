@@ -108,7 +108,17 @@ __device__ __forceinline__ void store_planes(unsigned short *ph, unsigned short 
     *pl = __builtin_bit_cast(unsigned short, hl);
 }
 
-template <int H, int WAVES, bool PLANES>
+// Per-row lengths (LENS, LstmArgs::lens): the forms below read the lengths of their sequences (clamped to [0, T]; sequences past B have
+// length 0) and run tmax = the longest of them steps instead of T, the forward direction over frames 0 .. tmax - 1, the backward one from
+// tmax - 1 down.  Backward lanes whose sequence has t >= its length force (h, c) to +0 by a SELECT after the cell update, so whatever the
+// padding gates hold (stale rows, NaN) never leaks, and step len - 1 starts from exactly the zero state a dense call of T = len starts from.
+// The forward direction is causal and needs no mask (its outputs past the length are padding).  Rows at t >= tmax are not written.
+__device__ __forceinline__ int lens_at(const LstmArgs &a, int b) {
+    const int v = b < a.nB ? a.lens[b] : 0;
+    return v < 0 ? 0 : v > a.T ? a.T : v;
+}
+
+template <int H, int WAVES, bool PLANES, bool LENS>
 __global__ __launch_bounds__(WAVES * 64) void lstm_rec_kernel(LstmArgs a) {
     constexpr int HS = H + 4;   // LDS row stride (floats): the 4 sequence rows land on disjoint banks
     constexpr int PD = UVAD_LSTM_PD;
@@ -122,6 +132,12 @@ __global__ __launch_bounds__(WAVES * 64) void lstm_rec_kernel(LstmArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int jb = lane & 3;    // sequence within the tile (B / D operand column), gate index of the A operand
     const int blk = lane >> 2;  // MFMA block = hidden unit within the wave's row block
+    int tmax = 0, lim = 0;      // (LENS) steps of this workgroup; frames t >= lim of this lane's sequence are reset (backward only)
+    if constexpr (LENS) {
+#pragma unroll
+        for (int i = 0; i < SEQ_TILE; ++i) tmax = max(tmax, lens_at(a, tile * SEQ_TILE + i));
+        lim = reverse ? lens_at(a, tile * SEQ_TILE + jb) : 0x7fffffff;   // (tmax = 0: no step runs, the prefetch reads row 0)
+    }
 
     // ---- resident recurrent weights -------------------------------------------------------
     float w[H];
@@ -162,12 +178,12 @@ __global__ __launch_bounds__(WAVES * 64) void lstm_rec_kernel(LstmArgs a) {
     const size_t y_tile = (size_t)(a.ldy / 16) * (PLANE_TILE * 16);   // elements per 128-row tile of a Y plane
 
     // the steps of this launch: all T frames, or a chunk of them continuing from the carried state (LstmArgs::steps)
-    const int nst = a.steps > 0 ? a.steps : a.T;
-    const int t_lo = a.steps > 0 ? a.t_begin[dir] : 0;
+    const int nst = LENS ? tmax : a.steps > 0 ? a.steps : a.T;
+    const int t_lo = !LENS && a.steps > 0 ? a.t_begin[dir] : 0;
     auto t_of = [&](int s) { return reverse ? t_lo + nst - 1 - s : t_lo + s; };
     f32x4 gq[PD];
 #pragma unroll
-    for (int p = 0; p < PD; ++p) gq_load(gq[p], g_ptr(t_of(p < nst ? p : nst - 1)));
+    for (int p = 0; p < PD; ++p) gq_load(gq[p], g_ptr(t_of(p < nst ? p : (LENS && nst == 0 ? 0 : nst - 1))));
 
     float hlast = 0.0f;
 
@@ -222,7 +238,13 @@ __global__ __launch_bounds__(WAVES * 64) void lstm_rec_kernel(LstmArgs a) {
         }
         __builtin_amdgcn_sched_group_barrier(0x008, 4 * HR, 0);
         hlast = lstm_cell((a0 + a1) + (a2 + a3), c);
-        hbuf[(s + 1) & 1][jb][unit] = hlast;
+        if constexpr (LENS) {   // the reset acts on the carried state only: the output row of a padding frame is padding
+            const bool pad = t >= lim;
+            c = pad ? 0.0f : c;
+            hbuf[(s + 1) & 1][jb][unit] = pad ? 0.0f : hlast;
+        } else {
+            hbuf[(s + 1) & 1][jb][unit] = hlast;
+        }
         if constexpr (PLANES) {
             // K-blocked plane (uvad_internal.h plane_index): the 4 sequence rows x 16 units of a wave are 128 contiguous bytes
             const size_t R = rowu + (size_t)t * SEQ_TILE;
@@ -277,7 +299,7 @@ using i32x8 = __attribute__((ext_vector_type(8))) int;
 // replaces the four f16 MFMAs of a row block (64 cycles): 896 instead of 1 024 matrix cycles per wave and step, the P2 image 64 instead of
 // 128 KiB.  The k order of that product is the kernel's own: byte 16 w + 4 q + rb of a sequence's fp8 row is unit 16 w + 4 rb + q, so the
 // four cells a lane updates are one aligned dword of the image (one ds_write_b32); the host packs P2's columns in the same order.
-template <bool PLANES, int NPROD, bool P2Q>
+template <bool PLANES, int NPROD, bool P2Q, bool LENS>
 __global__ __launch_bounds__(512) void lstm_rec16h_kernel(LstmArgs a) {
     constexpr int H = 128, RB = 4, KST = 4;
     static_assert(!P2Q || NPROD == 4, "the fp8 form of the P2 product exists for four products only");
@@ -290,6 +312,13 @@ __global__ __launch_bounds__(512) void lstm_rec16h_kernel(LstmArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int j = lane & 15, q = lane >> 4;
+    int tmax = 0, lim = 0;   // (LENS) steps of this workgroup; frames t >= lim of this lane's sequence are reset (backward only)
+    if constexpr (LENS) {
+        for (int i = 0; i < 16; ++i) tmax = max(tmax, lens_at(a, tile16 * 16 + i));
+        if (tmax == 0) return;   // workgroup-uniform, before any barrier
+        lim = reverse ? lens_at(a, tile16 * 16 + j) : 0x7fffffff;
+    }
+    const int nst = LENS ? tmax : a.T;
 
     // ---- resident P0 / P1: register r = ((plane * 16 + rb * 4 + ks) * 4 + v) holds elements 2v, 2v+1 of that fragment
     u32x4 w[32];   // fragment (plane, rb, ks) = w[plane * 16 + rb * 4 + ks]: one aligned 4-register tuple each
@@ -325,7 +354,7 @@ __global__ __launch_bounds__(512) void lstm_rec16h_kernel(LstmArgs a) {
     const float wscale = a.whh16h_scale[dir];
     // Row pointers are stepped, not recomputed (the kernel is bound by vector-instruction issue): a step moves 4 rows inside a
     // 128-row tile of the blocked layouts (g_index / plane_index) or, on a wrap, to the neighbouring tile.
-    const int sgn = reverse ? -1 : 1, t_first = reverse ? a.T - 1 : 0;
+    const int sgn = reverse ? -1 : 1, t_first = reverse ? nst - 1 : 0;
     const int g_in = 4 * 64 * sgn, g_wrap = ((int)g_tile - 124 * 64) * sgn;
     const int y_in = 4 * 16 * sgn, y_wrap = ((int)y_tile - 124 * 16) * sgn;
     auto advance = [&](auto *&ptr, int &rl, int d_in, int d_wrap) {
@@ -386,12 +415,12 @@ __global__ __launch_bounds__(512) void lstm_rec16h_kernel(LstmArgs a) {
     const int hfrag = j * R16_HP + 8 * q;                                   // + 32 ks inside a plane
     const int hq_rd = j * R16_HQ + 32 * q, hq_wr = j * R16_HQ + 16 * wave + 4 * q;   // (P2Q) this lane's B fragment / the dword of its four cells
     const int p2q_scale = P2Q ? a.p2q_scale : 127;
-    for (int s = 0; s < a.T; ++s) {
-        const int t = reverse ? a.T - 1 - s : s;
+    for (int s = 0; s < nst; ++s) {
+        const int t = reverse ? nst - 1 - s : s;
 #pragma unroll
         for (int k = 0; k < 32; ++k) asm volatile("" : "+a"(w[k]));   // P0 / P1 stay in AGPRs (constraint only)
 
-        if (s + 1 < a.T) advance(g_p, g_rl, g_in, g_wrap);   // the gates of the next step (the last step re-reads its own)
+        if (s + 1 < nst) advance(g_p, g_rl, g_in, g_wrap);   // the gates of the next step (the last step re-reads its own)
         const float *gnext = g_p;
         const unsigned short *hcur = hb + (s & 1) * (2 * 16 * R16_HP);
         unsigned short *hnxt = hb + ((s + 1) & 1) * (2 * 16 * R16_HP);
@@ -447,6 +476,11 @@ __global__ __launch_bounds__(512) void lstm_rec16h_kernel(LstmArgs a) {
                                                  f32x4{wscale, wscale, wscale, wscale}, gq[rb]);
             gq[rb] = *reinterpret_cast<const f32x4 *>(gnext + 16 * rb);   // next step's gates of this row block: a whole step to arrive
             lstm_cell1(gpre[rb], c[rb], hnew[rb]);   // behind its own row block's MFMAs: overlaps the next row block's, one cell exposed at the end
+            if constexpr (LENS) {
+                const bool pad = t >= lim;
+                c[rb] = pad ? 0.0f : c[rb];
+                hnew[rb] = pad ? 0.0f : hnew[rb];
+            }
         }
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
@@ -469,7 +503,7 @@ __global__ __launch_bounds__(512) void lstm_rec16h_kernel(LstmArgs a) {
         if (s > 0) coop_store(hcur, true);
         __syncthreads();
     }
-    if (a.T > 0) coop_store(hb + (a.T & 1) * (2 * 16 * R16_HP), false);
+    if (nst > 0) coop_store(hb + (nst & 1) * (2 * 16 * R16_HP), false);
 }
 
 
@@ -480,7 +514,7 @@ __global__ __launch_bounds__(512) void lstm_rec16h_kernel(LstmArgs a) {
 // torch CPU / the oracle's row dot product has), W_hh rows (torch layout [4H][H]) streamed from L2 every step, h_{t-1} broadcast from
 // LDS.  Slow by design -- the weight matrix crosses the CU once per step -- and exact f32; it exists so that no constructor argument of
 // the reference is refused, the fast forms are the H = 128 / 64 kernels above.
-template <bool PLANES>
+template <bool PLANES, bool LENS>
 __global__ __launch_bounds__(256) void lstm_rec_any_kernel(LstmArgs a) {
     constexpr int MAXU = 4;
     extern __shared__ __attribute__((aligned(16))) float hs[];   // [2][SEQ_TILE][HS]
@@ -489,8 +523,20 @@ __global__ __launch_bounds__(256) void lstm_rec_any_kernel(LstmArgs a) {
     const bool reverse = dir == 1;
     const int nseq = a.tiles * SEQ_TILE;
     const float *W = a.Whh_packed + (size_t)dir * 4 * H * H;     // this form reads the plain torch matrix
-    const int nst = a.steps > 0 ? a.steps : a.T;
-    const int t_lo = a.steps > 0 ? a.t_begin[dir] : 0;
+    int nst = a.steps > 0 ? a.steps : a.T;
+    const int t_lo = !LENS && a.steps > 0 ? a.t_begin[dir] : 0;
+    int lim[SEQ_TILE];   // (LENS) frames t >= lim[j] of sequence j are reset (backward only)
+    if constexpr (LENS) {
+        int tmax = 0;
+#pragma unroll
+        for (int j = 0; j < SEQ_TILE; ++j) {
+            const int l = lens_at(a, tile * SEQ_TILE + j);
+            tmax = max(tmax, l);
+            lim[j] = reverse ? l : 0x7fffffff;
+        }
+        if (tmax == 0) return;   // workgroup-uniform, before any barrier
+        nst = tmax;
+    }
     float c[MAXU][SEQ_TILE], hl[MAXU][SEQ_TILE];
 #pragma unroll
     for (int i = 0; i < MAXU; ++i) {
@@ -539,7 +585,13 @@ __global__ __launch_bounds__(256) void lstm_rec_any_kernel(LstmArgs a) {
             for (int j = 0; j < SEQ_TILE; ++j) {
                 const float h = lstm_cell(f32x4{acc[0][j], acc[1][j], acc[2][j], acc[3][j]}, c[i][j]);
                 hl[i][j] = h;
-                hn[j * HS + u] = h;
+                if constexpr (LENS) {   // the reset acts on the carried state only: the output row of a padding frame is padding
+                    const bool pad = t >= lim[j];
+                    c[i][j] = pad ? 0.0f : c[i][j];
+                    hn[j * HS + u] = pad ? 0.0f : h;
+                } else {
+                    hn[j * HS + u] = h;
+                }
                 const size_t row = rowu + (size_t)t * SEQ_TILE + j;
                 if constexpr (PLANES) {
                     const size_t yo = plane_index(row, dir * H + u, a.ldy);
@@ -709,6 +761,7 @@ int lstm_auto_tile(int tiles, int dirs, int H, int n_cu) {
 hipError_t launch_lstm(const LstmArgs &a, hipStream_t s, int *tile_used) {
     if (tile_used) *tile_used = 0;
     if (a.tiles <= 0 || a.T <= 0) return hipSuccess;
+    if (a.lens && (a.steps > 0 || a.h0 || a.c0 || a.hN || a.cN)) return hipErrorInvalidValue;   // per-row lengths: whole sequences from zero state
     if (a.H != 128 && a.H != 64) {   // no register-resident form: the generic kernel (plain torch W_hh in Whh_packed)
         if (a.H < 4 || a.H % 4 || a.H > 1024 || a.tile_mode == 16 || !a.Whh_packed) return hipErrorInvalidValue;
         if (tile_used) *tile_used = 4;
@@ -716,9 +769,11 @@ hipError_t launch_lstm(const LstmArgs &a, hipStream_t s, int *tile_used) {
         const dim3 grid(a.tiles, a.dirs);
         if (a.Y == nullptr) {
             if (!a.Yh || !a.Yl) return hipErrorInvalidValue;
-            hipLaunchKernelGGL((lstm_rec_any_kernel<true>), grid, dim3(256), lds, s, a);
+            if (a.lens) hipLaunchKernelGGL((lstm_rec_any_kernel<true, true>), grid, dim3(256), lds, s, a);
+            else hipLaunchKernelGGL((lstm_rec_any_kernel<true, false>), grid, dim3(256), lds, s, a);
         } else {
-            hipLaunchKernelGGL((lstm_rec_any_kernel<false>), grid, dim3(256), lds, s, a);
+            if (a.lens) hipLaunchKernelGGL((lstm_rec_any_kernel<false, true>), grid, dim3(256), lds, s, a);
+            else hipLaunchKernelGGL((lstm_rec_any_kernel<false, false>), grid, dim3(256), lds, s, a);
         }
         return hipGetLastError();
     }
@@ -738,10 +793,14 @@ hipError_t launch_lstm(const LstmArgs &a, hipStream_t s, int *tile_used) {
         const bool q8 = !three && a.Whh16h_p2q != nullptr;   // the P2 product on the 8-bit matrix pipe (weights verified exact as bf8)
         // 145 KiB with the f16 P2 image, 86 with the bf8 one, 17 without: one workgroup per CU either way (registers)
         const size_t lds = (size_t)((three ? 0 : q8 ? R16_P2Q_ELEMS : R16_P2_ELEMS) + R16_HB_ELEMS + (q8 ? R16_HQ_ELEMS : 0)) * sizeof(unsigned short);
-        const void *fn = planes ? (three ? reinterpret_cast<const void *>(lstm_rec16h_kernel<true, 3, false>)
-                                         : q8 ? reinterpret_cast<const void *>(lstm_rec16h_kernel<true, 4, true>) : reinterpret_cast<const void *>(lstm_rec16h_kernel<true, 4, false>))
-                                : (three ? reinterpret_cast<const void *>(lstm_rec16h_kernel<false, 3, false>)
-                                         : q8 ? reinterpret_cast<const void *>(lstm_rec16h_kernel<false, 4, true>) : reinterpret_cast<const void *>(lstm_rec16h_kernel<false, 4, false>));
+        const void *fn = a.lens ? (planes ? (three ? reinterpret_cast<const void *>(lstm_rec16h_kernel<true, 3, false, true>)
+                                                   : q8 ? reinterpret_cast<const void *>(lstm_rec16h_kernel<true, 4, true, true>) : reinterpret_cast<const void *>(lstm_rec16h_kernel<true, 4, false, true>))
+                                          : (three ? reinterpret_cast<const void *>(lstm_rec16h_kernel<false, 3, false, true>)
+                                                   : q8 ? reinterpret_cast<const void *>(lstm_rec16h_kernel<false, 4, true, true>) : reinterpret_cast<const void *>(lstm_rec16h_kernel<false, 4, false, true>)))
+                       : planes ? (three ? reinterpret_cast<const void *>(lstm_rec16h_kernel<true, 3, false, false>)
+                                         : q8 ? reinterpret_cast<const void *>(lstm_rec16h_kernel<true, 4, true, false>) : reinterpret_cast<const void *>(lstm_rec16h_kernel<true, 4, false, false>))
+                                : (three ? reinterpret_cast<const void *>(lstm_rec16h_kernel<false, 3, false, false>)
+                                         : q8 ? reinterpret_cast<const void *>(lstm_rec16h_kernel<false, 4, true, false>) : reinterpret_cast<const void *>(lstm_rec16h_kernel<false, 4, false, false>));
         {   // the attribute belongs to the (function, device) pair and a process may own contexts on several GPUs (include/uvad.h), so it
             // is set for the CURRENT device on every launch (as launch_fbank / launch_sinc_conv do; no process-global "done" flag)
             const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -755,14 +814,25 @@ hipError_t launch_lstm(const LstmArgs &a, hipStream_t s, int *tile_used) {
     }
     if (tile_used) *tile_used = 4;
     const dim3 grid(a.tiles, a.dirs);
+    if (a.lens) {
+        if (a.H == 128 && planes)
+            hipLaunchKernelGGL((lstm_rec_kernel<128, 8, true, true>), grid, dim3(512), 0, s, a);
+        else if (a.H == 128)
+            hipLaunchKernelGGL((lstm_rec_kernel<128, 8, false, true>), grid, dim3(512), 0, s, a);
+        else if (planes)
+            hipLaunchKernelGGL((lstm_rec_kernel<64, 4, true, true>), grid, dim3(256), 0, s, a);
+        else
+            hipLaunchKernelGGL((lstm_rec_kernel<64, 4, false, true>), grid, dim3(256), 0, s, a);
+        return hipGetLastError();
+    }
     if (a.H == 128 && planes)
-        hipLaunchKernelGGL((lstm_rec_kernel<128, 8, true>), grid, dim3(512), 0, s, a);
+        hipLaunchKernelGGL((lstm_rec_kernel<128, 8, true, false>), grid, dim3(512), 0, s, a);
     else if (a.H == 128)
-        hipLaunchKernelGGL((lstm_rec_kernel<128, 8, false>), grid, dim3(512), 0, s, a);
+        hipLaunchKernelGGL((lstm_rec_kernel<128, 8, false, false>), grid, dim3(512), 0, s, a);
     else if (a.H == 64 && planes)
-        hipLaunchKernelGGL((lstm_rec_kernel<64, 4, true>), grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL((lstm_rec_kernel<64, 4, true, false>), grid, dim3(256), 0, s, a);
     else if (a.H == 64)
-        hipLaunchKernelGGL((lstm_rec_kernel<64, 4, false>), grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL((lstm_rec_kernel<64, 4, false, false>), grid, dim3(256), 0, s, a);
     else
         return hipErrorInvalidValue;
     return hipGetLastError();

@@ -876,7 +876,7 @@ int uvad_sincnet_i16(uvad_ctx *c, const int16_t *d_wav, int B, int64_t S, float 
 
 static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float *d_logits, float *d_probs,
                          void *ws, size_t ws_bytes, hipStream_t s, bool record_start, bool check_range,
-                         const StreamState *ss, int ld_out, bool feats_in_planes, const FbankArgs *fused_fb);
+                         const StreamState *ss, int ld_out, bool feats_in_planes, const FbankArgs *fused_fb, const int *lens = nullptr);
 
 static int forward_wav_impl(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64_t S, float *d_logits, float *d_probs,
                             void *ws, size_t ws_bytes, void *stream) {
@@ -920,7 +920,7 @@ size_t uvad_workspace_bytes(const uvad_ctx *c, int B, int64_t T) {
 }
 
 static int fbank_impl(uvad_ctx *c, const void *d_pcm, int is_i16, int B, int64_t S, float *d_feats, void *stream,
-                      unsigned short *plane_hi = nullptr, unsigned short *plane_lo = nullptr, int plane_w = 0) {
+                      unsigned short *plane_hi = nullptr, unsigned short *plane_lo = nullptr, int plane_w = 0, const int64_t *nsamp = nullptr) {
     if (!c || !d_pcm || (!d_feats && !plane_hi) || B <= 0 || S <= 0) return fail(c, UVAD_E_ARG, "uvad_fbank: bad argument");
     if (!c->has_fb || !c->tables_set) return fail(c, UVAD_E_STATE, "uvad_fbank: uvad_set_tables has not been called");
     const int64_t T = uvad_num_frames(c, S);
@@ -931,7 +931,7 @@ static int fbank_impl(uvad_ctx *c, const void *d_pcm, int is_i16, int B, int64_t
     a.pcm = d_pcm; a.pcm_is_i16 = is_i16; a.B = B; a.S = S; a.T = T;
     a.frame_len = c->fb.frame_len; a.frame_shift = c->fb.frame_shift; a.n_mels = c->fb.n_mels;
     a.preemph = c->fb.preemph; a.log_floor = c->fb.log_floor; a.remove_dc = c->fb.remove_dc; a.snip_edges = c->fb.snip_edges;
-    a.feats = d_feats; a.plane_hi = plane_hi; a.plane_lo = plane_lo; a.plane_w = plane_w;
+    a.feats = d_feats; a.plane_hi = plane_hi; a.plane_lo = plane_lo; a.plane_w = plane_w; a.nsamp = nsamp;
     a.tab.window = c->d_window; a.tab.mel_start = c->d_mel_start; a.tab.mel_len = c->d_mel_len;
     a.tab.mel_w = c->d_mel_w; a.tab.mel_wt = c->d_mel_wt; a.tab.mel_stride = c->mel_stride; a.tab.tw512 = c->d_tw512; a.tab.nyquist = c->mel_nyquist;
     HIPCHK(c, launch_fbank(a, (hipStream_t)stream));
@@ -943,6 +943,17 @@ int uvad_fbank(uvad_ctx *c, const float *d_pcm, int B, int64_t S, float *d_feats
 }
 int uvad_fbank_i16(uvad_ctx *c, const int16_t *d_pcm, int B, int64_t S, float *d_feats, void *stream) {
     return fbank_impl(c, d_pcm, 1, B, S, d_feats, stream);
+}
+static int fbank_lens_entry(uvad_ctx *c, const void *d_pcm, int is_i16, int B, int64_t S, const int64_t *d_nsamp, float *d_feats, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_nsamp) return fail(c, UVAD_E_ARG, "uvad_fbank_lens: d_nsamp is NULL");
+    return fbank_impl(c, d_pcm, is_i16, B, S, d_feats, stream, nullptr, nullptr, 0, d_nsamp);
+}
+int uvad_fbank_lens(uvad_ctx *c, const float *d_pcm, int B, int64_t S, const int64_t *d_nsamp, float *d_feats, void *stream) {
+    return fbank_lens_entry(c, d_pcm, 0, B, S, d_nsamp, d_feats, stream);
+}
+int uvad_fbank_lens_i16(uvad_ctx *c, const int16_t *d_pcm, int B, int64_t S, const int64_t *d_nsamp, float *d_feats, void *stream) {
+    return fbank_lens_entry(c, d_pcm, 1, B, S, d_nsamp, d_feats, stream);
 }
 
 // The feed-forward layers one GEMM each (leaky_relu epilogue): workspace buffers Y[last] -> Z[0] -> Z[1] ...; the last one f32.
@@ -1147,9 +1158,12 @@ static int auto_time_chunks(int T, int tiles, int D, int n_cu) {
 // check_range: the features come from the caller (or from a front end with learnable scales) and may lie outside the f16
 // range; the split-f16 layer-0 projection is then replaced by the exact-f32 one ON THE DEVICE (both are enqueued, a flag
 // written by range_flag_kernel lets exactly one of them run), so the call stays asynchronous and capturable.
+// lens (uvad_classify_lens / uvad_forward_lens): device int32 [B] frame counts.  The recurrences run the lens forms (per-workgroup step
+// count, backward reset past each length), time chunks are off, and the outputs at t >= len_b are set to 0 after the head.  Rows past a
+// length carry padding values through the row-independent GEMMs and are never read by a valid row.
 static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float *d_logits, float *d_probs,
                          void *ws, size_t ws_bytes, hipStream_t s, bool record_start, bool check_range,
-                         const StreamState *ss, int ld_out, bool feats_in_planes, const FbankArgs *fused_fb) {
+                         const StreamState *ss, int ld_out, bool feats_in_planes, const FbankArgs *fused_fb, const int *lens) {
     const uvad_model_cfg &m = c->mc;
     const WsLayout w = carve(c, B, T);
     if (ws_bytes < w.total) return fail(c, UVAD_E_WORKSPACE, "workspace too small: need " + std::to_string(w.total) + " bytes");
@@ -1206,7 +1220,7 @@ static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float 
     // time chunks (see above): only for the 4-sequence recurrence on the weight-stationary split-f16 projections, never for streaming steps
     int NC = 1;
     const ChunkPlan *plan = nullptr;
-    if (!ss && !use_stack && f16 && mode_is_ws(c) && c->chunk_mode != 1 && (H == 128 || H == 64) &&
+    if (!ss && !use_stack && !lens && f16 && mode_is_ws(c) && c->chunk_mode != 1 && (H == 128 || H == 64) &&
         (c->rec_tile_mode ? c->rec_tile_mode : lstm_auto_tile(w.tiles, D, H, c->n_cu)) == 4) {
         int want = c->chunk_mode > 1 ? std::min(c->chunk_mode, T) : auto_time_chunks(T, w.tiles, D, c->n_cu);
         const long mt = (long)((w.M + 127) / 128);
@@ -1300,6 +1314,7 @@ static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float 
         else r.Y = Yf(k & 1);
         r.tiles = w.tiles; r.T = T; r.H = H; r.dirs = D; r.tile_mode = ss ? 4 : c->rec_tile_mode; r.n_cu = c->n_cu;
         r.products = f16 ? mode_products(c) : 4;
+        r.lens = lens; r.nB = B;
         if (ss) {   // carried (h, c) of this layer, updated in place
             r.h0 = r.hN = ss->h + (size_t)k * ss->layer_stride;
             r.c0 = r.cN = ss->c + (size_t)k * ss->layer_stride;
@@ -1321,6 +1336,7 @@ static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float 
         h.counter = reinterpret_cast<unsigned *>(base + w.off_ctr);
         h.products = mode_products(c);
         HIPCHK(c, launch_head_fused(h, c->n_cu, s));
+        if (lens) HIPCHK(c, launch_lens_fill(d_logits, d_probs, B, T, h.ld_out, lens, s));
         if (c->timing) {
             HIPCHK(c, hipEventRecord(c->ev[3], s));
             c->ev_valid = true;
@@ -1335,6 +1351,7 @@ static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float 
     q.Z = cur; q.ldz = curw; q.K = curw; q.w = c->cls_w; q.b = c->cls_b; q.logits = d_logits; q.probs = d_probs;
     q.tiles = w.tiles; q.T = T; q.B = B; q.ld_out = ld_out > 0 ? ld_out : T;
     HIPCHK(c, launch_classifier(q, s));
+    if (lens) HIPCHK(c, launch_lens_fill(d_logits, d_probs, B, T, q.ld_out, lens, s));
     if (c->timing) {
         HIPCHK(c, hipEventRecord(c->ev[3], s));
         c->ev_valid = true;
@@ -1351,8 +1368,26 @@ int uvad_classify(uvad_ctx *c, const float *d_feats, int B, int T, float *d_logi
     return classify_impl(c, d_feats, B, T, d_logits, d_probs, ws, ws_bytes, (hipStream_t)stream, true, true, nullptr, 0, false, nullptr);
 }
 
+int uvad_classify_lens(uvad_ctx *c, const float *d_feats, int B, int T, const int32_t *d_lens, float *d_logits, float *d_probs,
+                       void *ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_feats || B <= 0 || T <= 0 || !ws) return fail(c, UVAD_E_ARG, "uvad_classify_lens: bad argument");
+    if (!d_lens) return fail(c, UVAD_E_ARG, "uvad_classify_lens: d_lens is NULL");
+    if (!c->finalized) return fail(c, UVAD_E_STATE, "uvad_classify_lens: uvad_finalize has not been called");
+    const WsLayout w = carve(c, B, T);
+    if (ws_bytes < w.total) return fail(c, UVAD_E_WORKSPACE, "workspace too small: need " + std::to_string(w.total) + " bytes");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->timing) HIPCHK(c, hipEventRecord(c->ev[0], s));
+    // the caller's padding frames are never read: the classifier runs on a copy whose padding is zero (split, range check and the exact
+    // projection all read that copy)
+    float *masked = reinterpret_cast<float *>(reinterpret_cast<char *>(ws) + w.off_feats);
+    HIPCHK(c, launch_mask_features(d_feats, B, T, c->mc.in_dim, d_lens, masked, s));
+    return classify_impl(c, masked, B, T, d_logits, d_probs, ws, ws_bytes, s, false, true, nullptr, 0, false, nullptr, d_lens);
+}
+
 static int forward_impl(uvad_ctx *c, const void *d_pcm, int is_i16, int B, int64_t S, float *d_logits, float *d_probs,
-                        void *ws, size_t ws_bytes, void *stream) {
+                        void *ws, size_t ws_bytes, void *stream, const int64_t *nsamp = nullptr) {
     if (!c) return UVAD_E_ARG;
     if (!d_pcm || B <= 0 || S <= 0 || !ws) return fail(c, UVAD_E_ARG, "uvad_forward: bad argument");
     if (!c->finalized) return fail(c, UVAD_E_STATE, "uvad_forward: uvad_finalize has not been called");
@@ -1370,10 +1405,15 @@ static int forward_impl(uvad_ctx *c, const void *d_pcm, int is_i16, int B, int64
     // the f32 feature tensor never exists; exact-f32 mode: f32 features.  (log-mel values are within +-90: no range check.)
     const bool planes = c->gemm_mode >= 1 && c->f16_ok;
     unsigned short *ph = reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(ws) + w.off_fplanes);
-    int r = planes ? fbank_impl(c, d_pcm, is_i16, B, S, nullptr, stream, ph, ph + plane_rows(w.M) * (size_t)w.Fp, w.Fp)
-                   : fbank_impl(c, d_pcm, is_i16, B, S, feats, stream);
+    int r = planes ? fbank_impl(c, d_pcm, is_i16, B, S, nullptr, stream, ph, ph + plane_rows(w.M) * (size_t)w.Fp, w.Fp, nsamp)
+                   : fbank_impl(c, d_pcm, is_i16, B, S, feats, stream, nullptr, nullptr, 0, nsamp);
     if (r) return r;
-    return classify_impl(c, feats, B, (int)T, d_logits, d_probs, ws, ws_bytes, s, false, false, nullptr, 0, planes, nullptr);
+    int *lens = nullptr;
+    if (nsamp) {   // frame counts of the rows, in the workspace of the time chunks' carried state (a lens call runs unchunked)
+        lens = reinterpret_cast<int *>(reinterpret_cast<char *>(ws) + w.off_hc);
+        HIPCHK(c, launch_frames_of(nsamp, B, S, c->fb.frame_len, c->fb.frame_shift, c->fb.snip_edges, lens, s));
+    }
+    return classify_impl(c, feats, B, (int)T, d_logits, d_probs, ws, ws_bytes, s, false, false, nullptr, 0, planes, nullptr, lens);
 }
 
 int uvad_forward(uvad_ctx *c, const float *d_pcm, int B, int64_t S, float *d_logits, float *d_probs,
@@ -1384,6 +1424,21 @@ int uvad_forward(uvad_ctx *c, const float *d_pcm, int B, int64_t S, float *d_log
 int uvad_forward_i16(uvad_ctx *c, const int16_t *d_pcm, int B, int64_t S, float *d_logits, float *d_probs,
                      void *ws, size_t ws_bytes, void *stream) {
     return forward_impl(c, d_pcm, 1, B, S, d_logits, d_probs, ws, ws_bytes, stream);
+}
+
+static int forward_lens_entry(uvad_ctx *c, const void *d_pcm, int is_i16, int B, int64_t S, const int64_t *d_nsamp, float *d_logits,
+                              float *d_probs, void *ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_nsamp) return fail(c, UVAD_E_ARG, "uvad_forward_lens: d_nsamp is NULL");
+    return forward_impl(c, d_pcm, is_i16, B, S, d_logits, d_probs, ws, ws_bytes, stream, d_nsamp);
+}
+int uvad_forward_lens(uvad_ctx *c, const float *d_pcm, int B, int64_t S, const int64_t *d_nsamp, float *d_logits, float *d_probs,
+                      void *ws, size_t ws_bytes, void *stream) {
+    return forward_lens_entry(c, d_pcm, 0, B, S, d_nsamp, d_logits, d_probs, ws, ws_bytes, stream);
+}
+int uvad_forward_lens_i16(uvad_ctx *c, const int16_t *d_pcm, int B, int64_t S, const int64_t *d_nsamp, float *d_logits, float *d_probs,
+                          void *ws, size_t ws_bytes, void *stream) {
+    return forward_lens_entry(c, d_pcm, 1, B, S, d_nsamp, d_logits, d_probs, ws, ws_bytes, stream);
 }
 
 int uvad_get_taps(uvad_ctx *c, int B, int T, float *d_lstm_out, float *d_lin_out, const void *ws, void *stream) {
@@ -1796,6 +1851,27 @@ int uvad_label_runs(uvad_ctx *c, const uint8_t *d_labels, int B, int T, int max_
     if (!c || !d_labels || !d_runs || !d_counts || B <= 0 || T <= 0 || max_runs <= 0) return UVAD_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, launch_runs(d_labels, B, T, max_runs, d_runs, d_counts, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_median_filter_lens(uvad_ctx *c, const float *d_probs, int B, int T, const int32_t *d_lens, int kernel, uint8_t *d_labels,
+                            void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_probs || !d_labels || B <= 0 || T <= 0) return fail(c, UVAD_E_ARG, "uvad_median_filter_lens: bad argument");
+    if (!d_lens) return fail(c, UVAD_E_ARG, "uvad_median_filter_lens: d_lens is NULL");
+    if (kernel < 1 || kernel % 2 == 0) return fail(c, UVAD_E_ARG, "median kernel must be odd");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_median_lens(d_probs, B, T, kernel, d_labels, d_lens, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_label_runs_lens(uvad_ctx *c, const uint8_t *d_labels, int B, int T, const int32_t *d_lens, int max_runs, int32_t *d_runs,
+                         int32_t *d_counts, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_labels || !d_runs || !d_counts || B <= 0 || T <= 0 || max_runs <= 0) return fail(c, UVAD_E_ARG, "uvad_label_runs_lens: bad argument");
+    if (!d_lens) return fail(c, UVAD_E_ARG, "uvad_label_runs_lens: d_lens is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_runs_lens(d_labels, B, T, max_runs, d_runs, d_counts, d_lens, (hipStream_t)stream));
     return UVAD_OK;
 }
 

@@ -84,6 +84,8 @@ size_t gemm_f16p_ws_counter_bytes();
 hipError_t launch_gemm_f16p_ws(const GemmArgs &a, unsigned *counters, int n_cu, hipStream_t s);
 size_t weight_plane_elems(int N, int ldw);
 bool split_weights_f16x3(const float *w, int N, int ldw, unsigned short *out /*3 * weight_plane_elems*/, float *wscale);   // false: not representable
+// canonical f32 features [B][T][F] -> the same with frames t >= clamp(lens[b], 0, T) zero (never read): the operand of a lens classify
+hipError_t launch_mask_features(const float *x, int B, int T, int F, const int *lens, float *out, hipStream_t s);
 // canonical f32 features [B][T][F] -> tile-major K-blocked f16 planes (tiles*T*4 rows, Fp columns); *flag (optional) = 1 if a value is non-finite or
 // outside the f16 range
 hipError_t launch_split_features(const float *x, int B, int T, int F, int Fp, int tiles, unsigned short *xh, unsigned short *xl, int *flag,
@@ -112,6 +114,9 @@ struct LstmArgs {
     int n_cu;                    // compute units of the device (0 = 256)
     // optional carried state (streaming): [dirs][tiles*SEQ_TILE][H], nullptr = zeros / discard
     const float *h0, *c0; float *hN, *cN;
+    // optional per-row lengths (uvad_classify_lens): device int32 [nB], clamped to [0, T], sequences past nB have length 0; every sequence
+    // runs from zero state over its first len frames (no steps / carried state); a workgroup runs max(len) steps of its sequences
+    const int *lens; int nB;
 };
 hipError_t launch_lstm(const LstmArgs &a, hipStream_t s, int *tile_used = nullptr);
 int lstm_auto_tile(int tiles, int dirs, int H, int n_cu);   // what tile_mode 0 picks (4 or 16)
@@ -144,6 +149,10 @@ hipError_t launch_untile(const void *src, const void *src_lo, int lds_, int W, f
 hipError_t launch_median(const float *probs, int B, int T, int kernel, uint8_t *labels, hipStream_t s);
 // 0/1 label rows -> ordered (start frame, first non-speech frame) pairs per row + the number of runs
 hipError_t launch_runs(const uint8_t *labels, int B, int T, int max_runs, int *runs, int *counts, hipStream_t s);
+// per-row lengths (device int32 [B], clamped to [0, T]): outputs [B][ld] at t >= len_b set to 0; median / runs on each row's prefix
+hipError_t launch_lens_fill(float *logits, float *probs, int B, int T, int ld, const int *lens, hipStream_t s);
+hipError_t launch_median_lens(const float *probs, int B, int T, int kernel, uint8_t *labels, const int *lens, hipStream_t s);
+hipError_t launch_runs_lens(const uint8_t *labels, int B, int T, int max_runs, int *runs, int *counts, const int *lens, hipStream_t s);
 // per-row {false alarm, missed detection} frame counts of 0/1 label rows
 hipError_t launch_der(const uint8_t *pred, const uint8_t *gt, int B, int T, uint32_t *counts, hipStream_t s);
 
@@ -205,8 +214,13 @@ struct FbankArgs {
     const float *vs_chunk, *vs_tail_in; float *vs_tail_out;
     int vs_tail, vs_chunk_len, vs_first, vs_n_left, vs_offset;
     FbankTables tab;
+    // optional per-row sample counts (uvad_fbank_lens): device int64 [B], clamped to [0, S]; row b is framed as a row of nsamp[b] samples
+    // alone (reflection at its end, later samples never read) and its frames past uvad_num_frames(nsamp[b]) are written as zero
+    const int64_t *nsamp;
 };
 hipError_t launch_fbank(const FbankArgs &a, hipStream_t s);
+// frames[b] = the frame count of a row of clamp(nsamp[b], 0, S) samples (uvad_num_frames), device int32 [B]
+hipError_t launch_frames_of(const int64_t *nsamp, int B, int64_t S, int frame_len, int frame_shift, int snip_edges, int *frames, hipStream_t s);
 size_t fbank_lds_bytes(const FbankArgs &a);
 // streaming: staging[b] = [tail (frame_len samples, reflection-filled on the first step) | chunk];
 // new tail = last `tail` samples of staging

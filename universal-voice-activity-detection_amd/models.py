@@ -112,25 +112,27 @@ class PyanNet2(nn.Module):
                                "and has no CPU fallback (move the batch to 'cuda')")
 
     @torch.no_grad()
-    def forward(self, audio_feats: torch.Tensor) -> torch.Tensor:
-        """(batch, frames, features) -> (batch, frames, 1) speech probabilities."""
+    def forward(self, audio_feats: torch.Tensor, lengths=None) -> torch.Tensor:
+        """(batch, frames, features) -> (batch, frames, 1) speech probabilities.  lengths (batch,): valid frames per row, with
+        pack_padded_sequence semantics (row b is the model on its first lengths[b] frames alone; the rest is 0)."""
         self._require_gpu(audio_feats, "audio_feats")
-        _, probs = self.runtime(audio_feats.device).classify(audio_feats, want_logits=False)
+        _, probs = self.runtime(audio_feats.device).classify(audio_feats, want_logits=False, lengths=lengths)
         return probs.unsqueeze(-1)
 
     @torch.no_grad()
-    def forward_logits(self, audio_feats: torch.Tensor):
-        """(logits, probs), both (batch, frames): the pre-sigmoid value BASELINE.json's metric is judged on."""
+    def forward_logits(self, audio_feats: torch.Tensor, lengths=None):
+        """(logits, probs), both (batch, frames): the pre-sigmoid value BASELINE.json's metric is judged on.  lengths as in forward."""
         self._require_gpu(audio_feats, "audio_feats")
-        return self.runtime(audio_feats.device).classify(audio_feats)
+        return self.runtime(audio_feats.device).classify(audio_feats, lengths=lengths)
 
     @torch.no_grad()
-    def forward_waveform(self, pcm: torch.Tensor):
-        """(batch, samples) PCM -> (logits, probs); needs ``attach_fbank``."""
+    def forward_waveform(self, pcm: torch.Tensor, lengths=None):
+        """(batch, samples) PCM -> (logits, probs); needs ``attach_fbank``.  lengths (batch,): samples per row (row b is the model on
+        pcm[b, :lengths[b]] alone; its frames past num_frames(lengths[b]) are 0)."""
         self._require_gpu(pcm, "pcm")
         if self._fbank_cfg is None:
             raise RuntimeError("attach_fbank(FbankConfig(...)) first")
-        return self.runtime(pcm.device).forward(pcm)
+        return self.runtime(pcm.device).forward(pcm, lengths=lengths)
 
 
 class PyanNet(PyanNet2):
@@ -166,24 +168,31 @@ class PyanNet(PyanNet2):
     def num_frames(self, num_samples: int) -> int:
         return self.sincnet.num_frames(num_samples, self.sincnet.stride)
 
+    _NO_LENGTHS = ("PyanNet has no variable-length batches: every SincNet stage normalises over the whole row (instance norm), so "
+                   "per-row lengths would need per-row statistics in every stage; run rows of different lengths in separate calls")
+
     @torch.no_grad()
-    def forward(self, waveforms: torch.Tensor) -> torch.Tensor:
+    def forward(self, waveforms: torch.Tensor, lengths=None) -> torch.Tensor:
         """(batch, channel, samples) -> (batch, frames, 1) speech probabilities.  f32 samples, or int16 as read from a wav file (read as
         q / 32768 by uvad_forward_wav_i16, no conversion on the host)."""
+        if lengths is not None:
+            raise NotImplementedError(self._NO_LENGTHS)
         _, probs = self.forward_logits(waveforms, want_logits=False)
         return probs.unsqueeze(-1)
 
     @torch.no_grad()
-    def forward_logits(self, waveforms: torch.Tensor, want_logits=True):
+    def forward_logits(self, waveforms: torch.Tensor, want_logits=True, lengths=None):
         """(batch, [channel = 1,] samples) f32 or int16 -> (logits, probs), both (batch, frames); int16 is passed through unconverted."""
+        if lengths is not None:
+            raise NotImplementedError(self._NO_LENGTHS)
         self._require_gpu(waveforms, "waveforms")
         if waveforms.dim() == 3:
             assert waveforms.shape[1] == 1, f"Only single channel is supported. You have {waveforms.shape[1]}"
             waveforms = waveforms[:, 0, :]
         return self.runtime(waveforms.device).forward_wav(waveforms, want_logits=want_logits)
 
-    def forward_waveform(self, pcm: torch.Tensor):
-        return self.forward_logits(pcm)
+    def forward_waveform(self, pcm: torch.Tensor, lengths=None):
+        return self.forward_logits(pcm, lengths=lengths)
 
     def attach_fbank(self, config):
         raise RuntimeError("PyanNet consumes raw waveforms (SincNet); log-mel features belong to PyanNet2")

@@ -102,10 +102,13 @@ class ForwardPipeline:
         return kept
 
     # ------------------------------------------------------------------ use
-    def submit(self, pcm: torch.Tensor, want_logits: bool = True, want_probs: bool = False, timed: bool = False) -> Pending:
+    def submit(self, pcm: torch.Tensor, want_logits: bool = True, want_probs: bool = False, timed: bool = False, lengths=None) -> Pending:
         """pcm (B, S) f32, or int16 read as q / 32768, on the device, ready on the CURRENT stream.  Returns at once; the step runs on the
         next slot's stream (VadRuntime.forward, or forward_wav for a PyanNet).
-        timed: bracket the step with timing events on its own stream (Pending.elapsed_ms)."""
+        timed: bracket the step with timing events on its own stream (Pending.elapsed_ms).
+        lengths: samples per row (B,) -- a ragged batch (VadRuntime.forward(lengths=...)); a PyanNet refuses it."""
+        if lengths is not None and self.wav:
+            raise NotImplementedError("PyanNet has no variable-length batches (SincNet's instance norms are per row)")
         i = self._k % self._active
         self._k += 1
         s = self.streams[i]
@@ -115,8 +118,10 @@ class ForwardPipeline:
             if timed:
                 start = torch.cuda.Event(enable_timing=True)
                 start.record(s)
-            run = self.runtimes[i].forward_wav if self.wav else self.runtimes[i].forward
-            logits, probs = run(pcm, want_logits=want_logits, want_probs=want_probs)
+            if self.wav:
+                logits, probs = self.runtimes[i].forward_wav(pcm, want_logits=want_logits, want_probs=want_probs)
+            else:
+                logits, probs = self.runtimes[i].forward(pcm, want_logits=want_logits, want_probs=want_probs, lengths=lengths)
             ev = torch.cuda.Event(enable_timing=timed)
             ev.record(s)
         pcm.record_stream(s)

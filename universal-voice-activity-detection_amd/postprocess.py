@@ -14,16 +14,17 @@ def median_window(window: float, speech_window: float = 0.5) -> int:
     return k - 1 if k % 2 == 0 else k
 
 
-def median_filter(x: torch.Tensor, SPEECH_WINDOW: float = 0.5, window: float = 0.02, runtime=None) -> torch.Tensor:
+def median_filter(x: torch.Tensor, SPEECH_WINDOW: float = 0.5, window: float = 0.02, runtime=None, lengths=None) -> torch.Tensor:
     """(batch, frames) probabilities -> (batch, frames) int64 0/1, same contract as the reference
     (which returns the tensor on "cuda"); thresholds at 0.5 then applies the odd binary median
-    with zero-padded edges."""
+    with zero-padded edges.  lengths (batch,): valid frames per row -- each row's prefix is filtered
+    alone (zero padded at its own end), labels past it are 0."""
     if not x.is_cuda:
         raise RuntimeError("median_filter runs on the GPU only")
     if runtime is None:
         from .runtime import VadRuntime
         runtime = _shared_runtime(x.device)
-    return runtime.median_filter(x, median_window(window, SPEECH_WINDOW)).to(torch.int64)
+    return runtime.median_filter(x, median_window(window, SPEECH_WINDOW), lengths=lengths).to(torch.int64)
 
 
 _RT = {}
@@ -56,24 +57,30 @@ def labels_to_intervals(labels, frame_shift: float) -> List[Tuple[float, float]]
     return out
 
 
-def labels_to_intervals_batch(labels: torch.Tensor, frame_shift: float, runtime=None) -> List[List[Tuple[float, float]]]:
+def labels_to_intervals_batch(labels: torch.Tensor, frame_shift: float, runtime=None, lengths=None) -> List[List[Tuple[float, float]]]:
     """(B, T) 0/1 labels ON THE GPU -> per row [(start_s, end_s)], same values as ``labels_to_intervals`` row by row.
     The run-length walk runs in ``uvad_label_runs``; only the (start, stop) frame pairs cross to the host (one copy
-    for the whole batch), where the reference's rounding / empty-interval rule is applied."""
+    for the whole batch), where the reference's rounding / empty-interval rule is applied.  lengths (B,): valid frames
+    per row; row b gives what ``labels_to_intervals(labels[b, :lengths[b]])`` gives."""
     if not (torch.is_tensor(labels) and labels.is_cuda):
         raise RuntimeError("labels_to_intervals_batch runs on the GPU only (use labels_to_intervals for host rows)")
     if labels.dim() == 3:
         labels = labels.squeeze(-1)
     rt = runtime or _shared_runtime(labels.device)
     T = labels.shape[1]
-    runs, counts = rt.label_runs(labels)
+    runs, counts = rt.label_runs(labels, lengths=lengths)
+    if lengths is None:
+        lens_h = [T] * labels.shape[0]
+    else:   # the kernel clamped them to [0, T]; so does the host side
+        lens_h = [min(max(int(v), 0), T) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
     counts_h = counts.cpu().numpy()
     runs_h = runs[:, : max(int(counts_h.max()), 1)].cpu().numpy()
     out = []
     for b in range(labels.shape[0]):
         row = []
+        Tb = lens_h[b]
         for k, k2 in runs_h[b, : counts_h[b]]:
-            last = (T - 1) if k2 >= T else (k2 - 1)
+            last = (Tb - 1) if k2 >= Tb else (k2 - 1)
             s, e = round(float(k * frame_shift), 2), round(float(last * frame_shift), 2)
             if e - s > 0.0:
                 row.append((s, e))

@@ -128,6 +128,22 @@ class VadRuntime:
     def num_frames(self, S: int) -> int:
         return int(self.lib.uvad_num_frames(self.ctx, S))
 
+    def _dev_lens(self, lengths, B: int, limit: int, dtype, what: str) -> "torch.Tensor":
+        """Per-row lengths for a *_lens call: a tensor on this device (int32 / int64) is used as it is -- the library clamps it to
+        [0, limit] on the device, so a captured graph can replay with new values -- anything else (a list, a CPU tensor) is validated
+        here and uploaded."""
+        if torch.is_tensor(lengths) and lengths.device == self.device:
+            if lengths.dtype not in (torch.int32, torch.int64) or lengths.shape != (B,):
+                raise ValueError(f"{what} must be an int32 / int64 tensor of shape ({B},), got {lengths.dtype} {tuple(lengths.shape)}")
+            return lengths.to(dtype).contiguous()
+        host = lengths.tolist() if torch.is_tensor(lengths) else list(lengths)
+        if len(host) != B:
+            raise ValueError(f"{what}: {len(host)} lengths for {B} rows")
+        for v in host:
+            if isinstance(v, bool) or int(v) != v or not 0 <= v <= limit:
+                raise ValueError(f"{what}: every length must be an integer in [0, {limit}], got {v!r}")
+        return torch.tensor([int(v) for v in host], dtype=dtype, device=self.device)
+
     def workspace(self, B: int, T: int) -> "torch.Tensor":
         need = int(self.lib.uvad_workspace_bytes(self.ctx, B, T))
         if self._ws is None or self._ws.numel() < need:
@@ -136,25 +152,32 @@ class VadRuntime:
         return self._ws
 
     # ------------------------------------------------------------------ compute
-    def fbank(self, pcm: "torch.Tensor") -> "torch.Tensor":
-        """pcm (B,S) f32 or int16 on the GPU -> (B,T,n_mels) f32."""
+    def fbank(self, pcm: "torch.Tensor", lengths=None) -> "torch.Tensor":
+        """pcm (B,S) f32 or int16 on the GPU -> (B,T,n_mels) f32.  lengths: samples per row (B,); row b is framed as pcm[b, :lengths[b]]
+        alone and its frames past uvad_num_frames(lengths[b]) are zero."""
         with torch.cuda.device(self.device):
-            if pcm.dtype == torch.int16:
+            i16 = pcm.dtype == torch.int16
+            if i16:
                 if pcm.device != self.device:
                     raise RuntimeError(f"pcm must be on {self.device}")
                 pcm = pcm.contiguous()
-                fn = self.lib.uvad_fbank_i16
             else:
                 pcm = self._dev_f32(pcm, "pcm")
-                fn = self.lib.uvad_fbank
             B, S = pcm.shape
             T = self.num_frames(S)
             feats = torch.empty((B, T, self._fb_c.n_mels), dtype=torch.float32, device=self.device)
-            self._check(fn(self.ctx, pcm.data_ptr(), B, S, feats.data_ptr(), self._stream()))
+            if lengths is None:
+                fn = self.lib.uvad_fbank_i16 if i16 else self.lib.uvad_fbank
+                self._check(fn(self.ctx, pcm.data_ptr(), B, S, feats.data_ptr(), self._stream()))
+            else:
+                n = self._dev_lens(lengths, B, S, torch.int64, "lengths (samples)")
+                fn = self.lib.uvad_fbank_lens_i16 if i16 else self.lib.uvad_fbank_lens
+                self._check(fn(self.ctx, pcm.data_ptr(), B, S, n.data_ptr(), feats.data_ptr(), self._stream()))
             return feats
 
-    def classify(self, feats: "torch.Tensor", want_logits=True, want_probs=True):
-        """feats (B,T,F) on the GPU -> (logits (B,T) | None, probs (B,T) | None)."""
+    def classify(self, feats: "torch.Tensor", want_logits=True, want_probs=True, lengths=None):
+        """feats (B,T,F) on the GPU -> (logits (B,T) | None, probs (B,T) | None).  lengths: valid frames per row (B,) -- pack_padded_sequence
+        semantics: row b is the model on feats[b, :lengths[b]] alone, frames past it are never read and come out as 0."""
         with torch.cuda.device(self.device):
             feats = self._dev_f32(feats, "feats")
             B, T, F = feats.shape
@@ -163,33 +186,44 @@ class VadRuntime:
             ws = self.workspace(B, T)
             logits = torch.empty((B, T), dtype=torch.float32, device=self.device) if want_logits else None
             probs = torch.empty((B, T), dtype=torch.float32, device=self.device) if want_probs else None
-            self._check(self.lib.uvad_classify(self.ctx, feats.data_ptr(), B, T,
-                                               logits.data_ptr() if want_logits else None,
-                                               probs.data_ptr() if want_probs else None,
-                                               ws.data_ptr(), ws.numel(), self._stream()))
+            if lengths is None:
+                self._check(self.lib.uvad_classify(self.ctx, feats.data_ptr(), B, T,
+                                                   logits.data_ptr() if want_logits else None,
+                                                   probs.data_ptr() if want_probs else None,
+                                                   ws.data_ptr(), ws.numel(), self._stream()))
+            else:
+                n = self._dev_lens(lengths, B, T, torch.int32, "lengths (frames)")
+                self._check(self.lib.uvad_classify_lens(self.ctx, feats.data_ptr(), B, T, n.data_ptr(),
+                                                        logits.data_ptr() if want_logits else None,
+                                                        probs.data_ptr() if want_probs else None,
+                                                        ws.data_ptr(), ws.numel(), self._stream()))
             self._last_bt = (B, T)
             return logits, probs
 
-    def forward(self, pcm: "torch.Tensor", want_logits=True, want_probs=True):
-        """pcm (B,S) f32 (or int16, as read from a wav file) on the GPU -> (logits, probs); features never leave the workspace."""
+    def forward(self, pcm: "torch.Tensor", want_logits=True, want_probs=True, lengths=None):
+        """pcm (B,S) f32 (or int16, as read from a wav file) on the GPU -> (logits, probs); features never leave the workspace.
+        lengths: samples per row (B,); row b is the model on pcm[b, :lengths[b]] alone, its frames past uvad_num_frames(lengths[b]) are 0."""
         with torch.cuda.device(self.device):
-            if pcm.dtype == torch.int16:
+            i16 = pcm.dtype == torch.int16
+            if i16:
                 if pcm.device != self.device:
                     raise RuntimeError(f"pcm must be on {self.device}")
                 pcm = pcm.contiguous()
-                fn = self.lib.uvad_forward_i16
             else:
                 pcm = self._dev_f32(pcm, "pcm")
-                fn = self.lib.uvad_forward
             B, S = pcm.shape
             T = self.num_frames(S)
             ws = self.workspace(B, T)
             logits = torch.empty((B, T), dtype=torch.float32, device=self.device) if want_logits else None
             probs = torch.empty((B, T), dtype=torch.float32, device=self.device) if want_probs else None
-            self._check(fn(self.ctx, pcm.data_ptr(), B, S,
-                           logits.data_ptr() if want_logits else None,
-                           probs.data_ptr() if want_probs else None,
-                           ws.data_ptr(), ws.numel(), self._stream()))
+            outs = (logits.data_ptr() if want_logits else None, probs.data_ptr() if want_probs else None, ws.data_ptr(), ws.numel(), self._stream())
+            if lengths is None:
+                fn = self.lib.uvad_forward_i16 if i16 else self.lib.uvad_forward
+                self._check(fn(self.ctx, pcm.data_ptr(), B, S, *outs))
+            else:
+                n = self._dev_lens(lengths, B, S, torch.int64, "lengths (samples)")
+                fn = self.lib.uvad_forward_lens_i16 if i16 else self.lib.uvad_forward_lens
+                self._check(fn(self.ctx, pcm.data_ptr(), B, S, n.data_ptr(), *outs))
             self._last_bt = (B, T)
             return logits, probs
 
@@ -267,12 +301,18 @@ class VadRuntime:
                                                self._ws.data_ptr(), self._stream()))
             return y, z
 
-    def median_filter(self, probs: "torch.Tensor", kernel: int) -> "torch.Tensor":
+    def median_filter(self, probs: "torch.Tensor", kernel: int, lengths=None) -> "torch.Tensor":
+        """lengths: valid frames per row (B,): the median of each row's prefix alone, labels past it 0."""
         with torch.cuda.device(self.device):
             probs = self._dev_f32(probs, "probs")
             B, T = probs.shape
             out = torch.empty((B, T), dtype=torch.uint8, device=self.device)
-            self._check(self.lib.uvad_median_filter(self.ctx, probs.data_ptr(), B, T, int(kernel), out.data_ptr(), self._stream()))
+            if lengths is None:
+                self._check(self.lib.uvad_median_filter(self.ctx, probs.data_ptr(), B, T, int(kernel), out.data_ptr(), self._stream()))
+            else:
+                n = self._dev_lens(lengths, B, T, torch.int32, "lengths (frames)")
+                self._check(self.lib.uvad_median_filter_lens(self.ctx, probs.data_ptr(), B, T, n.data_ptr(), int(kernel), out.data_ptr(),
+                                                             self._stream()))
             return out
 
     # ------------------------------------------------------------------ streaming (BASELINE cfg 5)
@@ -473,8 +513,9 @@ class VadRuntime:
             self._check(self.lib.uvad_der_counts(self.ctx, pred.data_ptr(), gt.data_ptr(), B, T, out.data_ptr(), self._stream()))
             return out
 
-    def label_runs(self, labels: "torch.Tensor", max_runs: int = 0):
-        """labels (B, T) uint8 0/1 on the GPU -> (runs (B, max_runs, 2) int32, counts (B,) int32), both on the GPU."""
+    def label_runs(self, labels: "torch.Tensor", max_runs: int = 0, lengths=None):
+        """labels (B, T) uint8 0/1 on the GPU -> (runs (B, max_runs, 2) int32, counts (B,) int32), both on the GPU.
+        lengths: valid frames per row (B,): runs of each row's prefix, a run open at its end closes at lengths[b]."""
         with torch.cuda.device(self.device):
             if not torch.is_tensor(labels) or labels.device != self.device:
                 raise RuntimeError(f"labels must be a tensor on {self.device}")
@@ -483,7 +524,12 @@ class VadRuntime:
             max_runs = int(max_runs) if max_runs > 0 else (T + 1) // 2
             runs = torch.empty((B, max_runs, 2), dtype=torch.int32, device=self.device)
             counts = torch.empty((B,), dtype=torch.int32, device=self.device)
-            self._check(self.lib.uvad_label_runs(self.ctx, labels.data_ptr(), B, T, max_runs, runs.data_ptr(), counts.data_ptr(), self._stream()))
+            if lengths is None:
+                self._check(self.lib.uvad_label_runs(self.ctx, labels.data_ptr(), B, T, max_runs, runs.data_ptr(), counts.data_ptr(), self._stream()))
+            else:
+                n = self._dev_lens(lengths, B, T, torch.int32, "lengths (frames)")
+                self._check(self.lib.uvad_label_runs_lens(self.ctx, labels.data_ptr(), B, T, n.data_ptr(), max_runs, runs.data_ptr(),
+                                                          counts.data_ptr(), self._stream()))
             return runs, counts
 
     def streams_overlap(self, a: "torch.cuda.Stream", b: "torch.cuda.Stream") -> bool:

@@ -68,6 +68,22 @@ def cut_into_windows(num_samples: int, window: int, min_keep: int):
     return out
 
 
+def pack_ragged_batches(lengths, max_samples: int):
+    """Ragged batches of whole recordings (predict_vad with ragged_batches): indices sorted by length (longest first, ties by index),
+    cut into consecutive groups whose PADDED size -- rows x the group's longest row -- stays within max_samples (a recording longer
+    than that runs alone).  Each group is one uvad_forward_lens call; a row's results are those of the recording alone."""
+    order = sorted(range(len(lengths)), key=lambda i: (-lengths[i], i))
+    batches, cur = [], []
+    for i in order:
+        if cur and (len(cur) + 1) * lengths[cur[0]] > max_samples:   # cur[0] is the group's longest row
+            batches.append(cur)
+            cur = []
+        cur.append(i)
+    if cur:
+        batches.append(cur)
+    return batches
+
+
 def open_pipeline(net, device, depth: int):
     """ForwardPipeline with as many steps in flight as the device proves concurrent: the constructor raises when it cannot find
     `depth` pairwise-concurrent HIP streams (GPU_MAX_HW_QUEUES of 1 or 2, a shared or restricted device); fewer steps in flight
@@ -136,9 +152,15 @@ def predict_vad(**kwargs):
     W = None if window_s is None else int(round(window_s * sr))
     med_window = 0.02 if net.encoding_dim == 768 else 0.01   # vad_engine.py:207-208
 
-    # ---- batches: pieces of equal length together, at most max_duration seconds of audio per batch
+    # ---- batches: pieces of equal length together, at most max_duration seconds of audio per batch; with ragged_batches (whole
+    #      recordings of the log-mel model only) pieces of any length together, padded to the batch's longest, each row classified
+    #      on its own length (uvad_forward_lens)
+    ragged = bool(kwargs.get("ragged_batches", False)) and window_s is None and not sincnet
     order = sorted(range(len(pieces)), key=lambda i: (-pieces[i][2], i))
     batches, i = [], 0
+    if ragged:
+        batches = pack_ragged_batches([p[2] for p in pieces], int(kwargs["max_duration"] * sr))
+        i = len(order)
     while i < len(order):
         n = pieces[order[i]][2]
         group = [order[i]]
@@ -157,9 +179,35 @@ def predict_vad(**kwargs):
         rows = [recs[pieces[j][0]]["pcm"][pieces[j][1]:pieces[j][1] + pieces[j][2]] for j in group]
         return torch.from_numpy(np.stack(rows)).to(device)
 
+    def stack_ragged(group):   # rows zero-padded to the longest (the padding is never read)
+        rows = [recs[pieces[j][0]]["pcm"][pieces[j][1]:pieces[j][1] + pieces[j][2]] for j in group]
+        x = np.zeros((len(rows), max(len(r) for r in rows)), dtype=rows[0].dtype)
+        for r, row in enumerate(rows):
+            x[r, :len(row)] = row
+        return torch.from_numpy(x).to(device)
+
     piece_probs = [None] * len(pieces)
+    piece_post = {}   # ragged: piece -> (labels, intervals) from the batch's lens median and runs
     pending = []
+
+    def ragged_post(group, probs):
+        nsamp = [pieces[j][2] for j in group]
+        fr = [rt.num_frames(n) for n in nsamp]
+        lab = median_filter(probs, window=med_window, lengths=fr)                      # uvad_median_filter_lens
+        ivs = labels_to_intervals_batch(lab, frame_shift, runtime=rt, lengths=fr)     # uvad_label_runs_lens
+        for r, j in enumerate(group):
+            piece_probs[j] = probs[r, :fr[r]]
+            piece_post[j] = (lab[r, :fr[r]], ivs[r])
+
     for group in batches:
+        if ragged:
+            x = stack_ragged(group)
+            nsamp = [pieces[j][2] for j in group]
+            if pipe is not None:
+                pending.append((group, pipe.submit(x, want_logits=False, want_probs=True, lengths=nsamp)))
+            else:
+                ragged_post(group, rt.forward(x, want_logits=False, lengths=nsamp)[1])
+            continue
         n = pieces[group[0]][2]
         x = stack(group)
         if sincnet:   # (batch, samples), int16 from a wav file as it is (uvad_forward_wav_i16 reads q / 32768); the model consumes raw audio
@@ -188,6 +236,9 @@ def predict_vad(**kwargs):
             piece_probs[j] = probs[r]
     for group, p in pending:
         _, probs = p.result()
+        if ragged:
+            ragged_post(group, probs)
+            continue
         for r, j in enumerate(group):
             piece_probs[j] = probs[r]
     if pipe is not None:
@@ -201,6 +252,12 @@ def predict_vad(**kwargs):
         if not mine:
             results.append({"recording_id": r["id"], "num_frames": 0, "labels": np.zeros(0, np.uint8), "probs": np.zeros(0, np.float32),
                             "intervals": []})
+            continue
+        if ragged:   # one piece per recording, post-processed with its batch
+            (j,) = mine
+            labels, intervals = piece_post[j]
+            results.append({"recording_id": r["id"], "num_frames": int(labels.shape[0]), "labels": labels.cpu().numpy().astype(np.uint8),
+                            "probs": piece_probs[j].cpu().numpy(), "intervals": intervals})
             continue
         rows_l, rows_p = [], []
         by_len = {}
