@@ -18,7 +18,7 @@
  *     allocates or frees caller tensors.  It owns only the weights / tables inside uvad_ctx.
  *   - compute calls are ASYNCHRONOUS on `stream` (a hipStream_t passed as void*; NULL = the
  *     default stream) and perform no allocation or synchronisation => hipGraph-capturable
- *     (exceptions: uvad_stream_step and uvad_window_step, see there).  Every call makes the context's device current
+ *     (exceptions: uvad_stream_step, uvad_window_step and uvad_window_wav_step, see there).  Every call makes the context's device current
  *     (hipSetDevice) before it enqueues, so a multi-GPU process may interleave contexts freely.
  *   - one ctx per (device, model); a ctx is NOT thread-safe (the reference drives the model
  *     from a single thread: Trainer(devices=1), src/scripts/predict.py:79-85).
@@ -299,6 +299,46 @@ int uvad_sincnet_i16(uvad_ctx *, const int16_t *d_wav, int B, int64_t S, float *
                      size_t ws_bytes, void *stream);
 int uvad_forward_wav_i16(uvad_ctx *, const int16_t *d_wav, int B, int64_t S, float *d_logits, float *d_probs,
                          void *d_workspace, size_t ws_bytes, void *stream);
+
+/* Windowed streaming of the waveform model (PyanNet: SincNet + classifier), the uvad_window_* semantic on raw PCM.  SincNet normalises
+ * every stage over the whole row, so nothing carries from step to step: each step re-runs uvad_forward_wav over a sliding window,
+ * as the reference infers this model on fixed 5 s cuts, each normalised and run from zero state (predict_sincnet.py, custom_vad.py).
+ *   Geometry: J = 27 * stride is the frame step and R = kernel_size + stride * (9 * k3 + 3 * k2 + 14) the receptive field, in samples
+ *   (J = 270, R = 991 for the reference); frames(S) = S < R ? 0 : (S - R) / J + 1 = uvad_sincnet_num_frames(S).
+ *   B feeds advance in lockstep, `chunk` samples per step.  After a step n samples per feed have arrived and e = frames(n) frames are
+ *   complete.  The window is the last Tw = min(e, W) frames [e - Tw, e), whose samples are exactly [J (e - Tw), J (e - Tw) + S_w),
+ *   S_w = R + J (Tw - 1).  During the warm-up (e < W) it is the prefix; trailing samples of an incomplete frame are never in it.
+ *   The model runs on those S_w samples exactly as uvad_forward_wav (_i16) runs a (B, S_w) batch: from zero state, every norm over the
+ *   window.  The step emits frames [f0, e - L) (f0 = what earlier steps emitted; none while e <= L); frame t's logit is row t - (e - Tw)
+ *   of that run.  Streams are open-ended: the last L frames are never emitted.
+ *   W is in frames and a window holds whole frames only: W = 293 spans 79 831 samples, not the 80 000 of a reference 5 s cut (the
+ *   reference's last 169 samples complete no frame).  This is the one difference from the reference's cuts.
+ * uvad_window_wav_reset: 0 <= L < W (else UVAD_E_ARG); is_i16 fixes the sample type of the state: uvad_window_wav_step reads f32,
+ * uvad_window_wav_step_i16 reads int16 as q / 32768 (as uvad_forward_wav_i16), and a step of the other type is UVAD_E_ARG.  A step
+ * needs L + ceil(chunk / J) <= W (else UVAD_E_ARG).  Outputs d_logits / d_probs [B][ld_out] (row b, columns 0 .. k - 1; either may be
+ * NULL, not both); an ld_out below the step's k is UVAD_E_ARG and nothing is enqueued or counted.  Returns k >= 0.
+ * State: a per-feed ring of the latest PCM in the state's sample type, the last window's SincNet output and a device sample counter.
+ * A step commits its chunk to the ring and writes the window [B][S_w] contiguously into the workspace (one kernel), then runs the
+ * SincNet stages at (B, S_w), the classifier at (B, Tw) -- time chunks off, uvad_get_time_chunks() is 1 afterwards -- and a gather of
+ * the emitted rows.  A step that completes no frame only commits its samples and moves the device counter.  Steps never allocate,
+ * free or synchronise, warm-up included.  Once the window is full the ring position comes from the device and every launch argument
+ * except k is constant, so two steps with the same replay_key (uvad_window_wav_peek: k; -1 during the warm-up) and the same buffers
+ * enqueue identical work: a graph captured around one replays for the other, followed by uvad_window_wav_advance, which moves the
+ * counters as the step would and returns its k.
+ * uvad_window_wav_features (debug tap) copies the SincNet output [B][Tw][c3] of the last window the model ran on to d_feats and sets
+ * *Tw; d_feats = NULL only sets *Tw.
+ * Every entry needs a context with a model, uvad_sincnet_configure and uvad_finalize done: otherwise UVAD_E_STATE.  The byte counts
+ * need the model and SincNet configurations only, and return 0 without them. */
+size_t uvad_window_wav_state_bytes(const uvad_ctx *, int B, int window, int is_i16);
+size_t uvad_window_wav_workspace_bytes(const uvad_ctx *, int B, int chunk, int window);
+int uvad_window_wav_reset(uvad_ctx *, void *d_state, int B, int window, int lookahead, int is_i16, void *stream);
+int uvad_window_wav_step(uvad_ctx *, const float *d_pcm_chunk, int B, int chunk, void *d_state,
+                         float *d_logits, float *d_probs, int ld_out, void *d_workspace, size_t ws_bytes, void *stream);
+int uvad_window_wav_step_i16(uvad_ctx *, const int16_t *d_pcm_chunk, int B, int chunk, void *d_state,
+                             float *d_logits, float *d_probs, int ld_out, void *d_workspace, size_t ws_bytes, void *stream);
+int uvad_window_wav_peek(const uvad_ctx *, const void *d_state, int chunk, int *k, int64_t *replay_key);
+int uvad_window_wav_advance(uvad_ctx *, void *d_state, int chunk);
+int uvad_window_wav_features(uvad_ctx *, const void *d_state, int B, float *d_feats, int *Tw, void *stream);
 
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;

@@ -402,8 +402,8 @@ hipError_t launch_gemm_f16p(const GemmArgs &a, hipStream_t s) {
 
 hipError_t launch_split_features(const float *x, int B, int T, int F, int Fp, int tiles, unsigned short *xh, unsigned short *xl, int *flag,
                                  hipStream_t s) {
-    if (flag) {
-        hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), s);
+    if (flag) {   // reset by an atomic kernel, not a memset node: the kernel below sets it with atomicOr (see launch_zero_counters)
+        hipError_t e = launch_zero_counters(reinterpret_cast<unsigned *>(flag), 1, s);
         if (e != hipSuccess) return e;
     }
     const long long n = (long long)tiles * T * SEQ_TILE * (Fp / 4);

@@ -88,10 +88,12 @@ constexpr int SIDE_RETRY_AFTER = 256;       // calls after which a caller stream
 struct StreamCounters { int64_t n_samples = 0, n_frames = 0, n_steps = 0; };
 struct StreamState { float *h = nullptr, *c = nullptr; size_t layer_stride = 0; };
 struct WindowGroup { StreamCounters sc; int B = 0, W = 0, L = 0; };
+struct WavWindowGroup { int64_t n_samples = 0, n_frames = 0, n_steps = 0; int B = 0, W = 0, L = 0, is_i16 = 0; };
 
 struct uvad_ctx {
     std::map<void *, StreamCounters> streams;   // host mirror of the lock-step stream groups, keyed by d_state
     std::map<void *, WindowGroup> windows;      // ... and of the windowed stream groups (uvad_window_*)
+    std::map<void *, WavWindowGroup> wav_windows;   // ... and of the waveform model's windowed stream groups (uvad_window_wav_*)
     int device = 0, n_cu = 256;
     bool has_fb = false, has_model = false, finalized = false, tables_set = false;
     uvad_fbank_cfg fb{};
@@ -1829,6 +1831,215 @@ int uvad_window_features(uvad_ctx *c, const void *d_state, int B, float *d_feats
     a.ctr_in = reinterpret_cast<const long long *>(st + SL.off_ctr) + (g.sc.n_steps & 1);
     a.B = B; a.R = g.W; a.F = c->fb.n_mels; a.k = 0; a.Tw = *Tw; a.out = d_feats;
     HIPCHK(c, launch_window_assemble(a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+// ---- windowed streaming of the waveform model (PyanNet) ------------------------------------------------------------------------
+// state layout (bytes, 256-aligned blocks): ring [B][R + J W] samples in the state's type (f32 / int16) | feats [B][W][c3] f32 (the SincNet
+// output of the window the model last ran on) | ctr[2] int64 (samples received: the step's assembly kernel reads ctr[0] and writes
+// ctr[1], a one-thread carry right behind it copies ctr[1] to ctr[0]: every step reads the same slot, so the replay key needs no parity)
+// workspace: window [B][Sw_max] samples (sized for f32) | logits, probs [B][W] | classifier workspace of (B, W) | SincNet workspace of
+//            (B, Sw_max) (carve() and sinc_carve() grow with T and S, so they hold every warm-up window too)
+extern "C++" {
+namespace {
+struct WavGeom { int64_t J = 0, R = 0; };
+// J = 27 stride (three MaxPool1d(3) after the strided first stage); R = the shortest input of one frame, restated from the floor chain
+// of sinc_carve: Lpool3 >= f  <=>  S >= stride (3 (3 (3 f + k3 - 1) + k2 - 1) - 1) + kernel_size = J f + R - J
+WavGeom wav_geom(const uvad_ctx *c) {
+    const uvad_sincnet_cfg &q = c->sc;
+    WavGeom g;
+    g.J = 27LL * q.stride;
+    g.R = (int64_t)q.kernel_size + (int64_t)q.stride * (9LL * q.k3 + 3LL * q.k2 + 14);
+    return g;
+}
+int64_t wav_frames(const WavGeom &g, int64_t S) { return S < g.R ? 0 : (S - g.R) / g.J + 1; }
+int64_t wav_span(const WavGeom &g, int64_t Tw) { return Tw > 0 ? g.R + g.J * (Tw - 1) : 0; }
+int wav_kmax(const WavGeom &g, int chunk) { return (int)((chunk + g.J - 1) / g.J); }
+// n - start < Sw + J for every window (it ends at J (e - 1) + R <= n, less than J before n), and a chunk is at most J (W - L) < Sw_max + J
+// samples: a ring of Sw_max + J slots keeps every sample a later window reads, and one launch never writes a slot it reads
+int64_t wav_ring_len(const WavGeom &g, int W) { return wav_span(g, W) + g.J; }
+struct WavWindowLayout { size_t off_ring = 0, off_feats = 0, off_ctr = 0, total = 0; int64_t ring_len = 0; };
+WavWindowLayout wav_window_layout(const uvad_ctx *c, int B, int W, int is_i16) {
+    WavWindowLayout L;
+    L.ring_len = wav_ring_len(wav_geom(c), W);
+    size_t o = 0;
+    L.off_ring = o; o += align_up((size_t)B * (size_t)L.ring_len * (is_i16 ? sizeof(int16_t) : sizeof(float)));
+    L.off_feats = o; o += align_up((size_t)B * W * c->sc.c3 * sizeof(float));
+    L.off_ctr = o; o += align_up(2 * sizeof(long long));
+    L.total = o;
+    return L;
+}
+struct WavWindowWs { size_t off_logits = 0, off_probs = 0, off_cls = 0, cls_bytes = 0, off_sinc = 0, sinc_bytes = 0, total = 0; };
+WavWindowWs wav_window_ws(const uvad_ctx *c, int B, int W) {
+    WavWindowWs w;
+    const int64_t sw = wav_span(wav_geom(c), W);
+    size_t o = align_up((size_t)B * (size_t)sw * sizeof(float));
+    w.off_logits = o; o += align_up((size_t)B * W * sizeof(float));
+    w.off_probs = o; o += align_up((size_t)B * W * sizeof(float));
+    w.off_cls = o; w.cls_bytes = carve(c, B, W).total; o += w.cls_bytes;
+    w.off_sinc = o; w.sinc_bytes = sinc_carve(c, B, sw).total; o += w.sinc_bytes;
+    w.total = o;
+    return w;
+}
+// What the next step of a waveform window group does: k new frames, the window [e - Tw, e) of Sw samples the model runs on and the rows
+// [r0, r0 + n_emit) of it that it emits (frames [max(0, e_prev - L), max(0, e - L))).  Once the window is full, Tw = W, Sw, r0 = W - L - k
+// and n_emit = k follow from k, and the ring position from the device counter: replay key k.
+struct WavWindowPlan { int64_t n = 0, e = 0, Sw = 0; int k = 0, Tw = 0, r0 = 0, n_emit = 0; int64_t key = -1; };
+WavWindowPlan wav_window_plan(const uvad_ctx *c, const WavWindowGroup &g, int chunk) {
+    const WavGeom geo = wav_geom(c);
+    WavWindowPlan p;
+    p.n = g.n_samples + chunk;
+    p.e = wav_frames(geo, p.n);
+    p.k = (int)(p.e - g.n_frames);
+    p.Tw = (int)std::min<int64_t>(p.e, g.W);
+    p.Sw = wav_span(geo, p.Tw);
+    const int64_t f0 = std::max<int64_t>(0, g.n_frames - g.L), f1 = std::max<int64_t>(0, p.e - g.L);
+    p.n_emit = (int)(f1 - f0);
+    p.r0 = (int)(f0 - (p.e - p.Tw));
+    if (p.e >= g.W && g.n_frames >= g.L) p.key = p.k;
+    return p;
+}
+void wav_window_advance(WavWindowGroup &g, const WavWindowPlan &p) {
+    g.n_samples = p.n;
+    g.n_frames = p.e;
+    g.n_steps += 1;
+}
+int wav_window_check_cfg(uvad_ctx *c, const std::string &who) {
+    if (!c->has_model || !c->has_sinc)
+        return fail(c, UVAD_E_STATE, who + ": needs a model and a SincNet configuration (uvad_sincnet_configure)");
+    if (!c->finalized || !c->sinc_ready) return fail(c, UVAD_E_STATE, who + ": SincNet tensors not set / uvad_finalize not called");
+    return UVAD_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+size_t uvad_window_wav_state_bytes(const uvad_ctx *c, int B, int window, int is_i16) {
+    if (!c || !c->has_model || !c->has_sinc || B <= 0 || window < 1 || (is_i16 != 0 && is_i16 != 1)) return 0;
+    return wav_window_layout(c, B, window, is_i16).total;
+}
+
+size_t uvad_window_wav_workspace_bytes(const uvad_ctx *c, int B, int chunk, int window) {
+    if (!c || !c->has_model || !c->has_sinc || B <= 0 || chunk <= 0 || window < 1) return 0;
+    return wav_window_ws(c, B, window).total;
+}
+
+int uvad_window_wav_reset(uvad_ctx *c, void *d_state, int B, int window, int lookahead, int is_i16, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_state || B <= 0 || B > 65535 || (is_i16 != 0 && is_i16 != 1)) return fail(c, UVAD_E_ARG, "uvad_window_wav_reset: bad argument");
+    if (window < 1) return fail(c, UVAD_E_ARG, "uvad_window_wav_reset: window must be >= 1 frame");
+    if (lookahead < 0 || lookahead >= window) return fail(c, UVAD_E_ARG, "uvad_window_wav_reset: need 0 <= lookahead < window");
+    if (int r = wav_window_check_cfg(c, "uvad_window_wav_reset")) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemsetAsync(d_state, 0, wav_window_layout(c, B, window, is_i16).total, (hipStream_t)stream));
+    WavWindowGroup g;
+    g.B = B; g.W = window; g.L = lookahead; g.is_i16 = is_i16;
+    c->wav_windows[d_state] = g;
+    return UVAD_OK;
+}
+
+static int window_wav_step_impl(uvad_ctx *c, const void *d_pcm_chunk, int is_i16, int B, int chunk, void *d_state, float *d_logits,
+                                float *d_probs, int ld_out, void *ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    const std::string who = is_i16 ? "uvad_window_wav_step_i16" : "uvad_window_wav_step";
+    if (!d_pcm_chunk || !d_state || (!d_logits && !d_probs) || !ws || B <= 0 || chunk <= 0) return fail(c, UVAD_E_ARG, who + ": bad argument");
+    if (int r = wav_window_check_cfg(c, who)) return r;
+    auto it = c->wav_windows.find(d_state);
+    if (it == c->wav_windows.end()) return fail(c, UVAD_E_STATE, who + ": call uvad_window_wav_reset on this state first");
+    WavWindowGroup &g = it->second;
+    if (B != g.B) return fail(c, UVAD_E_ARG, who + ": B differs from the one the state was reset with");
+    if (g.is_i16 != is_i16)
+        return fail(c, UVAD_E_ARG, who + (g.is_i16 ? ": the state was reset for int16 samples (uvad_window_wav_step_i16)"
+                                                   : ": the state was reset for f32 samples (uvad_window_wav_step)"));
+    const WavGeom geo = wav_geom(c);
+    const int kmax = wav_kmax(geo, chunk);
+    if ((int64_t)g.L + kmax > g.W)
+        return fail(c, UVAD_E_ARG, who + ": lookahead + ceil(chunk / J) = " + std::to_string((int64_t)g.L + kmax) + " frames exceeds the window of " +
+                                       std::to_string(g.W));
+    const WavWindowWs wl = wav_window_ws(c, B, g.W);
+    if (ws_bytes < wl.total) return fail(c, UVAD_E_WORKSPACE, who + ": window workspace too small: need " + std::to_string(wl.total) + " bytes");
+    const WavWindowPlan p = wav_window_plan(c, g, chunk);
+    if (p.n_emit > ld_out) return fail(c, UVAD_E_ARG, who + ": ld_out smaller than the number of emitted frames");
+    // the closed form the window arithmetic rests on, against the stage-by-stage floor chain
+    if (p.e != uvad_sincnet_num_frames(c, p.n) || (p.Tw > 0 && uvad_sincnet_num_frames(c, p.Sw) != p.Tw))
+        return fail(c, UVAD_E_STATE, who + ": internal: frames(S) = (S - R) / J + 1 disagrees with uvad_sincnet_num_frames");
+    const WavWindowLayout SL = wav_window_layout(c, B, g.W, is_i16);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    char *st = reinterpret_cast<char *>(d_state);
+    char *wsb = reinterpret_cast<char *>(ws);
+    long long *ctr = reinterpret_cast<long long *>(st + SL.off_ctr);
+    c->chunks_used = 1;
+    // the chunk into the ring and, if a frame completes, the window into the workspace (a step without one only commits its samples)
+    WavWindowArgs a{};
+    a.chunk = d_pcm_chunk; a.ring = st + SL.off_ring; a.ctr_in = ctr; a.ctr_out = ctr + 1;
+    a.B = B; a.chunk_len = chunk; a.J = (int)geo.J; a.R = (int)geo.R; a.Tw = p.Tw; a.Sw = (int)p.Sw; a.ring_len = SL.ring_len;
+    a.out = p.k > 0 ? wsb : nullptr;
+    HIPCHK(c, launch_wav_window_assemble(a, is_i16, s));
+    HIPCHK(c, launch_window_carry(ctr + 1, ctr, s));
+    wav_window_advance(g, p);
+    if (p.k <= 0) return 0;
+    // the model on the window's Sw samples as uvad_forward_wav runs a (B, Sw) batch: SincNet into the state (the features tap) ...
+    float *feats = reinterpret_cast<float *>(st + SL.off_feats);
+    if (int r = sincnet_impl(c, wsb, is_i16, B, p.Sw, feats, wsb + wl.off_sinc, wl.sinc_bytes, s)) return r;
+    if (p.n_emit <= 0) return 0;
+    // ... and the classifier at (B, Tw) with time chunks off (a new T every warm-up step would churn the chunk-plan cache)
+    float *lg = reinterpret_cast<float *>(wsb + wl.off_logits), *pr = reinterpret_cast<float *>(wsb + wl.off_probs);
+    const bool timing = c->timing;
+    const int chunk_mode = c->chunk_mode;
+    c->timing = false;
+    c->chunk_mode = 1;
+    const int r = classify_impl(c, feats, B, p.Tw, d_logits ? lg : nullptr, d_probs ? pr : nullptr, wsb + wl.off_cls, wl.cls_bytes, s, false,
+                                true, nullptr, 0, false, nullptr);
+    c->timing = timing;
+    c->chunk_mode = chunk_mode;
+    if (r) return r;
+    HIPCHK(c, launch_window_emit(lg, pr, B, p.Tw, p.r0, p.n_emit, d_logits, d_probs, ld_out, s));
+    return p.n_emit;
+}
+
+int uvad_window_wav_step(uvad_ctx *c, const float *d_pcm_chunk, int B, int chunk, void *d_state, float *d_logits, float *d_probs, int ld_out,
+                         void *ws, size_t ws_bytes, void *stream) {
+    return window_wav_step_impl(c, d_pcm_chunk, 0, B, chunk, d_state, d_logits, d_probs, ld_out, ws, ws_bytes, stream);
+}
+int uvad_window_wav_step_i16(uvad_ctx *c, const int16_t *d_pcm_chunk, int B, int chunk, void *d_state, float *d_logits, float *d_probs,
+                             int ld_out, void *ws, size_t ws_bytes, void *stream) {
+    return window_wav_step_impl(c, d_pcm_chunk, 1, B, chunk, d_state, d_logits, d_probs, ld_out, ws, ws_bytes, stream);
+}
+
+int uvad_window_wav_peek(const uvad_ctx *c, const void *d_state, int chunk, int *k, int64_t *replay_key) {
+    if (!c || !d_state || chunk <= 0 || !k || !replay_key) return UVAD_E_ARG;
+    auto it = c->wav_windows.find(const_cast<void *>(d_state));
+    if (it == c->wav_windows.end() || !c->has_sinc) return UVAD_E_STATE;
+    const WavWindowPlan p = wav_window_plan(c, it->second, chunk);
+    *k = p.n_emit;
+    *replay_key = p.key;
+    return UVAD_OK;
+}
+
+int uvad_window_wav_advance(uvad_ctx *c, void *d_state, int chunk) {
+    if (!c || !d_state || chunk <= 0) return UVAD_E_ARG;
+    auto it = c->wav_windows.find(d_state);
+    if (it == c->wav_windows.end() || !c->has_sinc)
+        return fail(c, UVAD_E_STATE, "uvad_window_wav_advance: call uvad_window_wav_reset on this state first");
+    const WavWindowPlan p = wav_window_plan(c, it->second, chunk);
+    wav_window_advance(it->second, p);
+    return p.n_emit;
+}
+
+int uvad_window_wav_features(uvad_ctx *c, const void *d_state, int B, float *d_feats, int *Tw, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_state || !Tw || B <= 0) return fail(c, UVAD_E_ARG, "uvad_window_wav_features: bad argument");
+    if (int r = wav_window_check_cfg(c, "uvad_window_wav_features")) return r;
+    auto it = c->wav_windows.find(const_cast<void *>(d_state));
+    if (it == c->wav_windows.end()) return fail(c, UVAD_E_STATE, "uvad_window_wav_features: call uvad_window_wav_reset on this state first");
+    const WavWindowGroup &g = it->second;
+    if (B != g.B) return fail(c, UVAD_E_ARG, "uvad_window_wav_features: B differs from the one the state was reset with");
+    *Tw = (int)std::min<int64_t>(g.n_frames, g.W);
+    if (!d_feats || *Tw == 0) return UVAD_OK;
+    const WavWindowLayout SL = wav_window_layout(c, B, g.W, g.is_i16);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(d_feats, reinterpret_cast<const char *>(d_state) + SL.off_feats, (size_t)B * *Tw * c->sc.c3 * sizeof(float),
+                             hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return UVAD_OK;
 }
 

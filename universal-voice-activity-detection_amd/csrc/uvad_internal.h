@@ -245,6 +245,18 @@ hipError_t launch_window_carry(const long long *ctr_in, long long *ctr_out, hipS
 hipError_t launch_window_emit(const float *logits_in, const float *probs_in, int B, int Tw, int r0, int n, float *logits, float *probs,
                               int ld_out, hipStream_t s);
 
+// ---- wav_window_stream.hip: the PCM ring of the waveform model's windowed stream (uvad_window_wav_step) ----------------------------
+// n_prev = *ctr_in samples have arrived before the step (read on the device); the chunk [B][chunk] is committed to the ring [B][ring]
+// (sample p in slot p % ring) and, when out != nullptr, the window of Tw frames, e = frames(n_prev + chunk) = (n - R) / J + 1, samples
+// [J (e - Tw), J (e - Tw) + Sw) is written to out [B][Sw]; *ctr_out = n_prev + chunk.  Samples of the type of the state (f32 or int16).
+struct WavWindowArgs {
+    const void *chunk; void *ring; const long long *ctr_in; long long *ctr_out;
+    int B, chunk_len, J, R, Tw, Sw;
+    long long ring_len;
+    void *out;
+};
+hipError_t launch_wav_window_assemble(const WavWindowArgs &a, int is_i16, hipStream_t s);
+
 // ---- lstm_stack.hip: every layer of a causal (one-direction, H = 128) stack for T <= LSTM_STACK_TMAX new frames in ONE launch, carried
 //      (h, c) updated in place: the streaming step (uvad_stream_step).  Exact f32.
 constexpr int LSTM_STACK_TMAX = 4, LSTM_STACK_MAX_LAYERS = 8, LSTM_STACK_MAX_LIN = 4;

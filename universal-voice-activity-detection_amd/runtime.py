@@ -42,6 +42,39 @@ def window_schedule(steps: int, chunk: int, window: int, lookahead: int = 0, fra
     return out
 
 
+def wav_frame_geometry(stride: int = 10, kernel_size: int = 251, k2: int = 5, k3: int = 5):
+    """(J, R) of a SincNet geometry (include/uvad.h): the frame step J = 27 * stride and the receptive field R, both in samples, of the
+    three valid-padding (conv, MaxPool1d(3)) stages; frames(S) = 0 if S < R else (S - R) // J + 1.  The reference's: (270, 991)."""
+    return 27 * stride, kernel_size + stride * (9 * k3 + 3 * k2 + 14)
+
+
+def wav_window_step_plan(samples: int, frames: int, chunk: int, window: int, lookahead: int, J: int = 270, R: int = 991):
+    """One step of a waveform window stream group (uvad_window_wav_step, include/uvad.h) from its counters (samples received, frames
+    complete) -> (samples, frames, (k, window_lo, window_hi, emit_lo, emit_hi, sample_lo, sample_hi)) after the step.  The model runs
+    over frames [window_lo, window_hi), i.e. samples [sample_lo, sample_hi), and the step emits frames [emit_lo, emit_hi), k of them."""
+    kmax = -(-chunk // J)
+    if lookahead < 0 or lookahead >= window:
+        raise ValueError(f"need 0 <= lookahead < window (got lookahead {lookahead}, window {window})")
+    if lookahead + kmax > window:
+        raise ValueError(f"need lookahead + ceil(chunk / J) <= window (got {lookahead} + {kmax} > {window})")
+    n = samples + chunk
+    e = 0 if n < R else (n - R) // J + 1
+    lo, hi = max(0, frames - lookahead), max(0, e - lookahead)
+    w0 = max(0, e - window)
+    s0 = J * w0
+    return n, e, (hi - lo, w0, e, lo, hi, s0, s0 + (R + J * (e - w0 - 1) if e > w0 else 0))
+
+
+def wav_window_schedule(steps: int, chunk: int, window: int, lookahead: int = 0, J: int = 270, R: int = 991):
+    """[(k, window_lo, window_hi, emit_lo, emit_hi, sample_lo, sample_hi)] for `steps` steps of `chunk` samples of a waveform window
+    stream group (wav_window_step_plan)."""
+    out, n, e = [], 0, 0
+    for _ in range(steps):
+        n, e, row = wav_window_step_plan(n, e, chunk, window, lookahead, J, R)
+        out.append(row)
+    return out
+
+
 class VadRuntime:
     def __init__(self, device, fbank: Optional[FbankConfig] = None, model: Optional[dict] = None, sincnet: Optional[dict] = None):
         """model: {"encoding_dim": int, "lstm": {...merged defaults...}, "linear": {...}} or None.
@@ -384,6 +417,42 @@ class VadRuntime:
             return out[:, :k]
 
     # ------------------------------------------------------------------ windowed streaming (any model, bidirectional included)
+    def _windowed_step(self, st, pcm_chunk, enqueue, peek, advance) -> int:
+        """One step of a windowed stream group (uvad_window_step / uvad_window_wav_step): enqueue(src) runs the step on the chunk src.
+        Without graphs, and during the warm-up (peek's replay key -1), the step is enqueued kernel by kernel; afterwards each replay
+        key is captured once into a hipGraph reading the fixed buffer st["in"], replayed, and the host counters are moved by
+        advance(ctx, state, chunk).  Graphs captured before a weight hot-swap are dropped.  Returns the step's k (checked)."""
+        graphs = st.get("graphs")
+        if graphs is not None and st.get("weights_gen") != getattr(self, "_weights_gen", 0):
+            graphs.clear()           # captured before a weight hot-swap: their kernel nodes point at freed buffers
+            st["weights_gen"] = getattr(self, "_weights_gen", 0)
+        key = -1
+        if graphs is not None:
+            kk, rk = C.c_int(), C.c_int64()
+            self._check(peek(self.ctx, st["state"].data_ptr(), st["chunk"], C.byref(kk), C.byref(rk)))
+            key = rk.value
+        if key < 0:
+            k = enqueue(pcm_chunk)
+        else:
+            st["in"].copy_(pcm_chunk)                    # the graphs read their input from a fixed buffer
+            g = graphs.get(key)
+            if g is None:
+                cur = torch.cuda.current_stream(self.device)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):                # capture: the step's launches are recorded, not run; its counters advance
+                    k = enqueue(st["in"])
+                if k < 0:
+                    self._check(k)
+                graphs[key] = g
+                torch.cuda.current_stream(self.device).wait_stream(cur)
+                g.replay()                               # now run it
+            else:
+                g.replay()
+                k = advance(self.ctx, st["state"].data_ptr(), st["chunk"])
+        if k < 0:
+            self._check(k)
+        return k
+
     def window_stream_open(self, B: int, chunk: int, window: int = 500, lookahead: int = 0, graphs: bool = False):
         """Allocate and reset a windowed stream group (uvad_window_reset): B lock-step feeds of `chunk` samples per step, the model
         run from zero state over the last `window` frames, frames emitted `lookahead` frames behind the newest complete one.
@@ -417,35 +486,7 @@ class VadRuntime:
                 return self.lib.uvad_window_step(self.ctx, src.data_ptr(), st["B"], st["chunk"], st["state"].data_ptr(), out.data_ptr(),
                                                  None, out.shape[1], st["ws"].data_ptr(), st["ws"].numel(), self._stream())
 
-            graphs = st.get("graphs")
-            if graphs is not None and st.get("weights_gen") != getattr(self, "_weights_gen", 0):
-                graphs.clear()           # captured before a weight hot-swap: their kernel nodes point at freed buffers
-                st["weights_gen"] = getattr(self, "_weights_gen", 0)
-            key = -1
-            if graphs is not None:
-                kk, rk = C.c_int(), C.c_int64()
-                self._check(self.lib.uvad_window_peek(self.ctx, st["state"].data_ptr(), st["chunk"], C.byref(kk), C.byref(rk)))
-                key = rk.value
-            if key < 0:
-                k = enqueue(pcm_chunk)
-            else:
-                st["in"].copy_(pcm_chunk)                    # the graphs read their input from a fixed buffer
-                g = graphs.get(key)
-                if g is None:
-                    cur = torch.cuda.current_stream(self.device)
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):                # capture: the step's launches are recorded, not run; its counters advance
-                        k = enqueue(st["in"])
-                    if k < 0:
-                        self._check(k)
-                    graphs[key] = g
-                    torch.cuda.current_stream(self.device).wait_stream(cur)
-                    g.replay()                               # now run it
-                else:
-                    g.replay()
-                    k = self.lib.uvad_window_advance(self.ctx, st["state"].data_ptr(), st["chunk"])
-            if k < 0:
-                self._check(k)
+            k = self._windowed_step(st, pcm_chunk, enqueue, self.lib.uvad_window_peek, self.lib.uvad_window_advance)
             if k != k_want:
                 raise RuntimeError(f"uvad_window_step emitted {k} frames, the schedule says {k_want}")
             st["samples"], st["frames"] = n, e
@@ -460,6 +501,75 @@ class VadRuntime:
             if tw.value:
                 self._check(self.lib.uvad_window_features(self.ctx, st["state"].data_ptr(), st["B"], feats.data_ptr(), C.byref(tw),
                                                           self._stream()))
+            return feats
+
+    # ------------------------------------------------------------------ windowed streaming of the waveform model (PyanNet)
+    def wav_window_geometry(self):
+        """(J, R) of this runtime's SincNet: frame step and receptive field in samples (wav_frame_geometry)."""
+        if self._sn_c is None:
+            raise RuntimeError("this runtime was created without a SincNet configuration")
+        q = self._sn_c
+        return wav_frame_geometry(q.stride, q.kernel_size, q.k2, q.k3)
+
+    def wav_window_stream_open(self, B: int, chunk: int, window: int = 293, lookahead: int = 0, graphs: bool = False,
+                               dtype=torch.float32):
+        """Allocate and reset a waveform window stream group (uvad_window_wav_reset): B lock-step feeds of `chunk` PCM samples per
+        step (dtype torch.float32, or torch.int16 read as q / 32768), the model run from zero state over the last `window` frames,
+        frames emitted `lookahead` frames behind the newest complete one.  graphs: once the window is full, capture each distinct step
+        (uvad_window_wav_peek's replay key) into a hipGraph and replay it."""
+        if dtype not in (torch.float32, torch.int16):
+            raise ValueError(f"dtype must be torch.float32 or torch.int16, got {dtype}")
+        J, R = self.wav_window_geometry()
+        wav_window_step_plan(0, 0, chunk, window, lookahead, J, R)          # the limits, before anything is allocated
+        i16 = int(dtype == torch.int16)
+        with torch.cuda.device(self.device):
+            nbytes = int(self.lib.uvad_window_wav_state_bytes(self.ctx, B, window, i16))
+            if nbytes == 0:
+                raise RuntimeError("waveform windowed streaming needs a runtime built with a model and a SincNet configuration")
+            state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._check(self.lib.uvad_window_wav_reset(self.ctx, state.data_ptr(), B, window, lookahead, i16, self._stream()))
+            ws = torch.empty(int(self.lib.uvad_window_wav_workspace_bytes(self.ctx, B, chunk, window)), dtype=torch.uint8,
+                             device=self.device)
+            return {"state": state, "ws": ws, "B": B, "chunk": chunk, "window": window, "lookahead": lookahead, "J": J, "R": R,
+                    "dtype": dtype, "samples": 0, "frames": 0,
+                    "out": torch.empty((B, -(-chunk // J)), dtype=torch.float32, device=self.device),
+                    "in": torch.empty((B, chunk), dtype=dtype, device=self.device),
+                    "graphs": {} if graphs else None, "weights_gen": getattr(self, "_weights_gen", 0)}
+
+    def wav_window_stream_step(self, st, pcm_chunk: "torch.Tensor") -> "torch.Tensor":
+        """pcm_chunk (B, chunk) on the GPU, of the dtype the group was opened with -> logits (B, k) of the k frames this step emits
+        (wav_window_step_plan; a view of a buffer that the next step overwrites).  With graphs=True warm-up steps are enqueued kernel by
+        kernel and the steady-state ones replay one hipGraph per replay key, then move the counters with uvad_window_wav_advance."""
+        with torch.cuda.device(self.device):
+            if not torch.is_tensor(pcm_chunk) or pcm_chunk.device != self.device or pcm_chunk.dtype != st["dtype"]:
+                raise RuntimeError(f"pcm_chunk must be a {st['dtype']} tensor on {self.device}")
+            pcm_chunk = pcm_chunk.contiguous()
+            if tuple(pcm_chunk.shape) != (st["B"], st["chunk"]):
+                raise ValueError(f"expected a ({st['B']}, {st['chunk']}) chunk, got {tuple(pcm_chunk.shape)}")
+            n, e, (k_want, *_) = wav_window_step_plan(st["samples"], st["frames"], st["chunk"], st["window"], st["lookahead"],
+                                                      st["J"], st["R"])
+            out = st["out"]
+            fn = self.lib.uvad_window_wav_step_i16 if st["dtype"] == torch.int16 else self.lib.uvad_window_wav_step
+
+            def enqueue(src):
+                return fn(self.ctx, src.data_ptr(), st["B"], st["chunk"], st["state"].data_ptr(), out.data_ptr(), None, out.shape[1],
+                          st["ws"].data_ptr(), st["ws"].numel(), self._stream())
+
+            k = self._windowed_step(st, pcm_chunk, enqueue, self.lib.uvad_window_wav_peek, self.lib.uvad_window_wav_advance)
+            if k != k_want:
+                raise RuntimeError(f"uvad_window_wav_step emitted {k} frames, the schedule says {k_want}")
+            st["samples"], st["frames"] = n, e
+            return out[:, :k]
+
+    def wav_window_features(self, st) -> "torch.Tensor":
+        """The SincNet output (B, Tw, c3) of the window the model last ran on (debug tap, uvad_window_wav_features)."""
+        with torch.cuda.device(self.device):
+            tw = C.c_int()
+            self._check(self.lib.uvad_window_wav_features(self.ctx, st["state"].data_ptr(), st["B"], None, C.byref(tw), self._stream()))
+            feats = torch.empty((st["B"], tw.value, self._sn_c.c3), dtype=torch.float32, device=self.device)
+            if tw.value:
+                self._check(self.lib.uvad_window_wav_features(self.ctx, st["state"].data_ptr(), st["B"], feats.data_ptr(), C.byref(tw),
+                                                              self._stream()))
             return feats
 
     def set_gemm_mode(self, mode: str):
