@@ -232,6 +232,28 @@ int uvad_median_filter_lens(uvad_ctx *, const float *d_probs, int B, int T, cons
 int uvad_label_runs_lens(uvad_ctx *, const uint8_t *d_labels, int B, int T, const int32_t *d_lens, int max_runs, int32_t *d_runs,
                          int32_t *d_counts, void *stream);
 
+/* The waveform model (PyanNet: SincNet + classifier) with per-row sample counts, the semantics above applied to waveforms.
+ *   - d_nsamp: device int64 [B], clamped to [0, S].  Row b has T_b = uvad_sincnet_num_frames(S_b) frames; at t < T_b its features /
+ *     outputs equal uvad_sincnet / uvad_forward_wav on wav[b, :S_b] alone (the waveform norm and the three instance norms are taken over
+ *     the row's own samples / positions), at t >= T_b they are exactly +0.  A row with T_b = 0 (S_b < the receptive field, S_b = 0 too)
+ *     is all +0.  Samples >= S_b are never read.  Outputs are [B][frames(S)].
+ *   - Features: bit-identical to the dense call on the row when both run the same SincNet form.  The form is chosen on the padded S
+ *     (the f16 range guard bounds every row by it), so a lens call can run the exact-f32 form where a row alone would run the split-f16
+ *     form; uvad_get_sincnet_form says which ran.  The forward is bit-identical to the dense call on the row for GEMM modes 0 and 2 and a
+ *     pinned recurrent tile; modes 1 and 3 agree to rounding (launch-size kernel choice, as uvad_forward_lens).
+ *   - The SincNet workgroups share the rows' valid tiles only: padding costs no conv work.  The classifier GEMMs still run over all rows.
+ *   - Workspace: uvad_sincnet_workspace_bytes(B, S) (+ uvad_workspace_bytes(B, frames(S)) for the forward), as for the dense calls.
+ *     The call is refused only when S itself gives no frame.  d_nsamp == NULL: UVAD_E_ARG; no SincNet configuration or tensors:
+ *     UVAD_E_STATE; a workspace too small: UVAD_E_WORKSPACE. */
+int uvad_sincnet_lens(uvad_ctx *, const float *d_wav, int B, int64_t S, const int64_t *d_nsamp, float *d_feats, void *d_workspace,
+                      size_t ws_bytes, void *stream);
+int uvad_sincnet_lens_i16(uvad_ctx *, const int16_t *d_wav, int B, int64_t S, const int64_t *d_nsamp, float *d_feats, void *d_workspace,
+                          size_t ws_bytes, void *stream);
+int uvad_forward_wav_lens(uvad_ctx *, const float *d_wav, int B, int64_t S, const int64_t *d_nsamp, float *d_logits, float *d_probs,
+                          void *d_workspace, size_t ws_bytes, void *stream);
+int uvad_forward_wav_lens_i16(uvad_ctx *, const int16_t *d_wav, int B, int64_t S, const int64_t *d_nsamp, float *d_logits, float *d_probs,
+                              void *d_workspace, size_t ws_bytes, void *stream);
+
 /* Replaces: median_filter (src/utils/helper.py:66-97) as used by VadModel.predict_step
  * (vad_engine.py:204-211): threshold 0.5 then odd `kernel`-tap median, zero padded edges.
  * d_probs [B][T] -> d_labels [B][T] uint8 (0/1). */

@@ -45,16 +45,30 @@ __device__ __forceinline__ float half_sum(float v, bool upper) {
 
 constexpr int YS = 97;        // LDS row stride of the conv-output staging tile
 
+// LENS (uvad_sincnet_lens): row b's statistics over its first row_n[b] samples (0: scale = shift = 0, nothing read).  The sums take the
+// order of the 16-byte-aligned path even where the row start is not aligned (rows of a padded batch), so every row reaches the bits of a
+// dense call on that row alone in its own (aligned) buffer for any f32 samples, not only for sums that are exact.
+template <bool LENS>
 __global__ __launch_bounds__(1024) void wav_stats_kernel(const float *wav, long long S, long long row_stride, const float *gamma,
-                                                         const float *beta, float eps, float *scale, float *shift) {
+                                                         const float *beta, float eps, float *scale, float *shift, SincRowTArg<LENS> row_n) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const float *x = wav + (size_t)b * row_stride;
+    if constexpr (LENS) {
+        S = row_n[b];
+        if (S <= 0) {
+            if (tid == 0) { scale[b] = 0.f; shift[b] = 0.f; }
+            return;
+        }
+    }
     double s = 0.0, ss = 0.0;
     long long i0 = 0;
-    if ((reinterpret_cast<uintptr_t>(x) & 15) == 0) {   // 16-byte loads, 1024 threads: the whole row is in flight at once
+    const bool vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+    if (vec || LENS) {   // 16-byte loads, 1024 threads: the whole row is in flight at once
         const long long n4 = S >> 2;
         for (long long i = tid; i < n4; i += 1024) {
-            const float4 v = reinterpret_cast<const float4 *>(x)[i];
+            float4 v;
+            if (!LENS || vec) v = reinterpret_cast<const float4 *>(x)[i];
+            else v = make_float4(x[4 * i], x[4 * i + 1], x[4 * i + 2], x[4 * i + 3]);
             s += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
             ss += ((double)v.x * v.x + (double)v.y * v.y) + ((double)v.z * v.z + (double)v.w * v.w);
         }
@@ -87,10 +101,19 @@ __global__ __launch_bounds__(1024) void wav_stats_kernel(const float *wav, long 
 // row): every term of the sum is a multiple of 2^-15 and every square a multiple of 2^-30, each of magnitude <= 1, so a 53-bit significand
 // holds every partial sum.  Both kernels therefore reach the same (s, ss) and, through the same closing arithmetic, (scale, shift) that are
 // bit-identical to the f32 call on q.float() / 32768 for S < 2^23; longer rows get the exact statistics here.
+// LENS: over the first row_n[b] samples, as wav_stats_kernel (the integer sums are exact in any order)
+template <bool LENS>
 __global__ __launch_bounds__(1024) void wav_stats_i16_kernel(const int16_t *wav, long long S, long long row_stride, const float *gamma,
-                                                             const float *beta, float eps, float *scale, float *shift) {
+                                                             const float *beta, float eps, float *scale, float *shift, SincRowTArg<LENS> row_n) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const int16_t *x = wav + (size_t)b * row_stride;
+    if constexpr (LENS) {
+        S = row_n[b];
+        if (S <= 0) {
+            if (tid == 0) { scale[b] = 0.f; shift[b] = 0.f; }
+            return;
+        }
+    }
     long long s = 0, ss = 0;
     long long i0 = 0;
     if ((reinterpret_cast<uintptr_t>(x) & 15) == 0) {   // 16-byte loads (8 samples)
@@ -139,8 +162,10 @@ __device__ __forceinline__ float wav_sample(float v) { return v; }
 __device__ __forceinline__ float wav_sample(int16_t v) { return (float)v * 0x1p-15f; }
 
 // I16: the single-channel stage reads the waveform as int16 (a.in_i16), converted in the prefetch with wav_sample
-template <int NT, bool CIN1, int EPT, int WAVES, bool I16 = false>
-__global__ __launch_bounds__(WAVES * 64) void conv_pool_kernel(SincConvArgs a) {
+// LENS (uvad_sincnet_lens): the workgroups share the valid (row, tile) pairs of the rows' own lengths (SincRowCursor); the window and the
+// pooled outputs are bounded by the row's Lin / Lpool (a.Lin / a.Lpool stay the padded strides): each tile is a dense call's on that row.
+template <int NT, bool CIN1, int EPT, int WAVES, bool I16 = false, bool LENS = false>
+__global__ __launch_bounds__(WAVES * 64) void conv_pool_kernel(SincArgsT<LENS, SincConvArgs> a) {
     static_assert(CIN1 || !I16, "int16 input is the waveform: single-channel stage only");
     using Tin = typename std::conditional<I16, int16_t, float>::type;
     constexpr int NW = NT * 32;
@@ -164,7 +189,8 @@ __global__ __launch_bounds__(WAVES * 64) void conv_pool_kernel(SincConvArgs a) {
 
     // Persistent workgroups (one per CU: the filter matrix takes most of the LDS): workgroup w owns the contiguous
     // range [g_begin, g_end) of the B*ntiles (utterance, tile) pairs, so the filter matrix is staged once per launch.
-    const long long total = (long long)a.B * a.ntiles;
+    long long total;
+    if constexpr (LENS) total = a.rows.prefix[a.B]; else total = (long long)a.B * a.ntiles;
     const long long per = (total + gridDim.x - 1) / gridDim.x;
     const long long g_begin = per * blockIdx.x;
     const long long g_end = g_begin + per < total ? g_begin + per : total;
@@ -189,25 +215,42 @@ __global__ __launch_bounds__(WAVES * 64) void conv_pool_kernel(SincConvArgs a) {
     float pre[EPT];
     const Tin *in_base;
     if constexpr (I16) in_base = a.in_i16; else in_base = a.in;
-#define UVAD_SN_PREFETCH(g_)                                                               \
+#define UVAD_SN_PREFETCH_AT(b_, tile_, lin_)                                               \
     {   /* 32-bit element offsets from the utterance's (wave-uniform) base: one address VGPR per load */ \
-        const int b_ = (int)((g_) / a.ntiles), tile_ = (int)((g_) - (long long)b_ * a.ntiles); \
-        const Tin *inb_ = in_base + (size_t)b_ * a.in_bstride;                             \
-        const int x0_ = tile_ * TA * a.stride;                                             \
+        const Tin *inb_ = in_base + (size_t)(b_) * a.in_bstride;                           \
+        const int x0_ = (tile_) * TA * a.stride;                                           \
         int x_ = xs0;                                                                      \
         unsigned off_ = (unsigned)ci0 * (unsigned)a.Lin + (unsigned)(x0_ + xs0);           \
         _Pragma("unroll") for (int e = 0; e < EPT; ++e) {                                  \
-            const bool ok_ = tid + NTHR * e < nelem && x0_ + x_ < a.Lin;                   \
+            const bool ok_ = tid + NTHR * e < nelem && x0_ + x_ < (lin_);                  \
             pre[e] = wav_sample(inb_[ok_ ? off_ : 0u]);                                    \
             x_ += rstep; off_ += (unsigned)qstep * (unsigned)a.Lin + (unsigned)rstep;      \
             if (x_ >= XW) { x_ -= XW; off_ += (unsigned)(a.Lin - XW); }                    \
         }                                                                                  \
     }
-    UVAD_SN_PREFETCH(g_begin)
+#define UVAD_SN_PREFETCH(g_)                                                               \
+    {                                                                                      \
+        const int pb_ = (int)((g_) / a.ntiles), pt_ = (int)((g_) - (long long)pb_ * a.ntiles); \
+        UVAD_SN_PREFETCH_AT(pb_, pt_, a.Lin)                                            \
+    }
+    SincRowCursor cur{}, nxt{};   // LENS: the pair g and the one after it
+    if constexpr (LENS) {
+        cur = sinc_cursor_seek(a.rows, a.B, g_begin);
+        UVAD_SN_PREFETCH_AT(cur.b, cur.tile, cur.lin)
+    } else {
+        UVAD_SN_PREFETCH(g_begin)
+    }
 
     int cur_b = -1;
     for (long long g = g_begin; g < g_end; ++g) {
-        const int b = (int)(g / a.ntiles), tile = (int)(g - (long long)b * a.ntiles);
+        int b, tile, lin, lpool;
+        if constexpr (LENS) {
+            b = cur.b; tile = cur.tile; lin = cur.lin; lpool = cur.lpool;
+            nxt = cur;
+            if (g + 1 < g_end) sinc_cursor_next(a.rows, g + 1, nxt);
+        } else {
+            b = (int)(g / a.ntiles); tile = (int)(g - (long long)b * a.ntiles); lin = a.Lin; lpool = a.Lpool;
+        }
         __syncthreads();   // filter matrix staged / previous tile's pooled reads of xy are complete
         if (b != cur_b) {  // (scale, shift) of this utterance's input norm
             cur_b = b;
@@ -225,7 +268,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv_pool_kernel(SincConvArgs a) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     ns[j] = nrm[ci < a.Cin ? ci : 0];
-                    in[j] = x0 + x < a.Lin;
+                    in[j] = x0 + x < lin;
                     ci += qstep; x += rstep;
                     if (x >= XW) { x -= XW; ++ci; }
                 }
@@ -242,7 +285,9 @@ __global__ __launch_bounds__(WAVES * 64) void conv_pool_kernel(SincConvArgs a) {
         }
         __syncthreads();
         // the next tile's window is fetched now and lands while the matrix cores work on this one
-        if (g + 1 < g_end) UVAD_SN_PREFETCH(g + 1)
+        if (g + 1 < g_end) {
+            if constexpr (LENS) UVAD_SN_PREFETCH_AT(nxt.b, nxt.tile, nxt.lin) else UVAD_SN_PREFETCH(g + 1)
+        }
 
         f32x16 acc[NT];
 #pragma unroll
@@ -327,7 +372,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv_pool_kernel(SincConvArgs a) {
             __syncthreads();
             const int cap = ph == PHASES - 1 ? PT - 32 * (PHASES - 1) : 32;
             const int p0 = tile * PT + 32 * ph;
-            int nt = a.Lpool - p0 < cap ? a.Lpool - p0 : cap;
+            int nt = lpool - p0 < cap ? lpool - p0 : cap;
             if (nt < 0) nt = 0;
             const float inv_nt = nt > 0 ? 1.0f / (float)nt : 0.f;
             constexpr int PASSES = (NW + 2 * WAVES - 1) / (2 * WAVES);
@@ -349,17 +394,34 @@ __global__ __launch_bounds__(WAVES * 64) void conv_pool_kernel(SincConvArgs a) {
                 }
             }
         }
+        if constexpr (LENS) cur = nxt;
     }
+#undef UVAD_SN_PREFETCH
+#undef UVAD_SN_PREFETCH_AT
 }
 
 // per-tile (sum, M2) partials, combined in tile order -> per (b, c) affine of the instance norm:
 //   y = (x - mean) / sqrt(var + eps) * gamma + beta = x * scale + shift      (biased variance, torch InstanceNorm1d)
+// LENS: row b walks its own prefix[b + 1] - prefix[b] tiles over L_b = lpool[b] positions (`ntiles` stays the padded row
+// stride of the partials): the groups and order of a dense call of that length.  L_b = 0: scale = shift = 0.
+template <bool LENS>
 __global__ __launch_bounds__(128) void norm_finalize_kernel(const float *partials, int ntiles, int pt, int phases, int NW, int C, int L,
-                                                            const float *gamma, const float *beta, float eps, float *scale, float *shift) {
+                                                            const float *gamma, const float *beta, float eps, float *scale, float *shift,
+                                                            SincRowsArg<LENS> rows) {
     const int b = blockIdx.x, n = threadIdx.x;
     if (n >= C) return;
+    int nrow = ntiles;
+    if constexpr (LENS) {
+        nrow = rows.prefix[b + 1] - rows.prefix[b];
+        L = rows.lpool[b];
+        if (L <= 0) {
+            scale[(size_t)b * C + n] = 0.f;
+            shift[(size_t)b * C + n] = 0.f;
+            return;
+        }
+    }
     double mean = 0.0, M2 = 0.0, cnt = 0.0;
-    for (int t = 0; t < ntiles; ++t)
+    for (int t = 0; t < nrow; ++t)
         for (int ph = 0; ph < phases; ++ph) {   // the statistics groups of conv_pool_kernel, in position order
             const int start = t * pt + 32 * ph, cap = ph == phases - 1 ? pt - 32 * (phases - 1) : 32;
             const int ni = L - start < cap ? L - start : cap;
@@ -378,17 +440,74 @@ __global__ __launch_bounds__(128) void norm_finalize_kernel(const float *partial
 }
 
 // last norm + leaky_relu and the "batch feature frames -> batch frames feature" rearrange (PyanNet.py:179)
+// LENS: frames t >= row_T[b] are +0, and P is not read there.
+template <bool LENS>
 __global__ __launch_bounds__(256) void sinc_out_kernel(const float *P, const float *scale, const float *shift, int B, int C, int L, float slope,
-                                                       float *feats, int ldf) {
+                                                       float *feats, int ldf, SincRowTArg<LENS> row_T) {
     const long long n = (long long)B * L * C;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const int c = (int)(i % C);
         const long long bt = i / C;
         const int t = (int)(bt % L), b = (int)(bt / L);
+        if constexpr (LENS) {
+            if (t >= row_T[b]) { feats[((size_t)b * L + t) * ldf + c] = 0.f; continue; }
+        }
         float v = __builtin_fmaf(P[((size_t)b * C + c) * L + t], scale[(size_t)b * C + c], shift[(size_t)b * C + c]);
         v = v >= 0.f ? v : v * slope;
         feats[((size_t)b * L + t) * ldf + c] = v;
     }
+}
+
+// Per-row geometry of a lens call (SincGeoArgs): one workgroup; thread t takes a contiguous run of rows, the six tile counts are scanned
+// across the workgroup (Hillis-Steele in LDS) and each thread writes its rows' exclusive prefixes.  The floor chain is sinc_carve's.
+constexpr int GEO_THR = 1024;
+__global__ __launch_bounds__(GEO_THR) void sinc_row_geometry_kernel(SincGeoArgs g) {
+    __shared__ int scan[2][6][GEO_THR];
+    const int tid = threadIdx.x, ld = g.B + 1;
+    const int per = (g.B + GEO_THR - 1) / GEO_THR, r0 = tid * per < g.B ? tid * per : g.B, r1 = r0 + per < g.B ? r0 + per : g.B;
+    int *T = g.geo;
+    auto arr = [&](int stage, int k) { return g.geo + (size_t)(1 + 6 * stage + k) * ld; };   // k: 0 Lin, 1 Lpool, 2 / 3 split tiles / prefix, 4 / 5 exact
+    int own[6] = {0, 0, 0, 0, 0, 0};
+    for (int b = r0; b < r1; ++b) {
+        long long n = g.nsamp[b];
+        n = n < 0 ? 0 : n > g.S ? g.S : n;
+        long long lin[3], lpool[3], L = n;
+        for (int i = 0; i < 3; ++i) {
+            const int st = i == 0 ? g.stride0 : 1;
+            lin[i] = L;
+            const long long lconv = L >= g.kw[i] ? (L - g.kw[i]) / st + 1 : 0;
+            lpool[i] = lconv / 3;
+            L = lpool[i];
+        }
+        const bool any = lpool[2] > 0;   // a row without frames is not touched by any stage
+        T[b] = any ? (int)lpool[2] : 0;
+        for (int i = 0; i < 3; ++i) {
+            const int lp = any ? (int)lpool[i] : 0;
+            const int t16 = (lp + 63) / 64, t32 = (lp + g.pt[i] - 1) / g.pt[i];
+            arr(i, 0)[b] = any ? (int)lin[i] : 0;
+            arr(i, 1)[b] = lp;
+            arr(i, 2)[b] = t16;
+            arr(i, 4)[b] = t32;
+            own[2 * i] += t16;
+            own[2 * i + 1] += t32;
+        }
+    }
+    int src = 0;
+    for (int k = 0; k < 6; ++k) scan[0][k][tid] = own[k];
+    __syncthreads();
+    for (int d = 1; d < GEO_THR; d <<= 1) {   // inclusive scan of the per-thread sums
+        for (int k = 0; k < 6; ++k) scan[src ^ 1][k][tid] = scan[src][k][tid] + (tid >= d ? scan[src][k][tid - d] : 0);
+        src ^= 1;
+        __syncthreads();
+    }
+    for (int i = 0; i < 3; ++i)
+        for (int f = 0; f < 2; ++f) {
+            const int k = 2 * i + f;
+            int run = scan[src][k][tid] - own[k];
+            int *cnt = arr(i, 2 + 2 * f), *pre = arr(i, 3 + 2 * f);
+            for (int b = r0; b < r1; ++b) { pre[b] = run; run += cnt[b]; }
+            if (tid == GEO_THR - 1) pre[g.B] = scan[src][k][tid];
+        }
 }
 
 }  // namespace
@@ -421,18 +540,26 @@ SincConvPlan sinc_conv_plan(const SincConvArgs &a) {
 }
 
 hipError_t launch_wav_stats(const float *wav, int B, long long S, long long row_stride, const float *gamma, const float *beta, float eps,
-                            float *scale, float *shift, hipStream_t s) {
-    hipLaunchKernelGGL(wav_stats_kernel, dim3(B), dim3(1024), 0, s, wav, S, row_stride, gamma, beta, eps, scale, shift);
+                            float *scale, float *shift, hipStream_t s, const int *row_n) {
+    if (row_n) hipLaunchKernelGGL(wav_stats_kernel<true>, dim3(B), dim3(1024), 0, s, wav, S, row_stride, gamma, beta, eps, scale, shift, row_n);
+    else hipLaunchKernelGGL(wav_stats_kernel<false>, dim3(B), dim3(1024), 0, s, wav, S, row_stride, gamma, beta, eps, scale, shift, SincNoRows{});
     return hipGetLastError();
 }
 
 hipError_t launch_wav_stats(const int16_t *wav, int B, long long S, long long row_stride, const float *gamma, const float *beta, float eps,
-                            float *scale, float *shift, hipStream_t s) {
-    hipLaunchKernelGGL(wav_stats_i16_kernel, dim3(B), dim3(1024), 0, s, wav, S, row_stride, gamma, beta, eps, scale, shift);
+                            float *scale, float *shift, hipStream_t s, const int *row_n) {
+    if (row_n) hipLaunchKernelGGL(wav_stats_i16_kernel<true>, dim3(B), dim3(1024), 0, s, wav, S, row_stride, gamma, beta, eps, scale, shift, row_n);
+    else hipLaunchKernelGGL(wav_stats_i16_kernel<false>, dim3(B), dim3(1024), 0, s, wav, S, row_stride, gamma, beta, eps, scale, shift, SincNoRows{});
     return hipGetLastError();
 }
 
-hipError_t launch_sinc_conv(const SincConvArgs &a, hipStream_t s) {
+hipError_t launch_sinc_row_geometry(const SincGeoArgs &g, hipStream_t s) {
+    if (g.B <= 0 || !g.nsamp || !g.geo) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sinc_row_geometry_kernel, dim3(1), dim3(GEO_THR), 0, s, g);
+    return hipGetLastError();
+}
+
+hipError_t launch_sinc_conv(const SincConvArgs &a, hipStream_t s, const SincRows *rows) {
     const int NT = (a.Cout + 31) / 32;
     if (NT != 2 && NT != 3) return hipErrorInvalidValue;
     const SincConvPlan plan = sinc_conv_plan(a);
@@ -450,13 +577,18 @@ hipError_t launch_sinc_conv(const SincConvArgs &a, hipStream_t s) {
     if (ept > 48 || (cin1 && ept > 8)) return hipErrorInvalidValue;   // uvad_sincnet_configure rejects these geometries
     if (a.in_i16 && !cin1) return hipErrorInvalidValue;               // int16 is the waveform: the single-channel stage only
     const bool i16 = a.in_i16 != nullptr;
-#define UVAD_SINC_LAUNCH_T(NT_, C1_, EPT_, W_, I16_)                                                                       \
+#define UVAD_SINC_LAUNCH_L(NT_, C1_, EPT_, W_, I16_, L_, ROWS_)                                                            \
     {                                                                                                                      \
-        auto k = conv_pool_kernel<NT_, C1_, EPT_, W_, I16_>;                                                               \
+        auto k = conv_pool_kernel<NT_, C1_, EPT_, W_, I16_, L_>;                                                           \
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         if (e != hipSuccess) return e;                                                                                     \
-        hipLaunchKernelGGL(k, grid, block, lds, s, a);                                                                     \
+        hipLaunchKernelGGL(k, grid, block, lds, s, ROWS_);                                                                 \
     }
+    SincLensArgs<SincConvArgs> la{};
+    static_cast<SincConvArgs &>(la) = a;
+    if (rows) la.rows = *rows;
+#define UVAD_SINC_LAUNCH_T(NT_, C1_, EPT_, W_, I16_) \
+    { if (rows) UVAD_SINC_LAUNCH_L(NT_, C1_, EPT_, W_, I16_, true, la) else UVAD_SINC_LAUNCH_L(NT_, C1_, EPT_, W_, I16_, false, a) }
 #define UVAD_SINC_LAUNCH(NT_, C1_, EPT_, W_) UVAD_SINC_LAUNCH_T(NT_, C1_, EPT_, W_, false)
 #define UVAD_SINC_LAUNCH1(NT_, W_) { if (i16) UVAD_SINC_LAUNCH_T(NT_, true, 8, W_, true) else UVAD_SINC_LAUNCH_T(NT_, true, 8, W_, false) }
     if (cin1 && plan.waves == 8) {
@@ -474,22 +606,29 @@ hipError_t launch_sinc_conv(const SincConvArgs &a, hipStream_t s) {
 #undef UVAD_SINC_LAUNCH1
 #undef UVAD_SINC_LAUNCH
 #undef UVAD_SINC_LAUNCH_T
+#undef UVAD_SINC_LAUNCH_L
     return hipGetLastError();
 }
 
 hipError_t launch_norm_finalize(const float *partials, int B, int ntiles, int pt, int phases, int NW, int C, int L, const float *gamma,
-                                const float *beta, float eps, float *scale, float *shift, hipStream_t s) {
-    hipLaunchKernelGGL(norm_finalize_kernel, dim3(B), dim3(128), 0, s, partials, ntiles, pt, phases, NW, C, L, gamma, beta, eps, scale, shift);
+                                const float *beta, float eps, float *scale, float *shift, hipStream_t s, const SincRows *rows) {
+    if (rows)
+        hipLaunchKernelGGL(norm_finalize_kernel<true>, dim3(B), dim3(128), 0, s, partials, ntiles, pt, phases, NW, C, L, gamma, beta, eps, scale, shift,
+                           *rows);
+    else
+        hipLaunchKernelGGL(norm_finalize_kernel<false>, dim3(B), dim3(128), 0, s, partials, ntiles, pt, phases, NW, C, L, gamma, beta, eps, scale, shift,
+                           SincNoRows{});
     return hipGetLastError();
 }
 
 hipError_t launch_sinc_out(const float *P, const float *scale, const float *shift, int B, int C, int L, float slope, float *feats, int ldf,
-                           hipStream_t s) {
+                           hipStream_t s, const int *row_T) {
     const long long n = (long long)B * L * C;
     if (n <= 0) return hipSuccess;
     long long g = (n + 255) / 256;
     if (g > 8192) g = 8192;
-    hipLaunchKernelGGL(sinc_out_kernel, dim3((int)g), dim3(256), 0, s, P, scale, shift, B, C, L, slope, feats, ldf);
+    if (row_T) hipLaunchKernelGGL(sinc_out_kernel<true>, dim3((int)g), dim3(256), 0, s, P, scale, shift, B, C, L, slope, feats, ldf, row_T);
+    else hipLaunchKernelGGL(sinc_out_kernel<false>, dim3((int)g), dim3(256), 0, s, P, scale, shift, B, C, L, slope, feats, ldf, SincNoRows{});
     return hipGetLastError();
 }
 

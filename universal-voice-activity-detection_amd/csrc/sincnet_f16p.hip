@@ -76,8 +76,10 @@ __device__ __forceinline__ void split2(float v, _Float16 &hi, _Float16 &lo) {
 
 // I16 (stage 1 only): the waveform is int16 (a.in_i16); a chunk of 8 samples is one 16-byte load, kept raw in registers until the staging
 // converts it as (float)q * 2^-15 -- exactly the f32 value of q / 32768, so the staged f16 planes are the f32 call's bits.
-template <int ST, bool I16 = false>
-__global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
+// LENS (uvad_sincnet_lens): the workgroups share the valid (row, tile) pairs of the rows' own lengths (SincRowCursor); staging and the
+// valid_tile masks are bounded by the row's Lin / Lpool, so a tile is the tile of a dense call on that row alone, bit for bit.
+template <int ST, bool I16 = false, bool LENS = false>
+__global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincArgsT<LENS, SincF16Args> a) {
     static_assert(ST == 1 || !I16, "int16 input is the waveform: stage 1 only");
     using S = Stage<ST>;
     constexpr int KS = S::KS;
@@ -87,7 +89,8 @@ __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
     const int n = lane & 15, q = lane >> 4;            // accumulator layout: channel n of the wave's tile, row quarter q
     const int ar = lane & 15, akq = lane >> 4;         // A operand: MFMA row ar (quarter ar >> 2, position ar & 3 inside it), k quarter akq
 
-    const long long total = (long long)a.B * a.ntiles;
+    long long total;
+    if constexpr (LENS) total = a.rows.prefix[a.B]; else total = (long long)a.B * a.ntiles;
     const long long per = (total + gridDim.x - 1) / gridDim.x;
     const long long g_begin = per * blockIdx.x;
     const long long g_end = g_begin + per < total ? g_begin + per : total;
@@ -144,11 +147,14 @@ __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
     // memory path takes 17 x 4 KiB from four waves at once -- with the matrix pipe idle.
     const float *pf_src = a.in;
     int pf_rows = 0;
-    auto pf_setup = [&](long long gi) __attribute__((always_inline)) {
-        const int b = (int)(gi / a.ntiles), tile = (int)(gi - (long long)b * a.ntiles);
-        const long long x0s = (long long)tile * TILE_POS, left = (long long)a.Lin - x0s;
+    auto pf_setup_at = [&](int b, int tile, int lin) __attribute__((always_inline)) {
+        const long long x0s = (long long)tile * TILE_POS, left = (long long)lin - x0s;
         pf_src = a.in + ((size_t)b * a.Lin + x0s) * (ST == 1 ? 1 : SIN_CST);
         pf_rows = left < SROWS ? (int)left : SROWS;
+    };
+    auto pf_setup = [&](long long gi) __attribute__((always_inline)) {
+        const int b = (int)(gi / a.ntiles), tile = (int)(gi - (long long)b * a.ntiles);
+        pf_setup_at(b, tile, a.Lin);
     };
     auto pf_load = [&](int i) __attribute__((always_inline)) {
         const int r0 = tid / SU;
@@ -157,8 +163,8 @@ __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
     };
     // the k-step slot (group * (KS - 1) + ks - 1, ks = 1 .. KS - 1) in which unit i of the next tile is fetched: spread evenly over the tile
     auto pf_slot = [](int i) { return (i * NGROUP * (KS - 1)) / NPRE; };
-    auto prefetch = [&](long long gi) __attribute__((always_inline)) {
-        const int b = (int)(gi / a.ntiles), tile = (int)(gi - (long long)b * a.ntiles);
+    auto prefetch_at = [&](int b, int tile, int lin_b) __attribute__((always_inline)) {
+        const int lin = LENS ? lin_b : a.Lin;   // (dense: the kernel argument itself, as before the lens form)
         if constexpr (ST == 1 && I16) {
             const int16_t *src = a.in_i16 + (size_t)b * a.in_bstride;
             const long long x0s = (long long)tile * (TILE_POS * 10);
@@ -169,12 +175,12 @@ __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
                 const long long x = x0s + 8 * c;
                 int4 v = make_int4(0, 0, 0, 0);
                 if (c < S::WIN / 8) {
-                    if (vec && x + 8 <= a.Lin) {
+                    if (vec && x + 8 <= lin) {
                         v = *reinterpret_cast<const int4 *>(src + x);
                     } else {   // unaligned row or the row's end: samples past it read as 0 (int16 has no NaN; stage() zeroes them by position)
                         int e[8];
 #pragma unroll
-                        for (int k = 0; k < 8; ++k) e[k] = x + k < a.Lin ? (int)(unsigned short)src[x + k] : 0;
+                        for (int k = 0; k < 8; ++k) e[k] = x + k < lin ? (int)(unsigned short)src[x + k] : 0;
                         v = make_int4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
                     }
                 }
@@ -190,13 +196,13 @@ __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
                 const long long x = x0s + 8 * c;
                 float4 lo4 = make_float4(0.f, 0.f, 0.f, 0.f), hi4 = lo4;
                 if (c < S::WIN / 8) {
-                    if (vec && x + 8 <= a.Lin) {
+                    if (vec && x + 8 <= lin) {
                         lo4 = *reinterpret_cast<const float4 *>(src + x);
                         hi4 = *reinterpret_cast<const float4 *>(src + x + 4);
                     } else {
                         float e[8];
 #pragma unroll
-                        for (int k = 0; k < 8; ++k) e[k] = x + k < a.Lin ? src[x + k] : __builtin_nanf("");   // NaN marks "past the end": staged as zero
+                        for (int k = 0; k < 8; ++k) e[k] = x + k < lin ? src[x + k] : __builtin_nanf("");   // NaN marks "past the end": staged as zero
                         lo4 = make_float4(e[0], e[1], e[2], e[3]);
                         hi4 = make_float4(e[4], e[5], e[6], e[7]);
                     }
@@ -205,12 +211,17 @@ __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
                 pre[2 * r + 1] = hi4;
             }
         } else {
-            pf_setup(gi);
+            pf_setup_at(b, tile, lin);
 #pragma unroll
             for (int i = 0; i < NPRE; ++i) pf_load(i);
         }
     };
-    auto stage = [&](int b, int tile) __attribute__((always_inline)) {
+    auto prefetch = [&](long long gi) __attribute__((always_inline)) {
+        const int b = (int)(gi / a.ntiles), tile = (int)(gi - (long long)b * a.ntiles);
+        prefetch_at(b, tile, a.Lin);
+    };
+    auto stage = [&](int b, int tile, int lin_b) __attribute__((always_inline)) {
+        const int lin = LENS ? lin_b : a.Lin;
         if constexpr (ST == 1) {
             const float sc = a.in_scale[b], sh = a.in_shift[b];
             const long long x0s = (long long)tile * (TILE_POS * 10);
@@ -234,7 +245,7 @@ __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
                     _Float16 h[8], l[8];
 #pragma unroll
                     for (int k = 0; k < 8; ++k) {
-                        const float v = x0s + 8 * c + k < a.Lin ? __builtin_fmaf(e[k], sc, sh) : 0.f;
+                        const float v = x0s + 8 * c + k < lin ? __builtin_fmaf(e[k], sc, sh) : 0.f;
                         split2(v, h[k], l[k]);
                     }
                     uint4 ph, pl;
@@ -260,7 +271,7 @@ __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
             const int r0 = tid / SU, c4 = tid - r0 * SU;
             const float4 sc = *reinterpret_cast<const float4 *>(nrm + 4 * c4), sh = *reinterpret_cast<const float4 *>(nrm + 80 + 4 * c4);   // (c4 < 20: inside the table for every thread)
             unsigned char *d = smem + r0 * S::ROWB + 8 * c4;
-            const long long left = (long long)a.Lin - (long long)tile * TILE_POS;
+            const long long left = (long long)lin - (long long)tile * TILE_POS;
             const int rows = left < SROWS ? (int)left : SROWS;                   // rows of this window that exist (the others: the unit-0 re-read, staged as zero)
 #pragma unroll
             for (int i = 0; i < NPRE; ++i) {
@@ -285,9 +296,22 @@ __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
     };
 
     int cur_b = -1;
-    prefetch(g_begin);
+    SincRowCursor cur{}, nxt{};   // LENS: the pair gi and the one after it
+    if constexpr (LENS) {
+        cur = sinc_cursor_seek(a.rows, a.B, g_begin);
+        prefetch_at(cur.b, cur.tile, cur.lin);
+    } else {
+        prefetch(g_begin);
+    }
     for (long long gi = g_begin; gi < g_end; ++gi) {
-        const int b = (int)(gi / a.ntiles), tile = (int)(gi - (long long)b * a.ntiles);
+        int b, tile, lin, lpool;
+        if constexpr (LENS) {
+            b = cur.b; tile = cur.tile; lin = cur.lin; lpool = cur.lpool;
+            nxt = cur;
+            if (gi + 1 < g_end) sinc_cursor_next(a.rows, gi + 1, nxt);
+        } else {
+            b = (int)(gi / a.ntiles); tile = (int)(gi - (long long)b * a.ntiles); lin = a.Lin; lpool = a.Lpool;
+        }
         __syncthreads();   // the previous tile's fragment reads are complete
         if constexpr (ST != 1) {
             if (b != cur_b) {   // [80] scale, [80] shift of this utterance's input norm (0, 0 past the real channels)
@@ -301,10 +325,14 @@ __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
                 __syncthreads();
             }
         }
-        stage(b, tile);
+        stage(b, tile, lin);
         __syncthreads();
         if constexpr (ST == 1) {
-            if (gi + 1 < g_end) prefetch(gi + 1);
+            if (gi + 1 < g_end) {
+                if constexpr (LENS) prefetch_at(nxt.b, nxt.tile, nxt.lin); else prefetch(gi + 1);
+            }
+        } else if constexpr (LENS) {
+            pf_setup_at(nxt.b, nxt.tile, nxt.lin);    // (nxt = cur at the range's end, as below)
         } else {
             pf_setup(gi + 1 < g_end ? gi + 1 : gi);   // (the range's last tile re-reads its own window: no branch in the MFMA stream)
         }
@@ -326,7 +354,7 @@ __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
             }
         };
         // pooled outputs of this tile: whole (every one of its 64 below Lpool: plain stores, plain sums) or the utterance's last, ragged one
-        const int valid_tile = a.Lpool - tile * TILE_POOL < TILE_POOL ? a.Lpool - tile * TILE_POOL : TILE_POOL;
+        const int valid_tile = lpool - tile * TILE_POOL < TILE_POOL ? lpool - tile * TILE_POOL : TILE_POOL;
         const bool full = valid_tile == TILE_POOL;
         float *out_tile = a.out + ((size_t)b * a.Lpool + (size_t)tile * TILE_POOL) * S::CST;
         auto run_group = [&](int g, const unsigned char *ap, const unsigned char *ap_next, const f16x8(&p0)[KS], const f16x8(&p1)[KS], const f16x8(&p2)[KS],
@@ -478,6 +506,7 @@ __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
                 return d2;
             }, wave, 4);
         }
+        if constexpr (LENS) cur = nxt;
     }
 }
 
@@ -488,12 +517,25 @@ __global__ __launch_bounds__(256, 1) void sinc_conv_f16p_kernel(SincF16Args a) {
 // batch neighbours or scheduling.  (One thread per channel walking all 4 x ntiles partials took 0.14 ms of dependent loads per launch.)
 constexpr int FIN_NCH = 12, FIN_CP = 80;
 // Channels below `split_from` have ONE partial per tile (slot 0 of its NGROUP slots), the others (stage 1's shared channel tile) NGROUP.
+// LENS: row b combines its own ntiles_b = prefix[b + 1] - prefix[b] tiles over L_b = lpool[b] positions, in the chunks a dense
+// call of that length cuts (per = ceil(ntiles_b / FIN_NCH)); `ntiles` stays the padded row stride of the partials.  L_b = 0: scale = shift = 0.
+template <bool LENS>
 __global__ __launch_bounds__(FIN_NCH * FIN_CP) void norm_finalize_f16p_kernel(const float *partials, int ntiles, int split_from, int CST, int C, int L,
-                                                                           const float *gamma, const float *beta, float eps, float *scale, float *shift) {
+                                                                           const float *gamma, const float *beta, float eps, float *scale, float *shift,
+                                                                           SincRowsArg<LENS> rows) {
     __shared__ double red[FIN_NCH][3][FIN_CP];
     const int b = blockIdx.x, n = threadIdx.x % FIN_CP, ch = threadIdx.x / FIN_CP;
     const int slots = n >= split_from ? NGROUP : 1;
-    const int per = (ntiles + FIN_NCH - 1) / FIN_NCH, t0 = ch * per, t1 = t0 + per < ntiles ? t0 + per : ntiles;
+    int nrow = ntiles;
+    if constexpr (LENS) {
+        nrow = rows.prefix[b + 1] - rows.prefix[b];
+        L = rows.lpool[b];
+        if (L <= 0) {   // a row without frames: nothing to normalise, no division by a zero count
+            if (ch == 0 && n < C) { scale[(size_t)b * C + n] = 0.f; shift[(size_t)b * C + n] = 0.f; }
+            return;
+        }
+    }
+    const int per = (nrow + FIN_NCH - 1) / FIN_NCH, t0 = ch * per, t1 = t0 + per < nrow ? t0 + per : nrow;
     double mean = 0.0, M2 = 0.0, cnt = 0.0;
     if (n < C) {
         for (int t = t0; t < t1; ++t) {
@@ -525,14 +567,19 @@ __global__ __launch_bounds__(FIN_NCH * FIN_CP) void norm_finalize_f16p_kernel(co
     shift[(size_t)b * C + n] = (float)((double)beta[n] - mean * sc);
 }
 
-// last norm + leaky_relu; the stage output is already "batch frames feature" (PyanNet.py:179), CST floats per row
+// last norm + leaky_relu; the stage output is already "batch frames feature" (PyanNet.py:179), CST floats per row.
+// LENS: frames t >= row_T[b] are +0, and P is not read there.
+template <bool LENS>
 __global__ __launch_bounds__(256) void sinc_out_f16p_kernel(const float *P, const float *scale, const float *shift, int B, int C, int CST, int L, float slope,
-                                                            float *feats, int ldf) {
+                                                            float *feats, int ldf, SincRowTArg<LENS> row_T) {
     const long long total = (long long)B * L * C;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int c = (int)(i % C);
         const long long bt = i / C;
         const int b = (int)(bt / L);
+        if constexpr (LENS) {
+            if (bt - (long long)b * L >= row_T[b]) { feats[(size_t)bt * ldf + c] = 0.f; continue; }
+        }
         float v = __builtin_fmaf(P[(size_t)bt * CST + c], scale[(size_t)b * C + c], shift[(size_t)b * C + c]);
         v = v >= 0.f ? v : v * slope;
         feats[(size_t)bt * ldf + c] = v;
@@ -597,39 +644,50 @@ bool sinc_f16p_pack_weights(int stage, const float *w, int nrows, int ldk, unsig
     return finite;
 }
 
-hipError_t launch_sinc_conv_f16p(int stage, const SincF16Args &a, hipStream_t s) {
+hipError_t launch_sinc_conv_f16p(int stage, const SincF16Args &a, hipStream_t s, const SincRows *rows) {
     const long long total = (long long)a.B * a.ntiles;
     if (total <= 0) return hipSuccess;
     const int ncu = a.n_cu > 0 ? a.n_cu : 256;
     const dim3 grid((unsigned)(total < ncu ? total : ncu)), block(256);
-#define UVAD_SF_LAUNCH(ST_, I16_)                                                                                                    \
+#define UVAD_SF_LAUNCH_L(ST_, I16_, L_, ROWS_)                                                                                      \
     {                                                                                                                                \
-        auto k = sinc_conv_f16p_kernel<ST_, I16_>;                                                                                   \
+        auto k = sinc_conv_f16p_kernel<ST_, I16_, L_>;                                                                               \
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, Stage<ST_>::LDS_BYTES); \
         if (e != hipSuccess) return e;                                                                                               \
-        hipLaunchKernelGGL(k, grid, block, Stage<ST_>::LDS_BYTES, s, a);                                                             \
+        hipLaunchKernelGGL(k, grid, block, Stage<ST_>::LDS_BYTES, s, ROWS_);                                                         \
     }
+    SincLensArgs<SincF16Args> la{};
+    static_cast<SincF16Args &>(la) = a;
+    if (rows) la.rows = *rows;
+#define UVAD_SF_LAUNCH(ST_, I16_) { if (rows) UVAD_SF_LAUNCH_L(ST_, I16_, true, la) else UVAD_SF_LAUNCH_L(ST_, I16_, false, a) }
     if (a.in_i16 && stage != 0) return hipErrorInvalidValue;   // int16 is the waveform: stage 0 only
     if (stage == 0 && a.in_i16) UVAD_SF_LAUNCH(1, true) else if (stage == 0) UVAD_SF_LAUNCH(1, false)
     else if (stage == 1) UVAD_SF_LAUNCH(2, false) else if (stage == 2) UVAD_SF_LAUNCH(3, false) else return hipErrorInvalidValue;
 #undef UVAD_SF_LAUNCH
+#undef UVAD_SF_LAUNCH_L
     return hipGetLastError();
 }
 
 hipError_t launch_norm_finalize_f16p(int stage, const float *partials, int B, int ntiles, int C, int L, const float *gamma, const float *beta, float eps,
-                                     float *scale, float *shift, hipStream_t s) {
+                                     float *scale, float *shift, hipStream_t s, const SincRows *rows) {
     const int CST = sinc_f16p_cst(stage), split_from = stage == 0 ? 64 : CST;
-    hipLaunchKernelGGL(norm_finalize_f16p_kernel, dim3(B), dim3(FIN_NCH * FIN_CP), 0, s, partials, ntiles, split_from, CST, C, L, gamma, beta, eps, scale, shift);
+    if (rows)
+        hipLaunchKernelGGL(norm_finalize_f16p_kernel<true>, dim3(B), dim3(FIN_NCH * FIN_CP), 0, s, partials, ntiles, split_from, CST, C, L, gamma, beta, eps,
+                           scale, shift, *rows);
+    else
+        hipLaunchKernelGGL(norm_finalize_f16p_kernel<false>, dim3(B), dim3(FIN_NCH * FIN_CP), 0, s, partials, ntiles, split_from, CST, C, L, gamma, beta, eps,
+                           scale, shift, SincNoRows{});
     return hipGetLastError();
 }
 
 hipError_t launch_sinc_out_f16p(const float *P, const float *scale, const float *shift, int B, int C, int CST, int L, float slope, float *feats, int ldf,
-                                hipStream_t s) {
+                                hipStream_t s, const int *row_T) {
     const long long n = (long long)B * L * C;
     if (n <= 0) return hipSuccess;
     long long g = (n + 255) / 256;
     if (g > 8192) g = 8192;
-    hipLaunchKernelGGL(sinc_out_f16p_kernel, dim3((int)g), dim3(256), 0, s, P, scale, shift, B, C, CST, L, slope, feats, ldf);
+    if (row_T) hipLaunchKernelGGL(sinc_out_f16p_kernel<true>, dim3((int)g), dim3(256), 0, s, P, scale, shift, B, C, CST, L, slope, feats, ldf, row_T);
+    else hipLaunchKernelGGL(sinc_out_f16p_kernel<false>, dim3((int)g), dim3(256), 0, s, P, scale, shift, B, C, CST, L, slope, feats, ldf, SincNoRows{});
     return hipGetLastError();
 }
 

@@ -212,6 +212,7 @@ struct SincLayout {
     int ntiles[3];
     bool f16 = false; int cst[3] = {0, 0, 0}, ntiles16[3] = {0, 0, 0};   // split-f16 form (sincnet_f16p.hip): floats per output row, tiles of 64 pooled outputs
     size_t off_s0 = 0, off_P[3] = {0, 0, 0}, off_part[3] = {0, 0, 0}, off_sc[3] = {0, 0, 0}, total = 0;
+    size_t off_geo = 0;   // lens calls: the per-row geometry (SincGeoArgs), behind everything else so no other offset moves
     bool ok = false;
 };
 SincLayout sinc_carve(const uvad_ctx *c, int B, int64_t S) {
@@ -253,6 +254,7 @@ SincLayout sinc_carve(const uvad_ctx *c, int B, int64_t S) {
         l.off_part[i] = o; o += align_up(part * sizeof(float));
         l.off_sc[i] = o; o += align_up((size_t)2 * B * l.Cout[i] * sizeof(float));
     }
+    l.off_geo = o; o += align_up((size_t)SINC_GEO_ARRAYS * (B + 1) * sizeof(int));
     l.total = o;
     return l;
 }
@@ -800,7 +802,11 @@ size_t uvad_sincnet_workspace_bytes(const uvad_ctx *c, int B, int64_t S) {
 
 // d_wav: f32, or int16 read as q / 32768 (is_i16): the waveform kernels (statistics, the first conv stage of either form) read it as
 // given -- no conversion pass, no f32 copy -- and everything after the first stage is the same for both sample types.
-static int sincnet_impl(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64_t S, float *d_feats, void *ws, size_t ws_bytes, hipStream_t s) {
+// nsamp (uvad_sincnet_lens): device int64 [B] sample counts, clamped to [0, S] on the device.  A geometry kernel turns them into each
+// row's stage lengths, frame count T_b and the exclusive prefixes of the rows' tile counts; every later kernel runs its lens form, so row b
+// gets the bits of a dense call on wav[b, :S_b] at t < T_b and +0 after.  *row_T: where T_b (int32 [B]) lands, for classify_impl.
+static int sincnet_impl(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64_t S, float *d_feats, void *ws, size_t ws_bytes, hipStream_t s,
+                        const int64_t *nsamp = nullptr, const int **row_T = nullptr) {
     if (!c->has_sinc) return fail(c, UVAD_E_STATE, "uvad_sincnet: uvad_sincnet_configure has not been called");
     if (!c->finalized || !c->sinc_ready) return fail(c, UVAD_E_STATE, "uvad_sincnet: SincNet tensors not set / uvad_finalize not called");
     const SincLayout l = sinc_carve(c, B, S);
@@ -811,13 +817,32 @@ static int sincnet_impl(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64
     const uvad_sincnet_cfg &q = c->sc;
     float *s0 = reinterpret_cast<float *>(base + l.off_s0);
     const int16_t *wav16 = is_i16 ? static_cast<const int16_t *>(d_wav) : nullptr;
-    if (wav16) HIPCHK(c, launch_wav_stats(wav16, B, S, S, c->sn_wav_g, c->sn_wav_b, q.eps, s0, s0 + B, s));
-    else HIPCHK(c, launch_wav_stats(static_cast<const float *>(d_wav), B, S, S, c->sn_wav_g, c->sn_wav_b, q.eps, s0, s0 + B, s));
+    // lens: the rows of each stage in both forms' tiles (geo arrays of SincGeoArgs)
+    int *geo = reinterpret_cast<int *>(base + l.off_geo);
+    auto garr = [&](int k) { return geo + (size_t)k * (B + 1); };
+    SincRows rows16[3], rows32[3];
+    const int *T_rows = nullptr;
+    if (nsamp) {
+        SincGeoArgs g{};
+        g.nsamp = nsamp; g.B = B; g.S = S; g.stride0 = q.stride; g.geo = geo;
+        for (int i = 0; i < 3; ++i) {
+            g.kw[i] = l.Kw[i]; g.pt[i] = l.pt[i];
+            rows16[i] = SincRows{garr(1 + 6 * i), garr(2 + 6 * i), garr(4 + 6 * i)};
+            rows32[i] = SincRows{garr(1 + 6 * i), garr(2 + 6 * i), garr(6 + 6 * i)};
+        }
+        HIPCHK(c, launch_sinc_row_geometry(g, s));
+        T_rows = garr(0);
+        if (row_T) *row_T = T_rows;
+    }
+    const int *row_n = nsamp ? rows16[0].lin : nullptr;
+    if (wav16) HIPCHK(c, launch_wav_stats(wav16, B, S, S, c->sn_wav_g, c->sn_wav_b, q.eps, s0, s0 + B, s, row_n));
+    else HIPCHK(c, launch_wav_stats(static_cast<const float *>(d_wav), B, S, S, c->sn_wav_g, c->sn_wav_b, q.eps, s0, s0 + B, s, row_n));
     const float *in = wav16 ? nullptr : static_cast<const float *>(d_wav), *in_scale = s0, *in_shift = s0 + B;
     // Split-f16 form (GEMM modes 1 / 3) when the geometry is the reference's and every stage input provably fits the f16 range: an
     // instance-normalised value is at most sqrt(L - 1) in magnitude, so |gamma| * sqrt(L) + |beta| bounds what the staging converts, and
     // the leaky_relu in front of stages 2 and 3 scales that by at most max(1, |slope|).  The staging of those stages applies leaky_relu
-    // as max(e, e * slope), which is leaky_relu only for slope <= 1: a larger slope runs the exact-f32 stages.
+    // as max(e, e * slope), which is leaky_relu only for slope <= 1: a larger slope runs the exact-f32 stages.  A lens call checks the
+    // padded S, which bounds every row: it can run the exact form where one of its rows alone would run the split form.
     bool f16 = l.f16 && c->sinc_f16 && (c->gemm_mode == 1 || c->gemm_mode == 3) && q.leaky_slope <= 1.0f;
     const double act = std::fmax(1.0, std::fabs((double)q.leaky_slope));
     for (int i = 0; i < 3 && f16; ++i)
@@ -834,12 +859,12 @@ static int sincnet_impl(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64
             a.Wfrag = c->sn_wfrag[i]; a.wscale = c->sn_wscale[i]; a.bias = c->sn_bias16[i];
             a.Lpool = (int)l.Lpool[i]; a.ntiles = l.ntiles16[i];
             a.out = P; a.partials = part; a.B = B; a.n_cu = c->n_cu;
-            HIPCHK(c, launch_sinc_conv_f16p(i, a, s));
+            HIPCHK(c, launch_sinc_conv_f16p(i, a, s, nsamp ? &rows16[i] : nullptr));
             HIPCHK(c, launch_norm_finalize_f16p(i, part, B, l.ntiles16[i], l.Cout[i], (int)l.Lpool[i], c->sn_g[i], c->sn_b[i], q.eps, sc,
-                                                sc + (size_t)B * l.Cout[i], s));
+                                                sc + (size_t)B * l.Cout[i], s, nsamp ? &rows16[i] : nullptr));
             in = P; in_scale = sc; in_shift = sc + (size_t)B * l.Cout[i];
         }
-        HIPCHK(c, launch_sinc_out_f16p(in, in_scale, in_shift, B, l.Cout[2], l.cst[2], (int)l.Lpool[2], q.leaky_slope, d_feats, l.Cout[2], s));
+        HIPCHK(c, launch_sinc_out_f16p(in, in_scale, in_shift, B, l.Cout[2], l.cst[2], (int)l.Lpool[2], q.leaky_slope, d_feats, l.Cout[2], s, T_rows));
         return UVAD_OK;
     }
     for (int i = 0; i < 3; ++i) {
@@ -853,12 +878,12 @@ static int sincnet_impl(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64
         a.Kw = l.Kw[i]; a.stride = l.stride[i]; a.Ktot = l.Cin[i] * l.Kw[i]; a.Kp = (a.Ktot + 7) / 8 * 8; a.Cout = l.Cout[i]; a.do_abs = i == 0;
         a.Lconv = (int)l.Lconv[i]; a.Lpool = (int)l.Lpool[i]; a.ntiles = l.ntiles[i];
         a.out = P; a.partials = part; a.B = B; a.n_cu = c->n_cu;
-        HIPCHK(c, launch_sinc_conv(a, s));
+        HIPCHK(c, launch_sinc_conv(a, s, nsamp ? &rows32[i] : nullptr));
         HIPCHK(c, launch_norm_finalize(part, B, l.ntiles[i], l.pt[i], l.phases[i], l.NW[i], l.Cout[i], (int)l.Lpool[i], c->sn_g[i], c->sn_b[i], q.eps, sc,
-                                       sc + (size_t)B * l.Cout[i], s));
+                                       sc + (size_t)B * l.Cout[i], s, nsamp ? &rows32[i] : nullptr));
         in = P; in_scale = sc; in_shift = sc + (size_t)B * l.Cout[i];
     }
-    HIPCHK(c, launch_sinc_out(in, in_scale, in_shift, B, l.Cout[2], (int)l.Lpool[2], q.leaky_slope, d_feats, l.Cout[2], s));
+    HIPCHK(c, launch_sinc_out(in, in_scale, in_shift, B, l.Cout[2], (int)l.Lpool[2], q.leaky_slope, d_feats, l.Cout[2], s, T_rows));
     return UVAD_OK;
 }
 
@@ -876,12 +901,31 @@ int uvad_sincnet_i16(uvad_ctx *c, const int16_t *d_wav, int B, int64_t S, float 
     return sincnet_entry(c, d_wav, 1, B, S, d_feats, ws, ws_bytes, stream);
 }
 
+static int sincnet_lens_entry(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64_t S, const int64_t *d_nsamp, float *d_feats, void *ws,
+                              size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_nsamp) return fail(c, UVAD_E_ARG, "uvad_sincnet_lens: d_nsamp is NULL");
+    if (!d_wav || !d_feats || B <= 0 || S <= 0 || !ws) return fail(c, UVAD_E_ARG, "uvad_sincnet_lens: bad argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    return sincnet_impl(c, d_wav, is_i16, B, S, d_feats, ws, ws_bytes, (hipStream_t)stream, d_nsamp);
+}
+int uvad_sincnet_lens(uvad_ctx *c, const float *d_wav, int B, int64_t S, const int64_t *d_nsamp, float *d_feats, void *ws, size_t ws_bytes,
+                      void *stream) {
+    return sincnet_lens_entry(c, d_wav, 0, B, S, d_nsamp, d_feats, ws, ws_bytes, stream);
+}
+int uvad_sincnet_lens_i16(uvad_ctx *c, const int16_t *d_wav, int B, int64_t S, const int64_t *d_nsamp, float *d_feats, void *ws, size_t ws_bytes,
+                          void *stream) {
+    return sincnet_lens_entry(c, d_wav, 1, B, S, d_nsamp, d_feats, ws, ws_bytes, stream);
+}
+
 static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float *d_logits, float *d_probs,
                          void *ws, size_t ws_bytes, hipStream_t s, bool record_start, bool check_range,
                          const StreamState *ss, int ld_out, bool feats_in_planes, const FbankArgs *fused_fb, const int *lens = nullptr);
 
+// nsamp (uvad_forward_wav_lens): the SincNet stage in its lens form, then the classifier with lens = the rows' frame counts T_b (the
+// geometry block of the SincNet workspace): time chunks off, outputs at t >= T_b exactly +0.
 static int forward_wav_impl(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64_t S, float *d_logits, float *d_probs,
-                            void *ws, size_t ws_bytes, void *stream) {
+                            void *ws, size_t ws_bytes, void *stream, const int64_t *nsamp = nullptr) {
     if (!c) return UVAD_E_ARG;
     if (!d_wav || B <= 0 || S <= 0 || !ws) return fail(c, UVAD_E_ARG, "uvad_forward_wav: bad argument");
     if (!c->has_sinc) return fail(c, UVAD_E_STATE, "uvad_forward_wav: uvad_sincnet_configure has not been called");
@@ -896,9 +940,10 @@ static int forward_wav_impl(uvad_ctx *c, const void *d_wav, int is_i16, int B, i
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(c, hipSetDevice(c->device));
     if (c->timing) HIPCHK(c, hipEventRecord(c->ev[0], s));
-    int r = sincnet_impl(c, d_wav, is_i16, B, S, feats, base + w.total, ws_bytes - w.total, s);
+    const int *lens = nullptr;
+    int r = sincnet_impl(c, d_wav, is_i16, B, S, feats, base + w.total, ws_bytes - w.total, s, nsamp, &lens);
     if (r) return r;
-    return classify_impl(c, feats, B, (int)T, d_logits, d_probs, ws, w.total, s, false, true, nullptr, 0, false, nullptr);
+    return classify_impl(c, feats, B, (int)T, d_logits, d_probs, ws, w.total, s, false, true, nullptr, 0, false, nullptr, lens);
 }
 
 int uvad_forward_wav(uvad_ctx *c, const float *d_wav, int B, int64_t S, float *d_logits, float *d_probs,
@@ -908,6 +953,20 @@ int uvad_forward_wav(uvad_ctx *c, const float *d_wav, int B, int64_t S, float *d
 int uvad_forward_wav_i16(uvad_ctx *c, const int16_t *d_wav, int B, int64_t S, float *d_logits, float *d_probs,
                          void *ws, size_t ws_bytes, void *stream) {
     return forward_wav_impl(c, d_wav, 1, B, S, d_logits, d_probs, ws, ws_bytes, stream);
+}
+static int forward_wav_lens_entry(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64_t S, const int64_t *d_nsamp, float *d_logits,
+                                  float *d_probs, void *ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_nsamp) return fail(c, UVAD_E_ARG, "uvad_forward_wav_lens: d_nsamp is NULL");
+    return forward_wav_impl(c, d_wav, is_i16, B, S, d_logits, d_probs, ws, ws_bytes, stream, d_nsamp);
+}
+int uvad_forward_wav_lens(uvad_ctx *c, const float *d_wav, int B, int64_t S, const int64_t *d_nsamp, float *d_logits, float *d_probs,
+                          void *ws, size_t ws_bytes, void *stream) {
+    return forward_wav_lens_entry(c, d_wav, 0, B, S, d_nsamp, d_logits, d_probs, ws, ws_bytes, stream);
+}
+int uvad_forward_wav_lens_i16(uvad_ctx *c, const int16_t *d_wav, int B, int64_t S, const int64_t *d_nsamp, float *d_logits, float *d_probs,
+                              void *ws, size_t ws_bytes, void *stream) {
+    return forward_wav_lens_entry(c, d_wav, 1, B, S, d_nsamp, d_logits, d_probs, ws, ws_bytes, stream);
 }
 
 int64_t uvad_num_frames(const uvad_ctx *c, int64_t S) {

@@ -2,6 +2,7 @@
 // Everything here is gfx950-only HIP; no torch types, no CPU fallbacks.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include <stdint.h>
 
 namespace uvad {
@@ -288,6 +289,41 @@ void pack_lstm_image(const float *w /*[4 * 128][K], torch row order*/, int K, fl
 size_t fc_image_elems();                                                   // a 128 x 128 feed-forward matrix as a register image
 void pack_fc_image(const float *w /*[128][128], torch nn.Linear.weight*/, float *out);
 
+// ---- lens calls of the SincNet stages: the persistent workgroups walk the valid (row, tile) pairs only.  Pair g of the walk is tile
+//      g - prefix[b] of the row b with prefix[b] <= g < prefix[b + 1] (prefix: the exclusive prefix of the rows' tile counts, SincGeo); a
+//      workgroup finds its first pair with a binary search and steps to the next one, which reads memory only when the row changes.
+//      Everything here is wave-uniform (scalar loads).
+// The lens conv kernels take their arguments with the rows appended (SincArgsT); the small kernels take the rows as one more argument,
+// which is an empty struct in the dense instantiations and adds no kernel-argument bytes.  Either way the dense kernels keep their
+// argument layout and code.
+struct SincRows { const int *lin, *lpool, *prefix; };   // device int32 [B] Lin_b, [B] Lpool_b, [B + 1] exclusive prefix of the rows' tiles
+struct SincNoRows {};
+template <class A> struct SincLensArgs : A { SincRows rows; };
+template <bool LENS, class A> using SincArgsT = typename std::conditional<LENS, SincLensArgs<A>, A>::type;
+template <bool LENS> using SincRowsArg = typename std::conditional<LENS, SincRows, SincNoRows>::type;
+template <bool LENS> using SincRowTArg = typename std::conditional<LENS, const int *, SincNoRows>::type;
+struct SincRowCursor { int b, tile, end, lin, lpool; };
+__device__ __forceinline__ void sinc_cursor_at(const SincRows &r, int b, long long g, SincRowCursor &c) {
+    c.b = b; c.tile = (int)(g - r.prefix[b]); c.end = r.prefix[b + 1]; c.lin = r.lin[b]; c.lpool = r.lpool[b];
+}
+__device__ __forceinline__ SincRowCursor sinc_cursor_seek(const SincRows &r, int B, long long g) {
+    int lo = 0, hi = B;   // prefix[lo] <= g < prefix[hi] (prefix[B] = the total > g)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (r.prefix[mid] <= g) lo = mid; else hi = mid;
+    }
+    SincRowCursor c;
+    sinc_cursor_at(r, lo, g, c);
+    return c;
+}
+// c (pair g - 1) -> pair g
+__device__ __forceinline__ void sinc_cursor_next(const SincRows &r, long long g, SincRowCursor &c) {
+    if (g < c.end) { ++c.tile; return; }
+    int b = c.b + 1;
+    while (r.prefix[b + 1] <= g) ++b;   // (rows without tiles)
+    sinc_cursor_at(r, b, g, c);
+}
+
 // ---- sincnet.hip: SincNet front end of PyanNet (conv + |.| + maxpool(3) + instance-norm statistics) ----------
 struct SincConvArgs {
     const float *in; long long in_bstride; int Cin, Lin;   // in[b*in_bstride + ci*Lin + x]
@@ -303,19 +339,34 @@ struct SincConvArgs {
     int B;
     int n_cu;                                              // compute units of the device (persistent grid size); 0 = 256
 };
+// row_n (lens calls): device int32 [B], row b's statistics over its first row_n[b] samples (0: scale = shift = 0); null = S for every row
 hipError_t launch_wav_stats(const float *wav, int B, long long S, long long row_stride, const float *gamma, const float *beta, float eps,
-                            float *scale, float *shift, hipStream_t s);
+                            float *scale, float *shift, hipStream_t s, const int *row_n = nullptr);
 hipError_t launch_wav_stats(const int16_t *wav, int B, long long S, long long row_stride, const float *gamma, const float *beta, float eps,
-                            float *scale, float *shift, hipStream_t s);   // int16 samples read as q / 32768
+                            float *scale, float *shift, hipStream_t s, const int *row_n = nullptr);   // int16 samples read as q / 32768
 struct SincConvPlan { int waves, pt, phases; };            // waves per workgroup, pooled outputs per tile, statistics groups per tile
 SincConvPlan sinc_conv_plan(const SincConvArgs &a);        // needs Cin, Cout, Kw, stride, Kp
-hipError_t launch_sinc_conv(const SincConvArgs &a, hipStream_t s);
+hipError_t launch_sinc_conv(const SincConvArgs &a, hipStream_t s, const SincRows *rows = nullptr);   // rows: a lens call (exact-form tiles)
 size_t sinc_conv_lds_bytes(const SincConvArgs &a, int NT, int waves);
 int sinc_conv_ept(const SincConvArgs &a, int waves);   // window elements per thread held in registers (<= 8 single-channel, <= 48 otherwise)
+// rows (lens calls): row b combines its own ntiles_b partials over L_b positions (L_b = 0: scale = shift = 0)
 hipError_t launch_norm_finalize(const float *partials, int B, int ntiles, int pt, int phases, int NW, int C, int L, const float *gamma,
-                                const float *beta, float eps, float *scale, float *shift, hipStream_t s);
+                                const float *beta, float eps, float *scale, float *shift, hipStream_t s, const SincRows *rows = nullptr);
+// row_T (lens calls): frames t >= row_T[b] are written as +0 (P is not read there)
 hipError_t launch_sinc_out(const float *P, const float *scale, const float *shift, int B, int C, int L, float slope, float *feats, int ldf,
-                           hipStream_t s);
+                           hipStream_t s, const int *row_T = nullptr);
+
+// Per-row geometry of a lens call (uvad_sincnet_lens): SINC_GEO_ARRAYS int32 arrays of ld = B + 1 entries in the workspace.
+//   [0] T_b (frames); stage i: [1 + 6 i] Lin_b, [2 + 6 i] Lpool_b, [3 + 6 i] tiles of the split form (sinc_f16p_ntiles(Lpool_b)),
+//   [4 + 6 i] their exclusive prefix over rows (entry B: the total), [5 + 6 i] tiles of the exact form (ceil(Lpool_b / pt_i)), [6 + 6 i] prefix.
+// A row with T_b = 0 has 0 in every array: no stage touches it.
+constexpr int SINC_GEO_ARRAYS = 19;
+struct SincGeoArgs {
+    const int64_t *nsamp; int B; long long S;   // lengths clamped to [0, S]
+    int kw[3], stride0, pt[3];                  // taps of the stages, the sinc bank's stride, the exact form's pooled outputs per tile
+    int *geo;                                   // [SINC_GEO_ARRAYS][B + 1]
+};
+hipError_t launch_sinc_row_geometry(const SincGeoArgs &g, hipStream_t s);
 
 // ---- sincnet_f16p.hip: the same three stages on the f16 matrix cores (f32-equivalent split arithmetic), channel-minor intermediates ----
 struct SincF16Args {
@@ -338,10 +389,10 @@ int sinc_f16p_ntiles(long long Lpool);
 size_t sinc_f16p_partial_floats(int stage, int B, int ntiles);
 size_t sinc_f16p_wfrag_elems(int stage);
 bool sinc_f16p_pack_weights(int stage, const float *w, int nrows, int ldk, unsigned short *out, float *wscale);
-hipError_t launch_sinc_conv_f16p(int stage, const SincF16Args &a, hipStream_t s);
+hipError_t launch_sinc_conv_f16p(int stage, const SincF16Args &a, hipStream_t s, const SincRows *rows = nullptr);   // rows: split-form tiles
 hipError_t launch_norm_finalize_f16p(int stage, const float *partials, int B, int ntiles, int C, int L, const float *gamma, const float *beta, float eps,
-                                     float *scale, float *shift, hipStream_t s);
+                                     float *scale, float *shift, hipStream_t s, const SincRows *rows = nullptr);
 hipError_t launch_sinc_out_f16p(const float *P, const float *scale, const float *shift, int B, int C, int CST, int L, float slope, float *feats, int ldf,
-                                hipStream_t s);
+                                hipStream_t s, const int *row_T = nullptr);
 
 }  // namespace uvad

@@ -168,8 +168,8 @@ class PyanNet(PyanNet2):
     def num_frames(self, num_samples: int) -> int:
         return self.sincnet.num_frames(num_samples, self.sincnet.stride)
 
-    _NO_LENGTHS = ("PyanNet has no variable-length batches: every SincNet stage normalises over the whole row (instance norm), so "
-                   "per-row lengths would need per-row statistics in every stage; run rows of different lengths in separate calls")
+    _NO_LENGTHS = ("PyanNet.forward / forward_logits keep the reference's signature: every SincNet stage normalises over the whole row "
+                   "(instance norm), so a ragged batch needs per-row statistics; use PyanNet.forward_ragged(waveforms, lengths)")
 
     @torch.no_grad()
     def forward(self, waveforms: torch.Tensor, lengths=None) -> torch.Tensor:
@@ -191,8 +191,21 @@ class PyanNet(PyanNet2):
             waveforms = waveforms[:, 0, :]
         return self.runtime(waveforms.device).forward_wav(waveforms, want_logits=want_logits)
 
+    @torch.no_grad()
+    def forward_ragged(self, waveforms: torch.Tensor, lengths, want_logits=True):
+        """A ragged batch: (batch, [channel = 1,] samples) f32 or int16 and lengths (batch,) samples per row -> (logits, probs), both
+        (batch, frames(samples)).  Row b is the model on waveforms[b, :lengths[b]] alone -- the waveform norm and every instance norm
+        over the row's own samples / positions -- and its frames past num_frames(lengths[b]) are 0 (uvad_forward_wav_lens)."""
+        self._require_gpu(waveforms, "waveforms")
+        if waveforms.dim() == 3:
+            assert waveforms.shape[1] == 1, f"Only single channel is supported. You have {waveforms.shape[1]}"
+            waveforms = waveforms[:, 0, :]
+        return self.runtime(waveforms.device).forward_wav(waveforms, want_logits=want_logits, lengths=lengths)
+
     def forward_waveform(self, pcm: torch.Tensor, lengths=None):
-        return self.forward_logits(pcm, lengths=lengths)
+        if lengths is not None:
+            return self.forward_ragged(pcm, lengths)
+        return self.forward_logits(pcm)
 
     def attach_fbank(self, config):
         raise RuntimeError("PyanNet consumes raw waveforms (SincNet); log-mel features belong to PyanNet2")

@@ -106,9 +106,7 @@ class ForwardPipeline:
         """pcm (B, S) f32, or int16 read as q / 32768, on the device, ready on the CURRENT stream.  Returns at once; the step runs on the
         next slot's stream (VadRuntime.forward, or forward_wav for a PyanNet).
         timed: bracket the step with timing events on its own stream (Pending.elapsed_ms).
-        lengths: samples per row (B,) -- a ragged batch (VadRuntime.forward(lengths=...)); a PyanNet refuses it."""
-        if lengths is not None and self.wav:
-            raise NotImplementedError("PyanNet has no variable-length batches (SincNet's instance norms are per row)")
+        lengths: samples per row (B,) -- a ragged batch (VadRuntime.forward / forward_wav(lengths=...))."""
         i = self._k % self._active
         self._k += 1
         s = self.streams[i]
@@ -119,7 +117,7 @@ class ForwardPipeline:
                 start = torch.cuda.Event(enable_timing=True)
                 start.record(s)
             if self.wav:
-                logits, probs = self.runtimes[i].forward_wav(pcm, want_logits=want_logits, want_probs=want_probs)
+                logits, probs = self.runtimes[i].forward_wav(pcm, want_logits=want_logits, want_probs=want_probs, lengths=lengths)
             else:
                 logits, probs = self.runtimes[i].forward(pcm, want_logits=want_logits, want_probs=want_probs, lengths=lengths)
             ev = torch.cuda.Event(enable_timing=timed)

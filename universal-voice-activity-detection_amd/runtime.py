@@ -281,9 +281,11 @@ class VadRuntime:
             return wav.contiguous(), True
         return self._dev_f32(wav, "wav"), False
 
-    def sincnet(self, wav: "torch.Tensor") -> "torch.Tensor":
+    def sincnet(self, wav: "torch.Tensor", lengths=None) -> "torch.Tensor":
         """wav (B,S) f32, or int16 as read from a wav file (samples read as q / 32768, the same signal as uvad_fbank_i16 / forward()
-        take: the f32 call on q.float() / 32768 gives the same bits), on the GPU -> SincNet features (B, frames, c3)."""
+        take: the f32 call on q.float() / 32768 gives the same bits), on the GPU -> SincNet features (B, frames, c3).
+        lengths: samples per row (B,); row b is SincNet on wav[b, :lengths[b]] alone (every norm over the row's own samples), its
+        frames past sincnet_num_frames(lengths[b]) are 0 (uvad_sincnet_lens)."""
         if self._sn_c is None:
             raise RuntimeError("this runtime was created without a SincNet configuration")
         with torch.cuda.device(self.device):
@@ -294,13 +296,19 @@ class VadRuntime:
                 raise ValueError(f"{S} samples are too short for one SincNet frame")
             ws = self._wav_ws(B, S, T, False)
             feats = torch.empty((B, T, self._sn_c.c3), dtype=torch.float32, device=self.device)
-            fn = self.lib.uvad_sincnet_i16 if i16 else self.lib.uvad_sincnet
-            self._check(fn(self.ctx, wav.data_ptr(), B, S, feats.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+            if lengths is None:
+                fn = self.lib.uvad_sincnet_i16 if i16 else self.lib.uvad_sincnet
+                self._check(fn(self.ctx, wav.data_ptr(), B, S, feats.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+            else:
+                n = self._dev_lens(lengths, B, S, torch.int64, "lengths (samples)")
+                fn = self.lib.uvad_sincnet_lens_i16 if i16 else self.lib.uvad_sincnet_lens
+                self._check(fn(self.ctx, wav.data_ptr(), B, S, n.data_ptr(), feats.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
             return feats
 
-    def forward_wav(self, wav: "torch.Tensor", want_logits=True, want_probs=True):
+    def forward_wav(self, wav: "torch.Tensor", want_logits=True, want_probs=True, lengths=None):
         """wav (B,S) f32, or int16 read as q / 32768 (as in sincnet()), on the GPU -> (logits, probs) of PyanNet (SincNet -> LSTM stack ->
-        head); int16 runs uvad_forward_wav_i16."""
+        head); int16 runs uvad_forward_wav_i16.  lengths: samples per row (B,); row b is the model on wav[b, :lengths[b]] alone, its
+        frames past sincnet_num_frames(lengths[b]) are 0 (uvad_forward_wav_lens)."""
         if self._sn_c is None:
             raise RuntimeError("this runtime was created without a SincNet configuration")
         with torch.cuda.device(self.device):
@@ -312,11 +320,14 @@ class VadRuntime:
             ws = self._wav_ws(B, S, T, True)
             logits = torch.empty((B, T), dtype=torch.float32, device=self.device) if want_logits else None
             probs = torch.empty((B, T), dtype=torch.float32, device=self.device) if want_probs else None
-            fn = self.lib.uvad_forward_wav_i16 if i16 else self.lib.uvad_forward_wav
-            self._check(fn(self.ctx, wav.data_ptr(), B, S,
-                           logits.data_ptr() if want_logits else None,
-                           probs.data_ptr() if want_probs else None,
-                           ws.data_ptr(), ws.numel(), self._stream()))
+            outs = (logits.data_ptr() if want_logits else None, probs.data_ptr() if want_probs else None, ws.data_ptr(), ws.numel(), self._stream())
+            if lengths is None:
+                fn = self.lib.uvad_forward_wav_i16 if i16 else self.lib.uvad_forward_wav
+                self._check(fn(self.ctx, wav.data_ptr(), B, S, *outs))
+            else:
+                n = self._dev_lens(lengths, B, S, torch.int64, "lengths (samples)")
+                fn = self.lib.uvad_forward_wav_lens_i16 if i16 else self.lib.uvad_forward_wav_lens
+                self._check(fn(self.ctx, wav.data_ptr(), B, S, n.data_ptr(), *outs))
             self._last_bt = (B, T)
             return logits, probs
 

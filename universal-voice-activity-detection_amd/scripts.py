@@ -153,9 +153,9 @@ def predict_vad(**kwargs):
     med_window = 0.02 if net.encoding_dim == 768 else 0.01   # vad_engine.py:207-208
 
     # ---- batches: pieces of equal length together, at most max_duration seconds of audio per batch; with ragged_batches (whole
-    #      recordings of the log-mel model only) pieces of any length together, padded to the batch's longest, each row classified
-    #      on its own length (uvad_forward_lens)
-    ragged = bool(kwargs.get("ragged_batches", False)) and window_s is None and not sincnet
+    #      recordings, window_seconds None) pieces of any length together, padded to the batch's longest, each row run on its own
+    #      length (uvad_forward_lens; the SincNet model: uvad_forward_wav_lens, every norm over the row's own samples)
+    ragged = bool(kwargs.get("ragged_batches", False)) and window_s is None
     order = sorted(range(len(pieces)), key=lambda i: (-pieces[i][2], i))
     batches, i = [], 0
     if ragged:
@@ -192,9 +192,12 @@ def predict_vad(**kwargs):
 
     def ragged_post(group, probs):
         nsamp = [pieces[j][2] for j in group]
-        fr = [rt.num_frames(n) for n in nsamp]
+        fr = [rt.sincnet_num_frames(n) if sincnet else rt.num_frames(n) for n in nsamp]
         lab = median_filter(probs, window=med_window, lengths=fr)                      # uvad_median_filter_lens
-        ivs = labels_to_intervals_batch(lab, frame_shift, runtime=rt, lengths=fr)     # uvad_label_runs_lens
+        if sincnet:   # frame index -> seconds by the receptive field, as the dense path below (whole recordings: every frame is kept)
+            ivs = [sincnet_labels_to_intervals(lab[r, :fr[r]], n / sr) if fr[r] else [] for r, n in enumerate(nsamp)]
+        else:
+            ivs = labels_to_intervals_batch(lab, frame_shift, runtime=rt, lengths=fr)     # uvad_label_runs_lens
         for r, j in enumerate(group):
             piece_probs[j] = probs[r, :fr[r]]
             piece_post[j] = (lab[r, :fr[r]], ivs[r])
@@ -206,7 +209,8 @@ def predict_vad(**kwargs):
             if pipe is not None:
                 pending.append((group, pipe.submit(x, want_logits=False, want_probs=True, lengths=nsamp)))
             else:
-                ragged_post(group, rt.forward(x, want_logits=False, lengths=nsamp)[1])
+                fwd = rt.forward_wav if sincnet else rt.forward
+                ragged_post(group, fwd(x, want_logits=False, lengths=nsamp)[1])
             continue
         n = pieces[group[0]][2]
         x = stack(group)
