@@ -362,6 +362,65 @@ int uvad_window_wav_peek(const uvad_ctx *, const void *d_state, int chunk, int *
 int uvad_window_wav_advance(uvad_ctx *, void *d_state, int chunk);
 int uvad_window_wav_features(uvad_ctx *, const void *d_state, int B, float *d_feats, int *Tw, void *stream);
 
+/* Slot pools of both window families: windowed streams where feeds start and end independently.  A pool of B slots advances in lockstep,
+ * `chunk` samples per step; each slot holds at most one session (one call of a server) at a time, and a per-step flag byte per slot
+ * starts and ends sessions.  The existing window families (uvad_window_*, uvad_window_wav_*) are unchanged.
+ *   State: after *_slots_reset every slot is idle.  d_flags is a DEVICE uint8 [B] per step, or NULL for no changes:
+ *     UVAD_SLOT_START  the slot drops whatever it held and a new session begins with this step's chunk as its first samples;
+ *     UVAD_SLOT_END    the session ends after this chunk: the slot is idle from the next step on.  Both bits: a one-chunk session.
+ *   Idle slots: the chunk row of an idle slot is never read (NaN or Inf there changes no output bit anywhere); they emit nothing.
+ *   A session's frames are those of a single-feed stream of the family (B = 1 uvad_window_step / uvad_window_wav_step[_i16]) opened at
+ *   the session's start and fed the same chunks: for log-mel the uvad_window_step framing (first chunk reflected on the left, a per-feed
+ *   ring, windows of the last min(e, W) frames run from zero state); for the waveform model whole frames of J samples with receptive
+ *   field R, the window's samples run as uvad_forward_wav runs them.
+ *   Emission, per session: with e_prev complete frames before the step and e after it, a step emits frames [max(0, e_prev - L),
+ *   max(0, e - L)); the END step emits [max(0, e_prev - L), e) instead, flushing the L held-back frames from the same window run (no
+ *   right-edge reflection, as the window families).  Row b of d_logits / d_probs [B][ld_out] (either may be NULL, not both) gets its
+ *   n_b frames in columns 0 .. n_b - 1; columns at and past n_b are not written; d_counts (DEVICE int32 [B], required) receives n_b.
+ *   ld_out must be at least L + kmax, kmax = chunk / frame_shift + 1 (log-mel) or ceil(chunk / J) (waveform): else UVAD_E_ARG and
+ *   nothing is enqueued.
+ *   Enqueue only: a step never allocates, frees or synchronises, and reads every per-slot quantity -- samples since the session's start,
+ *   frames, the PCM tail and its ring position, first-chunk status -- from the device (emitted frames follow from frames and L).  Two
+ *   steps with the same (B, chunk) and buffers enqueue identical work: a graph captured around any one step replays for every later
+ *   one, warm-ups and session changes included.  Steps return UVAD_OK, not a count.
+ *   Fixed at reset: chunk, W = window and L = lookahead (0 <= L < W), so the workspace and the graph's shape are fixed too.  Both
+ *   families need L + kmax <= W; log-mel needs chunk >= (frame_len - frame_shift) / 2, since any step can be a session's first.
+ *   Violations: UVAD_E_ARG.  A step with another B or chunk than the reset's, or the other sample type (waveform): UVAD_E_ARG; a state
+ *   never reset: UVAD_E_STATE; a missing configuration / tables / weights: UVAD_E_STATE; a workspace too small: UVAD_E_WORKSPACE.
+ *   Work per step: every slot's window runs at (B, W) with per-row lengths Tw_b = min(e_b, W) (0 for an idle slot), the semantics of
+ *   uvad_classify_lens: in GEMM modes 0 and 2 with a pinned recurrent tile a session's outputs are bit-identical to its B = 1 stream's,
+ *   modes 1 and 3 agree to rounding.  The GEMMs run over all W rows of every slot, idle ones included.
+ *   Log-mel: one kernel applies the flags and writes an aligned staging row per slot (its first new frame at column 0) and the next
+ *   PCM tail; the unchanged feature kernel transforms kmax frames of every row (plain rows, snip_edges = 1; frames past k_b are
+ *   discarded); one kernel commits the k_b new frames to the slot's ring and writes its window left-aligned into the first projection's
+ *   operand; then the classifier and a gather of the emitted rows that also commits the counters.
+ *   Waveform: one kernel applies the flags, commits the chunk to the slot's PCM ring and writes its window of Sw_b = R + J (Tw_b - 1)
+ *   samples left-aligned into [B][Sw_max]; SincNet runs in its lens form at S = Sw_max (workgroups walk the valid tiles only), then the
+ *   classifier and the gather.  The SincNet form is chosen on the padded S = Sw_max (uvad_sincnet_lens): a slot can run the exact-f32
+ *   form where its B = 1 stream runs the split-f16 one; uvad_get_sincnet_form says which ran.  GEMM modes 0 and 2 always run exact-f32.
+ *   *_slots_features (debug tap): the window each slot's last step classified -- log-mel features [B][W][n_mels] / SincNet output
+ *   [B][W][c3], left-aligned, rows past Tw_b zero -- and d_tw (DEVICE int32 [B]) = Tw_b (0 for a slot idle in that step).
+ *   Time chunks are off in every step (uvad_get_time_chunks() is 1 afterwards). */
+#define UVAD_SLOT_START 1
+#define UVAD_SLOT_END   2
+size_t uvad_window_slots_state_bytes(const uvad_ctx *, int B, int window);
+size_t uvad_window_slots_workspace_bytes(const uvad_ctx *, int B, int chunk, int window);
+int uvad_window_slots_reset(uvad_ctx *, void *d_state, int B, int chunk, int window, int lookahead, void *stream);
+int uvad_window_slots_step(uvad_ctx *, const float *d_pcm_chunk, const uint8_t *d_flags, int B, int chunk, void *d_state,
+                           float *d_logits, float *d_probs, int ld_out, int32_t *d_counts, void *d_workspace, size_t ws_bytes, void *stream);
+int uvad_window_slots_features(uvad_ctx *, const void *d_state, int B, float *d_feats, int32_t *d_tw, void *stream);
+/* the same for the waveform model; the sample type (f32, or int16 read as q / 32768) is fixed at reset as in uvad_window_wav_reset */
+size_t uvad_window_wav_slots_state_bytes(const uvad_ctx *, int B, int window, int is_i16);
+size_t uvad_window_wav_slots_workspace_bytes(const uvad_ctx *, int B, int chunk, int window);
+int uvad_window_wav_slots_reset(uvad_ctx *, void *d_state, int B, int chunk, int window, int lookahead, int is_i16, void *stream);
+int uvad_window_wav_slots_step(uvad_ctx *, const float *d_pcm_chunk, const uint8_t *d_flags, int B, int chunk, void *d_state,
+                               float *d_logits, float *d_probs, int ld_out, int32_t *d_counts, void *d_workspace, size_t ws_bytes,
+                               void *stream);
+int uvad_window_wav_slots_step_i16(uvad_ctx *, const int16_t *d_pcm_chunk, const uint8_t *d_flags, int B, int chunk, void *d_state,
+                                   float *d_logits, float *d_probs, int ld_out, int32_t *d_counts, void *d_workspace, size_t ws_bytes,
+                                   void *stream);
+int uvad_window_wav_slots_features(uvad_ctx *, const void *d_state, int B, float *d_feats, int32_t *d_tw, void *stream);
+
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;
  *   1  (default) f32-accurate on the f16 matrix cores: weights scaled by a power of two and split on the host into THREE

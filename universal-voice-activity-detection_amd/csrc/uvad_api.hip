@@ -89,11 +89,14 @@ struct StreamCounters { int64_t n_samples = 0, n_frames = 0, n_steps = 0; };
 struct StreamState { float *h = nullptr, *c = nullptr; size_t layer_stride = 0; };
 struct WindowGroup { StreamCounters sc; int B = 0, W = 0, L = 0; };
 struct WavWindowGroup { int64_t n_samples = 0, n_frames = 0, n_steps = 0; int B = 0, W = 0, L = 0, is_i16 = 0; };
+// a slot pool (uvad_window_slots_*, uvad_window_wav_slots_*): only what reset fixes; every per-slot counter lives on the device
+struct SlotPool { int B = 0, chunk = 0, W = 0, L = 0, is_i16 = 0; };
 
 struct uvad_ctx {
     std::map<void *, StreamCounters> streams;   // host mirror of the lock-step stream groups, keyed by d_state
     std::map<void *, WindowGroup> windows;      // ... and of the windowed stream groups (uvad_window_*)
     std::map<void *, WavWindowGroup> wav_windows;   // ... and of the waveform model's windowed stream groups (uvad_window_wav_*)
+    std::map<void *, SlotPool> slot_pools, wav_slot_pools;   // ... and of the slot pools of both window families (uvad_window_*slots_*)
     int device = 0, n_cu = 256;
     bool has_fb = false, has_model = false, finalized = false, tables_set = false;
     uvad_fbank_cfg fb{};
@@ -2099,6 +2102,328 @@ int uvad_window_wav_features(uvad_ctx *c, const void *d_state, int B, float *d_f
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemcpyAsync(d_feats, reinterpret_cast<const char *>(d_state) + SL.off_feats, (size_t)B * *Tw * c->sc.c3 * sizeof(float),
                              hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+// ---- slot pools of both window families -------------------------------------------------------------------------------------------
+// Every per-slot quantity lives on the device (window_slots.hip): a step's launch arguments depend on (B, chunk) and the buffers alone.
+// counters (both families, 256-aligned blocks): n [B] int64 | e [B] int64 | active [B] int32 | tw_last [B] int32 | step int64
+// log-mel state:  tails [2][B][frame_len] f32 | ring [B][W][n_mels] f32 | counters
+// log-mel workspace: staging [B][nfr frame_len] | new frames [B][nfr][n_mels] | plan [B] | lens [B] int32 |  (nfr = kmax rounded up to even)
+//                    logits, probs [B][W] | classifier workspace of (B, W)
+// waveform state: ring [B][R + J W] samples (f32 / int16) | feats [B][W][c3] f32 (the last step's SincNet output) | counters
+// waveform workspace: window [B][Sw_max] (sized for f32) | nsamp [B] int64 | plan [B] | logits, probs [B][W] | classifier workspace
+//                     of (B, W) | SincNet workspace of (B, Sw_max)
+extern "C++" {
+namespace {
+size_t slot_counter_bytes(int B) {
+    return 2 * align_up((size_t)B * sizeof(long long)) + 2 * align_up((size_t)B * sizeof(int)) + align_up(sizeof(long long));
+}
+SlotCounters slot_counters(char *base, int B) {
+    SlotCounters k;
+    size_t o = 0;
+    k.n = reinterpret_cast<long long *>(base + o); o += align_up((size_t)B * sizeof(long long));
+    k.e = reinterpret_cast<long long *>(base + o); o += align_up((size_t)B * sizeof(long long));
+    k.active = reinterpret_cast<int *>(base + o); o += align_up((size_t)B * sizeof(int));
+    k.tw_last = reinterpret_cast<int *>(base + o); o += align_up((size_t)B * sizeof(int));
+    k.step = reinterpret_cast<long long *>(base + o);
+    return k;
+}
+struct SlotsLayout { size_t off_tail[2] = {0, 0}, off_ring = 0, off_ctr = 0, total = 0; };
+SlotsLayout slots_layout(const uvad_ctx *c, int B, int W) {
+    SlotsLayout L;
+    size_t o = 0;
+    for (int i = 0; i < 2; ++i) { L.off_tail[i] = o; o += align_up((size_t)B * c->fb.frame_len * sizeof(float)); }
+    L.off_ring = o; o += align_up((size_t)B * W * c->fb.n_mels * sizeof(float));
+    L.off_ctr = o; o += slot_counter_bytes(B);
+    L.total = o;
+    return L;
+}
+// the frames of a staging row: kmax, rounded up to even (the feature kernel transforms frames in pairs)
+int slots_frames(const uvad_ctx *c, int chunk) { return (stream_max_frames(c, chunk) + 1) / 2 * 2; }
+int slots_row(const uvad_ctx *c, int chunk) { return slots_frames(c, chunk) * c->fb.frame_len; }
+struct SlotsWs { size_t off_new = 0, off_plan = 0, off_lens = 0, off_logits = 0, off_probs = 0, off_cls = 0, total = 0; };
+SlotsWs slots_ws(const uvad_ctx *c, int B, int chunk, int W) {
+    SlotsWs w;
+    size_t o = align_up((size_t)B * slots_row(c, chunk) * sizeof(float));
+    w.off_new = o; o += align_up((size_t)B * slots_frames(c, chunk) * c->fb.n_mels * sizeof(float));
+    w.off_plan = o; o += align_up((size_t)B * sizeof(SlotPlan));
+    w.off_lens = o; o += align_up((size_t)B * sizeof(int));
+    w.off_logits = o; o += align_up((size_t)B * W * sizeof(float));
+    w.off_probs = o; o += align_up((size_t)B * W * sizeof(float));
+    w.off_cls = o; o += carve(c, B, W).total;
+    w.total = o;
+    return w;
+}
+struct WavSlotsLayout { size_t off_ring = 0, off_feats = 0, off_ctr = 0, total = 0; int64_t ring_len = 0; };
+WavSlotsLayout wav_slots_layout(const uvad_ctx *c, int B, int W, int is_i16) {
+    WavSlotsLayout L;
+    L.ring_len = wav_ring_len(wav_geom(c), W);
+    size_t o = 0;
+    L.off_ring = o; o += align_up((size_t)B * (size_t)L.ring_len * (is_i16 ? sizeof(int16_t) : sizeof(float)));
+    L.off_feats = o; o += align_up((size_t)B * W * c->sc.c3 * sizeof(float));
+    L.off_ctr = o; o += slot_counter_bytes(B);
+    L.total = o;
+    return L;
+}
+struct WavSlotsWs { size_t off_nsamp = 0, off_plan = 0, off_logits = 0, off_probs = 0, off_cls = 0, cls_bytes = 0, off_sinc = 0, sinc_bytes = 0, total = 0; };
+WavSlotsWs wav_slots_ws(const uvad_ctx *c, int B, int W) {
+    WavSlotsWs w;
+    const int64_t sw = wav_span(wav_geom(c), W);
+    size_t o = align_up((size_t)B * (size_t)sw * sizeof(float));
+    w.off_nsamp = o; o += align_up((size_t)B * sizeof(int64_t));
+    w.off_plan = o; o += align_up((size_t)B * sizeof(SlotPlan));
+    w.off_logits = o; o += align_up((size_t)B * W * sizeof(float));
+    w.off_probs = o; o += align_up((size_t)B * W * sizeof(float));
+    w.off_cls = o; w.cls_bytes = carve(c, B, W).total; o += w.cls_bytes;
+    w.off_sinc = o; w.sinc_bytes = sinc_carve(c, B, sw).total; o += w.sinc_bytes;
+    w.total = o;
+    return w;
+}
+// the classifier at (B, W) with per-row lengths, time chunks off and no timing events, as the window steps run it
+int slots_classify(uvad_ctx *c, const float *feats, int B, int W, float *lg, float *pr, char *cws, size_t cws_bytes, hipStream_t s,
+                   bool check_range, bool planes, const int *lens) {
+    const bool timing = c->timing;
+    const int chunk_mode = c->chunk_mode;
+    c->timing = false;
+    c->chunk_mode = 1;
+    const int r = classify_impl(c, feats, B, W, lg, pr, cws, cws_bytes, s, false, check_range, nullptr, 0, planes, nullptr, lens);
+    c->timing = timing;
+    c->chunk_mode = chunk_mode;
+    return r;
+}
+}  // namespace
+}  // extern "C++"
+
+size_t uvad_window_slots_state_bytes(const uvad_ctx *c, int B, int window) {
+    if (!c || !c->has_fb || !c->has_model || B <= 0 || window < 1) return 0;
+    return slots_layout(c, B, window).total;
+}
+
+size_t uvad_window_slots_workspace_bytes(const uvad_ctx *c, int B, int chunk, int window) {
+    if (!c || !c->has_fb || !c->has_model || B <= 0 || chunk <= 0 || window < 1) return 0;
+    return slots_ws(c, B, chunk, window).total;
+}
+
+int uvad_window_slots_reset(uvad_ctx *c, void *d_state, int B, int chunk, int window, int lookahead, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_state || B <= 0 || B > 65535 || chunk <= 0) return fail(c, UVAD_E_ARG, "uvad_window_slots_reset: bad argument");
+    if (window < 1) return fail(c, UVAD_E_ARG, "uvad_window_slots_reset: window must be >= 1 frame");
+    if (lookahead < 0 || lookahead >= window) return fail(c, UVAD_E_ARG, "uvad_window_slots_reset: need 0 <= lookahead < window");
+    if (int r = window_check_cfg(c, "uvad_window_slots_reset")) return r;
+    const int n_left = (c->fb.frame_len - c->fb.frame_shift) / 2, kmax = stream_max_frames(c, chunk);
+    if (chunk < n_left)
+        return fail(c, UVAD_E_ARG, "uvad_window_slots_reset: every step can be a session's first: chunk must hold at least (frame_len - shift) / 2 = " +
+                                       std::to_string(n_left) + " samples");
+    if ((int64_t)lookahead + kmax > window)
+        return fail(c, UVAD_E_ARG, "uvad_window_slots_reset: lookahead + chunk / frame_shift + 1 = " + std::to_string(lookahead + kmax) +
+                                       " frames exceeds the window of " + std::to_string(window));
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemsetAsync(d_state, 0, slots_layout(c, B, window).total, (hipStream_t)stream));
+    SlotPool g;
+    g.B = B; g.chunk = chunk; g.W = window; g.L = lookahead;
+    c->slot_pools[d_state] = g;
+    return UVAD_OK;
+}
+
+int uvad_window_slots_step(uvad_ctx *c, const float *d_pcm_chunk, const uint8_t *d_flags, int B, int chunk, void *d_state, float *d_logits,
+                           float *d_probs, int ld_out, int32_t *d_counts, void *ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_pcm_chunk || !d_state || (!d_logits && !d_probs) || !d_counts || !ws || B <= 0 || chunk <= 0)
+        return fail(c, UVAD_E_ARG, "uvad_window_slots_step: bad argument");
+    if (!c->finalized || !c->tables_set) return fail(c, UVAD_E_STATE, "uvad_window_slots_step: context not ready (tables / weights)");
+    if (int r = window_check_cfg(c, "uvad_window_slots_step")) return r;
+    auto it = c->slot_pools.find(d_state);
+    if (it == c->slot_pools.end()) return fail(c, UVAD_E_STATE, "uvad_window_slots_step: call uvad_window_slots_reset on this state first");
+    const SlotPool &g = it->second;
+    if (B != g.B) return fail(c, UVAD_E_ARG, "uvad_window_slots_step: B differs from the one the state was reset with");
+    if (chunk != g.chunk) return fail(c, UVAD_E_ARG, "uvad_window_slots_step: chunk differs from the one the state was reset with");
+    const int kmax = stream_max_frames(c, chunk), F = c->fb.n_mels;
+    if ((int64_t)ld_out < (int64_t)g.L + kmax)
+        return fail(c, UVAD_E_ARG, "uvad_window_slots_step: ld_out must be at least lookahead + chunk / frame_shift + 1 = " + std::to_string(g.L + kmax));
+    const SlotsWs wl = slots_ws(c, B, chunk, g.W);
+    if (ws_bytes < wl.total) return fail(c, UVAD_E_WORKSPACE, "slot pool workspace too small: need " + std::to_string(wl.total) + " bytes");
+    const SlotsLayout SL = slots_layout(c, B, g.W);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    char *st = reinterpret_cast<char *>(d_state);
+    char *wsb = reinterpret_cast<char *>(ws);
+    const SlotCounters ctr = slot_counters(st + SL.off_ctr, B);
+    SlotPlan *plan = reinterpret_cast<SlotPlan *>(wsb + wl.off_plan);
+    int *lens = reinterpret_cast<int *>(wsb + wl.off_lens);
+    float *staging = reinterpret_cast<float *>(wsb), *newf = reinterpret_cast<float *>(wsb + wl.off_new);
+    // 1. flags, plans, aligned staging rows and the next tails
+    SlotStageArgs sa{};
+    sa.chunk = d_pcm_chunk; sa.flags = d_flags; sa.ctr = ctr; sa.tails = reinterpret_cast<float *>(st + SL.off_tail[0]);
+    sa.staging = staging; sa.plan = plan;
+    sa.B = B; sa.chunk_len = chunk; sa.frame_len = c->fb.frame_len; sa.shift = c->fb.frame_shift; sa.n_left = (c->fb.frame_len - c->fb.frame_shift) / 2;
+    sa.row = slots_row(c, chunk); sa.W = g.W; sa.L = g.L;
+    HIPCHK(c, launch_slot_stage(sa, s));
+    // 2. the unchanged feature kernel on plain rows of side-by-side frames (frame_shift = frame_len): the staging row's frames, those
+    //    at t >= k_b discarded by the assembly
+    const int nfr = slots_frames(c, chunk);
+    FbankArgs fa{};
+    fa.pcm = staging; fa.pcm_is_i16 = 0; fa.B = B; fa.S = sa.row; fa.T = nfr; fa.row_stride = sa.row;
+    fa.frame_len = c->fb.frame_len; fa.frame_shift = c->fb.frame_len; fa.n_mels = F;
+    fa.preemph = c->fb.preemph; fa.log_floor = c->fb.log_floor; fa.remove_dc = c->fb.remove_dc; fa.snip_edges = 1;
+    fa.tab.window = c->d_window; fa.tab.mel_start = c->d_mel_start; fa.tab.mel_len = c->d_mel_len;
+    fa.tab.mel_w = c->d_mel_w; fa.tab.mel_wt = c->d_mel_wt; fa.tab.mel_stride = c->mel_stride; fa.tab.tw512 = c->d_tw512; fa.tab.nyquist = c->mel_nyquist;
+    fa.feats = newf;
+    HIPCHK(c, launch_fbank(fa, s));
+    // 3. ring commit and the left-aligned windows into the first projection's operand; lens = Tw_b
+    char *cws = wsb + wl.off_cls;
+    const WsLayout w = carve(c, B, g.W);
+    const bool planes = c->gemm_mode >= 1 && c->f16_ok;
+    float *feats = reinterpret_cast<float *>(cws + w.off_feats);
+    SlotAssembleArgs a{};
+    a.plan = plan; a.ctr = ctr; a.newf = newf; a.kmax = nfr; a.ring = reinterpret_cast<float *>(st + SL.off_ring);
+    a.B = B; a.W = g.W; a.F = F;
+    a.planes = planes; a.Fp = w.Fp; a.tiles = w.tiles;
+    a.xh = reinterpret_cast<unsigned short *>(cws + w.off_fplanes); a.xl = a.xh + plane_rows(w.M) * (size_t)w.Fp;
+    a.out = feats; a.lens = lens;
+    HIPCHK(c, launch_slot_assemble(a, s));
+    // 4. the classifier at (B, W) with lens
+    float *lg = reinterpret_cast<float *>(wsb + wl.off_logits), *pr = reinterpret_cast<float *>(wsb + wl.off_probs);
+    if (int r = slots_classify(c, feats, B, g.W, d_logits ? lg : nullptr, d_probs ? pr : nullptr, cws, wl.total - wl.off_cls, s, false, planes, lens))
+        return r;
+    // 5. emission, counts and the counters
+    SlotEmitArgs ea{};
+    ea.plan = plan; ea.ctr = ctr; ea.logits_in = lg; ea.probs_in = pr; ea.B = B; ea.W = g.W;
+    ea.logits = d_logits; ea.probs = d_probs; ea.ld_out = ld_out; ea.counts = d_counts;
+    HIPCHK(c, launch_slot_emit(ea, s));
+    return UVAD_OK;
+}
+
+int uvad_window_slots_features(uvad_ctx *c, const void *d_state, int B, float *d_feats, int32_t *d_tw, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_state || !d_feats || !d_tw || B <= 0) return fail(c, UVAD_E_ARG, "uvad_window_slots_features: bad argument");
+    if (int r = window_check_cfg(c, "uvad_window_slots_features")) return r;
+    auto it = c->slot_pools.find(const_cast<void *>(d_state));
+    if (it == c->slot_pools.end()) return fail(c, UVAD_E_STATE, "uvad_window_slots_features: call uvad_window_slots_reset on this state first");
+    const SlotPool &g = it->second;
+    if (B != g.B) return fail(c, UVAD_E_ARG, "uvad_window_slots_features: B differs from the one the state was reset with");
+    const SlotsLayout SL = slots_layout(c, B, g.W);
+    char *st = reinterpret_cast<char *>(const_cast<void *>(d_state));
+    HIPCHK(c, hipSetDevice(c->device));
+    SlotAssembleArgs a{};
+    a.ctr = slot_counters(st + SL.off_ctr, B); a.ring = reinterpret_cast<float *>(st + SL.off_ring);
+    a.B = B; a.W = g.W; a.F = c->fb.n_mels; a.out = d_feats; a.lens = d_tw;
+    HIPCHK(c, launch_slot_assemble(a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+size_t uvad_window_wav_slots_state_bytes(const uvad_ctx *c, int B, int window, int is_i16) {
+    if (!c || !c->has_model || !c->has_sinc || B <= 0 || window < 1 || (is_i16 != 0 && is_i16 != 1)) return 0;
+    return wav_slots_layout(c, B, window, is_i16).total;
+}
+
+size_t uvad_window_wav_slots_workspace_bytes(const uvad_ctx *c, int B, int chunk, int window) {
+    if (!c || !c->has_model || !c->has_sinc || B <= 0 || chunk <= 0 || window < 1) return 0;
+    return wav_slots_ws(c, B, window).total;
+}
+
+int uvad_window_wav_slots_reset(uvad_ctx *c, void *d_state, int B, int chunk, int window, int lookahead, int is_i16, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_state || B <= 0 || B > 65535 || chunk <= 0 || (is_i16 != 0 && is_i16 != 1))
+        return fail(c, UVAD_E_ARG, "uvad_window_wav_slots_reset: bad argument");
+    if (window < 1) return fail(c, UVAD_E_ARG, "uvad_window_wav_slots_reset: window must be >= 1 frame");
+    if (lookahead < 0 || lookahead >= window) return fail(c, UVAD_E_ARG, "uvad_window_wav_slots_reset: need 0 <= lookahead < window");
+    if (int r = wav_window_check_cfg(c, "uvad_window_wav_slots_reset")) return r;
+    const WavGeom geo = wav_geom(c);
+    const int kmax = wav_kmax(geo, chunk);
+    if ((int64_t)lookahead + kmax > window)
+        return fail(c, UVAD_E_ARG, "uvad_window_wav_slots_reset: lookahead + ceil(chunk / J) = " + std::to_string((int64_t)lookahead + kmax) +
+                                       " frames exceeds the window of " + std::to_string(window));
+    const int64_t sw = wav_span(geo, window);
+    if (sw > 0x7fffffff - chunk) return fail(c, UVAD_E_UNSUPPORTED, "uvad_window_wav_slots_reset: window too long");
+    // the closed form the window arithmetic rests on, against the stage-by-stage floor chain
+    if (uvad_sincnet_num_frames(c, sw) != window)
+        return fail(c, UVAD_E_STATE, "uvad_window_wav_slots_reset: internal: frames(S) = (S - R) / J + 1 disagrees with uvad_sincnet_num_frames");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemsetAsync(d_state, 0, wav_slots_layout(c, B, window, is_i16).total, (hipStream_t)stream));
+    SlotPool g;
+    g.B = B; g.chunk = chunk; g.W = window; g.L = lookahead; g.is_i16 = is_i16;
+    c->wav_slot_pools[d_state] = g;
+    return UVAD_OK;
+}
+
+static int window_wav_slots_step_impl(uvad_ctx *c, const void *d_pcm_chunk, int is_i16, const uint8_t *d_flags, int B, int chunk, void *d_state,
+                                      float *d_logits, float *d_probs, int ld_out, int32_t *d_counts, void *ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    const std::string who = is_i16 ? "uvad_window_wav_slots_step_i16" : "uvad_window_wav_slots_step";
+    if (!d_pcm_chunk || !d_state || (!d_logits && !d_probs) || !d_counts || !ws || B <= 0 || chunk <= 0)
+        return fail(c, UVAD_E_ARG, who + ": bad argument");
+    if (int r = wav_window_check_cfg(c, who)) return r;
+    auto it = c->wav_slot_pools.find(d_state);
+    if (it == c->wav_slot_pools.end()) return fail(c, UVAD_E_STATE, who + ": call uvad_window_wav_slots_reset on this state first");
+    const SlotPool &g = it->second;
+    if (B != g.B) return fail(c, UVAD_E_ARG, who + ": B differs from the one the state was reset with");
+    if (chunk != g.chunk) return fail(c, UVAD_E_ARG, who + ": chunk differs from the one the state was reset with");
+    if (g.is_i16 != is_i16)
+        return fail(c, UVAD_E_ARG, who + (g.is_i16 ? ": the state was reset for int16 samples (uvad_window_wav_slots_step_i16)"
+                                                   : ": the state was reset for f32 samples (uvad_window_wav_slots_step)"));
+    const WavGeom geo = wav_geom(c);
+    const int kmax = wav_kmax(geo, chunk);
+    if ((int64_t)ld_out < (int64_t)g.L + kmax)
+        return fail(c, UVAD_E_ARG, who + ": ld_out must be at least lookahead + ceil(chunk / J) = " + std::to_string((int64_t)g.L + kmax));
+    const WavSlotsWs wl = wav_slots_ws(c, B, g.W);
+    if (ws_bytes < wl.total) return fail(c, UVAD_E_WORKSPACE, who + ": slot pool workspace too small: need " + std::to_string(wl.total) + " bytes");
+    const WavSlotsLayout SL = wav_slots_layout(c, B, g.W, is_i16);
+    const int64_t sw_max = wav_span(geo, g.W);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    char *st = reinterpret_cast<char *>(d_state);
+    char *wsb = reinterpret_cast<char *>(ws);
+    const SlotCounters ctr = slot_counters(st + SL.off_ctr, B);
+    SlotPlan *plan = reinterpret_cast<SlotPlan *>(wsb + wl.off_plan);
+    int64_t *nsamp = reinterpret_cast<int64_t *>(wsb + wl.off_nsamp);
+    // 1. flags, plans, the chunk into the ring and each slot's window left-aligned at S = Sw_max
+    WavSlotArgs a{};
+    a.chunk = d_pcm_chunk; a.flags = d_flags; a.ctr = ctr; a.ring = st + SL.off_ring; a.ring_len = SL.ring_len;
+    a.out = wsb; a.Sw_max = (int)sw_max; a.nsamp = reinterpret_cast<long long *>(nsamp); a.plan = plan;
+    a.B = B; a.chunk_len = chunk; a.J = (int)geo.J; a.R = (int)geo.R; a.W = g.W; a.L = g.L;
+    HIPCHK(c, launch_wav_slot_assemble(a, is_i16, s));
+    // 2. SincNet in its lens form (workgroups walk the valid tiles only) into the state (the features tap) ...
+    float *feats = reinterpret_cast<float *>(st + SL.off_feats);
+    const int *lens = nullptr;
+    if (int r = sincnet_impl(c, wsb, is_i16, B, sw_max, feats, wsb + wl.off_sinc, wl.sinc_bytes, s, nsamp, &lens)) return r;
+    // 3. ... the classifier at (B, W) with the rows' frame counts ...
+    float *lg = reinterpret_cast<float *>(wsb + wl.off_logits), *pr = reinterpret_cast<float *>(wsb + wl.off_probs);
+    if (int r = slots_classify(c, feats, B, g.W, d_logits ? lg : nullptr, d_probs ? pr : nullptr, wsb + wl.off_cls, wl.cls_bytes, s, true, false,
+                               lens))
+        return r;
+    // 4. ... and emission, counts and the counters
+    SlotEmitArgs ea{};
+    ea.plan = plan; ea.ctr = ctr; ea.logits_in = lg; ea.probs_in = pr; ea.B = B; ea.W = g.W;
+    ea.logits = d_logits; ea.probs = d_probs; ea.ld_out = ld_out; ea.counts = d_counts;
+    HIPCHK(c, launch_slot_emit(ea, s));
+    return UVAD_OK;
+}
+
+int uvad_window_wav_slots_step(uvad_ctx *c, const float *d_pcm_chunk, const uint8_t *d_flags, int B, int chunk, void *d_state, float *d_logits,
+                               float *d_probs, int ld_out, int32_t *d_counts, void *ws, size_t ws_bytes, void *stream) {
+    return window_wav_slots_step_impl(c, d_pcm_chunk, 0, d_flags, B, chunk, d_state, d_logits, d_probs, ld_out, d_counts, ws, ws_bytes, stream);
+}
+int uvad_window_wav_slots_step_i16(uvad_ctx *c, const int16_t *d_pcm_chunk, const uint8_t *d_flags, int B, int chunk, void *d_state,
+                                   float *d_logits, float *d_probs, int ld_out, int32_t *d_counts, void *ws, size_t ws_bytes, void *stream) {
+    return window_wav_slots_step_impl(c, d_pcm_chunk, 1, d_flags, B, chunk, d_state, d_logits, d_probs, ld_out, d_counts, ws, ws_bytes, stream);
+}
+
+int uvad_window_wav_slots_features(uvad_ctx *c, const void *d_state, int B, float *d_feats, int32_t *d_tw, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_state || !d_feats || !d_tw || B <= 0) return fail(c, UVAD_E_ARG, "uvad_window_wav_slots_features: bad argument");
+    if (int r = wav_window_check_cfg(c, "uvad_window_wav_slots_features")) return r;
+    auto it = c->wav_slot_pools.find(const_cast<void *>(d_state));
+    if (it == c->wav_slot_pools.end())
+        return fail(c, UVAD_E_STATE, "uvad_window_wav_slots_features: call uvad_window_wav_slots_reset on this state first");
+    const SlotPool &g = it->second;
+    if (B != g.B) return fail(c, UVAD_E_ARG, "uvad_window_wav_slots_features: B differs from the one the state was reset with");
+    const WavSlotsLayout SL = wav_slots_layout(c, B, g.W, g.is_i16);
+    char *st = reinterpret_cast<char *>(const_cast<void *>(d_state));
+    const SlotCounters ctr = slot_counters(st + SL.off_ctr, B);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(d_feats, st + SL.off_feats, (size_t)B * g.W * c->sc.c3 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIPCHK(c, hipMemcpyAsync(d_tw, ctr.tw_last, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return UVAD_OK;
 }
 

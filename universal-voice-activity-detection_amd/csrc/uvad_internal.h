@@ -258,6 +258,55 @@ struct WavWindowArgs {
 };
 hipError_t launch_wav_window_assemble(const WavWindowArgs &a, int is_i16, hipStream_t s);
 
+// ---- window_slots.hip: the slot pools of both window families (uvad_window_slots_*, uvad_window_wav_slots_*) ------------------------
+// Per-slot counters in the pool's state, device arrays [B]: samples and frames of the slot's session so far, whether a session is open,
+// the window length the last step classified (the features tap); step: the pool's step count (the log-mel tail's ping-pong parity).
+struct SlotCounters { long long *n, *e; int *active, *tw_last; long long *step; };
+// What one step does to one slot, written by the step's first kernel into the workspace and read by the later ones
+struct alignas(16) SlotPlan {
+    long long n, e, e_prev;          // samples and frames of the session after the step, frames before it
+    int live, end, first, k;         // holds a session this step / it ends now / this is its first chunk / new frames
+    int offset, Tw, r0, n_emit;      // (log-mel) first new frame in the virtual [tail | chunk] row; window; emitted rows [r0, r0 + n_emit)
+    int pad[2];
+};
+// log-mel: flags applied, plan[b] written, aligned staging rows [B][row] of the new frames side by side (row = frames * frame_len, frames =
+// kmax rounded up to even) and the next tails
+struct SlotStageArgs {
+    const float *chunk; const uint8_t *flags; SlotCounters ctr;
+    float *tails;                    // [2][B][frame_len]: the step reads tails[step & 1], writes tails[(step & 1) ^ 1]
+    float *staging; SlotPlan *plan;
+    int B, chunk_len, frame_len, shift, n_left, row, W, L;
+};
+hipError_t launch_slot_stage(const SlotStageArgs &a, hipStream_t s);
+// log-mel: the new frames newf [B][kmax][F] (kmax: the staging rows' frames) committed to the ring [B][W][F] (session frame f in slot f % W) and each slot's window of
+// Tw_b frames left-aligned into the planes (window_assemble_kernel's layout at T = W) or out [B][W][F], zero past Tw_b; lens[b] = Tw_b.
+// plan == nullptr: the read-only tap of the window the last step classified (ctr.e, ctr.tw_last), into out.
+struct SlotAssembleArgs {
+    const SlotPlan *plan; SlotCounters ctr;
+    const float *newf; int kmax; float *ring;
+    int B, W, F;
+    int planes; unsigned short *xh, *xl; int Fp, tiles;
+    float *out; int *lens;
+};
+hipError_t launch_slot_assemble(const SlotAssembleArgs &a, hipStream_t s);
+// waveform: flags applied, plan[b] written, the chunk committed to the PCM ring [B][ring_len] (session sample p in slot p % ring_len),
+// each slot's window of Sw_b samples left-aligned into out [B][Sw_max] (zero past Sw_b), nsamp[b] = Sw_b
+struct WavSlotArgs {
+    const void *chunk; const uint8_t *flags; SlotCounters ctr;
+    void *ring; long long ring_len;
+    void *out; int Sw_max; long long *nsamp; SlotPlan *plan;
+    int B, chunk_len, J, R, W, L;
+};
+hipError_t launch_wav_slot_assemble(const WavSlotArgs &a, int is_i16, hipStream_t s);
+// both: rows [r0_b, r0_b + n_b) of logits_in / probs_in [B][W] -> columns 0 .. n_b - 1 of logits / probs [B][ld_out], counts[b] = n_b,
+// the counters committed and the step counted
+struct SlotEmitArgs {
+    const SlotPlan *plan; SlotCounters ctr;
+    const float *logits_in, *probs_in; int B, W;
+    float *logits, *probs; int ld_out; int *counts;
+};
+hipError_t launch_slot_emit(const SlotEmitArgs &a, hipStream_t s);
+
 // ---- lstm_stack.hip: every layer of a causal (one-direction, H = 128) stack for T <= LSTM_STACK_TMAX new frames in ONE launch, carried
 //      (h, c) updated in place: the streaming step (uvad_stream_step).  Exact f32.
 constexpr int LSTM_STACK_TMAX = 4, LSTM_STACK_MAX_LAYERS = 8, LSTM_STACK_MAX_LIN = 4;

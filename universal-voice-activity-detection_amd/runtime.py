@@ -75,6 +75,71 @@ def wav_window_schedule(steps: int, chunk: int, window: int, lookahead: int = 0,
     return out
 
 
+def _slots_plan(flags, step_frames, window: int, lookahead: int):
+    """Shared walk of a slot pool schedule: flags[step][slot] (bit 0 START, bit 1 END); step_frames(samples) -> frames complete after
+    `samples` samples of a session.  -> [[(session, emit_lo, emit_hi, frames) per slot] per step]; session = -1 for an idle slot."""
+    rows, sessions, live, next_id = [], {}, {}, 0
+    for fl in flags:
+        row = []
+        for b, f in enumerate(fl):
+            f = int(f)
+            if f & 1:
+                live[b] = next_id
+                sessions[next_id] = [0, 0]
+                next_id += 1
+            sid = live.get(b)
+            if sid is None:
+                row.append((-1, 0, 0, 0))
+                continue
+            n_prev, e_prev = sessions[sid]
+            n = n_prev + step_frames[1]
+            e = max(e_prev, step_frames[0](n))
+            lo = max(0, e_prev - lookahead)
+            hi = e if f & 2 else max(0, e - lookahead)
+            sessions[sid] = [n, e]
+            row.append((sid, lo, hi, e))
+            if f & 2:
+                del live[b]
+        rows.append(row)
+    return rows
+
+
+def window_slots_ld_out(chunk: int, lookahead: int, frame_shift: int = 160) -> int:
+    """The least ld_out a log-mel slot pool step accepts: L + kmax, kmax = chunk // frame_shift + 1 frames a step can complete."""
+    return lookahead + chunk // frame_shift + 1
+
+
+def wav_window_slots_ld_out(chunk: int, lookahead: int, J: int = 270) -> int:
+    """The least ld_out a waveform slot pool step accepts: L + kmax, kmax = ceil(chunk / J)."""
+    return lookahead + -(-chunk // J)
+
+
+def window_slots_plan(flags, chunk: int, window: int, lookahead: int = 0, frame_len: int = 400, frame_shift: int = 160):
+    """The frames each step of a log-mel slot pool (uvad_window_slots_step, include/uvad.h) emits.  flags: per step, one flag per slot
+    (bit 0 UVAD_SLOT_START, bit 1 UVAD_SLOT_END; a (steps, B) array or nested lists).  -> per step, per slot (session, emit_lo, emit_hi,
+    frames): the slot's session (numbered in order of their starts, -1 for an idle slot), the session-local frames [emit_lo, emit_hi) the
+    step emits (emit_hi - emit_lo = its count) and the session's complete frames after the step.  A session's frames are those of a
+    single-feed window stream opened at its start (window_step_plan); its END step also flushes the lookahead frames held back."""
+    n_left = (frame_len - frame_shift) // 2
+    if chunk < n_left:
+        raise ValueError(f"every step can be a session's first: chunk must hold at least (frame_len - shift) / 2 = {n_left} samples")
+    if lookahead < 0 or lookahead >= window or window_slots_ld_out(chunk, lookahead, frame_shift) > window:
+        raise ValueError(f"need 0 <= lookahead < window and lookahead + chunk // frame_shift + 1 <= window (got {lookahead}, {chunk}, {window})")
+
+    def frames(n):
+        return (n + n_left - frame_len) // frame_shift + 1 if n + n_left - frame_len >= 0 else 0
+
+    return _slots_plan(flags, (frames, chunk), window, lookahead)
+
+
+def wav_window_slots_plan(flags, chunk: int, window: int, lookahead: int = 0, J: int = 270, R: int = 991):
+    """The frames each step of a waveform slot pool (uvad_window_wav_slots_step, include/uvad.h) emits: as window_slots_plan, with the
+    whole frames of J samples and receptive field R of wav_window_step_plan."""
+    if lookahead < 0 or lookahead >= window or wav_window_slots_ld_out(chunk, lookahead, J) > window:
+        raise ValueError(f"need 0 <= lookahead < window and lookahead + ceil(chunk / J) <= window (got {lookahead}, {chunk}, {window})")
+    return _slots_plan(flags, (lambda n: 0 if n < R else (n - R) // J + 1, chunk), window, lookahead)
+
+
 class VadRuntime:
     def __init__(self, device, fbank: Optional[FbankConfig] = None, model: Optional[dict] = None, sincnet: Optional[dict] = None):
         """model: {"encoding_dim": int, "lstm": {...merged defaults...}, "linear": {...}} or None.
@@ -582,6 +647,150 @@ class VadRuntime:
                 self._check(self.lib.uvad_window_wav_features(self.ctx, st["state"].data_ptr(), st["B"], feats.data_ptr(), C.byref(tw),
                                                               self._stream()))
             return feats
+
+    # ------------------------------------------------------------------ slot pools: window streams whose feeds start and end independently
+    def _slot_flags(self, B: int, start, end, buf=None):
+        """start / end: None, a bool mask of B entries or a list of slot indices (host or device) -> uint8 flags [B] on the device
+        (UVAD_SLOT_START | UVAD_SLOT_END), written into buf if given; None when neither is given and there is no buf."""
+        if start is None and end is None and buf is None:
+            return None
+
+        def mask(m):
+            if m is None:
+                return torch.zeros(B, dtype=torch.uint8, device=self.device)
+            t = m if torch.is_tensor(m) else torch.as_tensor(np.asarray(m))
+            t = t.to(self.device)
+            if t.dtype == torch.bool:
+                if tuple(t.shape) != (B,):
+                    raise ValueError(f"a slot mask must have {B} entries, got {tuple(t.shape)}")
+                return t.to(torch.uint8)
+            out = torch.zeros(B, dtype=torch.uint8, device=self.device)
+            if t.numel():
+                idx = t.reshape(-1).long()
+                if not torch.is_tensor(m) and (int(idx.min()) < 0 or int(idx.max()) >= B):
+                    raise ValueError(f"slot indices must lie in [0, {B})")
+                out[idx] = 1
+            return out
+
+        flags = mask(start) | (mask(end) << 1)
+        if buf is None:
+            return flags
+        buf.copy_(flags)
+        return buf
+
+    def _slots_step(self, st, pcm_chunk, start, end, fn):
+        """One slot pool step: eager, or (graphs=True) the single graph captured on the first step and replayed for every later one,
+        reading the chunk and the flags from fixed buffers.  Graphs captured before a weight hot-swap are dropped."""
+        B = st["B"]
+        out, counts = st["out"], st["counts"]
+
+        def enqueue(src, flags):
+            return fn(self.ctx, src.data_ptr(), flags.data_ptr() if flags is not None else None, B, st["chunk"], st["state"].data_ptr(),
+                      out.data_ptr(), None, out.shape[1], counts.data_ptr(), st["ws"].data_ptr(), st["ws"].numel(), self._stream())
+
+        if st["graphs"] is None:
+            self._check(enqueue(pcm_chunk, self._slot_flags(B, start, end)))
+            return out, counts
+        if st.get("weights_gen") != getattr(self, "_weights_gen", 0):
+            st["graph"] = None       # captured before a weight hot-swap: its kernel nodes point at freed buffers
+            st["weights_gen"] = getattr(self, "_weights_gen", 0)
+        st["in"].copy_(pcm_chunk)
+        self._slot_flags(B, start, end, st["flags"])
+        if st["graph"] is None:
+            cur = torch.cuda.current_stream(self.device)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):                    # capture: recorded, not run
+                r = enqueue(st["in"], st["flags"])
+            self._check(r)
+            st["graph"] = g
+            st["graphs"] += 1
+            torch.cuda.current_stream(self.device).wait_stream(cur)
+        st["graph"].replay()
+        return out, counts
+
+    def window_slots_open(self, B: int, chunk: int, window: int = 500, lookahead: int = 0, graphs: bool = False):
+        """Allocate and reset a log-mel slot pool (uvad_window_slots_reset): B slots stepping `chunk` samples at a time, each holding at
+        most one session, windows of `window` frames, frames emitted `lookahead` frames behind the newest complete one (the END step
+        flushes them).  graphs: capture the first step into a hipGraph and replay it for every later step."""
+        window_slots_plan([], chunk, window, lookahead, self._fb_c.frame_len, self._fb_c.frame_shift)   # the limits, before allocating
+        with torch.cuda.device(self.device):
+            nbytes = int(self.lib.uvad_window_slots_state_bytes(self.ctx, B, window))
+            if nbytes == 0:
+                raise RuntimeError("slot pools need a runtime built with both a FbankConfig and a model, and window >= 1")
+            state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._check(self.lib.uvad_window_slots_reset(self.ctx, state.data_ptr(), B, chunk, window, lookahead, self._stream()))
+            ws = torch.empty(int(self.lib.uvad_window_slots_workspace_bytes(self.ctx, B, chunk, window)), dtype=torch.uint8, device=self.device)
+            ld = window_slots_ld_out(chunk, lookahead, self._fb_c.frame_shift)
+            return {"state": state, "ws": ws, "B": B, "chunk": chunk, "window": window, "lookahead": lookahead,
+                    "out": torch.empty((B, ld), dtype=torch.float32, device=self.device),
+                    "counts": torch.zeros(B, dtype=torch.int32, device=self.device),
+                    "in": torch.empty((B, chunk), dtype=torch.float32, device=self.device),
+                    "flags": torch.zeros(B, dtype=torch.uint8, device=self.device),
+                    "graphs": 0 if graphs else None, "graph": None, "weights_gen": getattr(self, "_weights_gen", 0)}
+
+    def window_slots_step(self, st, pcm_chunk: "torch.Tensor", start=None, end=None):
+        """pcm_chunk (B, chunk) f32 on the GPU; start / end: slots whose session starts with this chunk / ends after it (bool masks or
+        index lists, host or device).  -> (logits (B, lookahead + kmax), counts int32 (B,)), both on the device and overwritten by the
+        next step: row b holds the counts[b] frames slot b emits this step in its first columns (window_slots_plan says which)."""
+        with torch.cuda.device(self.device):
+            pcm_chunk = self._dev_f32(pcm_chunk, "pcm_chunk")
+            if tuple(pcm_chunk.shape) != (st["B"], st["chunk"]):
+                raise ValueError(f"expected a ({st['B']}, {st['chunk']}) chunk, got {tuple(pcm_chunk.shape)}")
+            return self._slots_step(st, pcm_chunk, start, end, self.lib.uvad_window_slots_step)
+
+    def window_slots_features(self, st):
+        """(features (B, W, n_mels), Tw int32 (B,)): the window each slot's last step classified, left-aligned (uvad_window_slots_features)."""
+        with torch.cuda.device(self.device):
+            feats = torch.empty((st["B"], st["window"], self._fb_c.n_mels), dtype=torch.float32, device=self.device)
+            tw = torch.empty(st["B"], dtype=torch.int32, device=self.device)
+            self._check(self.lib.uvad_window_slots_features(self.ctx, st["state"].data_ptr(), st["B"], feats.data_ptr(), tw.data_ptr(),
+                                                            self._stream()))
+            return feats, tw
+
+    def wav_window_slots_open(self, B: int, chunk: int, window: int = 293, lookahead: int = 0, graphs: bool = False,
+                              dtype=torch.float32):
+        """Allocate and reset a waveform slot pool (uvad_window_wav_slots_reset): window_slots_open for the SincNet PyanNet, samples of
+        dtype torch.float32 or torch.int16 (read as q / 32768)."""
+        if dtype not in (torch.float32, torch.int16):
+            raise ValueError(f"dtype must be torch.float32 or torch.int16, got {dtype}")
+        J, R = self.wav_window_geometry()
+        wav_window_slots_plan([], chunk, window, lookahead, J, R)            # the limits, before anything is allocated
+        i16 = int(dtype == torch.int16)
+        with torch.cuda.device(self.device):
+            nbytes = int(self.lib.uvad_window_wav_slots_state_bytes(self.ctx, B, window, i16))
+            if nbytes == 0:
+                raise RuntimeError("waveform slot pools need a runtime built with a model and a SincNet configuration")
+            state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._check(self.lib.uvad_window_wav_slots_reset(self.ctx, state.data_ptr(), B, chunk, window, lookahead, i16, self._stream()))
+            ws = torch.empty(int(self.lib.uvad_window_wav_slots_workspace_bytes(self.ctx, B, chunk, window)), dtype=torch.uint8,
+                             device=self.device)
+            return {"state": state, "ws": ws, "B": B, "chunk": chunk, "window": window, "lookahead": lookahead, "J": J, "R": R,
+                    "dtype": dtype,
+                    "out": torch.empty((B, wav_window_slots_ld_out(chunk, lookahead, J)), dtype=torch.float32, device=self.device),
+                    "counts": torch.zeros(B, dtype=torch.int32, device=self.device),
+                    "in": torch.empty((B, chunk), dtype=dtype, device=self.device),
+                    "flags": torch.zeros(B, dtype=torch.uint8, device=self.device),
+                    "graphs": 0 if graphs else None, "graph": None, "weights_gen": getattr(self, "_weights_gen", 0)}
+
+    def wav_window_slots_step(self, st, pcm_chunk: "torch.Tensor", start=None, end=None):
+        """window_slots_step for a waveform slot pool: pcm_chunk (B, chunk) of the dtype the pool was opened with."""
+        with torch.cuda.device(self.device):
+            if not torch.is_tensor(pcm_chunk) or pcm_chunk.device != self.device or pcm_chunk.dtype != st["dtype"]:
+                raise RuntimeError(f"pcm_chunk must be a {st['dtype']} tensor on {self.device}")
+            pcm_chunk = pcm_chunk.contiguous()
+            if tuple(pcm_chunk.shape) != (st["B"], st["chunk"]):
+                raise ValueError(f"expected a ({st['B']}, {st['chunk']}) chunk, got {tuple(pcm_chunk.shape)}")
+            fn = self.lib.uvad_window_wav_slots_step_i16 if st["dtype"] == torch.int16 else self.lib.uvad_window_wav_slots_step
+            return self._slots_step(st, pcm_chunk, start, end, fn)
+
+    def wav_window_slots_features(self, st):
+        """(SincNet output (B, W, c3), Tw int32 (B,)) of each slot's last step (uvad_window_wav_slots_features)."""
+        with torch.cuda.device(self.device):
+            feats = torch.empty((st["B"], st["window"], self._sn_c.c3), dtype=torch.float32, device=self.device)
+            tw = torch.empty(st["B"], dtype=torch.int32, device=self.device)
+            self._check(self.lib.uvad_window_wav_slots_features(self.ctx, st["state"].data_ptr(), st["B"], feats.data_ptr(), tw.data_ptr(),
+                                                                self._stream()))
+            return feats, tw
 
     def set_gemm_mode(self, mode: str):
         """"f32": exact f32 MFMA; "f16p": split-f16 on the f16 matrix cores (default: the weight-stationary kernel for the large
