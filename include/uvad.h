@@ -421,6 +421,66 @@ int uvad_window_wav_slots_step_i16(uvad_ctx *, const int16_t *d_pcm_chunk, const
                                    void *stream);
 int uvad_window_wav_slots_features(uvad_ctx *, const void *d_state, int B, float *d_feats, int32_t *d_tw, void *stream);
 
+/* ---- Ingest stage: audio as it arrives -> the [rows][samples] f32, 16 kHz layout every entry point above takes ------------------------
+ * Replaces: the audio loading of the reference's non-16 kHz recipes, multi_cut.to_mono(mono_downmix=False) and CutSet.resample(16000)
+ * (src/datasets/switchboard/utils.py:102-107, fisher_english/utils.py:106-108, callhome_english/utils.py:110-112, eval2000/utils.py:92-94,
+ * babel/utils.py:139, santa_barbara/utils.py:90; lhotse / torchaudio, third party), and the G.711 decode a telephone feed needs first.
+ * A stage in FRONT of the existing calls: its output is handed to uvad_forward*, uvad_window_*_step, uvad_*_slots_step unchanged.
+ *   Source: `encoding` -- UVAD_INGEST_F32, UVAD_INGEST_I16 (read as q / 32768, as the _i16 calls), UVAD_INGEST_ULAW / UVAD_INGEST_ALAW
+ *   (G.711, one byte per sample, expanded to the standard 16-bit value, then / 32768); `channels` C in 1 .. 8, interleaved frame by frame
+ *   as in a wav file: input [B][S_in][C]; `sample_rate`: 16000 / sample_rate reduced to up / down.
+ *   Channels: every channel becomes a row of its own, output row b * C + c (to_mono(mono_downmix=False)); there is no down-mix.
+ *   Resampler: a polyphase FIR whose taps the HOST uploads (uvad_ingest_set_taps: taps[up][K] row-major, K = 2 * width + down), as the
+ *   window and mel tables are; output o = j * up + p of a row is the f32 fma chain over k = 0 .. K - 1, in that order from +0, of
+ *   x[j * down + k - width] * taps[p][k], x read as zero outside the row.  The order is part of the contract: the dense, ragged and
+ *   stream forms give the same bits.  Output length: ceil(up * S_in / down) (uvad_ingest_out_len).  A table of more than 8 phases
+ *   (up) or more than 64 taps per phase (K) is UVAD_E_UNSUPPORTED (44.1 kHz: 160 x 475).  up / down = 1 / 1 takes no table and is a
+ *   pure decode / de-interleave (bit-exact).  The Python host computes the published Hann-windowed sinc design (width 6, rolloff 0.99).
+ *   uvad_ingest_configure drops a table uploaded for another ratio.  uvad_ingest_set_taps with the table the context already holds
+ *   (same up, down, width and values) does nothing; with another table it waits for the device to go idle first.  The table keeps its
+ *   device address, so a graph captured earlier stays valid only if the new table has the SAME width: K, width, the delay and the LDS
+ *   size are baked into a captured step, and the stream state's layout depends on the width.  After a uvad_ingest_set_taps with another
+ *   width every ingest stream must be reset on a state of the new uvad_ingest_state_bytes and every graph captured again.
+ * uvad_ingest: d_in [B][S_in][C] in the source encoding -> d_out [B * C][ceil(up * S_in / down)] f32.  Outputs leave as 16-byte
+ *   vector stores when d_out is 16-byte aligned and the output length is a multiple of 4; any other length is correct but stored
+ *   4 bytes at a time throughout (every row then starts at 4-byte alignment only): a caller who chooses S_in picks it so.
+ * uvad_ingest_lens: d_nsamp DEVICE int64 [B] input frames per row, clamped to [0, S_in]; frames at or past a row's count are read as
+ *   zero and NEVER from memory; row b * C + c equals uvad_ingest on d_in[b, :n_b] alone, and is +0 from ceil(up * n_b / down) on.
+ *   d_out_nsamp DEVICE int64 [B * C] receives ceil(up * n_b / down), repeated per channel: it is what uvad_forward_lens /
+ *   uvad_forward_wav_lens take as d_nsamp.
+ * Stream: B feeds x C channels in lockstep, chunk_in input frames per step (a multiple of down), d_out [B * C][chunk_in * up / down].
+ *   The stream cannot see the future: its output is the dense output DELAYED by D = ceil((width + down - 1) / down) * up samples (14
+ *   samples = 0.875 ms for 8 kHz; 0 for 1 / 1).  The first D samples of a session are +0 and the last D samples of a session are never
+ *   produced.  d_state: caller-owned device memory of uvad_ingest_state_bytes(ctx, B) bytes -- per output row the most recent
+ *   H = D * down / up + width decoded input samples and a counter -- cleared by uvad_ingest_stream_reset.  d_flags: DEVICE uint8 [B * C],
+ *   one per output row with the slot pools' meaning, or NULL: a row with UVAD_SLOT_START has its history and counter zeroed before the
+ *   chunk is consumed (a new session); UVAD_SLOT_END needs no action here.  Everything a step depends on is on the device: a step's
+ *   launch depends only on (B, C, chunk_in) and the buffers, so one captured graph replays every step.
+ * All compute entries are enqueue-only on `stream` and capturable.  Errors: before uvad_ingest_configure, or without a table where
+ * the ratio needs one: UVAD_E_STATE; chunk_in not a multiple of down, NULL pointers: UVAD_E_ARG; state_bytes below
+ * uvad_ingest_state_bytes: UVAD_E_WORKSPACE.  A context created without feature / model configuration serves these calls. */
+#define UVAD_INGEST_F32  0
+#define UVAD_INGEST_I16  1
+#define UVAD_INGEST_ULAW 2
+#define UVAD_INGEST_ALAW 3
+#define UVAD_INGEST_MAX_PHASES 8
+#define UVAD_INGEST_MAX_TAPS   64
+typedef struct {
+    int encoding;      /* UVAD_INGEST_* */
+    int channels;      /* 1 .. 8, interleaved */
+    int sample_rate;   /* of the source, Hz */
+} uvad_ingest_cfg;
+int uvad_ingest_configure(uvad_ctx *, const uvad_ingest_cfg *);
+int uvad_ingest_set_taps(uvad_ctx *, const float *taps /* host [up][2 * width + down] */, int up, int down, int width);
+int64_t uvad_ingest_out_len(const uvad_ctx *, int64_t S_in);   /* negative: not configured / bad argument */
+size_t uvad_ingest_state_bytes(const uvad_ctx *, int B);       /* 0: not configured, or no table where one is needed */
+int uvad_ingest(uvad_ctx *, const void *d_in, int B, int64_t S_in, float *d_out, void *stream);
+int uvad_ingest_lens(uvad_ctx *, const void *d_in, int B, int64_t S_in, const int64_t *d_nsamp, float *d_out, int64_t *d_out_nsamp,
+                     void *stream);
+int uvad_ingest_stream_reset(uvad_ctx *, void *d_state, size_t state_bytes, int B, void *stream);
+int uvad_ingest_stream_step(uvad_ctx *, const void *d_in, const uint8_t *d_flags, int B, int chunk_in, void *d_state, size_t state_bytes,
+                            float *d_out, void *stream);
+
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;
  *   1  (default) f32-accurate on the f16 matrix cores: weights scaled by a power of two and split on the host into THREE

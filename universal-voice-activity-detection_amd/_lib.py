@@ -31,6 +31,10 @@ class SincNetCfg(C.Structure):
                 ("c3", C.c_int), ("k3", C.c_int), ("leaky_slope", C.c_float), ("eps", C.c_float)]
 
 
+class IngestCfg(C.Structure):
+    _fields_ = [("encoding", C.c_int), ("channels", C.c_int), ("sample_rate", C.c_int)]
+
+
 class UvadError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{ERR_NAMES.get(code, code)}: {msg}")
@@ -104,6 +108,15 @@ SIGNATURES = {
     "uvad_window_wav_slots_step_i16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_window_wav_slots_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uvad_ingest_configure": (C.c_int, [C.c_void_p, C.POINTER(IngestCfg)]),
+    "uvad_ingest_set_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "uvad_ingest_out_len": (C.c_int64, [C.c_void_p, C.c_int64]),
+    "uvad_ingest_state_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "uvad_ingest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "uvad_ingest_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uvad_ingest_stream_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "uvad_ingest_stream_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.c_void_p]),
     "uvad_classify_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_forward_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -146,6 +159,20 @@ SIGNATURES = {
 _lib = None
 
 
+def bind(lib):
+    """Declare every prototype of SIGNATURES on `lib`.  The ABI number did not move when entries were appended (the ingest stage among
+    them), so a library built from an older tree passes the version check: a symbol it lacks is a loud error here, by name."""
+    for name, (res, args) in SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise RuntimeError(f"libuvad.so does not export {name}: it was built from an older source tree; rebuild the library "
+                               "(`make -C universal-voice-activity-detection_amd/csrc`)") from None
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
 def load():
     """dlopen libuvad.so and declare every prototype.  Raises (never falls back) if it is absent."""
     global _lib
@@ -156,15 +183,7 @@ def load():
             f"{LIB_PATH} is missing: the HIP extension has not been built. "
             "Run `python -c 'import __graft_entry__ as g; g.build()'` or "
             "`make -C universal-voice-activity-detection_amd/csrc`. There is no CPU fallback.")
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise RuntimeError(f"libuvad.so does not export {name}: it was built from an older source tree; rebuild the library "
-                               "(`make -C universal-voice-activity-detection_amd/csrc`)") from None
-        fn.restype = res
-        fn.argtypes = args
+    lib = bind(C.CDLL(LIB_PATH))
     got = lib.uvad_abi_version()
     if got != ABI_VERSION:
         raise RuntimeError(f"libuvad.so ABI {got} != binding ABI {ABI_VERSION}; rebuild the library")

@@ -64,7 +64,10 @@ def load_config() -> ConfigDict:
     # manifest-free input (BASELINE cfg 1: one 30 s 16 kHz utterance)
     cfg.input = ConfigDict()
     cfg.input.kind = "synthetic"      # "synthetic" | "wav"
-    cfg.input.paths = []              # wav files (16 kHz mono int16) when kind == "wav"
+    cfg.input.paths = []              # wav files when kind == "wav": 16 kHz 16-bit as they are; other rates, G.711 (A-law / mu-law) and
+                                      # multi-channel files through the ingest stage (decode, channels to rows, resampling to 16 kHz)
+    cfg.input.channels = "first"      # "first": channel 0 only (the reference's to_mono(mono_downmix=False)[0]); "all": every channel a
+                                      # recording of its own, "-ch<N>" appended to its id
     cfg.input.num_utterances = 1
     cfg.input.seconds = 30.0
     cfg.input.seed = 1000

@@ -148,6 +148,12 @@ struct uvad_ctx {
     hipEvent_t ev_fork = nullptr;
     std::vector<hipEvent_t> ev_chunk;
     std::map<std::tuple<int, int, int, int>, ChunkPlan> chunk_plans;   // (tiles, T, dirs, chunks) -> row-tile lists on the device
+    // ingest stage (uvad_ingest*, ingest.hip): the source description, the ratio 16000 / sample_rate reduced, and the uploaded taps
+    bool has_ingest = false, ig_taps = false;
+    uvad_ingest_cfg ig{};
+    int ig_up = 1, ig_down = 1, ig_width = 0;
+    std::vector<float> ig_taps_host;   // what d_ig_taps holds (an unchanged table is not uploaded again)
+    float *d_ig_taps = nullptr;   // [INGEST_MAX_PHASES * INGEST_MAX_TAPS], allocated by the first uvad_ingest_set_taps, lives with the context
 };
 
 namespace {
@@ -2424,6 +2430,174 @@ int uvad_window_wav_slots_features(uvad_ctx *c, const void *d_state, int B, floa
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemcpyAsync(d_feats, st + SL.off_feats, (size_t)B * g.W * c->sc.c3 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     HIPCHK(c, hipMemcpyAsync(d_tw, ctr.tw_last, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+// ---- ingest stage (ingest.hip) ---------------------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+struct IngestGeom { int up, down, width, K, Dj, H; };
+IngestGeom ingest_geom(const uvad_ctx *c) {
+    IngestGeom g{};
+    g.up = c->ig_up; g.down = c->ig_down; g.width = c->ig_width;
+    g.K = 2 * g.width + g.down;
+    g.Dj = (g.width + g.down - 1 + g.down - 1) / g.down;   // ceil((width + down - 1) / down) output groups of delay
+    g.H = g.Dj * g.down + g.width;
+    return g;
+}
+bool ingest_identity(const uvad_ctx *c) { return c->ig_up == 1 && c->ig_down == 1; }
+// configured, and a table where the ratio needs one
+int ingest_check(uvad_ctx *c, const char *who) {
+    if (!c->has_ingest) return fail(c, UVAD_E_STATE, std::string(who) + ": call uvad_ingest_configure first");
+    if (!ingest_identity(c) && !c->ig_taps)
+        return fail(c, UVAD_E_STATE, std::string(who) + ": no resampler taps for " + std::to_string(c->ig_up) + " / " + std::to_string(c->ig_down) +
+                                         " (uvad_ingest_set_taps)");
+    return UVAD_OK;
+}
+struct IngestState { size_t off_seen = 0, total = 0; };
+IngestState ingest_state(const uvad_ctx *c, int B) {
+    IngestState s;
+    const size_t rows = (size_t)B * c->ig.channels;
+    s.off_seen = align_up(rows * (size_t)ingest_geom(c).H * sizeof(float));
+    s.total = s.off_seen + align_up(rows * sizeof(long long));
+    return s;
+}
+IngestArgs ingest_args(const uvad_ctx *c, const void *d_in, int B, int64_t S_in, float *d_out) {
+    const IngestGeom g = ingest_geom(c);
+    IngestArgs a{};
+    a.in = d_in; a.enc = c->ig.encoding; a.C = c->ig.channels; a.S_in = S_in;
+    a.taps = ingest_identity(c) ? nullptr : c->d_ig_taps;
+    a.up = g.up; a.down = g.down; a.width = g.width; a.K = g.K;
+    a.out = d_out; a.S_out = (S_in * g.up + g.down - 1) / g.down;
+    a.B = B;
+    return a;
+}
+}  // namespace
+}  // extern "C++"
+
+int uvad_ingest_configure(uvad_ctx *c, const uvad_ingest_cfg *q) {
+    if (!c) return UVAD_E_ARG;
+    if (!q) return fail(c, UVAD_E_ARG, "uvad_ingest_configure: bad argument");
+    if (q->encoding < UVAD_INGEST_F32 || q->encoding > UVAD_INGEST_ALAW)
+        return fail(c, UVAD_E_ARG, "uvad_ingest_configure: encoding must be UVAD_INGEST_F32, _I16, _ULAW or _ALAW");
+    if (q->channels < 1) return fail(c, UVAD_E_ARG, "uvad_ingest_configure: channels must be >= 1");
+    if (q->channels > INGEST_MAX_CHANNELS)
+        return fail(c, UVAD_E_UNSUPPORTED, "uvad_ingest_configure: at most " + std::to_string(INGEST_MAX_CHANNELS) + " interleaved channels");
+    if (q->sample_rate < 1 || q->sample_rate > 16000 * 4096) return fail(c, UVAD_E_ARG, "uvad_ingest_configure: bad sample_rate");
+    int a = 16000, b = q->sample_rate;
+    while (b) { const int t = a % b; a = b; b = t; }
+    const int up = 16000 / a, down = q->sample_rate / a;
+    if (!c->has_ingest || up != c->ig_up || down != c->ig_down) {   // a table for another ratio is dropped
+        c->ig_taps = false;
+        c->ig_width = 0;
+    }
+    c->ig = *q; c->ig_up = up; c->ig_down = down;
+    c->has_ingest = true;
+    return UVAD_OK;
+}
+
+int uvad_ingest_set_taps(uvad_ctx *c, const float *taps, int up, int down, int width) {
+    if (!c) return UVAD_E_ARG;
+    if (!c->has_ingest) return fail(c, UVAD_E_STATE, "uvad_ingest_set_taps: call uvad_ingest_configure first");
+    if (!taps || up < 1 || down < 1 || width < 0) return fail(c, UVAD_E_ARG, "uvad_ingest_set_taps: bad argument");
+    if (up != c->ig_up || down != c->ig_down)
+        return fail(c, UVAD_E_ARG, "uvad_ingest_set_taps: the table is for " + std::to_string(up) + " / " + std::to_string(down) +
+                                       ", the configured rate needs " + std::to_string(c->ig_up) + " / " + std::to_string(c->ig_down));
+    const long long K = 2LL * width + down;
+    if (up > UVAD_INGEST_MAX_PHASES || K > UVAD_INGEST_MAX_TAPS)
+        return fail(c, UVAD_E_UNSUPPORTED, "uvad_ingest_set_taps: a table of " + std::to_string(up) + " phases x " + std::to_string(K) +
+                                               " taps exceeds the limit of " + std::to_string(UVAD_INGEST_MAX_PHASES) + " phases x " +
+                                               std::to_string(UVAD_INGEST_MAX_TAPS) + " taps per phase");
+    if (up == 1 && down == 1) return fail(c, UVAD_E_ARG, "uvad_ingest_set_taps: 1 / 1 takes no table (a pure decode / de-interleave)");
+    for (long long i = 0; i < up * K; ++i)
+        if (!std::isfinite(taps[i])) return fail(c, UVAD_E_ARG, "uvad_ingest_set_taps: taps must be finite");
+    // the table the device already holds: nothing to upload, nothing to wait for
+    if (c->ig_taps && c->ig_width == width && c->ig_taps_host.size() == (size_t)(up * K) &&
+        std::memcmp(c->ig_taps_host.data(), taps, (size_t)(up * K) * sizeof(float)) == 0)
+        return UVAD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_ig_taps) {
+        void *p = nullptr;
+        HIPCHK(c, hipMalloc(&p, (size_t)UVAD_INGEST_MAX_PHASES * UVAD_INGEST_MAX_TAPS * sizeof(float)));
+        c->allocs.push_back(p);
+        c->d_ig_taps = reinterpret_cast<float *>(p);
+    } else {
+        HIPCHK(c, hipDeviceSynchronize());   // kernels of earlier calls may still be reading the table
+    }
+    c->ig_taps = false;
+    HIPCHK(c, hipMemcpy(c->d_ig_taps, taps, (size_t)(up * K) * sizeof(float), hipMemcpyHostToDevice));
+    c->ig_taps_host.assign(taps, taps + up * K);
+    c->ig_width = width;
+    c->ig_taps = true;
+    return UVAD_OK;
+}
+
+int64_t uvad_ingest_out_len(const uvad_ctx *c, int64_t S_in) {
+    if (!c || S_in < 0) return UVAD_E_ARG;
+    if (!c->has_ingest) return UVAD_E_STATE;
+    return (S_in * c->ig_up + c->ig_down - 1) / c->ig_down;
+}
+
+size_t uvad_ingest_state_bytes(const uvad_ctx *c, int B) {
+    if (!c || !c->has_ingest || B <= 0 || (!ingest_identity(c) && !c->ig_taps)) return 0;
+    return ingest_state(c, B).total;
+}
+
+int uvad_ingest(uvad_ctx *c, const void *d_in, int B, int64_t S_in, float *d_out, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (int r = ingest_check(c, "uvad_ingest")) return r;
+    if (!d_in || B <= 0 || S_in < 0 || (S_in > 0 && !d_out)) return fail(c, UVAD_E_ARG, "uvad_ingest: bad argument");
+    if (S_in == 0) return UVAD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_ingest(ingest_args(c, d_in, B, S_in, d_out), (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_ingest_lens(uvad_ctx *c, const void *d_in, int B, int64_t S_in, const int64_t *d_nsamp, float *d_out, int64_t *d_out_nsamp,
+                     void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (int r = ingest_check(c, "uvad_ingest_lens")) return r;
+    if (!d_in || !d_nsamp || !d_out_nsamp || B <= 0 || S_in < 0 || (S_in > 0 && !d_out)) return fail(c, UVAD_E_ARG, "uvad_ingest_lens: bad argument");
+    IngestArgs a = ingest_args(c, d_in, B, S_in, d_out);
+    a.nsamp = reinterpret_cast<const long long *>(d_nsamp);
+    a.out_nsamp = reinterpret_cast<long long *>(d_out_nsamp);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_ingest(a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_ingest_stream_reset(uvad_ctx *c, void *d_state, size_t state_bytes, int B, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (int r = ingest_check(c, "uvad_ingest_stream_reset")) return r;
+    if (!d_state || B <= 0) return fail(c, UVAD_E_ARG, "uvad_ingest_stream_reset: bad argument");
+    const IngestState st = ingest_state(c, B);
+    if (state_bytes < st.total)
+        return fail(c, UVAD_E_WORKSPACE, "uvad_ingest_stream_reset: state too small: need " + std::to_string(st.total) + " bytes");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemsetAsync(d_state, 0, st.total, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_ingest_stream_step(uvad_ctx *c, const void *d_in, const uint8_t *d_flags, int B, int chunk_in, void *d_state, size_t state_bytes,
+                            float *d_out, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!c->has_ingest) return fail(c, UVAD_E_STATE, "uvad_ingest_stream_step: call uvad_ingest_configure first");
+    if (!d_in || !d_state || !d_out || B <= 0 || chunk_in <= 0) return fail(c, UVAD_E_ARG, "uvad_ingest_stream_step: bad argument");
+    if (chunk_in % c->ig_down)
+        return fail(c, UVAD_E_ARG, "uvad_ingest_stream_step: chunk_in must be a multiple of down = " + std::to_string(c->ig_down));
+    if (int r = ingest_check(c, "uvad_ingest_stream_step")) return r;
+    const IngestGeom g = ingest_geom(c);
+    const IngestState st = ingest_state(c, B);
+    if (state_bytes < st.total)
+        return fail(c, UVAD_E_WORKSPACE, "uvad_ingest_stream_step: state too small: need " + std::to_string(st.total) + " bytes");
+    IngestArgs a = ingest_args(c, d_in, B, chunk_in, d_out);
+    char *base = reinterpret_cast<char *>(d_state);
+    a.hist = reinterpret_cast<float *>(base);
+    a.seen = reinterpret_cast<long long *>(base + st.off_seen);
+    a.flags = d_flags; a.H = g.H; a.Dj = g.Dj;
+    a.S_out = (long long)chunk_in / g.down * g.up;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_ingest(a, (hipStream_t)stream));
     return UVAD_OK;
 }
 

@@ -444,4 +444,21 @@ hipError_t launch_norm_finalize_f16p(int stage, const float *partials, int B, in
 hipError_t launch_sinc_out_f16p(const float *P, const float *scale, const float *shift, int B, int C, int CST, int L, float slope, float *feats, int ldf,
                                 hipStream_t s, const int *row_T = nullptr);
 
+// ---- ingest.hip: the ingest stage (uvad_ingest*, include/uvad.h): decode, de-interleave and polyphase resampling to 16 kHz ----
+// Output sample o = j up + p of a row is the f32 fma chain, k ascending from +0, over x[j down + k - shift] taps[p][k], k < K = 2 width +
+// down; x is the decoded channel, zero outside [0, n), and for a stream step the row's history at negative indices.  shift = width for
+// the dense and ragged forms, Dj down + width = H for a stream step (the output delayed by Dj up samples).
+constexpr int INGEST_MAX_PHASES = 8, INGEST_MAX_TAPS = 64, INGEST_MAX_CHANNELS = 8;
+struct IngestArgs {
+    const void *in; int enc, C; long long S_in;      // in[(b S_in + f) C + c] in the source encoding (UVAD_INGEST_*), S_in frames per row
+    const long long *nsamp;                          // ragged: device int64 [B] frames per row, clamped to [0, S_in]; null: S_in
+    const float *taps; int up, down, width, K;       // taps[up][K] on the device; null: the 1/1 pass (up = down = K = 1, width = 0)
+    float *out; long long S_out;                     // out[(b C + c) S_out + o]
+    long long *out_nsamp;                            // ragged: [B C] = ceil(up n_b / down), repeated per channel; else null
+    float *hist; long long *seen; const uint8_t *flags; int H, Dj;   // stream: hist [B C][H] decoded samples, seen [B C] output groups
+                                                                     // since the session's start (saturating at Dj), flags [B C] or null
+    int B;
+};
+hipError_t launch_ingest(const IngestArgs &a, hipStream_t s);
+
 }  // namespace uvad

@@ -9,6 +9,7 @@ import torch
 
 from . import _lib
 from .features import FbankConfig, make_mel_matrix, make_window
+from .ingest import ENCODINGS, g711_table, ingest_plan, resample_ratio, resample_taps, stream_delay  # noqa: F401  (re-exported)
 
 
 def _model_cfg(encoding_dim: int, lstm: dict, linear: dict, leaky_slope: float = 0.01) -> _lib.ModelCfg:
@@ -791,6 +792,134 @@ class VadRuntime:
             self._check(self.lib.uvad_window_wav_slots_features(self.ctx, st["state"].data_ptr(), st["B"], feats.data_ptr(), tw.data_ptr(),
                                                                 self._stream()))
             return feats, tw
+
+    # ------------------------------------------------------------------ ingest stage: audio as it arrives -> (rows, samples) f32 at 16 kHz
+    _INGEST_DTYPES = {"f32": torch.float32, "int16": torch.int16, "ulaw": torch.uint8, "alaw": torch.uint8}
+
+    def ingest_configure(self, encoding: str, channels: int = 1, sample_rate: int = 16000, taps=None):
+        """Describe the source of ingest() / ingest_step() (uvad_ingest_configure): encoding "f32", "int16" (q / 32768), "ulaw" or "alaw"
+        (G.711 bytes); `channels` interleaved channels, each of which becomes an output row of its own (row b * channels + c, no
+        down-mix); sample_rate in Hz.  taps: a polyphase table (up, 2 * width + down) for 16000 / sample_rate = up / down; default
+        resample_taps(sample_rate), the published Hann-windowed sinc design.  16 kHz takes no table.  Returns ingest_plan's geometry."""
+        if encoding not in ENCODINGS:
+            raise ValueError(f"encoding must be one of {sorted(ENCODINGS)}, got {encoding!r}")
+        up, down = resample_ratio(sample_rate)
+        width = 0
+        if (up, down) != (1, 1):
+            if taps is None:
+                taps, up, down, width = resample_taps(sample_rate)
+            else:
+                taps = np.ascontiguousarray(taps, np.float32)
+                if taps.ndim != 2 or taps.shape[0] != up or taps.shape[1] < down or (taps.shape[1] - down) % 2:
+                    raise ValueError(f"taps must have shape ({up}, 2 * width + {down}), got {taps.shape}")
+                width = (taps.shape[1] - down) // 2
+        cfg = _lib.IngestCfg(ENCODINGS[encoding], int(channels), int(sample_rate))
+        self._check(self.lib.uvad_ingest_configure(self.ctx, C.byref(cfg)))
+        self._ingest = None
+        if (up, down) != (1, 1):
+            self._check(self.lib.uvad_ingest_set_taps(self.ctx, taps.ctypes.data, up, down, width))
+        D, H = stream_delay(up, down, width)
+        self._ingest = {"encoding": encoding, "dtype": self._INGEST_DTYPES[encoding], "channels": int(channels), "sample_rate": int(sample_rate),
+                        "up": up, "down": down, "width": width, "delay": D, "history": H}
+        return dict(self._ingest)
+
+    def _ingest_input(self, x, frames=None, contiguous=True):
+        ig = getattr(self, "_ingest", None)
+        if ig is None:
+            raise RuntimeError("call ingest_configure first")
+        if not torch.is_tensor(x) or x.device != self.device or x.dtype != ig["dtype"]:
+            raise RuntimeError(f"the {ig['encoding']} source must be a {ig['dtype']} tensor on {self.device}")
+        Cn = ig["channels"]
+        if x.dim() == 2 and Cn == 1:
+            x = x.unsqueeze(-1)
+        if x.dim() != 3 or x.shape[2] != Cn or (frames is not None and x.shape[1] != frames):
+            raise ValueError(f"expected (rows, {'frames' if frames is None else frames}, {Cn}) interleaved input, got {tuple(x.shape)}")
+        return ig, (x.contiguous() if contiguous else x)
+
+    def ingest(self, x: "torch.Tensor", lengths=None, out=None):
+        """x (B, S_in, channels) -- (B, S_in) for one channel -- in the configured encoding on the GPU -> (B * channels, ceil(up * S_in /
+        down)) f32 at 16 kHz, row b * channels + c (uvad_ingest).  lengths: input frames per row (B,): row b is ingested as x[b, :lengths[b]]
+        alone, what lies past it is never read and the output past its count is +0; returns (out, counts int64 (B * channels,)) with the
+        per-row output counts on the device, as forward(..., lengths=) / forward_wav(..., lengths=) take them (uvad_ingest_lens).
+        out: a contiguous f32 tensor of the output's shape on this device to write into (a caller that ingests the same shape again and
+        again keeps one), else a new one."""
+        with torch.cuda.device(self.device):
+            ig, x = self._ingest_input(x)
+            B, S_in, Cn = x.shape
+            S_out = -(-(ig["up"] * S_in) // ig["down"])
+            if out is None:
+                out = torch.empty((B * Cn, S_out), dtype=torch.float32, device=self.device)
+            elif (not torch.is_tensor(out) or out.device != self.device or out.dtype != torch.float32 or tuple(out.shape) != (B * Cn, S_out)
+                  or not out.is_contiguous()):
+                raise ValueError(f"out must be a contiguous float32 tensor of shape ({B * Cn}, {S_out}) on {self.device}")
+            if lengths is None:
+                if B and S_in:
+                    self._check(self.lib.uvad_ingest(self.ctx, x.data_ptr(), B, S_in, out.data_ptr(), self._stream()))
+                return out
+            n = self._dev_lens(lengths, B, S_in, torch.int64, "lengths (input frames)")
+            counts = torch.empty(B * Cn, dtype=torch.int64, device=self.device)
+            src = x if x.numel() else torch.zeros(1, dtype=x.dtype, device=self.device)   # (a non-null pointer that is never read)
+            self._check(self.lib.uvad_ingest_lens(self.ctx, src.data_ptr(), B, S_in, n.data_ptr(), out.data_ptr() if S_out else None,
+                                                  counts.data_ptr(), self._stream()))
+            return out, counts
+
+    def ingest_open(self, B: int, chunk_in: int, graphs: bool = False):
+        """Allocate and reset an ingest stream (uvad_ingest_stream_reset): B feeds x channels in lockstep, chunk_in input frames per step
+        (a multiple of `down`).  Its output is the dense ingest delayed by the plan's `delay` samples: the first `delay` samples of a
+        session are +0, the last `delay` are never produced.  graphs: capture the first step into a hipGraph and replay it for every
+        later one (a step depends on nothing on the host)."""
+        ig = getattr(self, "_ingest", None)
+        if ig is None:
+            raise RuntimeError("call ingest_configure first")
+        if chunk_in <= 0 or chunk_in % ig["down"]:
+            raise ValueError(f"chunk_in must be a positive multiple of down = {ig['down']}, got {chunk_in}")
+        with torch.cuda.device(self.device):
+            nbytes = int(self.lib.uvad_ingest_state_bytes(self.ctx, B))
+            if nbytes == 0:
+                raise RuntimeError("ingest streams need ingest_configure (and a table where the rate needs one)")
+            state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._check(self.lib.uvad_ingest_stream_reset(self.ctx, state.data_ptr(), nbytes, B, self._stream()))
+            rows = B * ig["channels"]
+            return {"state": state, "B": B, "chunk_in": chunk_in, "rows": rows, "delay": ig["delay"],
+                    "out": torch.empty((rows, chunk_in // ig["down"] * ig["up"]), dtype=torch.float32, device=self.device),
+                    "in": torch.empty((B, chunk_in, ig["channels"]), dtype=ig["dtype"], device=self.device),
+                    "flags": torch.zeros(rows, dtype=torch.uint8, device=self.device), "flags_set": False,
+                    "graphs": 0 if graphs else None, "graph": None}
+
+    def ingest_step(self, st, chunk: "torch.Tensor", start=None) -> "torch.Tensor":
+        """chunk (B, chunk_in, channels) in the configured encoding on the GPU -> (B * channels, chunk_in * up / down) f32, a buffer the
+        next step overwrites; hand it to any *_stream_step / *_slots_step.  start: output rows (a bool mask of B * channels entries or
+        an index list, as the slot pools' `start`) whose session begins with this chunk: their history is zeroed first."""
+        with torch.cuda.device(self.device):
+            _, chunk = self._ingest_input(chunk, st["chunk_in"], contiguous=st["graphs"] is None)   # (the graph's fixed buffer takes any strides)
+            if chunk.shape[0] != st["B"]:
+                raise ValueError(f"expected {st['B']} rows, got {chunk.shape[0]}")
+            out = st["out"]
+
+            def enqueue(src, flags):
+                return self.lib.uvad_ingest_stream_step(self.ctx, src.data_ptr(), flags.data_ptr() if flags is not None else None, st["B"],
+                                                        st["chunk_in"], st["state"].data_ptr(), st["state"].numel(), out.data_ptr(),
+                                                        self._stream())
+
+            if st["graphs"] is None:
+                self._check(enqueue(chunk, self._slot_flags(st["rows"], start, None)))
+                return out
+            st["in"].copy_(chunk)
+            if start is not None:
+                self._slot_flags(st["rows"], start, None, st["flags"])
+                st["flags_set"] = True
+            elif st["flags_set"]:                            # (a step without starts costs no flag kernels once the buffer is clear)
+                st["flags"].zero_()
+                st["flags_set"] = False
+            if st["graph"] is None:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):                    # capture: recorded, not run
+                    r = enqueue(st["in"], st["flags"])
+                self._check(r)
+                st["graph"] = g
+                st["graphs"] += 1
+            st["graph"].replay()
+            return out
 
     def set_gemm_mode(self, mode: str):
         """"f32": exact f32 MFMA; "f16p": split-f16 on the f16 matrix cores (default: the weight-stationary kernel for the large

@@ -22,6 +22,7 @@ Every batch goes through the fused hot path: PCM (int16 straight from the wav fi
 import json
 import math
 import os
+import struct
 import wave
 from typing import List
 
@@ -46,6 +47,68 @@ def read_wav_int16(path: str, sample_rate: int = 16000) -> np.ndarray:
         if w.getnchannels() > 1:
             pcm = pcm.reshape(-1, w.getnchannels())[:, 0]
     return np.ascontiguousarray(pcm)
+
+
+def read_audio(path: str):
+    """A small RIFF/WAVE reader for what telephone audio comes as: format tags 1 (16-bit linear PCM), 6 (G.711 A-law) and 7 (G.711
+    mu-law), any channel count and sample rate (Python's ``wave`` refuses tags 6 and 7).  -> (raw, (encoding, channels, rate)): raw is
+    the interleaved samples as stored, shape (frames, channels), int16 for "int16" and uint8 for "alaw" / "ulaw" -- undecoded: the
+    ingest stage (VadRuntime.ingest) decodes, de-interleaves and resamples on the GPU."""
+    with open(path, "rb") as f:
+        blob = f.read()
+    if len(blob) < 12 or blob[:4] != b"RIFF" or blob[8:12] != b"WAVE":
+        raise ValueError(f"{path}: not a RIFF/WAVE file")
+    fmt = data = None
+    pos = 12
+    while pos + 8 <= len(blob):
+        cid, size = blob[pos:pos + 4], struct.unpack("<I", blob[pos + 4:pos + 8])[0]
+        body = blob[pos + 8:pos + 8 + size]
+        if cid == b"fmt ":
+            fmt = body
+        elif cid == b"data":
+            data = body
+            break
+        pos += 8 + size + (size & 1)      # chunks are word aligned
+    if fmt is None or data is None or len(fmt) < 16:
+        raise ValueError(f"{path}: no fmt / data chunk")
+    tag, channels, rate, _, _, bits = struct.unpack("<HHIIHH", fmt[:16])
+    if tag == 0xFFFE and len(fmt) >= 26:  # WAVE_FORMAT_EXTENSIBLE: the tag is the head of the sub-format GUID
+        tag = struct.unpack("<H", fmt[24:26])[0]
+    if channels < 1 or rate < 1:
+        raise ValueError(f"{path}: bad channel count / sample rate")
+    if tag == 1 and bits == 16:
+        encoding, dtype = "int16", "<i2"
+    elif tag in (6, 7) and bits == 8:
+        encoding, dtype = ("alaw" if tag == 6 else "ulaw"), np.uint8
+    else:
+        raise ValueError(f"{path}: format tag {tag} with {bits} bits per sample is not supported (16-bit PCM, A-law, mu-law)")
+    width = channels * np.dtype(dtype).itemsize
+    raw = np.frombuffer(data[:len(data) // width * width], dtype=dtype).reshape(-1, channels)
+    return raw.copy(), (encoding, channels, rate)
+
+
+def _wav_recordings(path: str, channels: str, rt, sample_rate: int = 16000):
+    """The recordings of one wav file.  A file read_wav_int16 accepts (16 kHz, 16-bit) whose first channel is all that is asked for
+    takes that path: int16 samples, converted on the GPU by the _i16 entry points.  Anything else -- another rate, G.711, every
+    channel of a multi-channel file -- goes through read_audio and the ingest stage to f32 rows at 16 kHz."""
+    rid = os.path.basename(path)
+    try:
+        with wave.open(path, "rb") as w:
+            plain = w.getframerate() == sample_rate and w.getsampwidth() == 2 and (channels == "first" or w.getnchannels() == 1)
+    except (wave.Error, EOFError):
+        plain = False
+    if plain:
+        return [{"id": rid + ("-ch0" if channels == "all" else ""), "pcm": read_wav_int16(path, sample_rate)}]
+    raw, (encoding, nch, rate) = read_audio(path)
+    ig = getattr(rt, "_ingest", None) or {}
+    if (ig.get("encoding"), ig.get("channels"), ig.get("sample_rate")) != (encoding, nch, rate):   # files of one kind configure once
+        rt.ingest_configure(encoding, nch, rate)
+    # (channels, samples at 16 kHz) f32, back on the host: the recordings are cut into windows and batched there, like the int16 ones,
+    # and each batch is uploaded again -- one extra round trip per file, kept so that both kinds of recording share one batching path
+    rows = rt.ingest(torch.from_numpy(raw[None]).to(rt.device)).cpu().numpy()
+    if channels == "first":
+        return [{"id": rid, "pcm": rows[0]}]
+    return [{"id": f"{rid}-ch{c}", "pcm": rows[c]} for c in range(nch)]
 
 
 def _resolve_device(name: str) -> torch.device:
@@ -128,8 +191,11 @@ def predict_vad(**kwargs):
     src = kwargs["input"]
     recs: List[dict] = []
     if src["kind"] == "wav":
+        channels = src.get("channels", "first")
+        if channels not in ("first", "all"):
+            raise ValueError(f"input channels must be 'first' or 'all', got {channels!r}")
         for p in src["paths"]:
-            recs.append({"id": os.path.basename(p), "pcm": read_wav_int16(p)})             # int16: converted on the GPU
+            recs.extend(_wav_recordings(p, channels, net.runtime(device), sr))             # int16: converted on the GPU
     elif src["kind"] == "synthetic":
         S = int(round(src["seconds"] * sr))
         pcm = synth_pcm(src["num_utterances"], S, seed=src["seed"])
@@ -175,12 +241,17 @@ def predict_vad(**kwargs):
     if len(batches) > 1:   # log-mel: kept tails (n < W) take the unfused branch below; SincNet: every batch, tails padded first
         pipe = open_pipeline(net, device, min(3, len(batches)))
 
-    def stack(group):
+    def piece_rows(group):   # int16 rows beside ingested f32 ones are read as q / 32768, the value the _i16 entry points give them
         rows = [recs[pieces[j][0]]["pcm"][pieces[j][1]:pieces[j][1] + pieces[j][2]] for j in group]
-        return torch.from_numpy(np.stack(rows)).to(device)
+        if len({r.dtype for r in rows}) > 1:
+            rows = [r.astype(np.float32) / np.float32(32768.0) if r.dtype == np.int16 else r for r in rows]
+        return rows
+
+    def stack(group):
+        return torch.from_numpy(np.stack(piece_rows(group))).to(device)
 
     def stack_ragged(group):   # rows zero-padded to the longest (the padding is never read)
-        rows = [recs[pieces[j][0]]["pcm"][pieces[j][1]:pieces[j][1] + pieces[j][2]] for j in group]
+        rows = piece_rows(group)
         x = np.zeros((len(rows), max(len(r) for r in rows)), dtype=rows[0].dtype)
         for r, row in enumerate(rows):
             x[r, :len(row)] = row
