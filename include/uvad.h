@@ -137,7 +137,9 @@ int uvad_forward_i16(uvad_ctx *, const int16_t *d_pcm, int B, int64_t S, float *
  * feed-forward activation [B][T][lin_hidden] from the most recent uvad_classify on this
  * workspace (async on stream).  Either pointer may be NULL.  Where the fused head ran (two 128-unit feed-forward layers, large
  * launch) the feed-forward tap is recomputed from the LSTM output with the per-layer kernels -- the same bits in GEMM modes 1 / 2;
- * in mode 3 (three products) no kernel can reproduce the fused head's activation and d_lin_out != NULL returns UVAD_E_UNSUPPORTED. */
+ * in mode 3 (three products) no kernel can reproduce the fused head's activation and d_lin_out != NULL returns UVAD_E_UNSUPPORTED.
+ * After a *_lens call the taps of row b are defined at frames t < len_b only: the rows past a length are padding (the forward direction
+ * runs on over the zeroed features up to its workgroup's longest row, rows past that are not written); logits and probabilities there are +0. */
 int uvad_get_taps(uvad_ctx *, int B, int T, float *d_lstm_out, float *d_lin_out,
                   const void *d_workspace, void *stream);
 
