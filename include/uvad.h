@@ -423,6 +423,61 @@ int uvad_window_wav_slots_step_i16(uvad_ctx *, const int16_t *d_pcm_chunk, const
                                    void *stream);
 int uvad_window_wav_slots_features(uvad_ctx *, const void *d_state, int B, float *d_feats, int32_t *d_tw, void *stream);
 
+/* ---- Sliding-window inference over whole recordings, aggregated on the device --------------------------------------------------------
+ * The offline counterpart of the window streams: every recording is covered by overlapping windows of the trained length, each run from
+ * zero state, and a frame's score is the weighted mean over all windows that cover it.  Replaces the reference's disjoint 5 s cuts
+ * (cut_into_windows(duration=5).filter(duration > 3), src/datasets/ami/utils.py:107, rows laid end to end, predict.py:451-458) with two
+ * documented differences: features are slices of the recording's CONTINUOUS feature stream (one uvad_fbank_lens pass per recording,
+ * right-edge reflection at S_r; the reference frames every cut anew), and no tail is dropped.
+ *   uvad_sliding_configure: window W and hop Hf in frames, 1 <= Hf <= W, and a HOST weight table w[W] (NULL: all ones), uploaded here
+ *     once; every weight must be finite and > 0 (so the denominator below is never zero where a window covers): else UVAD_E_ARG.
+ *     Configuring again with a table of other values waits for the device to go idle first.
+ *   Windows of a recording of T_r frames: n_r = uvad_sliding_count(T_r, W, Hf) = 0 if T_r == 0, 1 if T_r <= W, else
+ *     ceil((T_r - W) / Hf) + 1.  Window j starts at frame j Hf and holds len_j = min(W, T_r - j Hf) frames; it runs AT ITS OWN LENGTH with
+ *     the semantics of uvad_classify_lens (backward direction from len_j - 1) and is never padded.  Every frame t < T_r is covered and the
+ *     last window holds more than W - Hf frames whenever T_r > W.
+ *   Aggregate: out[r][t] = (sum_j w[t - j Hf] p_j[t - j Hf]) / (sum_j w[t - j Hf]) over the windows j of r with 0 <= t - j Hf < len_j, in
+ *     ascending j, in f32 with every product, sum and the quotient rounded once; probabilities (after the sigmoid), not logits;
+ *     out[r][t] = +0 for t >= T_r and for any frame no planned window covers.  Columns [T, ld_out) are not written.
+ *   Window list: the host owns the launch count, so it passes d_first, DEVICE int32 [R + 1], the exclusive prefix sums of n_r, and
+ *     N = first[R]: global window i in [first[r], first[r + 1]) is window j = i - first[r] of r.  Lengths stay on the device (d_lens int32
+ *     frames / d_nsamp int64 samples, clamped as in the lens calls) and len_j is derived there as clamp(T_r - j Hf, 0, W): a plan that
+ *     disagrees with the device lengths never causes an out-of-row read, only empty windows or uncovered (zero) frames.  The N windows
+ *     are classified in groups of at most `group` per classifier launch, so the workspace is bounded by the group and not by N, each
+ *     group writing its rows of an [N][W] buffer; one aggregate launch follows the last group: the result does not depend on `group`
+ *     (bit for bit in GEMM modes 0 and 2 with a pinned recurrent tile).  d_win_probs (debug tap, or NULL): DEVICE f32 [N][W], every
+ *     window's probabilities left-aligned, +0 past len_j.  d_frames (or NULL): DEVICE int32 [R] receives T_r.
+ *   uvad_sliding_classify: caller features d_feats [R][T][F] with d_lens; rows past a length are never read.  uvad_sliding_forward
+ *     [_i16]: PCM [R][S] with d_nsamp; T = uvad_num_frames(S), T_r = uvad_num_frames(S_r).  uvad_sliding_forward_wav[_i16]: the
+ *     waveform model on samples: window j of r is samples [J Hf j, J Hf j + R + J (W - 1)) clipped to S_r, run through SincNet in its
+ *     lens form with every norm over the window's own samples; its frame i is the recording's frame j Hf + i; T_r =
+ *     uvad_sincnet_num_frames(S_r).  A geometry without a single frame step J: UVAD_E_UNSUPPORTED.
+ *   uvad_sliding_workspace_bytes(ctx, R, T, N, group) serves uvad_sliding_classify at that T and uvad_sliding_forward[_i16] at
+ *     T = uvad_num_frames(S); uvad_sliding_wav_workspace_bytes(ctx, R, S, N, group) the waveform calls.  0: not configured / bad argument.
+ *   Enqueue only: the calls never allocate or synchronise; a graph captured around one replays with other device lengths <= S under the
+ *   same plan.  Refusals: before uvad_sliding_configure (or without model / tables / weights): UVAD_E_STATE; group < 1, N < 0, NULL
+ *   d_first or lengths, ld_out < T: UVAD_E_ARG; a workspace too small: UVAD_E_WORKSPACE, the needed size in the message.  Time chunks
+ *   are off in every call (uvad_get_time_chunks() is 1 afterwards). */
+int uvad_sliding_configure(uvad_ctx *, int window, int hop, const float *h_weights /* host [window] or NULL */);
+int64_t uvad_sliding_count(int64_t frames, int window, int hop);   /* pure; negative: bad argument */
+size_t uvad_sliding_workspace_bytes(const uvad_ctx *, int R, int64_t T, int64_t N, int group);
+size_t uvad_sliding_wav_workspace_bytes(const uvad_ctx *, int R, int64_t S, int64_t N, int group);
+int uvad_sliding_classify(uvad_ctx *, const float *d_feats, int R, int T, const int32_t *d_lens, const int32_t *d_first, int64_t N, int group,
+                          float *d_probs, int ld_out, int32_t *d_frames, float *d_win_probs, void *d_workspace, size_t ws_bytes,
+                          void *stream);
+int uvad_sliding_forward(uvad_ctx *, const float *d_pcm, int R, int64_t S, const int64_t *d_nsamp, const int32_t *d_first, int64_t N,
+                         int group, float *d_probs, int ld_out, int32_t *d_frames, float *d_win_probs, void *d_workspace, size_t ws_bytes,
+                         void *stream);
+int uvad_sliding_forward_i16(uvad_ctx *, const int16_t *d_pcm, int R, int64_t S, const int64_t *d_nsamp, const int32_t *d_first, int64_t N,
+                             int group, float *d_probs, int ld_out, int32_t *d_frames, float *d_win_probs, void *d_workspace,
+                             size_t ws_bytes, void *stream);
+int uvad_sliding_forward_wav(uvad_ctx *, const float *d_wav, int R, int64_t S, const int64_t *d_nsamp, const int32_t *d_first, int64_t N,
+                             int group, float *d_probs, int ld_out, int32_t *d_frames, float *d_win_probs, void *d_workspace,
+                             size_t ws_bytes, void *stream);
+int uvad_sliding_forward_wav_i16(uvad_ctx *, const int16_t *d_wav, int R, int64_t S, const int64_t *d_nsamp, const int32_t *d_first,
+                                 int64_t N, int group, float *d_probs, int ld_out, int32_t *d_frames, float *d_win_probs,
+                                 void *d_workspace, size_t ws_bytes, void *stream);
+
 /* ---- Ingest stage: audio as it arrives -> the [rows][samples] f32, 16 kHz layout every entry point above takes ------------------------
  * Replaces: the audio loading of the reference's non-16 kHz recipes, multi_cut.to_mono(mono_downmix=False) and CutSet.resample(16000)
  * (src/datasets/switchboard/utils.py:102-107, fisher_english/utils.py:106-108, callhome_english/utils.py:110-112, eval2000/utils.py:92-94,

@@ -108,6 +108,15 @@ SIGNATURES = {
     "uvad_window_wav_slots_step_i16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_window_wav_slots_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uvad_sliding_configure": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "uvad_sliding_count": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "uvad_sliding_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int]),
+    "uvad_sliding_wav_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int]),
+    "uvad_sliding_classify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                        C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    **{name: (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                        C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
+       for name in ("uvad_sliding_forward", "uvad_sliding_forward_i16", "uvad_sliding_forward_wav", "uvad_sliding_forward_wav_i16")},
     "uvad_ingest_configure": (C.c_int, [C.c_void_p, C.POINTER(IngestCfg)]),
     "uvad_ingest_set_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "uvad_ingest_out_len": (C.c_int64, [C.c_void_p, C.c_int64]),

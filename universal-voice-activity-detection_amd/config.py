@@ -51,6 +51,12 @@ def load_config() -> ConfigDict:
     # with window_seconds = None: recordings of different lengths share a batch (sorted by length, padded size within max_duration),
     # each row classified on its own length (uvad_forward_lens); False runs recordings of equal length together only
     cfg.ragged_batches = False
+    # hop_seconds = None: the cuts above.  A number: overlapping windows of window_seconds every hop_seconds over whole recordings, each
+    # run from zero state, a frame's probability the weighted mean over the windows that cover it (uvad_sliding_forward); no tail is
+    # dropped and features are slices of each recording's continuous feature stream
+    cfg.hop_seconds = None
+    cfg.sliding_weights = "hamming"   # "rect" | "hamming" (postprocess.sliding_weights)
+    cfg.sliding_group = 512           # windows per classifier launch: bounds the workspace, not the result
 
     cfg.experiments_dir = os.environ.get("UVAD_EXPERIMENTS_DIR", "experiments")
     cfg.load_checkpoint = False

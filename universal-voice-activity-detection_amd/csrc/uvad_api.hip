@@ -154,6 +154,11 @@ struct uvad_ctx {
     int ig_up = 1, ig_down = 1, ig_width = 0;
     std::vector<float> ig_taps_host;   // what d_ig_taps holds (an unchanged table is not uploaded again)
     float *d_ig_taps = nullptr;   // [INGEST_MAX_PHASES * INGEST_MAX_TAPS], allocated by the first uvad_ingest_set_taps, lives with the context
+    // sliding-window inference (uvad_sliding_*, sliding.hip): window and hop in frames, the weight table as uploaded (empty: all ones)
+    bool has_sliding = false;
+    int sl_W = 0, sl_Hf = 0;
+    std::vector<float> sl_w_host;
+    float *d_sl_w = nullptr; int sl_w_cap = 0;   // [sl_w_cap] floats, grown by uvad_sliding_configure, lives with the context
 };
 
 namespace {
@@ -2431,6 +2436,259 @@ int uvad_window_wav_slots_features(uvad_ctx *c, const void *d_state, int B, floa
     HIPCHK(c, hipMemcpyAsync(d_feats, st + SL.off_feats, (size_t)B * g.W * c->sc.c3 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     HIPCHK(c, hipMemcpyAsync(d_tw, ctr.tw_last, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return UVAD_OK;
+}
+
+// ---- sliding-window inference over whole recordings (sliding.hip) -------------------------------------------------------------------
+// log-mel workspace: window probabilities [N][W] | lens [group] | frames [R] | features [R][T][F] (uvad_sliding_forward) | classifier
+//                    workspace of (group, W)
+// waveform workspace: windows [group][Sw] samples (sized for f32) | nsamp [group] int64 | window probabilities [N][W] | SincNet output
+//                     [group][W][c3] | classifier workspace of (group, W) | SincNet workspace of (group, Sw)
+extern "C++" {
+namespace {
+struct SlidingWs { size_t off_win = 0, off_lens = 0, off_frames = 0, off_feats = 0, off_cls = 0, cls_bytes = 0, total = 0; };
+SlidingWs sliding_ws(const uvad_ctx *c, int R, int64_t T, int64_t N, int group) {
+    SlidingWs w;
+    size_t o = 0;
+    w.off_win = o; o += align_up((size_t)std::max<int64_t>(N, 1) * c->sl_W * sizeof(float));
+    w.off_lens = o; o += align_up((size_t)group * sizeof(int));
+    w.off_frames = o; o += align_up((size_t)R * sizeof(int));
+    w.off_feats = o; o += align_up((size_t)R * (size_t)T * c->mc.in_dim * sizeof(float));
+    w.off_cls = o; w.cls_bytes = carve(c, group, c->sl_W).total; o += w.cls_bytes;
+    w.total = o;
+    return w;
+}
+struct SlidingWavWs { size_t off_nsamp = 0, off_win = 0, off_feats = 0, off_cls = 0, cls_bytes = 0, off_sinc = 0, sinc_bytes = 0, total = 0; };
+SlidingWavWs sliding_wav_ws(const uvad_ctx *c, int64_t N, int group) {
+    SlidingWavWs w;
+    const int64_t sw = wav_span(wav_geom(c), c->sl_W);
+    size_t o = align_up((size_t)group * (size_t)sw * sizeof(float));
+    w.off_nsamp = o; o += align_up((size_t)group * sizeof(int64_t));
+    w.off_win = o; o += align_up((size_t)std::max<int64_t>(N, 1) * c->sl_W * sizeof(float));
+    w.off_feats = o; o += align_up((size_t)group * c->sl_W * c->sc.c3 * sizeof(float));
+    w.off_cls = o; w.cls_bytes = carve(c, group, c->sl_W).total; o += w.cls_bytes;
+    w.off_sinc = o; w.sinc_bytes = sinc_carve(c, group, sw).total; o += w.sinc_bytes;
+    w.total = o;
+    return w;
+}
+// what every sliding call refuses before it enqueues anything
+int sliding_check(uvad_ctx *c, const std::string &who, const void *d_in, int R, int64_t len, const void *d_lens, const int32_t *d_first, int64_t N,
+                  int group, const float *d_probs, const void *ws) {
+    if (!c->has_sliding) return fail(c, UVAD_E_STATE, who + ": uvad_sliding_configure has not been called");
+    if (!d_lens) return fail(c, UVAD_E_ARG, who + ": the per-recording lengths are NULL");
+    if (!d_first) return fail(c, UVAD_E_ARG, who + ": d_first is NULL");
+    if (group < 1) return fail(c, UVAD_E_ARG, who + ": group must be >= 1");
+    if (N < 0 || N > 0x7fffffff) return fail(c, UVAD_E_ARG, who + ": N must be in [0, 2^31)");
+    if (!d_in || !d_probs || !ws || R <= 0 || R > 65535 || len <= 0) return fail(c, UVAD_E_ARG, who + ": bad argument");
+    return UVAD_OK;
+}
+// the windows [0, N) in groups of at most `group` through assemble + classifier (log-mel), into win [N][W]
+int sliding_run_groups(uvad_ctx *c, const SlidingPlan &plan, const float *feats, bool caller_feats, int group, float *win, int *lens,
+                       char *cws, size_t cws_bytes, hipStream_t s) {
+    const bool planes = c->gemm_mode >= 1 && c->f16_ok;
+    const int W = c->sl_W;
+    for (int64_t i0 = 0; i0 < plan.N; i0 += group) {
+        const int Bg = (int)std::min<int64_t>(group, plan.N - i0);
+        const WsLayout w = carve(c, Bg, W);
+        float *rows = reinterpret_cast<float *>(cws + w.off_feats);
+        SlidingAssembleArgs a{};
+        a.plan = plan; a.feats = feats; a.i0 = i0; a.Bg = Bg; a.F = c->mc.in_dim;
+        a.planes = planes; a.Fp = w.Fp; a.tiles = w.tiles;
+        a.xh = reinterpret_cast<unsigned short *>(cws + w.off_fplanes); a.xl = a.xh + plane_rows(w.M) * (size_t)w.Fp;
+        a.lens = lens;
+        // caller-supplied features can lie outside the f16 range: the f32 rows and the device flag beside the planes, as uvad_classify;
+        // the feature kernel's log-mel values cannot (uvad_forward): planes alone
+        const bool check_range = planes && caller_feats;
+        if (!planes || check_range) a.out = rows;
+        if (check_range) {
+            a.flag = reinterpret_cast<int *>(cws + w.off_flag);
+            HIPCHK(c, launch_zero_counters(reinterpret_cast<unsigned *>(a.flag), 1, s));
+        }
+        HIPCHK(c, launch_sliding_assemble(a, s));
+        if (int r = slots_classify(c, rows, Bg, W, nullptr, win + (size_t)i0 * W, cws, cws_bytes, s, check_range, planes, lens)) return r;
+    }
+    return UVAD_OK;
+}
+int sliding_finish(uvad_ctx *c, const SlidingPlan &plan, const float *win, float *d_probs, int ld_out, int32_t *d_frames, float *d_win_probs,
+                   hipStream_t s) {
+    SlidingAggregateArgs g{};
+    g.plan = plan; g.win = win; g.weights = c->sl_w_host.empty() ? nullptr : c->d_sl_w;
+    g.out = d_probs; g.ld_out = ld_out; g.frames = d_frames;
+    HIPCHK(c, launch_sliding_aggregate(g, s));
+    if (d_win_probs && plan.N > 0)
+        HIPCHK(c, hipMemcpyAsync(d_win_probs, win, (size_t)plan.N * plan.W * sizeof(float), hipMemcpyDeviceToDevice, s));
+    c->chunks_used = 1;
+    return UVAD_OK;
+}
+int sliding_logmel_cfg(uvad_ctx *c, const std::string &who, bool from_pcm) {
+    if (!c->has_model) return fail(c, UVAD_E_STATE, who + ": needs a model configuration");
+    if (!c->finalized) return fail(c, UVAD_E_STATE, who + ": uvad_finalize has not been called");
+    if (from_pcm) {
+        if (!c->has_fb || !c->tables_set) return fail(c, UVAD_E_STATE, who + ": uvad_set_tables has not been called");
+        if (c->fb.n_mels != c->mc.in_dim) return fail(c, UVAD_E_ARG, who + ": n_mels != encoding_dim");
+    }
+    return UVAD_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int uvad_sliding_configure(uvad_ctx *c, int window, int hop, const float *h_weights) {
+    if (!c) return UVAD_E_ARG;
+    if (window < 1) return fail(c, UVAD_E_ARG, "uvad_sliding_configure: window must be >= 1 frame");
+    if (hop < 1 || hop > window) return fail(c, UVAD_E_ARG, "uvad_sliding_configure: need 1 <= hop <= window");
+    for (int i = 0; h_weights && i < window; ++i)
+        if (!std::isfinite(h_weights[i]) || !(h_weights[i] > 0.0f))
+            return fail(c, UVAD_E_ARG, "uvad_sliding_configure: every weight must be finite and > 0 (weight " + std::to_string(i) + ")");
+    if (h_weights) {
+        HIPCHK(c, hipSetDevice(c->device));
+        const bool same = c->has_sliding && c->sl_w_host.size() == (size_t)window &&
+                          std::memcmp(c->sl_w_host.data(), h_weights, (size_t)window * sizeof(float)) == 0;
+        if (!same) {
+            if (c->sl_w_cap < window) {   // a larger table: a new buffer (the old one lives with the context: captured graphs may name it)
+                void *p = nullptr;
+                HIPCHK(c, hipMalloc(&p, (size_t)window * sizeof(float)));
+                c->allocs.push_back(p);
+                c->d_sl_w = reinterpret_cast<float *>(p);
+                c->sl_w_cap = window;
+            } else {
+                HIPCHK(c, hipDeviceSynchronize());   // kernels of earlier calls may still be reading the table
+            }
+            HIPCHK(c, hipMemcpy(c->d_sl_w, h_weights, (size_t)window * sizeof(float), hipMemcpyHostToDevice));
+            c->sl_w_host.assign(h_weights, h_weights + window);
+        }
+    } else {
+        c->sl_w_host.clear();
+    }
+    c->sl_W = window; c->sl_Hf = hop;
+    c->has_sliding = true;
+    return UVAD_OK;
+}
+
+int64_t uvad_sliding_count(int64_t frames, int window, int hop) {
+    if (frames < 0 || window < 1 || hop < 1 || hop > window) return UVAD_E_ARG;
+    if (frames == 0) return 0;
+    if (frames <= window) return 1;
+    return (frames - window + hop - 1) / hop + 1;
+}
+
+size_t uvad_sliding_workspace_bytes(const uvad_ctx *c, int R, int64_t T, int64_t N, int group) {
+    if (!c || !c->has_model || !c->has_sliding || R <= 0 || T <= 0 || N < 0 || group < 1) return 0;
+    return sliding_ws(c, R, T, N, group).total;
+}
+
+size_t uvad_sliding_wav_workspace_bytes(const uvad_ctx *c, int R, int64_t S, int64_t N, int group) {
+    if (!c || !c->has_model || !c->has_sinc || !c->has_sliding || R <= 0 || S <= 0 || N < 0 || group < 1) return 0;
+    return sliding_wav_ws(c, N, group).total;
+}
+
+int uvad_sliding_classify(uvad_ctx *c, const float *d_feats, int R, int T, const int32_t *d_lens, const int32_t *d_first, int64_t N, int group,
+                          float *d_probs, int ld_out, int32_t *d_frames, float *d_win_probs, void *ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    const std::string who = "uvad_sliding_classify";
+    if (int r = sliding_check(c, who, d_feats, R, T, d_lens, d_first, N, group, d_probs, ws)) return r;
+    if (int r = sliding_logmel_cfg(c, who, false)) return r;
+    if (ld_out < T) return fail(c, UVAD_E_ARG, who + ": ld_out must be at least T");
+    const SlidingWs wl = sliding_ws(c, R, T, N, group);
+    if (ws_bytes < wl.total) return fail(c, UVAD_E_WORKSPACE, who + ": workspace too small: need " + std::to_string(wl.total) + " bytes");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    char *wsb = reinterpret_cast<char *>(ws);
+    SlidingPlan plan{};
+    plan.first = d_first; plan.nrec = R; plan.N = N; plan.W = c->sl_W; plan.Hf = c->sl_Hf; plan.lens = d_lens; plan.T = T;
+    float *win = reinterpret_cast<float *>(wsb + wl.off_win);
+    if (int r = sliding_run_groups(c, plan, d_feats, true, group, win, reinterpret_cast<int *>(wsb + wl.off_lens), wsb + wl.off_cls, wl.cls_bytes, s))
+        return r;
+    return sliding_finish(c, plan, win, d_probs, ld_out, d_frames, d_win_probs, s);
+}
+
+static int sliding_forward_impl(uvad_ctx *c, const void *d_pcm, int is_i16, int R, int64_t S, const int64_t *d_nsamp, const int32_t *d_first,
+                                int64_t N, int group, float *d_probs, int ld_out, int32_t *d_frames, float *d_win_probs, void *ws,
+                                size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    const std::string who = is_i16 ? "uvad_sliding_forward_i16" : "uvad_sliding_forward";
+    if (int r = sliding_check(c, who, d_pcm, R, S, d_nsamp, d_first, N, group, d_probs, ws)) return r;
+    if (int r = sliding_logmel_cfg(c, who, true)) return r;
+    const int64_t T = uvad_num_frames(c, S);
+    if (T <= 0 || T > 0x7fffffff) return fail(c, UVAD_E_ARG, who + ": bad frame count");
+    if (ld_out < T) return fail(c, UVAD_E_ARG, who + ": ld_out must be at least uvad_num_frames(S) = " + std::to_string(T));
+    const SlidingWs wl = sliding_ws(c, R, T, N, group);
+    if (ws_bytes < wl.total) return fail(c, UVAD_E_WORKSPACE, who + ": workspace too small: need " + std::to_string(wl.total) + " bytes");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    char *wsb = reinterpret_cast<char *>(ws);
+    // the recordings' continuous feature rows, once, by the unchanged feature kernel in its lens form (right-edge reflection at S_r)
+    float *feats = reinterpret_cast<float *>(wsb + wl.off_feats);
+    if (int r = fbank_impl(c, d_pcm, is_i16, R, S, feats, stream, nullptr, nullptr, 0, d_nsamp)) return r;
+    int *frames = reinterpret_cast<int *>(wsb + wl.off_frames);
+    HIPCHK(c, launch_frames_of(d_nsamp, R, S, c->fb.frame_len, c->fb.frame_shift, c->fb.snip_edges, frames, s));
+    SlidingPlan plan{};
+    plan.first = d_first; plan.nrec = R; plan.N = N; plan.W = c->sl_W; plan.Hf = c->sl_Hf; plan.lens = frames; plan.T = (int)T;
+    float *win = reinterpret_cast<float *>(wsb + wl.off_win);
+    if (int r = sliding_run_groups(c, plan, feats, false, group, win, reinterpret_cast<int *>(wsb + wl.off_lens), wsb + wl.off_cls, wl.cls_bytes, s))
+        return r;
+    return sliding_finish(c, plan, win, d_probs, ld_out, d_frames, d_win_probs, s);
+}
+
+int uvad_sliding_forward(uvad_ctx *c, const float *d_pcm, int R, int64_t S, const int64_t *d_nsamp, const int32_t *d_first, int64_t N, int group,
+                         float *d_probs, int ld_out, int32_t *d_frames, float *d_win_probs, void *ws, size_t ws_bytes, void *stream) {
+    return sliding_forward_impl(c, d_pcm, 0, R, S, d_nsamp, d_first, N, group, d_probs, ld_out, d_frames, d_win_probs, ws, ws_bytes, stream);
+}
+int uvad_sliding_forward_i16(uvad_ctx *c, const int16_t *d_pcm, int R, int64_t S, const int64_t *d_nsamp, const int32_t *d_first, int64_t N,
+                             int group, float *d_probs, int ld_out, int32_t *d_frames, float *d_win_probs, void *ws, size_t ws_bytes,
+                             void *stream) {
+    return sliding_forward_impl(c, d_pcm, 1, R, S, d_nsamp, d_first, N, group, d_probs, ld_out, d_frames, d_win_probs, ws, ws_bytes, stream);
+}
+
+static int sliding_forward_wav_impl(uvad_ctx *c, const void *d_wav, int is_i16, int R, int64_t S, const int64_t *d_nsamp,
+                                    const int32_t *d_first, int64_t N, int group, float *d_probs, int ld_out, int32_t *d_frames,
+                                    float *d_win_probs, void *ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    const std::string who = is_i16 ? "uvad_sliding_forward_wav_i16" : "uvad_sliding_forward_wav";
+    if (int r = sliding_check(c, who, d_wav, R, S, d_nsamp, d_first, N, group, d_probs, ws)) return r;
+    if (int r = wav_window_check_cfg(c, who)) return r;
+    const WavGeom geo = wav_geom(c);
+    const int W = c->sl_W;
+    const int64_t sw = wav_span(geo, W);
+    if (sw > 0x7fffffff || geo.J * (int64_t)c->sl_Hf > 0x7fffffff) return fail(c, UVAD_E_UNSUPPORTED, who + ": window too long");
+    // the closed form the window arithmetic rests on (one constant stride J, receptive field R), against the stage-by-stage floor chain
+    if (uvad_sincnet_num_frames(c, sw) != W || uvad_sincnet_num_frames(c, sw + geo.J) != W + 1 || uvad_sincnet_num_frames(c, sw - 1) != W - 1)
+        return fail(c, UVAD_E_UNSUPPORTED, who + ": the SincNet geometry has no single frame step: frames(S) = (S - R) / J + 1 does not hold");
+    const int64_t T = uvad_sincnet_num_frames(c, S);
+    if (T <= 0 || T > 0x7fffffff) return fail(c, UVAD_E_ARG, who + ": rows too short for one output frame");
+    if (ld_out < T) return fail(c, UVAD_E_ARG, who + ": ld_out must be at least uvad_sincnet_num_frames(S) = " + std::to_string(T));
+    const SlidingWavWs wl = sliding_wav_ws(c, N, group);
+    if (ws_bytes < wl.total) return fail(c, UVAD_E_WORKSPACE, who + ": workspace too small: need " + std::to_string(wl.total) + " bytes");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    char *wsb = reinterpret_cast<char *>(ws);
+    SlidingPlan plan{};
+    plan.first = d_first; plan.nrec = R; plan.N = N; plan.W = W; plan.Hf = c->sl_Hf; plan.T = (int)T;
+    plan.nsamp = reinterpret_cast<const long long *>(d_nsamp); plan.S = S; plan.J = (int)geo.J; plan.R0 = (int)geo.R;
+    float *win = reinterpret_cast<float *>(wsb + wl.off_win);
+    float *feats = reinterpret_cast<float *>(wsb + wl.off_feats);
+    int64_t *nsamp = reinterpret_cast<int64_t *>(wsb + wl.off_nsamp);
+    for (int64_t i0 = 0; i0 < N; i0 += group) {
+        const int Bg = (int)std::min<int64_t>(group, N - i0);
+        // 1. the group's PCM windows left-aligned at S = Sw, 2. SincNet in its lens form (every norm over the window's own samples),
+        // 3. the classifier at (Bg, W) with the windows' frame counts
+        SlidingWavArgs a{};
+        a.plan = plan; a.pcm = d_wav; a.i0 = i0; a.Bg = Bg; a.Sw = sw; a.out = wsb; a.nsamp_out = reinterpret_cast<long long *>(nsamp);
+        HIPCHK(c, launch_sliding_wav_gather(a, is_i16, s));
+        const int *lens = nullptr;
+        if (int r = sincnet_impl(c, wsb, is_i16, Bg, sw, feats, wsb + wl.off_sinc, wl.sinc_bytes, s, nsamp, &lens)) return r;
+        if (int r = slots_classify(c, feats, Bg, W, nullptr, win + (size_t)i0 * W, wsb + wl.off_cls, wl.cls_bytes, s, true, false, lens)) return r;
+    }
+    return sliding_finish(c, plan, win, d_probs, ld_out, d_frames, d_win_probs, s);
+}
+
+int uvad_sliding_forward_wav(uvad_ctx *c, const float *d_wav, int R, int64_t S, const int64_t *d_nsamp, const int32_t *d_first, int64_t N,
+                             int group, float *d_probs, int ld_out, int32_t *d_frames, float *d_win_probs, void *ws, size_t ws_bytes,
+                             void *stream) {
+    return sliding_forward_wav_impl(c, d_wav, 0, R, S, d_nsamp, d_first, N, group, d_probs, ld_out, d_frames, d_win_probs, ws, ws_bytes, stream);
+}
+int uvad_sliding_forward_wav_i16(uvad_ctx *c, const int16_t *d_wav, int R, int64_t S, const int64_t *d_nsamp, const int32_t *d_first, int64_t N,
+                                 int group, float *d_probs, int ld_out, int32_t *d_frames, float *d_win_probs, void *ws, size_t ws_bytes,
+                                 void *stream) {
+    return sliding_forward_wav_impl(c, d_wav, 1, R, S, d_nsamp, d_first, N, group, d_probs, ld_out, d_frames, d_win_probs, ws, ws_bytes, stream);
 }
 
 // ---- ingest stage (ingest.hip) ---------------------------------------------------------------------------------------------------

@@ -307,6 +307,40 @@ struct SlotEmitArgs {
 };
 hipError_t launch_slot_emit(const SlotEmitArgs &a, hipStream_t s);
 
+// ---- sliding.hip: sliding-window inference over whole recordings (uvad_sliding_*) ------------------------------------------------------
+// The window list of a batch of nrec recordings: first (device int32 [nrec + 1], the exclusive prefix of the planned window counts, from
+// the host), N = first[nrec] as the host passed it, window W and hop Hf in frames.  T_r comes from the device lengths alone: lens (int32
+// [nrec] frames, clamped to [0, T]) for log-mel, or nsamp (int64 [nrec] samples, clamped to [0, S]) with the waveform model's closed
+// form frames(S) = 0 if S < R0 else (S - R0) / J + 1.  Window j of r holds clamp(T_r - j Hf, 0, W) frames, whatever the plan says.
+struct SlidingPlan {
+    const int *first; int nrec; long long N; int W, Hf;
+    const int *lens; int T;                              // T: frames per row of the recordings' feature / output rows
+    const long long *nsamp; long long S; int J, R0;      // waveform model: samples per PCM row, frame step and receptive field
+};
+// log-mel: windows [i0, i0 + Bg) of the plan out of feats [nrec][T][F] -> the planes (window_assemble_kernel's layout at T = W) and / or
+// f32 rows out [Bg][W][F] (planes: optional, the exact projection's operand), zero past each length; lens [Bg] = the lengths; flag
+// (planes only, optional, zeroed by the caller): set to 1 if a value is non-finite or outside the f16 range
+struct SlidingAssembleArgs {
+    SlidingPlan plan; const float *feats; long long i0; int Bg, F;
+    int planes; unsigned short *xh, *xl; int Fp, tiles;
+    float *out; int *lens; int *flag;
+};
+hipError_t launch_sliding_assemble(const SlidingAssembleArgs &a, hipStream_t s);
+// waveform: the same windows' samples [J Hf j, J Hf j + Sw) of pcm [nrec][S], clipped to S_r, left-aligned into out [Bg][Sw] (zero past
+// the clipped length), nsamp_out [Bg] = that length; Sw = R0 + J (W - 1)
+struct SlidingWavArgs {
+    SlidingPlan plan; const void *pcm; long long i0; int Bg; long long Sw;
+    void *out; long long *nsamp_out;
+};
+hipError_t launch_sliding_wav_gather(const SlidingWavArgs &a, int is_i16, hipStream_t s);
+// out [nrec][ld_out] at t < T: the weighted mean over the covering windows of win [N][W] (weights: device [W] or nullptr = ones), +0 at
+// t >= T_r and where no planned window covers; frames [nrec] (optional) = T_r
+struct SlidingAggregateArgs {
+    SlidingPlan plan; const float *win, *weights;
+    float *out; int ld_out; int *frames;
+};
+hipError_t launch_sliding_aggregate(const SlidingAggregateArgs &a, hipStream_t s);
+
 // ---- lstm_stack.hip: every layer of a causal (one-direction, H = 128) stack for T <= LSTM_STACK_TMAX new frames in ONE launch, carried
 //      (h, c) updated in place: the streaming step (uvad_stream_step).  Exact f32.
 constexpr int LSTM_STACK_TMAX = 4, LSTM_STACK_MAX_LAYERS = 8, LSTM_STACK_MAX_LIN = 4;

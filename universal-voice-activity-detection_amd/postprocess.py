@@ -27,6 +27,21 @@ def median_filter(x: torch.Tensor, SPEECH_WINDOW: float = 0.5, window: float = 0
     return runtime.median_filter(x, median_window(window, SPEECH_WINDOW), lengths=lengths).to(torch.int64)
 
 
+def sliding_weights(kind: str, W: int) -> np.ndarray:
+    """The aggregation weights (W,) f32 of the sliding calls (VadRuntime.sliding_configure): "rect" -- every window counts alike at every
+    frame -- or "hamming", 0.54 - 0.46 cos(2 pi k / (W - 1)), which trusts a window's middle (the BiLSTM has context on both sides there)
+    over its edges; its smallest value is 0.08, so every weight is > 0 as the library requires."""
+    if W < 1:
+        raise ValueError(f"W must be >= 1, got {W}")
+    if kind == "rect" or W == 1:
+        if kind not in ("rect", "hamming"):
+            raise ValueError(f"unknown sliding weights {kind!r} (rect, hamming)")
+        return np.ones(W, np.float32)
+    if kind == "hamming":
+        return (0.54 - 0.46 * np.cos(2.0 * np.pi * np.arange(W) / (W - 1))).astype(np.float32)
+    raise ValueError(f"unknown sliding weights {kind!r} (rect, hamming)")
+
+
 _RT = {}
 
 

@@ -141,6 +141,28 @@ def wav_window_slots_plan(flags, chunk: int, window: int, lookahead: int = 0, J:
     return _slots_plan(flags, (lambda n: 0 if n < R else (n - R) // J + 1, chunk), window, lookahead)
 
 
+def sliding_count(frames: int, window: int, hop: int) -> int:
+    """Windows that cover a recording of `frames` frames (uvad_sliding_count, include/uvad.h): 0 for an empty one, 1 up to a window's
+    length, else ceil((frames - window) / hop) + 1: window j starts at frame j * hop and holds min(window, frames - j * hop) frames."""
+    if frames < 0 or window < 1 or not 1 <= hop <= window:
+        raise ValueError(f"need frames >= 0, window >= 1 and 1 <= hop <= window (got {frames}, {window}, {hop})")
+    if frames == 0:
+        return 0
+    if frames <= window:
+        return 1
+    return -(-(frames - window) // hop) + 1
+
+
+def sliding_plan(frames, window: int, hop: int):
+    """The window list of the sliding calls from the recordings' frame counts: (counts, first) -- counts[r] = sliding_count(frames[r])
+    and first, the R + 1 exclusive prefix sums the library takes as d_first (first[R] = N windows in all)."""
+    counts = [sliding_count(int(t), window, hop) for t in frames]
+    first = [0]
+    for n in counts:
+        first.append(first[-1] + n)
+    return counts, first
+
+
 class VadRuntime:
     def __init__(self, device, fbank: Optional[FbankConfig] = None, model: Optional[dict] = None, sincnet: Optional[dict] = None):
         """model: {"encoding_dim": int, "lstm": {...merged defaults...}, "linear": {...}} or None.
@@ -792,6 +814,96 @@ class VadRuntime:
             self._check(self.lib.uvad_window_wav_slots_features(self.ctx, st["state"].data_ptr(), st["B"], feats.data_ptr(), tw.data_ptr(),
                                                                 self._stream()))
             return feats, tw
+
+    # ------------------------------------------------------------------ sliding windows over whole recordings (uvad_sliding_*)
+    def sliding_configure(self, window: int, hop: int, weights=None):
+        """Window and hop in frames and the aggregation weights (W,) -- None: all ones; postprocess.sliding_weights makes the usual ones
+        -- of the sliding calls below (uvad_sliding_configure).  The table is uploaded here, once."""
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights), np.float32)
+            if w.shape != (int(window),):
+                raise ValueError(f"weights must have shape ({int(window)},), got {w.shape}")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_sliding_configure(self.ctx, int(window), int(hop), w.ctypes.data if w is not None else None))
+        self._sliding = (int(window), int(hop))
+
+    def _sliding_call(self, fn, ws_bytes, x, R, L, T, n, host_frames, first, group, tap):
+        """ws_bytes(N, group) -> workspace size; L: the row length the entry point takes (frames or samples), T: frames per output row."""
+        if getattr(self, "_sliding", None) is None:
+            raise RuntimeError("call sliding_configure(window, hop, weights) first")
+        W, Hf = self._sliding
+        if first is None:
+            first = sliding_plan(host_frames, W, Hf)[1]
+        first = [int(v) for v in first]
+        if len(first) != R + 1:
+            raise ValueError(f"first must hold {R + 1} prefix sums, got {len(first)}")
+        N = first[-1]
+        group = max(1, min(int(group), max(N, 1)))
+        d_first = torch.tensor(first, dtype=torch.int32, device=self.device)
+        need = int(ws_bytes(N, group))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        probs = torch.empty((R, T), dtype=torch.float32, device=self.device)
+        frames = torch.empty(R, dtype=torch.int32, device=self.device)
+        win = torch.empty((N, W), dtype=torch.float32, device=self.device) if tap else None
+        self._check(fn(self.ctx, x.data_ptr(), R, L, n.data_ptr(), d_first.data_ptr(), N, group, probs.data_ptr(), T, frames.data_ptr(),
+                       win.data_ptr() if tap and N else None, self._ws.data_ptr(), self._ws.numel(), self._stream()))
+        return (probs, frames, win) if tap else (probs, frames)
+
+    @staticmethod
+    def _host_lengths(lengths):
+        return [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+
+    def sliding_classify(self, feats: "torch.Tensor", lengths, group: int = 512, first=None, tap: bool = False):
+        """feats (R,T,F) on the GPU, lengths: valid frames per recording (R,) -> (probs (R,T), frames int32 (R,)): every recording
+        covered by windows of the configured length and hop (sliding_plan), each run from zero state on its own length, a frame's
+        probability the weighted mean over the windows that cover it; 0 past a recording's length (uvad_sliding_classify).  group: windows
+        per classifier launch (bounds the workspace, not the result).  first: another window list than sliding_plan's (R + 1 prefix
+        sums).  tap: also return every window's probabilities (N, W)."""
+        with torch.cuda.device(self.device):
+            feats = self._dev_f32(feats, "feats")
+            R, T, F = feats.shape
+            if F != self._mc_c.in_dim:
+                raise ValueError(f"feature dim {F} != encoding_dim {self._mc_c.in_dim}")
+            host = [min(max(v, 0), T) for v in self._host_lengths(lengths)]
+            n = self._dev_lens(lengths, R, T, torch.int32, "lengths (frames)")
+            ws = lambda N, g: self.lib.uvad_sliding_workspace_bytes(self.ctx, R, T, N, g)   # noqa: E731
+            return self._sliding_call(self.lib.uvad_sliding_classify, ws, feats, R, T, T, n, host, first, group, tap)
+
+    def sliding_forward(self, pcm: "torch.Tensor", lengths, group: int = 512, first=None, tap: bool = False):
+        """pcm (R,S) f32 or int16 on the GPU, lengths: samples per recording (R,) -> (probs (R,T), frames (R,)), T = num_frames(S): the
+        recordings' continuous log-mel rows are computed once (uvad_fbank_lens), then as sliding_classify (uvad_sliding_forward[_i16])."""
+        with torch.cuda.device(self.device):
+            pcm, i16 = self._dev_wav(pcm)
+            R, S = pcm.shape
+            T = self.num_frames(S)
+            if T <= 0:
+                raise ValueError(f"{S} samples are too short for one frame")
+            host = [self.num_frames(min(max(v, 0), S)) for v in self._host_lengths(lengths)]
+            n = self._dev_lens(lengths, R, S, torch.int64, "lengths (samples)")
+            fn = self.lib.uvad_sliding_forward_i16 if i16 else self.lib.uvad_sliding_forward
+            ws = lambda N, g: self.lib.uvad_sliding_workspace_bytes(self.ctx, R, T, N, g)   # noqa: E731
+            return self._sliding_call(fn, ws, pcm, R, S, T, n, host, first, group, tap)
+
+    def sliding_forward_wav(self, wav: "torch.Tensor", lengths, group: int = 512, first=None, tap: bool = False):
+        """The waveform model: wav (R,S) f32 or int16, lengths: samples per recording -> (probs (R,T), frames (R,)), T =
+        sincnet_num_frames(S).  Window j of a recording is its samples from 270 * hop * j on (991 + 270 * (W - 1) of them, clipped to the
+        recording), through SincNet with every norm over the window's own samples (uvad_sliding_forward_wav[_i16])."""
+        if self._sn_c is None:
+            raise RuntimeError("this runtime was created without a SincNet configuration")
+        with torch.cuda.device(self.device):
+            wav, i16 = self._dev_wav(wav)
+            R, S = wav.shape
+            T = self.sincnet_num_frames(S)
+            if T <= 0:
+                raise ValueError(f"{S} samples are too short for one SincNet frame")
+            host = [self.sincnet_num_frames(min(max(v, 0), S)) for v in self._host_lengths(lengths)]
+            n = self._dev_lens(lengths, R, S, torch.int64, "lengths (samples)")
+            fn = self.lib.uvad_sliding_forward_wav_i16 if i16 else self.lib.uvad_sliding_forward_wav
+            ws = lambda N, g: self.lib.uvad_sliding_wav_workspace_bytes(self.ctx, R, S, N, g)   # noqa: E731
+            return self._sliding_call(fn, ws, wav, R, S, T, n, host, first, group, tap)
 
     # ------------------------------------------------------------------ ingest stage: audio as it arrives -> (rows, samples) f32 at 16 kHz
     _INGEST_DTYPES = {"f32": torch.float32, "int16": torch.int16, "ulaw": torch.uint8, "alaw": torch.uint8}

@@ -32,7 +32,7 @@ import torch
 from .engine import VadModel
 from .features import FbankConfig
 from .pipeline import ForwardPipeline
-from .postprocess import labels_to_intervals_batch, median_filter, sincnet_labels_to_intervals
+from .postprocess import labels_to_intervals_batch, median_filter, sincnet_labels_to_intervals, sliding_weights
 from .sincnet import SincNet
 from .synth import seed_weights, synth_pcm
 
@@ -162,6 +162,68 @@ def open_pipeline(net, device, depth: int):
     return None
 
 
+def _write_results(results, kwargs):
+    results.sort(key=lambda r: r["recording_id"])
+
+    out_dir = kwargs.get("predict_output_dir") or ""
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "predictions.json"), "w") as f:
+            json.dump([{"recording_id": r["recording_id"], "num_frames": r["num_frames"],
+                        "speech_frames": int(r["labels"].sum()), "intervals": r["intervals"]} for r in results], f, indent=1)
+    for r in results:
+        print(f"{r['recording_id']}: {r['num_frames']} frames, {int(r['labels'].sum())} speech, {len(r['intervals'])} intervals")
+    return results
+
+
+def sliding_geometry(rt, sincnet: bool, window_seconds: float, hop_seconds: float, frame_shift: float, sr: int = 16000):
+    """(W, Hf) in frames of predict_vad's sliding path: the frames of one window of window_seconds -- 500 log-mel frames, 293 of the
+    waveform model for the reference's 5 s -- and the hop rounded to whole frames (10 ms log-mel frames; 270-sample SincNet frames)."""
+    wn = int(round(window_seconds * sr))
+    W = rt.sincnet_num_frames(wn) if sincnet else rt.num_frames(wn)
+    Hf = int(round(hop_seconds * sr / 270.0)) if sincnet else int(round(hop_seconds / frame_shift))
+    if W < 1 or not 1 <= Hf <= W:
+        raise ValueError(f"hop_seconds={hop_seconds} gives a hop of {Hf} frames: need 1 <= hop <= window = {W} frames")
+    return W, Hf
+
+
+def _predict_sliding(recs, rt, sincnet, kwargs, window_s, hop_s, frame_shift, med_window, device, sr=16000):
+    """predict_vad with hop_seconds: whole recordings as ragged [R][S_max] batches within the max_duration budget, overlapping windows
+    aggregated on the device (uvad_sliding_forward[_wav][_i16]), then the lens median filter and run-length kernels on the frame counts
+    the call returned.  Every recording is copied into its row of the device batch by itself: nothing is stacked on the host."""
+    W, Hf = sliding_geometry(rt, sincnet, window_s, hop_s, frame_shift, sr)
+    rt.sliding_configure(W, Hf, sliding_weights(kwargs.get("sliding_weights", "hamming"), W))
+    group = int(kwargs.get("sliding_group", 512))
+    results = [None] * len(recs)
+    lengths = [len(r["pcm"]) for r in recs]
+    min_samples = 991 if sincnet else 1
+    for batch in pack_ragged_batches(lengths, int(kwargs["max_duration"] * sr)):
+        smax = max(lengths[i] for i in batch)
+        if smax < min_samples:   # nothing in this batch holds a frame
+            for i in batch:
+                results[i] = {"recording_id": recs[i]["id"], "num_frames": 0, "labels": np.zeros(0, np.uint8), "probs": np.zeros(0, np.float32),
+                              "intervals": []}
+            continue
+        mixed = len({recs[i]["pcm"].dtype for i in batch}) > 1   # int16 rows beside ingested f32 ones: read as q / 32768
+        i16 = not mixed and recs[batch[0]]["pcm"].dtype == np.int16
+        x = torch.zeros((len(batch), smax), dtype=torch.int16 if i16 else torch.float32, device=device)
+        for r, i in enumerate(batch):
+            row = torch.from_numpy(np.array(recs[i]["pcm"])).to(device)
+            x[r, :lengths[i]] = row.float() / 32768.0 if mixed and row.dtype == torch.int16 else row
+        nsamp = [lengths[i] for i in batch]
+        probs, frames = (rt.sliding_forward_wav if sincnet else rt.sliding_forward)(x, nsamp, group=group)
+        lab = median_filter(probs, window=med_window, runtime=rt, lengths=frames)         # uvad_median_filter_lens
+        fr = frames.tolist()
+        if sincnet:
+            ivs = [sincnet_labels_to_intervals(lab[r, :fr[r]], nsamp[r] / sr, runtime=rt) if fr[r] else [] for r in range(len(batch))]
+        else:
+            ivs = labels_to_intervals_batch(lab, frame_shift, runtime=rt, lengths=frames)     # uvad_label_runs_lens
+        for r, i in enumerate(batch):
+            results[i] = {"recording_id": recs[i]["id"], "num_frames": int(fr[r]), "labels": lab[r, :fr[r]].cpu().numpy().astype(np.uint8),
+                          "probs": probs[r, :fr[r]].cpu().numpy(), "intervals": ivs[r]}
+    return results
+
+
 def predict_vad(**kwargs):
     assert kwargs["model_name"] in kwargs["supported_models"], \
         f"Invalid model {kwargs['model_name']}. Model should be one of {kwargs['supported_models']}"
@@ -217,6 +279,12 @@ def predict_vad(**kwargs):
                 pieces.append((ri, st, ln))
     W = None if window_s is None else int(round(window_s * sr))
     med_window = 0.02 if net.encoding_dim == 768 else 0.01   # vad_engine.py:207-208
+    hop_s = kwargs.get("hop_seconds")
+    if hop_s is not None:   # overlapping windows of window_seconds every hop_seconds, aggregated on the device; None: the cuts below, unchanged
+        if window_s is None:
+            raise ValueError("hop_seconds needs window_seconds (the window the model was trained on)")
+        return _write_results(_predict_sliding(recs, net.runtime(device), sincnet, kwargs, window_s, hop_s, frame_shift, med_window, device, sr),
+                              kwargs)
 
     # ---- batches: pieces of equal length together, at most max_duration seconds of audio per batch; with ragged_batches (whole
     #      recordings, window_seconds None) pieces of any length together, padded to the batch's longest, each row run on its own
@@ -372,14 +440,4 @@ def predict_vad(**kwargs):
             intervals = labels_to_intervals_batch(labels.unsqueeze(0), frame_shift)[0]   # run-length walk on the GPU (uvad_label_runs)
         results.append({"recording_id": r["id"], "num_frames": int(labels.shape[0]), "labels": labels.cpu().numpy().astype(np.uint8),
                         "probs": probs.cpu().numpy(), "intervals": intervals})
-    results.sort(key=lambda r: r["recording_id"])
-
-    out_dir = kwargs.get("predict_output_dir") or ""
-    if out_dir:
-        os.makedirs(out_dir, exist_ok=True)
-        with open(os.path.join(out_dir, "predictions.json"), "w") as f:
-            json.dump([{"recording_id": r["recording_id"], "num_frames": r["num_frames"],
-                        "speech_frames": int(r["labels"].sum()), "intervals": r["intervals"]} for r in results], f, indent=1)
-    for r in results:
-        print(f"{r['recording_id']}: {r['num_frames']} frames, {int(r['labels'].sum())} speech, {len(r['intervals'])} intervals")
-    return results
+    return _write_results(results, kwargs)
