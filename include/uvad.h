@@ -538,6 +538,53 @@ int uvad_ingest_stream_reset(uvad_ctx *, void *d_state, size_t state_bytes, int 
 int uvad_ingest_stream_step(uvad_ctx *, const void *d_in, const uint8_t *d_flags, int B, int chunk_in, void *d_state, size_t state_bytes,
                             float *d_out, void *stream);
 
+/* ---- Live endpointing: per-feed speech start / end events on the device --------------------------------------------------------------
+ * The streaming counterpart of uvad_median_filter_lens, uvad_label_runs_lens and merge_intervals_with_buffer in frame units.  Replaces,
+ * used live: median_filter (src/utils/helper.py:66-97), the run walk of get_new_cuts (src/scripts/predict.py:472-490) and
+ * merge_intervals_with_buffer (predict.py:614-634).  Everything is integer: the outputs equal the offline kernels' on the whole session.
+ *   Sessions: the state holds B slots, one session each; after uvad_endpoint_reset every slot holds the empty session (n = 0 frames).
+ *     A step hands slot b the next n_b = clamp(d_counts[b], 0, ld_in) probabilities of its session, columns 0 .. n_b - 1 of row b of
+ *     d_probs [B][ld_in]: the d_probs and d_counts a slot pool step wrote, consumed as they are.  d_flags is the slot pools' byte, or NULL:
+ *     UVAD_SLOT_START  before this step's frames the slot drops whatever session it held -- silently, no closing events -- and begins at 0;
+ *     UVAD_SLOT_END    after this step's frames the session is flushed (below) and the slot holds the empty session again.
+ *     Both bits: a one-step session.  Columns >= n_b, and whole rows with n_b = 0, are never read (NaN there changes no output byte).
+ *   Labels: x[t] = !(p[t] < threshold) (NaN counts as speech, as uvad_median_filter); with the odd kernel K = 2 h + 1, y[t] = 1 iff the sum
+ *     of x[u] over u in [t - h, t + h] and [0, n) exceeds h: scipy.signal.medfilt with zero padding, what uvad_median_filter_lens computes
+ *     on the prefix n.  y[t] is final once frame t + h has arrived, or at END: with m frames seen, labels are final on [0, max(0, m - h)),
+ *     and END finalises up to n.  A session's finalised labels, concatenated over its steps, are byte-identical to
+ *     uvad_median_filter_lens on the session's whole row with len = n (threshold 0.5).
+ *   Intervals with a pad of P >= 0 frames: the raw runs [s_i, c_i) of y (uvad_label_runs_lens) become [max(s_i - P, 0), min(c_i + P, n)),
+ *     and an interval merges into its predecessor when its start <= the predecessor's end.  Streaming: START at frame max(s - P, 0) is
+ *     issued when y[s] = 1 becomes final and no interval is open or pending; a run closed at c stays pending until y[c .. c + 2 P] are all
+ *     final and zero, then END is issued at c + P; a run that starts at s <= c + 2 P rejoins the pending interval without events; the END
+ *     flag closes what is open or pending at min(c + P, n), or at n while still in speech.  A session's events, concatenated, are exactly
+ *     START(lo_0), END(hi_0), START(lo_1), ... of the merged interval list of the whole session, however its frames were cut into steps.
+ *   Outputs per step, all DEVICE memory; d_ev_counts is required, the others may be NULL:
+ *     d_events [B][max_events][2] int32 {kind, frame}: kind 1 = START, 2 = END; frames count from the session's start;
+ *     d_ev_counts [B] int32: the true number of events of this step; events beyond max_events are counted but not stored (as
+ *       uvad_label_runs treats max_runs); max_events = ld_in + h + 2 always suffices;
+ *     d_active [B] uint8: 1 while a merged interval is open or pending after the step -- the gate a downstream recogniser wants;
+ *     d_labels [B][ld_lab] uint8: the labels finalised by this step, d_lab_counts [B] int32 their number (at most n_b + h);
+ *       ld_lab >= ld_in + h, and d_labels needs d_lab_counts.
+ *   Frames are int32 and saturate: a session consumes no frames past 2^31 - 1 (over a year at 20 ms) and an event frame never wraps.
+ *   The configuration lives in the state (a header written by reset): a step carries none, is one launch, allocates nothing, never
+ *   synchronises and reads every per-slot quantity from the device, so a graph captured around any step -- alone or in the same capture
+ *   as the slot pool step that feeds it -- replays for every later one.  ld_in is at most 2^18 frames per step.
+ *   A context created without feature / model configuration serves these calls.  Refusals (UVAD_E_ARG, nothing enqueued): kernel even,
+ *   < 1 or > 255; pad < 0 or > 2^20; threshold not finite; B < 1; ld_in < 1; NULL d_probs / d_counts / d_ev_counts / d_state; d_events NULL
+ *   with max_events > 0; d_labels with ld_lab < ld_in + h or without d_lab_counts; state_bytes below uvad_endpoint_state_bytes.  A state
+ *   never reset, or reset with another B: UVAD_E_STATE. */
+typedef struct {
+    int kernel;        /* odd median taps K, 1 .. 255 (25 at 20 ms frames, 49 at 10 ms) */
+    int pad;           /* P frames added to both ends of every run before merging, 0 .. 2^20 */
+    float threshold;   /* speech iff !(p < threshold); finite; 0.5 is the offline kernels' */
+} uvad_endpoint_cfg;
+size_t uvad_endpoint_state_bytes(const uvad_ctx *, int B, const uvad_endpoint_cfg *);   /* 0 on a bad configuration */
+int uvad_endpoint_reset(uvad_ctx *, void *d_state, size_t state_bytes, int B, const uvad_endpoint_cfg *, void *stream);
+int uvad_endpoint_step(uvad_ctx *, const float *d_probs, int ld_in, const int32_t *d_counts, const uint8_t *d_flags, int B, void *d_state,
+                       size_t state_bytes, int32_t *d_events, int max_events, int32_t *d_ev_counts, uint8_t *d_active, uint8_t *d_labels,
+                       int ld_lab, int32_t *d_lab_counts, void *stream);
+
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;
  *   1  (default) f32-accurate on the f16 matrix cores: weights scaled by a power of two and split on the host into THREE

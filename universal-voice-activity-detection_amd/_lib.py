@@ -35,6 +35,10 @@ class IngestCfg(C.Structure):
     _fields_ = [("encoding", C.c_int), ("channels", C.c_int), ("sample_rate", C.c_int)]
 
 
+class EndpointCfg(C.Structure):
+    _fields_ = [("kernel", C.c_int), ("pad", C.c_int), ("threshold", C.c_float)]
+
+
 class UvadError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{ERR_NAMES.get(code, code)}: {msg}")
@@ -126,6 +130,10 @@ SIGNATURES = {
     "uvad_ingest_stream_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "uvad_ingest_stream_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                           C.c_void_p]),
+    "uvad_endpoint_state_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.POINTER(EndpointCfg)]),
+    "uvad_endpoint_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(EndpointCfg), C.c_void_p]),
+    "uvad_endpoint_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "uvad_classify_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_forward_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -170,7 +178,7 @@ _lib = None
 
 def bind(lib):
     """Declare every prototype of SIGNATURES on `lib`.  The ABI number did not move when entries were appended (the ingest stage among
-    them), so a library built from an older tree passes the version check: a symbol it lacks is a loud error here, by name."""
+    them, and the endpointer after it), so a library built from an older tree passes the version check: a symbol it lacks is a loud error here, by name."""
     for name, (res, args) in SIGNATURES.items():
         try:
             fn = getattr(lib, name)

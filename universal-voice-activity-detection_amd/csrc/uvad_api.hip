@@ -91,12 +91,15 @@ struct WindowGroup { StreamCounters sc; int B = 0, W = 0, L = 0; };
 struct WavWindowGroup { int64_t n_samples = 0, n_frames = 0, n_steps = 0; int B = 0, W = 0, L = 0, is_i16 = 0; };
 // a slot pool (uvad_window_slots_*, uvad_window_wav_slots_*): only what reset fixes; every per-slot counter lives on the device
 struct SlotPool { int B = 0, chunk = 0, W = 0, L = 0, is_i16 = 0; };
+// an endpointer state (uvad_endpoint_*): what reset fixed; the device header holds the same and every per-slot quantity
+struct EndpointPool { int B = 0, kernel = 0, pad = 0; float threshold = 0.5f; };
 
 struct uvad_ctx {
     std::map<void *, StreamCounters> streams;   // host mirror of the lock-step stream groups, keyed by d_state
     std::map<void *, WindowGroup> windows;      // ... and of the windowed stream groups (uvad_window_*)
     std::map<void *, WavWindowGroup> wav_windows;   // ... and of the waveform model's windowed stream groups (uvad_window_wav_*)
     std::map<void *, SlotPool> slot_pools, wav_slot_pools;   // ... and of the slot pools of both window families (uvad_window_*slots_*)
+    std::map<void *, EndpointPool> endpoints;   // ... and of the endpointer states (uvad_endpoint_*)
     int device = 0, n_cu = 256;
     bool has_fb = false, has_model = false, finalized = false, tables_set = false;
     uvad_fbank_cfg fb{};
@@ -2899,6 +2902,57 @@ int uvad_label_runs_lens(uvad_ctx *c, const uint8_t *d_labels, int B, int T, con
     if (!d_lens) return fail(c, UVAD_E_ARG, "uvad_label_runs_lens: d_lens is NULL");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, launch_runs_lens(d_labels, B, T, max_runs, d_runs, d_counts, d_lens, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+// ---- the live endpointer (endpoint.hip) ------------------------------------------------------------------------------------------------
+static bool endpoint_cfg_ok(const uvad_endpoint_cfg *q) {
+    return q && q->kernel >= 1 && q->kernel <= 255 && q->kernel % 2 == 1 && q->pad >= 0 && q->pad <= (1 << 20) && std::isfinite(q->threshold);
+}
+
+size_t uvad_endpoint_state_bytes(const uvad_ctx *c, int B, const uvad_endpoint_cfg *q) {
+    if (!c || B < 1 || !endpoint_cfg_ok(q)) return 0;
+    return endpoint_state_bytes(B);
+}
+
+int uvad_endpoint_reset(uvad_ctx *c, void *d_state, size_t state_bytes, int B, const uvad_endpoint_cfg *q, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_state || B < 1 || !q) return fail(c, UVAD_E_ARG, "uvad_endpoint_reset: bad argument");
+    if (q->kernel < 1 || q->kernel > 255 || q->kernel % 2 == 0) return fail(c, UVAD_E_ARG, "uvad_endpoint_reset: kernel must be odd, 1 .. 255");
+    if (q->pad < 0 || q->pad > (1 << 20)) return fail(c, UVAD_E_ARG, "uvad_endpoint_reset: pad must lie in [0, 2^20] frames");
+    if (!std::isfinite(q->threshold)) return fail(c, UVAD_E_ARG, "uvad_endpoint_reset: threshold must be finite");
+    if (state_bytes < endpoint_state_bytes(B))
+        return fail(c, UVAD_E_ARG, "uvad_endpoint_reset: state too small: need " + std::to_string(endpoint_state_bytes(B)) + " bytes");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_endpoint_reset(d_state, B, q->kernel, q->pad, q->threshold, (hipStream_t)stream));
+    EndpointPool g;
+    g.B = B; g.kernel = q->kernel; g.pad = q->pad; g.threshold = q->threshold;
+    c->endpoints[d_state] = g;
+    return UVAD_OK;
+}
+
+int uvad_endpoint_step(uvad_ctx *c, const float *d_probs, int ld_in, const int32_t *d_counts, const uint8_t *d_flags, int B, void *d_state,
+                       size_t state_bytes, int32_t *d_events, int max_events, int32_t *d_ev_counts, uint8_t *d_active, uint8_t *d_labels,
+                       int ld_lab, int32_t *d_lab_counts, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_probs || !d_counts || !d_ev_counts || !d_state || B < 1 || ld_in < 1) return fail(c, UVAD_E_ARG, "uvad_endpoint_step: bad argument");
+    if (ld_in > EP_MAX_LD_IN) return fail(c, UVAD_E_ARG, "uvad_endpoint_step: ld_in above " + std::to_string(EP_MAX_LD_IN) + " frames per step");
+    if (max_events < 0 || (max_events > 0 && !d_events)) return fail(c, UVAD_E_ARG, "uvad_endpoint_step: d_events is NULL with max_events > 0");
+    if (d_labels && !d_lab_counts) return fail(c, UVAD_E_ARG, "uvad_endpoint_step: d_labels needs d_lab_counts");
+    auto it = c->endpoints.find(d_state);
+    if (it == c->endpoints.end()) return fail(c, UVAD_E_STATE, "uvad_endpoint_step: call uvad_endpoint_reset on this state first");
+    const EndpointPool &g = it->second;
+    if (B != g.B) return fail(c, UVAD_E_STATE, "uvad_endpoint_step: the state was reset with B = " + std::to_string(g.B));
+    if (state_bytes < endpoint_state_bytes(B))
+        return fail(c, UVAD_E_ARG, "uvad_endpoint_step: state too small: need " + std::to_string(endpoint_state_bytes(B)) + " bytes");
+    if (d_labels && (int64_t)ld_lab < (int64_t)ld_in + g.kernel / 2)
+        return fail(c, UVAD_E_ARG, "uvad_endpoint_step: ld_lab must be at least ld_in + kernel / 2 = " + std::to_string(ld_in + g.kernel / 2));
+    EndpointArgs a{};
+    a.probs = d_probs; a.ld_in = ld_in; a.counts = d_counts; a.flags = d_flags; a.B = B; a.state = d_state;
+    a.events = d_events; a.max_events = max_events; a.ev_counts = d_ev_counts; a.active = d_active;
+    a.labels = d_labels; a.ld_lab = ld_lab; a.lab_counts = d_lab_counts;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_endpoint_step(a, g.kernel, (hipStream_t)stream));
     return UVAD_OK;
 }
 

@@ -495,4 +495,31 @@ struct IngestArgs {
 };
 hipError_t launch_ingest(const IngestArgs &a, hipStream_t s);
 
+// ---- endpoint.hip: the live endpointer (uvad_endpoint_*, include/uvad.h): streaming median, runs and the padded merge, one slot per feed ----
+// The state is a header (what reset fixed: B and the configuration, so a step carries none) followed by one EndpointSlot per slot.
+// hist[0 .. n), n = ceil(2 h / 64), holds the thresholded frames before the slot's frame m as a bit string that ENDS at the top bit of
+// word n - 1 (frame m - 1); only its newest 2 h bits are ever read, and a new session starts from all zeros -- the median's zero padding
+// on the left.
+constexpr int EP_HIST_WORDS = 4;                      // 2 h <= 254 bits
+constexpr unsigned EP_MAGIC = 0x55564550u;            // "UVEP"
+constexpr int EP_IDLE = 0, EP_SPEECH = 1, EP_PENDING = 2;
+constexpr int EP_MAX_LD_IN = 1 << 18;                 // the step keeps the step's bits in LDS: 8 bytes per 64 frames
+struct EndpointHeader { unsigned magic; int B, kernel, pad; float threshold; int reserved[59]; };   // 256 bytes
+struct EndpointSlot {
+    unsigned long long hist[EP_HIST_WORDS];
+    int m;        // frames of the session so far (saturates at 2^31 - 1: frames past that are not consumed)
+    int st;       // EP_IDLE / EP_SPEECH (inside a run) / EP_PENDING (a run closed at frame c, its padded end not yet decided)
+    int c;        // EP_PENDING: the first non-speech frame after the last run
+    int reserved;
+};
+struct EndpointArgs {
+    const float *probs; int ld_in; const int *counts; const uint8_t *flags; int B;
+    void *state;
+    int *events; int max_events; int *ev_counts; uint8_t *active;
+    uint8_t *labels; int ld_lab; int *lab_counts;
+};
+size_t endpoint_state_bytes(int B);
+hipError_t launch_endpoint_reset(void *state, int B, int kernel, int pad, float threshold, hipStream_t s);
+hipError_t launch_endpoint_step(const EndpointArgs &a, int kernel, hipStream_t s);   // kernel: the reset's, for the LDS size only
+
 }  // namespace uvad

@@ -155,6 +155,42 @@ def merge_intervals_with_buffer(intervals, total_duration: float, buffer: float)
     return out
 
 
+def merged_runs(labels, pad: int) -> List[Tuple[int, int]]:
+    """merge_intervals_with_buffer in FRAMES on one row of 0/1 labels (host; what uvad_endpoint_step reports as events, restated): every run
+    [s, c) becomes [max(s - pad, 0), min(c + pad, len)), and an interval merges into its predecessor when its start <= the predecessor's
+    end.  pad = 0 gives the raw runs."""
+    if pad < 0:
+        raise ValueError(f"pad must be >= 0, got {pad}")
+    v = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels).astype(np.int8).ravel()
+    d = np.diff(np.concatenate(([0], v, [0])))
+    out = []
+    for s, c in zip(np.flatnonzero(d == 1).tolist(), np.flatnonzero(d == -1).tolist()):
+        lo, hi = max(s - pad, 0), min(c + pad, len(v))
+        if out and lo <= out[-1][1]:
+            out[-1][1] = hi
+        else:
+            out.append([lo, hi])
+    return [(lo, hi) for lo, hi in out]
+
+
+def events_to_intervals(events, frame_shift: float):
+    """One session's endpointer events in order, [(kind, frame)] with kind 1 = START and 2 = END -> [(start_s, end_s)] with the reference's
+    round(k * shift, 2); an interval still open (a START without its END yet) comes last as (start_s, None)."""
+    ev = np.asarray(events.cpu() if torch.is_tensor(events) else events).reshape(-1, 2).tolist()
+    out, lo = [], None
+    for kind, frame in ev:
+        if kind == 1 and lo is None:
+            lo = frame
+        elif kind == 2 and lo is not None:
+            out.append((round(float(lo * frame_shift), 2), round(float(frame * frame_shift), 2)))
+            lo = None
+        else:
+            raise ValueError(f"events out of order at {(kind, frame)}")
+    if lo is not None:
+        out.append((round(float(lo * frame_shift), 2), None))
+    return out
+
+
 def split_into_windows(intervals, window: float = 10):
     """predict.py:638-647: cut intervals longer than `window` seconds; drop remainders of 0.1 s or less."""
     out = []

@@ -706,10 +706,16 @@ class VadRuntime:
         reading the chunk and the flags from fixed buffers.  Graphs captured before a weight hot-swap are dropped."""
         B = st["B"]
         out, counts = st["out"], st["counts"]
+        ep = st.get("endpoint")
 
         def enqueue(src, flags):
-            return fn(self.ctx, src.data_ptr(), flags.data_ptr() if flags is not None else None, B, st["chunk"], st["state"].data_ptr(),
-                      out.data_ptr(), None, out.shape[1], counts.data_ptr(), st["ws"].data_ptr(), st["ws"].numel(), self._stream())
+            fp = flags.data_ptr() if flags is not None else None
+            r = fn(self.ctx, src.data_ptr(), fp, B, st["chunk"], st["state"].data_ptr(), out.data_ptr(),
+                   st["probs"].data_ptr() if ep is not None else None, out.shape[1], counts.data_ptr(), st["ws"].data_ptr(), st["ws"].numel(),
+                   self._stream())
+            if r == 0 and ep is not None:            # the endpointer right behind the pool step: its probabilities, counts and flags as they are
+                r = self._endpoint_enqueue(ep, st["probs"].data_ptr(), counts.data_ptr(), fp)
+            return r
 
         if st["graphs"] is None:
             self._check(enqueue(pcm_chunk, self._slot_flags(B, start, end)))
@@ -731,10 +737,23 @@ class VadRuntime:
         st["graph"].replay()
         return out, counts
 
-    def window_slots_open(self, B: int, chunk: int, window: int = 500, lookahead: int = 0, graphs: bool = False):
+    def _slots_endpoint(self, st, endpoint):
+        """endpoint: None, or {"kernel", "pad", "threshold"} (any subset): the pool gets a probabilities buffer and an endpointer over its
+        B slots (endpoint_open) whose step is enqueued right behind every pool step -- inside the one capture under graphs=True -- with the
+        pool's counts and flags.  st["endpoint"] holds its events / ev_counts / active, overwritten by the next step."""
+        if endpoint is None:
+            return st
+        extra = set(endpoint) - {"kernel", "pad", "threshold"}
+        if extra:
+            raise ValueError(f"unknown endpoint parameters {sorted(extra)} (kernel, pad, threshold)")
+        st["probs"] = torch.zeros_like(st["out"])
+        st["endpoint"] = self.endpoint_open(st["B"], st["out"].shape[1], **endpoint)
+        return st
+
+    def window_slots_open(self, B: int, chunk: int, window: int = 500, lookahead: int = 0, graphs: bool = False, endpoint=None):
         """Allocate and reset a log-mel slot pool (uvad_window_slots_reset): B slots stepping `chunk` samples at a time, each holding at
         most one session, windows of `window` frames, frames emitted `lookahead` frames behind the newest complete one (the END step
-        flushes them).  graphs: capture the first step into a hipGraph and replay it for every later step."""
+        flushes them).  graphs: capture the first step into a hipGraph and replay it for every later step.  endpoint: _slots_endpoint."""
         window_slots_plan([], chunk, window, lookahead, self._fb_c.frame_len, self._fb_c.frame_shift)   # the limits, before allocating
         with torch.cuda.device(self.device):
             nbytes = int(self.lib.uvad_window_slots_state_bytes(self.ctx, B, window))
@@ -744,12 +763,13 @@ class VadRuntime:
             self._check(self.lib.uvad_window_slots_reset(self.ctx, state.data_ptr(), B, chunk, window, lookahead, self._stream()))
             ws = torch.empty(int(self.lib.uvad_window_slots_workspace_bytes(self.ctx, B, chunk, window)), dtype=torch.uint8, device=self.device)
             ld = window_slots_ld_out(chunk, lookahead, self._fb_c.frame_shift)
-            return {"state": state, "ws": ws, "B": B, "chunk": chunk, "window": window, "lookahead": lookahead,
-                    "out": torch.empty((B, ld), dtype=torch.float32, device=self.device),
-                    "counts": torch.zeros(B, dtype=torch.int32, device=self.device),
-                    "in": torch.empty((B, chunk), dtype=torch.float32, device=self.device),
-                    "flags": torch.zeros(B, dtype=torch.uint8, device=self.device),
-                    "graphs": 0 if graphs else None, "graph": None, "weights_gen": getattr(self, "_weights_gen", 0)}
+            return self._slots_endpoint(
+                {"state": state, "ws": ws, "B": B, "chunk": chunk, "window": window, "lookahead": lookahead,
+                 "out": torch.empty((B, ld), dtype=torch.float32, device=self.device),
+                 "counts": torch.zeros(B, dtype=torch.int32, device=self.device),
+                 "in": torch.empty((B, chunk), dtype=torch.float32, device=self.device),
+                 "flags": torch.zeros(B, dtype=torch.uint8, device=self.device),
+                 "graphs": 0 if graphs else None, "graph": None, "weights_gen": getattr(self, "_weights_gen", 0)}, endpoint)
 
     def window_slots_step(self, st, pcm_chunk: "torch.Tensor", start=None, end=None):
         """pcm_chunk (B, chunk) f32 on the GPU; start / end: slots whose session starts with this chunk / ends after it (bool masks or
@@ -771,9 +791,9 @@ class VadRuntime:
             return feats, tw
 
     def wav_window_slots_open(self, B: int, chunk: int, window: int = 293, lookahead: int = 0, graphs: bool = False,
-                              dtype=torch.float32):
+                              dtype=torch.float32, endpoint=None):
         """Allocate and reset a waveform slot pool (uvad_window_wav_slots_reset): window_slots_open for the SincNet PyanNet, samples of
-        dtype torch.float32 or torch.int16 (read as q / 32768)."""
+        dtype torch.float32 or torch.int16 (read as q / 32768).  endpoint: _slots_endpoint."""
         if dtype not in (torch.float32, torch.int16):
             raise ValueError(f"dtype must be torch.float32 or torch.int16, got {dtype}")
         J, R = self.wav_window_geometry()
@@ -787,13 +807,14 @@ class VadRuntime:
             self._check(self.lib.uvad_window_wav_slots_reset(self.ctx, state.data_ptr(), B, chunk, window, lookahead, i16, self._stream()))
             ws = torch.empty(int(self.lib.uvad_window_wav_slots_workspace_bytes(self.ctx, B, chunk, window)), dtype=torch.uint8,
                              device=self.device)
-            return {"state": state, "ws": ws, "B": B, "chunk": chunk, "window": window, "lookahead": lookahead, "J": J, "R": R,
-                    "dtype": dtype,
-                    "out": torch.empty((B, wav_window_slots_ld_out(chunk, lookahead, J)), dtype=torch.float32, device=self.device),
-                    "counts": torch.zeros(B, dtype=torch.int32, device=self.device),
-                    "in": torch.empty((B, chunk), dtype=dtype, device=self.device),
-                    "flags": torch.zeros(B, dtype=torch.uint8, device=self.device),
-                    "graphs": 0 if graphs else None, "graph": None, "weights_gen": getattr(self, "_weights_gen", 0)}
+            return self._slots_endpoint(
+                {"state": state, "ws": ws, "B": B, "chunk": chunk, "window": window, "lookahead": lookahead, "J": J, "R": R,
+                 "dtype": dtype,
+                 "out": torch.empty((B, wav_window_slots_ld_out(chunk, lookahead, J)), dtype=torch.float32, device=self.device),
+                 "counts": torch.zeros(B, dtype=torch.int32, device=self.device),
+                 "in": torch.empty((B, chunk), dtype=dtype, device=self.device),
+                 "flags": torch.zeros(B, dtype=torch.uint8, device=self.device),
+                 "graphs": 0 if graphs else None, "graph": None, "weights_gen": getattr(self, "_weights_gen", 0)}, endpoint)
 
     def wav_window_slots_step(self, st, pcm_chunk: "torch.Tensor", start=None, end=None):
         """window_slots_step for a waveform slot pool: pcm_chunk (B, chunk) of the dtype the pool was opened with."""
@@ -814,6 +835,52 @@ class VadRuntime:
             self._check(self.lib.uvad_window_wav_slots_features(self.ctx, st["state"].data_ptr(), st["B"], feats.data_ptr(), tw.data_ptr(),
                                                                 self._stream()))
             return feats, tw
+
+    # ------------------------------------------------------------------ live endpointing (uvad_endpoint_*)
+    def endpoint_open(self, B: int, ld_in: int, kernel: int = 25, pad: int = 0, threshold: float = 0.5, max_events=None):
+        """Allocate and reset an endpointer of B slots (uvad_endpoint_reset): per slot the streaming median of `kernel` taps at `threshold`,
+        its runs widened by `pad` frames and merged, reported as START / END events.  ld_in: columns of the probability rows a step
+        reads; max_events: events kept per slot and step (default ld_in + kernel // 2 + 2, which never overflows)."""
+        cfg = _lib.EndpointCfg(int(kernel), int(pad), float(threshold))
+        if B < 1 or ld_in < 1:
+            raise ValueError(f"need B >= 1 and ld_in >= 1, got {B}, {ld_in}")
+        h = int(kernel) // 2
+        max_events = ld_in + h + 2 if max_events is None else int(max_events)
+        if max_events < 0:
+            raise ValueError("max_events must be >= 0")
+        with torch.cuda.device(self.device):
+            nbytes = int(self.lib.uvad_endpoint_state_bytes(self.ctx, B, C.byref(cfg)))
+            if nbytes == 0:
+                raise ValueError(f"bad endpoint configuration: kernel {kernel} (odd, 1 .. 255), pad {pad} (0 .. 2^20), threshold {threshold} (finite)")
+            state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._check(self.lib.uvad_endpoint_reset(self.ctx, state.data_ptr(), nbytes, B, C.byref(cfg), self._stream()))
+            return {"state": state, "B": B, "ld_in": ld_in, "kernel": int(kernel), "pad": int(pad), "threshold": float(threshold),
+                    "max_events": max_events,
+                    "events": torch.zeros((B, max_events, 2), dtype=torch.int32, device=self.device),
+                    "ev_counts": torch.zeros(B, dtype=torch.int32, device=self.device),
+                    "active": torch.zeros(B, dtype=torch.uint8, device=self.device),
+                    "labels": torch.zeros((B, ld_in + h), dtype=torch.uint8, device=self.device),
+                    "lab_counts": torch.zeros(B, dtype=torch.int32, device=self.device)}
+
+    def _endpoint_enqueue(self, ep, probs_ptr, counts_ptr, flags_ptr):
+        return self.lib.uvad_endpoint_step(self.ctx, probs_ptr, ep["ld_in"], counts_ptr, flags_ptr, ep["B"], ep["state"].data_ptr(),
+                                           ep["state"].numel(), ep["events"].data_ptr() if ep["max_events"] else None, ep["max_events"],
+                                           ep["ev_counts"].data_ptr(), ep["active"].data_ptr(), ep["labels"].data_ptr(),
+                                           ep["labels"].shape[1], ep["lab_counts"].data_ptr(), self._stream())
+
+    def endpoint_step(self, ep, probs: "torch.Tensor", counts: "torch.Tensor", start=None, end=None):
+        """probs (B, ld_in) f32 and counts (B,) int32 on the GPU: slot b consumes probs[b, :counts[b]]; start / end as window_slots_step.
+        -> (events (B, max_events, 2) int32 {kind 1 START / 2 END, frame}, ev_counts (B,) int32, active (B,) uint8), on the device and
+        overwritten by the next step; ep["labels"] / ep["lab_counts"] hold the labels the step finalised."""
+        with torch.cuda.device(self.device):
+            probs = self._dev_f32(probs, "probs")
+            if tuple(probs.shape) != (ep["B"], ep["ld_in"]):
+                raise ValueError(f"expected ({ep['B']}, {ep['ld_in']}) probabilities, got {tuple(probs.shape)}")
+            if not torch.is_tensor(counts) or counts.device != self.device or counts.dtype != torch.int32 or tuple(counts.shape) != (ep["B"],):
+                raise ValueError(f"counts must be an int32 tensor of shape ({ep['B']},) on {self.device}")
+            flags = self._slot_flags(ep["B"], start, end)
+            self._check(self._endpoint_enqueue(ep, probs.data_ptr(), counts.contiguous().data_ptr(), flags.data_ptr() if flags is not None else None))
+            return ep["events"], ep["ev_counts"], ep["active"]
 
     # ------------------------------------------------------------------ sliding windows over whole recordings (uvad_sliding_*)
     def sliding_configure(self, window: int, hop: int, weights=None):
