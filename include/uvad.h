@@ -585,6 +585,67 @@ int uvad_endpoint_step(uvad_ctx *, const float *d_probs, int ld_in, const int32_
                        size_t state_bytes, int32_t *d_events, int max_events, int32_t *d_ev_counts, uint8_t *d_active, uint8_t *d_labels,
                        int ld_lab, int32_t *d_lab_counts, void *stream);
 
+/* ---- Scoring against reference labels: counts, loss, threshold sweep, accumulated on the device ---------------------------------------
+ * Replaces: test_step / validation_step of src/engines/vad_engine.py:128-202 (BinaryStatScores at one operating point, the median filter
+ * in front of it, binary_cross_entropy of _common_step, :247-278), get_false_alarm / get_missed_detection and get_binary_tensor of
+ * src/scripts/other_vad_metrics.py:299-318 and supervisions_feature_mask of src/datasets/custom_vad.py:41-75.  Everything but the loss
+ * is integer and exact; the state accumulates over any number of steps, and a step allocates nothing, never synchronises and reads the
+ * row lengths from the device, so it can be one more node of a captured graph.
+ *
+ * uvad_intervals_to_labels: d_iv [B][max_iv][2] int32 {start, end} in frames, d_iv_counts [B] int32 (clamped to [0, max_iv]).  Row b of
+ *   d_labels [B][ld] uint8 becomes 1 on the union of [max(s, 0), min(e, len_b)) over its first d_iv_counts[b] intervals and 0 elsewhere
+ *   on [0, len_b), len_b = clamp(d_lens[b], 0, T) (T when d_lens is NULL).  Intervals may be unsorted and overlapping; e <= s is ignored.
+ *   Columns at or past len_b are not written.  ld >= T; d_iv may be NULL when max_iv is 0.
+ *
+ * Configuration (uvad_score_configure; a context created without feature / model configuration serves these calls):
+ *   n_points 1 .. 8 operating points (threshold[m] finite, kernel[m] odd 1 .. 255); collar 0 .. 1024 frames; bins a power of two 2 .. 1024;
+ *   segment: frames one workgroup scores, 1 .. 16384, 0 = the built-in default (2048).  No output depends on it.
+ * Semantics of a step for row b with n = clamp(d_lens[b], 0, T) (T when d_lens is NULL), p = d_probs [B][ld_p] f32, gt = d_gt [B][ld_gt]
+ * uint8 (non-zero = speech); columns at or past n, and rows with n = 0, are never read in either:
+ *   labels at point m   x[t] = !(p[t] < threshold[m]) (NaN counts as speech); with K = 2 h + 1, y[t] = 1 iff the sum of x over
+ *                       [t - h, t + h] and [0, n) exceeds h: uvad_median_filter_lens at that threshold; K = 1 is the raw threshold;
+ *   collar c            with k over the boundaries 1 <= k <= n - 1 where gt[k - 1] != gt[k], frame t is unscored iff some k has
+ *                       k - c <= t <= k + c - 1; row ends are not boundaries; c = 0 scores every valid frame;
+ *   counts              tp, fp, tn, fn per point over the scored frames, pooled in the state; for point 0 also per row:
+ *                       d_rows [B][4] uint64 {tp, fp, tn, fn} of this step (may be NULL);
+ *   sweep               hist[class][bin] over the scored frames, class = (gt != 0), bin = min(bins - 1, floor(p * bins)) (NaN: the last
+ *                       bin; p * bins is exact in f32): the sum of hist[0] over bins >= j is the number of false-alarm frames at
+ *                       threshold j / bins with K = 1, the sum of hist[1] over bins < j the number of missed frames, both exactly, for
+ *                       every j < bins (j = bins stands for a threshold above every probability: p = 1 and NaN sit in the last bin);
+ *   loss                the sum of F.binary_cross_entropy's terms -(g max(log p, -100) + (1 - g) max(log(1 - p), -100)) over ALL valid
+ *                       frames (no collar), each evaluated in f64 from the f32 probability, summed per (row, segment), then over the
+ *                       segments and rows in a fixed order by a second kernel: no floating-point atomics, the same calls give the same
+ *                       bits.  A NaN probability (or one outside [0, 1]) in a valid frame makes the loss NaN.
+ * Workspace: uvad_score_ws_bytes(ctx, B, T) bytes (0 on a bad argument or before uvad_score_configure).  After a step its first 16 bytes
+ *   hold {double loss sum, uint64 valid frames} of THAT step (what test_step returns as the batch loss, without a copy to the host).
+ * uvad_score_totals writes UVAD_SCORE_TOTALS_WORDS uint64 words to d_out (device memory, for the host to copy):
+ *   [0] n_points  [1] bins  [2] valid frames  [3] the loss sum, the bits of a double  [4] steps  [5 .. 7] 0
+ *   [8 + 4 m + k] k = 0 .. 3: tp, fp, tn, fn of point m (m < 8)
+ *   [40 + 1024 cls + j] hist[cls][j], j < bins
+ * Refusals (nothing enqueued).  UVAD_E_ARG: n_points outside 1 .. 8; kernel even, < 1 or > 255; threshold not finite; collar < 0 or
+ *   > 1024; bins not a power of two in 2 .. 1024; segment < 0 or > 16384; NULL d_probs / d_gt / d_state / d_ws / d_out; B < 1; T < 1 or
+ *   > 2^30; ld_p < T or ld_gt < T; state_bytes below uvad_score_state_bytes or ws_bytes below uvad_score_ws_bytes.  UVAD_E_STATE: no
+ *   uvad_score_configure yet; a state that was never reset, or reset under another n_points / bins. */
+#define UVAD_SCORE_MAX_POINTS 8
+#define UVAD_SCORE_TOTALS_WORDS 2088
+typedef struct {
+    int n_points;                            /* 1 .. 8 */
+    float threshold[UVAD_SCORE_MAX_POINTS];  /* speech iff !(p < threshold) */
+    int kernel[UVAD_SCORE_MAX_POINTS];       /* odd median taps, 1 .. 255 (1: the raw threshold, what validation_step scores) */
+    int collar;                              /* frames left unscored on each side of a reference boundary, 0 .. 1024 */
+    int bins;                                /* histogram bins, a power of two, 2 .. 1024 */
+    int segment;                             /* frames per workgroup, 0 = default */
+} uvad_score_cfg;
+int uvad_intervals_to_labels(uvad_ctx *, const int32_t *d_iv, const int32_t *d_iv_counts, int B, int max_iv, int T, int ld,
+                             const int32_t *d_lens, uint8_t *d_labels, void *stream);
+int uvad_score_configure(uvad_ctx *, const uvad_score_cfg *);
+size_t uvad_score_state_bytes(const uvad_ctx *);   /* 0 before uvad_score_configure */
+size_t uvad_score_ws_bytes(const uvad_ctx *, int B, int T);
+int uvad_score_reset(uvad_ctx *, void *d_state, size_t state_bytes, void *stream);
+int uvad_score_step(uvad_ctx *, const float *d_probs, int ld_p, const uint8_t *d_gt, int ld_gt, int B, int T, const int32_t *d_lens,
+                    void *d_state, size_t state_bytes, uint64_t *d_rows, void *d_ws, size_t ws_bytes, void *stream);
+int uvad_score_totals(uvad_ctx *, const void *d_state, size_t state_bytes, uint64_t *d_out, void *stream);
+
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;
  *   1  (default) f32-accurate on the f16 matrix cores: weights scaled by a power of two and split on the host into THREE

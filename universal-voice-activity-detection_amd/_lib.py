@@ -39,6 +39,15 @@ class EndpointCfg(C.Structure):
     _fields_ = [("kernel", C.c_int), ("pad", C.c_int), ("threshold", C.c_float)]
 
 
+SCORE_MAX_POINTS = 8
+SCORE_TOTALS_WORDS = 2088        # uint64 words uvad_score_totals writes (include/uvad.h gives the layout)
+
+
+class ScoreCfg(C.Structure):
+    _fields_ = [("n_points", C.c_int), ("threshold", C.c_float * SCORE_MAX_POINTS), ("kernel", C.c_int * SCORE_MAX_POINTS),
+                ("collar", C.c_int), ("bins", C.c_int), ("segment", C.c_int)]
+
+
 class UvadError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{ERR_NAMES.get(code, code)}: {msg}")
@@ -134,6 +143,15 @@ SIGNATURES = {
     "uvad_endpoint_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(EndpointCfg), C.c_void_p]),
     "uvad_endpoint_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "uvad_intervals_to_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "uvad_score_configure": (C.c_int, [C.c_void_p, C.POINTER(ScoreCfg)]),
+    "uvad_score_state_bytes": (C.c_size_t, [C.c_void_p]),
+    "uvad_score_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "uvad_score_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_score_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_score_totals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "uvad_classify_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_forward_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -178,7 +196,7 @@ _lib = None
 
 def bind(lib):
     """Declare every prototype of SIGNATURES on `lib`.  The ABI number did not move when entries were appended (the ingest stage among
-    them, and the endpointer after it), so a library built from an older tree passes the version check: a symbol it lacks is a loud error here, by name."""
+    them, the endpointer and the scoring stage after it), so a library built from an older tree passes the version check: a symbol it lacks is a loud error here, by name."""
     for name, (res, args) in SIGNATURES.items():
         try:
             fn = getattr(lib, name)

@@ -21,7 +21,7 @@ def load_config() -> ConfigDict:
     cfg = ConfigDict()
 
     cfg.task = "run"            # only "run" is in scope (reference: wer/download/prepare/... are data plumbing)
-    cfg.function = "predict"    # only "predict" is in scope
+    cfg.function = "predict"    # "predict" | "test" (scoring against label files: input.labels)
 
     cfg.seed = 42
     cfg.device = "gpu"          # the HIP path needs a GPU; "cpu" raises (no fallback)
@@ -72,6 +72,7 @@ def load_config() -> ConfigDict:
     cfg.input.kind = "synthetic"      # "synthetic" | "wav"
     cfg.input.paths = []              # wav files when kind == "wav": 16 kHz 16-bit as they are; other rates, G.711 (A-law / mu-law) and
                                       # multi-channel files through the ingest stage (decode, channels to rows, resampling to 16 kHz)
+    cfg.input.labels = []             # function == "test": one label file per path, `start<TAB>end<TAB>LABEL` lines (get_audacity_labels)
     cfg.input.channels = "first"      # "first": channel 0 only (the reference's to_mono(mono_downmix=False)[0]); "all": every channel a
                                       # recording of its own, "-ch<N>" appended to its id
     cfg.input.num_utterances = 1

@@ -93,6 +93,8 @@ struct WavWindowGroup { int64_t n_samples = 0, n_frames = 0, n_steps = 0; int B 
 struct SlotPool { int B = 0, chunk = 0, W = 0, L = 0, is_i16 = 0; };
 // an endpointer state (uvad_endpoint_*): what reset fixed; the device header holds the same and every per-slot quantity
 struct EndpointPool { int B = 0, kernel = 0, pad = 0; float threshold = 0.5f; };
+// a scoring state (uvad_score_*): the configuration's n_points and bins at its reset (the device header holds the same)
+struct ScoreState { int n_points = 0, bins = 0; };
 
 struct uvad_ctx {
     std::map<void *, StreamCounters> streams;   // host mirror of the lock-step stream groups, keyed by d_state
@@ -100,6 +102,9 @@ struct uvad_ctx {
     std::map<void *, WavWindowGroup> wav_windows;   // ... and of the waveform model's windowed stream groups (uvad_window_wav_*)
     std::map<void *, SlotPool> slot_pools, wav_slot_pools;   // ... and of the slot pools of both window families (uvad_window_*slots_*)
     std::map<void *, EndpointPool> endpoints;   // ... and of the endpointer states (uvad_endpoint_*)
+    std::map<void *, ScoreState> scores;        // ... and of the scoring states (uvad_score_*)
+    bool has_score = false;                     // uvad_score_configure: operating points, collar, bins, segment (0 replaced by the default)
+    uvad_score_cfg sq{};
     int device = 0, n_cu = 256;
     bool has_fb = false, has_model = false, finalized = false, tables_set = false;
     uvad_fbank_cfg fb{};
@@ -2953,6 +2958,101 @@ int uvad_endpoint_step(uvad_ctx *c, const float *d_probs, int ld_in, const int32
     a.labels = d_labels; a.ld_lab = ld_lab; a.lab_counts = d_lab_counts;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, launch_endpoint_step(a, g.kernel, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+// ---- scoring against reference labels (score.hip) --------------------------------------------------------------------------------------
+int uvad_intervals_to_labels(uvad_ctx *c, const int32_t *d_iv, const int32_t *d_iv_counts, int B, int max_iv, int T, int ld,
+                             const int32_t *d_lens, uint8_t *d_labels, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_iv_counts || !d_labels || B < 1 || T < 1 || T > SC_MAX_T || max_iv < 0 || (max_iv > 0 && !d_iv))
+        return fail(c, UVAD_E_ARG, "uvad_intervals_to_labels: bad argument");
+    if (ld < T) return fail(c, UVAD_E_ARG, "uvad_intervals_to_labels: ld must be at least T");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_intervals_to_labels(d_iv, d_iv_counts, B, max_iv, T, ld, d_lens, d_labels, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_score_configure(uvad_ctx *c, const uvad_score_cfg *q) {
+    if (!c) return UVAD_E_ARG;
+    if (!q) return fail(c, UVAD_E_ARG, "uvad_score_configure: bad argument");
+    if (q->n_points < 1 || q->n_points > SC_MAX_POINTS) return fail(c, UVAD_E_ARG, "uvad_score_configure: n_points must lie in 1 .. 8");
+    for (int m = 0; m < q->n_points; ++m) {
+        if (q->kernel[m] < 1 || q->kernel[m] > 255 || q->kernel[m] % 2 == 0)
+            return fail(c, UVAD_E_ARG, "uvad_score_configure: kernel must be odd, 1 .. 255");
+        if (!std::isfinite(q->threshold[m])) return fail(c, UVAD_E_ARG, "uvad_score_configure: threshold must be finite");
+    }
+    if (q->collar < 0 || q->collar > SC_MAX_COLLAR) return fail(c, UVAD_E_ARG, "uvad_score_configure: collar must lie in [0, 1024] frames");
+    if (q->bins < 2 || q->bins > SC_MAX_BINS || (q->bins & (q->bins - 1)))
+        return fail(c, UVAD_E_ARG, "uvad_score_configure: bins must be a power of two, 2 .. 1024");
+    if (q->segment < 0 || q->segment > SC_MAX_SEGMENT) return fail(c, UVAD_E_ARG, "uvad_score_configure: segment must lie in [0, 16384] frames");
+    c->sq = *q;
+    if (c->sq.segment == 0) c->sq.segment = SC_DEFAULT_SEGMENT;
+    c->has_score = true;
+    return UVAD_OK;
+}
+
+size_t uvad_score_state_bytes(const uvad_ctx *c) { return c && c->has_score ? score_state_bytes() : 0; }
+
+size_t uvad_score_ws_bytes(const uvad_ctx *c, int B, int T) {
+    if (!c || !c->has_score || B < 1 || T < 1 || T > SC_MAX_T) return 0;
+    return score_ws_bytes(B, T, c->sq.segment);
+}
+
+int uvad_score_reset(uvad_ctx *c, void *d_state, size_t state_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_state) return fail(c, UVAD_E_ARG, "uvad_score_reset: bad argument");
+    if (!c->has_score) return fail(c, UVAD_E_STATE, "uvad_score_reset: call uvad_score_configure first");
+    if (state_bytes < score_state_bytes())
+        return fail(c, UVAD_E_ARG, "uvad_score_reset: state too small: need " + std::to_string(score_state_bytes()) + " bytes");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_score_reset(d_state, c->sq.n_points, c->sq.bins, (hipStream_t)stream));
+    ScoreState g;
+    g.n_points = c->sq.n_points; g.bins = c->sq.bins;
+    c->scores[d_state] = g;
+    return UVAD_OK;
+}
+
+int uvad_score_step(uvad_ctx *c, const float *d_probs, int ld_p, const uint8_t *d_gt, int ld_gt, int B, int T, const int32_t *d_lens,
+                    void *d_state, size_t state_bytes, uint64_t *d_rows, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_probs || !d_gt || !d_state || !d_ws || B < 1 || T < 1 || T > SC_MAX_T) return fail(c, UVAD_E_ARG, "uvad_score_step: bad argument");
+    if (ld_p < T || ld_gt < T) return fail(c, UVAD_E_ARG, "uvad_score_step: ld_p and ld_gt must be at least T");
+    if (!c->has_score) return fail(c, UVAD_E_STATE, "uvad_score_step: call uvad_score_configure first");
+    if (state_bytes < score_state_bytes())
+        return fail(c, UVAD_E_ARG, "uvad_score_step: state too small: need " + std::to_string(score_state_bytes()) + " bytes");
+    const uvad_score_cfg &q = c->sq;
+    const size_t need = score_ws_bytes(B, T, q.segment);
+    if (ws_bytes < need) return fail(c, UVAD_E_ARG, "uvad_score_step: workspace too small: need " + std::to_string(need) + " bytes");
+    if ((long long)B * score_nseg(T, q.segment) > 0x7fffffffll) return fail(c, UVAD_E_ARG, "uvad_score_step: B x segments above 2^31 - 1");
+    auto it = c->scores.find(d_state);
+    if (it == c->scores.end()) return fail(c, UVAD_E_STATE, "uvad_score_step: call uvad_score_reset on this state first");
+    if (it->second.n_points != q.n_points || it->second.bins != q.bins)
+        return fail(c, UVAD_E_STATE, "uvad_score_step: the state was reset under another n_points / bins");
+    ScoreArgs a{};
+    a.probs = d_probs; a.ld_p = ld_p; a.gt = d_gt; a.ld_gt = ld_gt; a.B = B; a.T = T; a.lens = d_lens;
+    a.state = d_state; a.rows = reinterpret_cast<unsigned long long *>(d_rows); a.ws = d_ws;
+    a.n_points = q.n_points; a.collar = q.collar; a.bins = q.bins; a.seg = q.segment; a.nseg = score_nseg(T, q.segment);
+    a.halo = q.collar;
+    for (int m = 0; m < q.n_points; ++m) {
+        a.thr[m] = q.threshold[m];
+        a.half[m] = q.kernel[m] / 2;
+        a.halo = std::max(a.halo, a.half[m]);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_score_step(a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_score_totals(uvad_ctx *c, const void *d_state, size_t state_bytes, uint64_t *d_out, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_state || !d_out) return fail(c, UVAD_E_ARG, "uvad_score_totals: bad argument");
+    if (state_bytes < score_state_bytes())
+        return fail(c, UVAD_E_ARG, "uvad_score_totals: state too small: need " + std::to_string(score_state_bytes()) + " bytes");
+    if (c->scores.find(const_cast<void *>(d_state)) == c->scores.end())
+        return fail(c, UVAD_E_STATE, "uvad_score_totals: call uvad_score_reset on this state first");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_score_totals(d_state, reinterpret_cast<unsigned long long *>(d_out), (hipStream_t)stream));
     return UVAD_OK;
 }
 

@@ -522,4 +522,30 @@ size_t endpoint_state_bytes(int B);
 hipError_t launch_endpoint_reset(void *state, int B, int kernel, int pad, float threshold, hipStream_t s);
 hipError_t launch_endpoint_step(const EndpointArgs &a, int kernel, hipStream_t s);   // kernel: the reset's, for the LDS size only
 
+// ---- score.hip: scoring against reference labels (uvad_score_*, uvad_intervals_to_labels, include/uvad.h) ---------------------------------
+// The state is a 256-byte header followed by the record uvad_score_totals copies out (SC_* word offsets, include/uvad.h).  The workspace
+// is a 32-byte head (this step's loss sum and valid frames) followed by one ScorePartial per (row, segment).
+constexpr int SC_MAX_POINTS = 8, SC_MAX_BINS = 1024, SC_MAX_COLLAR = 1024, SC_MAX_SEGMENT = 1 << 14, SC_DEFAULT_SEGMENT = 2048;
+constexpr int SC_MAX_T = 1 << 30;                     // frame arithmetic stays in int32 with a segment and two halos on top
+constexpr unsigned SC_MAGIC = 0x55565343u;            // "UVSC"
+constexpr int SC_W_POINTS = 0, SC_W_BINS = 1, SC_W_VALID = 2, SC_W_LOSS = 3, SC_W_STEPS = 4, SC_W_COUNTS = 8, SC_W_HIST = 40;
+constexpr int SC_RECORD_WORDS = SC_W_HIST + 2 * SC_MAX_BINS;   // == UVAD_SCORE_TOTALS_WORDS
+struct ScoreHeader { unsigned magic; int n_points, bins, reserved[61]; };   // 256 bytes
+struct ScoreWsHead { double loss; unsigned long long valid; unsigned long long reserved[2]; };
+struct ScorePartial { double loss; unsigned tp, fp, tn, fn; unsigned reserved[2]; };   // point 0's counts and the loss of one (row, segment)
+struct ScoreArgs {
+    const float *probs; int ld_p; const uint8_t *gt; int ld_gt; int B, T; const int *lens;
+    void *state; unsigned long long *rows; void *ws;
+    int n_points; float thr[SC_MAX_POINTS]; int half[SC_MAX_POINTS];
+    int collar, bins, seg, halo, nseg;
+};
+constexpr size_t score_state_bytes() { return sizeof(ScoreHeader) + (size_t)SC_RECORD_WORDS * sizeof(unsigned long long); }
+constexpr int score_nseg(int T, int seg) { return (T + seg - 1) / seg; }
+constexpr size_t score_ws_bytes(int B, int T, int seg) { return sizeof(ScoreWsHead) + (size_t)B * score_nseg(T, seg) * sizeof(ScorePartial); }
+hipError_t launch_score_reset(void *state, int n_points, int bins, hipStream_t s);
+hipError_t launch_score_step(const ScoreArgs &a, hipStream_t s);
+hipError_t launch_score_totals(const void *state, unsigned long long *out, hipStream_t s);
+hipError_t launch_intervals_to_labels(const int *iv, const int *iv_counts, int B, int max_iv, int T, int ld, const int *lens, uint8_t *labels,
+                                      hipStream_t s);
+
 }  // namespace uvad

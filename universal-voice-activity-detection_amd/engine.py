@@ -1,13 +1,14 @@
 """Host-side mirror of ``src.engines.vad_engine.VadModel`` (reference vad_engine.py:20-281),
-inference surface only: constructor arguments, ``.model`` / ``.model_name``, ``forward``,
-``predict_step``, ``_common_step`` and ``load_from_checkpoint`` keep their names, argument
-meaning and return shapes.  Training (``training_step``, torchmetrics, Adam) is outside the
-accelerated path and raises."""
+inference and scoring surface: constructor arguments, ``.model`` / ``.model_name``, ``forward``,
+``predict_step``, ``test_step``, ``validation_step``, ``_common_step`` and ``load_from_checkpoint``
+keep their names, argument meaning and return shapes; what the reference logs through torchmetrics
+is accumulated on the device (``uvad_score_*``) and read with ``test_metrics`` / ``validation_metrics``.
+Training (``training_step``, Adam) is outside the accelerated path and raises."""
 import torch
 import torch.nn as nn
 
 from .models import PyanNet, PyanNet2
-from .postprocess import median_filter
+from .postprocess import median_filter, median_window, score_metrics
 
 
 class VadModel(nn.Module):
@@ -18,19 +19,22 @@ class VadModel(nn.Module):
         self.model = PyanNet(**model_dict) if model_name == "PyanNet" else PyanNet2(**model_dict)
         self.model.build()
         self.learning_rate = learning_rate
+        self._scorers = {}   # "test" / "val" -> (runtime, scoring state)
 
     # -- inference ---------------------------------------------------------------------------
     def forward(self, audio_feats: torch.Tensor) -> torch.Tensor:
         return self.model(audio_feats)
 
-    def _common_step(self, batch, batch_idx):
+    def _common_step(self, batch, batch_idx, loss: bool = True):
         """vad_engine.py:247-278.  The reference also evaluates BCE against ``batch["is_voice"]``
-        here (its value is unused by predict); it is computed only when labels are present."""
+        here (its value is unused by predict); it is computed only when labels are present.
+        loss=False (test_step / validation_step) leaves the loss to the scoring stage, which sums it on the device:
+        the NaN check below costs a synchronisation per batch."""
         x = batch["inputs"]
         y_pred = self.model(x.unsqueeze(1)) if self.model_name == "PyanNet" else self.model(x)
         y = batch.get("is_voice")
-        loss = None
-        if y is not None:
+        want_loss, loss = loss, None
+        if y is not None and want_loss:
             loss = nn.functional.binary_cross_entropy(y_pred.squeeze(-1), y.to(y_pred.device, y_pred.dtype))
             if torch.isnan(loss):
                 return None
@@ -65,8 +69,53 @@ class VadModel(nn.Module):
             raise RuntimeError(f"checkpoint is missing tensors: {missing[:4]}{'...' if len(missing) > 4 else ''}")
         return obj
 
+    # -- scoring (vad_engine.py:128-202) ---------------------------------------------------------
+    def _score_step(self, which, batch, batch_idx):
+        _, y_pred, y = self._common_step(batch, batch_idx, loss=False)
+        if y is None:
+            raise ValueError(f'{which}_step needs batch["is_voice"]')
+        probs = y_pred.squeeze(-1)
+        rt = self.model.runtime(probs.device)
+        held = self._scorers.get(which)
+        if held is None or held[0] is not rt:
+            window = 0.02 if self.model.encoding_dim == 768 else 0.01
+            kernel = median_window(window) if which == "test" else 1    # test_step scores the median-filtered labels, validation_step the raw threshold
+            held = self._scorers[which] = (rt, rt.score_open(points=[(0.5, kernel)]))
+        gt = (y.to(probs.device) != 0).to(torch.uint8).reshape(probs.shape)
+        rt.score_step(held[1], probs, gt, lengths=batch.get("lengths"))
+        return rt.score_batch_loss(held[1])
+
+    def test_step(self, batch, batch_idx=0):
+        """vad_engine.py:167-202: the batch's probabilities against batch["is_voice"] at threshold 0.5 behind the reference's median window,
+        accumulated on the device (one uvad_score_step, no copy to the host).  Returns the batch's mean loss as a 0-d tensor on the device
+        without synchronising; where the reference's _common_step returns None for a NaN loss, the tensor is NaN.  batch["lengths"]
+        (optional): valid frames per row."""
+        return self._score_step("test", batch, batch_idx)
+
+    def validation_step(self, batch, batch_idx=0):
+        """vad_engine.py:128-165: as test_step without the median filter (kernel 1)."""
+        return self._score_step("val", batch, batch_idx)
+
+    def _metrics(self, which, reset):
+        held = self._scorers.get(which)
+        if held is None:
+            raise RuntimeError(f"no {which}_step has run yet")
+        rt, sc = held
+        out = score_metrics(rt.score_read(sc), prefix=which)
+        if reset:
+            rt.score_reset(sc)
+        return out
+
+    def test_metrics(self, reset: bool = True) -> dict:
+        """The reference's test_* names over every test_step since the last reset (postprocess.score_metrics: pooled, not Lightning's
+        batch-weighted mean)."""
+        return self._metrics("test", reset)
+
+    def validation_metrics(self, reset: bool = True) -> dict:
+        return self._metrics("val", reset)
+
     # -- training is out of scope --------------------------------------------------------------
     def training_step(self, *a, **k):
         raise NotImplementedError("training is outside the accelerated inference path (SURVEY.md section 2, rows 6/12)")
 
-    validation_step = test_step = configure_optimizers = training_step
+    configure_optimizers = training_step

@@ -1,7 +1,8 @@
 """Post-processing next to the hot path: the reference's ``median_filter``
 (src/utils/helper.py:66-97) and the run-length interval extraction of ``get_new_cuts``
 (src/scripts/predict.py:472-490).  The filter runs on the GPU (``uvad_median_filter``) instead of
-the reference's device -> CPU -> scipy -> "cuda" round trip; the interval walk is vectorised."""
+the reference's device -> CPU -> scipy -> "cuda" round trip; the interval walk is vectorised.  The scoring side
+(``supervision_frames``, ``score_metrics``, ``det_curve``) is the host half of ``uvad_score_*``."""
 from typing import List, Tuple
 
 import numpy as np
@@ -222,3 +223,97 @@ def detection_error(pred_labels: torch.Tensor, gt_labels: torch.Tensor, runtime=
     n = float(pred_labels.shape[1])
     fa, md = counts[:, 0] / n, counts[:, 1] / n
     return {"false_alarm": fa, "missed_detection": md, "detection_error_rate": fa + md}
+
+
+# ---- scoring against reference labels (uvad_score_*, uvad_intervals_to_labels) ----------------------------------
+
+def supervision_frames(intervals_s, duration: float, frame_shift: float = 0.01, geometry: str = "fbank", num_frames=None) -> np.ndarray:
+    """Reference intervals in seconds -> the (n, 2) int32 {start, end} frame table VadRuntime.intervals_to_labels rasterises, with the
+    reference's own rounding:
+      "fbank"    int(s / shift), int(e / shift) over ceil(duration / shift) frames (get_binary_tensor, predict.py:654-663);
+      "sincnet"  supervisions_feature_mask (src/datasets/custom_vad.py:41-75): (round(s * 16000) - SINC_HALF) // 270, with start 0 when
+                 s <= 0 and end num_frames when e >= duration (num_frames is required).  SINC_HALF is what the reference's code
+                 computes, round(0.5 * 991) = 496; its comment says 495.
+    One deviation: a negative index is clamped to 0.  The reference lets numpy wrap it, which silently drops a supervision that starts
+    in the first 31 ms.  Ends past the row are cut by the rasteriser (as the reference's slice is)."""
+    out = np.zeros((len(intervals_s), 2), np.int32)
+    if geometry == "fbank":
+        for i, (s, e) in enumerate(intervals_s):
+            out[i] = max(int(s / frame_shift), 0), max(int(e / frame_shift), 0)
+    elif geometry == "sincnet":
+        if num_frames is None:
+            raise ValueError("geometry 'sincnet' needs num_frames")
+        for i, (s, e) in enumerate(intervals_s):
+            st = int((round(s * 16000) - SINC_HALF) // SINC_STEP) if s > 0 else 0
+            et = int((round(e * 16000) - SINC_HALF) // SINC_STEP) if e < duration else int(num_frames)
+            out[i] = max(st, 0), max(et, 0)
+    else:
+        raise ValueError(f"unknown geometry {geometry!r} (fbank, sincnet)")
+    return out
+
+
+def _ratio(a, b) -> float:
+    return float(a) / float(b) if b else 0.0
+
+
+def score_metrics(read: dict, prefix: str = "test", point: int = 0) -> dict:
+    """VadRuntime.score_read's dict -> what test_step / validation_step log (vad_engine.py:128-202), under the reference's names:
+    {prefix}_detection_error_rate, _false_alarm, _missed_detection, _acc, _precision, _recall, _f1_score, _denominator, _loss, at
+    operating point `point`.  The values are POOLED over everything accumulated: counts over the scored frames, the loss sum over the
+    valid frames.  Lightning instead averages the per-batch values weighted by batch_size=80; for equal-size batches without padding
+    the two coincide.  A ratio with a zero denominator is 0 (as torchmetrics); the loss of zero frames is NaN."""
+    tp, fp, tn, fn = (int(v) for v in read["counts"][point])
+    den = tp + fp + tn + fn
+    valid = int(read["valid"])
+    return {f"{prefix}_detection_error_rate": _ratio(fp + fn, den),
+            f"{prefix}_false_alarm": _ratio(fp, den),
+            f"{prefix}_missed_detection": _ratio(fn, den),
+            f"{prefix}_acc": _ratio(tp + tn, den),
+            f"{prefix}_precision": _ratio(tp, tp + fp),
+            f"{prefix}_recall": _ratio(tp, tp + fn),
+            f"{prefix}_f1_score": _ratio(2 * tp, 2 * tp + fp + fn),
+            f"{prefix}_denominator": float(den),
+            f"{prefix}_loss": float(read["loss_sum"]) / valid if valid else float("nan")}
+
+
+def det_curve(read: dict) -> dict:
+    """The threshold sweep of a scoring state: with hist[class][bin] of the raw probabilities, at threshold j / bins (j = 0 .. bins, K = 1)
+    the false-alarm frames are the sum of hist[0] over bins >= j and the missed frames the sum of hist[1] over bins < j, exactly, for j < bins; the last entry, j = bins, stands for a threshold above every
+    probability (nothing is speech: p = 1 and NaN sit in the last bin).
+    -> thresholds (bins + 1,), fa_frames, md_frames (int64), false_alarm_rate = fa / non-speech frames, missed_detection_rate = md / speech
+    frames (0 where the class is empty), eer and eer_threshold (where the two rates cross, linearly interpolated), best_threshold and
+    best_detection_error_rate (the minimum of (fa + md) / scored frames; the lowest threshold on ties)."""
+    hist = np.asarray(read["hist"], np.int64)
+    bins = hist.shape[1]
+    neg, pos = int(hist[0].sum()), int(hist[1].sum())
+    fa = np.concatenate((np.cumsum(hist[0][::-1])[::-1], [0])).astype(np.int64)
+    md = np.concatenate(([0], np.cumsum(hist[1]))).astype(np.int64)
+    thr = np.arange(bins + 1, dtype=np.float64) / bins
+    far = fa / neg if neg else np.zeros(bins + 1)
+    mdr = md / pos if pos else np.zeros(bins + 1)
+    d = far - mdr                                   # non-increasing in j
+    j = int(np.argmax(d <= 0)) if (d <= 0).any() else bins
+    if j == 0 or d[j] == 0 or d[j] > 0:
+        eer, eer_thr = 0.5 * (far[j] + mdr[j]), thr[j]
+    else:
+        w = d[j - 1] / (d[j - 1] - d[j])
+        eer, eer_thr = far[j - 1] + w * (far[j] - far[j - 1]), thr[j - 1] + w * (thr[j] - thr[j - 1])
+    best = int(np.argmin(fa + md))
+    return {"thresholds": thr, "fa_frames": fa, "md_frames": md, "false_alarm_rate": far, "missed_detection_rate": mdr,
+            "eer": float(eer), "eer_threshold": float(eer_thr), "best_threshold": float(thr[best]),
+            "best_detection_error_rate": _ratio(fa[best] + md[best], neg + pos)}
+
+
+def read_label_file(path: str):
+    """A label file in the text form the reference's get_audacity_labels writes (helper.py:135-151), one `start<TAB>end<TAB>LABEL` line
+    per speech interval -> [(start_s, end_s)]; blank lines are skipped."""
+    out = []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            parts = line.split()
+            if not parts:
+                continue
+            if len(parts) < 2:
+                raise ValueError(f"{path}:{ln}: expected `start<TAB>end<TAB>LABEL`")
+            out.append((float(parts[0]), float(parts[1])))
+    return out

@@ -882,6 +882,116 @@ class VadRuntime:
             self._check(self._endpoint_enqueue(ep, probs.data_ptr(), counts.contiguous().data_ptr(), flags.data_ptr() if flags is not None else None))
             return ep["events"], ep["ev_counts"], ep["active"]
 
+    # ------------------------------------------------------------------ scoring against reference labels (uvad_score_*)
+    def score_open(self, points=((0.5, 25),), collar: int = 0, bins: int = 256, segment: int = 0):
+        """Allocate and reset a scoring state (uvad_score_reset): points [(threshold, odd median kernel)], 1 .. 8 of them; collar frames
+        left unscored around every reference boundary; bins of the threshold sweep (a power of two); segment: frames per workgroup
+        (0 = the library's default; no output depends on it)."""
+        points = [(float(t), int(k)) for t, k in points]
+        if not 1 <= len(points) <= _lib.SCORE_MAX_POINTS:
+            raise ValueError(f"need 1 .. {_lib.SCORE_MAX_POINTS} operating points, got {len(points)}")
+        cfg = _lib.ScoreCfg()
+        cfg.n_points, cfg.collar, cfg.bins, cfg.segment = len(points), int(collar), int(bins), int(segment)
+        for m, (t, k) in enumerate(points):
+            cfg.threshold[m], cfg.kernel[m] = t, k
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_score_configure(self.ctx, C.byref(cfg)))
+            nbytes = int(self.lib.uvad_score_state_bytes(self.ctx))
+            sc = {"cfg": cfg, "points": points, "collar": int(collar), "bins": int(bins),
+                  "state": torch.empty(nbytes, dtype=torch.uint8, device=self.device), "ws": None, "rows": None,
+                  "totals": torch.zeros(_lib.SCORE_TOTALS_WORDS, dtype=torch.int64, device=self.device)}
+            self.score_reset(sc)
+            return sc
+
+    def score_reset(self, sc):
+        """Empty the accumulated totals (uvad_score_reset)."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_score_configure(self.ctx, C.byref(sc["cfg"])))   # host only: the context serves any number of scorers
+            self._check(self.lib.uvad_score_reset(self.ctx, sc["state"].data_ptr(), sc["state"].numel(), self._stream()))
+
+    @staticmethod
+    def _rows_2d(t, dtype, name):
+        if t.dim() != 2 or t.dtype != dtype or (t.shape[1] > 1 and t.stride(1) != 1) or t.stride(0) < t.shape[1]:
+            raise ValueError(f"{name} must be a (B, T) {dtype} tensor with contiguous rows")
+        return t
+
+    def score_step(self, sc, probs: "torch.Tensor", gt: "torch.Tensor", lengths=None, rows: bool = False):
+        """Accumulate one batch (uvad_score_step): probs (B, T) f32 and gt (B, T) uint8 (non-zero = speech) on the GPU -- row-strided views
+        are used as they are -- and lengths (B,) valid frames per row (a device int32 tensor is read on the device).  No copy to the host
+        and no synchronisation: once the workspace has the size of the batch shape (the first call with it allocates), the call can be
+        captured into a graph.  rows=True returns this step's (B, 4) int64 {tp, fp, tn, fn} of operating point 0, on the device and
+        overwritten by the next such step.  score_batch_loss gives the step's mean loss."""
+        with torch.cuda.device(self.device):
+            for t, name in ((probs, "probs"), (gt, "gt")):
+                if not torch.is_tensor(t) or t.device != self.device:
+                    raise RuntimeError(f"{name} must be a tensor on {self.device}")
+            probs = self._rows_2d(probs, torch.float32, "probs")
+            gt = self._rows_2d(gt, torch.uint8, "gt")
+            B, T = probs.shape
+            if tuple(gt.shape) != (B, T):
+                raise ValueError(f"gt {tuple(gt.shape)} does not match probs {(B, T)}")
+            n = None if lengths is None else self._dev_lens(lengths, B, T, torch.int32, "lengths (frames)")
+            self._check(self.lib.uvad_score_configure(self.ctx, C.byref(sc["cfg"])))
+            need = int(self.lib.uvad_score_ws_bytes(self.ctx, B, T))
+            if sc["ws"] is None or sc["ws"].numel() < need:
+                sc["ws"] = torch.zeros(max(need, 32), dtype=torch.uint8, device=self.device)
+            out = None
+            if rows:
+                if sc["rows"] is None or sc["rows"].shape[0] < B:
+                    sc["rows"] = torch.zeros((B, 4), dtype=torch.int64, device=self.device)
+                out = sc["rows"][:B]
+            self._check(self.lib.uvad_score_step(self.ctx, probs.data_ptr(), probs.stride(0), gt.data_ptr(), gt.stride(0), B, T,
+                                                 n.data_ptr() if n is not None else None, sc["state"].data_ptr(), sc["state"].numel(),
+                                                 out.data_ptr() if out is not None else None, sc["ws"].data_ptr(), sc["ws"].numel(),
+                                                 self._stream()))
+            sc["_keep"] = (probs, gt, n)   # the launch reads them after this call returns
+            return out
+
+    def score_batch_loss(self, sc) -> "torch.Tensor":
+        """The most recent step's mean binary cross-entropy over its valid frames as a 0-d f64 tensor on the device (NaN when a valid
+        probability is NaN, or when the step had no valid frame): what test_step returns, without a synchronisation."""
+        head = sc["ws"][:16]
+        return head[:8].view(torch.float64)[0] / head[8:].view(torch.int64)[0].to(torch.float64)
+
+    def score_read(self, sc) -> dict:
+        """Copy the accumulated totals to the host (uvad_score_totals; synchronises) -> {"points", "collar", "bins", "counts" (n_points, 4)
+        int64 {tp, fp, tn, fn} pooled over the scored frames, "hist" (2, bins) int64 [class][bin], "loss_sum" float, "valid" frames,
+        "steps"}: what postprocess.score_metrics and det_curve take."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_score_totals(self.ctx, sc["state"].data_ptr(), sc["state"].numel(), sc["totals"].data_ptr(), self._stream()))
+            w = sc["totals"].cpu().numpy()
+        npts, bins = int(w[0]), int(w[1])
+        return {"points": list(sc["points"]), "collar": sc["collar"], "bins": bins,
+                "counts": w[8:8 + 4 * npts].reshape(npts, 4).copy(),
+                "hist": np.stack([w[40:40 + bins], w[40 + 1024:40 + 1024 + bins]]).copy(),
+                "loss_sum": float(w[3:4].view(np.float64)[0]), "valid": int(w[2]), "steps": int(w[4])}
+
+    def intervals_to_labels(self, intervals, counts, T: int, lengths=None, out=None) -> "torch.Tensor":
+        """Reference intervals -> label rows on the device (uvad_intervals_to_labels): intervals (B, max_iv, 2) int32 {start, end} frames and
+        counts (B,) int32, tensors on the GPU or anything numpy converts; lengths (B,) valid frames per row.  -> (B, T) uint8, 1 on the
+        union of the row's intervals inside [0, len), 0 elsewhere on it.  out: a (B, >= T) uint8 tensor with contiguous rows to write
+        into -- its bytes at or past each row's length are left as they are; without it a zeroed tensor is made."""
+        with torch.cuda.device(self.device):
+            iv = intervals if torch.is_tensor(intervals) else torch.from_numpy(np.ascontiguousarray(intervals, np.int32))
+            iv = iv.to(self.device, torch.int32).contiguous()
+            if iv.dim() != 3 or iv.shape[2] != 2:
+                raise ValueError(f"intervals must be (B, max_iv, 2), got {tuple(iv.shape)}")
+            B, max_iv = int(iv.shape[0]), int(iv.shape[1])
+            cn = counts if torch.is_tensor(counts) else torch.from_numpy(np.ascontiguousarray(counts, np.int32))
+            cn = cn.to(self.device, torch.int32).contiguous()
+            if tuple(cn.shape) != (B,):
+                raise ValueError(f"counts must be ({B},), got {tuple(cn.shape)}")
+            if out is None:
+                out = torch.zeros((B, T), dtype=torch.uint8, device=self.device)
+            elif not torch.is_tensor(out) or out.device != self.device or out.shape[0] != B:
+                raise ValueError(f"out must be a ({B}, >= {T}) uint8 tensor on {self.device}")
+            out = self._rows_2d(out, torch.uint8, "out")
+            n = None if lengths is None else self._dev_lens(lengths, B, T, torch.int32, "lengths (frames)")
+            self._check(self.lib.uvad_intervals_to_labels(self.ctx, iv.data_ptr() if max_iv else None, cn.data_ptr(), B, max_iv, int(T),
+                                                          out.stride(0), n.data_ptr() if n is not None else None, out.data_ptr(),
+                                                          self._stream()))
+            return out[:, :T]
+
     # ------------------------------------------------------------------ sliding windows over whole recordings (uvad_sliding_*)
     def sliding_configure(self, window: int, hop: int, weights=None):
         """Window and hop in frames and the aggregation weights (W,) -- None: all ones; postprocess.sliding_weights makes the usual ones

@@ -441,3 +441,75 @@ def predict_vad(**kwargs):
         results.append({"recording_id": r["id"], "num_frames": int(labels.shape[0]), "labels": labels.cpu().numpy().astype(np.uint8),
                         "probs": probs.cpu().numpy(), "intervals": intervals})
     return _write_results(results, kwargs)
+
+
+def _wav_duration(path: str) -> float:
+    try:
+        with wave.open(path, "rb") as w:
+            return w.getnframes() / float(w.getframerate())
+    except (wave.Error, EOFError):      # G.711 and the other forms read_audio takes
+        raw, (_, _, rate) = read_audio(path)
+        return raw.shape[0] / float(rate)
+
+
+def test_vad(**kwargs):
+    """The reference's test entry point (src/scripts/test.py:16-102, ``function == "test"``) with its lhotse / Lightning plumbing replaced
+    by wav files and label files: ``input = {"kind": "wav", "paths": [...], "labels": [...]}``, one label file per recording in the
+    ``start<TAB>end<TAB>LABEL`` text form the reference's get_audacity_labels writes.  The recordings go through predict_vad with every
+    option it takes (window_seconds, hop_seconds, ragged_batches, ingest of telephone audio); then, on the device, the reference
+    intervals are rasterised with the reference's rounding (postprocess.supervision_frames, uvad_intervals_to_labels) and two scoring
+    states accumulate over all recordings as one ragged batch: predict_vad's OWN labels against the reference (the counts test_step
+    logs, and per recording the FA / MD / DER fractions get_metrics averages, other_vad_metrics.py:204-255), and the raw probabilities
+    (the loss and the threshold sweep).  Prints and returns {"metrics": the reference's test_* names pooled over all recordings,
+    "recordings": [{recording_id, false_alarm, missed_detection, detection_error_rate}], "false_alarm" / "missed_detection" /
+    "detection_error_rate": their means over the recordings, "det": postprocess.det_curve}."""
+    from .postprocess import det_curve, read_label_file, score_metrics, supervision_frames
+    src = kwargs["input"]
+    if src.get("kind") != "wav" or len(src.get("labels", ())) != len(src["paths"]):
+        raise ValueError('test_vad needs input = {"kind": "wav", "paths": [...], "labels": [one label file per path]}')
+    if src.get("channels", "first") != "first":
+        raise ValueError("test_vad scores one recording per file (channels = 'first')")
+    sincnet = kwargs["feature_extractor"] == "sincnet"
+    results = predict_vad(**kwargs)                        # sorted by recording id
+    label_of = {os.path.basename(p): l for p, l in zip(src["paths"], src["labels"])}
+    device = _resolve_device(kwargs["device"])
+    from .postprocess import _shared_runtime
+    rt = _shared_runtime(device)
+    R, T = len(results), max(max(r["num_frames"] for r in results), 1)
+    frames = [r["num_frames"] for r in results]
+    probs = np.zeros((R, T), np.float32)
+    labels = np.zeros((R, T), np.float32)
+    tables = []
+    for i, r in enumerate(results):
+        probs[i, :frames[i]] = r["probs"]
+        labels[i, :frames[i]] = r["labels"]
+        duration = _wav_duration(next(p for p in src["paths"] if os.path.basename(p) == r["recording_id"]))
+        tables.append(supervision_frames(read_label_file(label_of[r["recording_id"]]), duration, frame_shift=kwargs["frame_shift"],
+                                         geometry="sincnet" if sincnet else "fbank", num_frames=frames[i]))
+    max_iv = max(max(len(t) for t in tables), 1)
+    iv = np.zeros((R, max_iv, 2), np.int32)
+    for i, t in enumerate(tables):
+        iv[i, :len(t)] = t
+    lens = torch.tensor(frames, dtype=torch.int32, device=device)
+    gt = rt.intervals_to_labels(iv, [len(t) for t in tables], T, lengths=lens)
+    by_label = rt.score_open(points=[(0.5, 1)], bins=2)                                        # the labels as 0.0 / 1.0: exactly predict_vad's
+    by_prob = rt.score_open(points=[(0.5, 1)], bins=int(kwargs.get("score_bins", 256)))        # the raw probabilities: loss and sweep
+    rows = rt.score_step(by_label, torch.from_numpy(labels).to(device), gt, lengths=lens, rows=True).cpu().numpy()
+    rt.score_step(by_prob, torch.from_numpy(probs).to(device), gt, lengths=lens)
+    read_l, read_p = rt.score_read(by_label), rt.score_read(by_prob)
+    metrics = score_metrics(read_l, prefix="test")
+    metrics["test_loss"] = score_metrics(read_p, prefix="test")["test_loss"]
+    recs = []
+    for i, r in enumerate(results):
+        n = max(frames[i], 1)
+        fa, md = float(rows[i, 1]) / n, float(rows[i, 3]) / n
+        recs.append({"recording_id": r["recording_id"], "false_alarm": fa, "missed_detection": md, "detection_error_rate": fa + md})
+    out = {"metrics": metrics, "recordings": recs, "det": det_curve(read_p)}
+    for k in ("false_alarm", "missed_detection", "detection_error_rate"):
+        out[k] = float(np.mean([r[k] for r in recs])) if recs else 0.0
+    for k, v in metrics.items():
+        print(f"{k}: {v}")
+    print(f"Detection Error Rate: {out['detection_error_rate']}\nFalse Alarm Rate: {out['false_alarm']}\n"
+          f"Missed Detection Rate: {out['missed_detection']}")
+    print(f"EER: {out['det']['eer']} at threshold {out['det']['eer_threshold']}; best threshold {out['det']['best_threshold']}")
+    return out
