@@ -646,6 +646,69 @@ int uvad_score_step(uvad_ctx *, const float *d_probs, int ld_p, const uint8_t *d
                     void *d_state, size_t state_bytes, uint64_t *d_rows, void *d_ws, size_t ws_bytes, void *stream);
 int uvad_score_totals(uvad_ctx *, const void *d_state, size_t state_bytes, uint64_t *d_out, void *stream);
 
+/* ---- Speech cuts: merged, split segments and their audio, on the device ---------------------------------------------------------------
+ * The offline counterpart of the endpointer.  Replaces the tail of get_new_cuts (src/scripts/predict.py): the run walk (:472-490),
+ * merge_intervals_with_buffer (:614-634) in frames, split_into_windows (:638-647) on integers, and the truncation of the recording to
+ * each window -- with no copy to the host in between.  The input is the output of uvad_median_filter(_lens).  Everything is integer;
+ * every output is byte-exact against a numpy restatement (tests/cuts_ref.py).
+ *
+ * Cut semantics for row b with n = clamp(d_lens[b], 0, T) frames and S_b = clamp(d_nsamp[b], 0, S) samples (NULL: T and S):
+ *   1 runs      [s_i, c_i) of the labels on [0, n), exactly as uvad_label_runs_lens; any non-zero byte counts as 1;
+ *   2 merge     with the pad P: each run becomes [max(s - P, 0), min(c + P, n)), and an interval merges into its predecessor when its
+ *               start <= the predecessor's end (what the endpointer reports as START / END events over the whole session);
+ *   3 split     a merged interval [lo, hi) of L frames: with W = max_len > 0, q = (L - 1) / W pieces of W frames from lo on and a last
+ *               piece of r = L - q W frames, 0 < r <= W; W = 0: q = 0, r = L.  The last piece is kept iff r > m = min_len.  This is
+ *               split_into_windows (predict.py:638-647: `while e - s > window` cuts full windows, `if e - s > 0.1` keeps the rest) on
+ *               integer frames, its 0.1 s made the parameter m;
+ *   4 samples   a piece [f, f + k) covers samples [max(f hop - lead, 0), min((f + k) hop + tail, S_b)), in int64; a piece whose range
+ *               is empty is still listed, with n_samples = 0.  With tail = frame_len - hop (240 for log-mel, 721 for SincNet's 991 - 270)
+ *               a cut holds every sample any of its frames saw; tail = 0 gives disjoint cuts.
+ *   Cuts are ordered by row, then by time.  The reference's split=True, window=10 at 10 ms frames is max_len = 1000, min_len = 10; its
+ *   split=False is 0, 0.
+ * uvad_cuts_max_per_row: (T + 1) / 2 + (W ? T / W : 0), a bound on one row's cuts; uvad_cuts_max_samples: W ? min(S, W hop + lead + tail)
+ *   : S, a bound on n_samples.  Both 0 on a bad configuration (or T outside 1 .. 2^30, S < 0).
+ * uvad_cuts_table: d_labels [B][ld] uint8, ld >= T.  d_table [max_cuts] receives the first min(total, max_cuts) cuts (cuts past max_cuts
+ *   are counted but not stored, as uvad_label_runs treats max_runs; later entries are not written); d_row_first [B + 1] int32: entry b
+ *   the index of row b's first cut, entry B the total; d_total [1] int32: the true number of cuts.  Label columns at or past n, and
+ *   whole rows with n = 0, are never read.  Workspace: uvad_cuts_ws_bytes(ctx, B, T) bytes (0 on a bad argument).
+ * uvad_cuts_gather: output row i < min(*d_total, max_cuts) of d_out [max_cuts][ld_out] receives units [0, c) of cut i, c = min(n, ld_out),
+ *   then zero bytes up to ld_out, and d_out_len[i] = c (int32): truncation shows as d_out_len[i] < n.  Later rows and lengths are not
+ *   written; source units outside a cut's range are never read.
+ *     UVAD_CUTS_SAMPLES  n = n_samples from first_sample on; d_src [B][row_stride] units of 2 bytes (int16 PCM) or 4 (f32);
+ *     UVAD_CUTS_FRAMES   n = n_frames from first_frame on; d_src [B][row_stride] records of unit_bytes, any multiple of 4 up to 4096
+ *                        (a feature tensor [B][T][F] f32: unit_bytes = 4 F, row_stride = T): the rows a recogniser with log-mel input wants.
+ *   Stores are 16 bytes wide when ld_out x unit_bytes is a multiple of 16 and d_out is 16-byte aligned; any other stride works, slower.
+ * Both calls allocate nothing, never synchronise and read every count from the device; their grids depend on B, T, max_cuts and ld_out
+ * alone, and workgroups past the total do nothing: a graph captured around table + gather replays for new labels, lengths and audio.
+ * A context created without feature / model configuration serves them.
+ * Refusals (UVAD_E_ARG, nothing enqueued, uvad_last_error names the word): a NULL cfg; pad outside [0, 2^20]; max_len outside [0, 2^24];
+ *   min_len < 0, or >= max_len when max_len > 0; hop < 1; lead < 0; tail < 0; B < 1; T < 1 or > 2^30; ld < T; S < 0; max_cuts < 0; NULL
+ *   d_labels / d_row_first / d_total / d_ws; NULL d_table with max_cuts > 0; B x uvad_cuts_max_per_row above 2^31 - 1; ws_bytes below
+ *   uvad_cuts_ws_bytes ("need N bytes"); unit_bytes not 2 or 4 (samples) or no multiple of 4 in [4, 4096] (frames); which unknown;
+ *   ld_out < 1 or > 2^31 - 1; row_stride < 0; NULL d_src / d_table / d_total / d_out / d_out_len. */
+#define UVAD_CUTS_SAMPLES 0
+#define UVAD_CUTS_FRAMES 1
+typedef struct {
+    int pad;       /* P frames added to both ends of every run before merging, 0 .. 2^20 (as uvad_endpoint_cfg.pad) */
+    int max_len;   /* W frames: 0 = no splitting, 1 .. 2^24 = no cut longer than W frames */
+    int min_len;   /* m frames: a last piece of <= m frames is dropped; 0 drops nothing; < max_len when max_len > 0 */
+    int hop;       /* samples per frame, >= 1 (160 log-mel at 10 ms, 270 SincNet) */
+    int lead;      /* samples taken before the first frame's first sample, >= 0 */
+    int tail;      /* samples taken past the last frame's hop, >= 0 */
+} uvad_cuts_cfg;
+typedef struct {
+    int32_t row, index, first_frame, n_frames;
+    int64_t first_sample, n_samples;
+} uvad_cut;   /* 32 bytes; index = position within its row */
+int uvad_cuts_max_per_row(const uvad_cuts_cfg *, int T);
+int64_t uvad_cuts_max_samples(const uvad_cuts_cfg *, int64_t S);
+size_t uvad_cuts_ws_bytes(const uvad_ctx *, int B, int T);
+int uvad_cuts_table(uvad_ctx *, const uint8_t *d_labels, int ld, int B, int T, const int32_t *d_lens, const int64_t *d_nsamp, int64_t S,
+                    const uvad_cuts_cfg *, uvad_cut *d_table, int max_cuts, int32_t *d_row_first, int32_t *d_total, void *d_ws,
+                    size_t ws_bytes, void *stream);
+int uvad_cuts_gather(uvad_ctx *, const void *d_src, int64_t row_stride, int unit_bytes, int which, const uvad_cut *d_table,
+                     const int32_t *d_total, int max_cuts, void *d_out, int64_t ld_out, int32_t *d_out_len, void *stream);
+
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;
  *   1  (default) f32-accurate on the f16 matrix cores: weights scaled by a power of two and split on the host into THREE

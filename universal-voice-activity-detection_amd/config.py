@@ -57,6 +57,11 @@ def load_config() -> ConfigDict:
     cfg.hop_seconds = None
     cfg.sliding_weights = "hamming"   # "rect" | "hamming" (postprocess.sliding_weights)
     cfg.sliding_group = 512           # windows per classifier launch: bounds the workspace, not the result
+    # cuts = None: nothing more.  A dict {"buffer": s, "split": bool, "window": 10.0, "min": 0.1, "write_dir": None} (the options of the
+    # reference's get_new_cuts, seconds): every result gains "cuts", [(start_s, end_s, first_sample, n_samples)] -- the runs widened by
+    # buffer and merged, with split cut to at most window seconds, remainders of min seconds or less dropped (uvad_cuts_table); with
+    # write_dir one 16 kHz wav per cut is written there (uvad_cuts_gather)
+    cfg.cuts = None
 
     cfg.experiments_dir = os.environ.get("UVAD_EXPERIMENTS_DIR", "experiments")
     cfg.load_checkpoint = False

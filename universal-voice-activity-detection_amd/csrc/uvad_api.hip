@@ -3056,6 +3056,92 @@ int uvad_score_totals(uvad_ctx *c, const void *d_state, size_t state_bytes, uint
     return UVAD_OK;
 }
 
+// ---- speech cuts (cuts.hip) --------------------------------------------------------------------------------------------------------------
+// nullptr: the configuration is in range; else the word uvad_last_error names
+static const char *cuts_cfg_error(const uvad_cuts_cfg *q) {
+    if (!q) return "cfg is NULL";
+    if (q->pad < 0 || q->pad > CUTS_MAX_PAD) return "pad must lie in [0, 2^20] frames";
+    if (q->max_len < 0 || q->max_len > CUTS_MAX_LEN) return "max_len must lie in [0, 2^24] frames";
+    if (q->min_len < 0 || (q->max_len > 0 && q->min_len >= q->max_len)) return "min_len must be >= 0 and below max_len";
+    if (q->hop < 1) return "hop must be >= 1";
+    if (q->lead < 0) return "lead must be >= 0";
+    if (q->tail < 0) return "tail must be >= 0";
+    return nullptr;
+}
+static CutsCfgInt cuts_cfg_of(const uvad_cuts_cfg *q) { return CutsCfgInt{q->pad, q->max_len, q->min_len, q->hop, q->lead, q->tail}; }
+
+int uvad_cuts_max_per_row(const uvad_cuts_cfg *q, int T) {
+    if (cuts_cfg_error(q) || T < 1 || T > CUTS_MAX_T) return 0;
+    return cuts_max_per_row(cuts_cfg_of(q), T);
+}
+
+int64_t uvad_cuts_max_samples(const uvad_cuts_cfg *q, int64_t S) {
+    if (cuts_cfg_error(q) || S < 0) return 0;
+    if (q->max_len == 0) return S;
+    return std::min<int64_t>(S, (int64_t)q->max_len * q->hop + q->lead + q->tail);
+}
+
+size_t uvad_cuts_ws_bytes(const uvad_ctx *c, int B, int T) {
+    if (!c || B < 1 || T < 1 || T > CUTS_MAX_T) return 0;
+    return cuts_ws_bytes(B, T);
+}
+
+int uvad_cuts_table(uvad_ctx *c, const uint8_t *d_labels, int ld, int B, int T, const int32_t *d_lens, const int64_t *d_nsamp, int64_t S,
+                    const uvad_cuts_cfg *q, uvad_cut *d_table, int max_cuts, int32_t *d_row_first, int32_t *d_total, void *d_ws,
+                    size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (const char *w = cuts_cfg_error(q)) return fail(c, UVAD_E_ARG, std::string("uvad_cuts_table: ") + w);
+    if (B < 1) return fail(c, UVAD_E_ARG, "uvad_cuts_table: B must be >= 1");
+    if (T < 1 || T > CUTS_MAX_T) return fail(c, UVAD_E_ARG, "uvad_cuts_table: T must lie in [1, 2^30]");
+    if (ld < T) return fail(c, UVAD_E_ARG, "uvad_cuts_table: ld must be at least T");
+    if (S < 0) return fail(c, UVAD_E_ARG, "uvad_cuts_table: S must be >= 0");
+    if (max_cuts < 0) return fail(c, UVAD_E_ARG, "uvad_cuts_table: max_cuts must be >= 0");
+    if (!d_labels) return fail(c, UVAD_E_ARG, "uvad_cuts_table: d_labels is NULL");
+    if (!d_row_first) return fail(c, UVAD_E_ARG, "uvad_cuts_table: d_row_first is NULL");
+    if (!d_total) return fail(c, UVAD_E_ARG, "uvad_cuts_table: d_total is NULL");
+    if (!d_ws) return fail(c, UVAD_E_ARG, "uvad_cuts_table: d_ws is NULL");
+    if (max_cuts > 0 && !d_table) return fail(c, UVAD_E_ARG, "uvad_cuts_table: d_table is NULL with max_cuts > 0");
+    const CutsCfgInt qi = cuts_cfg_of(q);
+    if ((long long)B * cuts_max_per_row(qi, T) > 0x7fffffffll) return fail(c, UVAD_E_ARG, "uvad_cuts_table: B x uvad_cuts_max_per_row above 2^31 - 1");
+    const size_t need = cuts_ws_bytes(B, T);
+    if (ws_bytes < need) return fail(c, UVAD_E_ARG, "uvad_cuts_table: workspace too small: need " + std::to_string(need) + " bytes");
+    CutsTableArgs a{};
+    a.labels = d_labels; a.ld = ld; a.B = B; a.T = T; a.lens = d_lens; a.nsamp = reinterpret_cast<const long long *>(d_nsamp); a.S = S;
+    a.q = qi;
+    a.table = reinterpret_cast<CutRecord *>(d_table); a.max_cuts = max_cuts; a.row_first = d_row_first; a.total = d_total;
+    a.counts = reinterpret_cast<int *>(d_ws);
+    a.iv = reinterpret_cast<CutsInterval *>(reinterpret_cast<char *>(d_ws) + cuts_counts_bytes(B));
+    a.cap = (T + 1) / 2;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_cuts_table(a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_cuts_gather(uvad_ctx *c, const void *d_src, int64_t row_stride, int unit_bytes, int which, const uvad_cut *d_table,
+                     const int32_t *d_total, int max_cuts, void *d_out, int64_t ld_out, int32_t *d_out_len, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (which != UVAD_CUTS_SAMPLES && which != UVAD_CUTS_FRAMES) return fail(c, UVAD_E_ARG, "uvad_cuts_gather: which must be UVAD_CUTS_SAMPLES or UVAD_CUTS_FRAMES");
+    if (which == UVAD_CUTS_SAMPLES && unit_bytes != 2 && unit_bytes != 4)
+        return fail(c, UVAD_E_ARG, "uvad_cuts_gather: unit_bytes must be 2 (int16) or 4 (f32) for samples");
+    if (which == UVAD_CUTS_FRAMES && (unit_bytes < 4 || unit_bytes > 4096 || unit_bytes % 4))
+        return fail(c, UVAD_E_ARG, "uvad_cuts_gather: unit_bytes must be a multiple of 4 in [4, 4096] for frames");
+    if (ld_out < 1 || ld_out > 0x7fffffffll) return fail(c, UVAD_E_ARG, "uvad_cuts_gather: ld_out must lie in [1, 2^31 - 1]");
+    if (row_stride < 0) return fail(c, UVAD_E_ARG, "uvad_cuts_gather: row_stride must be >= 0");
+    if (max_cuts < 0) return fail(c, UVAD_E_ARG, "uvad_cuts_gather: max_cuts must be >= 0");
+    if (!d_src) return fail(c, UVAD_E_ARG, "uvad_cuts_gather: d_src is NULL");
+    if (!d_table) return fail(c, UVAD_E_ARG, "uvad_cuts_gather: d_table is NULL");
+    if (!d_total) return fail(c, UVAD_E_ARG, "uvad_cuts_gather: d_total is NULL");
+    if (!d_out) return fail(c, UVAD_E_ARG, "uvad_cuts_gather: d_out is NULL");
+    if (!d_out_len) return fail(c, UVAD_E_ARG, "uvad_cuts_gather: d_out_len is NULL");
+    CutsGatherArgs a{};
+    a.src = d_src; a.row_stride = row_stride; a.unit_bytes = unit_bytes; a.frames = which == UVAD_CUTS_FRAMES;
+    a.table = reinterpret_cast<const CutRecord *>(d_table); a.total = d_total; a.max_cuts = max_cuts;
+    a.out = d_out; a.ld_out = ld_out; a.out_len = d_out_len; a.tiles = cuts_gather_tiles(ld_out, unit_bytes);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_cuts_gather(a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
 int uvad_set_gemm_mode(uvad_ctx *c, int mode) {
     if (!c) return UVAD_E_ARG;
     if (mode < 0 || mode > 3)

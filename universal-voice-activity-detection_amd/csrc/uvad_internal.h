@@ -548,4 +548,34 @@ hipError_t launch_score_totals(const void *state, unsigned long long *out, hipSt
 hipError_t launch_intervals_to_labels(const int *iv, const int *iv_counts, int B, int max_iv, int T, int ld, const int *lens, uint8_t *labels,
                                       hipStream_t s);
 
+// ---- cuts.hip: speech cuts (uvad_cuts_*, include/uvad.h): the cut table of a batch of label rows and the gather of the cuts' audio ----------
+// The workspace is 2 B int32 {cuts, stored intervals} per row, rounded up to 16 bytes, followed by (T + 1) / 2 CutsInterval per row: the
+// row's merged intervals that keep at least one piece, in order, with the index of their first piece within the row.
+constexpr int CUTS_MAX_T = 1 << 30;                   // frame arithmetic stays in int32 with a pad and a pass on top
+constexpr int CUTS_MAX_PAD = 1 << 20, CUTS_MAX_LEN = 1 << 24;
+constexpr int CUTS_SPAN_WORDS = 64;                   // 64-frame words per pass of a row: 4096 frames
+constexpr int CUTS_ROWS_THREADS = 320;                // cuts_rows_kernel: wave 0 walks a pass, waves 1 .. 4 load the next
+constexpr int CUTS_TILE_BYTES = 65536;                // of an output row per (cut, tile) pair of the gather
+constexpr int CUTS_MAX_BLOCKS = 1 << 16;              // grids are capped: the write and gather kernels stride over their items
+struct CutsCfgInt { int pad, max_len, min_len, hop, lead, tail; };   // uvad_cuts_cfg, field for field
+struct alignas(16) CutsInterval { int lo, hi, base, reserved; };
+struct CutRecord { int row, index, first_frame, n_frames; long long first_sample, n_samples; };   // uvad_cut, field for field
+struct CutsTableArgs {
+    const uint8_t *labels; int ld, B, T; const int *lens; const long long *nsamp; long long S;
+    CutsCfgInt q;
+    CutRecord *table; int max_cuts; int *row_first, *total;
+    int *counts; CutsInterval *iv; int cap;           // the workspace: [B][2], [B][cap], cap = (T + 1) / 2
+};
+struct CutsGatherArgs {
+    const void *src; long long row_stride; int unit_bytes, frames;   // frames: ranges from first_frame / n_frames, records of unit_bytes
+    const CutRecord *table; const int *total; int max_cuts;
+    void *out; long long ld_out; int *out_len; int tiles;
+};
+constexpr size_t cuts_counts_bytes(int B) { return ((size_t)B * 2 * sizeof(int) + 15) / 16 * 16; }
+constexpr size_t cuts_ws_bytes(int B, int T) { return cuts_counts_bytes(B) + (size_t)B * ((T + 1) / 2) * sizeof(CutsInterval); }
+constexpr int cuts_gather_tiles(long long ld_out, int unit_bytes) { return (int)((ld_out * unit_bytes + CUTS_TILE_BYTES - 1) / CUTS_TILE_BYTES); }
+int cuts_max_per_row(const CutsCfgInt &q, int T);
+hipError_t launch_cuts_table(const CutsTableArgs &a, hipStream_t s);
+hipError_t launch_cuts_gather(const CutsGatherArgs &a, hipStream_t s);
+
 }  // namespace uvad

@@ -204,6 +204,43 @@ def split_into_windows(intervals, window: float = 10):
     return out
 
 
+def split_runs(intervals, max_len: int, min_len: int = 0) -> List[Tuple[int, int]]:
+    """split_into_windows (predict.py:638-647) on integer FRAMES, in closed form (host; step 3 of uvad_cuts_table, restated): an interval
+    [lo, hi) of L frames gives q = (L - 1) // max_len pieces of max_len frames from lo on and a last piece of r = L - q * max_len frames,
+    0 < r <= max_len, kept iff r > min_len.  max_len = 0: no splitting (q = 0, r = L).  The reference's window=10 with its 0.1 s rule at
+    10 ms frames is max_len=1000, min_len=10."""
+    max_len, min_len = int(max_len), int(min_len)
+    if max_len < 0 or min_len < 0 or (max_len > 0 and min_len >= max_len):
+        raise ValueError(f"need max_len >= 0 and 0 <= min_len (< max_len when splitting), got {max_len}, {min_len}")
+    out = []
+    for lo, hi in intervals:
+        lo, hi = int(lo), int(hi)
+        L = hi - lo
+        if L < 1:
+            continue
+        q = (L - 1) // max_len if max_len else 0
+        out.extend((lo + j * max_len, lo + (j + 1) * max_len) for j in range(q))
+        if L - q * max_len > min_len:
+            out.append((lo + q * max_len, hi))
+    return out
+
+
+def cut_table(labels, pad: int, max_len: int = 0, min_len: int = 0) -> List[Tuple[int, int]]:
+    """One row of 0/1 labels -> its cuts [(first_frame, end_frame)]: merged_runs, then split_runs.  The host restatement of what
+    uvad_cuts_table (VadRuntime.cuts_table) lists for the row, frames only."""
+    return split_runs(merged_runs(labels, pad), max_len, min_len)
+
+
+def cuts_config(buffer: float = 0.0, split: bool = False, window: float = 10.0, min: float = 0.1, frame_shift: float = 0.01,
+                hop: int = 160, tail: int = 240, lead: int = 0) -> dict:
+    """The reference's get_new_cuts options in seconds -> the integer configuration of uvad_cuts_table: seconds become frames by
+    round(x / frame_shift); split=False is max_len = min_len = 0.  hop / tail: samples per frame and the samples a frame sees past its
+    hop (160 / 240 for log-mel at 10 ms, 270 / 721 for SincNet)."""
+    fr = lambda x: int(round(float(x) / frame_shift))
+    return {"pad": fr(buffer), "max_len": fr(window) if split else 0, "min_len": fr(min) if split else 0,
+            "hop": int(hop), "lead": int(lead), "tail": int(tail)}
+
+
 def intervals_to_labels(intervals, total_duration: float, frame_shift: float) -> np.ndarray:
     """predict.py:654-663 (get_binary_tensor): ceil(duration/shift) frames, [int(s/shift), int(e/shift)) set to 1."""
     import math

@@ -992,6 +992,117 @@ class VadRuntime:
                                                           self._stream()))
             return out[:, :T]
 
+    # ------------------------------------------------------------------ speech cuts (uvad_cuts_*)
+    def cuts_open(self, pad: int = 0, max_len: int = 0, min_len: int = 0, hop: int = 160, lead: int = 0, tail: int = 240, max_cuts=None):
+        """The configuration and the buffers of the cut calls below: runs widened by `pad` frames and merged, split into pieces of at
+        most `max_len` frames (0: no splitting) whose last piece is dropped when it has `min_len` frames or fewer; `hop` samples per
+        frame, `lead` / `tail` samples taken before the first frame and past the last frame's hop (postprocess.cuts_config makes these
+        from the reference's seconds).  max_cuts: rows of the table and of the gathered batch (default: B x uvad_cuts_max_per_row, which
+        never overflows).  Buffers are sized by the first call with a shape; after that the calls allocate nothing and can be captured."""
+        cfg = _lib.CutsCfg(int(pad), int(max_len), int(min_len), int(hop), int(lead), int(tail))
+        if int(self.lib.uvad_cuts_max_per_row(C.byref(cfg), 1)) == 0:
+            raise ValueError(f"bad cuts configuration: pad {pad} (0 .. 2^20), max_len {max_len} (0 .. 2^24), min_len {min_len} (>= 0, < max_len "
+                             f"when splitting), hop {hop} (>= 1), lead {lead} and tail {tail} (>= 0)")
+        if max_cuts is not None and int(max_cuts) < 0:
+            raise ValueError("max_cuts must be >= 0")
+        return {"cfg": cfg, "max_cuts": None if max_cuts is None else int(max_cuts), "table": None, "row_first": None,
+                "total": torch.zeros(1, dtype=torch.int32, device=self.device), "ws": None, "out": {}, "out_len": None}
+
+    def cuts_table(self, labels: "torch.Tensor", lengths=None, nsamp=None, S=None, cuts=None, **cfg):
+        """labels (B, T) uint8 on the GPU (non-zero = speech; row-strided views are used as they are), lengths (B,) valid frames and nsamp
+        (B,) samples per row (device tensors are read on the device), S: samples per row of the audio the cuts will be taken from
+        (default: the largest nsamp, or T * hop + tail).  cuts: a state of cuts_open; without it one is opened from **cfg.
+        -> (table (max_cuts, 8) int32 -- uvad_cut rows {row, index, first_frame, n_frames, first_sample lo / hi, n_samples lo / hi} --,
+        row_first (B + 1,) int32, total (1,) int32), on the device and overwritten by the next call on the state.  cuts_read gives the
+        host view."""
+        ct = cuts if cuts is not None else self.cuts_open(**cfg)
+        with torch.cuda.device(self.device):
+            if not torch.is_tensor(labels) or labels.device != self.device:
+                raise RuntimeError(f"labels must be a tensor on {self.device}")
+            labels = self._rows_2d(labels, torch.uint8, "labels")
+            B, T = labels.shape
+            q = ct["cfg"]
+            n = None if lengths is None else self._dev_lens(lengths, B, T, torch.int32, "lengths (frames)")
+            if S is None:
+                S = int(max(nsamp.tolist() if torch.is_tensor(nsamp) else nsamp)) if nsamp is not None else T * q.hop + q.tail
+            ns = None if nsamp is None else self._dev_lens(nsamp, B, int(S), torch.int64, "nsamp (samples)")
+            per_row = int(self.lib.uvad_cuts_max_per_row(C.byref(q), T))
+            if ct["max_cuts"] is None:
+                ct["max_cuts"] = B * per_row
+            mc = ct["max_cuts"]
+            if ct["table"] is None:
+                ct["table"] = torch.zeros((max(mc, 1), 8), dtype=torch.int32, device=self.device)
+                ct["out_len"] = torch.zeros(max(mc, 1), dtype=torch.int32, device=self.device)
+            if ct["row_first"] is None or ct["row_first"].numel() != B + 1:
+                ct["row_first"] = torch.zeros(B + 1, dtype=torch.int32, device=self.device)
+            need = int(self.lib.uvad_cuts_ws_bytes(self.ctx, B, T))
+            if ct["ws"] is None or ct["ws"].numel() < need:
+                ct["ws"] = torch.zeros(max(need, 16), dtype=torch.uint8, device=self.device)
+            self._check(self.lib.uvad_cuts_table(self.ctx, labels.data_ptr(), labels.stride(0) if B > 1 else max(labels.stride(0), T), B, T,
+                                                 n.data_ptr() if n is not None else None, ns.data_ptr() if ns is not None else None, int(S),
+                                                 C.byref(q), ct["table"].data_ptr() if mc else None, mc, ct["row_first"].data_ptr(),
+                                                 ct["total"].data_ptr(), ct["ws"].data_ptr(), ct["ws"].numel(), self._stream()))
+            ct["_keep"] = (labels, n, ns)   # the launch reads them after this call returns
+            ct["S"] = int(S)
+            return ct["table"][:mc], ct["row_first"], ct["total"]
+
+    def cuts_gather(self, src: "torch.Tensor", cuts, which: str = "samples", ld_out=None, rows=None):
+        """The audio (which="samples": src (B, S) int16 or f32) or the feature frames (which="frames": src (B, T, F) f32) of the cuts the
+        last cuts_table on the state `cuts` listed -> (batch (max_cuts, ld_out[, F]) of src's type, lengths (max_cuts,) int32): row i <
+        total holds the cut's first min(n, ld_out) units, then zeros; later rows are left as they are.  ld_out defaults to
+        uvad_cuts_max_samples rounded up to 8 (samples) or the longest possible cut in frames; rows (default max_cuts) bounds the
+        batch's rows: the batch is rows x ld_out units of memory whatever the labels hold, so a caller who knows the total (cuts_read)
+        or an upper bound passes it, here or as cuts_open's max_cuts."""
+        ct = cuts
+        if ct.get("table") is None:
+            raise RuntimeError("cuts_gather needs a state on which cuts_table has run")
+        if which not in ("samples", "frames"):
+            raise ValueError(f"which must be 'samples' or 'frames', got {which!r}")
+        with torch.cuda.device(self.device):
+            if not torch.is_tensor(src) or src.device != self.device:
+                raise RuntimeError(f"src must be a tensor on {self.device}")
+            q = ct["cfg"]
+            if which == "samples":
+                if src.dim() != 2 or src.dtype not in (torch.int16, torch.float32) or (src.shape[1] > 1 and src.stride(1) != 1):
+                    raise ValueError("samples: src must be a (B, S) int16 or float32 tensor with contiguous rows")
+                unit, tailshape, row_stride = src.element_size(), (), src.stride(0) if src.shape[0] > 1 else max(src.stride(0), src.shape[1])
+                if ld_out is None:
+                    ld_out = -(-int(self.lib.uvad_cuts_max_samples(C.byref(q), src.shape[1])) // 8) * 8
+            else:
+                if src.dim() != 3 or src.dtype != torch.float32 or not src.is_contiguous():
+                    raise ValueError("frames: src must be a contiguous (B, T, F) float32 tensor")
+                unit, tailshape, row_stride = 4 * src.shape[2], (src.shape[2],), src.shape[1]
+                if ld_out is None:
+                    ld_out = q.max_len if q.max_len else src.shape[1]
+            ld_out = max(int(ld_out), 1)
+            mc = ct["max_cuts"] if rows is None else min(ct["max_cuts"], max(int(rows), 0))
+            key = (which, src.dtype, ld_out, mc) + tailshape
+            if key not in ct["out"]:
+                ct["out"][key] = torch.zeros((max(mc, 1), ld_out) + tailshape, dtype=src.dtype, device=self.device)
+            out = ct["out"][key]
+            self._check(self.lib.uvad_cuts_gather(self.ctx, src.data_ptr(), row_stride, unit, _lib.CUTS_SAMPLES if which == "samples" else _lib.CUTS_FRAMES,
+                                                  ct["table"].data_ptr(), ct["total"].data_ptr(), mc, out.data_ptr(), ld_out,
+                                                  ct["out_len"].data_ptr(), self._stream()))
+            ct["_keep_src"] = src
+            return out[:mc], ct["out_len"][:mc]
+
+    def speech_cuts(self, labels: "torch.Tensor", pcm: "torch.Tensor", lengths=None, nsamp=None, cuts=None, ld_out=None, **cfg):
+        """Labels and the audio they were made from, both on the GPU -> (table, batch, lengths): cuts_table, then cuts_gather of the
+        samples, with no copy to the host in between -- the padded batch a recogniser takes.  pcm (B, S) int16 or f32; see cuts_table
+        and cuts_gather for the rest.  The state used is returned by neither: pass one from cuts_open to keep it (graphs, cuts_read)."""
+        ct = cuts if cuts is not None else self.cuts_open(**cfg)
+        table, _, _ = self.cuts_table(labels, lengths=lengths, nsamp=nsamp, S=int(pcm.shape[1]), cuts=ct)
+        batch, lens = self.cuts_gather(pcm, ct, "samples", ld_out=ld_out)
+        return table, batch, lens
+
+    def cuts_read(self, cuts) -> np.ndarray:
+        """The cuts the last cuts_table listed, copied to the host (synchronises): a structured array with uvad_cut's fields {row, index,
+        first_frame, n_frames, first_sample, n_samples}, min(total, max_cuts) entries."""
+        dt = np.dtype([("row", "<i4"), ("index", "<i4"), ("first_frame", "<i4"), ("n_frames", "<i4"), ("first_sample", "<i8"), ("n_samples", "<i8")])
+        with torch.cuda.device(self.device):
+            n = min(int(cuts["total"].cpu()[0]), cuts["max_cuts"])
+            return cuts["table"][:n].cpu().numpy().view(dt).reshape(-1).copy()
+
     # ------------------------------------------------------------------ sliding windows over whole recordings (uvad_sliding_*)
     def sliding_configure(self, window: int, hop: int, weights=None):
         """Window and hop in frames and the aggregation weights (W,) -- None: all ones; postprocess.sliding_weights makes the usual ones

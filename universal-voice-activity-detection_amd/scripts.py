@@ -32,7 +32,7 @@ import torch
 from .engine import VadModel
 from .features import FbankConfig
 from .pipeline import ForwardPipeline
-from .postprocess import labels_to_intervals_batch, median_filter, sincnet_labels_to_intervals, sliding_weights
+from .postprocess import cuts_config, labels_to_intervals_batch, median_filter, sincnet_labels_to_intervals, sliding_weights
 from .sincnet import SincNet
 from .synth import seed_weights, synth_pcm
 
@@ -170,10 +170,74 @@ def _write_results(results, kwargs):
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "predictions.json"), "w") as f:
             json.dump([{"recording_id": r["recording_id"], "num_frames": r["num_frames"],
-                        "speech_frames": int(r["labels"].sum()), "intervals": r["intervals"]} for r in results], f, indent=1)
+                        "speech_frames": int(r["labels"].sum()), "intervals": r["intervals"],
+                        **({"cuts": r["cuts"]} if "cuts" in r else {})} for r in results], f, indent=1)
     for r in results:
         print(f"{r['recording_id']}: {r['num_frames']} frames, {int(r['labels'].sum())} speech, {len(r['intervals'])} intervals")
     return results
+
+
+CUTS_DEFAULTS = {"buffer": 0.0, "split": False, "window": 10.0, "min": 0.1, "write_dir": None}
+
+
+def _write_wav_int16(path: str, x: np.ndarray, sample_rate: int = 16000):
+    if x.dtype != np.int16:   # f32 in [-1, 1): the value an int16 file would have held
+        x = np.clip(np.rint(x.astype(np.float64) * 32768.0), -32768, 32767).astype(np.int16)
+    with wave.open(path, "wb") as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(sample_rate)
+        w.writeframes(x.astype("<i2").tobytes())
+
+
+def _attach_cuts(results, recs, dev_labels, rt, cuts, sincnet, frame_shift, device, max_samples, sr=16000):
+    """predict_vad(cuts=...): the tail of the reference's get_new_cuts on the device.  results[i], recs[i] and dev_labels[i] (the
+    recording's whole-row labels, a 1-D tensor on the GPU, or None when it has no frame) belong together.  Recordings are grouped within
+    the max_duration budget; a group is one uvad_cuts_table call on its padded label rows, and its table is the only thing that crosses
+    to the host -- with write_dir also one uvad_cuts_gather of the group's audio, written as one 16 kHz wav per cut.  Every result gains
+    "cuts": [(start_s, end_s, first_sample, n_samples)]."""
+    unknown = set(cuts) - set(CUTS_DEFAULTS)
+    if unknown:
+        raise ValueError(f"unknown cuts option(s) {sorted(unknown)} (known: {sorted(CUTS_DEFAULTS)})")
+    opt = {**CUTS_DEFAULTS, **cuts}
+    hop = 270 if sincnet else int(round(frame_shift * sr))
+    tail = 721 if sincnet else max(400 - hop, 0)          # what a frame sees past its hop: 991 - 270, frame_len - hop
+    shift = hop / float(sr) if sincnet else frame_shift
+    cfg = cuts_config(opt["buffer"], opt["split"], opt["window"], opt["min"], frame_shift=shift, hop=hop, tail=tail)
+    if opt["write_dir"]:
+        os.makedirs(opt["write_dir"], exist_ok=True)
+    for r in results:
+        r["cuts"] = []
+    have = [i for i in range(len(results)) if dev_labels[i] is not None and dev_labels[i].numel()]
+    lengths = [len(recs[i]["pcm"]) for i in have]
+    for group in pack_ragged_batches(lengths, max_samples):
+        idx = [have[g] for g in group]
+        T = max(int(dev_labels[i].numel()) for i in idx)
+        lab = torch.zeros((len(idx), T), dtype=torch.uint8, device=device)
+        for r, i in enumerate(idx):
+            lab[r, :dev_labels[i].numel()] = dev_labels[i].to(torch.uint8)
+        frames = [int(dev_labels[i].numel()) for i in idx]
+        nsamp = [len(recs[i]["pcm"]) for i in idx]
+        S = max(nsamp)
+        ct = rt.cuts_open(**cfg)
+        rt.cuts_table(lab, lengths=frames, nsamp=nsamp, S=S, cuts=ct)
+        tab = rt.cuts_read(ct)
+        batch = lens = None
+        if opt["write_dir"] and len(tab):
+            mixed = len({recs[i]["pcm"].dtype for i in idx}) > 1
+            i16 = not mixed and recs[idx[0]]["pcm"].dtype == np.int16
+            x = torch.zeros((len(idx), S), dtype=torch.int16 if i16 else torch.float32, device=device)
+            for r, i in enumerate(idx):
+                row = torch.from_numpy(np.array(recs[i]["pcm"])).to(device)
+                x[r, :nsamp[r]] = row.float() / 32768.0 if mixed and row.dtype == torch.int16 else row
+            batch, lens = rt.cuts_gather(x, ct, "samples", ld_out=-(-max(int(tab["n_samples"].max()), 1) // 8) * 8, rows=len(tab))
+            batch, lens = batch.cpu().numpy(), lens.cpu().numpy()
+        for k, c in enumerate(tab):
+            res = results[idx[int(c["row"])]]
+            f, nf = int(c["first_frame"]), int(c["n_frames"])
+            res["cuts"].append((round(f * shift, 6), round((f + nf) * shift, 6), int(c["first_sample"]), int(c["n_samples"])))
+            if batch is not None:
+                _write_wav_int16(os.path.join(opt["write_dir"], f"{res['recording_id']}_{int(c['index']):04d}.wav"), batch[k, :lens[k]], sr)
 
 
 def sliding_geometry(rt, sincnet: bool, window_seconds: float, hop_seconds: float, frame_shift: float, sr: int = 16000):
@@ -187,7 +251,7 @@ def sliding_geometry(rt, sincnet: bool, window_seconds: float, hop_seconds: floa
     return W, Hf
 
 
-def _predict_sliding(recs, rt, sincnet, kwargs, window_s, hop_s, frame_shift, med_window, device, sr=16000):
+def _predict_sliding(recs, rt, sincnet, kwargs, window_s, hop_s, frame_shift, med_window, device, sr=16000, dev_labels=None):
     """predict_vad with hop_seconds: whole recordings as ragged [R][S_max] batches within the max_duration budget, overlapping windows
     aggregated on the device (uvad_sliding_forward[_wav][_i16]), then the lens median filter and run-length kernels on the frame counts
     the call returned.  Every recording is copied into its row of the device batch by itself: nothing is stacked on the host."""
@@ -221,6 +285,8 @@ def _predict_sliding(recs, rt, sincnet, kwargs, window_s, hop_s, frame_shift, me
         for r, i in enumerate(batch):
             results[i] = {"recording_id": recs[i]["id"], "num_frames": int(fr[r]), "labels": lab[r, :fr[r]].cpu().numpy().astype(np.uint8),
                           "probs": probs[r, :fr[r]].cpu().numpy(), "intervals": ivs[r]}
+            if dev_labels is not None:
+                dev_labels[i] = lab[r, :fr[r]]
     return results
 
 
@@ -279,12 +345,16 @@ def predict_vad(**kwargs):
                 pieces.append((ri, st, ln))
     W = None if window_s is None else int(round(window_s * sr))
     med_window = 0.02 if net.encoding_dim == 768 else 0.01   # vad_engine.py:207-208
+    cuts = kwargs.get("cuts")   # None: every output below is what it was; a dict (CUTS_DEFAULTS): every result gains "cuts" (_attach_cuts)
+    dev_labels = [None] * len(recs) if cuts is not None else None   # each recording's whole-row labels, kept on the device
     hop_s = kwargs.get("hop_seconds")
     if hop_s is not None:   # overlapping windows of window_seconds every hop_seconds, aggregated on the device; None: the cuts below, unchanged
         if window_s is None:
             raise ValueError("hop_seconds needs window_seconds (the window the model was trained on)")
-        return _write_results(_predict_sliding(recs, net.runtime(device), sincnet, kwargs, window_s, hop_s, frame_shift, med_window, device, sr),
-                              kwargs)
+        results = _predict_sliding(recs, net.runtime(device), sincnet, kwargs, window_s, hop_s, frame_shift, med_window, device, sr, dev_labels)
+        if cuts is not None:
+            _attach_cuts(results, recs, dev_labels, net.runtime(device), cuts, sincnet, frame_shift, device, int(kwargs["max_duration"] * sr), sr)
+        return _write_results(results, kwargs)
 
     # ---- batches: pieces of equal length together, at most max_duration seconds of audio per batch; with ragged_batches (whole
     #      recordings, window_seconds None) pieces of any length together, padded to the batch's longest, each row run on its own
@@ -401,6 +471,8 @@ def predict_vad(**kwargs):
             labels, intervals = piece_post[j]
             results.append({"recording_id": r["id"], "num_frames": int(labels.shape[0]), "labels": labels.cpu().numpy().astype(np.uint8),
                             "probs": piece_probs[j].cpu().numpy(), "intervals": intervals})
+            if dev_labels is not None:
+                dev_labels[ri] = labels
             continue
         rows_l, rows_p = [], []
         by_len = {}
@@ -440,6 +512,10 @@ def predict_vad(**kwargs):
             intervals = labels_to_intervals_batch(labels.unsqueeze(0), frame_shift)[0]   # run-length walk on the GPU (uvad_label_runs)
         results.append({"recording_id": r["id"], "num_frames": int(labels.shape[0]), "labels": labels.cpu().numpy().astype(np.uint8),
                         "probs": probs.cpu().numpy(), "intervals": intervals})
+        if dev_labels is not None:
+            dev_labels[ri] = labels
+    if cuts is not None:
+        _attach_cuts(results, recs, dev_labels, rt, cuts, sincnet, frame_shift, device, int(kwargs["max_duration"] * sr), sr)
     return _write_results(results, kwargs)
 
 
