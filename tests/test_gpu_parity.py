@@ -676,6 +676,55 @@ def test_finalize_twice_hot_swaps_weights():
     assert leaked < 8 << 20, f"40 reloads leaked {leaked} bytes of device memory"
 
 
+def test_finalize_that_fails_late_leaves_nothing_behind():
+    """A uvad_finalize that fails at its LAST check (the classifier's shape: every other tensor is packed and uploaded by then) leaves the
+    context unfinalized and without a block, frees what it had uploaded, and does not touch a second context that shares the weights; the
+    next good load joins that context's block again, bit for bit."""
+    import gc
+    import uvad_amd
+    from oracle import torch_ref as tr
+    dev = torch.device("cuda:0")
+    gc.collect()   # (a context an earlier test left to the collector with these very weights would be counted by weights_shared_by)
+    sd_a = tr.seeded_state_dict(64, seed=11, scale=2.0)
+    sd_bad = dict(sd_a)
+    sd_bad["classifier.weight"] = torch.zeros(1, 127)
+    m = uvad_amd.PyanNet2(encoding_dim=64)
+    m.build()
+    cfg = {"encoding_dim": 64, "lstm": m.hparams.lstm, "linear": m.hparams.linear}
+    rt = uvad_amd.VadRuntime(device=dev, fbank=None, model=cfg)
+    twin = uvad_amd.VadRuntime(device=dev, fbank=None, model=cfg)
+    rt.load_state_dict(sd_a)
+    twin.load_state_dict(sd_a)
+    x = torch.randn(3, 50, 64, generator=torch.Generator().manual_seed(1)).to(dev) * 2 - 3
+    la = rt.classify(x, want_probs=False)[0].clone()
+    assert torch.equal(twin.classify(x, want_probs=False)[0], la)
+    assert rt.weights_shared_by() == 2 and twin.weights_shared_by() == 2
+
+    def cycle():
+        with pytest.raises(RuntimeError, match="classifier shape mismatch"):
+            rt.load_state_dict(sd_bad)
+        with pytest.raises(RuntimeError, match="uvad_finalize has not been called"):
+            rt.classify(x)
+        assert rt.weights_shared_by() == 0 and twin.weights_shared_by() == 1
+        assert torch.equal(twin.classify(x, want_probs=False)[0], la)
+        rt.load_state_dict(sd_a)
+        assert torch.equal(rt.classify(x, want_probs=False)[0], la)
+        assert rt.weights_shared_by() == 2 and twin.weights_shared_by() == 2
+
+    # one cycle BEFORE the baseline, as in test_finalize_twice_hot_swaps_weights: torch's first torch.equal of a process takes device memory
+    # of its own, which is not this library's
+    cycle()
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info(dev)[0]
+    for _ in range(20):
+        cycle()
+    torch.cuda.synchronize()
+    leaked = free0 - torch.cuda.mem_get_info(dev)[0]
+    assert leaked < 8 << 20, f"20 failed and 20 good reloads leaked {leaked} bytes of device memory"
+    rt.close()
+    twin.close()
+
+
 def test_contexts_with_identical_weights_share_one_upload_and_stay_independent():
     """uvad_finalize: contexts of the process that hold identical tensors / configuration on one device share the packed weights (one host-side
     packing and upload instead of one per context: uvad_weights_shared_by).  Sharing must be invisible: same logits bit for bit, a hot-swap in ONE

@@ -44,21 +44,27 @@ struct LayerDev {
 
 // Everything uvad_finalize produces from the host tensors: the device buffers (owned here, freed with the last owner) and the values derived
 // while packing.  Contexts that are finalized with IDENTICAL host tensors, model / SincNet configuration and device share one of these through a
-// process-wide cache (find_or_insert_packed): the twelve slots of a ForwardPipeline, or the three of predict_vad, repack and upload the 6 MB of
+// process-wide cache (packed_cache): the twelve slots of a ForwardPipeline, or the three of predict_vad, repack and upload the 6 MB of
 // weights once instead of once per context (host-side packing is ~45 ms per context: it was 0.18 of the 0.26 s predict_vad spends on a one-hour
 // recording).  Read-only on the device, so sharing needs no synchronisation; a weight hot-swap gives the swapping context a block of its own.
+// uvad_finalize fills a fresh block and publishes it only when every step has succeeded (a block dropped half-built frees its uploads);
+// from then on it is immutable -- contexts hold it as pointer-to-const -- and the launch code reads the weights through it.
 struct PackedWeights {
     int device = 0;
     std::vector<void *> allocs;
     std::vector<LayerDev> layers;
-    bool f16_ok = true;
-    std::vector<float *> lin_w, lin_b, lin_w_img;
+    bool f16_ok = true;   // every GEMM operand the weights determine fits the f16 range (gemm mode 1 is usable)
+    std::vector<float *> lin_w, lin_b;
+    std::vector<float *> lin_w_img;   // 128 x 128 layers as register images (lstm_stack.hip), else nullptr
     std::vector<unsigned short *> lin_w_split16;
     std::vector<float> lin_w_scale;
     float *cls_w = nullptr, *cls_b = nullptr;
-    bool sinc_ready = false, sinc_f16 = false;
+    // SincNet front end (sincnet.hip): packed only when its tensors were given (sinc_ready)
+    bool sinc_ready = false, sinc_f16 = false;   // sinc_f16: the split-f16 form below is packed and usable
     float *sn_wav_g = nullptr, *sn_wav_b = nullptr;
     float *sn_wt[3] = {nullptr, nullptr, nullptr}, *sn_bias[3] = {nullptr, nullptr, nullptr}, *sn_g[3] = {nullptr, nullptr, nullptr}, *sn_b[3] = {nullptr, nullptr, nullptr};
+    // ... and for the split-f16 form of the stages (sincnet_f16p.hip; GEMM modes 1 / 3): B-operand register images, 2^-S, padded biases,
+    // and the largest |gamma| / |beta| of the norm in FRONT of each stage (the f16 range guard of sincnet_impl)
     unsigned short *sn_wfrag[3] = {nullptr, nullptr, nullptr};
     float sn_wscale[3] = {1.f, 1.f, 1.f}, *sn_bias16[3] = {nullptr, nullptr, nullptr};
     float sn_in_gmax[3] = {0.f, 0.f, 0.f}, sn_in_bmax[3] = {0.f, 0.f, 0.f};
@@ -88,7 +94,7 @@ constexpr int SIDE_RETRY_AFTER = 256;       // calls after which a caller stream
 struct StreamCounters { int64_t n_samples = 0, n_frames = 0, n_steps = 0; };
 struct StreamState { float *h = nullptr, *c = nullptr; size_t layer_stride = 0; };
 struct WindowGroup { StreamCounters sc; int B = 0, W = 0, L = 0; };
-struct WavWindowGroup { int64_t n_samples = 0, n_frames = 0, n_steps = 0; int B = 0, W = 0, L = 0, is_i16 = 0; };
+struct WavWindowGroup { StreamCounters sc; int B = 0, W = 0, L = 0, is_i16 = 0; };
 // a slot pool (uvad_window_slots_*, uvad_window_wav_slots_*): only what reset fixes; every per-slot counter lives on the device
 struct SlotPool { int B = 0, chunk = 0, W = 0, L = 0, is_i16 = 0; };
 // an endpointer state (uvad_endpoint_*): what reset fixed; the device header holds the same and every per-slot quantity
@@ -115,30 +121,16 @@ struct uvad_ctx {
     float *d_window = nullptr, *d_mel_w = nullptr, *d_mel_wt = nullptr, *d_tw512 = nullptr;
     int *d_mel_start = nullptr, *d_mel_len = nullptr;
     int mel_stride = 0, mel_nyquist = 1;
-    std::vector<LayerDev> layers;
-    std::vector<float *> lin_w, lin_b;
-    std::vector<unsigned short *> lin_w_split16;
-    std::vector<float *> lin_w_img;   // 128 x 128 layers as register images (lstm_stack.hip), else nullptr
-    std::vector<float> lin_w_scale;
-    bool f16_ok = true;   // every GEMM operand the weights determine fits the f16 range (gemm mode 1 is usable)
     int gemm_mode = 1;    // 0: exact f32 MFMA (gemm.hip); 1: split-f16 x3 (gemm_f16p.hip)
     int rec_tile_mode = 0, rec_tile_used = 0;   // sequences per recurrent workgroup: requested (0 = by batch size) / last launched
-    float *cls_w = nullptr, *cls_b = nullptr;
     // SincNet front end (sincnet.hip)
-    bool has_sinc = false, sinc_ready = false;
+    bool has_sinc = false;
     uvad_sincnet_cfg sc{};
-    float *sn_wav_g = nullptr, *sn_wav_b = nullptr;
-    float *sn_wt[3] = {nullptr, nullptr, nullptr}, *sn_bias[3] = {nullptr, nullptr, nullptr};
-    float *sn_g[3] = {nullptr, nullptr, nullptr}, *sn_b[3] = {nullptr, nullptr, nullptr};
-    // ... and for the split-f16 form of the stages (sincnet_f16p.hip; GEMM modes 1 / 3): B-operand register images, 2^-S, padded biases,
-    // and the largest |gamma| / |beta| of the norm in FRONT of each stage (the f16 range guard of sincnet_impl)
-    bool sinc_f16 = false, sinc_f16_used = false;   // packed and usable / what the most recent uvad_sincnet ran
-    unsigned short *sn_wfrag[3] = {nullptr, nullptr, nullptr};
-    float sn_wscale[3] = {1.f, 1.f, 1.f}, *sn_bias16[3] = {nullptr, nullptr, nullptr};
-    float sn_in_gmax[3] = {0.f, 0.f, 0.f}, sn_in_bmax[3] = {0.f, 0.f, 0.f};
+    bool sinc_f16_used = false;          // the form the most recent uvad_sincnet ran (1: split-f16)
     std::vector<void *> allocs;          // feature tables, twiddles: live as long as the context
-    std::vector<void *> weight_allocs;   // what the uvad_finalize in progress has uploaded so far (moved into `packed` when it succeeds)
-    std::shared_ptr<PackedWeights> packed;   // the finalized weights this context uses (possibly shared with other contexts: PackedWeights)
+    // the finalized weights, the only thing the context knows about them (possibly shared with other contexts: PackedWeights); set
+    // whenever `finalized` is, and kept after uvad_set_weight until the next uvad_finalize
+    std::shared_ptr<const PackedWeights> packed;
     // timing
     bool timing = false;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -187,11 +179,18 @@ int hip_fail(uvad_ctx *c, hipError_t e, const char *what) {
 
 size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
+// The two questions the launch code asks of the finalized weights besides their pointers.  (f16_planes: callers have checked `finalized`.)
+// split-f16 GEMMs are on and every operand the weights determine fits the f16 range: activations, and features, travel as f16 planes
+bool f16_planes(const uvad_ctx *c) { return c->gemm_mode >= 1 && c->packed->f16_ok; }
+// finalized with the SincNet tensors (uvad_sincnet_configure and uvad_set_weight clear `finalized`)
+bool sinc_weights_ready(const uvad_ctx *c) { return c->finalized && c->packed->sinc_ready; }
+
+// `owner`: the list the allocation is freed with (the context's tables, or the PackedWeights block a uvad_finalize is filling)
 template <typename T>
-int dev_upload(uvad_ctx *c, const T *host, size_t n, T **out, bool weight = false) {
+int dev_upload(uvad_ctx *c, std::vector<void *> &owner, const T *host, size_t n, T **out) {
     void *p = nullptr;
     HIPCHK(c, hipMalloc(&p, n * sizeof(T) ? n * sizeof(T) : sizeof(T)));
-    (weight ? c->weight_allocs : c->allocs).push_back(p);
+    owner.push_back(p);
     if (n) HIPCHK(c, hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice));
     *out = reinterpret_cast<T *>(p);
     return UVAD_OK;
@@ -345,7 +344,7 @@ int uvad_create(int device, const uvad_fbank_cfg *fb, const uvad_model_cfg *mode
             tw[2 * j] = (float)std::cos(a);
             tw[2 * j + 1] = (float)(-std::sin(a));
         }
-        int r = dev_upload(c, tw.data(), tw.size(), &c->d_tw512);
+        int r = dev_upload(c, c->allocs, tw.data(), tw.size(), &c->d_tw512);
         if (r) return r;
     }
     if (model) {
@@ -442,15 +441,15 @@ int uvad_set_tables(uvad_ctx *c, const float *window, const float *mel) {
     for (int m = 0; m < F; ++m)
         for (int i = 0; i < ln[m]; ++i) w[(size_t)m * maxlen + i] = mel[(size_t)m * nb + st[m] + i];
     int r;
-    if ((r = dev_upload(c, window, (size_t)c->fb.frame_len, &c->d_window))) return r;
-    if ((r = dev_upload(c, st.data(), st.size(), &c->d_mel_start))) return r;
-    if ((r = dev_upload(c, ln.data(), ln.size(), &c->d_mel_len))) return r;
-    if ((r = dev_upload(c, w.data(), w.size(), &c->d_mel_w))) return r;
+    if ((r = dev_upload(c, c->allocs, window, (size_t)c->fb.frame_len, &c->d_window))) return r;
+    if ((r = dev_upload(c, c->allocs, st.data(), st.size(), &c->d_mel_start))) return r;
+    if ((r = dev_upload(c, c->allocs, ln.data(), ln.size(), &c->d_mel_len))) return r;
+    if ((r = dev_upload(c, c->allocs, w.data(), w.size(), &c->d_mel_w))) return r;
     const int ld_t = mel_image_ld(F);
     std::vector<float> wt(mel_image_floats(maxlen, F), 0.0f);
     for (int m = 0; m < F; ++m)
         for (int i = 0; i < ln[m]; ++i) wt[(size_t)i * ld_t + m] = 0.25f * w[(size_t)m * maxlen + i];   // the spectrum split leaves 4 |X|^2 (fbank_pair.h): exact
-    if ((r = dev_upload(c, wt.data(), wt.size(), &c->d_mel_wt))) return r;
+    if ((r = dev_upload(c, c->allocs, wt.data(), wt.size(), &c->d_mel_wt))) return r;
     c->tables_set = true;
     return UVAD_OK;
 }
@@ -474,21 +473,10 @@ int uvad_set_weight(uvad_ctx *c, const char *torch_key, const float *host, const
 extern "C++" {
 namespace {
 void free_weights(uvad_ctx *c) {
-    for (void *p : c->weight_allocs) (void)hipFree(p);   // (leftovers of a uvad_finalize that failed half-way)
-    c->weight_allocs.clear();
-    c->packed.reset();                                   // the shared block goes with its last owner
     for (auto &ev : c->layer_ev)
         if (ev) (void)hipEventDestroy(ev);
     c->layer_ev.clear();
-    c->layers.clear();
-    c->lin_w.clear(); c->lin_b.clear(); c->lin_w_split16.clear(); c->lin_w_scale.clear(); c->lin_w_img.clear();
-    c->cls_w = c->cls_b = nullptr;
-    c->sn_wav_g = c->sn_wav_b = nullptr;
-    for (int i = 0; i < 3; ++i) {
-        c->sn_wt[i] = c->sn_bias[i] = c->sn_g[i] = c->sn_b[i] = c->sn_bias16[i] = nullptr;
-        c->sn_wfrag[i] = nullptr;
-    }
-    c->sinc_ready = c->sinc_f16 = false;
+    c->packed.reset();   // the shared block goes with its last owner
     c->finalized = false;
 }
 }  // namespace
@@ -532,38 +520,7 @@ WeightKey weight_key(const uvad_ctx *c) {
     return k;
 }
 std::mutex packed_mu;
-std::map<WeightKey, std::weak_ptr<PackedWeights>> packed_cache;
-
-// the context's view of a block: plain copies of the pointers and flags (the launch code reads them from the context as before)
-void adopt_packed(uvad_ctx *c, const std::shared_ptr<PackedWeights> &pw) {
-    c->packed = pw;
-    c->layers = pw->layers; c->f16_ok = pw->f16_ok;
-    c->lin_w = pw->lin_w; c->lin_b = pw->lin_b; c->lin_w_img = pw->lin_w_img; c->lin_w_split16 = pw->lin_w_split16; c->lin_w_scale = pw->lin_w_scale;
-    c->cls_w = pw->cls_w; c->cls_b = pw->cls_b;
-    c->sinc_ready = pw->sinc_ready; c->sinc_f16 = pw->sinc_f16;
-    c->sn_wav_g = pw->sn_wav_g; c->sn_wav_b = pw->sn_wav_b;
-    for (int i = 0; i < 3; ++i) {
-        c->sn_wt[i] = pw->sn_wt[i]; c->sn_bias[i] = pw->sn_bias[i]; c->sn_g[i] = pw->sn_g[i]; c->sn_b[i] = pw->sn_b[i];
-        c->sn_wfrag[i] = pw->sn_wfrag[i]; c->sn_wscale[i] = pw->sn_wscale[i]; c->sn_bias16[i] = pw->sn_bias16[i];
-        c->sn_in_gmax[i] = pw->sn_in_gmax[i]; c->sn_in_bmax[i] = pw->sn_in_bmax[i];
-    }
-}
-std::shared_ptr<PackedWeights> snapshot_packed(uvad_ctx *c) {
-    auto pw = std::make_shared<PackedWeights>();
-    pw->device = c->device;
-    pw->allocs.swap(c->weight_allocs);
-    pw->layers = c->layers; pw->f16_ok = c->f16_ok;
-    pw->lin_w = c->lin_w; pw->lin_b = c->lin_b; pw->lin_w_img = c->lin_w_img; pw->lin_w_split16 = c->lin_w_split16; pw->lin_w_scale = c->lin_w_scale;
-    pw->cls_w = c->cls_w; pw->cls_b = c->cls_b;
-    pw->sinc_ready = c->sinc_ready; pw->sinc_f16 = c->sinc_f16;
-    pw->sn_wav_g = c->sn_wav_g; pw->sn_wav_b = c->sn_wav_b;
-    for (int i = 0; i < 3; ++i) {
-        pw->sn_wt[i] = c->sn_wt[i]; pw->sn_bias[i] = c->sn_bias[i]; pw->sn_g[i] = c->sn_g[i]; pw->sn_b[i] = c->sn_b[i];
-        pw->sn_wfrag[i] = c->sn_wfrag[i]; pw->sn_wscale[i] = c->sn_wscale[i]; pw->sn_bias16[i] = c->sn_bias16[i];
-        pw->sn_in_gmax[i] = c->sn_in_gmax[i]; pw->sn_in_bmax[i] = c->sn_in_bmax[i];
-    }
-    return pw;
-}
+std::map<WeightKey, std::weak_ptr<const PackedWeights>> packed_cache;
 }  // namespace
 }  // extern "C++"
 
@@ -573,7 +530,8 @@ int uvad_finalize(uvad_ctx *c) {
     HIPCHK(c, hipSetDevice(c->device));
     // Idempotent: a second call (e.g. after swapping weights with uvad_set_weight) replaces the previous upload.
     // Kernels of earlier calls may still be reading the old buffers.
-    if (c->packed || !c->weight_allocs.empty()) HIPCHK(c, hipDeviceSynchronize());
+    // The previous block goes before packing starts, so the peak is one block.
+    if (c->packed) HIPCHK(c, hipDeviceSynchronize());
     free_weights(c);
     const uvad_model_cfg &m = c->mc;
     const int H = m.hidden, D = m.bidirectional ? 2 : 1;
@@ -583,10 +541,10 @@ int uvad_finalize(uvad_ctx *c) {
         std::lock_guard<std::mutex> lk(packed_mu);
         auto it = packed_cache.find(wkey);
         if (it != packed_cache.end()) {
-            if (std::shared_ptr<PackedWeights> pw = it->second.lock()) {
-                adopt_packed(c, pw);
+            if (std::shared_ptr<const PackedWeights> hit = it->second.lock()) {
                 c->layer_ev.assign((size_t)2 * m.num_layers + 2, nullptr);
                 for (auto &ev : c->layer_ev) HIPCHK(c, hipEventCreate(&ev));
+                c->packed = hit;
                 c->finalized = true;
                 return UVAD_OK;
             }
@@ -597,8 +555,12 @@ int uvad_finalize(uvad_ctx *c) {
         auto it = c->host_w.find(k);
         return it == c->host_w.end() ? nullptr : &it->second;
     };
-    c->layers.assign(m.num_layers, LayerDev());
-    c->f16_ok = true;
+    // A block of this call's own: every early return below drops it, and its destructor frees what was uploaded so far.
+    const std::shared_ptr<PackedWeights> pw = std::make_shared<PackedWeights>();
+    PackedWeights &W = *pw;
+    W.device = c->device;
+    auto upload = [&](const auto *host, size_t n, auto **out) { return dev_upload(c, W.allocs, host, n, out); };
+    W.layers.assign(m.num_layers, LayerDev());
     for (int k = 0; k < m.num_layers; ++k) {
         const int in = k == 0 ? m.in_dim : H * D;
         const int inp = gemm_padded_k(in);   // rows zero-padded to the GEMM's K-step
@@ -635,33 +597,33 @@ int uvad_finalize(uvad_ctx *c) {
                 hh16ok = false;
             if (H == 128 && !pack_whh16h_p2q(whh->data.data(), &hh16q[(size_t)d * whh16h_p2q_elems()], &hh16q_scale)) hh16q_ok = false;
         }
-        LayerDev &L = c->layers[k];
+        LayerDev &L = W.layers[k];
         L.in = in;
         int r;
-        if ((r = dev_upload(c, wp.data(), wp.size(), &L.w_ih, true))) return r;
+        if ((r = upload(wp.data(), wp.size(), &L.w_ih))) return r;
         {
             std::vector<unsigned short> sp(3 * weight_plane_elems(D * 4 * H, inp));
-            if (!split_weights_f16x3(wp.data(), D * 4 * H, inp, sp.data(), &L.w_ih_scale)) c->f16_ok = false;
-            if ((r = dev_upload(c, sp.data(), sp.size(), &L.w_ih_split16, true))) return r;
+            if (!split_weights_f16x3(wp.data(), D * 4 * H, inp, sp.data(), &L.w_ih_scale)) W.f16_ok = false;
+            if ((r = upload(sp.data(), sp.size(), &L.w_ih_split16))) return r;
         }
-        if ((r = dev_upload(c, bp.data(), bp.size(), &L.bias, true))) return r;
-        if ((r = dev_upload(c, hh.data(), hh.size(), &L.w_hh, true))) return r;
-        if (!ih_img.empty() && (r = dev_upload(c, ih_img.data(), ih_img.size(), &L.w_ih_img, true))) return r;
+        if ((r = upload(bp.data(), bp.size(), &L.bias))) return r;
+        if ((r = upload(hh.data(), hh.size(), &L.w_hh))) return r;
+        if (!ih_img.empty() && (r = upload(ih_img.data(), ih_img.size(), &L.w_ih_img))) return r;
         if (H == 128) {
-            if ((r = dev_upload(c, hh16r.data(), hh16r.size(), &L.w_hh16_regs, true))) return r;
-            if ((r = dev_upload(c, hh16p.data(), hh16p.size(), &L.w_hh16_p2, true))) return r;
+            if ((r = upload(hh16r.data(), hh16r.size(), &L.w_hh16_regs))) return r;
+            if ((r = upload(hh16p.data(), hh16p.size(), &L.w_hh16_p2))) return r;
             L.w_hh16_p2q = nullptr;
             L.w_hh16_p2q_scale = hh16q_scale;
-            if (hh16q_ok && (r = dev_upload(c, hh16q.data(), hh16q.size(), &L.w_hh16_p2q, true))) return r;
-            if ((r = dev_upload(c, hh16s.data(), hh16s.size(), &L.w_hh16_scale, true))) return r;
+            if (hh16q_ok && (r = upload(hh16q.data(), hh16q.size(), &L.w_hh16_p2q))) return r;
+            if ((r = upload(hh16s.data(), hh16s.size(), &L.w_hh16_scale))) return r;
         }
         L.w_hh16_ok = hh16ok;
     }
-    c->lin_w.assign(m.lin_layers, nullptr);
-    c->lin_b.assign(m.lin_layers, nullptr);
-    c->lin_w_split16.assign(m.lin_layers, nullptr);
-    c->lin_w_img.assign(m.lin_layers, nullptr);
-    c->lin_w_scale.assign(m.lin_layers, 1.0f);
+    W.lin_w.assign(m.lin_layers, nullptr);
+    W.lin_b.assign(m.lin_layers, nullptr);
+    W.lin_w_split16.assign(m.lin_layers, nullptr);
+    W.lin_w_img.assign(m.lin_layers, nullptr);
+    W.lin_w_scale.assign(m.lin_layers, 1.0f);
     int prev = H * D;
     // Static bound on what the feed-forward GEMMs can be fed: |h| < 1 out of the LSTM, so |z_j| <= sum_k |w_jk| * amax + |b_j|
     // (leaky_relu does not grow magnitudes for slopes in [-1, 1]).  If that can leave the f16 range the split-f16 GEMM is not used.
@@ -682,36 +644,34 @@ int uvad_finalize(uvad_ctx *c) {
             const double z = l1 * amax + std::fabs((double)b->data[o]);
             if (!(z <= zmax)) zmax = z;   // NaN-propagating max
         }
-        if ((r = dev_upload(c, wpad.data(), wpad.size(), &c->lin_w[j], true))) return r;
+        if ((r = upload(wpad.data(), wpad.size(), &W.lin_w[j]))) return r;
         {
             std::vector<unsigned short> sp(3 * weight_plane_elems(m.lin_hidden, prevp));
-            if (!split_weights_f16x3(wpad.data(), m.lin_hidden, prevp, sp.data(), &c->lin_w_scale[j])) c->f16_ok = false;
-            if ((r = dev_upload(c, sp.data(), sp.size(), &c->lin_w_split16[j], true))) return r;
+            if (!split_weights_f16x3(wpad.data(), m.lin_hidden, prevp, sp.data(), &W.lin_w_scale[j])) W.f16_ok = false;
+            if ((r = upload(sp.data(), sp.size(), &W.lin_w_split16[j]))) return r;
         }
-        if ((r = dev_upload(c, b->data.data(), b->data.size(), &c->lin_b[j], true))) return r;
+        if ((r = upload(b->data.data(), b->data.size(), &W.lin_b[j]))) return r;
         if (m.lin_hidden == 128 && prev == 128) {   // the streaming step's in-launch head (lstm_stack.hip)
             std::vector<float> img(fc_image_elems());
             pack_fc_image(w->data.data(), img.data());
-            if ((r = dev_upload(c, img.data(), img.size(), &c->lin_w_img[j], true))) return r;
+            if ((r = upload(img.data(), img.size(), &W.lin_w_img[j]))) return r;
         }
         amax = zmax * std::fmax(1.0, std::fabs((double)m.leaky_slope));
-        if (j + 1 < m.lin_layers && !(amax < 65504.0)) c->f16_ok = false;   // the next feed-forward GEMM would see it
+        if (j + 1 < m.lin_layers && !(amax < 65504.0)) W.f16_ok = false;   // the next feed-forward GEMM would see it
         prev = m.lin_hidden;
     }
     const HostTensor *cw = get("classifier.weight"), *cb = get("classifier.bias");
     if (!cw || !cb) return fail(c, UVAD_E_STATE, "missing classifier tensors");
     if (!expect_shape(*cw, {1, prev}) || !expect_shape(*cb, {1})) return fail(c, UVAD_E_ARG, "classifier shape mismatch");
     int r;
-    if ((r = dev_upload(c, cw->data.data(), cw->data.size(), &c->cls_w, true))) return r;
-    if ((r = dev_upload(c, cb->data.data(), cb->data.size(), &c->cls_b, true))) return r;
-    c->layer_ev.assign((size_t)2 * m.num_layers + 2, nullptr);
-    for (auto &ev : c->layer_ev) HIPCHK(c, hipEventCreate(&ev));
+    if ((r = upload(cw->data.data(), cw->data.size(), &W.cls_w))) return r;
+    if ((r = upload(cb->data.data(), cb->data.size(), &W.cls_b))) return r;
     if (c->has_sinc && get("sincnet.conv1d.0.filters")) {   // the stage is optional: packed only when its tensors were given
         const uvad_sincnet_cfg &q = c->sc;
         const HostTensor *wg = get("sincnet.wav_norm1d.weight"), *wb = get("sincnet.wav_norm1d.bias");
         if (!wg || !wb || !expect_shape(*wg, {1}) || !expect_shape(*wb, {1})) return fail(c, UVAD_E_STATE, "missing / misshaped sincnet.wav_norm1d tensors");
-        if ((r = dev_upload(c, wg->data.data(), 1, &c->sn_wav_g, true))) return r;
-        if ((r = dev_upload(c, wb->data.data(), 1, &c->sn_wav_b, true))) return r;
+        if ((r = upload(wg->data.data(), 1, &W.sn_wav_g))) return r;
+        if ((r = upload(wb->data.data(), 1, &W.sn_wav_b))) return r;
         const int cin[3] = {1, q.n_filters, q.c2}, cout[3] = {q.n_filters, q.c2, q.c3}, kw[3] = {q.kernel_size, q.k2, q.k3};
         for (int i = 0; i < 3; ++i) {
             const std::string id = std::to_string(i);
@@ -731,22 +691,22 @@ int uvad_finalize(uvad_ctx *c) {
                         wt[(size_t)(t * cin[i] + ci) * NW + n] = w->data[((size_t)n * cin[i] + ci) * kw[i] + t];
                 if (b) bias[n] = b->data[n];
             }
-            if ((r = dev_upload(c, wt.data(), wt.size(), &c->sn_wt[i], true))) return r;
-            if ((r = dev_upload(c, bias.data(), bias.size(), &c->sn_bias[i], true))) return r;
-            if ((r = dev_upload(c, g->data.data(), g->data.size(), &c->sn_g[i], true))) return r;
-            if ((r = dev_upload(c, be->data.data(), be->data.size(), &c->sn_b[i], true))) return r;
+            if ((r = upload(wt.data(), wt.size(), &W.sn_wt[i]))) return r;
+            if ((r = upload(bias.data(), bias.size(), &W.sn_bias[i]))) return r;
+            if ((r = upload(g->data.data(), g->data.size(), &W.sn_g[i]))) return r;
+            if ((r = upload(be->data.data(), be->data.size(), &W.sn_b[i]))) return r;
             // the norm in FRONT of stage i + 1 (stage 0's is the waveform norm): bounds for the f16 range guard
             if (i < 2) {
                 float gm = 0.f, bm = 0.f;
                 for (float v : g->data) gm = std::max(gm, std::fabs(v));
                 for (float v : be->data) bm = std::max(bm, std::fabs(v));
-                c->sn_in_gmax[i + 1] = gm; c->sn_in_bmax[i + 1] = bm;
+                W.sn_in_gmax[i + 1] = gm; W.sn_in_bmax[i + 1] = bm;
             }
         }
-        c->sn_in_gmax[0] = std::fabs(wg->data[0]); c->sn_in_bmax[0] = std::fabs(wb->data[0]);
+        W.sn_in_gmax[0] = std::fabs(wg->data[0]); W.sn_in_bmax[0] = std::fabs(wb->data[0]);
         // the split-f16 form of the stages (sincnet_f16p.hip): W[n][k] in the stage's K order -> three exact f16 planes as register images
-        c->sinc_f16 = sinc_f16p_supported(q.n_filters, q.kernel_size, q.stride, q.c2, q.k2, q.c3, q.k3);
-        for (int i = 0; i < 3 && c->sinc_f16; ++i) {
+        W.sinc_f16 = sinc_f16p_supported(q.n_filters, q.kernel_size, q.stride, q.c2, q.k2, q.c3, q.k3);
+        for (int i = 0; i < 3 && W.sinc_f16; ++i) {
             const std::string id = std::to_string(i);
             const HostTensor *w = get(i == 0 ? std::string("sincnet.conv1d.0.filters") : "sincnet.conv1d." + id + ".weight");
             const HostTensor *b = i == 0 ? nullptr : get("sincnet.conv1d." + id + ".bias");
@@ -762,14 +722,15 @@ int uvad_finalize(uvad_ctx *c) {
                 if (b) bias[n] = b->data[n];
             }
             std::vector<unsigned short> frag(sinc_f16p_wfrag_elems(i));
-            if (!sinc_f16p_pack_weights(i, wn.data(), cout[i], ldk, frag.data(), &c->sn_wscale[i])) { c->sinc_f16 = false; break; }   // a non-finite weight: exact kernels
-            if ((r = dev_upload(c, frag.data(), frag.size(), &c->sn_wfrag[i], true))) return r;
-            if ((r = dev_upload(c, bias.data(), bias.size(), &c->sn_bias16[i], true))) return r;
+            if (!sinc_f16p_pack_weights(i, wn.data(), cout[i], ldk, frag.data(), &W.sn_wscale[i])) { W.sinc_f16 = false; break; }   // a non-finite weight: exact kernels
+            if ((r = upload(frag.data(), frag.size(), &W.sn_wfrag[i]))) return r;
+            if ((r = upload(bias.data(), bias.size(), &W.sn_bias16[i]))) return r;
         }
-        c->sinc_ready = true;
+        W.sinc_ready = true;
     }
-    {   // the uploads become a block other contexts with the same weights can share
-        std::shared_ptr<PackedWeights> pw = snapshot_packed(c);
+    c->layer_ev.assign((size_t)2 * m.num_layers + 2, nullptr);
+    for (auto &ev : c->layer_ev) HIPCHK(c, hipEventCreate(&ev));
+    {   // complete: the context's weights from here on, and a block other contexts with the same weights can share
         c->packed = pw;
         std::lock_guard<std::mutex> lk(packed_mu);
         for (auto it = packed_cache.begin(); it != packed_cache.end();)   // (entries whose block is gone: a process that cycles through weight sets)
@@ -806,8 +767,7 @@ int uvad_sincnet_configure(uvad_ctx *c, const uvad_sincnet_cfg *q) {
     }
     c->sc = *q;
     c->has_sinc = true;
-    c->sinc_ready = false;
-    c->finalized = false;
+    c->finalized = false;   // (with it, "the SincNet weights are ready": sinc_weights_ready)
     return UVAD_OK;
 }
 
@@ -830,7 +790,8 @@ size_t uvad_sincnet_workspace_bytes(const uvad_ctx *c, int B, int64_t S) {
 static int sincnet_impl(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64_t S, float *d_feats, void *ws, size_t ws_bytes, hipStream_t s,
                         const int64_t *nsamp = nullptr, const int **row_T = nullptr) {
     if (!c->has_sinc) return fail(c, UVAD_E_STATE, "uvad_sincnet: uvad_sincnet_configure has not been called");
-    if (!c->finalized || !c->sinc_ready) return fail(c, UVAD_E_STATE, "uvad_sincnet: SincNet tensors not set / uvad_finalize not called");
+    if (!sinc_weights_ready(c)) return fail(c, UVAD_E_STATE, "uvad_sincnet: SincNet tensors not set / uvad_finalize not called");
+    const PackedWeights &W = *c->packed;
     const SincLayout l = sinc_carve(c, B, S);
     if (!l.ok) return fail(c, UVAD_E_ARG, "uvad_sincnet: waveform too short for one output frame");
     if (l.Lconv[0] > 0x7fffffff / 4) return fail(c, UVAD_E_UNSUPPORTED, "uvad_sincnet: waveform too long");
@@ -857,18 +818,18 @@ static int sincnet_impl(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64
         if (row_T) *row_T = T_rows;
     }
     const int *row_n = nsamp ? rows16[0].lin : nullptr;
-    if (wav16) HIPCHK(c, launch_wav_stats(wav16, B, S, S, c->sn_wav_g, c->sn_wav_b, q.eps, s0, s0 + B, s, row_n));
-    else HIPCHK(c, launch_wav_stats(static_cast<const float *>(d_wav), B, S, S, c->sn_wav_g, c->sn_wav_b, q.eps, s0, s0 + B, s, row_n));
+    if (wav16) HIPCHK(c, launch_wav_stats(wav16, B, S, S, W.sn_wav_g, W.sn_wav_b, q.eps, s0, s0 + B, s, row_n));
+    else HIPCHK(c, launch_wav_stats(static_cast<const float *>(d_wav), B, S, S, W.sn_wav_g, W.sn_wav_b, q.eps, s0, s0 + B, s, row_n));
     const float *in = wav16 ? nullptr : static_cast<const float *>(d_wav), *in_scale = s0, *in_shift = s0 + B;
     // Split-f16 form (GEMM modes 1 / 3) when the geometry is the reference's and every stage input provably fits the f16 range: an
     // instance-normalised value is at most sqrt(L - 1) in magnitude, so |gamma| * sqrt(L) + |beta| bounds what the staging converts, and
     // the leaky_relu in front of stages 2 and 3 scales that by at most max(1, |slope|).  The staging of those stages applies leaky_relu
     // as max(e, e * slope), which is leaky_relu only for slope <= 1: a larger slope runs the exact-f32 stages.  A lens call checks the
     // padded S, which bounds every row: it can run the exact form where one of its rows alone would run the split form.
-    bool f16 = l.f16 && c->sinc_f16 && (c->gemm_mode == 1 || c->gemm_mode == 3) && q.leaky_slope <= 1.0f;
+    bool f16 = l.f16 && W.sinc_f16 && (c->gemm_mode == 1 || c->gemm_mode == 3) && q.leaky_slope <= 1.0f;
     const double act = std::fmax(1.0, std::fabs((double)q.leaky_slope));
     for (int i = 0; i < 3 && f16; ++i)
-        if (!((c->sn_in_gmax[i] * std::sqrt((double)l.Lin[i]) + c->sn_in_bmax[i]) * (i > 0 ? act : 1.0) < 60000.0)) f16 = false;
+        if (!((W.sn_in_gmax[i] * std::sqrt((double)l.Lin[i]) + W.sn_in_bmax[i]) * (i > 0 ? act : 1.0) < 60000.0)) f16 = false;
     c->sinc_f16_used = f16;
     if (f16) {
         for (int i = 0; i < 3; ++i) {
@@ -878,11 +839,11 @@ static int sincnet_impl(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64
             SincF16Args a{};
             a.in = in; a.in_i16 = i == 0 ? wav16 : nullptr; a.in_bstride = S; a.Lin = (int)l.Lin[i];
             a.in_scale = in_scale; a.in_shift = in_shift; a.n_in = l.Cin[i]; a.slope = q.leaky_slope;
-            a.Wfrag = c->sn_wfrag[i]; a.wscale = c->sn_wscale[i]; a.bias = c->sn_bias16[i];
+            a.Wfrag = W.sn_wfrag[i]; a.wscale = W.sn_wscale[i]; a.bias = W.sn_bias16[i];
             a.Lpool = (int)l.Lpool[i]; a.ntiles = l.ntiles16[i];
             a.out = P; a.partials = part; a.B = B; a.n_cu = c->n_cu;
             HIPCHK(c, launch_sinc_conv_f16p(i, a, s, nsamp ? &rows16[i] : nullptr));
-            HIPCHK(c, launch_norm_finalize_f16p(i, part, B, l.ntiles16[i], l.Cout[i], (int)l.Lpool[i], c->sn_g[i], c->sn_b[i], q.eps, sc,
+            HIPCHK(c, launch_norm_finalize_f16p(i, part, B, l.ntiles16[i], l.Cout[i], (int)l.Lpool[i], W.sn_g[i], W.sn_b[i], q.eps, sc,
                                                 sc + (size_t)B * l.Cout[i], s, nsamp ? &rows16[i] : nullptr));
             in = P; in_scale = sc; in_shift = sc + (size_t)B * l.Cout[i];
         }
@@ -896,12 +857,12 @@ static int sincnet_impl(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64
         SincConvArgs a{};
         a.in = in; a.in_i16 = i == 0 ? wav16 : nullptr; a.in_bstride = (long long)l.Cin[i] * l.Lin[i]; a.Cin = l.Cin[i]; a.Lin = (int)l.Lin[i];
         a.in_scale = in_scale; a.in_shift = in_shift; a.in_lrelu = i > 0; a.slope = q.leaky_slope;
-        a.Wt2 = c->sn_wt[i]; a.bias = c->sn_bias[i];
+        a.Wt2 = W.sn_wt[i]; a.bias = W.sn_bias[i];
         a.Kw = l.Kw[i]; a.stride = l.stride[i]; a.Ktot = l.Cin[i] * l.Kw[i]; a.Kp = (a.Ktot + 7) / 8 * 8; a.Cout = l.Cout[i]; a.do_abs = i == 0;
         a.Lconv = (int)l.Lconv[i]; a.Lpool = (int)l.Lpool[i]; a.ntiles = l.ntiles[i];
         a.out = P; a.partials = part; a.B = B; a.n_cu = c->n_cu;
         HIPCHK(c, launch_sinc_conv(a, s, nsamp ? &rows32[i] : nullptr));
-        HIPCHK(c, launch_norm_finalize(part, B, l.ntiles[i], l.pt[i], l.phases[i], l.NW[i], l.Cout[i], (int)l.Lpool[i], c->sn_g[i], c->sn_b[i], q.eps, sc,
+        HIPCHK(c, launch_norm_finalize(part, B, l.ntiles[i], l.pt[i], l.phases[i], l.NW[i], l.Cout[i], (int)l.Lpool[i], W.sn_g[i], W.sn_b[i], q.eps, sc,
                                        sc + (size_t)B * l.Cout[i], s, nsamp ? &rows32[i] : nullptr));
         in = P; in_scale = sc; in_shift = sc + (size_t)B * l.Cout[i];
     }
@@ -940,57 +901,6 @@ int uvad_sincnet_lens_i16(uvad_ctx *c, const int16_t *d_wav, int B, int64_t S, c
     return sincnet_lens_entry(c, d_wav, 1, B, S, d_nsamp, d_feats, ws, ws_bytes, stream);
 }
 
-static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float *d_logits, float *d_probs,
-                         void *ws, size_t ws_bytes, hipStream_t s, bool record_start, bool check_range,
-                         const StreamState *ss, int ld_out, bool feats_in_planes, const FbankArgs *fused_fb, const int *lens = nullptr);
-
-// nsamp (uvad_forward_wav_lens): the SincNet stage in its lens form, then the classifier with lens = the rows' frame counts T_b (the
-// geometry block of the SincNet workspace): time chunks off, outputs at t >= T_b exactly +0.
-static int forward_wav_impl(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64_t S, float *d_logits, float *d_probs,
-                            void *ws, size_t ws_bytes, void *stream, const int64_t *nsamp = nullptr) {
-    if (!c) return UVAD_E_ARG;
-    if (!d_wav || B <= 0 || S <= 0 || !ws) return fail(c, UVAD_E_ARG, "uvad_forward_wav: bad argument");
-    if (!c->has_sinc) return fail(c, UVAD_E_STATE, "uvad_forward_wav: uvad_sincnet_configure has not been called");
-    if (!c->finalized) return fail(c, UVAD_E_STATE, "uvad_forward_wav: uvad_finalize has not been called");
-    const int64_t T = uvad_sincnet_num_frames(c, S);
-    if (T <= 0 || T > 0x7fffffff) return fail(c, UVAD_E_ARG, "uvad_forward_wav: waveform too short for one output frame");
-    const WsLayout w = carve(c, B, T);
-    const size_t sn = sinc_carve(c, B, S).total;
-    if (ws_bytes < w.total + sn) return fail(c, UVAD_E_WORKSPACE, "workspace too small: need " + std::to_string(w.total + sn) + " bytes");
-    char *base = reinterpret_cast<char *>(ws);
-    float *feats = reinterpret_cast<float *>(base + w.off_feats);
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (c->timing) HIPCHK(c, hipEventRecord(c->ev[0], s));
-    const int *lens = nullptr;
-    int r = sincnet_impl(c, d_wav, is_i16, B, S, feats, base + w.total, ws_bytes - w.total, s, nsamp, &lens);
-    if (r) return r;
-    return classify_impl(c, feats, B, (int)T, d_logits, d_probs, ws, w.total, s, false, true, nullptr, 0, false, nullptr, lens);
-}
-
-int uvad_forward_wav(uvad_ctx *c, const float *d_wav, int B, int64_t S, float *d_logits, float *d_probs,
-                     void *ws, size_t ws_bytes, void *stream) {
-    return forward_wav_impl(c, d_wav, 0, B, S, d_logits, d_probs, ws, ws_bytes, stream);
-}
-int uvad_forward_wav_i16(uvad_ctx *c, const int16_t *d_wav, int B, int64_t S, float *d_logits, float *d_probs,
-                         void *ws, size_t ws_bytes, void *stream) {
-    return forward_wav_impl(c, d_wav, 1, B, S, d_logits, d_probs, ws, ws_bytes, stream);
-}
-static int forward_wav_lens_entry(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64_t S, const int64_t *d_nsamp, float *d_logits,
-                                  float *d_probs, void *ws, size_t ws_bytes, void *stream) {
-    if (!c) return UVAD_E_ARG;
-    if (!d_nsamp) return fail(c, UVAD_E_ARG, "uvad_forward_wav_lens: d_nsamp is NULL");
-    return forward_wav_impl(c, d_wav, is_i16, B, S, d_logits, d_probs, ws, ws_bytes, stream, d_nsamp);
-}
-int uvad_forward_wav_lens(uvad_ctx *c, const float *d_wav, int B, int64_t S, const int64_t *d_nsamp, float *d_logits, float *d_probs,
-                          void *ws, size_t ws_bytes, void *stream) {
-    return forward_wav_lens_entry(c, d_wav, 0, B, S, d_nsamp, d_logits, d_probs, ws, ws_bytes, stream);
-}
-int uvad_forward_wav_lens_i16(uvad_ctx *c, const int16_t *d_wav, int B, int64_t S, const int64_t *d_nsamp, float *d_logits, float *d_probs,
-                              void *ws, size_t ws_bytes, void *stream) {
-    return forward_wav_lens_entry(c, d_wav, 1, B, S, d_nsamp, d_logits, d_probs, ws, ws_bytes, stream);
-}
-
 int64_t uvad_num_frames(const uvad_ctx *c, int64_t S) {
     if (!c || !c->has_fb || S < 0) return -1;
     if (c->fb.snip_edges) return S < c->fb.frame_len ? 0 : 1 + (S - c->fb.frame_len) / c->fb.frame_shift;
@@ -1002,6 +912,17 @@ size_t uvad_workspace_bytes(const uvad_ctx *c, int B, int64_t T) {
     return carve(c, B, T).total;
 }
 
+// What every launch of the feature kernel takes from the context: the front-end configuration and the tables of uvad_set_tables.  The
+// callers add what differs: input, geometry, snip_edges, outputs.
+static FbankArgs fbank_cfg_args(const uvad_ctx *c) {
+    FbankArgs a{};
+    a.frame_len = c->fb.frame_len; a.frame_shift = c->fb.frame_shift; a.n_mels = c->fb.n_mels;
+    a.preemph = c->fb.preemph; a.log_floor = c->fb.log_floor; a.remove_dc = c->fb.remove_dc;
+    a.tab.window = c->d_window; a.tab.mel_start = c->d_mel_start; a.tab.mel_len = c->d_mel_len;
+    a.tab.mel_w = c->d_mel_w; a.tab.mel_wt = c->d_mel_wt; a.tab.mel_stride = c->mel_stride; a.tab.tw512 = c->d_tw512; a.tab.nyquist = c->mel_nyquist;
+    return a;
+}
+
 static int fbank_impl(uvad_ctx *c, const void *d_pcm, int is_i16, int B, int64_t S, float *d_feats, void *stream,
                       unsigned short *plane_hi = nullptr, unsigned short *plane_lo = nullptr, int plane_w = 0, const int64_t *nsamp = nullptr) {
     if (!c || !d_pcm || (!d_feats && !plane_hi) || B <= 0 || S <= 0) return fail(c, UVAD_E_ARG, "uvad_fbank: bad argument");
@@ -1010,13 +931,9 @@ static int fbank_impl(uvad_ctx *c, const void *d_pcm, int is_i16, int B, int64_t
     if (T <= 0) return fail(c, UVAD_E_ARG, "uvad_fbank: input shorter than one frame");
     HIPCHK(c, hipSetDevice(c->device));
     if (B > 65535) return fail(c, UVAD_E_UNSUPPORTED, "uvad_fbank: B > 65535 (grid.y); split the batch");
-    FbankArgs a{};
-    a.pcm = d_pcm; a.pcm_is_i16 = is_i16; a.B = B; a.S = S; a.T = T;
-    a.frame_len = c->fb.frame_len; a.frame_shift = c->fb.frame_shift; a.n_mels = c->fb.n_mels;
-    a.preemph = c->fb.preemph; a.log_floor = c->fb.log_floor; a.remove_dc = c->fb.remove_dc; a.snip_edges = c->fb.snip_edges;
+    FbankArgs a = fbank_cfg_args(c);
+    a.pcm = d_pcm; a.pcm_is_i16 = is_i16; a.B = B; a.S = S; a.T = T; a.snip_edges = c->fb.snip_edges;
     a.feats = d_feats; a.plane_hi = plane_hi; a.plane_lo = plane_lo; a.plane_w = plane_w; a.nsamp = nsamp;
-    a.tab.window = c->d_window; a.tab.mel_start = c->d_mel_start; a.tab.mel_len = c->d_mel_len;
-    a.tab.mel_w = c->d_mel_w; a.tab.mel_wt = c->d_mel_wt; a.tab.mel_stride = c->mel_stride; a.tab.tw512 = c->d_tw512; a.tab.nyquist = c->mel_nyquist;
     HIPCHK(c, launch_fbank(a, (hipStream_t)stream));
     return UVAD_OK;
 }
@@ -1048,6 +965,7 @@ static bool mode_fuses_head(const uvad_ctx *c) { return mode_is_ws(c); }
 static int mode_products(const uvad_ctx *c) { return c->gemm_mode == 3 ? 3 : 4; }
 static int feed_forward_layers(uvad_ctx *c, const WsLayout &w, char *base, int B, int T, bool f16, hipStream_t s) {
     const uvad_model_cfg &m = c->mc;
+    const PackedWeights &W = *c->packed;
     auto Yf = [&](int i) { return reinterpret_cast<float *>(base + w.off_Y[i]); };
     auto Zf = [&](int i) { return reinterpret_cast<float *>(base + w.off_Z[i]); };
     auto hi_of = [&](size_t off) { return reinterpret_cast<unsigned short *>(base + off); };
@@ -1057,7 +975,7 @@ static int feed_forward_layers(uvad_ctx *c, const WsLayout &w, char *base, int B
     int curw = w.Wd;
     for (int j = 0; j < m.lin_layers; ++j) {
         GemmArgs g{};
-        g.W = c->lin_w[j]; g.ldw = gemm_padded_k(curw); g.Wsplit16 = c->lin_w_split16[j]; g.wscale = c->lin_w_scale[j]; g.bias = c->lin_b[j];
+        g.W = W.lin_w[j]; g.ldw = gemm_padded_k(curw); g.Wsplit16 = W.lin_w_split16[j]; g.wscale = W.lin_w_scale[j]; g.bias = W.lin_b[j];
         g.M = (int)w.M; g.N = m.lin_hidden; g.B = B; g.T = T; g.act = 1; g.leaky_slope = m.leaky_slope;
         if (f16) {
             const size_t in_off = j == 0 ? w.off_Y[last] : w.off_Z[(j - 1) & 1];
@@ -1080,8 +998,8 @@ static int feed_forward_layers(uvad_ctx *c, const WsLayout &w, char *base, int B
 static bool stream_uses_stack(const uvad_ctx *c, int T) {
     const uvad_model_cfg &m = c->mc;
     if (!lstm_stack_supported(m.hidden, m.bidirectional ? 2 : 1, m.in_dim, T, m.num_layers)) return false;
-    for (int k = 0; k < m.num_layers; ++k)
-        if (!c->layers[k].w_ih_img) return false;
+    for (const LayerDev &L : c->packed->layers)
+        if (!L.w_ih_img) return false;
     return true;
 }
 
@@ -1090,7 +1008,7 @@ static bool stream_head_in_stack(const uvad_ctx *c) {
     const uvad_model_cfg &m = c->mc;
     if (m.lin_layers > LSTM_STACK_MAX_LIN) return false;
     for (int j = 0; j < m.lin_layers; ++j)
-        if (!c->lin_w_img[j]) return false;
+        if (!c->packed->lin_w_img[j]) return false;
     return true;
 }
 
@@ -1238,20 +1156,54 @@ static int auto_time_chunks(int T, int tiles, int D, int n_cu) {
     return std::min(6, T / 96);   // (lengths grow x 1.3 per chunk: six chunks of T = 1000 are 78 ... 290 frames)
 }
 
-// check_range: the features come from the caller (or from a front end with learnable scales) and may lie outside the f16
-// range; the split-f16 layer-0 projection is then replaced by the exact-f32 one ON THE DEVICE (both are enqueued, a flag
-// written by range_flag_kernel lets exactly one of them run), so the call stays asynchronous and capturable.
-// lens (uvad_classify_lens / uvad_forward_lens): device int32 [B] frame counts.  The recurrences run the lens forms (per-workgroup step
-// count, backward reset past each length), time chunks are off, and the outputs at t >= len_b are set to 0 after the head.  Rows past a
-// length carry padding values through the row-independent GEMMs and are never read by a valid row.
-static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float *d_logits, float *d_probs,
-                         void *ws, size_t ws_bytes, hipStream_t s, bool record_start, bool check_range,
-                         const StreamState *ss, int ld_out, bool feats_in_planes, const FbankArgs *fused_fb, const int *lens) {
+// One run of the classifier (LSTM stack, feed-forward layers, head) on B sequences of T frames.  The options default to what uvad_classify
+// asks for; every caller names the ones it sets.
+struct ClassifyCall {
+    const float *feats = nullptr;   // [B][T][in_dim] f32
+    int B = 0, T = 0;
+    float *logits = nullptr, *probs = nullptr;
+    void *ws = nullptr;
+    size_t ws_bytes = 0;
+    hipStream_t stream = nullptr;
+    bool record_start = true;       // record ev[0] here (false: the caller did, in front of its feature stage)
+    // check_range: the features come from the caller (or from a front end with learnable scales) and may lie outside the f16
+    // range; the split-f16 layer-0 projection is then replaced by the exact-f32 one ON THE DEVICE (both are enqueued, a flag
+    // written by range_flag_kernel lets exactly one of them run), so the call stays asynchronous and capturable.
+    bool check_range = true;
+    const StreamState *stream_state = nullptr;   // a streaming step: (h, c) carried in the caller's state, updated in place
+    int ld_out = 0;                 // row stride of logits / probs (0: T)
+    bool feats_in_planes = false;   // the feature stage has written the first projection's f16 operand planes itself
+    const FbankArgs *fused_fb = nullptr;   // the feature stage inside the one-launch stack (uvad_stream_step decides)
+    // lens (uvad_classify_lens / uvad_forward_lens): device int32 [B] frame counts.  The recurrences run the lens forms (per-workgroup step
+    // count, backward reset past each length), time chunks are off, and the outputs at t >= len_b are set to 0 after the head.  Rows past a
+    // length carry padding values through the row-independent GEMMs and are never read by a valid row.
+    const int *lens = nullptr;
+    bool timed = true;                // record the timing events if uvad_set_timing asked for them (the step calls: never)
+    bool time_chunks_allowed = true;  // follow uvad_set_time_chunks (false: unchunked whatever it says)
+};
+// the request of a caller's (B, T) problem on its buffers and stream, every option at its default
+static ClassifyCall classify_call(const float *feats, int B, int T, float *logits, float *probs, void *ws, size_t ws_bytes, hipStream_t s) {
+    ClassifyCall rq;
+    rq.feats = feats; rq.B = B; rq.T = T; rq.logits = logits; rq.probs = probs; rq.ws = ws; rq.ws_bytes = ws_bytes; rq.stream = s;
+    return rq;
+}
+static int classify_impl(uvad_ctx *c, const ClassifyCall &rq) {
+    const float *d_feats = rq.feats;
+    const int B = rq.B, T = rq.T, ld_out = rq.ld_out;
+    float *d_logits = rq.logits, *d_probs = rq.probs;
+    hipStream_t s = rq.stream;
+    const bool check_range = rq.check_range, feats_in_planes = rq.feats_in_planes;
+    const StreamState *ss = rq.stream_state;
+    const FbankArgs *fused_fb = rq.fused_fb;
+    const int *lens = rq.lens;
+    const bool timing = rq.timed && c->timing;
+    const int chunk_mode = rq.time_chunks_allowed ? c->chunk_mode : 1;
     const uvad_model_cfg &m = c->mc;
+    const PackedWeights &W = *c->packed;
     const WsLayout w = carve(c, B, T);
-    if (ws_bytes < w.total) return fail(c, UVAD_E_WORKSPACE, "workspace too small: need " + std::to_string(w.total) + " bytes");
+    if (rq.ws_bytes < w.total) return fail(c, UVAD_E_WORKSPACE, "workspace too small: need " + std::to_string(w.total) + " bytes");
     if (w.M > (size_t)0x7fffffff) return fail(c, UVAD_E_UNSUPPORTED, "B*T exceeds 2^31 rows; split the batch");
-    char *base = reinterpret_cast<char *>(ws);
+    char *base = reinterpret_cast<char *>(rq.ws);
     float *G = reinterpret_cast<float *>(base + w.off_G);
     int *flag = reinterpret_cast<int *>(base + w.off_flag);
     const int H = m.hidden, D = w.D, N4 = 4 * H * D;
@@ -1261,11 +1213,11 @@ static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float 
     auto hi_of = [&](size_t off) { return reinterpret_cast<unsigned short *>(base + off); };
     auto lo_of = [&](size_t off, int width) { return reinterpret_cast<unsigned short *>(base + off) + plane_rows(w.M) * (size_t)width; };
     // the split-f16 GEMM needs operands inside the f16 range: weights were checked by uvad_finalize (f16_ok)
-    const bool f16 = c->gemm_mode >= 1 && c->f16_ok;
+    const bool f16 = f16_planes(c);
     // the last LSTM layer feeds the classifier kernel directly when there are no feed-forward layers: f32 then
     auto y_planes = [&](int k) { return f16 && (k + 1 < m.num_layers || m.lin_layers > 0); };
-    if (c->timing && record_start) HIPCHK(c, hipEventRecord(c->ev[0], s));
-    if (c->timing) HIPCHK(c, hipEventRecord(c->ev[1], s));
+    if (timing && rq.record_start) HIPCHK(c, hipEventRecord(c->ev[0], s));
+    if (timing) HIPCHK(c, hipEventRecord(c->ev[1], s));
     // Streaming steps of a causal model: the whole stack in one launch (lstm_stack.hip; every layer of a sequence depends on that
     // sequence only, so a workgroup takes its 4 sequences through all layers).  Needs the f32 features (uvad_stream_step asks the
     // feature kernel for them when stream_uses_stack() says so).
@@ -1273,7 +1225,7 @@ static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float 
     if (use_stack) {
         LstmStackArgs q{};
         q.feats = d_feats; q.kin0 = m.in_dim; q.n_layers = m.num_layers;
-        for (int k = 0; k < m.num_layers; ++k) { q.wih[k] = c->layers[k].w_ih_img; q.whh[k] = c->layers[k].w_hh; q.bias[k] = c->layers[k].bias; }
+        for (int k = 0; k < m.num_layers; ++k) { q.wih[k] = W.layers[k].w_ih_img; q.whh[k] = W.layers[k].w_hh; q.bias[k] = W.layers[k].bias; }
         q.h = ss->h; q.c = ss->c; q.layer_stride = ss->layer_stride;
         const int lastl = m.num_layers - 1;
         if (y_planes(lastl)) { q.Yh = hi_of(w.off_Y[lastl & 1]); q.Yl = lo_of(w.off_Y[lastl & 1], w.Wd); }
@@ -1284,14 +1236,14 @@ static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float 
         if (fused_fb && !head_in) return fail(c, UVAD_E_STATE, "internal: fused feature stage without the in-launch head");
         if (fused_fb) { q.fb = *fused_fb; q.fb_on = 1; }   // the feature stage in the same launch (uvad_stream_step decided)
         if (head_in) {
-            for (int j = 0; j < m.lin_layers; ++j) { q.lin_w[j] = c->lin_w_img[j]; q.lin_b[j] = c->lin_b[j]; }
-            q.n_lin = m.lin_layers; q.cls_w = c->cls_w; q.cls_b = c->cls_b; q.slope = m.leaky_slope;
+            for (int j = 0; j < m.lin_layers; ++j) { q.lin_w[j] = W.lin_w_img[j]; q.lin_b[j] = W.lin_b[j]; }
+            q.n_lin = m.lin_layers; q.cls_w = W.cls_w; q.cls_b = W.cls_b; q.slope = m.leaky_slope;
             q.logits = d_logits; q.probs = d_probs; q.ld_out = ld_out > 0 ? ld_out : T;
         }
         HIPCHK(c, launch_lstm_stack(q, s));
         c->rec_tile_used = 4;
         if (head_in) {
-            if (c->timing) {
+            if (timing) {
                 HIPCHK(c, hipEventRecord(c->layer_ev[2 * m.num_layers], s));
                 HIPCHK(c, hipEventRecord(c->ev[2], s));
                 HIPCHK(c, hipEventRecord(c->ev[3], s));
@@ -1303,9 +1255,9 @@ static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float 
     // time chunks (see above): only for the 4-sequence recurrence on the weight-stationary split-f16 projections, never for streaming steps
     int NC = 1;
     const ChunkPlan *plan = nullptr;
-    if (!ss && !use_stack && !lens && f16 && mode_is_ws(c) && c->chunk_mode != 1 && (H == 128 || H == 64) &&
+    if (!ss && !use_stack && !lens && f16 && mode_is_ws(c) && chunk_mode != 1 && (H == 128 || H == 64) &&
         (c->rec_tile_mode ? c->rec_tile_mode : lstm_auto_tile(w.tiles, D, H, c->n_cu)) == 4) {
-        int want = c->chunk_mode > 1 ? std::min(c->chunk_mode, T) : auto_time_chunks(T, w.tiles, D, c->n_cu);
+        int want = chunk_mode > 1 ? std::min(chunk_mode, T) : auto_time_chunks(T, w.tiles, D, c->n_cu);
         const long mt = (long)((w.M + 127) / 128);
         while (want > 1 && (mt / want) * (N4 / 128) < 2L * c->n_cu) --want;   // every chunk must still be a launch the weight-stationary kernel takes
         if (want > 1 && side_stream_for(c, s) && (plan = chunk_plan(c, w.tiles, T, D, want, s)) != nullptr) {
@@ -1320,11 +1272,11 @@ static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float 
     }
     c->chunks_used = NC;
     for (int k = 0; k < (use_stack ? 0 : m.num_layers); ++k) {
-        const LayerDev &L = c->layers[k];
+        const LayerDev &L = W.layers[k];
         GemmArgs g{};
         g.W = L.w_ih; g.ldw = gemm_padded_k(L.in); g.Wsplit16 = L.w_ih_split16; g.wscale = L.w_ih_scale; g.bias = L.bias; g.C = G;
         g.M = (int)w.M; g.N = N4; g.ldc = N4; g.c_blocked = 1; g.B = B; g.T = T; g.act = 0; g.leaky_slope = 0.f;
-        if (c->timing) HIPCHK(c, hipEventRecord(c->layer_ev[2 * k], s));
+        if (timing) HIPCHK(c, hipEventRecord(c->layer_ev[2 * k], s));
         if (f16) {
             if (k == 0) {
                 if (!feats_in_planes)   // (uvad_forward: the feature kernel has written the planes itself)
@@ -1357,7 +1309,7 @@ static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float 
                 float *cst = reinterpret_cast<float *>(base + w.off_hc + align_up((size_t)w.D * w.tiles * SEQ_TILE * m.hidden * sizeof(float)));
                 for (int i = 0; i < NC; ++i) {
                     HIPCHK(c, hipStreamWaitEvent(s, c->ev_chunk[i], 0));
-                    if (i == 0 && c->timing) HIPCHK(c, hipEventRecord(c->layer_ev[2 * k + 1], s));   // "projection" = what the recurrence had to wait for
+                    if (i == 0 && timing) HIPCHK(c, hipEventRecord(c->layer_ev[2 * k + 1], s));   // "projection" = what the recurrence had to wait for
                     LstmArgs r{};
                     r.G = G; r.ldg = N4; r.Whh_packed = L.w_hh; r.ldy = w.Wd;
                     if (y_planes(k)) { r.Yh = hi_of(w.off_Y[k & 1]); r.Yl = lo_of(w.off_Y[k & 1], w.Wd); }
@@ -1385,7 +1337,7 @@ static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float 
             else { g.A = Yf((k - 1) & 1); g.lda = w.Wd; g.a_mode = 0; }
             HIPCHK(c, launch_gemm(g, s));
         }
-        if (c->timing) HIPCHK(c, hipEventRecord(c->layer_ev[2 * k + 1], s));
+        if (timing) HIPCHK(c, hipEventRecord(c->layer_ev[2 * k + 1], s));
         LstmArgs r{};
         r.G = G; r.ldg = N4; r.Whh_packed = L.w_hh; r.ldy = w.Wd;
         if (L.w_hh16_ok) {
@@ -1404,8 +1356,8 @@ static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float 
         }
         HIPCHK(c, launch_lstm(r, s, &c->rec_tile_used));
     }
-    if (c->timing) HIPCHK(c, hipEventRecord(c->layer_ev[2 * m.num_layers], s));
-    if (c->timing) HIPCHK(c, hipEventRecord(c->ev[2], s));
+    if (timing) HIPCHK(c, hipEventRecord(c->layer_ev[2 * m.num_layers], s));
+    if (timing) HIPCHK(c, hipEventRecord(c->ev[2], s));
     const int last = (m.num_layers - 1) & 1;
     // The default head (two 128-unit feed-forward layers) in split-f16 mode, large launches: feed-forward layers, classifier and
     // sigmoid in one kernel (head_fused.hip); the LSTM output planes are read once and nothing but the logits is written.
@@ -1413,14 +1365,14 @@ static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float 
     if (f16 && mode_fuses_head(c) && head_fused_supported(w.Wd, m.lin_hidden, m.lin_layers, (long long)w.M, c->n_cu)) {
         HeadArgs h{};
         h.Yh = hi_of(w.off_Y[last]); h.Yl = lo_of(w.off_Y[last], w.Wd); h.M = (long long)w.M; h.K1 = w.Wd;
-        h.W1 = c->lin_w_split16[0]; h.W2 = c->lin_w_split16[1]; h.w1scale = c->lin_w_scale[0]; h.w2scale = c->lin_w_scale[1];
-        h.b1 = c->lin_b[0]; h.b2 = c->lin_b[1]; h.wc = c->cls_w; h.bc = c->cls_b; h.slope = m.leaky_slope;
+        h.W1 = W.lin_w_split16[0]; h.W2 = W.lin_w_split16[1]; h.w1scale = W.lin_w_scale[0]; h.w2scale = W.lin_w_scale[1];
+        h.b1 = W.lin_b[0]; h.b2 = W.lin_b[1]; h.wc = W.cls_w; h.bc = W.cls_b; h.slope = m.leaky_slope;
         h.logits = d_logits; h.probs = d_probs; h.tiles = w.tiles; h.T = T; h.B = B; h.ld_out = ld_out > 0 ? ld_out : T;
         h.counter = reinterpret_cast<unsigned *>(base + w.off_ctr);
         h.products = mode_products(c);
         HIPCHK(c, launch_head_fused(h, c->n_cu, s));
         if (lens) HIPCHK(c, launch_lens_fill(d_logits, d_probs, B, T, h.ld_out, lens, s));
-        if (c->timing) {
+        if (timing) {
             HIPCHK(c, hipEventRecord(c->ev[3], s));
             c->ev_valid = true;
         }
@@ -1431,11 +1383,11 @@ static int classify_impl(uvad_ctx *c, const float *d_feats, int B, int T, float 
     const float *cur = m.lin_layers > 0 ? Zf((m.lin_layers - 1) & 1) : Yf(last);
     const int curw = m.lin_layers > 0 ? m.lin_hidden : w.Wd;
     ClsArgs q{};
-    q.Z = cur; q.ldz = curw; q.K = curw; q.w = c->cls_w; q.b = c->cls_b; q.logits = d_logits; q.probs = d_probs;
+    q.Z = cur; q.ldz = curw; q.K = curw; q.w = W.cls_w; q.b = W.cls_b; q.logits = d_logits; q.probs = d_probs;
     q.tiles = w.tiles; q.T = T; q.B = B; q.ld_out = ld_out > 0 ? ld_out : T;
     HIPCHK(c, launch_classifier(q, s));
     if (lens) HIPCHK(c, launch_lens_fill(d_logits, d_probs, B, T, q.ld_out, lens, s));
-    if (c->timing) {
+    if (timing) {
         HIPCHK(c, hipEventRecord(c->ev[3], s));
         c->ev_valid = true;
     }
@@ -1448,7 +1400,7 @@ int uvad_classify(uvad_ctx *c, const float *d_feats, int B, int T, float *d_logi
     if (!d_feats || B <= 0 || T <= 0 || !ws) return fail(c, UVAD_E_ARG, "uvad_classify: bad argument");
     if (!c->finalized) return fail(c, UVAD_E_STATE, "uvad_classify: uvad_finalize has not been called");
     HIPCHK(c, hipSetDevice(c->device));
-    return classify_impl(c, d_feats, B, T, d_logits, d_probs, ws, ws_bytes, (hipStream_t)stream, true, true, nullptr, 0, false, nullptr);
+    return classify_impl(c, classify_call(d_feats, B, T, d_logits, d_probs, ws, ws_bytes, (hipStream_t)stream));
 }
 
 int uvad_classify_lens(uvad_ctx *c, const float *d_feats, int B, int T, const int32_t *d_lens, float *d_logits, float *d_probs,
@@ -1466,7 +1418,9 @@ int uvad_classify_lens(uvad_ctx *c, const float *d_feats, int B, int T, const in
     // projection all read that copy)
     float *masked = reinterpret_cast<float *>(reinterpret_cast<char *>(ws) + w.off_feats);
     HIPCHK(c, launch_mask_features(d_feats, B, T, c->mc.in_dim, d_lens, masked, s));
-    return classify_impl(c, masked, B, T, d_logits, d_probs, ws, ws_bytes, s, false, true, nullptr, 0, false, nullptr, d_lens);
+    ClassifyCall rq = classify_call(masked, B, T, d_logits, d_probs, ws, ws_bytes, s);
+    rq.record_start = false; rq.lens = d_lens;
+    return classify_impl(c, rq);
 }
 
 static int forward_impl(uvad_ctx *c, const void *d_pcm, int is_i16, int B, int64_t S, float *d_logits, float *d_probs,
@@ -1486,7 +1440,7 @@ static int forward_impl(uvad_ctx *c, const void *d_pcm, int is_i16, int B, int64
     if (c->timing) HIPCHK(c, hipEventRecord(c->ev[0], s));
     // split-f16 GEMM mode: the feature kernel writes the two f16 planes the first projection reads (K-blocked, tile-major rows) and
     // the f32 feature tensor never exists; exact-f32 mode: f32 features.  (log-mel values are within +-90: no range check.)
-    const bool planes = c->gemm_mode >= 1 && c->f16_ok;
+    const bool planes = f16_planes(c);
     unsigned short *ph = reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(ws) + w.off_fplanes);
     int r = planes ? fbank_impl(c, d_pcm, is_i16, B, S, nullptr, stream, ph, ph + plane_rows(w.M) * (size_t)w.Fp, w.Fp, nsamp)
                    : fbank_impl(c, d_pcm, is_i16, B, S, feats, stream, nullptr, nullptr, 0, nsamp);
@@ -1496,7 +1450,9 @@ static int forward_impl(uvad_ctx *c, const void *d_pcm, int is_i16, int B, int64
         lens = reinterpret_cast<int *>(reinterpret_cast<char *>(ws) + w.off_hc);
         HIPCHK(c, launch_frames_of(nsamp, B, S, c->fb.frame_len, c->fb.frame_shift, c->fb.snip_edges, lens, s));
     }
-    return classify_impl(c, feats, B, (int)T, d_logits, d_probs, ws, ws_bytes, s, false, false, nullptr, 0, planes, nullptr, lens);
+    ClassifyCall rq = classify_call(feats, B, (int)T, d_logits, d_probs, ws, ws_bytes, s);
+    rq.record_start = false; rq.check_range = false; rq.feats_in_planes = planes; rq.lens = lens;
+    return classify_impl(c, rq);
 }
 
 int uvad_forward(uvad_ctx *c, const float *d_pcm, int B, int64_t S, float *d_logits, float *d_probs,
@@ -1524,6 +1480,55 @@ int uvad_forward_lens_i16(uvad_ctx *c, const int16_t *d_pcm, int B, int64_t S, c
     return forward_lens_entry(c, d_pcm, 1, B, S, d_nsamp, d_logits, d_probs, ws, ws_bytes, stream);
 }
 
+// nsamp (uvad_forward_wav_lens): the SincNet stage in its lens form, then the classifier with lens = the rows' frame counts T_b (the
+// geometry block of the SincNet workspace): time chunks off, outputs at t >= T_b exactly +0.
+static int forward_wav_impl(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64_t S, float *d_logits, float *d_probs,
+                            void *ws, size_t ws_bytes, void *stream, const int64_t *nsamp = nullptr) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_wav || B <= 0 || S <= 0 || !ws) return fail(c, UVAD_E_ARG, "uvad_forward_wav: bad argument");
+    if (!c->has_sinc) return fail(c, UVAD_E_STATE, "uvad_forward_wav: uvad_sincnet_configure has not been called");
+    if (!c->finalized) return fail(c, UVAD_E_STATE, "uvad_forward_wav: uvad_finalize has not been called");
+    const int64_t T = uvad_sincnet_num_frames(c, S);
+    if (T <= 0 || T > 0x7fffffff) return fail(c, UVAD_E_ARG, "uvad_forward_wav: waveform too short for one output frame");
+    const WsLayout w = carve(c, B, T);
+    const size_t sn = sinc_carve(c, B, S).total;
+    if (ws_bytes < w.total + sn) return fail(c, UVAD_E_WORKSPACE, "workspace too small: need " + std::to_string(w.total + sn) + " bytes");
+    char *base = reinterpret_cast<char *>(ws);
+    float *feats = reinterpret_cast<float *>(base + w.off_feats);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->timing) HIPCHK(c, hipEventRecord(c->ev[0], s));
+    const int *lens = nullptr;
+    int r = sincnet_impl(c, d_wav, is_i16, B, S, feats, base + w.total, ws_bytes - w.total, s, nsamp, &lens);
+    if (r) return r;
+    ClassifyCall rq = classify_call(feats, B, (int)T, d_logits, d_probs, ws, w.total, s);
+    rq.record_start = false; rq.lens = lens;
+    return classify_impl(c, rq);
+}
+
+int uvad_forward_wav(uvad_ctx *c, const float *d_wav, int B, int64_t S, float *d_logits, float *d_probs,
+                     void *ws, size_t ws_bytes, void *stream) {
+    return forward_wav_impl(c, d_wav, 0, B, S, d_logits, d_probs, ws, ws_bytes, stream);
+}
+int uvad_forward_wav_i16(uvad_ctx *c, const int16_t *d_wav, int B, int64_t S, float *d_logits, float *d_probs,
+                         void *ws, size_t ws_bytes, void *stream) {
+    return forward_wav_impl(c, d_wav, 1, B, S, d_logits, d_probs, ws, ws_bytes, stream);
+}
+static int forward_wav_lens_entry(uvad_ctx *c, const void *d_wav, int is_i16, int B, int64_t S, const int64_t *d_nsamp, float *d_logits,
+                                  float *d_probs, void *ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_nsamp) return fail(c, UVAD_E_ARG, "uvad_forward_wav_lens: d_nsamp is NULL");
+    return forward_wav_impl(c, d_wav, is_i16, B, S, d_logits, d_probs, ws, ws_bytes, stream, d_nsamp);
+}
+int uvad_forward_wav_lens(uvad_ctx *c, const float *d_wav, int B, int64_t S, const int64_t *d_nsamp, float *d_logits, float *d_probs,
+                          void *ws, size_t ws_bytes, void *stream) {
+    return forward_wav_lens_entry(c, d_wav, 0, B, S, d_nsamp, d_logits, d_probs, ws, ws_bytes, stream);
+}
+int uvad_forward_wav_lens_i16(uvad_ctx *c, const int16_t *d_wav, int B, int64_t S, const int64_t *d_nsamp, float *d_logits, float *d_probs,
+                              void *ws, size_t ws_bytes, void *stream) {
+    return forward_wav_lens_entry(c, d_wav, 1, B, S, d_nsamp, d_logits, d_probs, ws, ws_bytes, stream);
+}
+
 int uvad_get_taps(uvad_ctx *c, int B, int T, float *d_lstm_out, float *d_lin_out, const void *ws, void *stream) {
     if (!c || !ws || B <= 0 || T <= 0) return UVAD_E_ARG;
     if (!c->finalized) return fail(c, UVAD_E_STATE, "not finalized");
@@ -1533,13 +1538,13 @@ int uvad_get_taps(uvad_ctx *c, int B, int T, float *d_lstm_out, float *d_lin_out
     const char *base = reinterpret_cast<const char *>(ws);
     if (d_lstm_out) {
         const char *y = base + w.off_Y[(m.num_layers - 1) & 1];
-        const bool planes = c->gemm_mode >= 1 && c->f16_ok && m.lin_layers > 0;   // what classify_impl made the last layer write
+        const bool planes = f16_planes(c) && m.lin_layers > 0;   // what classify_impl made the last layer write
         HIPCHK(c, launch_untile(y, planes ? y + plane_rows(w.M) * (size_t)w.Wd * sizeof(unsigned short) : nullptr, w.Wd, w.Wd, d_lstm_out, w.tiles, T, B,
                                 (hipStream_t)stream));
     }
     if (d_lin_out) {
         if (m.lin_layers <= 0) return fail(c, UVAD_E_ARG, "model has no feed-forward layers");
-        const bool f16 = c->gemm_mode >= 1 && c->f16_ok;
+        const bool f16 = f16_planes(c);
         if (f16 && mode_fuses_head(c) && head_fused_supported(w.Wd, m.lin_hidden, m.lin_layers, (long long)w.M, c->n_cu)) {
             // the fused head keeps the feed-forward activations on chip: recompute them from the LSTM output planes of the last call
             // with the per-layer kernels -- four products, exact weights: the bits of the fused head in modes 1 / 2.  In mode 3 the
@@ -1600,15 +1605,11 @@ StreamPlan stream_plan(const uvad_ctx *c, const StreamCounters &sc, int chunk) {
 FbankArgs stream_fbank_args(const uvad_ctx *c, const float *d_pcm_chunk, int B, int chunk, const StreamPlan &p, const float *staging,
                             const float *tail_in, float *tail_out) {
     const int L = c->fb.frame_len, sh = c->fb.frame_shift;
-    FbankArgs fa{};
+    FbankArgs fa = fbank_cfg_args(c);
     fa.pcm = staging + p.offset; fa.pcm_is_i16 = 0; fa.B = B; fa.S = (int64_t)(L + chunk) - p.offset; fa.T = p.k;
     fa.vs_chunk = d_pcm_chunk; fa.vs_tail_in = tail_in; fa.vs_tail_out = tail_out;
     fa.vs_tail = L; fa.vs_chunk_len = chunk; fa.vs_first = p.first; fa.vs_n_left = (L - sh) / 2; fa.vs_offset = (int)p.offset;
-    fa.row_stride = L + chunk;
-    fa.frame_len = L; fa.frame_shift = sh; fa.n_mels = c->fb.n_mels;
-    fa.preemph = c->fb.preemph; fa.log_floor = c->fb.log_floor; fa.remove_dc = c->fb.remove_dc; fa.snip_edges = 1;
-    fa.tab.window = c->d_window; fa.tab.mel_start = c->d_mel_start; fa.tab.mel_len = c->d_mel_len;
-    fa.tab.mel_w = c->d_mel_w; fa.tab.mel_wt = c->d_mel_wt; fa.tab.mel_stride = c->mel_stride; fa.tab.tw512 = c->d_tw512; fa.tab.nyquist = c->mel_nyquist;
+    fa.row_stride = L + chunk; fa.snip_edges = 1;
     return fa;
 }
 }  // namespace
@@ -1677,7 +1678,7 @@ int uvad_stream_step(uvad_ctx *c, const float *d_pcm_chunk, int B, int chunk, vo
                                      reinterpret_cast<float *>(st + S.off_tail[par ^ 1]));
     fa.feats = feats;
     // as in uvad_forward: features straight into the first projection's operand planes -- unless the one-launch stack runs (f32 features)
-    const bool planes = c->gemm_mode >= 1 && c->f16_ok && !stream_uses_stack(c, k);
+    const bool planes = f16_planes(c) && !stream_uses_stack(c, k);
     if (planes) {
         fa.plane_hi = reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(cws) + w.off_fplanes);
         fa.plane_lo = fa.plane_hi + plane_rows(w.M) * (size_t)w.Fp;
@@ -1689,10 +1690,10 @@ int uvad_stream_step(uvad_ctx *c, const float *d_pcm_chunk, int B, int chunk, vo
     StreamState ss;
     ss.h = reinterpret_cast<float *>(st + S.off_h); ss.c = reinterpret_cast<float *>(st + S.off_c);
     ss.layer_stride = S.layer_stride / sizeof(float);
-    const bool timing = c->timing;
-    c->timing = false;
-    const int r = classify_impl(c, feats, B, k, d_logits, nullptr, cws, ws_bytes - staging_bytes, s, false, false, &ss, ld_logits, planes, fuse_fb ? &fa : nullptr);
-    c->timing = timing;
+    ClassifyCall rq = classify_call(feats, B, k, d_logits, nullptr, cws, ws_bytes - staging_bytes, s);
+    rq.timed = false; rq.record_start = false; rq.check_range = false;
+    rq.stream_state = &ss; rq.ld_out = ld_logits; rq.feats_in_planes = planes; rq.fused_fb = fuse_fb ? &fa : nullptr;
+    const int r = classify_impl(c, rq);
     return r < 0 ? r : k;
 }
 
@@ -1850,7 +1851,7 @@ int uvad_window_step(uvad_ctx *c, const float *d_pcm_chunk, int B, int chunk, vo
     // the window into the first projection's operand, as uvad_forward's feature kernel writes it
     char *cws = wsb + wl.off_cls;
     const WsLayout w = carve(c, B, p.Tw);
-    const bool planes = c->gemm_mode >= 1 && c->f16_ok;
+    const bool planes = f16_planes(c);
     float *feats = reinterpret_cast<float *>(cws + w.off_feats);
     WindowArgs a{};
     a.newf = newf; a.ring = reinterpret_cast<float *>(st + SL.off_ring); a.ctr_in = ctr + par; a.ctr_out = ctr + (par ^ 1);
@@ -1863,15 +1864,9 @@ int uvad_window_step(uvad_ctx *c, const float *d_pcm_chunk, int B, int chunk, vo
     if (p.n_emit <= 0) return 0;
     float *lg = reinterpret_cast<float *>(wsb + wl.off_logits), *pr = reinterpret_cast<float *>(wsb + wl.off_probs);
     // the classifier at (B, Tw), time chunks off: a new T every warm-up step would churn the chunk-plan cache, whose eviction synchronises
-    const bool timing = c->timing;
-    const int chunk_mode = c->chunk_mode;
-    c->timing = false;
-    c->chunk_mode = 1;
-    const int r = classify_impl(c, feats, B, p.Tw, d_logits ? lg : nullptr, d_probs ? pr : nullptr, cws, wl.total - wl.off_cls, s, false, false,
-                                nullptr, 0, planes, nullptr);
-    c->timing = timing;
-    c->chunk_mode = chunk_mode;
-    if (r) return r;
+    ClassifyCall rq = classify_call(feats, B, p.Tw, d_logits ? lg : nullptr, d_probs ? pr : nullptr, cws, wl.total - wl.off_cls, s);
+    rq.timed = false; rq.time_chunks_allowed = false; rq.record_start = false; rq.check_range = false; rq.feats_in_planes = planes;
+    if (int r = classify_impl(c, rq)) return r;
     HIPCHK(c, launch_window_emit(lg, pr, B, p.Tw, p.r0, p.n_emit, d_logits, d_probs, ld_out, s));
     return p.n_emit;
 }
@@ -1969,26 +1964,26 @@ struct WavWindowPlan { int64_t n = 0, e = 0, Sw = 0; int k = 0, Tw = 0, r0 = 0, 
 WavWindowPlan wav_window_plan(const uvad_ctx *c, const WavWindowGroup &g, int chunk) {
     const WavGeom geo = wav_geom(c);
     WavWindowPlan p;
-    p.n = g.n_samples + chunk;
+    p.n = g.sc.n_samples + chunk;
     p.e = wav_frames(geo, p.n);
-    p.k = (int)(p.e - g.n_frames);
+    p.k = (int)(p.e - g.sc.n_frames);
     p.Tw = (int)std::min<int64_t>(p.e, g.W);
     p.Sw = wav_span(geo, p.Tw);
-    const int64_t f0 = std::max<int64_t>(0, g.n_frames - g.L), f1 = std::max<int64_t>(0, p.e - g.L);
+    const int64_t f0 = std::max<int64_t>(0, g.sc.n_frames - g.L), f1 = std::max<int64_t>(0, p.e - g.L);
     p.n_emit = (int)(f1 - f0);
     p.r0 = (int)(f0 - (p.e - p.Tw));
-    if (p.e >= g.W && g.n_frames >= g.L) p.key = p.k;
+    if (p.e >= g.W && g.sc.n_frames >= g.L) p.key = p.k;
     return p;
 }
 void wav_window_advance(WavWindowGroup &g, const WavWindowPlan &p) {
-    g.n_samples = p.n;
-    g.n_frames = p.e;
-    g.n_steps += 1;
+    g.sc.n_samples = p.n;
+    g.sc.n_frames = p.e;
+    g.sc.n_steps += 1;
 }
 int wav_window_check_cfg(uvad_ctx *c, const std::string &who) {
     if (!c->has_model || !c->has_sinc)
         return fail(c, UVAD_E_STATE, who + ": needs a model and a SincNet configuration (uvad_sincnet_configure)");
-    if (!c->finalized || !c->sinc_ready) return fail(c, UVAD_E_STATE, who + ": SincNet tensors not set / uvad_finalize not called");
+    if (!sinc_weights_ready(c)) return fail(c, UVAD_E_STATE, who + ": SincNet tensors not set / uvad_finalize not called");
     return UVAD_OK;
 }
 }  // namespace
@@ -2065,15 +2060,9 @@ static int window_wav_step_impl(uvad_ctx *c, const void *d_pcm_chunk, int is_i16
     if (p.n_emit <= 0) return 0;
     // ... and the classifier at (B, Tw) with time chunks off (a new T every warm-up step would churn the chunk-plan cache)
     float *lg = reinterpret_cast<float *>(wsb + wl.off_logits), *pr = reinterpret_cast<float *>(wsb + wl.off_probs);
-    const bool timing = c->timing;
-    const int chunk_mode = c->chunk_mode;
-    c->timing = false;
-    c->chunk_mode = 1;
-    const int r = classify_impl(c, feats, B, p.Tw, d_logits ? lg : nullptr, d_probs ? pr : nullptr, wsb + wl.off_cls, wl.cls_bytes, s, false,
-                                true, nullptr, 0, false, nullptr);
-    c->timing = timing;
-    c->chunk_mode = chunk_mode;
-    if (r) return r;
+    ClassifyCall rq = classify_call(feats, B, p.Tw, d_logits ? lg : nullptr, d_probs ? pr : nullptr, wsb + wl.off_cls, wl.cls_bytes, s);
+    rq.timed = false; rq.time_chunks_allowed = false; rq.record_start = false;
+    if (int r = classify_impl(c, rq)) return r;
     HIPCHK(c, launch_window_emit(lg, pr, B, p.Tw, p.r0, p.n_emit, d_logits, d_probs, ld_out, s));
     return p.n_emit;
 }
@@ -2115,7 +2104,7 @@ int uvad_window_wav_features(uvad_ctx *c, const void *d_state, int B, float *d_f
     if (it == c->wav_windows.end()) return fail(c, UVAD_E_STATE, "uvad_window_wav_features: call uvad_window_wav_reset on this state first");
     const WavWindowGroup &g = it->second;
     if (B != g.B) return fail(c, UVAD_E_ARG, "uvad_window_wav_features: B differs from the one the state was reset with");
-    *Tw = (int)std::min<int64_t>(g.n_frames, g.W);
+    *Tw = (int)std::min<int64_t>(g.sc.n_frames, g.W);
     if (!d_feats || *Tw == 0) return UVAD_OK;
     const WavWindowLayout SL = wav_window_layout(c, B, g.W, g.is_i16);
     HIPCHK(c, hipSetDevice(c->device));
@@ -2199,18 +2188,6 @@ WavSlotsWs wav_slots_ws(const uvad_ctx *c, int B, int W) {
     w.total = o;
     return w;
 }
-// the classifier at (B, W) with per-row lengths, time chunks off and no timing events, as the window steps run it
-int slots_classify(uvad_ctx *c, const float *feats, int B, int W, float *lg, float *pr, char *cws, size_t cws_bytes, hipStream_t s,
-                   bool check_range, bool planes, const int *lens) {
-    const bool timing = c->timing;
-    const int chunk_mode = c->chunk_mode;
-    c->timing = false;
-    c->chunk_mode = 1;
-    const int r = classify_impl(c, feats, B, W, lg, pr, cws, cws_bytes, s, false, check_range, nullptr, 0, planes, nullptr, lens);
-    c->timing = timing;
-    c->chunk_mode = chunk_mode;
-    return r;
-}
 }  // namespace
 }  // extern "C++"
 
@@ -2281,18 +2258,15 @@ int uvad_window_slots_step(uvad_ctx *c, const float *d_pcm_chunk, const uint8_t 
     // 2. the unchanged feature kernel on plain rows of side-by-side frames (frame_shift = frame_len): the staging row's frames, those
     //    at t >= k_b discarded by the assembly
     const int nfr = slots_frames(c, chunk);
-    FbankArgs fa{};
+    FbankArgs fa = fbank_cfg_args(c);
     fa.pcm = staging; fa.pcm_is_i16 = 0; fa.B = B; fa.S = sa.row; fa.T = nfr; fa.row_stride = sa.row;
-    fa.frame_len = c->fb.frame_len; fa.frame_shift = c->fb.frame_len; fa.n_mels = F;
-    fa.preemph = c->fb.preemph; fa.log_floor = c->fb.log_floor; fa.remove_dc = c->fb.remove_dc; fa.snip_edges = 1;
-    fa.tab.window = c->d_window; fa.tab.mel_start = c->d_mel_start; fa.tab.mel_len = c->d_mel_len;
-    fa.tab.mel_w = c->d_mel_w; fa.tab.mel_wt = c->d_mel_wt; fa.tab.mel_stride = c->mel_stride; fa.tab.tw512 = c->d_tw512; fa.tab.nyquist = c->mel_nyquist;
+    fa.frame_shift = c->fb.frame_len; fa.snip_edges = 1;
     fa.feats = newf;
     HIPCHK(c, launch_fbank(fa, s));
     // 3. ring commit and the left-aligned windows into the first projection's operand; lens = Tw_b
     char *cws = wsb + wl.off_cls;
     const WsLayout w = carve(c, B, g.W);
-    const bool planes = c->gemm_mode >= 1 && c->f16_ok;
+    const bool planes = f16_planes(c);
     float *feats = reinterpret_cast<float *>(cws + w.off_feats);
     SlotAssembleArgs a{};
     a.plan = plan; a.ctr = ctr; a.newf = newf; a.kmax = nfr; a.ring = reinterpret_cast<float *>(st + SL.off_ring);
@@ -2303,8 +2277,10 @@ int uvad_window_slots_step(uvad_ctx *c, const float *d_pcm_chunk, const uint8_t 
     HIPCHK(c, launch_slot_assemble(a, s));
     // 4. the classifier at (B, W) with lens
     float *lg = reinterpret_cast<float *>(wsb + wl.off_logits), *pr = reinterpret_cast<float *>(wsb + wl.off_probs);
-    if (int r = slots_classify(c, feats, B, g.W, d_logits ? lg : nullptr, d_probs ? pr : nullptr, cws, wl.total - wl.off_cls, s, false, planes, lens))
-        return r;
+    ClassifyCall rq = classify_call(feats, B, g.W, d_logits ? lg : nullptr, d_probs ? pr : nullptr, cws, wl.total - wl.off_cls, s);
+    rq.timed = false; rq.time_chunks_allowed = false; rq.record_start = false;
+    rq.check_range = false; rq.feats_in_planes = planes; rq.lens = lens;
+    if (int r = classify_impl(c, rq)) return r;
     // 5. emission, counts and the counters
     SlotEmitArgs ea{};
     ea.plan = plan; ea.ctr = ctr; ea.logits_in = lg; ea.probs_in = pr; ea.B = B; ea.W = g.W;
@@ -2408,9 +2384,9 @@ static int window_wav_slots_step_impl(uvad_ctx *c, const void *d_pcm_chunk, int 
     if (int r = sincnet_impl(c, wsb, is_i16, B, sw_max, feats, wsb + wl.off_sinc, wl.sinc_bytes, s, nsamp, &lens)) return r;
     // 3. ... the classifier at (B, W) with the rows' frame counts ...
     float *lg = reinterpret_cast<float *>(wsb + wl.off_logits), *pr = reinterpret_cast<float *>(wsb + wl.off_probs);
-    if (int r = slots_classify(c, feats, B, g.W, d_logits ? lg : nullptr, d_probs ? pr : nullptr, wsb + wl.off_cls, wl.cls_bytes, s, true, false,
-                               lens))
-        return r;
+    ClassifyCall rq = classify_call(feats, B, g.W, d_logits ? lg : nullptr, d_probs ? pr : nullptr, wsb + wl.off_cls, wl.cls_bytes, s);
+    rq.timed = false; rq.time_chunks_allowed = false; rq.record_start = false; rq.lens = lens;
+    if (int r = classify_impl(c, rq)) return r;
     // 4. ... and emission, counts and the counters
     SlotEmitArgs ea{};
     ea.plan = plan; ea.ctr = ctr; ea.logits_in = lg; ea.probs_in = pr; ea.B = B; ea.W = g.W;
@@ -2492,7 +2468,7 @@ int sliding_check(uvad_ctx *c, const std::string &who, const void *d_in, int R, 
 // the windows [0, N) in groups of at most `group` through assemble + classifier (log-mel), into win [N][W]
 int sliding_run_groups(uvad_ctx *c, const SlidingPlan &plan, const float *feats, bool caller_feats, int group, float *win, int *lens,
                        char *cws, size_t cws_bytes, hipStream_t s) {
-    const bool planes = c->gemm_mode >= 1 && c->f16_ok;
+    const bool planes = f16_planes(c);
     const int W = c->sl_W;
     for (int64_t i0 = 0; i0 < plan.N; i0 += group) {
         const int Bg = (int)std::min<int64_t>(group, plan.N - i0);
@@ -2512,7 +2488,10 @@ int sliding_run_groups(uvad_ctx *c, const SlidingPlan &plan, const float *feats,
             HIPCHK(c, launch_zero_counters(reinterpret_cast<unsigned *>(a.flag), 1, s));
         }
         HIPCHK(c, launch_sliding_assemble(a, s));
-        if (int r = slots_classify(c, rows, Bg, W, nullptr, win + (size_t)i0 * W, cws, cws_bytes, s, check_range, planes, lens)) return r;
+        ClassifyCall rq = classify_call(rows, Bg, W, nullptr, win + (size_t)i0 * W, cws, cws_bytes, s);
+        rq.timed = false; rq.time_chunks_allowed = false; rq.record_start = false;
+        rq.check_range = check_range; rq.feats_in_planes = planes; rq.lens = lens;
+        if (int r = classify_impl(c, rq)) return r;
     }
     return UVAD_OK;
 }
@@ -2683,7 +2662,9 @@ static int sliding_forward_wav_impl(uvad_ctx *c, const void *d_wav, int is_i16, 
         HIPCHK(c, launch_sliding_wav_gather(a, is_i16, s));
         const int *lens = nullptr;
         if (int r = sincnet_impl(c, wsb, is_i16, Bg, sw, feats, wsb + wl.off_sinc, wl.sinc_bytes, s, nsamp, &lens)) return r;
-        if (int r = slots_classify(c, feats, Bg, W, nullptr, win + (size_t)i0 * W, wsb + wl.off_cls, wl.cls_bytes, s, true, false, lens)) return r;
+        ClassifyCall rq = classify_call(feats, Bg, W, nullptr, win + (size_t)i0 * W, wsb + wl.off_cls, wl.cls_bytes, s);
+        rq.timed = false; rq.time_chunks_allowed = false; rq.record_start = false; rq.lens = lens;
+        if (int r = classify_impl(c, rq)) return r;
     }
     return sliding_finish(c, plan, win, d_probs, ld_out, d_frames, d_win_probs, s);
 }
@@ -3172,7 +3153,7 @@ int uvad_get_sincnet_form(const uvad_ctx *c) {
 int uvad_get_p2_on_fp8(const uvad_ctx *c) {
     if (!c) return UVAD_E_ARG;
     if (!c->has_model || !c->finalized || c->mc.hidden != 128 || c->gemm_mode == 2) return 0;
-    for (const LayerDev &L : c->layers)
+    for (const LayerDev &L : c->packed->layers)
         if (!L.w_hh16_ok || !L.w_hh16_p2q) return 0;
     return 1;
 }
@@ -3240,7 +3221,7 @@ const char *uvad_last_error(const uvad_ctx *c) { return c ? c->err.c_str() : "nu
 
 void uvad_destroy(uvad_ctx *c) {
     if (!c) return;
-    if (!c->allocs.empty() || !c->weight_allocs.empty() || c->packed || c->ev[0]) (void)hipSetDevice(c->device);
+    if (!c->allocs.empty() || c->packed || c->ev[0]) (void)hipSetDevice(c->device);
     free_weights(c);
     for (void *p : c->allocs) (void)hipFree(p);
     for (auto &ev : c->ev)
