@@ -709,6 +709,51 @@ int uvad_cuts_table(uvad_ctx *, const uint8_t *d_labels, int ld, int B, int T, c
 int uvad_cuts_gather(uvad_ctx *, const void *d_src, int64_t row_stride, int unit_bytes, int which, const uvad_cut *d_table,
                      const int32_t *d_total, int max_cuts, void *d_out, int64_t ld_out, int32_t *d_out_len, void *stream);
 
+/* ---- Hysteresis decisions with minimum durations, on the device -----------------------------------------------------------------------
+ * The other way from probabilities to speech labels, beside the threshold + median of uvad_median_filter (the reference's predict_step):
+ * two thresholds, a shortest speech interval, a shortest pause and asymmetric padding -- the parameter set of the pyannote pipeline whose
+ * output the reference scores itself against (src/scripts/other_vad_metrics.py reads baseline_vad/pyannote_output).  Offline: dense and
+ * ragged batches.  Everything after the two comparisons is integer; every output is byte-exact against a frame-loop restatement
+ * (tests/binarize_ref.py).
+ *
+ * Semantics for row b with n = clamp(d_lens[b], 0, T) (T when d_lens is NULL) and p = d_probs [B][ld_p] f32; columns at or past n, and
+ * whole rows with n = 0, are never read:
+ *   1 classes   frame t is HI iff !(p[t] < onset) (NaN counts as speech, as uvad_median_filter), LO iff p[t] < offset, MID otherwise;
+ *               offset <= onset, so no frame is both;
+ *   2 state     s[-1] = 0; s[t] = 1 on HI, 0 on LO, s[t - 1] on MID;
+ *   3 runs      [s_i, c_i) of s on [0, n), exactly as uvad_label_runs_lens;
+ *   4 pad       each run becomes [max(s_i - pad_on, 0), min(c_i + pad_off, n));
+ *   5 fill      left to right, an interval merges into its predecessor iff start - prev_end <= 0 or start - prev_end < min_off (on the
+ *               raw runs: s' - c <= pad_on + pad_off + max(min_off - 1, 0));
+ *   6 drop      a merged interval [lo, hi) is kept iff hi - lo >= min_on.
+ *   The order is pad, fill, drop.  onset = offset and all four integers 0 give the runs of !(p < onset): uvad_median_filter_lens with
+ *   kernel 1, then uvad_label_runs_lens.  pad_on = pad_off = P with min_off <= 1 and min_on = 0 is the merge step of uvad_cuts_table.
+ * Outputs: d_iv [B][max_iv][2] int32 {lo, hi} in time order and d_iv_counts [B] int32, the TRUE number of kept intervals: intervals past
+ *   max_iv are counted but not stored and later entries are not written (as uvad_label_runs treats max_runs; (T + 1) / 2 always
+ *   suffices).  The pair is what uvad_intervals_to_labels reads.  d_labels [B][ld] uint8 (may be NULL): 1 on the union of the row's kept
+ *   intervals, 0 elsewhere on [0, n); columns at or past n are not written.  The labels come from the row's full interval list, never
+ *   from a truncated d_iv.  d_iv may be NULL when max_iv is 0.
+ * Workspace: uvad_binarize_ws_bytes(ctx, B, T) bytes (0 on a bad argument), 16-byte aligned; its contents before the call do not matter.
+ * The call allocates nothing, never synchronises and reads the lengths on the device; its grids depend on B and T alone, so a graph
+ * captured around it replays for new probabilities and lengths.  Rows of d_probs that all start on a 16-byte boundary (d_probs aligned
+ * and ld_p a multiple of 4, or B = 1) are read with 16-byte loads; any other layout works, with 4-byte loads.  No atomics.  A context
+ * created without feature / model configuration serves it.
+ * Refusals (UVAD_E_ARG, nothing enqueued, uvad_last_error names the word): a NULL cfg, d_probs, d_iv_counts or d_ws; NULL d_iv with
+ *   max_iv > 0; onset or offset not finite, or offset > onset; min_on, min_off, pad_on or pad_off outside [0, 2^20]; B < 1; T < 1 or
+ *   > 2^30; ld_p < T; ld < T with labels; max_iv < 0; d_ws not 16-byte aligned; B x ceil(T / 2048) above 2^31 - 1; ws_bytes below
+ *   uvad_binarize_ws_bytes ("need N bytes"). */
+typedef struct {
+    float onset;    /* a frame with !(p < onset) turns speech on (NaN counts as speech, as uvad_median_filter) */
+    float offset;   /* a frame with p < offset turns speech off; finite, offset <= onset */
+    int min_on;     /* frames, 0 .. 2^20: a final interval shorter than this is dropped */
+    int min_off;    /* frames, 0 .. 2^20: a pause shorter than this between two intervals is filled */
+    int pad_on;     /* frames, 0 .. 2^20, added before every run */
+    int pad_off;    /* frames, 0 .. 2^20, added after every run */
+} uvad_binarize_cfg;   /* 24 bytes */
+size_t uvad_binarize_ws_bytes(const uvad_ctx *, int B, int T);
+int uvad_binarize(uvad_ctx *, const float *d_probs, int ld_p, int B, int T, const int32_t *d_lens, const uvad_binarize_cfg *,
+                  uint8_t *d_labels, int ld, int32_t *d_iv, int max_iv, int32_t *d_iv_counts, void *d_ws, size_t ws_bytes, void *stream);
+
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;
  *   1  (default) f32-accurate on the f16 matrix cores: weights scaled by a power of two and split on the host into THREE

@@ -60,6 +60,11 @@ class Cut(C.Structure):          # uvad_cut: one row of the cut table (32 bytes)
                 ("first_sample", C.c_int64), ("n_samples", C.c_int64)]
 
 
+class BinarizeCfg(C.Structure):  # uvad_binarize_cfg: thresholds and frame counts of uvad_binarize (24 bytes)
+    _fields_ = [("onset", C.c_float), ("offset", C.c_float), ("min_on", C.c_int), ("min_off", C.c_int), ("pad_on", C.c_int),
+                ("pad_off", C.c_int)]
+
+
 class UvadError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{ERR_NAMES.get(code, code)}: {msg}")
@@ -171,6 +176,9 @@ SIGNATURES = {
                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_cuts_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                    C.c_int64, C.c_void_p, C.c_void_p]),
+    "uvad_binarize_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "uvad_binarize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(BinarizeCfg), C.c_void_p, C.c_int,
+                                C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_classify_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_forward_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -215,7 +223,7 @@ _lib = None
 
 def bind(lib):
     """Declare every prototype of SIGNATURES on `lib`.  The ABI number did not move when entries were appended (the ingest stage among
-    them, the endpointer, the scoring stage and the speech cuts after it), so a library built from an older tree passes the version check: a symbol it lacks is a loud error here, by name."""
+    them, the endpointer, the scoring stage, the speech cuts and the hysteresis decisions after it), so a library built from an older tree passes the version check: a symbol it lacks is a loud error here, by name."""
     for name, (res, args) in SIGNATURES.items():
         try:
             fn = getattr(lib, name)

@@ -62,6 +62,11 @@ def load_config() -> ConfigDict:
     # buffer and merged, with split cut to at most window seconds, remainders of min seconds or less dropped (uvad_cuts_table); with
     # write_dir one 16 kHz wav per cut is written there (uvad_cuts_gather)
     cfg.cuts = None
+    # binarize = None: labels are threshold 0.5 + median, as the reference's predict_step.  A dict in seconds {"onset": 0.5, "offset": None,
+    # "min_duration_on": 0.0, "min_duration_off": 0.0, "pad_onset": 0.0, "pad_offset": 0.0}: hysteresis decisions instead (uvad_binarize)
+    # -- speech turns on at onset and off below offset, runs are padded, pauses shorter than min_duration_off filled and intervals shorter
+    # than min_duration_on dropped; with cuts, pass buffer = 0 there if padding was applied here
+    cfg.binarize = None
 
     cfg.experiments_dir = os.environ.get("UVAD_EXPERIMENTS_DIR", "experiments")
     cfg.load_checkpoint = False

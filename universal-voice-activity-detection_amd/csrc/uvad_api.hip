@@ -3123,6 +3123,54 @@ int uvad_cuts_gather(uvad_ctx *c, const void *d_src, int64_t row_stride, int uni
     return UVAD_OK;
 }
 
+// ---- hysteresis decisions with minimum durations (binarize.hip) ---------------------------------------------------------------------------
+// nullptr: the configuration is in range; else the word uvad_last_error names
+static const char *binarize_cfg_error(const uvad_binarize_cfg *q) {
+    if (!q) return "cfg is NULL";
+    if (!std::isfinite(q->onset)) return "onset must be finite";
+    if (!std::isfinite(q->offset)) return "offset must be finite";
+    if (q->offset > q->onset) return "offset must be <= onset";
+    if (q->min_on < 0 || q->min_on > BIN_MAX_FRAMES) return "min_on must lie in [0, 2^20] frames";
+    if (q->min_off < 0 || q->min_off > BIN_MAX_FRAMES) return "min_off must lie in [0, 2^20] frames";
+    if (q->pad_on < 0 || q->pad_on > BIN_MAX_FRAMES) return "pad_on must lie in [0, 2^20] frames";
+    if (q->pad_off < 0 || q->pad_off > BIN_MAX_FRAMES) return "pad_off must lie in [0, 2^20] frames";
+    return nullptr;
+}
+
+size_t uvad_binarize_ws_bytes(const uvad_ctx *c, int B, int T) {
+    if (!c || B < 1 || T < 1 || T > BIN_MAX_T) return 0;
+    return bin_ws_bytes(B, T);
+}
+
+int uvad_binarize(uvad_ctx *c, const float *d_probs, int ld_p, int B, int T, const int32_t *d_lens, const uvad_binarize_cfg *q,
+                  uint8_t *d_labels, int ld, int32_t *d_iv, int max_iv, int32_t *d_iv_counts, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (const char *w = binarize_cfg_error(q)) return fail(c, UVAD_E_ARG, std::string("uvad_binarize: ") + w);
+    if (B < 1) return fail(c, UVAD_E_ARG, "uvad_binarize: B must be >= 1");
+    if (T < 1 || T > BIN_MAX_T) return fail(c, UVAD_E_ARG, "uvad_binarize: T must lie in [1, 2^30]");
+    if (ld_p < T) return fail(c, UVAD_E_ARG, "uvad_binarize: ld_p must be at least T");
+    if (d_labels && ld < T) return fail(c, UVAD_E_ARG, "uvad_binarize: ld must be at least T");
+    if (max_iv < 0) return fail(c, UVAD_E_ARG, "uvad_binarize: max_iv must be >= 0");
+    if (!d_probs) return fail(c, UVAD_E_ARG, "uvad_binarize: d_probs is NULL");
+    if (!d_iv_counts) return fail(c, UVAD_E_ARG, "uvad_binarize: d_iv_counts is NULL");
+    if (!d_ws) return fail(c, UVAD_E_ARG, "uvad_binarize: d_ws is NULL");
+    if (reinterpret_cast<uintptr_t>(d_ws) % 16) return fail(c, UVAD_E_ARG, "uvad_binarize: d_ws must be 16-byte aligned");
+    if (max_iv > 0 && !d_iv) return fail(c, UVAD_E_ARG, "uvad_binarize: d_iv is NULL with max_iv > 0");
+    if ((long long)B * ((T + BIN_SEG - 1) / BIN_SEG) > 0x7fffffffll) return fail(c, UVAD_E_ARG, "uvad_binarize: B x segments above 2^31 - 1");
+    const size_t need = bin_ws_bytes(B, T);
+    if (ws_bytes < need) return fail(c, UVAD_E_ARG, "uvad_binarize: workspace too small: need " + std::to_string(need) + " bytes");
+    BinarizeArgs a{};
+    a.probs = d_probs; a.ld_p = ld_p; a.B = B; a.T = T; a.lens = d_lens;
+    a.q = BinCfgInt{q->onset, q->offset, q->min_on, q->min_off, q->pad_on, q->pad_off};
+    a.iv = d_iv; a.max_iv = max_iv; a.iv_counts = d_iv_counts;
+    a.words = reinterpret_cast<unsigned long long *>(d_ws);
+    a.list = reinterpret_cast<int *>(reinterpret_cast<char *>(d_ws) + bin_words_bytes(B, T));
+    a.nwt = bin_words(T); a.cap = (T + 1) / 2;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_binarize(a, d_labels, ld, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
 int uvad_set_gemm_mode(uvad_ctx *c, int mode) {
     if (!c) return UVAD_E_ARG;
     if (mode < 0 || mode > 3)

@@ -578,4 +578,23 @@ int cuts_max_per_row(const CutsCfgInt &q, int T);
 hipError_t launch_cuts_table(const CutsTableArgs &a, hipStream_t s);
 hipError_t launch_cuts_gather(const CutsGatherArgs &a, hipStream_t s);
 
+// ---- binarize.hip: hysteresis decisions with minimum durations (uvad_binarize, include/uvad.h) -------------------------------------------
+// The workspace is (T + 63) / 64 word pairs {HI mask, LO mask} per row (16 bytes a pair), followed by (T + 1) / 2 int32 pairs {lo, hi}
+// per row: the row's full interval list, which the labels are made from.
+constexpr int BIN_MAX_T = 1 << 30;                    // frame arithmetic stays in int32 with two pads, a pause and a pass on top
+constexpr int BIN_MAX_FRAMES = 1 << 20;               // min_on, min_off, pad_on, pad_off
+constexpr int BIN_SEG = 2048;                         // frames per workgroup of binarize_classify_kernel
+constexpr int BIN_SPAN_WORDS = CUTS_SPAN_WORDS;       // 64-frame words per pass of binarize_rows_kernel: 4096 frames
+struct BinCfgInt { float onset, offset; int min_on, min_off, pad_on, pad_off; };   // uvad_binarize_cfg, field for field
+struct BinarizeArgs {
+    const float *probs; int ld_p, B, T; const int *lens;
+    BinCfgInt q;
+    int *iv; int max_iv; int *iv_counts;
+    unsigned long long *words; int *list; int nwt, cap;   // the workspace: [B][nwt][2], [B][cap][2]; nwt = (T + 63) / 64, cap = (T + 1) / 2
+};
+constexpr int bin_words(int T) { return (T + 63) / 64; }
+constexpr size_t bin_words_bytes(int B, int T) { return (size_t)B * bin_words(T) * 16; }
+constexpr size_t bin_ws_bytes(int B, int T) { return bin_words_bytes(B, T) + (size_t)B * ((T + 1) / 2) * 2 * sizeof(int); }
+hipError_t launch_binarize(const BinarizeArgs &a, uint8_t *labels, int ld, hipStream_t s);   // labels may be NULL
+
 }  // namespace uvad

@@ -241,6 +241,41 @@ def cuts_config(buffer: float = 0.0, split: bool = False, window: float = 10.0, 
             "hop": int(hop), "lead": int(lead), "tail": int(tail)}
 
 
+def binarize_config(onset: float = 0.5, offset=None, min_duration_on: float = 0.0, min_duration_off: float = 0.0, pad_onset: float = 0.0,
+                    pad_offset: float = 0.0, frame_shift: float = 0.01) -> dict:
+    """Hysteresis options in seconds -> the configuration of uvad_binarize (VadRuntime.binarize_open): the two thresholds as they are
+    (offset defaults to onset), the durations in frames by int(round(x / frame_shift))."""
+    fr = lambda x: int(round(float(x) / frame_shift))
+    return {"onset": float(onset), "offset": float(onset if offset is None else offset), "min_on": fr(min_duration_on),
+            "min_off": fr(min_duration_off), "pad_on": fr(pad_onset), "pad_off": fr(pad_offset)}
+
+
+def hysteresis_runs(probs, cfg: dict) -> List[Tuple[int, int]]:
+    """One row of probabilities -> its speech intervals [(lo, hi)] in frames under cfg (binarize_config's dict): the host restatement of
+    what uvad_binarize (VadRuntime.binarize) lists for the row.  The state turns on at !(p < onset), off at p < offset (compared in f32,
+    NaN counts as speech) and holds in between; its runs are widened by pad_on / pad_off and clipped to the row, an interval merges into
+    its predecessor when the pause between them is <= 0 or shorter than min_off, and merged intervals shorter than min_on are dropped."""
+    onset, offset = np.float32(cfg.get("onset", 0.5)), np.float32(cfg.get("offset", cfg.get("onset", 0.5)))
+    min_on, min_off, pad_on, pad_off = (int(cfg.get(k, 0)) for k in ("min_on", "min_off", "pad_on", "pad_off"))
+    if not (np.isfinite(onset) and np.isfinite(offset)) or offset > onset or min(min_on, min_off, pad_on, pad_off) < 0:
+        raise ValueError(f"need finite offset <= onset and frame counts >= 0, got {cfg}")
+    p = np.asarray(probs.cpu() if torch.is_tensor(probs) else probs, np.float32).ravel()
+    hi_f, lo_f = ~(p < onset), p < offset
+    # the state holds the class of the last frame that was not MID: forward-fill the index of that frame
+    idx = np.where(hi_f | lo_f, np.arange(p.size), -1)
+    idx = np.maximum.accumulate(idx) if p.size else idx
+    v = np.where(idx >= 0, hi_f[np.maximum(idx, 0)], False).astype(np.int8)
+    d = np.diff(np.concatenate(([0], v, [0])))
+    out = []
+    for s, c in zip(np.flatnonzero(d == 1).tolist(), np.flatnonzero(d == -1).tolist()):
+        lo, hi = max(s - pad_on, 0), min(c + pad_off, len(v))
+        if out and (lo <= out[-1][1] or lo - out[-1][1] < min_off):
+            out[-1][1] = max(out[-1][1], hi)
+        else:
+            out.append([lo, hi])
+    return [(lo, hi) for lo, hi in out if hi - lo >= min_on]
+
+
 def intervals_to_labels(intervals, total_duration: float, frame_shift: float) -> np.ndarray:
     """predict.py:654-663 (get_binary_tensor): ceil(duration/shift) frames, [int(s/shift), int(e/shift)) set to 1."""
     import math

@@ -1103,6 +1103,66 @@ class VadRuntime:
             n = min(int(cuts["total"].cpu()[0]), cuts["max_cuts"])
             return cuts["table"][:n].cpu().numpy().view(dt).reshape(-1).copy()
 
+    # ------------------------------------------------------------------ hysteresis decisions with minimum durations (uvad_binarize)
+    def binarize_open(self, onset: float = 0.5, offset=None, min_on: int = 0, min_off: int = 0, pad_on: int = 0, pad_off: int = 0, max_iv=None):
+        """The configuration and the buffers of binarize below: speech turns on at a frame with !(p < onset) and off at one with p < offset
+        (default: onset), every run is widened by pad_on frames before and pad_off after, pauses shorter than min_off frames are filled and
+        intervals shorter than min_on frames dropped, in that order (postprocess.binarize_config makes these from seconds).  max_iv: the
+        intervals stored per row (default (T + 1) // 2, which never overflows).  Buffers are sized by the first call with a shape; after
+        that the call allocates nothing and can be captured."""
+        offset = onset if offset is None else offset
+        ints = {"min_on": min_on, "min_off": min_off, "pad_on": pad_on, "pad_off": pad_off}
+        ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 <= int(v) <= (1 << 20) for v in ints.values())
+        if not ok or not (np.isfinite(onset) and np.isfinite(offset)) or float(np.float32(offset)) > float(np.float32(onset)):
+            raise ValueError(f"bad binarize configuration: onset {onset} and offset {offset} must be finite with offset <= onset; "
+                             f"min_on {min_on}, min_off {min_off}, pad_on {pad_on} and pad_off {pad_off} must be integers in 0 .. 2^20 frames")
+        if max_iv is not None and int(max_iv) < 0:
+            raise ValueError("max_iv must be >= 0")
+        cfg = _lib.BinarizeCfg(float(onset), float(offset), int(min_on), int(min_off), int(pad_on), int(pad_off))
+        return {"cfg": cfg, "max_iv": None if max_iv is None else int(max_iv), "labels": None, "iv": None, "counts": None, "ws": None}
+
+    def binarize(self, probs: "torch.Tensor", lengths=None, state=None, labels: bool = True, **cfg):
+        """probs (B, T) f32 on the GPU (row-strided views are used as they are), lengths (B,) valid frames per row (a device tensor is read
+        on the device).  state: one of binarize_open; without it one is opened from **cfg.  -> (labels (B, T) uint8 or None, intervals
+        (B, max_iv, 2) int32 {lo, hi}, counts (B,) int32 -- the true numbers, which may exceed max_iv), on the device and overwritten by
+        the next call on the state.  Label columns at or past a row's length keep what they held (zero in a fresh state).  binarize_read
+        gives the host view."""
+        st = state if state is not None else self.binarize_open(**cfg)
+        with torch.cuda.device(self.device):
+            if not torch.is_tensor(probs) or probs.device != self.device:
+                raise RuntimeError(f"probs must be a tensor on {self.device}")
+            probs = self._rows_2d(probs, torch.float32, "probs")
+            B, T = probs.shape
+            n = None if lengths is None else self._dev_lens(lengths, B, T, torch.int32, "lengths (frames)")
+            if st["max_iv"] is None:
+                st["max_iv"] = (T + 1) // 2
+            mi = st["max_iv"]
+            if st["iv"] is None or st["iv"].shape[0] != B:
+                st["iv"] = torch.zeros((B, max(mi, 1), 2), dtype=torch.int32, device=self.device)
+                st["counts"] = torch.zeros(B, dtype=torch.int32, device=self.device)
+            if labels and (st["labels"] is None or tuple(st["labels"].shape) != (B, T)):
+                st["labels"] = torch.zeros((B, T), dtype=torch.uint8, device=self.device)
+            need = int(self.lib.uvad_binarize_ws_bytes(self.ctx, B, T))
+            if st["ws"] is None or st["ws"].numel() < need:
+                st["ws"] = torch.zeros(max(need, 16), dtype=torch.uint8, device=self.device)
+            lab = st["labels"] if labels else None
+            self._check(self.lib.uvad_binarize(self.ctx, probs.data_ptr(), probs.stride(0) if B > 1 else max(probs.stride(0), T), B, T,
+                                               n.data_ptr() if n is not None else None, C.byref(st["cfg"]),
+                                               lab.data_ptr() if lab is not None else None, T, st["iv"].data_ptr() if mi else None, mi,
+                                               st["counts"].data_ptr(), st["ws"].data_ptr(), st["ws"].numel(), self._stream()))
+            st["_keep"] = (probs, n)   # the launch reads them after this call returns
+            return lab, st["iv"][:, :mi], st["counts"]
+
+    def binarize_read(self, state):
+        """The intervals the last binarize on the state listed, copied to the host (synchronises): per row [(lo, hi)] in frames, the
+        first min(count, max_iv) of each row."""
+        if state.get("iv") is None:
+            raise RuntimeError("binarize_read needs a state on which binarize has run")
+        with torch.cuda.device(self.device):
+            cn = state["counts"].cpu().numpy()
+            iv = state["iv"].cpu().numpy()
+        return [[(int(lo), int(hi)) for lo, hi in iv[b, :min(int(cn[b]), state["max_iv"])]] for b in range(len(cn))]
+
     # ------------------------------------------------------------------ sliding windows over whole recordings (uvad_sliding_*)
     def sliding_configure(self, window: int, hop: int, weights=None):
         """Window and hop in frames and the aggregation weights (W,) -- None: all ones; postprocess.sliding_weights makes the usual ones

@@ -18,7 +18,11 @@ Cut geometry (``window_seconds``, default = the reference's 5.0):
 
 Every batch goes through the fused hot path: PCM (int16 straight from the wav file, or f32) ->
 ``uvad_forward[_i16]`` (features stay in the workspace; SincNet: ``uvad_forward_wav[_i16]``) -> ``uvad_median_filter`` ->
-``uvad_label_runs``; several batches are kept in flight with ``ForwardPipeline`` when there is more than one."""
+``uvad_label_runs``; several batches are kept in flight with ``ForwardPipeline`` when there is more than one.
+
+``binarize={...}`` (seconds; ``BINARIZE_DEFAULTS``) replaces the last two steps by ``uvad_binarize``: hysteresis between an onset and an
+offset threshold, padding, pauses shorter than ``min_duration_off`` filled and intervals shorter than ``min_duration_on`` dropped.  The
+default, ``None``, leaves every path as described above."""
 import json
 import math
 import os
@@ -32,7 +36,8 @@ import torch
 from .engine import VadModel
 from .features import FbankConfig
 from .pipeline import ForwardPipeline
-from .postprocess import cuts_config, labels_to_intervals_batch, median_filter, sincnet_labels_to_intervals, sliding_weights
+from .postprocess import (binarize_config, cuts_config, labels_to_intervals_batch, median_filter, sincnet_frame_times,
+                          sincnet_labels_to_intervals, sliding_weights)
 from .sincnet import SincNet
 from .synth import seed_weights, synth_pcm
 
@@ -240,6 +245,39 @@ def _attach_cuts(results, recs, dev_labels, rt, cuts, sincnet, frame_shift, devi
                 _write_wav_int16(os.path.join(opt["write_dir"], f"{res['recording_id']}_{int(c['index']):04d}.wav"), batch[k, :lens[k]], sr)
 
 
+BINARIZE_DEFAULTS = {"onset": 0.5, "offset": None, "min_duration_on": 0.0, "min_duration_off": 0.0, "pad_onset": 0.0, "pad_offset": 0.0}
+
+
+def _binarize_frames(binarize, sincnet, frame_shift, sr=16000):
+    """predict_vad(binarize=...): the options in seconds -> uvad_binarize's configuration in frames (10 ms log-mel frames; the SincNet
+    model's 270-sample hop)."""
+    unknown = set(binarize) - set(BINARIZE_DEFAULTS)
+    if unknown:
+        raise ValueError(f"unknown binarize option(s) {sorted(unknown)} (known: {sorted(BINARIZE_DEFAULTS)})")
+    return binarize_config(**{**BINARIZE_DEFAULTS, **binarize}, frame_shift=270.0 / sr if sincnet else frame_shift)
+
+
+def _binarize_post(rt, cfg, probs, frames, durations, sincnet, frame_shift):
+    """The decision stage of predict_vad(binarize=...) for one batch: probs (B, T) on the GPU with `frames` valid frames per row ->
+    (labels (B, T) uint8 on the GPU, per-row [(start_s, end_s)]).  One uvad_binarize call; its interval table is the only thing that
+    crosses to the host, where an interval [lo, hi) is given in seconds as the median path gives the run [lo, hi): round(lo * shift, 2)
+    and round((hi - 1) * shift, 2) for log-mel frames, sincnet_frame_times(lo, hi - 1) for the waveform model, kept iff end - start > 0."""
+    st = rt.binarize_open(**cfg)
+    lab, _, _ = rt.binarize(probs, lengths=frames, state=st)
+    out = []
+    for r, row in enumerate(rt.binarize_read(st)):
+        ivs = []
+        for lo, hi in row:
+            if sincnet:
+                s, e = sincnet_frame_times(lo, hi - 1, durations[r])
+            else:
+                s, e = round(float(lo * frame_shift), 2), round(float((hi - 1) * frame_shift), 2)
+            if e - s > 0.0:
+                ivs.append((s, e))
+        out.append(ivs)
+    return lab, out
+
+
 def sliding_geometry(rt, sincnet: bool, window_seconds: float, hop_seconds: float, frame_shift: float, sr: int = 16000):
     """(W, Hf) in frames of predict_vad's sliding path: the frames of one window of window_seconds -- 500 log-mel frames, 293 of the
     waveform model for the reference's 5 s -- and the hop rounded to whole frames (10 ms log-mel frames; 270-sample SincNet frames)."""
@@ -251,7 +289,7 @@ def sliding_geometry(rt, sincnet: bool, window_seconds: float, hop_seconds: floa
     return W, Hf
 
 
-def _predict_sliding(recs, rt, sincnet, kwargs, window_s, hop_s, frame_shift, med_window, device, sr=16000, dev_labels=None):
+def _predict_sliding(recs, rt, sincnet, kwargs, window_s, hop_s, frame_shift, med_window, device, sr=16000, dev_labels=None, binarize=None):
     """predict_vad with hop_seconds: whole recordings as ragged [R][S_max] batches within the max_duration budget, overlapping windows
     aggregated on the device (uvad_sliding_forward[_wav][_i16]), then the lens median filter and run-length kernels on the frame counts
     the call returned.  Every recording is copied into its row of the device batch by itself: nothing is stacked on the host."""
@@ -276,12 +314,15 @@ def _predict_sliding(recs, rt, sincnet, kwargs, window_s, hop_s, frame_shift, me
             x[r, :lengths[i]] = row.float() / 32768.0 if mixed and row.dtype == torch.int16 else row
         nsamp = [lengths[i] for i in batch]
         probs, frames = (rt.sliding_forward_wav if sincnet else rt.sliding_forward)(x, nsamp, group=group)
-        lab = median_filter(probs, window=med_window, runtime=rt, lengths=frames)         # uvad_median_filter_lens
         fr = frames.tolist()
-        if sincnet:
-            ivs = [sincnet_labels_to_intervals(lab[r, :fr[r]], nsamp[r] / sr, runtime=rt) if fr[r] else [] for r in range(len(batch))]
+        if binarize is not None:   # uvad_binarize in place of the median filter and the run walk
+            lab, ivs = _binarize_post(rt, binarize, probs, frames, [n / sr for n in nsamp], sincnet, frame_shift)
         else:
-            ivs = labels_to_intervals_batch(lab, frame_shift, runtime=rt, lengths=frames)     # uvad_label_runs_lens
+            lab = median_filter(probs, window=med_window, runtime=rt, lengths=frames)         # uvad_median_filter_lens
+            if sincnet:
+                ivs = [sincnet_labels_to_intervals(lab[r, :fr[r]], nsamp[r] / sr, runtime=rt) if fr[r] else [] for r in range(len(batch))]
+            else:
+                ivs = labels_to_intervals_batch(lab, frame_shift, runtime=rt, lengths=frames)     # uvad_label_runs_lens
         for r, i in enumerate(batch):
             results[i] = {"recording_id": recs[i]["id"], "num_frames": int(fr[r]), "labels": lab[r, :fr[r]].cpu().numpy().astype(np.uint8),
                           "probs": probs[r, :fr[r]].cpu().numpy(), "intervals": ivs[r]}
@@ -345,13 +386,16 @@ def predict_vad(**kwargs):
                 pieces.append((ri, st, ln))
     W = None if window_s is None else int(round(window_s * sr))
     med_window = 0.02 if net.encoding_dim == 768 else 0.01   # vad_engine.py:207-208
+    binarize = kwargs.get("binarize")   # None: threshold 0.5 + median as below; a dict in seconds (BINARIZE_DEFAULTS): uvad_binarize instead
+    if binarize is not None:
+        binarize = _binarize_frames(binarize, sincnet, frame_shift, sr)
     cuts = kwargs.get("cuts")   # None: every output below is what it was; a dict (CUTS_DEFAULTS): every result gains "cuts" (_attach_cuts)
     dev_labels = [None] * len(recs) if cuts is not None else None   # each recording's whole-row labels, kept on the device
     hop_s = kwargs.get("hop_seconds")
     if hop_s is not None:   # overlapping windows of window_seconds every hop_seconds, aggregated on the device; None: the cuts below, unchanged
         if window_s is None:
             raise ValueError("hop_seconds needs window_seconds (the window the model was trained on)")
-        results = _predict_sliding(recs, net.runtime(device), sincnet, kwargs, window_s, hop_s, frame_shift, med_window, device, sr, dev_labels)
+        results = _predict_sliding(recs, net.runtime(device), sincnet, kwargs, window_s, hop_s, frame_shift, med_window, device, sr, dev_labels, binarize)
         if cuts is not None:
             _attach_cuts(results, recs, dev_labels, net.runtime(device), cuts, sincnet, frame_shift, device, int(kwargs["max_duration"] * sr), sr)
         return _write_results(results, kwargs)
@@ -402,11 +446,14 @@ def predict_vad(**kwargs):
     def ragged_post(group, probs):
         nsamp = [pieces[j][2] for j in group]
         fr = [rt.sincnet_num_frames(n) if sincnet else rt.num_frames(n) for n in nsamp]
-        lab = median_filter(probs, window=med_window, lengths=fr)                      # uvad_median_filter_lens
-        if sincnet:   # frame index -> seconds by the receptive field, as the dense path below (whole recordings: every frame is kept)
-            ivs = [sincnet_labels_to_intervals(lab[r, :fr[r]], n / sr) if fr[r] else [] for r, n in enumerate(nsamp)]
+        if binarize is not None:   # uvad_binarize in place of the median filter and the run walk
+            lab, ivs = _binarize_post(rt, binarize, probs, fr, [n / sr for n in nsamp], sincnet, frame_shift)
         else:
-            ivs = labels_to_intervals_batch(lab, frame_shift, runtime=rt, lengths=fr)     # uvad_label_runs_lens
+            lab = median_filter(probs, window=med_window, lengths=fr)                      # uvad_median_filter_lens
+            if sincnet:   # frame index -> seconds by the receptive field, as the dense path below (whole recordings: every frame is kept)
+                ivs = [sincnet_labels_to_intervals(lab[r, :fr[r]], n / sr) if fr[r] else [] for r, n in enumerate(nsamp)]
+            else:
+                ivs = labels_to_intervals_batch(lab, frame_shift, runtime=rt, lengths=fr)     # uvad_label_runs_lens
         for r, j in enumerate(group):
             piece_probs[j] = probs[r, :fr[r]]
             piece_post[j] = (lab[r, :fr[r]], ivs[r])
@@ -474,20 +521,7 @@ def predict_vad(**kwargs):
             if dev_labels is not None:
                 dev_labels[ri] = labels
             continue
-        rows_l, rows_p = [], []
-        by_len = {}
-        for j in mine:
-            by_len.setdefault(piece_probs[j].shape[0], []).append(j)
-        lab_of = {}
-        for T, js in by_len.items():
-            lab = median_filter(torch.stack([piece_probs[j] for j in js]), window=med_window)   # (n, T) 0/1 on the GPU
-            for k, j in enumerate(js):
-                lab_of[j] = lab[k]
-        for j in mine:
-            rows_l.append(lab_of[j])
-            rows_p.append(piece_probs[j])
-        labels = torch.cat(rows_l)
-        probs = torch.cat(rows_p)
+        probs = torch.cat([piece_probs[j] for j in mine])
         duration = len(r["pcm"]) / sr
         # How many of a recording's frames are kept.  The reference lays the rows of ALL recordings end to end (preds_flat) and
         # gives recording i the slice [start_i, start_i + n_i) with start_i = the sum of the earlier n_j (predict.py:451-458,
@@ -498,18 +532,32 @@ def predict_vad(**kwargs):
         # reference computes for the first recording, and for every recording of a one-recording run).  The per-recording
         # behaviour is pinned by tests (single recordings against the reference-generated fixture, two recordings against their
         # single-recording runs); parity with the reference's drifting multi-recording slices is unpinned by intent.
+        keep = probs.shape[0]
         if sincnet:
             # n as the reference computes it: get_num_frames on the FLOAT 16000 * duration (receptive_field.py:28-55 floor-divides
-            # whatever it is given), then ceil + 1; :348-370 + :492-504: frame index -> seconds by receptive field (step 270
-            # samples, offset round(0.5 * 991) = 496), NOT by frame_shift
-            keep = min(int(math.ceil(SincNet.num_frames(16000 * duration))) + 1, labels.shape[0])
-            labels, probs = labels[:keep], probs[:keep]
-            intervals = sincnet_labels_to_intervals(labels, duration)
+            # whatever it is given), then ceil + 1
+            keep = min(int(math.ceil(SincNet.num_frames(16000 * duration))) + 1, keep)
+        elif window_s is not None:
+            keep = min(int(math.ceil(duration / frame_shift)) + 1, keep)
+        probs = probs[:keep]
+        if binarize is not None:   # one uvad_binarize call on the recording's kept frames laid end to end: the state, the pauses and the
+            # minimum durations carry across the windows' seams, which a per-window decision could not do
+            lab, ivs = _binarize_post(rt, binarize, probs.reshape(1, -1).contiguous(), None, [duration], sincnet, frame_shift)
+            labels, intervals = lab[0], ivs[0]
         else:
-            if window_s is not None:
-                keep = min(int(math.ceil(duration / frame_shift)) + 1, labels.shape[0])
-                labels, probs = labels[:keep], probs[:keep]
-            intervals = labels_to_intervals_batch(labels.unsqueeze(0), frame_shift)[0]   # run-length walk on the GPU (uvad_label_runs)
+            by_len = {}
+            for j in mine:
+                by_len.setdefault(piece_probs[j].shape[0], []).append(j)
+            lab_of = {}
+            for T, js in by_len.items():
+                lab = median_filter(torch.stack([piece_probs[j] for j in js]), window=med_window)   # (n, T) 0/1 on the GPU
+                for k, j in enumerate(js):
+                    lab_of[j] = lab[k]
+            labels = torch.cat([lab_of[j] for j in mine])[:keep]
+            if sincnet:   # :348-370 + :492-504: frame index -> seconds by receptive field (step 270 samples, offset round(0.5 * 991) = 496), NOT by frame_shift
+                intervals = sincnet_labels_to_intervals(labels, duration)
+            else:
+                intervals = labels_to_intervals_batch(labels.unsqueeze(0), frame_shift)[0]   # run-length walk on the GPU (uvad_label_runs)
         results.append({"recording_id": r["id"], "num_frames": int(labels.shape[0]), "labels": labels.cpu().numpy().astype(np.uint8),
                         "probs": probs.cpu().numpy(), "intervals": intervals})
         if dev_labels is not None:
