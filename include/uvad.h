@@ -713,8 +713,8 @@ int uvad_cuts_gather(uvad_ctx *, const void *d_src, int64_t row_stride, int unit
  * The other way from probabilities to speech labels, beside the threshold + median of uvad_median_filter (the reference's predict_step):
  * two thresholds, a shortest speech interval, a shortest pause and asymmetric padding -- the parameter set of the pyannote pipeline whose
  * output the reference scores itself against (src/scripts/other_vad_metrics.py reads baseline_vad/pyannote_output).  Offline: dense and
- * ragged batches.  Everything after the two comparisons is integer; every output is byte-exact against a frame-loop restatement
- * (tests/binarize_ref.py).
+ * ragged batches (live feeds: uvad_endpoint_hyst_* below).  Everything after the two comparisons is integer; every output is byte-exact
+ * against a frame-loop restatement (tests/binarize_ref.py).
  *
  * Semantics for row b with n = clamp(d_lens[b], 0, T) (T when d_lens is NULL) and p = d_probs [B][ld_p] f32; columns at or past n, and
  * whole rows with n = 0, are never read:
@@ -753,6 +753,59 @@ typedef struct {
 size_t uvad_binarize_ws_bytes(const uvad_ctx *, int B, int T);
 int uvad_binarize(uvad_ctx *, const float *d_probs, int ld_p, int B, int T, const int32_t *d_lens, const uvad_binarize_cfg *,
                   uint8_t *d_labels, int ld, int32_t *d_iv, int max_iv, int32_t *d_iv_counts, void *d_ws, size_t ws_bytes, void *stream);
+
+/* ---- Live hysteresis endpointing: uvad_binarize's decisions as per-feed events ----------------------------------------------------------
+ * The streaming counterpart of uvad_binarize, with the contract of uvad_endpoint_*: whatever way a session's frames are cut into steps,
+ * its events and labels, concatenated, are byte-identical to uvad_binarize on the session's whole row.  The configuration is
+ * uvad_binarize_cfg with uvad_binarize's validity rules; the step's argument list is uvad_endpoint_step's, so the d_probs / d_counts /
+ * d_flags a slot pool step wrote are consumed as they are.  Sessions, flags and n_b = clamp(d_counts[b], 0, ld_in) are exactly those of
+ * uvad_endpoint_step: UVAD_SLOT_START drops the old session silently, UVAD_SLOT_END flushes after the step's frames, columns >= n_b and
+ * rows with n_b = 0 are never read (NaN there changes no output byte).
+ *   The hysteresis state is causal -- s[t] is known the moment frame t arrives -- so the slot keeps no frames, and a START costs no frames
+ *   of delay when min_on is 0.  Let D = pad_on + pad_off + max(min_off - 1, 0).  Per slot the state is m, the frames seen; the state bit
+ *   s; mode, one of IDLE, SPEECH, PENDING; a confirmed bit; lo, c and the label frontier F.  For each new frame t = m, in order:
+ *     1 state bit   s becomes 1 on HI (!(p < onset), NaN included), 0 on LO (p < offset), and is unchanged on MID; compared in f32;
+ *     2 mode        IDLE and s = 1: lo = max(t - pad_on, 0), mode = SPEECH, unconfirmed.  SPEECH and s = 0: c = t, mode = PENDING.
+ *                   PENDING and s = 1: mode = SPEECH, the run rejoins with no event;
+ *     3 close       in PENDING with s = 0 and t >= c + D the interval is closed with hi = c + pad_off (with D = 0 in the frame that set
+ *                   c).  If it is confirmed END(hi) is issued; otherwise it vanishes without events: it is shorter than min_on.
+ *                   mode = IDLE;
+ *     4 confirm     m = t + 1.  If the mode is not IDLE and the interval is unconfirmed, let bound = m in SPEECH and min(c + pad_off, m)
+ *                   in PENDING; when bound - lo >= min_on, START(lo) is issued and the interval is confirmed (with min_on = 0 that is
+ *                   the frame the run begins in);
+ *     5 frontier    labels are final on [0, F).  IDLE: F = max(F, m - pad_on), the new labels are 0.  Confirmed SPEECH: F = m, the new
+ *                   labels are 1.  Confirmed PENDING: F = max(F, min(c + pad_off, m)), the new labels are 1.  Unconfirmed: F stays at
+ *                   lo.  When an interval closes, its frames [lo, hi) are written as 1 if it was kept and as 0 if it was dropped;
+ *     6 END flag    after the frames, n = m: an open interval closes at n, a pending one at min(c + pad_off, n); END is issued iff the
+ *                   interval is confirmed; F = n, and the slot holds the empty session again.
+ *   Hence a session's events, concatenated, are exactly START(lo_0), END(hi_0), START(lo_1), ... of uvad_binarize's kept interval list
+ *   on the whole session, and its finalised labels, concatenated, are uvad_binarize's d_labels row.  START is issued once the interval has
+ *   min_on frames the session has seen; END comes D - pad_off + 1 frames after hi.
+ *   Outputs per step, all DEVICE memory, as uvad_endpoint_step's; d_ev_counts is required, the others may be NULL:
+ *     d_events [B][max_events][2] int32 {kind, frame}, kind 1 = START, 2 = END; d_ev_counts [B] int32 the true number of events of this
+ *       step: at most n_b + 1 (one per frame, plus the flush), so max_events = ld_in + 1 always suffices; events beyond max_events are
+ *       counted but not stored;
+ *     d_active [B] uint8: 0 when idle, 1 while a confirmed interval is open or pending, 2 while an unconfirmed candidate is open or
+ *       pending -- the early gate a downstream recogniser may want before min_on is met;
+ *     d_labels [B][ld_lab] uint8: the labels finalised by this step, d_lab_counts [B] int32 their number: at most n_b + lag with
+ *       lag = uvad_endpoint_hyst_lag = min_on + D (attained), so ld_lab >= ld_in + lag, and d_labels needs d_lab_counts.
+ *   With onset = offset = thr, pad_on = pad_off = P, min_on = 0 and min_off <= 1 every step's events, event counts and active byte equal
+ *   those of uvad_endpoint_step with kernel 1, pad P, threshold thr.
+ *   Frames are int32 and saturate: a session consumes no frames past 2^31 - 1; positions such as c + pad_off are formed in 64 bits.
+ *   The configuration lives in the state (a header written by reset): a step carries none, is one launch, allocates nothing, never
+ *   synchronises and reads every per-slot quantity from the device, so a graph captured around any step -- alone or in the same capture
+ *   as the slot pool step that feeds it -- replays for every later one.  ld_in is at most 2^18 frames per step.  The state is 32 bytes
+ *   per slot behind a 256-byte header.  A context created without feature / model configuration serves these calls.
+ *   Refusals (UVAD_E_ARG, nothing enqueued, uvad_last_error names the word): uvad_binarize's checks on the cfg; B < 1; ld_in < 1 or
+ *   > 2^18; NULL d_probs / d_counts / d_ev_counts / d_state; max_events < 0, or d_events NULL with max_events > 0; d_labels with
+ *   ld_lab < ld_in + lag or without d_lab_counts; state_bytes below uvad_endpoint_hyst_state_bytes.  A state never reset, or reset with
+ *   another B: UVAD_E_STATE. */
+int uvad_endpoint_hyst_lag(const uvad_binarize_cfg *);   /* min_on + D; -1 on a bad cfg */
+size_t uvad_endpoint_hyst_state_bytes(const uvad_ctx *, int B, const uvad_binarize_cfg *);   /* 0 on a bad configuration */
+int uvad_endpoint_hyst_reset(uvad_ctx *, void *d_state, size_t state_bytes, int B, const uvad_binarize_cfg *, void *stream);
+int uvad_endpoint_hyst_step(uvad_ctx *, const float *d_probs, int ld_in, const int32_t *d_counts, const uint8_t *d_flags, int B,
+                            void *d_state, size_t state_bytes, int32_t *d_events, int max_events, int32_t *d_ev_counts, uint8_t *d_active,
+                            uint8_t *d_labels, int ld_lab, int32_t *d_lab_counts, void *stream);
 
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;

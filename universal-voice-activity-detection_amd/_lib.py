@@ -179,6 +179,11 @@ SIGNATURES = {
     "uvad_binarize_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "uvad_binarize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(BinarizeCfg), C.c_void_p, C.c_int,
                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_endpoint_hyst_lag": (C.c_int, [C.POINTER(BinarizeCfg)]),
+    "uvad_endpoint_hyst_state_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.POINTER(BinarizeCfg)]),
+    "uvad_endpoint_hyst_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(BinarizeCfg), C.c_void_p]),
+    "uvad_endpoint_hyst_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "uvad_classify_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_forward_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -223,7 +228,7 @@ _lib = None
 
 def bind(lib):
     """Declare every prototype of SIGNATURES on `lib`.  The ABI number did not move when entries were appended (the ingest stage among
-    them, the endpointer, the scoring stage, the speech cuts and the hysteresis decisions after it), so a library built from an older tree passes the version check: a symbol it lacks is a loud error here, by name."""
+    them, the endpointer, the scoring stage, the speech cuts, the hysteresis decisions and the hysteresis endpointer after it), so a library built from an older tree passes the version check: a symbol it lacks is a loud error here, by name."""
     for name, (res, args) in SIGNATURES.items():
         try:
             fn = getattr(lib, name)

@@ -99,6 +99,8 @@ struct WavWindowGroup { StreamCounters sc; int B = 0, W = 0, L = 0, is_i16 = 0; 
 struct SlotPool { int B = 0, chunk = 0, W = 0, L = 0, is_i16 = 0; };
 // an endpointer state (uvad_endpoint_*): what reset fixed; the device header holds the same and every per-slot quantity
 struct EndpointPool { int B = 0, kernel = 0, pad = 0; float threshold = 0.5f; };
+// a hysteresis endpointer state (uvad_endpoint_hyst_*): B and the lag of the configuration at its reset
+struct EndpointHystPool { int B = 0, lag = 0; };
 // a scoring state (uvad_score_*): the configuration's n_points and bins at its reset (the device header holds the same)
 struct ScoreState { int n_points = 0, bins = 0; };
 
@@ -108,6 +110,7 @@ struct uvad_ctx {
     std::map<void *, WavWindowGroup> wav_windows;   // ... and of the waveform model's windowed stream groups (uvad_window_wav_*)
     std::map<void *, SlotPool> slot_pools, wav_slot_pools;   // ... and of the slot pools of both window families (uvad_window_*slots_*)
     std::map<void *, EndpointPool> endpoints;   // ... and of the endpointer states (uvad_endpoint_*)
+    std::map<void *, EndpointHystPool> endpoint_hysts;   // ... and of the hysteresis endpointer states (uvad_endpoint_hyst_*)
     std::map<void *, ScoreState> scores;        // ... and of the scoring states (uvad_score_*)
     bool has_score = false;                     // uvad_score_configure: operating points, collar, bins, segment (0 replaced by the default)
     uvad_score_cfg sq{};
@@ -3168,6 +3171,58 @@ int uvad_binarize(uvad_ctx *c, const float *d_probs, int ld_p, int B, int T, con
     a.nwt = bin_words(T); a.cap = (T + 1) / 2;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, launch_binarize(a, d_labels, ld, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+// ---- the live hysteresis endpointer (endpoint_hyst.hip) --------------------------------------------------------------------------------------
+static int endpoint_hyst_lag(const uvad_binarize_cfg *q) {
+    return q->min_on + q->pad_on + q->pad_off + (q->min_off > 1 ? q->min_off - 1 : 0);   // at most 4 x 2^20
+}
+
+int uvad_endpoint_hyst_lag(const uvad_binarize_cfg *q) { return binarize_cfg_error(q) ? -1 : endpoint_hyst_lag(q); }
+
+size_t uvad_endpoint_hyst_state_bytes(const uvad_ctx *c, int B, const uvad_binarize_cfg *q) {
+    if (!c || B < 1 || binarize_cfg_error(q)) return 0;
+    return endpoint_hyst_state_bytes(B);
+}
+
+int uvad_endpoint_hyst_reset(uvad_ctx *c, void *d_state, size_t state_bytes, int B, const uvad_binarize_cfg *q, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (const char *w = binarize_cfg_error(q)) return fail(c, UVAD_E_ARG, std::string("uvad_endpoint_hyst_reset: ") + w);
+    if (!d_state || B < 1) return fail(c, UVAD_E_ARG, "uvad_endpoint_hyst_reset: bad argument");
+    if (state_bytes < endpoint_hyst_state_bytes(B))
+        return fail(c, UVAD_E_ARG, "uvad_endpoint_hyst_reset: state too small: need " + std::to_string(endpoint_hyst_state_bytes(B)) + " bytes");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_endpoint_hyst_reset(d_state, B, BinCfgInt{q->onset, q->offset, q->min_on, q->min_off, q->pad_on, q->pad_off},
+                                         (hipStream_t)stream));
+    EndpointHystPool g;
+    g.B = B; g.lag = endpoint_hyst_lag(q);
+    c->endpoint_hysts[d_state] = g;
+    return UVAD_OK;
+}
+
+int uvad_endpoint_hyst_step(uvad_ctx *c, const float *d_probs, int ld_in, const int32_t *d_counts, const uint8_t *d_flags, int B,
+                            void *d_state, size_t state_bytes, int32_t *d_events, int max_events, int32_t *d_ev_counts, uint8_t *d_active,
+                            uint8_t *d_labels, int ld_lab, int32_t *d_lab_counts, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_probs || !d_counts || !d_ev_counts || !d_state || B < 1 || ld_in < 1) return fail(c, UVAD_E_ARG, "uvad_endpoint_hyst_step: bad argument");
+    if (ld_in > EP_MAX_LD_IN) return fail(c, UVAD_E_ARG, "uvad_endpoint_hyst_step: ld_in above " + std::to_string(EP_MAX_LD_IN) + " frames per step");
+    if (max_events < 0 || (max_events > 0 && !d_events)) return fail(c, UVAD_E_ARG, "uvad_endpoint_hyst_step: d_events is NULL with max_events > 0");
+    if (d_labels && !d_lab_counts) return fail(c, UVAD_E_ARG, "uvad_endpoint_hyst_step: d_labels needs d_lab_counts");
+    auto it = c->endpoint_hysts.find(d_state);
+    if (it == c->endpoint_hysts.end()) return fail(c, UVAD_E_STATE, "uvad_endpoint_hyst_step: call uvad_endpoint_hyst_reset on this state first");
+    const EndpointHystPool &g = it->second;
+    if (B != g.B) return fail(c, UVAD_E_STATE, "uvad_endpoint_hyst_step: the state was reset with B = " + std::to_string(g.B));
+    if (state_bytes < endpoint_hyst_state_bytes(B))
+        return fail(c, UVAD_E_ARG, "uvad_endpoint_hyst_step: state too small: need " + std::to_string(endpoint_hyst_state_bytes(B)) + " bytes");
+    if (d_labels && (int64_t)ld_lab < (int64_t)ld_in + g.lag)
+        return fail(c, UVAD_E_ARG, "uvad_endpoint_hyst_step: ld_lab must be at least ld_in + lag = " + std::to_string((int64_t)ld_in + g.lag));
+    EndpointArgs a{};
+    a.probs = d_probs; a.ld_in = ld_in; a.counts = d_counts; a.flags = d_flags; a.B = B; a.state = d_state;
+    a.events = d_events; a.max_events = max_events; a.ev_counts = d_ev_counts; a.active = d_active;
+    a.labels = d_labels; a.ld_lab = ld_lab; a.lab_counts = d_lab_counts;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_endpoint_hyst_step(a, (hipStream_t)stream));
     return UVAD_OK;
 }
 

@@ -597,4 +597,23 @@ constexpr size_t bin_words_bytes(int B, int T) { return (size_t)B * bin_words(T)
 constexpr size_t bin_ws_bytes(int B, int T) { return bin_words_bytes(B, T) + (size_t)B * ((T + 1) / 2) * 2 * sizeof(int); }
 hipError_t launch_binarize(const BinarizeArgs &a, uint8_t *labels, int ld, hipStream_t s);   // labels may be NULL
 
+// ---- endpoint_hyst.hip: the live hysteresis endpointer (uvad_endpoint_hyst_*, include/uvad.h): uvad_binarize's decisions as per-feed events ----
+// The state is a header (what reset fixed: B and the uvad_binarize_cfg, so a step carries none) followed by one EndpointHystSlot per slot.
+// The hysteresis state is causal, so a slot keeps no frames at all: seven integers.  It takes EndpointArgs, as the median endpointer's step.
+constexpr unsigned EPH_MAGIC = 0x55564548u;           // "UVEH"
+struct EndpointHystHeader { unsigned magic; int B; BinCfgInt q; int reserved[56]; };   // 256 bytes
+struct EndpointHystSlot {
+    int m;        // frames of the session so far (saturates at 2^31 - 1: frames past that are not consumed)
+    int F;        // the label frontier: the session's labels are final on [0, F), F <= m
+    int lo;       // SPEECH / PENDING: the interval's first frame, the first run's start less pad_on, clipped at 0
+    int c;        // PENDING: the first non-speech frame after the last run
+    int mode;     // EP_IDLE / EP_SPEECH (inside a run) / EP_PENDING (a run closed at frame c, the interval's end not yet decided)
+    int conf;     // SPEECH / PENDING: 1 once START(lo) has been issued (the interval has min_on frames)
+    int s;        // the hysteresis state of frame m - 1 (0 before the first frame)
+    int reserved;
+};                // 32 bytes
+size_t endpoint_hyst_state_bytes(int B);
+hipError_t launch_endpoint_hyst_reset(void *state, int B, const BinCfgInt &q, hipStream_t s);
+hipError_t launch_endpoint_hyst_step(const EndpointArgs &a, hipStream_t s);
+
 }  // namespace uvad

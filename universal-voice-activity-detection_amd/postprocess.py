@@ -176,7 +176,8 @@ def merged_runs(labels, pad: int) -> List[Tuple[int, int]]:
 
 def events_to_intervals(events, frame_shift: float):
     """One session's endpointer events in order, [(kind, frame)] with kind 1 = START and 2 = END -> [(start_s, end_s)] with the reference's
-    round(k * shift, 2); an interval still open (a START without its END yet) comes last as (start_s, None)."""
+    round(k * shift, 2); an interval still open (a START without its END yet) comes last as (start_s, None).  The hysteresis endpointer
+    (uvad_endpoint_hyst_step) issues events of the same form: this serves them as they are."""
     ev = np.asarray(events.cpu() if torch.is_tensor(events) else events).reshape(-1, 2).tolist()
     out, lo = [], None
     for kind, frame in ev:

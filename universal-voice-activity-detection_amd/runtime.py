@@ -714,7 +714,8 @@ class VadRuntime:
                    st["probs"].data_ptr() if ep is not None else None, out.shape[1], counts.data_ptr(), st["ws"].data_ptr(), st["ws"].numel(),
                    self._stream())
             if r == 0 and ep is not None:            # the endpointer right behind the pool step: its probabilities, counts and flags as they are
-                r = self._endpoint_enqueue(ep, st["probs"].data_ptr(), counts.data_ptr(), fp)
+                step = self._endpoint_hyst_enqueue if "lag" in ep else self._endpoint_enqueue
+                r = step(ep, st["probs"].data_ptr(), counts.data_ptr(), fp)
             return r
 
         if st["graphs"] is None:
@@ -737,17 +738,28 @@ class VadRuntime:
         st["graph"].replay()
         return out, counts
 
+    _ENDPOINT_KEYS = {"kernel", "pad", "threshold"}
+    _ENDPOINT_HYST_KEYS = {"onset", "offset", "min_on", "min_off", "pad_on", "pad_off"}
+
     def _slots_endpoint(self, st, endpoint):
-        """endpoint: None, or {"kernel", "pad", "threshold"} (any subset): the pool gets a probabilities buffer and an endpointer over its
-        B slots (endpoint_open) whose step is enqueued right behind every pool step -- inside the one capture under graphs=True -- with the
-        pool's counts and flags.  st["endpoint"] holds its events / ev_counts / active, overwritten by the next step."""
+        """endpoint: None, {"kernel", "pad", "threshold"} (any subset) for the median endpointer (endpoint_open), or {"onset", "offset",
+        "min_on", "min_off", "pad_on", "pad_off"} (any non-empty subset; binarize_config's dict as it is) for the hysteresis endpointer
+        (endpoint_hyst_open).  The pool gets a probabilities buffer and an endpointer over its B slots whose step is enqueued right behind
+        every pool step -- inside the one capture under graphs=True -- with the pool's counts and flags.  st["endpoint"] holds its events /
+        ev_counts / active, overwritten by the next step."""
         if endpoint is None:
             return st
-        extra = set(endpoint) - {"kernel", "pad", "threshold"}
+        keys = set(endpoint)
+        hyst = keys & self._ENDPOINT_HYST_KEYS
+        if hyst and keys & self._ENDPOINT_KEYS:
+            raise ValueError(f"endpoint parameters mix the median endpointer's {sorted(keys & self._ENDPOINT_KEYS)} with the hysteresis "
+                             f"endpointer's {sorted(hyst)}: give one set")
+        extra = keys - (self._ENDPOINT_HYST_KEYS if hyst else self._ENDPOINT_KEYS)
         if extra:
-            raise ValueError(f"unknown endpoint parameters {sorted(extra)} (kernel, pad, threshold)")
+            raise ValueError(f"unknown endpoint parameters {sorted(extra)} " +
+                             ("(onset, offset, min_on, min_off, pad_on, pad_off)" if hyst else "(kernel, pad, threshold)"))
         st["probs"] = torch.zeros_like(st["out"])
-        st["endpoint"] = self.endpoint_open(st["B"], st["out"].shape[1], **endpoint)
+        st["endpoint"] = (self.endpoint_hyst_open if hyst else self.endpoint_open)(st["B"], st["out"].shape[1], **endpoint)
         return st
 
     def window_slots_open(self, B: int, chunk: int, window: int = 500, lookahead: int = 0, graphs: bool = False, endpoint=None):
@@ -862,16 +874,21 @@ class VadRuntime:
                     "labels": torch.zeros((B, ld_in + h), dtype=torch.uint8, device=self.device),
                     "lab_counts": torch.zeros(B, dtype=torch.int32, device=self.device)}
 
-    def _endpoint_enqueue(self, ep, probs_ptr, counts_ptr, flags_ptr):
-        return self.lib.uvad_endpoint_step(self.ctx, probs_ptr, ep["ld_in"], counts_ptr, flags_ptr, ep["B"], ep["state"].data_ptr(),
-                                           ep["state"].numel(), ep["events"].data_ptr() if ep["max_events"] else None, ep["max_events"],
-                                           ep["ev_counts"].data_ptr(), ep["active"].data_ptr(), ep["labels"].data_ptr(),
-                                           ep["labels"].shape[1], ep["lab_counts"].data_ptr(), self._stream())
+    def _endpoint_enqueue(self, ep, probs_ptr, counts_ptr, flags_ptr, fn=None):
+        """fn: the step to enqueue, uvad_endpoint_step or (same argument list) uvad_endpoint_hyst_step."""
+        return (fn or self.lib.uvad_endpoint_step)(self.ctx, probs_ptr, ep["ld_in"], counts_ptr, flags_ptr, ep["B"], ep["state"].data_ptr(),
+                                                   ep["state"].numel(), ep["events"].data_ptr() if ep["max_events"] else None,
+                                                   ep["max_events"], ep["ev_counts"].data_ptr(), ep["active"].data_ptr(),
+                                                   ep["labels"].data_ptr(), ep["labels"].shape[1], ep["lab_counts"].data_ptr(), self._stream())
 
     def endpoint_step(self, ep, probs: "torch.Tensor", counts: "torch.Tensor", start=None, end=None):
         """probs (B, ld_in) f32 and counts (B,) int32 on the GPU: slot b consumes probs[b, :counts[b]]; start / end as window_slots_step.
         -> (events (B, max_events, 2) int32 {kind 1 START / 2 END, frame}, ev_counts (B,) int32, active (B,) uint8), on the device and
         overwritten by the next step; ep["labels"] / ep["lab_counts"] hold the labels the step finalised."""
+        return self._endpoint_run(ep, self._endpoint_enqueue, probs, counts, start, end)
+
+    def _endpoint_run(self, ep, enqueue, probs, counts, start, end):
+        """One eager step of either endpointer: the checks on probs and counts, the flag byte, then `enqueue`."""
         with torch.cuda.device(self.device):
             probs = self._dev_f32(probs, "probs")
             if tuple(probs.shape) != (ep["B"], ep["ld_in"]):
@@ -879,8 +896,46 @@ class VadRuntime:
             if not torch.is_tensor(counts) or counts.device != self.device or counts.dtype != torch.int32 or tuple(counts.shape) != (ep["B"],):
                 raise ValueError(f"counts must be an int32 tensor of shape ({ep['B']},) on {self.device}")
             flags = self._slot_flags(ep["B"], start, end)
-            self._check(self._endpoint_enqueue(ep, probs.data_ptr(), counts.contiguous().data_ptr(), flags.data_ptr() if flags is not None else None))
+            self._check(enqueue(ep, probs.data_ptr(), counts.contiguous().data_ptr(), flags.data_ptr() if flags is not None else None))
             return ep["events"], ep["ev_counts"], ep["active"]
+
+    # ------------------------------------------------------------------ live hysteresis endpointing (uvad_endpoint_hyst_*)
+    def endpoint_hyst_open(self, B: int, ld_in: int, onset: float = 0.5, offset=None, min_on: int = 0, min_off: int = 0, pad_on: int = 0,
+                           pad_off: int = 0, max_events=None):
+        """Allocate and reset a hysteresis endpointer of B slots (uvad_endpoint_hyst_reset): per slot the decisions of `binarize` -- on at
+        !(p < onset), off at p < offset (default: onset), intervals shorter than min_on frames dropped, pauses shorter than min_off
+        filled, pad_on / pad_off frames added -- reported as START / END events the moment they are certain.  The dict has endpoint_open's
+        shape, plus "lag": its labels buffer is ld_in + lag columns wide.  max_events: events kept per slot and step (default ld_in + 1,
+        which never overflows)."""
+        cfg = _lib.BinarizeCfg(float(onset), float(onset if offset is None else offset), int(min_on), int(min_off), int(pad_on), int(pad_off))
+        if B < 1 or ld_in < 1:
+            raise ValueError(f"need B >= 1 and ld_in >= 1, got {B}, {ld_in}")
+        max_events = ld_in + 1 if max_events is None else int(max_events)
+        if max_events < 0:
+            raise ValueError("max_events must be >= 0")
+        with torch.cuda.device(self.device):
+            nbytes = int(self.lib.uvad_endpoint_hyst_state_bytes(self.ctx, B, C.byref(cfg)))
+            lag = int(self.lib.uvad_endpoint_hyst_lag(C.byref(cfg)))
+            if nbytes == 0 or lag < 0:
+                raise ValueError(f"bad hysteresis configuration: onset {cfg.onset} and offset {cfg.offset} (finite, offset <= onset), min_on "
+                                 f"{min_on}, min_off {min_off}, pad_on {pad_on}, pad_off {pad_off} (0 .. 2^20)")
+            state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._check(self.lib.uvad_endpoint_hyst_reset(self.ctx, state.data_ptr(), nbytes, B, C.byref(cfg), self._stream()))
+            return {"state": state, "B": B, "ld_in": ld_in, "onset": cfg.onset, "offset": cfg.offset, "min_on": int(min_on),
+                    "min_off": int(min_off), "pad_on": int(pad_on), "pad_off": int(pad_off), "lag": lag, "max_events": max_events,
+                    "events": torch.zeros((B, max_events, 2), dtype=torch.int32, device=self.device),
+                    "ev_counts": torch.zeros(B, dtype=torch.int32, device=self.device),
+                    "active": torch.zeros(B, dtype=torch.uint8, device=self.device),
+                    "labels": torch.zeros((B, ld_in + lag), dtype=torch.uint8, device=self.device),
+                    "lab_counts": torch.zeros(B, dtype=torch.int32, device=self.device)}
+
+    def _endpoint_hyst_enqueue(self, ep, probs_ptr, counts_ptr, flags_ptr):
+        return self._endpoint_enqueue(ep, probs_ptr, counts_ptr, flags_ptr, self.lib.uvad_endpoint_hyst_step)
+
+    def endpoint_hyst_step(self, ep, probs: "torch.Tensor", counts: "torch.Tensor", start=None, end=None):
+        """endpoint_step for a hysteresis endpointer: the same arguments and returns; active is 0 idle, 1 inside a confirmed interval,
+        2 inside a candidate that has not reached min_on frames yet."""
+        return self._endpoint_run(ep, self._endpoint_hyst_enqueue, probs, counts, start, end)
 
     # ------------------------------------------------------------------ scoring against reference labels (uvad_score_*)
     def score_open(self, points=((0.5, 25),), collar: int = 0, bins: int = 256, segment: int = 0):
