@@ -153,6 +153,11 @@ int uvad_get_taps(uvad_ctx *, int B, int T, float *d_lstm_out, float *d_lin_out,
  * device memory of uvad_stream_state_bytes(ctx, B) bytes holding the PCM tail and (h, c) of every layer;
  * uvad_stream_reset (re)starts all B streams.  The right-edge reflection of the offline path needs the end
  * of the signal and is therefore never produced (streams are open-ended).
+ * Nothing but row b's columns 0..k-1 is written; ld_logits < k is UVAD_E_ARG and leaves the streams where they were (the
+ * step can be repeated with room for its frames).  Feeds never mix: a NaN / Inf sample makes the logits of ITS feed
+ * non-finite from the first frame that holds it on (the energy floor keeps NaN, as the reference's clamp; the carried
+ * (h, c) stays NaN until uvad_stream_reset) -- and of the frame before it where the two share a transform (frames are
+ * transformed in pairs, positions 2i and 2i + 1 of a step) -- and changes no bit of any other feed.
  * uvad_stream_step is asynchronous but NOT replay-safe by itself under hipGraph capture: the number of complete frames, the
  * PCM-tail ping-pong parity and the first-chunk reflection are host-side counters baked into the launch arguments at
  * enqueue time.  Replay is offered explicitly: uvad_stream_peek says what the NEXT step will bake in -- two steps with the

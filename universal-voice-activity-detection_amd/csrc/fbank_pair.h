@@ -46,9 +46,10 @@ __device__ __forceinline__ float wave_sum(float v) {
 // value BIT FOR BIT (tests/test_gpu_parity.py compares the two paths) in 8 instead of 15 vector instructions.  A floor below
 // FLT_MIN takes ocml's logf.
 __device__ __forceinline__ float log_floored(float e, float floor, bool floor_is_normal) {
-    if (!floor_is_normal) return logf(fmaxf(e, floor));
-    float x;
-    asm("v_max_f32 %0, %1, %2" : "=v"(x) : "v"(e), "v"(floor));   // (fmaxf: a NaN energy reads as the floor, as with ocml)
+    // the floor as the reference's clamp(min = floor) and the oracle's `if (v < floor) v = floor`: a NaN energy (a non-finite sample in
+    // the frame) stays NaN and poisons the feed it belongs to; fmaxf / v_max_f32 would read it as the floor and hide it
+    const float x = e < floor ? floor : e;
+    if (!floor_is_normal) return logf(x);
     const float y = __builtin_amdgcn_logf(x);                     // log2
     constexpr float C = 0x1.62e42ep-1f, C_LO = 0x1.efa39ep-25f;   // ln 2 = C + C_LO (0x3f317217, 0x3377d1cf)
     const float t = C * y;

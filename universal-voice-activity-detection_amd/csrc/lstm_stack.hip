@@ -5,7 +5,7 @@
 // Why.  A streaming step of 512 feeds x 20 ms is 2 frames per feed: as per-layer kernels it was 8 dependent launches (projection +
 // recurrence per layer) of a few microseconds of work each, and the step's latency was the launches (0.104 ms for 11 of them).
 // In a causal stack nothing couples two sequences: layer l + 1 of a sequence needs layer l of THAT sequence only.  So one
-// workgroup takes 4 sequences through ALL layers for the step's T <= 8 frames and no workgroup ever waits for another:
+// workgroup takes 4 sequences through ALL layers for the step's T <= LSTM_STACK_TMAX (= 4) frames and no workgroup ever waits for another:
 //   per layer   phase A: W_ih's register image -> the wave's 128 resident registers (the A operand of v_mfma_f32_4x4x1_16B_f32, as
 //                        in lstm_rec_kernel); gates_t = b + W_ih x_t for the T frames, x_t read from LDS (the features, then the
 //                        previous layer's h_t); a lane ends a chain holding the four gate pre-activations of ONE (unit, sequence)

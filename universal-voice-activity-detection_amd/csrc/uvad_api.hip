@@ -1665,6 +1665,7 @@ int uvad_stream_step(uvad_ctx *c, const float *d_pcm_chunk, int B, int chunk, vo
     const int k = plan.k;
     // A step that produces frames reads its rows straight from the chunk and the carried tail inside the feature kernel, which also
     // writes the next tail (FbankArgs::vs_*); only a step without frames (a short first chunk) runs the staging kernel for the tail.
+    if (k > ld_logits) return fail(c, UVAD_E_ARG, "ld_logits smaller than the number of new frames");   // (before anything moves: the call can be repeated)
     if (k <= 0)
         HIPCHK(c, launch_stream_stage(d_pcm_chunk, B, chunk, S.tail, n_left, plan.first,
                                       reinterpret_cast<const float *>(st + S.off_tail[par]),
@@ -1672,7 +1673,6 @@ int uvad_stream_step(uvad_ctx *c, const float *d_pcm_chunk, int B, int chunk, vo
     sc.n_samples = plan.n_after;
     sc.n_steps += 1;
     if (k <= 0) return 0;
-    if (k > ld_logits) return fail(c, UVAD_E_ARG, "ld_logits smaller than the number of new frames");
     sc.n_frames += k;
     void *cws = wsb + staging_bytes;
     const WsLayout w = carve(c, B, k);
