@@ -812,6 +812,87 @@ int uvad_endpoint_hyst_step(uvad_ctx *, const float *d_probs, int ld_in, const i
                             void *d_state, size_t state_bytes, int32_t *d_events, int max_events, int32_t *d_ev_counts, uint8_t *d_active,
                             uint8_t *d_labels, int ld_lab, int32_t *d_lab_counts, void *stream);
 
+/* ---- Live speech gate: each feed's speech audio per step, on the device ---------------------------------------------------------------------
+ * The streaming counterpart of uvad_cuts_table + uvad_cuts_gather(UVAD_CUTS_SAMPLES), with the endpointers' contract: however a session's
+ * samples and labels are cut into steps, the fragments a slot emits, concatenated per cut, are byte-identical to the offline pair run on
+ * the whole session's labels and PCM with the same uvad_cuts_cfg (n = the session's labels, S_b = its samples).  It stands behind an
+ * endpointer step and hands a recogniser the speech audio, and only that, with no copy of events to the host and no PCM history there.
+ *   Sessions: the state holds B slots; after uvad_gate_reset every slot is idle.  d_flags is the slot pools' byte, or NULL:
+ *     UVAD_SLOT_START  before this step's input the slot drops whatever session it held -- silently, no closing records -- and a new
+ *                      session begins with this step's chunk and labels;
+ *     UVAD_SLOT_END    after this step's input the session is flushed (below) and the slot is idle again.  Both bits: a one-step session.
+ *   Inputs per step: row b of d_chunk [B][chunk] holds the session's next `chunk` samples of unit_bytes each, copied as bytes (int16 or
+ *     f32: a slot pool's own input buffer); columns 0 .. clamp(d_lab_counts[b], 0, ld_lab) - 1 of row b of d_labels [B][ld_lab] hold the
+ *     session's next finalised labels -- an endpointer step's d_labels / d_lab_counts, consumed as they are; any non-zero byte counts as
+ *     1, as in uvad_cuts_table.  The chunk row, the label row and the count of an idle slot, and label columns past the count, are never
+ *     read (NaN or junk there changes no output byte).  ld_lab = 0 feeds samples alone.
+ *   Cuts: uvad_cuts_cfg in full, with min_len required to be 0 (dropping a short last piece would need a further hold).  Per slot the
+ *     state is A, the samples received; F, the labels received; mode, one of IDLE, OPEN (inside a run), PENDING (a run closed at c); and
+ *     the current piece: its first frame f, its index, the samples it has delivered.  The step first commits the chunk (A += chunk), then
+ *     takes each label v of frame t = F in order:
+ *     1 mode     IDLE and v: f = max(t - pad, 0), mode = OPEN.  OPEN and !v: c = t, mode = PENDING.  PENDING and v: the run rejoins;
+ *     2 close    F = t + 1.  In PENDING with !v and t >= c + 2 pad (labels c .. c + 2 pad are final and zero: the median endpointer's
+ *                rule) the interval ends at hi = c + pad: after step 3 with g = hi the piece [f, hi) closes if hi > f; mode = IDLE;
+ *     3 split    otherwise, outside IDLE, the frames known to lie inside the interval end at g = F (OPEN) or min(c + pad, F) (PENDING);
+ *                while max_len > 0 and g - f >= max_len the piece [f, f + max_len) closes and f += max_len: a piece closes in the frame
+ *                that completes it, and the next one opens with the first frame known to lie behind it;
+ *     4 END flag after the labels, n = F: with g as in 3 (OPEN: n, PENDING: min(c + pad, n)) the piece [f, g) closes if g > f.
+ *     A piece [f, f + k) that closes covers samples [max(f hop - lead, 0), min((f + k) hop + tail, A)), exactly uvad_cuts_table's range
+ *     when the step carries the END flag (A = S_b).  A piece that closes in a step without END while A < (f + k) hop + tail carries
+ *     UVAD_GATE_SHORT: it is shorter than its offline cut.  That cannot happen with a pool's own geometry -- log-mel: lead =
+ *     (frame_len - shift) / 2, tail = frame_len - shift - lead; waveform: lead 0, tail R - J -- because frame t spans samples
+ *     [t hop - lead, (t + 1) hop + tail), a label exists only for a complete frame, and a piece closes with g <= F, so label g - 1 exists
+ *     and A >= g hop + tail.
+ *   Emission: cuts in table order and each cut's samples in order, nothing deferred.  Every piece that closes in a step gives one record
+ *     with the rest of its samples, up to its end; after the labels (without END) the open piece [f, g) gives one record with its samples
+ *     up to min(g hop, A), if there are new ones.  So a step emits at most one record per piece, a piece whose sample range is empty still
+ *     emits one (FIRST | LAST, n = 0), and the records of a cut are back to back in offset.
+ *   History ring: the slot keeps the last `history` samples it received in a ring in the state (its write position runs on across
+ *     sessions).  The step commits the chunk, then reads.  Samples a fragment needs that have left the ring -- positions below A - history
+ *     -- are written as zero bytes and the record carries UVAD_GATE_LOST.  uvad_gate_history = chunk + (lag_frames + pad + 1) hop + lead is
+ *     a size at which this never happens provided that after every step F >= floor(A / hop) - lag_frames (DESIGN.md 3.20 derives it; behind
+ *     a pool lag_frames = lookahead + the endpointer's lag + ceil(tail / hop)).
+ *   Outputs per step, all DEVICE memory:
+ *     d_out [B][ld_out] units: the step's fragments back to back in record order; units behind them are not written;
+ *     d_seg [B][max_seg] uvad_gate_seg: index = the cut's position within the session (uvad_cut.index); flags = UVAD_GATE_FIRST (the
+ *       cut's first record) | LAST (its last; n_frames is final) | LOST | SHORT; first_frame, n_frames = the piece's first frame and its
+ *       frames so far; offset = the fragment's first sample within the cut; n = its true sample count (saturating at 2^31 - 1);
+ *       n_stored = what fitted into the rest of the row: truncation shows as n_stored < n, and the rest is skipped, not deferred;
+ *     d_seg_counts [B] int32: the TRUE number of records; records past max_seg are counted but neither stored nor copied (as
+ *       uvad_label_runs treats max_runs).  An idle slot's count is 0 and nothing else of it is written.
+ *   uvad_gate_max_seg: 2 I + 1 + (max_len ? (ld_lab + 2 pad I) / max_len : 0) with I = (ld_lab + 1) / 2 + 1, the intervals a step can
+ *     touch: a max_seg that never overflows (saturating at 2^31 - 1).  uvad_gate_max_out: chunk + (ld_lab + 2 pad I) hop + max_seg x
+ *     (lead + tail), an ld_out that never truncates; lost samples are written too, so it does not depend on `history`, which is only
+ *     checked.  Both, and uvad_gate_history, return -1 on a bad argument.
+ *   Positions are int64; frames are int32 and saturate: a session consumes no labels past 2^31 - 1.  The configuration lives in the state
+ *   (a header written by reset; 64 bytes per slot and its ring, rounded up to 16 bytes, behind a 256-byte header): a step carries none, is
+ *   one launch of one workgroup per slot, allocates nothing, never synchronises and reads every per-slot quantity from the device; its
+ *   grid depends on B alone, so a graph captured around any step -- alone or in a pool's capture behind the endpointer -- replays for
+ *   every later one.  Copies are 16 bytes per lane where the output row's alignment allows and one unit at the edges; no atomics.  A
+ *   context created without feature / model configuration serves these calls.
+ *   Refusals (UVAD_E_ARG, nothing enqueued, uvad_last_error names the word): uvad_cuts_table's checks on the cfg; min_len != 0;
+ *   unit_bytes not 2 or 4; history < 1, above 2^31 - 1 or (step) below chunk; B < 1; chunk < 1 or > 2^24; ld_lab < 0; ld_out < 0;
+ *   max_seg < 0; NULL d_chunk / d_state / d_seg_counts; NULL d_labels or d_lab_counts with ld_lab > 0; d_out NULL with ld_out > 0; d_seg
+ *   NULL with max_seg > 0; state_bytes below uvad_gate_state_bytes.  A state never reset, or reset with another B: UVAD_E_STATE. */
+#define UVAD_GATE_FIRST 1
+#define UVAD_GATE_LAST  2
+#define UVAD_GATE_LOST  4
+#define UVAD_GATE_SHORT 8
+typedef struct {
+    int32_t index, flags, first_frame, n_frames;
+    int64_t offset;
+    int32_t n, n_stored;
+} uvad_gate_seg;   /* 32 bytes */
+size_t uvad_gate_state_bytes(const uvad_ctx *, int B, const uvad_cuts_cfg *, int unit_bytes, int64_t history);   /* 0 on a bad configuration */
+int64_t uvad_gate_history(const uvad_cuts_cfg *, int lag_frames, int chunk);
+int64_t uvad_gate_max_out(const uvad_cuts_cfg *, int ld_lab, int chunk, int64_t history);
+int uvad_gate_max_seg(const uvad_cuts_cfg *, int ld_lab);
+int uvad_gate_reset(uvad_ctx *, void *d_state, size_t state_bytes, int B, const uvad_cuts_cfg *, int unit_bytes, int64_t history,
+                    void *stream);
+int uvad_gate_step(uvad_ctx *, const void *d_chunk, int chunk, const uint8_t *d_labels, int ld_lab, const int32_t *d_lab_counts,
+                   const uint8_t *d_flags, int B, void *d_state, size_t state_bytes, void *d_out, int64_t ld_out, uvad_gate_seg *d_seg,
+                   int max_seg, int32_t *d_seg_counts, void *stream);
+
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;
  *   1  (default) f32-accurate on the f16 matrix cores: weights scaled by a power of two and split on the host into THREE

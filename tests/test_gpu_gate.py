@@ -1,0 +1,337 @@
+"""GPU tests (-m gpu) of the live speech gate (uvad_gate_*, include/uvad.h) through VadRuntime.gate_open / gate_step: every step's out / seg /
+seg_counts bytes against the step rule restated in tests/gate_ref.py (and nothing written beside them: the buffers are filled with a
+canary before every step), ended sessions against uvad_cuts_table + uvad_cuts_gather run on the device on the whole session, the same
+sessions cut three ways, junk where nothing may be read, overflow of max_seg and ld_out, the history ring at its bound and below it,
+SHORT, the copy's width edges, one captured graph for every later step, and the refusals.  B = 5 slots, hop 4, sessions of at most 120
+frames; the inputs are tests/test_gate_ref.py's."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import gate_ref as gr
+import test_gate_ref as tg
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda:0")
+CANARY = 0x5A
+E_ARG, E_STATE = -1, -3
+CFG = (2, 7, 0, 4, 3, 3)
+KEYS = ("pad", "max_len", "min_len", "hop", "lead", "tail")
+TORCH = {np.dtype(np.int16): torch.int16, np.dtype(np.float32): torch.float32}
+
+
+@pytest.fixture(scope="module")
+def rt():
+    import uvad_amd
+    from uvad_amd.runtime import VadRuntime
+    r = VadRuntime(DEV)                      # no feature tables, weights or model: a post-processing context
+    yield r
+    r.close()
+
+
+_CASES = {}
+
+
+def case(cfg, sched, seed, dtype=np.int16, chunk=None, hist=None, ld_out=None, max_seg=None):
+    """The inputs and the reference's answer, computed once per case and shared."""
+    key = (cfg, sched, seed, np.dtype(dtype).str, chunk, hist, ld_out, max_seg)
+    if key not in _CASES:
+        data = tg.build(cfg, sched, seed, B=5, per_slot=4, dtype=dtype, chunk=chunk)
+        h = gr.history(cfg, tg.schedule_lag(sched, cfg[3]), data["q"]) if hist is None else hist
+        lo = gr.max_out(cfg, tg.LD_LAB, data["q"]) if ld_out is None else ld_out
+        ms = gr.max_seg(cfg, tg.LD_LAB) if max_seg is None else max_seg
+        ref, _ = gr.simulate(cfg, h, data["chunks"], data["labels"], data["lab_counts"], data["flags"], lo, ms)
+        _CASES[key] = (data, ref, h, lo, ms)
+    return _CASES[key]
+
+
+def device_run(rt, cfg, data, hist, ld_out, max_seg, graph_at=None, ld_lab=tg.LD_LAB):
+    """Every step through gate_step (from step graph_at on: one graph captured there, replayed) -> [(out, seg, seg_counts)] as numpy,
+    out and seg pre-filled with the canary before every step."""
+    steps, B, q = data["chunks"].shape
+    g = rt.gate_open(B, q, ld_lab, TORCH[data["chunks"].dtype], 0, history=hist, ld_out=ld_out, max_seg=max_seg, **dict(zip(KEYS, cfg)))
+    assert g["history"] == hist and g["out"].shape == (B, max(ld_out, 1)) and g["seg"].shape == (B, max(max_seg, 1), 8)
+    chunks, labels = torch.from_numpy(data["chunks"]).to(DEV), torch.from_numpy(data["labels"]).to(DEV)
+    counts, flags = torch.from_numpy(data["lab_counts"]).to(DEV), torch.from_numpy(data["flags"]).to(DEV)
+    st = {k: torch.empty_like(v[0]) for k, v in (("chunk", chunks), ("labels", labels), ("counts", counts), ("flags", flags))}
+    graph, got = None, []
+    for s in range(steps):
+        g["out"].view(torch.uint8).fill_(CANARY)
+        g["seg"].view(torch.uint8).fill_(CANARY)
+        g["seg_counts"].fill_(-7)
+        if graph_at is None or s < graph_at:
+            rt.gate_step(g, chunks[s], labels[s], counts[s], start=(flags[s] & 1).bool(), end=(flags[s] & 2).bool())
+        else:
+            for k, v in (("chunk", chunks), ("labels", labels), ("counts", counts), ("flags", flags)):
+                st[k].copy_(v[s])
+            if graph is None:
+                cur = torch.cuda.current_stream(DEV)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):                               # capture: recorded, not run
+                    r = rt._gate_enqueue(g, st["chunk"].data_ptr(), st["labels"].data_ptr(), st["counts"].data_ptr(), st["flags"].data_ptr())
+                assert r == 0
+                torch.cuda.current_stream(DEV).wait_stream(cur)
+            graph.replay()
+        got.append((g["out"].clone(), g["seg"].clone(), g["seg_counts"].clone()))
+    torch.cuda.synchronize()
+    return [(o.cpu().numpy(), sg.cpu().numpy().view(gr.SEG_DTYPE).reshape(B, -1), c.cpu().numpy()) for o, sg, c in got], g
+
+
+def compare(got, ref, ld_out, max_seg):
+    """Bytes of every step and slot; what lies behind the records and the fragments still holds the canary."""
+    n_rec = n_units = 0
+    for s, ((out, seg, counts), row) in enumerate(zip(got, ref)):
+        for b, (want_out, want_seg, want_count) in enumerate(row):
+            assert counts[b] == want_count, (s, b, counts[b], want_count)
+            k = len(want_seg)
+            assert k == min(want_count, max_seg)
+            assert seg[b, :k].tobytes() == want_seg.tobytes(), (s, b, seg[b, :k], want_seg)
+            assert (seg[b, k:].view(np.uint8) == CANARY).all(), (s, b)
+            used = int(want_seg["n_stored"].sum())
+            assert used <= ld_out and out[b, :used].tobytes() == want_out[:used].tobytes(), (s, b)
+            assert (out[b, used:].view(np.uint8) == CANARY).all(), (s, b)
+            n_rec += k
+            n_units += used
+    return n_rec, n_units
+
+
+def device_records(got, sess):
+    out = []
+    for s in range(sess["s0"], sess["s1"] + 1):
+        row, seg, counts = got[s]
+        off = 0
+        for r in seg[sess["b"], :counts[sess["b"]]]:
+            out.append((r, row[sess["b"], off:off + int(r["n_stored"])]))
+            off += int(r["n_stored"])
+    return out
+
+
+@pytest.mark.parametrize("dtype", [np.int16, np.float32])
+@pytest.mark.parametrize("sched", ["prompt", "late", "big", "bursts"])
+def test_every_step_equals_the_reference(rt, sched, dtype):
+    data, ref, h, lo, ms = case(CFG, sched, 11, dtype)
+    got, g = device_run(rt, CFG, data, h, lo, ms)
+    assert h == int(rt.lib.uvad_gate_history(C.byref(g["cfg"]), tg.schedule_lag(sched, 4), data["q"]))
+    n_rec, n_units = compare(got, ref, lo, ms)
+    flags = 0
+    for sess in data["sessions"]:
+        for r, _ in device_records(got, sess):
+            flags |= int(r["flags"])
+    print(f"{sched} {np.dtype(dtype).name}: {len(got)} steps, {n_rec} records, {n_units} samples, history {h}")
+    assert n_rec > 100 and flags == gr.FIRST | gr.LAST                      # neither LOST nor SHORT at uvad_gate_history's size
+
+
+def test_same_sessions_cut_three_ways_equal_the_device_cuts(rt):
+    """prompt, late and at_end at one chunk size cut the very same sessions; every ended session's fragments equal the batch
+    uvad_cuts_table + uvad_cuts_gather make on the device from the session's whole labels and PCM."""
+    runs = {}
+    for sched in ("prompt", "late", "at_end"):
+        data, ref, h, lo, ms = case(CFG, sched, 12, chunk=9)
+        got, _ = device_run(rt, CFG, data, h, lo, ms)
+        compare(got, ref, lo, ms)
+        runs[sched] = (data, got)
+    base = runs["prompt"][0]["sessions"]
+    ended = [i for i, s in enumerate(base) if s["ended"]]
+    T, S = max(max(len(base[i]["labels"]) for i in ended), 1), max(len(base[i]["pcm"]) for i in ended)
+    labels, pcm = np.zeros((len(ended), T), np.uint8), np.zeros((len(ended), S), np.int16)
+    for r, i in enumerate(ended):
+        labels[r, :len(base[i]["labels"])], pcm[r, :len(base[i]["pcm"])] = base[i]["labels"], base[i]["pcm"]
+    lens = [len(base[i]["labels"]) for i in ended]
+    nsamp = [len(base[i]["pcm"]) for i in ended]
+    ct = rt.cuts_open(**dict(zip(KEYS, CFG)))
+    _, batch, blen = rt.speech_cuts(torch.from_numpy(labels).to(DEV), torch.from_numpy(pcm).to(DEV), lengths=lens, nsamp=nsamp, cuts=ct)
+    table, batch, blen = rt.cuts_read(ct), batch.cpu().numpy(), blen.cpu().numpy()
+    n_cuts = 0
+    for sched, (data, got) in runs.items():
+        for r, i in enumerate(ended):
+            sess = data["sessions"][i]
+            assert sess["labels"].tobytes() == base[i]["labels"].tobytes() and sess["pcm"].tobytes() == base[i]["pcm"].tobytes()
+            cuts = gr.assemble(device_records(got, sess))
+            rows = np.flatnonzero(table["row"] == r)
+            assert len(cuts) == len(rows), (sched, i)
+            for (f, k, fl, samples, done), j in zip(cuts, rows):
+                assert done and fl == gr.FIRST | gr.LAST and (f, k) == (table["first_frame"][j], table["n_frames"][j]), (sched, i, j)
+                assert len(samples) == table["n_samples"][j] == blen[j] and samples.tobytes() == batch[j, :len(samples)].tobytes(), (sched, i, j)
+                n_cuts += 1
+    assert n_cuts > 60
+
+
+def test_junk_where_nothing_is_read_changes_nothing(rt):
+    data, ref, h, lo, ms = case(CFG, "late", 11, np.float32)
+    other = dict(data, chunks=data["chunks"].copy(), labels=data["labels"].copy(), lab_counts=data["lab_counts"].copy())
+    idle = ~data["live"]
+    assert idle.any() and np.isnan(data["chunks"][idle]).all()
+    other["chunks"][idle] = np.inf
+    other["lab_counts"][idle] = 100
+    other["labels"][idle] = 1
+    past = np.arange(tg.LD_LAB)[None, None, :] >= np.clip(data["lab_counts"], 0, tg.LD_LAB)[:, :, None]
+    assert (data["labels"][past] == 255).all()
+    other["labels"][past & data["live"][:, :, None]] = 0
+    a, _ = device_run(rt, CFG, data, h, lo, ms)
+    b, _ = device_run(rt, CFG, other, h, lo, ms)
+    for (o1, s1, c1), (o2, s2, c2) in zip(a, b):
+        assert o1.tobytes() == o2.tobytes() and s1.tobytes() == s2.tobytes() and c1.tobytes() == c2.tobytes()
+
+
+def test_max_seg_and_ld_out_overflow_count_truly(rt):
+    data, full, h, lo, ms = case(CFG, "big", 11)
+    most = max(int(seg["n"].max(initial=0)) for row in full for _, seg, _ in row)
+    assert max(count for row in full for _, _, count in row) > 1 and most > 8
+    # (ld_out, max_seg) -> are fragments truncated (None: it depends on which record is stored), are records dropped
+    for (ld_out, max_seg), (cuts, drops) in {(lo, 1): (False, True), (most - 1, ms): (True, False), (most - 1, 1): (None, True),
+                                              (0, ms): (True, False), (lo, 0): (False, True)}.items():
+        _, ref, _, _, _ = case(CFG, "big", 11, ld_out=ld_out, max_seg=max_seg)
+        got, _ = device_run(rt, CFG, data, h, ld_out, max_seg)
+        compare(got, ref, ld_out, max_seg)                                  # other slots and the rows' rest: the canary
+        cut = sum(int((seg["n_stored"] < seg["n"]).sum()) for row in ref for _, seg, _ in row)
+        dropped = sum(count - len(seg) for row in ref for _, seg, count in row)
+        assert cuts is None or (cut > 0) == cuts, (ld_out, max_seg, cut)
+        assert (dropped > 0) == drops, (ld_out, max_seg, dropped)
+        for s in range(len(got)):                                           # the counts are the full run's: TRUE numbers
+            assert got[s][2].tolist() == [count for _, _, count in full[s]]
+
+
+def test_history_at_its_bound_and_below_and_short(rt):
+    cfg = (5, 7, 0, 4, 3, 3)                                                # the worst schedule: labels after the full lag, pad 5
+    data, ref, h, lo, ms = case(cfg, "late", 13)
+    assert h == data["q"] + (tg.schedule_lag("late", 4) + 5 + 1) * 4 + 3
+    got, _ = device_run(rt, cfg, data, h, lo, ms)
+    compare(got, ref, lo, ms)
+    assert not any(int(r["flags"]) & gr.LOST for sess in data["sessions"] for r, _ in device_records(got, sess))
+    small = data["q"] + 4                                                   # chunk + hop: the start of every padded piece is gone
+    _, ref, _, _, _ = case(cfg, "late", 13, hist=small)
+    got, _ = device_run(rt, cfg, data, small, lo, ms)
+    compare(got, ref, lo, ms)
+    lost = [(r, x) for sess in data["sessions"] for r, x in device_records(got, sess) if int(r["flags"]) & gr.LOST]
+    assert len(lost) > 10 and all(x[0] == 0 for r, x in lost)
+    cfg = (2, 7, 0, 4, 3, 40)                                               # an oversize tail: pieces close before their samples are there
+    data, ref, h, lo, ms = case(cfg, "prompt", 14)
+    got, _ = device_run(rt, cfg, data, h, lo, ms)
+    compare(got, ref, lo, ms)
+    assert sum(bool(int(r["flags"]) & gr.SHORT) for sess in data["sessions"] for r, _ in device_records(got, sess)) > 10
+
+
+def _scripted(B, q, ld_lab, scripts, dtype):
+    """scripts[b]: [(chunk or None, labels, flag)] -> the arrays device_run and gr.simulate take; idle rows hold junk."""
+    steps = max(len(s) for s in scripts)
+    chunks = np.full((steps, B, q), 77, dtype)
+    labels, counts, flags = np.full((steps, B, ld_lab), 255, np.uint8), np.full((steps, B), 5, np.int32), np.zeros((steps, B), np.uint8)
+    for b, script in enumerate(scripts):
+        for s, (c, lab, fl) in enumerate(script):
+            if c is not None:
+                chunks[s, b], counts[s, b], flags[s, b] = c, len(lab), fl
+                labels[s, b, :len(lab)] = lab
+    return dict(chunks=chunks, labels=labels, lab_counts=counts, flags=flags, q=q)
+
+
+@pytest.mark.parametrize("dtype", [np.int16, np.float32])
+def test_copy_width_edges(rt, dtype):
+    """hop 1 without lead, tail or pad: a run [s, s + k) is a cut of samples [s, s + k), so the runs below are fragments of 1, 7, 8, 9, 63,
+    64 and 65 samples that start at odd samples, and one of 0 samples past the audio's end.  All labels come with the END step, so the
+    fragments leave back to back: every destination alignment.  Two steps of an earlier session move the ring's write position, so the
+    64-sample fragment crosses the ring's end (history 300: ring index 239 .. 302); slot 1 runs the same one step later, slot 2 a step
+    later again with one more leading chunk -- other ring positions -- and slot 3 stays idle.  ld_out = 301 units: rows at 602 or
+    1204 bytes, no multiple of 16."""
+    cfg, q, H, ld_lab, ld_out = (0, 0, 0, 1, 0, 0), 64, 300, 512, 301
+    runs = [(1, 1), (5, 7), (15, 8), (27, 9), (41, 63), (111, 64), (181, 65), (300, 5)]
+    lab = np.zeros(400, np.uint8)
+    for s, k in runs:
+        lab[s:s + k] = 1
+    rng = np.random.default_rng(3)
+    mk = lambda n: rng.integers(1, 30000, n).astype(dtype) if np.dtype(dtype).kind == "i" else rng.uniform(0.1, 1.0, n).astype(dtype)
+    scripts = []
+    for b in range(3):
+        pre, pcm = mk((2 + b // 2) * q), mk(4 * q)
+        script = [(None, None, 0)] * b
+        script += [(pre[i * q:(i + 1) * q], lab[:0], gr.START if i == 0 else 0) for i in range(len(pre) // q)]     # abandoned by the next START
+        script += [(pcm[i * q:(i + 1) * q], lab if i == 3 else lab[:0], (gr.START if i == 0 else 0) | (gr.END if i == 3 else 0)) for i in range(4)]
+        scripts.append(script)
+    data = _scripted(4, q, ld_lab, scripts, dtype)
+    ms = gr.max_seg(cfg, ld_lab)
+    ref, slots = gr.simulate(cfg, H, data["chunks"], data["labels"], data["lab_counts"], data["flags"], ld_out, ms)
+    assert "ring wrap" in slots[0].trace and "empty piece" in slots[0].trace
+    last = ref[5][0][1]                                                     # slot 0's END step
+    assert last["n"].tolist() == [1, 7, 8, 9, 63, 64, 65, 0] and last["first_frame"].tolist() == [s for s, _ in runs]
+    assert last["n_stored"].tolist() == last["n"].tolist()
+    got, _ = device_run(rt, cfg, data, H, ld_out, ms, ld_lab=ld_lab)
+    compare(got, ref, ld_out, ms)
+
+
+def test_one_graph_captured_at_step_3_replays_every_later_step(rt):
+    for dtype, sched in ((np.int16, "late"), (np.float32, "big")):
+        data, ref, h, lo, ms = case(CFG, sched, 11, dtype)
+        got, _ = device_run(rt, CFG, data, h, lo, ms, graph_at=3)
+        assert len(got) > 20
+        compare(got, ref, lo, ms)
+
+
+def test_refusals_leave_state_and_outputs_untouched(rt):
+    data, ref, h, lo, ms = case(CFG, "late", 11)
+    B, q = data["chunks"].shape[1:]
+    g = rt.gate_open(B, q, tg.LD_LAB, torch.int16, 0, history=h, **dict(zip(KEYS, CFG)))
+    chunks, labels = torch.from_numpy(data["chunks"]).to(DEV), torch.from_numpy(data["labels"]).to(DEV)
+    counts, flags = torch.from_numpy(data["lab_counts"]).to(DEV), torch.from_numpy(data["flags"]).to(DEV)
+    for s in range(6):
+        rt.gate_step(g, chunks[s], labels[s], counts[s], start=(flags[s] & 1).bool(), end=(flags[s] & 2).bool())
+    torch.cuda.synchronize()
+    before = [g[k].clone() for k in ("state", "out", "seg", "seg_counts")]
+    lib, err = rt.lib, lambda: rt.lib.uvad_last_error(rt.ctx).decode()
+    big = torch.zeros((B, h + 1), dtype=torch.int16, device=DEV)
+    fresh = torch.zeros(g["state"].numel(), dtype=torch.uint8, device=DEV)
+
+    def step(chunk_p=chunks[6].data_ptr(), chunk=q, lab=labels[6].data_ptr(), ld_lab=tg.LD_LAB, cnt=counts[6].data_ptr(), nB=B,
+             state=g["state"].data_ptr(), nbytes=g["state"].numel(), out=g["out"].data_ptr(), ld_out=g["ld_out"], seg=g["seg"].data_ptr(),
+             max_seg=g["max_seg"], sc=g["seg_counts"].data_ptr()):
+        return lib.uvad_gate_step(rt.ctx, chunk_p, chunk, lab, ld_lab, cnt, None, nB, state, nbytes, out, ld_out, seg, max_seg, sc, rt._stream())
+
+    assert step(chunk_p=big.data_ptr(), chunk=h + 1) == E_ARG and "below chunk" in err()       # history < chunk
+    assert step(nbytes=g["state"].numel() - 1) == E_ARG and "state_bytes" in err()
+    assert step(nB=B - 1) == E_STATE and f"B = {B}" in err()
+    assert step(state=fresh.data_ptr()) == E_STATE and "uvad_gate_reset" in err()
+    for kw in ({"chunk_p": None}, {"lab": None}, {"cnt": None}, {"sc": None}, {"out": None}, {"seg": None}, {"chunk": 0}, {"ld_lab": -1},
+               {"ld_out": -1}, {"max_seg": -1}, {"nB": 0}):
+        assert step(**kw) == E_ARG, kw
+    bad = rt.lib.uvad_gate_reset
+    from uvad_amd import _lib
+    for q_, unit, hist in (((2, 7, 1, 4, 3, 3), 2, h), (CFG, 3, h), (CFG, 2, 0), ((2, 7, 0, 0, 3, 3), 2, h)):
+        assert bad(rt.ctx, g["state"].data_ptr(), g["state"].numel(), B, C.byref(_lib.CutsCfg(*q_)), unit, hist, rt._stream()) == E_ARG
+    assert bad(rt.ctx, g["state"].data_ptr(), g["state"].numel() - 1, B, C.byref(g["cfg"]), 2, h, rt._stream()) == E_ARG
+    with pytest.raises(ValueError):
+        rt.gate_open(B, q, tg.LD_LAB, torch.int16, 0, min_len=1)
+    with pytest.raises(ValueError):
+        rt.gate_open(B, q, tg.LD_LAB, torch.float64, 0)
+    with pytest.raises(ValueError):
+        rt.gate_open(B, q, tg.LD_LAB, torch.int16, 0, history=q - 1)
+    torch.cuda.synchronize()
+    for k, t in zip(("state", "out", "seg", "seg_counts"), before):
+        assert torch.equal(g[k], t), k
+    # and the state still steps on: the refused calls were not steps
+    for s in range(6, 12):
+        rt.gate_step(g, chunks[s], labels[s], counts[s], start=(flags[s] & 1).bool(), end=(flags[s] & 2).bool())
+        out, seg, cnt = (t.cpu().numpy() for t in (g["out"], g["seg"], g["seg_counts"]))
+        for b, (want_out, want_seg, want_count) in enumerate(ref[s]):
+            assert cnt[b] == want_count and seg.view(gr.SEG_DTYPE).reshape(B, -1)[b, :len(want_seg)].tobytes() == want_seg.tobytes()
+
+
+def test_gate_collect_lists_the_step_records(rt):
+    data, ref, h, lo, ms = case(CFG, "big", 11)
+    B, q = data["chunks"].shape[1:]
+    g = rt.gate_open(B, q, tg.LD_LAB, torch.int16, tg.schedule_lag("big", 4), **dict(zip(KEYS, CFG)))
+    assert g["history"] == h and g["ld_out"] == lo and g["max_seg"] == ms   # the defaults are the library's bounds
+    chunks, labels = torch.from_numpy(data["chunks"]).to(DEV), torch.from_numpy(data["labels"]).to(DEV)
+    counts, flags = torch.from_numpy(data["lab_counts"]).to(DEV), torch.from_numpy(data["flags"]).to(DEV)
+    n = 0
+    for s in range(12):
+        rt.gate_step(g, chunks[s], labels[s], counts[s], start=(flags[s] & 1).bool(), end=(flags[s] & 2).bool())
+        recs = rt.gate_collect(g)
+        want = [(b, r, want_out, off) for b, (want_out, seg, _) in enumerate(ref[s])
+                for r, off in zip(seg, np.concatenate(([0], np.cumsum(seg["n_stored"])))[:len(seg)])]
+        assert len(recs) == len(want)
+        for (b, index, fl, f, k, frag), (wb, r, want_out, off) in zip(recs, want):
+            assert (b, index, fl, f, k) == (wb, r["index"], r["flags"], r["first_frame"], r["n_frames"])
+            assert frag.cpu().numpy().tobytes() == want_out[off:off + int(r["n_stored"])].tobytes()
+            n += 1
+    assert n > 5

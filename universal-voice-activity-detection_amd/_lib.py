@@ -65,6 +65,14 @@ class BinarizeCfg(C.Structure):  # uvad_binarize_cfg: thresholds and frame count
                 ("pad_off", C.c_int)]
 
 
+GATE_FIRST, GATE_LAST, GATE_LOST, GATE_SHORT = 1, 2, 4, 8     # uvad_gate_seg.flags
+
+
+class GateSeg(C.Structure):      # uvad_gate_seg: one record of a gate step (32 bytes)
+    _fields_ = [("index", C.c_int32), ("flags", C.c_int32), ("first_frame", C.c_int32), ("n_frames", C.c_int32), ("offset", C.c_int64),
+                ("n", C.c_int32), ("n_stored", C.c_int32)]
+
+
 class UvadError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"{ERR_NAMES.get(code, code)}: {msg}")
@@ -184,6 +192,13 @@ SIGNATURES = {
     "uvad_endpoint_hyst_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(BinarizeCfg), C.c_void_p]),
     "uvad_endpoint_hyst_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                           C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "uvad_gate_state_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.POINTER(CutsCfg), C.c_int, C.c_int64]),
+    "uvad_gate_history": (C.c_int64, [C.POINTER(CutsCfg), C.c_int, C.c_int]),
+    "uvad_gate_max_out": (C.c_int64, [C.POINTER(CutsCfg), C.c_int, C.c_int, C.c_int64]),
+    "uvad_gate_max_seg": (C.c_int, [C.POINTER(CutsCfg), C.c_int]),
+    "uvad_gate_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(CutsCfg), C.c_int, C.c_int64, C.c_void_p]),
+    "uvad_gate_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "uvad_classify_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_forward_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -228,7 +243,7 @@ _lib = None
 
 def bind(lib):
     """Declare every prototype of SIGNATURES on `lib`.  The ABI number did not move when entries were appended (the ingest stage among
-    them, the endpointer, the scoring stage, the speech cuts, the hysteresis decisions and the hysteresis endpointer after it), so a library built from an older tree passes the version check: a symbol it lacks is a loud error here, by name."""
+    them, the endpointer, the scoring stage, the speech cuts, the hysteresis decisions, the hysteresis endpointer and the speech gate after it), so a library built from an older tree passes the version check: a symbol it lacks is a loud error here, by name."""
     for name, (res, args) in SIGNATURES.items():
         try:
             fn = getattr(lib, name)

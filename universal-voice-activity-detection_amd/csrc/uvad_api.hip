@@ -101,6 +101,8 @@ struct SlotPool { int B = 0, chunk = 0, W = 0, L = 0, is_i16 = 0; };
 struct EndpointPool { int B = 0, kernel = 0, pad = 0; float threshold = 0.5f; };
 // a hysteresis endpointer state (uvad_endpoint_hyst_*): B and the lag of the configuration at its reset
 struct EndpointHystPool { int B = 0, lag = 0; };
+// a speech gate state (uvad_gate_*): what reset fixed (the device header holds the same)
+struct GatePool { int B = 0, unit_bytes = 0, history = 0; };
 // a scoring state (uvad_score_*): the configuration's n_points and bins at its reset (the device header holds the same)
 struct ScoreState { int n_points = 0, bins = 0; };
 
@@ -111,6 +113,7 @@ struct uvad_ctx {
     std::map<void *, SlotPool> slot_pools, wav_slot_pools;   // ... and of the slot pools of both window families (uvad_window_*slots_*)
     std::map<void *, EndpointPool> endpoints;   // ... and of the endpointer states (uvad_endpoint_*)
     std::map<void *, EndpointHystPool> endpoint_hysts;   // ... and of the hysteresis endpointer states (uvad_endpoint_hyst_*)
+    std::map<void *, GatePool> gates;           // ... and of the speech gate states (uvad_gate_*)
     std::map<void *, ScoreState> scores;        // ... and of the scoring states (uvad_score_*)
     bool has_score = false;                     // uvad_score_configure: operating points, collar, bins, segment (0 replaced by the default)
     uvad_score_cfg sq{};
@@ -3223,6 +3226,98 @@ int uvad_endpoint_hyst_step(uvad_ctx *c, const float *d_probs, int ld_in, const 
     a.labels = d_labels; a.ld_lab = ld_lab; a.lab_counts = d_lab_counts;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, launch_endpoint_hyst_step(a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+// ---- the live speech gate (gate.hip) ---------------------------------------------------------------------------------------------------------
+// nullptr: a configuration the gate takes; else the word uvad_last_error names
+static const char *gate_cfg_error(const uvad_cuts_cfg *q) {
+    if (const char *w = cuts_cfg_error(q)) return w;
+    if (q->min_len != 0) return "min_len must be 0: the gate drops no short last piece";
+    return nullptr;
+}
+static const char *gate_size_error(int B, int unit_bytes, int64_t history) {
+    if (B < 1) return "B must be >= 1";
+    if (unit_bytes != 2 && unit_bytes != 4) return "unit_bytes must be 2 (int16) or 4 (f32)";
+    if (history < 1 || history > 0x7fffffffll) return "history must lie in [1, 2^31 - 1] samples";
+    return nullptr;
+}
+// the intervals a step of ld_lab labels can touch: the one it found open and one per run that starts in it
+static int64_t gate_intervals(int ld_lab) { return ((int64_t)ld_lab + 1) / 2 + 1; }
+static int64_t gate_max_seg(const uvad_cuts_cfg *q, int ld_lab) {
+    const int64_t I = gate_intervals(ld_lab);
+    return 2 * I + 1 + (q->max_len ? ((int64_t)ld_lab + 2 * (int64_t)q->pad * I) / q->max_len : 0);   // below 2^54
+}
+
+int64_t uvad_gate_history(const uvad_cuts_cfg *q, int lag_frames, int chunk) {
+    if (gate_cfg_error(q) || lag_frames < 0 || chunk < 1 || chunk > GATE_MAX_CHUNK) return -1;
+    return (int64_t)chunk + ((int64_t)lag_frames + q->pad + 1) * q->hop + q->lead;   // below 2^63: (2^31 + 2^20 + 1) 2^31 + 2^31 + 2^24
+}
+
+int uvad_gate_max_seg(const uvad_cuts_cfg *q, int ld_lab) {
+    if (gate_cfg_error(q) || ld_lab < 0) return -1;
+    return (int)std::min<int64_t>(gate_max_seg(q, ld_lab), 0x7fffffffll);
+}
+
+int64_t uvad_gate_max_out(const uvad_cuts_cfg *q, int ld_lab, int chunk, int64_t history) {
+    if (gate_cfg_error(q) || ld_lab < 0 || chunk < 1 || chunk > GATE_MAX_CHUNK || history < chunk || history > 0x7fffffffll) return -1;
+    const double est = (double)chunk + ((double)ld_lab + 2.0 * q->pad * (double)gate_intervals(ld_lab)) * q->hop +
+                       (double)gate_max_seg(q, ld_lab) * ((double)q->lead + q->tail);
+    if (est > 9.0e18) return INT64_MAX;                                             // saturates
+    return (int64_t)chunk + ((int64_t)ld_lab + 2 * (int64_t)q->pad * gate_intervals(ld_lab)) * q->hop +
+           gate_max_seg(q, ld_lab) * ((int64_t)q->lead + q->tail);
+}
+
+size_t uvad_gate_state_bytes(const uvad_ctx *c, int B, const uvad_cuts_cfg *q, int unit_bytes, int64_t history) {
+    if (!c || gate_cfg_error(q) || gate_size_error(B, unit_bytes, history)) return 0;
+    return gate_state_bytes(B, unit_bytes, history);
+}
+
+int uvad_gate_reset(uvad_ctx *c, void *d_state, size_t state_bytes, int B, const uvad_cuts_cfg *q, int unit_bytes, int64_t history,
+                    void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (const char *w = gate_cfg_error(q)) return fail(c, UVAD_E_ARG, std::string("uvad_gate_reset: ") + w);
+    if (const char *w = gate_size_error(B, unit_bytes, history)) return fail(c, UVAD_E_ARG, std::string("uvad_gate_reset: ") + w);
+    if (!d_state) return fail(c, UVAD_E_ARG, "uvad_gate_reset: d_state is NULL");
+    const size_t need = gate_state_bytes(B, unit_bytes, history);
+    if (state_bytes < need) return fail(c, UVAD_E_ARG, "uvad_gate_reset: state_bytes too small: need " + std::to_string(need) + " bytes");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_gate_reset(d_state, B, cuts_cfg_of(q), unit_bytes, (int)history, (hipStream_t)stream));
+    GatePool g;
+    g.B = B; g.unit_bytes = unit_bytes; g.history = (int)history;
+    c->gates[d_state] = g;
+    return UVAD_OK;
+}
+
+int uvad_gate_step(uvad_ctx *c, const void *d_chunk, int chunk, const uint8_t *d_labels, int ld_lab, const int32_t *d_lab_counts,
+                   const uint8_t *d_flags, int B, void *d_state, size_t state_bytes, void *d_out, int64_t ld_out, uvad_gate_seg *d_seg,
+                   int max_seg, int32_t *d_seg_counts, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (B < 1) return fail(c, UVAD_E_ARG, "uvad_gate_step: B must be >= 1");
+    if (chunk < 1 || chunk > GATE_MAX_CHUNK) return fail(c, UVAD_E_ARG, "uvad_gate_step: chunk must lie in [1, 2^24] samples");
+    if (ld_lab < 0) return fail(c, UVAD_E_ARG, "uvad_gate_step: ld_lab must be >= 0");
+    if (ld_out < 0) return fail(c, UVAD_E_ARG, "uvad_gate_step: ld_out must be >= 0");
+    if (max_seg < 0) return fail(c, UVAD_E_ARG, "uvad_gate_step: max_seg must be >= 0");
+    if (!d_chunk) return fail(c, UVAD_E_ARG, "uvad_gate_step: d_chunk is NULL");
+    if (!d_state) return fail(c, UVAD_E_ARG, "uvad_gate_step: d_state is NULL");
+    if (!d_seg_counts) return fail(c, UVAD_E_ARG, "uvad_gate_step: d_seg_counts is NULL");
+    if (ld_lab > 0 && !d_labels) return fail(c, UVAD_E_ARG, "uvad_gate_step: d_labels is NULL with ld_lab > 0");
+    if (ld_lab > 0 && !d_lab_counts) return fail(c, UVAD_E_ARG, "uvad_gate_step: d_lab_counts is NULL with ld_lab > 0");
+    if (ld_out > 0 && !d_out) return fail(c, UVAD_E_ARG, "uvad_gate_step: d_out is NULL with ld_out > 0");
+    if (max_seg > 0 && !d_seg) return fail(c, UVAD_E_ARG, "uvad_gate_step: d_seg is NULL with max_seg > 0");
+    auto it = c->gates.find(d_state);
+    if (it == c->gates.end()) return fail(c, UVAD_E_STATE, "uvad_gate_step: call uvad_gate_reset on this state first");
+    const GatePool &g = it->second;
+    if (B != g.B) return fail(c, UVAD_E_STATE, "uvad_gate_step: the state was reset with B = " + std::to_string(g.B));
+    if (g.history < chunk) return fail(c, UVAD_E_ARG, "uvad_gate_step: history " + std::to_string(g.history) + " is below chunk");
+    const size_t need = gate_state_bytes(B, g.unit_bytes, g.history);
+    if (state_bytes < need) return fail(c, UVAD_E_ARG, "uvad_gate_step: state_bytes too small: need " + std::to_string(need) + " bytes");
+    GateArgs a{};
+    a.chunk = d_chunk; a.chunk_n = chunk; a.labels = d_labels; a.ld_lab = ld_lab; a.lab_counts = d_lab_counts; a.flags = d_flags; a.B = B;
+    a.state = d_state; a.out = d_out; a.ld_out = ld_out; a.seg = reinterpret_cast<GateSeg *>(d_seg); a.max_seg = max_seg;
+    a.seg_counts = d_seg_counts;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_gate_step(a, g.unit_bytes, (hipStream_t)stream));
     return UVAD_OK;
 }
 

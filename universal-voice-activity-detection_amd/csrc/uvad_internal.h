@@ -616,4 +616,37 @@ size_t endpoint_hyst_state_bytes(int B);
 hipError_t launch_endpoint_hyst_reset(void *state, int B, const BinCfgInt &q, hipStream_t s);
 hipError_t launch_endpoint_hyst_step(const EndpointArgs &a, hipStream_t s);
 
+// ---- gate.hip: the live speech gate (uvad_gate_*, include/uvad.h): each feed's speech audio per step, the streaming uvad_cuts_* ------------
+// The state is a header (what reset fixed: B, the uvad_cuts_cfg, the unit size and the ring's length, so a step carries none), one GateSlot
+// per slot, then one ring of `history` units per slot, each rounded up to 16 bytes so that every ring starts as aligned as the state does.
+constexpr unsigned GATE_MAGIC = 0x55564754u;          // "UVGT"
+constexpr int GATE_MAX_CHUNK = 1 << 24;
+constexpr int GATE_THREADS = 256;                     // one workgroup per slot
+constexpr int GATE_LAB_TILE = 1024;                   // labels staged in LDS per round of the walk
+struct GateHeader { unsigned magic; int B; CutsCfgInt q; int unit_bytes, history; long long ring_bytes; int reserved[52]; };   // 256 bytes
+struct GateSlot {
+    long long A;      // samples of the session so far
+    long long sent;   // samples of the current piece delivered so far (the next fragment's offset)
+    int F;            // labels of the session so far (saturates at 2^31 - 1: labels past that are not consumed)
+    int c;            // PENDING: the first non-speech frame after the last run
+    int pf;           // the current piece's first frame (OPEN / PENDING)
+    int idx;          // the current piece's index within the session
+    int mode;         // EP_IDLE / EP_SPEECH (inside a run) / EP_PENDING
+    int started;      // 1 once the current piece has a record (the next one carries no FIRST)
+    int live;         // 1 from a START step to the END step: an idle slot reads no input and emits nothing
+    int wp;           // the ring's write position, 0 .. history - 1; it runs on across sessions
+    int reserved[4];
+};                    // 64 bytes
+struct GateSeg { int index, flags, first_frame, n_frames; long long offset; int n, n_stored; };   // uvad_gate_seg, field for field
+struct GateArgs {
+    const void *chunk; int chunk_n; const uint8_t *labels; int ld_lab; const int *lab_counts; const uint8_t *flags; int B;
+    void *state; void *out; long long ld_out; GateSeg *seg; int max_seg; int *seg_counts;
+};
+constexpr size_t gate_ring_bytes(int unit_bytes, long long history) { return ((size_t)history * unit_bytes + 15) / 16 * 16; }
+constexpr size_t gate_state_bytes(int B, int unit_bytes, long long history) {
+    return sizeof(GateHeader) + (size_t)B * (sizeof(GateSlot) + gate_ring_bytes(unit_bytes, history));
+}
+hipError_t launch_gate_reset(void *state, int B, const CutsCfgInt &q, int unit_bytes, int history, hipStream_t s);
+hipError_t launch_gate_step(const GateArgs &a, int unit_bytes, hipStream_t s);   // unit_bytes: the reset's, it picks the copy's granule
+
 }  // namespace uvad

@@ -716,6 +716,8 @@ class VadRuntime:
             if r == 0 and ep is not None:            # the endpointer right behind the pool step: its probabilities, counts and flags as they are
                 step = self._endpoint_hyst_enqueue if "lag" in ep else self._endpoint_enqueue
                 r = step(ep, st["probs"].data_ptr(), counts.data_ptr(), fp)
+            if r == 0 and st.get("gate") is not None:   # ... and the gate behind it: the pool's chunk, the endpointer's labels, the same flags
+                r = self._gate_enqueue(st["gate"], src.data_ptr(), ep["labels"].data_ptr(), ep["lab_counts"].data_ptr(), fp)
             return r
 
         if st["graphs"] is None:
@@ -741,13 +743,15 @@ class VadRuntime:
     _ENDPOINT_KEYS = {"kernel", "pad", "threshold"}
     _ENDPOINT_HYST_KEYS = {"onset", "offset", "min_on", "min_off", "pad_on", "pad_off"}
 
-    def _slots_endpoint(self, st, endpoint):
+    def _slots_endpoint(self, st, endpoint, gate=None, geometry=None):
         """endpoint: None, {"kernel", "pad", "threshold"} (any subset) for the median endpointer (endpoint_open), or {"onset", "offset",
         "min_on", "min_off", "pad_on", "pad_off"} (any non-empty subset; binarize_config's dict as it is) for the hysteresis endpointer
         (endpoint_hyst_open).  The pool gets a probabilities buffer and an endpointer over its B slots whose step is enqueued right behind
         every pool step -- inside the one capture under graphs=True -- with the pool's counts and flags.  st["endpoint"] holds its events /
         ev_counts / active, overwritten by the next step."""
         if endpoint is None:
+            if gate is not None:
+                raise ValueError("gate needs an endpoint: the gate reads the labels an endpointer finalises")
             return st
         keys = set(endpoint)
         hyst = keys & self._ENDPOINT_HYST_KEYS
@@ -760,13 +764,35 @@ class VadRuntime:
                              ("(onset, offset, min_on, min_off, pad_on, pad_off)" if hyst else "(kernel, pad, threshold)"))
         st["probs"] = torch.zeros_like(st["out"])
         st["endpoint"] = (self.endpoint_hyst_open if hyst else self.endpoint_open)(st["B"], st["out"].shape[1], **endpoint)
+        if gate is not None:
+            st["gate"] = self._slots_gate(st, dict(gate), geometry)
         return st
 
-    def window_slots_open(self, B: int, chunk: int, window: int = 500, lookahead: int = 0, graphs: bool = False, endpoint=None):
+    def _slots_gate(self, st, gate, geometry):
+        """gate: {} or any of pad, max_len, hop, lead, tail, lag_frames, history, ld_out, max_seg (gate_open's).  geometry = (hop, lead,
+        tail) of the pool's frames: frame t spans samples [t hop - lead, (t + 1) hop + tail), and hop / lead / tail default to it, so a
+        cut holds every sample its frames saw and no record is SHORT.  lag_frames defaults to the pool's lookahead + the endpointer's lag
+        (kernel // 2, or uvad_endpoint_hyst_lag) + ceil(tail / hop), the frames a complete frame trails the newest sample by.  pad
+        defaults to 0: the hysteresis endpointer's labels are already padded (pad_on / pad_off), and the median endpointer's pad shapes
+        its events, not its labels -- give pad here to widen the cuts as its events are widened.  The gate's step is enqueued behind the
+        endpointer's -- inside the one capture under graphs=True -- on the pool's input chunk, the endpointer's labels and the pool's flags;
+        st["gate"] holds its out / seg / seg_counts, overwritten by the next step (gate_collect reads them)."""
+        hop, lead, tail = geometry
+        ep = st["endpoint"]
+        ep_lag = ep["lag"] if "lag" in ep else ep["kernel"] // 2
+        gate.setdefault("hop", hop)
+        gate.setdefault("lead", lead)
+        gate.setdefault("tail", tail)
+        lag = gate.pop("lag_frames", st["lookahead"] + ep_lag + -(-tail // hop))
+        return self.gate_open(st["B"], st["chunk"], ep["labels"].shape[1], st["in"].dtype, lag, **gate)
+
+    def window_slots_open(self, B: int, chunk: int, window: int = 500, lookahead: int = 0, graphs: bool = False, endpoint=None, gate=None):
         """Allocate and reset a log-mel slot pool (uvad_window_slots_reset): B slots stepping `chunk` samples at a time, each holding at
         most one session, windows of `window` frames, frames emitted `lookahead` frames behind the newest complete one (the END step
-        flushes them).  graphs: capture the first step into a hipGraph and replay it for every later step.  endpoint: _slots_endpoint."""
+        flushes them).  graphs: capture the first step into a hipGraph and replay it for every later step.  endpoint: _slots_endpoint;
+        gate (needs endpoint): _slots_gate."""
         window_slots_plan([], chunk, window, lookahead, self._fb_c.frame_len, self._fb_c.frame_shift)   # the limits, before allocating
+        n_left = (self._fb_c.frame_len - self._fb_c.frame_shift) // 2
         with torch.cuda.device(self.device):
             nbytes = int(self.lib.uvad_window_slots_state_bytes(self.ctx, B, window))
             if nbytes == 0:
@@ -781,7 +807,8 @@ class VadRuntime:
                  "counts": torch.zeros(B, dtype=torch.int32, device=self.device),
                  "in": torch.empty((B, chunk), dtype=torch.float32, device=self.device),
                  "flags": torch.zeros(B, dtype=torch.uint8, device=self.device),
-                 "graphs": 0 if graphs else None, "graph": None, "weights_gen": getattr(self, "_weights_gen", 0)}, endpoint)
+                 "graphs": 0 if graphs else None, "graph": None, "weights_gen": getattr(self, "_weights_gen", 0)}, endpoint, gate,
+                (self._fb_c.frame_shift, n_left, self._fb_c.frame_len - self._fb_c.frame_shift - n_left))
 
     def window_slots_step(self, st, pcm_chunk: "torch.Tensor", start=None, end=None):
         """pcm_chunk (B, chunk) f32 on the GPU; start / end: slots whose session starts with this chunk / ends after it (bool masks or
@@ -803,9 +830,9 @@ class VadRuntime:
             return feats, tw
 
     def wav_window_slots_open(self, B: int, chunk: int, window: int = 293, lookahead: int = 0, graphs: bool = False,
-                              dtype=torch.float32, endpoint=None):
+                              dtype=torch.float32, endpoint=None, gate=None):
         """Allocate and reset a waveform slot pool (uvad_window_wav_slots_reset): window_slots_open for the SincNet PyanNet, samples of
-        dtype torch.float32 or torch.int16 (read as q / 32768).  endpoint: _slots_endpoint."""
+        dtype torch.float32 or torch.int16 (read as q / 32768).  endpoint: _slots_endpoint; gate (needs endpoint): _slots_gate."""
         if dtype not in (torch.float32, torch.int16):
             raise ValueError(f"dtype must be torch.float32 or torch.int16, got {dtype}")
         J, R = self.wav_window_geometry()
@@ -826,7 +853,8 @@ class VadRuntime:
                  "counts": torch.zeros(B, dtype=torch.int32, device=self.device),
                  "in": torch.empty((B, chunk), dtype=dtype, device=self.device),
                  "flags": torch.zeros(B, dtype=torch.uint8, device=self.device),
-                 "graphs": 0 if graphs else None, "graph": None, "weights_gen": getattr(self, "_weights_gen", 0)}, endpoint)
+                 "graphs": 0 if graphs else None, "graph": None, "weights_gen": getattr(self, "_weights_gen", 0)}, endpoint, gate,
+                (J, 0, R - J))
 
     def wav_window_slots_step(self, st, pcm_chunk: "torch.Tensor", start=None, end=None):
         """window_slots_step for a waveform slot pool: pcm_chunk (B, chunk) of the dtype the pool was opened with."""
@@ -936,6 +964,88 @@ class VadRuntime:
         """endpoint_step for a hysteresis endpointer: the same arguments and returns; active is 0 idle, 1 inside a confirmed interval,
         2 inside a candidate that has not reached min_on frames yet."""
         return self._endpoint_run(ep, self._endpoint_hyst_enqueue, probs, counts, start, end)
+
+    # ------------------------------------------------------------------ live speech gate (uvad_gate_*)
+    def gate_open(self, B: int, chunk: int, ld_lab: int, dtype, lag_frames: int, history=None, ld_out=None, max_seg=None, **cuts_cfg):
+        """Allocate and reset a speech gate of B slots (uvad_gate_reset): the streaming cuts_table + cuts_gather.  Every step takes a
+        (B, chunk) block of samples of `dtype` (torch.int16 or torch.float32) and up to ld_lab finalised labels per slot and emits each
+        slot's speech audio as fragments with records.  **cuts_cfg: pad, max_len, hop, lead, tail as cuts_open (min_len must be 0).
+        lag_frames: how far the label frontier may trail floor(samples / hop) after a step; it sizes the history ring
+        (uvad_gate_history) unless `history` samples are given.  ld_out / max_seg default to uvad_gate_max_out / uvad_gate_max_seg, which
+        never truncate."""
+        if dtype not in (torch.float32, torch.int16):
+            raise ValueError(f"dtype must be torch.float32 or torch.int16, got {dtype}")
+        q = dict(pad=0, max_len=0, min_len=0, hop=160, lead=0, tail=240)
+        extra = set(cuts_cfg) - set(q)
+        if extra:
+            raise ValueError(f"unknown gate parameters {sorted(extra)} (pad, max_len, hop, lead, tail)")
+        q.update(cuts_cfg)
+        cfg = _lib.CutsCfg(*(int(q[k]) for k in ("pad", "max_len", "min_len", "hop", "lead", "tail")))
+        unit = 2 if dtype == torch.int16 else 4
+        if history is None:
+            history = int(self.lib.uvad_gate_history(C.byref(cfg), int(lag_frames), int(chunk)))
+        history = int(history)
+        with torch.cuda.device(self.device):
+            nbytes = int(self.lib.uvad_gate_state_bytes(self.ctx, B, C.byref(cfg), unit, history)) if history >= 1 else 0
+            auto_out = int(self.lib.uvad_gate_max_out(C.byref(cfg), int(ld_lab), int(chunk), history))
+            auto_seg = int(self.lib.uvad_gate_max_seg(C.byref(cfg), int(ld_lab)))
+            if nbytes == 0 or auto_out < 0 or auto_seg < 0:
+                raise ValueError(f"bad gate configuration: B {B} (>= 1), chunk {chunk} (1 .. 2^24), ld_lab {ld_lab} (>= 0), lag_frames "
+                                 f"{lag_frames} (>= 0), history {history} (chunk .. 2^31 - 1), pad {q['pad']} (0 .. 2^20), max_len {q['max_len']} "
+                                 f"(0 .. 2^24), min_len {q['min_len']} (0), hop {q['hop']} (>= 1), lead {q['lead']} and tail {q['tail']} (>= 0)")
+            ld_out = auto_out if ld_out is None else int(ld_out)
+            max_seg = auto_seg if max_seg is None else int(max_seg)
+            if ld_out < 0 or max_seg < 0:
+                raise ValueError("ld_out and max_seg must be >= 0")
+            state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._check(self.lib.uvad_gate_reset(self.ctx, state.data_ptr(), nbytes, B, C.byref(cfg), unit, history, self._stream()))
+            return {"state": state, "B": B, "chunk": int(chunk), "ld_lab": int(ld_lab), "dtype": dtype, "cfg": cfg, "history": history,
+                    "lag_frames": int(lag_frames), "ld_out": ld_out, "max_seg": max_seg,
+                    "out": torch.zeros((B, max(ld_out, 1)), dtype=dtype, device=self.device),
+                    "seg": torch.zeros((B, max(max_seg, 1), 8), dtype=torch.int32, device=self.device),
+                    "seg_counts": torch.zeros(B, dtype=torch.int32, device=self.device)}
+
+    def _gate_enqueue(self, g, chunk_ptr, labels_ptr, lab_counts_ptr, flags_ptr):
+        return self.lib.uvad_gate_step(self.ctx, chunk_ptr, g["chunk"], labels_ptr, g["ld_lab"], lab_counts_ptr, flags_ptr, g["B"],
+                                       g["state"].data_ptr(), g["state"].numel(), g["out"].data_ptr() if g["ld_out"] else None, g["ld_out"],
+                                       g["seg"].data_ptr() if g["max_seg"] else None, g["max_seg"], g["seg_counts"].data_ptr(), self._stream())
+
+    def gate_step(self, g, chunk: "torch.Tensor", labels, lab_counts, start=None, end=None):
+        """chunk (B, chunk) of the gate's dtype, labels (B, ld_lab) uint8 and lab_counts (B,) int32 on the GPU (None, None with ld_lab = 0);
+        start / end as window_slots_step.  -> (out (B, ld_out), seg (B, max_seg, 8) int32 -- uvad_gate_seg rows {index, flags, first_frame,
+        n_frames, offset lo / hi, n, n_stored} --, seg_counts (B,) int32), on the device and overwritten by the next step."""
+        with torch.cuda.device(self.device):
+            if not torch.is_tensor(chunk) or chunk.device != self.device or chunk.dtype != g["dtype"] or tuple(chunk.shape) != (g["B"], g["chunk"]):
+                raise ValueError(f"chunk must be a ({g['B']}, {g['chunk']}) {g['dtype']} tensor on {self.device}")
+            chunk = chunk.contiguous()
+            lp = cp = None
+            if g["ld_lab"]:
+                if not torch.is_tensor(labels) or labels.device != self.device or labels.dtype != torch.uint8 or \
+                        tuple(labels.shape) != (g["B"], g["ld_lab"]):
+                    raise ValueError(f"labels must be a ({g['B']}, {g['ld_lab']}) uint8 tensor on {self.device}")
+                if not torch.is_tensor(lab_counts) or lab_counts.device != self.device or lab_counts.dtype != torch.int32 or \
+                        tuple(lab_counts.shape) != (g["B"],):
+                    raise ValueError(f"lab_counts must be an int32 tensor of shape ({g['B']},) on {self.device}")
+                labels, lab_counts = labels.contiguous(), lab_counts.contiguous()
+                lp, cp = labels.data_ptr(), lab_counts.data_ptr()
+            flags = self._slot_flags(g["B"], start, end)
+            self._check(self._gate_enqueue(g, chunk.data_ptr(), lp, cp, flags.data_ptr() if flags is not None else None))
+            return g["out"], g["seg"], g["seg_counts"]
+
+    def gate_collect(self, g):
+        """The records of the last step on the host -> [(slot, index, flags, first_frame, n_frames, fragment)]: fragment is a view of the
+        n_stored samples in g["out"] (on the device, overwritten by the next step).  One synchronising copy of the records and counts."""
+        with torch.cuda.device(self.device):
+            counts = g["seg_counts"].cpu().numpy()
+            seg = g["seg"].cpu().numpy()
+        out = []
+        for b in range(g["B"]):
+            off = 0
+            for r in seg[b, :min(int(counts[b]), g["max_seg"])]:
+                ns = int(r[7])
+                out.append((b, int(r[0]), int(r[1]), int(r[2]), int(r[3]), g["out"][b, off:off + ns]))
+                off += ns
+        return out
 
     # ------------------------------------------------------------------ scoring against reference labels (uvad_score_*)
     def score_open(self, points=((0.5, 25),), collar: int = 0, bins: int = 256, segment: int = 0):
