@@ -714,6 +714,54 @@ int uvad_cuts_table(uvad_ctx *, const uint8_t *d_labels, int ld, int B, int T, c
 int uvad_cuts_gather(uvad_ctx *, const void *d_src, int64_t row_stride, int unit_bytes, int which, const uvad_cut *d_table,
                      const int32_t *d_total, int max_cuts, void *d_out, int64_t ld_out, int32_t *d_out_len, void *stream);
 
+/* ---- The cut-supervision join: which supervisions (or words) belong to which cut, and the audit, on the device -------------------------
+ * Replaces the step get_new_cuts exists for (src/scripts/predict.py): cut.truncate(offset, duration, keep_excessive_supervisions=True,
+ * _supervisions_index=...) (predict.py:515-520), which gives each new cut the supervisions that overlap it; the exceed test of :541; the
+ * transcript of a cut, its supervisions' texts or the alignment's words that lie wholly inside it (:549-572); and the seven counters
+ * printed after every run (:597-611, again in other_vad_metrics.py:259-271).  Everything is integer, in frames; every output is
+ * byte-exact against a brute-force numpy restatement (tests/join_ref.py).
+ *
+ * Inputs: d_table, d_row_first [B + 1] and d_total exactly as uvad_cuts_table wrote them; d_iv [B][max_iv][2] int32 {s, e} in frames and
+ *   d_iv_counts [B] int32 (clamped to [0, max_iv]), the layout of uvad_intervals_to_labels.  Items may be unsorted, overlapping, negative
+ *   or past the row.  With m = min(*d_total, max_cuts), only cuts with global index < m take part (later cuts are not in the table);
+ *   row b's cuts are [d_row_first[b], min(d_row_first[b + 1], m)), ascending and disjoint in frames.
+ * Semantics: a cut covers [f, f + k), f = first_frame, k = n_frames; an item is [s, e).
+ *   UVAD_JOIN_OVERLAP  the item matches the cut iff s < f + k and e > f (the half-open rule of the interval tree behind truncate);
+ *   UVAD_JOIN_INSIDE   iff s >= f and e <= f + k (the word rule of predict.py:565-568);
+ *   an item with e <= s matches nothing in either mode, and is still counted as an item;
+ *   a matched pair EXCEEDS iff f > s or f + k < e (predict.py:541); INSIDE can never exceed.
+ * Outputs:
+ *   d_pair_first [max_cuts + 1] int32: entry i <= m the index of cut i's first pair, so entry m is the true number of pairs, which may
+ *     exceed max_pairs; entries past m are not written;
+ *   d_pairs [max_pairs] int32: for each cut in table order the indices, within the row, of its matching items, ascending within a cut;
+ *     pairs at or past max_pairs are counted, not stored (as uvad_label_runs treats max_runs);
+ *   d_item_cuts [B][max_iv][2] int32 (may be NULL): for each item below its row's count {global index of the first matching cut, number
+ *     of matching cuts} -- the matching cuts are contiguous because cuts are disjoint and ordered -- and {-1, 0} when none match;
+ *     slots past the count are not written;
+ *   d_audit [B + 1][UVAD_JOIN_AUDIT_WORDS] uint64, per row, row B the sum over rows:
+ *     [0] items  [1] cuts taking part  [2] pairs  [3] items with at least one cut  [4] items with none (= [0] - [3])
+ *     [5] exceeding pairs  [6] repeated pairs (= [2] - [3]; the reference's "in multiple")  [7] cuts with no item
+ *     The reference's report: Total = [0], in new cuts = [2], unique = [3], not in = [4], exceeding = [5], in multiple = [6], empty
+ *     cuts = [7].  Words 0, 3, 4, 5 are counted from the items' side and 1, 2, 7 from the cuts' side, independently.
+ * The call allocates nothing, never synchronises and reads every count from the device; its grids depend on B, max_iv and max_cuts
+ * alone, and workgroups past the totals do nothing: a graph captured around uvad_cuts_table + uvad_cuts_join (+ uvad_cuts_gather) replays
+ * for new labels, lengths and items.  Never read: table entries at or past m, item slots at or past the row's count, and the item
+ * slots of a row with no cuts (such a row still gets its counters; a row with no items gives every one of its cuts an empty pair list).
+ * No atomics: the same calls give the same bytes.  Workspace: uvad_cuts_join_ws_bytes(ctx, B, max_iv, max_cuts) bytes (0 on a bad
+ * argument).  The cost is cuts x items per row.  A context created without feature / model configuration serves the call.
+ * Refusals (UVAD_E_ARG, nothing enqueued, uvad_last_error names the word): B < 1; max_iv < 0; max_cuts < 0; max_pairs < 0; mode unknown;
+ *   NULL d_row_first / d_total / d_iv_counts / d_pair_first / d_audit / d_ws; NULL d_table with max_cuts > 0; NULL d_iv with max_iv > 0;
+ *   NULL d_pairs with max_pairs > 0; max_cuts x max_iv above 2^31 - 1 (what d_pair_first can count); ws_bytes below
+ *   uvad_cuts_join_ws_bytes ("need N bytes"). */
+#define UVAD_JOIN_OVERLAP 0
+#define UVAD_JOIN_INSIDE  1
+#define UVAD_JOIN_AUDIT_WORDS 8
+size_t uvad_cuts_join_ws_bytes(const uvad_ctx *, int B, int max_iv, int max_cuts);   /* 0 on a bad argument */
+int uvad_cuts_join(uvad_ctx *, const uvad_cut *d_table, const int32_t *d_row_first, const int32_t *d_total, int max_cuts, int B,
+                   const int32_t *d_iv, const int32_t *d_iv_counts, int max_iv, int mode,
+                   int32_t *d_pair_first, int32_t *d_pairs, int max_pairs, int32_t *d_item_cuts, uint64_t *d_audit,
+                   void *d_ws, size_t ws_bytes, void *stream);
+
 /* ---- Hysteresis decisions with minimum durations, on the device -----------------------------------------------------------------------
  * The other way from probabilities to speech labels, beside the threshold + median of uvad_median_filter (the reference's predict_step):
  * two thresholds, a shortest speech interval, a shortest pause and asymmetric padding -- the parameter set of the pyannote pipeline whose

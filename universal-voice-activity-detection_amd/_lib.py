@@ -55,6 +55,10 @@ class CutsCfg(C.Structure):
     _fields_ = [("pad", C.c_int), ("max_len", C.c_int), ("min_len", C.c_int), ("hop", C.c_int), ("lead", C.c_int), ("tail", C.c_int)]
 
 
+JOIN_OVERLAP, JOIN_INSIDE = 0, 1     # `mode` of uvad_cuts_join
+JOIN_AUDIT_WORDS = 8                 # uint64 words per row of uvad_cuts_join's d_audit (include/uvad.h gives the layout)
+
+
 class Cut(C.Structure):          # uvad_cut: one row of the cut table (32 bytes)
     _fields_ = [("row", C.c_int32), ("index", C.c_int32), ("first_frame", C.c_int32), ("n_frames", C.c_int32),
                 ("first_sample", C.c_int64), ("n_samples", C.c_int64)]
@@ -184,6 +188,9 @@ SIGNATURES = {
                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_cuts_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                    C.c_int64, C.c_void_p, C.c_void_p]),
+    "uvad_cuts_join_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "uvad_cuts_join": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_binarize_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "uvad_binarize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(BinarizeCfg), C.c_void_p, C.c_int,
                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -243,7 +250,7 @@ _lib = None
 
 def bind(lib):
     """Declare every prototype of SIGNATURES on `lib`.  The ABI number did not move when entries were appended (the ingest stage among
-    them, the endpointer, the scoring stage, the speech cuts, the hysteresis decisions, the hysteresis endpointer and the speech gate after it), so a library built from an older tree passes the version check: a symbol it lacks is a loud error here, by name."""
+    them, the endpointer, the scoring stage, the speech cuts, the hysteresis decisions, the hysteresis endpointer, the speech gate and the cut-supervision join after it), so a library built from an older tree passes the version check: a symbol it lacks is a loud error here, by name."""
     for name, (res, args) in SIGNATURES.items():
         try:
             fn = getattr(lib, name)

@@ -62,6 +62,12 @@ def load_config() -> ConfigDict:
     # buffer and merged, with split cut to at most window seconds, remainders of min seconds or less dropped (uvad_cuts_table); with
     # write_dir one 16 kHz wav per cut is written there (uvad_cuts_gather)
     cfg.cuts = None
+    # supervisions / alignments = None: nothing more.  With cuts, {recording_id: path or [(start_s, end_s, text)]} (a file of
+    # `start<TAB>end<TAB>text` lines, postprocess.read_supervisions): every cut gains the indices of the recording's supervisions that
+    # overlap it and their concatenated text, every result the reference's seven counters (uvad_cuts_join).  alignments has one entry
+    # per word; a word belongs to the cut that holds it whole, and with both given the words supply the text
+    cfg.supervisions = None
+    cfg.alignments = None
     # binarize = None: labels are threshold 0.5 + median, as the reference's predict_step.  A dict in seconds {"onset": 0.5, "offset": None,
     # "min_duration_on": 0.0, "min_duration_off": 0.0, "pad_onset": 0.0, "pad_offset": 0.0}: hysteresis decisions instead (uvad_binarize)
     # -- speech turns on at onset and off below offset, runs are padded, pauses shorter than min_duration_off filled and intervals shorter

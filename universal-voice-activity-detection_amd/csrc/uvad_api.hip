@@ -3129,6 +3129,45 @@ int uvad_cuts_gather(uvad_ctx *c, const void *d_src, int64_t row_stride, int uni
     return UVAD_OK;
 }
 
+// ---- the cut-supervision join (join.hip) --------------------------------------------------------------------------------------------------
+size_t uvad_cuts_join_ws_bytes(const uvad_ctx *c, int B, int max_iv, int max_cuts) {
+    if (!c || B < 1 || max_iv < 0 || max_cuts < 0 || (long long)max_cuts * max_iv > 0x7fffffffll) return 0;
+    return join_ws_bytes(max_cuts);
+}
+
+int uvad_cuts_join(uvad_ctx *c, const uvad_cut *d_table, const int32_t *d_row_first, const int32_t *d_total, int max_cuts, int B,
+                   const int32_t *d_iv, const int32_t *d_iv_counts, int max_iv, int mode, int32_t *d_pair_first, int32_t *d_pairs,
+                   int max_pairs, int32_t *d_item_cuts, uint64_t *d_audit, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (B < 1) return fail(c, UVAD_E_ARG, "uvad_cuts_join: B must be >= 1");
+    if (max_iv < 0) return fail(c, UVAD_E_ARG, "uvad_cuts_join: max_iv must be >= 0");
+    if (max_cuts < 0) return fail(c, UVAD_E_ARG, "uvad_cuts_join: max_cuts must be >= 0");
+    if (max_pairs < 0) return fail(c, UVAD_E_ARG, "uvad_cuts_join: max_pairs must be >= 0");
+    if (mode != UVAD_JOIN_OVERLAP && mode != UVAD_JOIN_INSIDE) return fail(c, UVAD_E_ARG, "uvad_cuts_join: mode must be UVAD_JOIN_OVERLAP or UVAD_JOIN_INSIDE");
+    if (!d_row_first) return fail(c, UVAD_E_ARG, "uvad_cuts_join: d_row_first is NULL");
+    if (!d_total) return fail(c, UVAD_E_ARG, "uvad_cuts_join: d_total is NULL");
+    if (!d_iv_counts) return fail(c, UVAD_E_ARG, "uvad_cuts_join: d_iv_counts is NULL");
+    if (!d_pair_first) return fail(c, UVAD_E_ARG, "uvad_cuts_join: d_pair_first is NULL");
+    if (!d_audit) return fail(c, UVAD_E_ARG, "uvad_cuts_join: d_audit is NULL");
+    if (!d_ws) return fail(c, UVAD_E_ARG, "uvad_cuts_join: d_ws is NULL");
+    if (max_cuts > 0 && !d_table) return fail(c, UVAD_E_ARG, "uvad_cuts_join: d_table is NULL with max_cuts > 0");
+    if (max_iv > 0 && !d_iv) return fail(c, UVAD_E_ARG, "uvad_cuts_join: d_iv is NULL with max_iv > 0");
+    if (max_pairs > 0 && !d_pairs) return fail(c, UVAD_E_ARG, "uvad_cuts_join: d_pairs is NULL with max_pairs > 0");
+    if ((long long)max_cuts * max_iv > 0x7fffffffll) return fail(c, UVAD_E_ARG, "uvad_cuts_join: max_cuts x max_iv above 2^31 - 1");
+    const size_t need = join_ws_bytes(max_cuts);
+    if (ws_bytes < need) return fail(c, UVAD_E_ARG, "uvad_cuts_join: workspace too small: need " + std::to_string(need) + " bytes");
+    JoinArgs a{};
+    a.table = reinterpret_cast<const CutRecord *>(d_table); a.row_first = d_row_first; a.total = d_total; a.max_cuts = max_cuts; a.B = B;
+    a.iv = d_iv; a.iv_counts = d_iv_counts; a.max_iv = max_iv; a.inside = mode == UVAD_JOIN_INSIDE;
+    a.pair_first = d_pair_first; a.pairs = d_pairs; a.max_pairs = max_pairs; a.item_cuts = d_item_cuts;
+    a.audit = reinterpret_cast<unsigned long long *>(d_audit);
+    a.counts = reinterpret_cast<int *>(d_ws);
+    a.empty_first = reinterpret_cast<int *>(reinterpret_cast<char *>(d_ws) + join_counts_bytes(max_cuts));
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_cuts_join(a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
 // ---- hysteresis decisions with minimum durations (binarize.hip) ---------------------------------------------------------------------------
 // nullptr: the configuration is in range; else the word uvad_last_error names
 static const char *binarize_cfg_error(const uvad_binarize_cfg *q) {

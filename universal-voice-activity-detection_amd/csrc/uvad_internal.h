@@ -578,6 +578,20 @@ int cuts_max_per_row(const CutsCfgInt &q, int T);
 hipError_t launch_cuts_table(const CutsTableArgs &a, hipStream_t s);
 hipError_t launch_cuts_gather(const CutsGatherArgs &a, hipStream_t s);
 
+// ---- join.hip: the cut-supervision join (uvad_cuts_join, include/uvad.h): which items of its row each cut of a cut table matches -----------
+// The workspace is one int32 per cut (its number of pairs), rounded up to 16 bytes, followed by max_cuts + 1 int32: the exclusive prefix
+// of the cuts without a pair, from which a row's empty cuts are one subtraction.
+constexpr int JOIN_AUDIT_WORDS = 8;                   // UVAD_JOIN_AUDIT_WORDS
+struct JoinArgs {
+    const CutRecord *table; const int *row_first, *total; int max_cuts, B;
+    const int *iv, *iv_counts; int max_iv, inside;    // inside: UVAD_JOIN_INSIDE, else UVAD_JOIN_OVERLAP
+    int *pair_first, *pairs; int max_pairs; int *item_cuts; unsigned long long *audit;
+    int *counts, *empty_first;                        // the workspace: [max_cuts], [max_cuts + 1]
+};
+constexpr size_t join_counts_bytes(int max_cuts) { return ((size_t)max_cuts * sizeof(int) + 15) / 16 * 16; }
+constexpr size_t join_ws_bytes(int max_cuts) { return join_counts_bytes(max_cuts) + (((size_t)max_cuts + 1) * sizeof(int) + 15) / 16 * 16; }
+hipError_t launch_cuts_join(const JoinArgs &a, hipStream_t s);
+
 // ---- binarize.hip: hysteresis decisions with minimum durations (uvad_binarize, include/uvad.h) -------------------------------------------
 // The workspace is (T + 63) / 64 word pairs {HI mask, LO mask} per row (16 bytes a pair), followed by (T + 1) / 2 int32 pairs {lo, hi}
 // per row: the row's full interval list, which the labels are made from.

@@ -390,3 +390,48 @@ def read_label_file(path: str):
                 raise ValueError(f"{path}:{ln}: expected `start<TAB>end<TAB>LABEL`")
             out.append((float(parts[0]), float(parts[1])))
     return out
+
+
+# ---- the cut-supervision join (uvad_cuts_join): supervisions, transcripts and the reference's report ------------
+
+JOIN_REPORT_NAMES = ("Total Supervisions", "Supervisions in new cuts", "Unique Supervisions in new cuts", "Supervisions not in new cuts",
+                     "Supervisions exceeding new cuts", "Supervisions in multiple new cuts", "Empty cuts")
+
+
+def read_supervisions(path: str):
+    """A supervision (or word alignment) file, one `start<TAB>end<TAB>text` line per item -> [(start_s, end_s, text)].  The text is the
+    rest of the line, stripped -- it may hold blanks and tabs -- and None when the line has none; blank lines are skipped.  The files
+    read_label_file reads are of this form with the label as text."""
+    out = []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            parts = line.strip().split(None, 2)
+            if not parts:
+                continue
+            if len(parts) < 2:
+                raise ValueError(f"{path}:{ln}: expected `start<TAB>end<TAB>text`")
+            out.append((float(parts[0]), float(parts[1]), parts[2].strip() if len(parts) > 2 else None))
+    return out
+
+
+def cut_transcripts(pairs_per_cut, texts) -> List[str]:
+    """The reference's transcript of each cut (predict.py:549-553, the alignment's words at :555-572): the texts of the cut's items in
+    the order listed, each followed by one blank, the whole stripped.  pairs_per_cut: for each cut the indices of its items
+    (VadRuntime.cuts_join_read); texts: the row's texts by item index.  A text of None is skipped."""
+    out = []
+    for items in pairs_per_cut:
+        text = ""
+        for j in items:
+            if texts[j] is not None:
+                text += texts[j] + " "
+        out.append(text.strip())
+    return out
+
+
+def join_report(audit: dict, dataset_name: str, buffer, phase: str) -> str:
+    """The text block get_new_cuts prints after a run (predict.py:597-611; its three detection-error lines belong to the scoring stage,
+    score_metrics) from an audit of VadRuntime.cuts_join_read -- its "audit" dict (the pooled counters are used) or one row of it."""
+    a = audit.get("pooled", audit)
+    lines = [f"Dataset: {dataset_name}, Buffer: {buffer}, Phase: {phase}", "", "----------------"]
+    lines += [f"{name}: {int(a[name])}" for name in JOIN_REPORT_NAMES]
+    return "\n".join(lines) + "\n"

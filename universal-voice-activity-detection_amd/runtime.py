@@ -1268,6 +1268,89 @@ class VadRuntime:
             n = min(int(cuts["total"].cpu()[0]), cuts["max_cuts"])
             return cuts["table"][:n].cpu().numpy().view(dt).reshape(-1).copy()
 
+    # ------------------------------------------------------------------ the cut-supervision join (uvad_cuts_join)
+    JOIN_MODES = {"overlap": _lib.JOIN_OVERLAP, "inside": _lib.JOIN_INSIDE}
+    # the reference's seven counters (predict.py:597-611) and the audit word each is; word 1, the cuts taking part, goes as "New cuts"
+    JOIN_AUDIT_NAMES = (("Total Supervisions", 0), ("Supervisions in new cuts", 2), ("Unique Supervisions in new cuts", 3),
+                        ("Supervisions not in new cuts", 4), ("Supervisions exceeding new cuts", 5),
+                        ("Supervisions in multiple new cuts", 6), ("Empty cuts", 7), ("New cuts", 1))
+
+    def cuts_join(self, cuts, intervals, counts, mode: str = "overlap", max_pairs=None, rows=None):
+        """Which items belong to which cut (uvad_cuts_join), on a state of cuts_open after cuts_table, with no copy to the host: intervals
+        (B, max_iv, 2) int32 {start, end} in frames and counts (B,) int32 -- one row per row of the labels, the layout of
+        intervals_to_labels, so postprocess.supervision_frames feeds both; tensors on the GPU are read in place (a captured graph
+        replays with new items), anything else is uploaded.  mode "overlap": an item matches every cut it shares a frame with (the
+        supervisions of cut.truncate); "inside": the cut that holds it whole (the words of an alignment).
+        max_pairs: slots of `pairs` (default: min(max_cuts x max_iv, max_cuts + B x max_iv), which holds every pair when a row's items
+        do not overlap one another; pairs past it are counted, not stored, and pair_first's last used entry is the true total to retry with).
+        rows (default max_cuts) bounds the cuts that take part, as in cuts_gather: a caller who knows the total (cuts_read) passes it, which
+        keeps max_cuts x max_iv, what the call can count, small.
+        -> {"pair_first" (max_cuts + 1,), "pairs" (max_pairs,), "item_cuts" (B, max_iv, 2) int32, "audit" (B + 1, 8) int64}: device
+        tensors kept on the state and overwritten by the next call.  cuts_join_read gives the host view."""
+        ct = cuts
+        if ct.get("table") is None:
+            raise RuntimeError("cuts_join needs a state on which cuts_table has run")
+        if mode not in self.JOIN_MODES:
+            raise ValueError(f"mode must be one of {sorted(self.JOIN_MODES)}, got {mode!r}")
+        with torch.cuda.device(self.device):
+            iv = intervals if torch.is_tensor(intervals) else torch.from_numpy(np.ascontiguousarray(intervals, np.int32))
+            iv = iv.to(self.device, torch.int32).contiguous()
+            if iv.dim() != 3 or iv.shape[2] != 2:
+                raise ValueError(f"intervals must be (B, max_iv, 2), got {tuple(iv.shape)}")
+            B, max_iv = int(iv.shape[0]), int(iv.shape[1])
+            if B != ct["row_first"].numel() - 1:
+                raise ValueError(f"intervals has {B} rows, the cut table was made from {ct['row_first'].numel() - 1}")
+            cn = counts if torch.is_tensor(counts) else torch.from_numpy(np.ascontiguousarray(counts, np.int32))
+            cn = cn.to(self.device, torch.int32).contiguous()
+            if tuple(cn.shape) != (B,):
+                raise ValueError(f"counts must be ({B},), got {tuple(cn.shape)}")
+            mc = ct["max_cuts"] if rows is None else min(ct["max_cuts"], max(int(rows), 0))
+            if mc * max_iv > 0x7fffffff:
+                raise ValueError(f"max_cuts x max_iv = {mc * max_iv} is above 2^31 - 1: pass rows= (or cuts_open's max_cuts) near the total")
+            mp = min(mc * max_iv, mc + B * max_iv) if max_pairs is None else int(max_pairs)
+            if mp < 0:
+                raise ValueError("max_pairs must be >= 0")
+            key = (B, max_iv, mp, mc)
+            jn = ct.get("join")
+            if jn is None or jn["key"] != key:
+                need = int(self.lib.uvad_cuts_join_ws_bytes(self.ctx, B, max_iv, mc))
+                jn = ct["join"] = {"key": key,
+                                   "pair_first": torch.zeros(mc + 1, dtype=torch.int32, device=self.device),
+                                   "pairs": torch.zeros(max(mp, 1), dtype=torch.int32, device=self.device),
+                                   "item_cuts": torch.zeros((B, max(max_iv, 1), 2), dtype=torch.int32, device=self.device),
+                                   "audit": torch.zeros((B + 1, _lib.JOIN_AUDIT_WORDS), dtype=torch.int64, device=self.device),
+                                   "ws": torch.zeros(max(need, 16), dtype=torch.uint8, device=self.device)}
+            self._check(self.lib.uvad_cuts_join(self.ctx, ct["table"].data_ptr() if mc else None, ct["row_first"].data_ptr(), ct["total"].data_ptr(),
+                                                mc, B, iv.data_ptr() if max_iv else None, cn.data_ptr(), max_iv, self.JOIN_MODES[mode],
+                                                jn["pair_first"].data_ptr(), jn["pairs"].data_ptr() if mp else None, mp,
+                                                jn["item_cuts"].data_ptr(), jn["audit"].data_ptr(), jn["ws"].data_ptr(), jn["ws"].numel(),
+                                                self._stream()))
+            jn["_keep"] = (iv, cn)          # the launch reads them after this call returns
+            jn["max_pairs"], jn["max_iv"], jn["max_cuts"] = mp, max_iv, mc
+            return {"pair_first": jn["pair_first"], "pairs": jn["pairs"][:mp], "item_cuts": jn["item_cuts"][:, :max_iv], "audit": jn["audit"]}
+
+    def cuts_join_read(self, cuts) -> dict:
+        """The last cuts_join on the state, copied to the host (synchronises) -> {"pairs_per_cut": for each cut that took part (the order of
+        cuts_read) the list of its items' indices within its row, ascending; "total_pairs": the true number of pairs; "stored_pairs":
+        min(total_pairs, max_pairs) -- a cut whose pairs were cut off by max_pairs lists the stored ones only --; "item_cuts" (B, max_iv,
+        2) int32 {first cut, number of cuts} per item (slots past a row's count hold what an earlier call left); "audit": {"rows": one
+        dict per row, "pooled": their sum} under the reference's seven names (predict.py:597-611) plus "New cuts"; "audit_words"
+        (B + 1, 8) int64, the raw words}."""
+        jn = cuts.get("join")
+        if jn is None:
+            raise RuntimeError("cuts_join_read needs a state on which cuts_join has run")
+        with torch.cuda.device(self.device):
+            m = min(int(cuts["total"].cpu()[0]), jn["max_cuts"])
+            first = jn["pair_first"][:m + 1].cpu().numpy()
+            total = int(first[m])
+            stored = min(total, jn["max_pairs"])
+            pairs = jn["pairs"][:stored].cpu().numpy()
+            words = jn["audit"].cpu().numpy().copy()
+            named = [{name: int(row[k]) for name, k in self.JOIN_AUDIT_NAMES} for row in words]
+            return {"pairs_per_cut": [pairs[min(int(first[i]), stored):min(int(first[i + 1]), stored)].tolist() for i in range(m)],
+                    "total_pairs": total, "stored_pairs": stored, "item_cuts": jn["item_cuts"][:, :jn["max_iv"]].cpu().numpy().copy(),
+                    "audit": {"rows": named[:-1], "pooled": named[-1]}, "audit_words": words}
+
     # ------------------------------------------------------------------ hysteresis decisions with minimum durations (uvad_binarize)
     def binarize_open(self, onset: float = 0.5, offset=None, min_on: int = 0, min_off: int = 0, pad_on: int = 0, pad_off: int = 0, max_iv=None):
         """The configuration and the buffers of binarize below: speech turns on at a frame with !(p < onset) and off at one with p < offset

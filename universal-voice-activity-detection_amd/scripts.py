@@ -176,7 +176,7 @@ def _write_results(results, kwargs):
         with open(os.path.join(out_dir, "predictions.json"), "w") as f:
             json.dump([{"recording_id": r["recording_id"], "num_frames": r["num_frames"],
                         "speech_frames": int(r["labels"].sum()), "intervals": r["intervals"],
-                        **({"cuts": r["cuts"]} if "cuts" in r else {})} for r in results], f, indent=1)
+                        **({k: r[k] for k in ("cuts", "audit", "audit_words") if k in r})} for r in results], f, indent=1)
     for r in results:
         print(f"{r['recording_id']}: {r['num_frames']} frames, {int(r['labels'].sum())} speech, {len(r['intervals'])} intervals")
     return results
@@ -195,12 +195,36 @@ def _write_wav_int16(path: str, x: np.ndarray, sample_rate: int = 16000):
         w.writeframes(x.astype("<i2").tobytes())
 
 
-def _attach_cuts(results, recs, dev_labels, rt, cuts, sincnet, frame_shift, device, max_samples, sr=16000):
+def _join_items(source, rec_ids, nsamp, frames, sincnet, shift, sr):
+    """predict_vad(supervisions= / alignments=): {recording_id: path or [(start_s, end_s, text)]} for a group's recordings -> (intervals
+    (B, max_iv, 2) int32 frames, counts (B,), texts per row): seconds become frames through supervision_frames with the geometry of the
+    model in use; a recording without an entry has no items."""
+    from .postprocess import read_supervisions, supervision_frames
+    rows = []
+    for rid in rec_ids:
+        items = source.get(rid, [])
+        rows.append(read_supervisions(items) if isinstance(items, (str, os.PathLike)) else [tuple(it) for it in items])
+    max_iv = max((len(r) for r in rows), default=0)
+    iv = np.zeros((len(rows), max_iv, 2), np.int32)
+    for b, r in enumerate(rows):
+        if r:
+            iv[b, :len(r)] = supervision_frames([(it[0], it[1]) for it in r], nsamp[b] / float(sr), frame_shift=shift,
+                                                geometry="sincnet" if sincnet else "fbank", num_frames=frames[b])
+    return iv, np.asarray([len(r) for r in rows], np.int32), [[it[2] if len(it) > 2 else None for it in r] for r in rows]
+
+
+def _attach_cuts(results, recs, dev_labels, rt, cuts, sincnet, frame_shift, device, max_samples, sr=16000, supervisions=None, alignments=None):
     """predict_vad(cuts=...): the tail of the reference's get_new_cuts on the device.  results[i], recs[i] and dev_labels[i] (the
     recording's whole-row labels, a 1-D tensor on the GPU, or None when it has no frame) belong together.  Recordings are grouped within
     the max_duration budget; a group is one uvad_cuts_table call on its padded label rows, and its table is the only thing that crosses
     to the host -- with write_dir also one uvad_cuts_gather of the group's audio, written as one 16 kHz wav per cut.  Every result gains
-    "cuts": [(start_s, end_s, first_sample, n_samples)]."""
+    "cuts": [(start_s, end_s, first_sample, n_samples)].
+    With supervisions and / or alignments ({recording_id: path or [(start_s, end_s, text)]}) each group also runs uvad_cuts_join on its
+    table, on the device -- supervisions by overlap, an alignment's words by containment -- and every cut becomes a dict {"start", "end",
+    "first_sample", "n_samples", "supervisions": indices into the recording's list, "text"} (with alignments also "words", whose text
+    replaces the supervisions' for a recording that has an alignment), every result gains "audit": the reference's seven counters for that recording (postprocess.join_report prints them)."""
+    from .postprocess import cut_transcripts
+    join = supervisions is not None or alignments is not None
     unknown = set(cuts) - set(CUTS_DEFAULTS)
     if unknown:
         raise ValueError(f"unknown cuts option(s) {sorted(unknown)} (known: {sorted(CUTS_DEFAULTS)})")
@@ -227,6 +251,12 @@ def _attach_cuts(results, recs, dev_labels, rt, cuts, sincnet, frame_shift, devi
         ct = rt.cuts_open(**cfg)
         rt.cuts_table(lab, lengths=frames, nsamp=nsamp, S=S, cuts=ct)
         tab = rt.cuts_read(ct)
+        joined = {}
+        for name, source, mode in (("supervisions", supervisions, "overlap"), ("words", alignments, "inside")):
+            if source is not None:   # one more launch on the table where it lies; the pair lists and eight counters a row cross to the host
+                iv, counts, texts = _join_items(source, [recs[i]["id"] for i in idx], nsamp, frames, sincnet, shift, sr)
+                rt.cuts_join(ct, iv, counts, mode=mode, rows=len(tab))
+                joined[name] = (rt.cuts_join_read(ct), texts, [recs[i]["id"] in source for i in idx])
         batch = lens = None
         if opt["write_dir"] and len(tab):
             mixed = len({recs[i]["pcm"].dtype for i in idx}) > 1
@@ -240,9 +270,25 @@ def _attach_cuts(results, recs, dev_labels, rt, cuts, sincnet, frame_shift, devi
         for k, c in enumerate(tab):
             res = results[idx[int(c["row"])]]
             f, nf = int(c["first_frame"]), int(c["n_frames"])
-            res["cuts"].append((round(f * shift, 6), round((f + nf) * shift, 6), int(c["first_sample"]), int(c["n_samples"])))
+            entry = (round(f * shift, 6), round((f + nf) * shift, 6), int(c["first_sample"]), int(c["n_samples"]))
+            if join:
+                entry = dict(zip(("start", "end", "first_sample", "n_samples"), entry))
+                for name, (read, texts, listed) in joined.items():
+                    entry[name] = read["pairs_per_cut"][k]
+                    if "text" not in entry or listed[int(c["row"])]:   # the words supply the text of a recording that has an alignment
+                        entry["text"] = cut_transcripts([entry[name]], texts[int(c["row"])])[0]
+            res["cuts"].append(entry)
             if batch is not None:
                 _write_wav_int16(os.path.join(opt["write_dir"], f"{res['recording_id']}_{int(c['index']):04d}.wav"), batch[k, :lens[k]], sr)
+        for name, (read, _, _) in joined.items():
+            for r, i in enumerate(idx):
+                results[i]["audit" if name == "supervisions" or supervisions is None else "audit_words"] = read["audit"]["rows"][r]
+    for source, key in ((supervisions, "audit"), (alignments, "audit" if supervisions is None else "audit_words")):
+        if source is not None:
+            for i, res in enumerate(results):   # a recording without a frame has no cut: all of its items are "not in new cuts"
+                if key not in res:
+                    n = int(_join_items(source, [recs[i]["id"]], [0], [0], False, shift, sr)[1][0])
+                    res[key] = {name: (n if k in (0, 4) else 0) for name, k in rt.JOIN_AUDIT_NAMES}
 
 
 BINARIZE_DEFAULTS = {"onset": 0.5, "offset": None, "min_duration_on": 0.0, "min_duration_off": 0.0, "pad_onset": 0.0, "pad_offset": 0.0}
@@ -391,13 +437,18 @@ def predict_vad(**kwargs):
         binarize = _binarize_frames(binarize, sincnet, frame_shift, sr)
     cuts = kwargs.get("cuts")   # None: every output below is what it was; a dict (CUTS_DEFAULTS): every result gains "cuts" (_attach_cuts)
     dev_labels = [None] * len(recs) if cuts is not None else None   # each recording's whole-row labels, kept on the device
+    # None: nothing more; {recording_id: path or [(start_s, end_s, text)]}: every cut gains its supervisions / words and text, every result "audit"
+    supervisions, alignments = kwargs.get("supervisions"), kwargs.get("alignments")
+    if (supervisions is not None or alignments is not None) and cuts is None:
+        raise ValueError("supervisions / alignments are joined with the cuts: pass cuts= as well")
     hop_s = kwargs.get("hop_seconds")
     if hop_s is not None:   # overlapping windows of window_seconds every hop_seconds, aggregated on the device; None: the cuts below, unchanged
         if window_s is None:
             raise ValueError("hop_seconds needs window_seconds (the window the model was trained on)")
         results = _predict_sliding(recs, net.runtime(device), sincnet, kwargs, window_s, hop_s, frame_shift, med_window, device, sr, dev_labels, binarize)
         if cuts is not None:
-            _attach_cuts(results, recs, dev_labels, net.runtime(device), cuts, sincnet, frame_shift, device, int(kwargs["max_duration"] * sr), sr)
+            _attach_cuts(results, recs, dev_labels, net.runtime(device), cuts, sincnet, frame_shift, device, int(kwargs["max_duration"] * sr), sr,
+                         supervisions, alignments)
         return _write_results(results, kwargs)
 
     # ---- batches: pieces of equal length together, at most max_duration seconds of audio per batch; with ragged_batches (whole
@@ -563,7 +614,7 @@ def predict_vad(**kwargs):
         if dev_labels is not None:
             dev_labels[ri] = labels
     if cuts is not None:
-        _attach_cuts(results, recs, dev_labels, rt, cuts, sincnet, frame_shift, device, int(kwargs["max_duration"] * sr), sr)
+        _attach_cuts(results, recs, dev_labels, rt, cuts, sincnet, frame_shift, device, int(kwargs["max_duration"] * sr), sr, supervisions, alignments)
     return _write_results(results, kwargs)
 
 
