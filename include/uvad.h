@@ -762,6 +762,83 @@ int uvad_cuts_join(uvad_ctx *, const uvad_cut *d_table, const int32_t *d_row_fir
                    int32_t *d_pair_first, int32_t *d_pairs, int max_pairs, int32_t *d_item_cuts, uint64_t *d_audit,
                    void *d_ws, size_t ws_bytes, void *stream);
 
+/* ---- Channel fusion: one decision per multi-microphone recording, on the device ------------------------------------------------------------
+ * The ingest stage makes a row of every channel; this stage puts the rows of one recording back together.  It replaces, for corpora with
+ * one set of reference labels over several channels (the `mdm` microphone-array and the two-channel telephone recipes under
+ * src/datasets/), the stack / reduce / argmax a caller would do on the host before the per-recording get_binary_tensor / FA / MD block of
+ * src/scripts/other_vad_metrics.py:156-213 -- with no copy to the host in between.  Every output is bit-defined and byte-exact against a
+ * numpy restatement (tests/fuse_ref.py).
+ *
+ * uvad_fuse_configure: all arrays are HOST arrays; they are validated, then uploaded into the context (as uvad_sliding_configure's weights
+ *   and uvad_ingest_set_taps' table).  Group g is member slots j in [h_group_first[g], h_group_first[g + 1]); slot j reads input row
+ *   h_members[j]; N = h_group_first[G].  Rows need not be contiguous and may appear in several groups.  h_weights [N] (NULL: all ones)
+ *   weigh MEAN and VOTE.  cfg.threshold is a member's own speech test, !(p < threshold); cfg.decide the same test on the fused value.
+ *   One configuration per context; a later configure replaces it (graphs captured before it keep the grid of the old one).
+ *   If the upload itself fails (UVAD_E_HIP) the validated configuration is kept, so uvad_fuse_ws_bytes and every argument refusal below
+ *   still answer; uvad_fuse and uvad_fuse_pick then return UVAD_E_HIP after their argument checks.
+ * uvad_fuse: d_in [B][ld_in] f32, d_lens [B] int32 or NULL, d_flags_in [B] uint8 or NULL.  One call serves dense and ragged batches and a
+ *   live step: there d_in, d_lens and d_flags_in are the d_probs, d_counts and flag bytes a slot pool step wrote, and T = ld_in.
+ *   With n_r = clamp(d_lens[r], 0, T) (T when d_lens is NULL):
+ *   group length  L_g = max n_r over the group's members -> d_glens[g] (int32).  At frame t < L_g the valid members are those with t < n_r.
+ *   never read    columns at or past n_r of any row; rows no group names; whole rows with n_r = 0.  Output columns at or past L_g are
+ *                 never written.
+ *   UVAD_FUSE_MAX   the largest valid member value, NaN ranking above everything: if any valid member is NaN the result is (that) NaN,
+ *                   in keeping with "NaN counts as speech" everywhere above;
+ *   UVAD_FUSE_MEAN  over the valid members in slot order, in f64: acc += (double)w_j * (double)p_j, W += (double)w_j; the result is
+ *                   (float)(acc / W), or 0.0f when W == 0.  A product of two f32 values is exact in f64, so contraction to an fma cannot
+ *                   change a bit.  The input may as well be logits: no meaning is attached to the range.  A NaN result (a NaN member,
+ *                   inf x 0, inf - inf) is written as the one quiet NaN 0x7fc00000, whatever sign the arithmetic gave it;
+ *   UVAD_FUSE_VOTE  the same expression with p_j replaced by 1.0 if !(p_j < threshold) (NaN votes speech) and 0.0 otherwise: the weighted
+ *                   share of members that hear speech.  decide = 0.5 is a majority; a decide just above 0 means any member.
+ *   d_fused [G][ld_f] f32   the fused value;
+ *   d_labels [G][ld_l] u8   !(fused < decide) as 0 / 1: raw labels, in the form uvad_cuts_table reads as it is;
+ *   d_best [G][ld_b] u8     the position within the group of the valid member with the largest value: NaN ranks above everything, ties
+ *                           go to the lowest position, weights play no part;
+ *   d_stats [N][UVAD_FUSE_STATS_WORDS] uint64 per member slot, ADDED to what is there (the caller zeroes it once with a memset; a live
+ *                           session or a sweep over batches then accumulates with no copy to the host): [0] valid frames  [1] frames
+ *                           with !(p < threshold)  [2] frames whose own decision equals the fused decision  [3] frames where it is best;
+ *   d_flags_out [G] u8      the bitwise OR of the members' d_flags_in bytes; written only when both flag pointers are given.
+ *   d_labels, d_best, d_stats and the two flag arrays may each be NULL; d_fused and d_glens are required.
+ *   The call allocates nothing, never synchronises and reads all lengths from the device; its grid depends on the configuration, B and T
+ *   alone: a captured graph replays for new inputs and lengths.  No atomics: ballots and population counts per wave, one partial per
+ *   (member slot, frame tile, wave) in d_ws, and a fold in a fixed order that adds into d_stats -- the same calls give the same bytes.
+ *   16-byte loads where a row's base is 16-byte aligned and four frames are valid, single loads elsewhere; the output does not depend on
+ *   which ran.  Workspace: uvad_fuse_ws_bytes(ctx, B, T) bytes (0 on a bad argument or before uvad_fuse_configure).
+ * uvad_fuse_pick: the channel of each cut.  For cut i < min(*d_total, max_cuts) of a table uvad_cuts_table made from the fused labels
+ *   (row = group g): among the group's members the position k with the most frames t in [first_frame, first_frame + n_frames) where
+ *   d_best[g][t] == k; ties go to the lowest position; a cut of 0 frames gets k = 0.  d_pick[i] = k (int32); d_out_table[i] is the cut
+ *   with row replaced by that member's INPUT row index and everything else unchanged, so the unchanged uvad_cuts_gather on the [B] audio
+ *   rows fetches each cut from the channel that heard it best.  Later entries are not written.  A cut whose row is not a group index is
+ *   skipped: its entry is copied unchanged and its pick is -1.  d_out_table may be d_table itself.
+ * A context created without feature / model configuration serves all of these calls.
+ * Refusals (UVAD_E_ARG, nothing enqueued, uvad_last_error names the word):
+ *   uvad_fuse_configure: NULL cfg / h_group_first / h_members; G < 1; h_group_first[0] != 0 or not non-decreasing; a group with 0 or
+ *     more than UVAD_FUSE_MAX_MEMBERS members; a member index < 0; a weight that is not finite or is < 0; a group whose weights sum to 0;
+ *     a threshold or decide that is not finite; an unknown mode;
+ *   uvad_fuse: NULL d_in / d_fused / d_glens / d_ws; B not above the largest configured member index; T < 1 or > 2^30; any of ld_in,
+ *     ld_f, ld_l, ld_b below T where its array is given; ws_bytes below uvad_fuse_ws_bytes ("need N bytes"); exactly one of the two flag
+ *     arrays given;
+ *   uvad_fuse_pick: NULL d_best / d_total; NULL d_table with max_cuts > 0; both outputs NULL; max_cuts < 0; ld_b < 1.
+ *   UVAD_E_STATE: uvad_fuse / uvad_fuse_pick before uvad_fuse_configure. */
+#define UVAD_FUSE_MAX  0
+#define UVAD_FUSE_MEAN 1
+#define UVAD_FUSE_VOTE 2
+#define UVAD_FUSE_MAX_MEMBERS 255
+#define UVAD_FUSE_STATS_WORDS 4
+typedef struct {
+    int mode;          /* UVAD_FUSE_MAX, UVAD_FUSE_MEAN or UVAD_FUSE_VOTE */
+    float threshold;   /* a member hears speech at !(p < threshold); finite */
+    float decide;      /* the fused label is !(fused < decide); finite */
+} uvad_fuse_cfg;
+int uvad_fuse_configure(uvad_ctx *, const uvad_fuse_cfg *, const int32_t *h_group_first, const int32_t *h_members, const float *h_weights,
+                        int G);
+size_t uvad_fuse_ws_bytes(const uvad_ctx *, int B, int T);   /* 0 on a bad argument or before uvad_fuse_configure */
+int uvad_fuse(uvad_ctx *, const float *d_in, int ld_in, int B, int T, const int32_t *d_lens, const uint8_t *d_flags_in,
+              float *d_fused, int ld_f, int32_t *d_glens, uint8_t *d_flags_out, uint8_t *d_labels, int ld_l, uint8_t *d_best, int ld_b,
+              uint64_t *d_stats, void *d_ws, size_t ws_bytes, void *stream);
+int uvad_fuse_pick(uvad_ctx *, const uint8_t *d_best, int ld_b, const uvad_cut *d_table, const int32_t *d_total, int max_cuts,
+                   uvad_cut *d_out_table, int32_t *d_pick, void *stream);
+
 /* ---- Hysteresis decisions with minimum durations, on the device -----------------------------------------------------------------------
  * The other way from probabilities to speech labels, beside the threshold + median of uvad_median_filter (the reference's predict_step):
  * two thresholds, a shortest speech interval, a shortest pause and asymmetric padding -- the parameter set of the pyannote pipeline whose

@@ -59,6 +59,15 @@ JOIN_OVERLAP, JOIN_INSIDE = 0, 1     # `mode` of uvad_cuts_join
 JOIN_AUDIT_WORDS = 8                 # uint64 words per row of uvad_cuts_join's d_audit (include/uvad.h gives the layout)
 
 
+FUSE_MAX, FUSE_MEAN, FUSE_VOTE = 0, 1, 2     # uvad_fuse_cfg.mode
+FUSE_MAX_MEMBERS = 255               # members of one group: a position fits d_best's byte
+FUSE_STATS_WORDS = 4                 # uint64 words per member slot of uvad_fuse's d_stats: valid, speech, agree, best
+
+
+class FuseCfg(C.Structure):      # uvad_fuse_cfg (12 bytes)
+    _fields_ = [("mode", C.c_int), ("threshold", C.c_float), ("decide", C.c_float)]
+
+
 class Cut(C.Structure):          # uvad_cut: one row of the cut table (32 bytes)
     _fields_ = [("row", C.c_int32), ("index", C.c_int32), ("first_frame", C.c_int32), ("n_frames", C.c_int32),
                 ("first_sample", C.c_int64), ("n_samples", C.c_int64)]
@@ -191,6 +200,11 @@ SIGNATURES = {
     "uvad_cuts_join_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "uvad_cuts_join": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_fuse_configure": (C.c_int, [C.c_void_p, C.POINTER(FuseCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "uvad_fuse_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "uvad_fuse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                            C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_fuse_pick": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uvad_binarize_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "uvad_binarize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(BinarizeCfg), C.c_void_p, C.c_int,
                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -250,7 +264,7 @@ _lib = None
 
 def bind(lib):
     """Declare every prototype of SIGNATURES on `lib`.  The ABI number did not move when entries were appended (the ingest stage among
-    them, the endpointer, the scoring stage, the speech cuts, the hysteresis decisions, the hysteresis endpointer, the speech gate and the cut-supervision join after it), so a library built from an older tree passes the version check: a symbol it lacks is a loud error here, by name."""
+    them, the endpointer, the scoring stage, the speech cuts, the hysteresis decisions, the hysteresis endpointer, the speech gate, the cut-supervision join and the channel fusion after it), so a library built from an older tree passes the version check: a symbol it lacks is a loud error here, by name."""
     for name, (res, args) in SIGNATURES.items():
         try:
             fn = getattr(lib, name)

@@ -73,6 +73,11 @@ def load_config() -> ConfigDict:
     # -- speech turns on at onset and off below offset, runs are padded, pauses shorter than min_duration_off filled and intervals shorter
     # than min_duration_on dropped; with cuts, pass buffer = 0 there if padding was applied here
     cfg.binarize = None
+    # fuse = None: with input.channels = "all" every channel of a file is a recording of its own (rec-ch0, rec-ch1, ...).  A dict {"mode":
+    # "max" | "mean" | "vote", "threshold": 0.5, "decide": None}: the channels' probabilities are fused on the device (uvad_fuse) and each
+    # file gives ONE result, with "channel_stats"; with cuts each cut's audio comes from the channel that heard it best and carries
+    # "channel" (uvad_fuse_pick).  function = "test" then scores the fused row of a multi-channel file against its label file
+    cfg.fuse = None
 
     cfg.experiments_dir = os.environ.get("UVAD_EXPERIMENTS_DIR", "experiments")
     cfg.load_checkpoint = False

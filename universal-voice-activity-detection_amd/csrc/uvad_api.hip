@@ -165,6 +165,14 @@ struct uvad_ctx {
     int sl_W = 0, sl_Hf = 0;
     std::vector<float> sl_w_host;
     float *d_sl_w = nullptr; int sl_w_cap = 0;   // [sl_w_cap] floats, grown by uvad_sliding_configure, lives with the context
+    // channel fusion (uvad_fuse_*, fuse.hip): the validated configuration as given, and its copy on the device: one buffer of
+    // fz_cap 4-byte words {group_first [G + 1], members [N], weights [N]}, grown by uvad_fuse_configure, lives with the context
+    bool has_fuse = false, fz_on_device = false;
+    uvad_fuse_cfg fz{};
+    int fz_G = 0, fz_N = 0, fz_max_member = -1;
+    bool fz_weighted = false;
+    std::vector<int32_t> fz_host;      // what d_fz holds
+    int32_t *d_fz = nullptr; size_t fz_cap = 0;
 };
 
 namespace {
@@ -3165,6 +3173,124 @@ int uvad_cuts_join(uvad_ctx *c, const uvad_cut *d_table, const int32_t *d_row_fi
     a.empty_first = reinterpret_cast<int *>(reinterpret_cast<char *>(d_ws) + join_counts_bytes(max_cuts));
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, launch_cuts_join(a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+// ---- channel fusion (fuse.hip) -----------------------------------------------------------------------------------------------------------
+int uvad_fuse_configure(uvad_ctx *c, const uvad_fuse_cfg *q, const int32_t *h_first, const int32_t *h_members, const float *h_weights, int G) {
+    if (!c) return UVAD_E_ARG;
+    if (!q) return fail(c, UVAD_E_ARG, "uvad_fuse_configure: cfg is NULL");
+    if (!h_first) return fail(c, UVAD_E_ARG, "uvad_fuse_configure: h_group_first is NULL");
+    if (!h_members) return fail(c, UVAD_E_ARG, "uvad_fuse_configure: h_members is NULL");
+    if (G < 1) return fail(c, UVAD_E_ARG, "uvad_fuse_configure: G must be >= 1");
+    if (q->mode != UVAD_FUSE_MAX && q->mode != UVAD_FUSE_MEAN && q->mode != UVAD_FUSE_VOTE)
+        return fail(c, UVAD_E_ARG, "uvad_fuse_configure: mode must be UVAD_FUSE_MAX, UVAD_FUSE_MEAN or UVAD_FUSE_VOTE");
+    if (!std::isfinite(q->threshold)) return fail(c, UVAD_E_ARG, "uvad_fuse_configure: threshold must be finite");
+    if (!std::isfinite(q->decide)) return fail(c, UVAD_E_ARG, "uvad_fuse_configure: decide must be finite");
+    if (h_first[0] != 0) return fail(c, UVAD_E_ARG, "uvad_fuse_configure: h_group_first[0] must be 0");
+    for (int g = 0; g < G; ++g) {
+        const long long m = (long long)h_first[g + 1] - h_first[g];
+        if (m < 0) return fail(c, UVAD_E_ARG, "uvad_fuse_configure: h_group_first must be non-decreasing (group " + std::to_string(g) + ")");
+        if (m < 1 || m > FUSE_MAX_MEMBERS)
+            return fail(c, UVAD_E_ARG, "uvad_fuse_configure: a group has 1 .. 255 members (group " + std::to_string(g) + " has " + std::to_string(m) + ")");
+    }
+    const int N = h_first[G];
+    int max_member = -1;
+    for (int j = 0; j < N; ++j) {
+        if (h_members[j] < 0) return fail(c, UVAD_E_ARG, "uvad_fuse_configure: a member index must be >= 0 (slot " + std::to_string(j) + ")");
+        max_member = std::max(max_member, (int)h_members[j]);
+    }
+    if (h_weights) {
+        for (int j = 0; j < N; ++j)
+            if (!std::isfinite(h_weights[j]) || h_weights[j] < 0.0f)
+                return fail(c, UVAD_E_ARG, "uvad_fuse_configure: every weight must be finite and >= 0 (slot " + std::to_string(j) + ")");
+        for (int g = 0; g < G; ++g) {
+            double sum = 0.0;
+            for (int j = h_first[g]; j < h_first[g + 1]; ++j) sum += (double)h_weights[j];
+            if (!(sum > 0.0)) return fail(c, UVAD_E_ARG, "uvad_fuse_configure: the weights of a group must not sum to 0 (group " + std::to_string(g) + ")");
+        }
+    }
+    std::vector<int32_t> host((size_t)G + 1 + 2 * (size_t)N);
+    std::memcpy(host.data(), h_first, ((size_t)G + 1) * sizeof(int32_t));
+    std::memcpy(host.data() + G + 1, h_members, (size_t)N * sizeof(int32_t));
+    if (h_weights) std::memcpy(host.data() + G + 1 + N, h_weights, (size_t)N * sizeof(float));
+    const bool same = c->has_fuse && c->fz_on_device && host == c->fz_host;
+    c->fz = *q; c->fz_G = G; c->fz_N = N; c->fz_max_member = max_member; c->fz_weighted = h_weights != nullptr;
+    c->has_fuse = true;
+    if (same) return UVAD_OK;
+    c->fz_on_device = false;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->fz_cap < host.size()) {   // a larger configuration: a new buffer (the old one lives with the context: captured graphs may name it)
+        void *p = nullptr;
+        HIPCHK(c, hipMalloc(&p, host.size() * sizeof(int32_t)));
+        c->allocs.push_back(p);
+        c->d_fz = reinterpret_cast<int32_t *>(p);
+        c->fz_cap = host.size();
+    } else {
+        HIPCHK(c, hipDeviceSynchronize());   // kernels of earlier calls may still be reading the arrays
+    }
+    HIPCHK(c, hipMemcpy(c->d_fz, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    c->fz_host.swap(host);
+    c->fz_on_device = true;
+    return UVAD_OK;
+}
+
+size_t uvad_fuse_ws_bytes(const uvad_ctx *c, int B, int T) {
+    if (!c || !c->has_fuse || B <= c->fz_max_member || T < 1 || T > FUSE_MAX_T) return 0;
+    return fuse_ws_bytes(c->fz_N, T);
+}
+
+int uvad_fuse(uvad_ctx *c, const float *d_in, int ld_in, int B, int T, const int32_t *d_lens, const uint8_t *d_flags_in, float *d_fused,
+              int ld_f, int32_t *d_glens, uint8_t *d_flags_out, uint8_t *d_labels, int ld_l, uint8_t *d_best, int ld_b, uint64_t *d_stats,
+              void *d_ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!c->has_fuse) return fail(c, UVAD_E_STATE, "uvad_fuse: uvad_fuse_configure has not been called");
+    if (!d_in) return fail(c, UVAD_E_ARG, "uvad_fuse: d_in is NULL");
+    if (!d_fused) return fail(c, UVAD_E_ARG, "uvad_fuse: d_fused is NULL");
+    if (!d_glens) return fail(c, UVAD_E_ARG, "uvad_fuse: d_glens is NULL");
+    if (!d_ws) return fail(c, UVAD_E_ARG, "uvad_fuse: d_ws is NULL");
+    if (B <= c->fz_max_member)
+        return fail(c, UVAD_E_ARG, "uvad_fuse: B must be above the largest configured member index (" + std::to_string(c->fz_max_member) + ")");
+    if (T < 1 || T > FUSE_MAX_T) return fail(c, UVAD_E_ARG, "uvad_fuse: T must lie in [1, 2^30]");
+    if (ld_in < T) return fail(c, UVAD_E_ARG, "uvad_fuse: ld_in must be at least T");
+    if (ld_f < T) return fail(c, UVAD_E_ARG, "uvad_fuse: ld_f must be at least T");
+    if (d_labels && ld_l < T) return fail(c, UVAD_E_ARG, "uvad_fuse: ld_l must be at least T");
+    if (d_best && ld_b < T) return fail(c, UVAD_E_ARG, "uvad_fuse: ld_b must be at least T");
+    if ((d_flags_in == nullptr) != (d_flags_out == nullptr))
+        return fail(c, UVAD_E_ARG, "uvad_fuse: d_flags_in and d_flags_out go together: give both or neither");
+    const size_t need = fuse_ws_bytes(c->fz_N, T);
+    if (ws_bytes < need) return fail(c, UVAD_E_ARG, "uvad_fuse: workspace too small: need " + std::to_string(need) + " bytes");
+    if (!c->fz_on_device) return fail(c, UVAD_E_HIP, "uvad_fuse: the configuration is not on the device (uvad_fuse_configure's upload failed)");
+    FuseArgs a{};
+    a.first = c->d_fz; a.members = c->d_fz + c->fz_G + 1; a.G = c->fz_G; a.N = c->fz_N;
+    a.weights = c->fz_weighted ? reinterpret_cast<const float *>(c->d_fz + c->fz_G + 1 + c->fz_N) : nullptr;
+    a.q = FuseCfgInt{c->fz.mode, c->fz.threshold, c->fz.decide};
+    a.in = d_in; a.ld_in = ld_in; a.T = T; a.lens = d_lens; a.flags_in = d_flags_in;
+    a.fused = d_fused; a.ld_f = ld_f; a.glens = d_glens; a.flags_out = d_flags_out; a.labels = d_labels; a.ld_l = ld_l;
+    a.best = d_best; a.ld_b = ld_b; a.stats = reinterpret_cast<unsigned long long *>(d_stats);
+    a.part = reinterpret_cast<FusePartial *>(d_ws); a.tiles = fuse_tiles(T);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_fuse(a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_fuse_pick(uvad_ctx *c, const uint8_t *d_best, int ld_b, const uvad_cut *d_table, const int32_t *d_total, int max_cuts,
+                   uvad_cut *d_out_table, int32_t *d_pick, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!c->has_fuse) return fail(c, UVAD_E_STATE, "uvad_fuse_pick: uvad_fuse_configure has not been called");
+    if (!d_best) return fail(c, UVAD_E_ARG, "uvad_fuse_pick: d_best is NULL");
+    if (!d_total) return fail(c, UVAD_E_ARG, "uvad_fuse_pick: d_total is NULL");
+    if (max_cuts < 0) return fail(c, UVAD_E_ARG, "uvad_fuse_pick: max_cuts must be >= 0");
+    if (max_cuts > 0 && !d_table) return fail(c, UVAD_E_ARG, "uvad_fuse_pick: d_table is NULL with max_cuts > 0");
+    if (!d_out_table && !d_pick) return fail(c, UVAD_E_ARG, "uvad_fuse_pick: d_out_table and d_pick are both NULL");
+    if (ld_b < 1) return fail(c, UVAD_E_ARG, "uvad_fuse_pick: ld_b must be >= 1");
+    if (!c->fz_on_device) return fail(c, UVAD_E_HIP, "uvad_fuse_pick: the configuration is not on the device (uvad_fuse_configure's upload failed)");
+    FusePickArgs a{};
+    a.first = c->d_fz; a.members = c->d_fz + c->fz_G + 1; a.G = c->fz_G;
+    a.best = d_best; a.ld_b = ld_b; a.table = reinterpret_cast<const CutRecord *>(d_table); a.total = d_total; a.max_cuts = max_cuts;
+    a.out_table = reinterpret_cast<CutRecord *>(d_out_table); a.pick = d_pick;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_fuse_pick(a, (hipStream_t)stream));
     return UVAD_OK;
 }
 

@@ -592,6 +592,33 @@ constexpr size_t join_counts_bytes(int max_cuts) { return ((size_t)max_cuts * si
 constexpr size_t join_ws_bytes(int max_cuts) { return join_counts_bytes(max_cuts) + (((size_t)max_cuts + 1) * sizeof(int) + 15) / 16 * 16; }
 hipError_t launch_cuts_join(const JoinArgs &a, hipStream_t s);
 
+// ---- fuse.hip: channel fusion (uvad_fuse_*, include/uvad.h): one row per group of input rows, and the channel of each cut ---------------------
+// The configuration (group_first [G + 1], members [N], weights [N] or none) lives on the device with the context.  The workspace of
+// uvad_fuse is, per member slot, one FusePartial per wave of every frame tile: [N][fuse_tiles(T) * FUSE_WAVES], 16 bytes each.
+constexpr int FUSE_MAX_T = 1 << 30;
+constexpr int FUSE_MAX_MEMBERS = 255;                 // per group: a position fits d_best's byte
+constexpr int FUSE_THREADS = 256, FUSE_WAVES = FUSE_THREADS / 64;
+constexpr int FUSE_TILE = FUSE_THREADS * 4;           // frames per workgroup pass: four consecutive frames a lane (one 16-byte load)
+constexpr int FUSE_MAX_BLOCKS = 1 << 16;              // grids are capped: workgroups stride over their (group, tile) items
+constexpr int FUSE_STATS_WORDS = 4;                   // valid, speech, agree, best
+struct FuseCfgInt { int mode; float threshold, decide; };   // uvad_fuse_cfg, field for field
+struct FusePartial { unsigned valid, speech, agree, best; };
+struct FuseArgs {
+    const int *first, *members; const float *weights; int G, N;   // the configuration on the device (weights may be null: all ones)
+    FuseCfgInt q;
+    const float *in; int ld_in, T; const int *lens; const uint8_t *flags_in;
+    float *fused; int ld_f; int *glens; uint8_t *flags_out; uint8_t *labels; int ld_l; uint8_t *best; int ld_b;
+    unsigned long long *stats; FusePartial *part; int tiles;
+};
+struct FusePickArgs {
+    const int *first, *members; int G;
+    const uint8_t *best; int ld_b; const CutRecord *table; const int *total; int max_cuts; CutRecord *out_table; int *pick;
+};
+constexpr int fuse_tiles(int T) { return (T + FUSE_TILE - 1) / FUSE_TILE; }
+constexpr size_t fuse_ws_bytes(int N, int T) { return (size_t)N * fuse_tiles(T) * FUSE_WAVES * sizeof(FusePartial); }
+hipError_t launch_fuse(const FuseArgs &a, hipStream_t s);
+hipError_t launch_fuse_pick(const FusePickArgs &a, hipStream_t s);
+
 // ---- binarize.hip: hysteresis decisions with minimum durations (uvad_binarize, include/uvad.h) -------------------------------------------
 // The workspace is (T + 63) / 64 word pairs {HI mask, LO mask} per row (16 bytes a pair), followed by (T + 1) / 2 int32 pairs {lo, hi}
 // per row: the row's full interval list, which the labels are made from.

@@ -435,3 +435,45 @@ def join_report(audit: dict, dataset_name: str, buffer, phase: str) -> str:
     lines = [f"Dataset: {dataset_name}, Buffer: {buffer}, Phase: {phase}", "", "----------------"]
     lines += [f"{name}: {int(a[name])}" for name in JOIN_REPORT_NAMES]
     return "\n".join(lines) + "\n"
+
+
+FUSE_MODE_NAMES = ("max", "mean", "vote")
+
+
+def fuse_config(mode="max", threshold=0.5, decide=None, groups=None, weights=None):
+    """A validated configuration of the channel fusion (VadRuntime.fuse_open, predict_vad(fuse=...)): groups is one list of input rows
+    per recording (1 .. 255 rows each, every index >= 0); weights None or one list per group of finite values >= 0 that do not sum to
+    0; threshold is a member's own speech test and decide the fused value's, both finite.  decide defaults to threshold, or to 0.5
+    (a majority) for "vote".  groups may be None where the caller makes them (predict_vad: the channels of each file)."""
+    if mode not in FUSE_MODE_NAMES:
+        raise ValueError(f"fuse mode must be one of {list(FUSE_MODE_NAMES)}, got {mode!r}")
+    if decide is None:
+        decide = 0.5 if mode == "vote" else threshold
+    for name, v in (("threshold", threshold), ("decide", decide)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not np.isfinite(v):
+            raise ValueError(f"fuse {name} must be a finite number, got {v!r}")
+    out = {"mode": mode, "threshold": float(threshold), "decide": float(decide), "groups": None, "weights": None}
+    if groups is None:
+        if weights is not None:
+            raise ValueError("fuse weights are given per group: they need groups")
+        return out
+    gs = [[int(r) for r in g] for g in groups]
+    if not gs:
+        raise ValueError("fuse needs at least one group")
+    for i, g in enumerate(gs):
+        if not 1 <= len(g) <= 255:
+            raise ValueError(f"a fuse group has 1 .. 255 members, group {i} has {len(g)}")
+        if min(g) < 0:
+            raise ValueError(f"fuse group {i} names a negative row")
+    out["groups"] = gs
+    if weights is not None:
+        ws = [[float(v) for v in w] for w in weights]
+        if len(ws) != len(gs) or any(len(w) != len(g) for w, g in zip(ws, gs)):
+            raise ValueError("fuse weights must have the shape of groups")
+        for i, w in enumerate(ws):
+            if any(not np.isfinite(v) or v < 0 for v in w):
+                raise ValueError(f"fuse weights must be finite and >= 0 (group {i})")
+            if not sum(w) > 0:
+                raise ValueError(f"the fuse weights of group {i} sum to 0")
+        out["weights"] = ws
+    return out

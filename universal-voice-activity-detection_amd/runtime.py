@@ -707,15 +707,24 @@ class VadRuntime:
         B = st["B"]
         out, counts = st["out"], st["counts"]
         ep = st.get("endpoint")
+        fz = st.get("fuse")
+        if fz is not None and getattr(self, "_fuse_current", None) is not fz:
+            self._fuse_configure(fz)                 # another fusion state was used on this runtime since: the context holds one
+            if st["graphs"] is not None:
+                st["graph"] = None                   # ... and a captured node names the arrays of the configuration it was captured with
 
         def enqueue(src, flags):
             fp = flags.data_ptr() if flags is not None else None
             r = fn(self.ctx, src.data_ptr(), fp, B, st["chunk"], st["state"].data_ptr(), out.data_ptr(),
-                   st["probs"].data_ptr() if ep is not None else None, out.shape[1], counts.data_ptr(), st["ws"].data_ptr(), st["ws"].numel(),
+                   st["probs"].data_ptr() if "probs" in st else None, out.shape[1], counts.data_ptr(), st["ws"].data_ptr(), st["ws"].numel(),
                    self._stream())
-            if r == 0 and ep is not None:            # the endpointer right behind the pool step: its probabilities, counts and flags as they are
+            p_ptr, c_ptr, f_ptr = st["probs"].data_ptr() if "probs" in st else None, counts.data_ptr(), fp
+            if r == 0 and fz is not None:            # the fusion right behind the pool step: one row per group for whatever follows
+                r = self._fuse_enqueue(fz, p_ptr, out.shape[1], B, out.shape[1], c_ptr, fp, False, True)
+                p_ptr, c_ptr, f_ptr = fz["fused"].data_ptr(), fz["glens"].data_ptr(), fz["flags"].data_ptr() if fp is not None else None
+            if r == 0 and ep is not None:            # the endpointer right behind: probabilities, counts and flags as they are
                 step = self._endpoint_hyst_enqueue if "lag" in ep else self._endpoint_enqueue
-                r = step(ep, st["probs"].data_ptr(), counts.data_ptr(), fp)
+                r = step(ep, p_ptr, c_ptr, f_ptr)
             if r == 0 and st.get("gate") is not None:   # ... and the gate behind it: the pool's chunk, the endpointer's labels, the same flags
                 r = self._gate_enqueue(st["gate"], src.data_ptr(), ep["labels"].data_ptr(), ep["lab_counts"].data_ptr(), fp)
             return r
@@ -743,12 +752,43 @@ class VadRuntime:
     _ENDPOINT_KEYS = {"kernel", "pad", "threshold"}
     _ENDPOINT_HYST_KEYS = {"onset", "offset", "min_on", "min_off", "pad_on", "pad_off"}
 
-    def _slots_endpoint(self, st, endpoint, gate=None, geometry=None):
+    def _slots_fuse(self, st, fuse, gate):
+        """fuse: None or {"groups": [[slots of one stream's channels], ...], "mode", "threshold", "decide", "weights"} (fuse_open's).  One
+        more node of the pool's step -- inside the one capture under graphs=True -- between the pool step and the endpointer: the
+        pool's probabilities, counts and flag bytes go through uvad_fuse, and the endpointer (if any) is opened for the G groups and reads
+        the fused rows, the group counts and the OR-ed flags.  st["fuse"] holds fused / glens / best / flags, overwritten by the next
+        step, and stats, accumulated over the steps (fuse_read).  The members of a group must be stepped in lockstep: the same START /
+        END flags and so the same counts every step -- which holds for the channels of one stream through ingest_step.  Opening or using
+        another fusion state on this runtime re-configures the context: the pool configures it back at its next step.  Not built: gate=
+        behind a fused pool (the gate would need a channel choice per fragment)."""
+        if fuse is None:
+            return None
+        if gate is not None:
+            raise ValueError("gate= together with fuse= is not built: the gate would need a channel choice per fragment")
+        from .postprocess import fuse_config
+        fuse = dict(fuse)
+        if fuse.get("groups") is None:
+            raise ValueError("fuse needs groups: the slots of each stream's channels")
+        q = fuse_config(**fuse)
+        if max(max(g) for g in q["groups"]) >= st["B"]:
+            raise ValueError(f"fuse groups name a slot at or past the pool's {st['B']}")
+        fz = self.fuse_open(fuse.pop("groups"), **fuse)
+        ld = st["out"].shape[1]
+        self._fuse_buffers(fz, ld, False, True, True)
+        need = int(self.lib.uvad_fuse_ws_bytes(self.ctx, st["B"], ld))
+        fz["ws"] = torch.zeros(max(need, 16), dtype=torch.uint8, device=self.device)
+        return fz
+
+    def _slots_endpoint(self, st, endpoint, gate=None, geometry=None, fuse=None):
         """endpoint: None, {"kernel", "pad", "threshold"} (any subset) for the median endpointer (endpoint_open), or {"onset", "offset",
         "min_on", "min_off", "pad_on", "pad_off"} (any non-empty subset; binarize_config's dict as it is) for the hysteresis endpointer
         (endpoint_hyst_open).  The pool gets a probabilities buffer and an endpointer over its B slots whose step is enqueued right behind
         every pool step -- inside the one capture under graphs=True -- with the pool's counts and flags.  st["endpoint"] holds its events /
         ev_counts / active, overwritten by the next step."""
+        fz = self._slots_fuse(st, fuse, gate)
+        if fz is not None:
+            st["fuse"] = fz
+            st["probs"] = torch.zeros_like(st["out"])
         if endpoint is None:
             if gate is not None:
                 raise ValueError("gate needs an endpoint: the gate reads the labels an endpointer finalises")
@@ -762,8 +802,9 @@ class VadRuntime:
         if extra:
             raise ValueError(f"unknown endpoint parameters {sorted(extra)} " +
                              ("(onset, offset, min_on, min_off, pad_on, pad_off)" if hyst else "(kernel, pad, threshold)"))
-        st["probs"] = torch.zeros_like(st["out"])
-        st["endpoint"] = (self.endpoint_hyst_open if hyst else self.endpoint_open)(st["B"], st["out"].shape[1], **endpoint)
+        st["probs"] = st["probs"] if "probs" in st else torch.zeros_like(st["out"])
+        st["endpoint"] = (self.endpoint_hyst_open if hyst else self.endpoint_open)(fz["G"] if fz is not None else st["B"], st["out"].shape[1],
+                                                                                  **endpoint)
         if gate is not None:
             st["gate"] = self._slots_gate(st, dict(gate), geometry)
         return st
@@ -786,11 +827,12 @@ class VadRuntime:
         lag = gate.pop("lag_frames", st["lookahead"] + ep_lag + -(-tail // hop))
         return self.gate_open(st["B"], st["chunk"], ep["labels"].shape[1], st["in"].dtype, lag, **gate)
 
-    def window_slots_open(self, B: int, chunk: int, window: int = 500, lookahead: int = 0, graphs: bool = False, endpoint=None, gate=None):
+    def window_slots_open(self, B: int, chunk: int, window: int = 500, lookahead: int = 0, graphs: bool = False, endpoint=None, gate=None,
+                          fuse=None):
         """Allocate and reset a log-mel slot pool (uvad_window_slots_reset): B slots stepping `chunk` samples at a time, each holding at
         most one session, windows of `window` frames, frames emitted `lookahead` frames behind the newest complete one (the END step
         flushes them).  graphs: capture the first step into a hipGraph and replay it for every later step.  endpoint: _slots_endpoint;
-        gate (needs endpoint): _slots_gate."""
+        gate (needs endpoint): _slots_gate; fuse: _slots_fuse (the endpointer then serves the groups, not the slots)."""
         window_slots_plan([], chunk, window, lookahead, self._fb_c.frame_len, self._fb_c.frame_shift)   # the limits, before allocating
         n_left = (self._fb_c.frame_len - self._fb_c.frame_shift) // 2
         with torch.cuda.device(self.device):
@@ -808,7 +850,7 @@ class VadRuntime:
                  "in": torch.empty((B, chunk), dtype=torch.float32, device=self.device),
                  "flags": torch.zeros(B, dtype=torch.uint8, device=self.device),
                  "graphs": 0 if graphs else None, "graph": None, "weights_gen": getattr(self, "_weights_gen", 0)}, endpoint, gate,
-                (self._fb_c.frame_shift, n_left, self._fb_c.frame_len - self._fb_c.frame_shift - n_left))
+                (self._fb_c.frame_shift, n_left, self._fb_c.frame_len - self._fb_c.frame_shift - n_left), fuse)
 
     def window_slots_step(self, st, pcm_chunk: "torch.Tensor", start=None, end=None):
         """pcm_chunk (B, chunk) f32 on the GPU; start / end: slots whose session starts with this chunk / ends after it (bool masks or
@@ -830,9 +872,10 @@ class VadRuntime:
             return feats, tw
 
     def wav_window_slots_open(self, B: int, chunk: int, window: int = 293, lookahead: int = 0, graphs: bool = False,
-                              dtype=torch.float32, endpoint=None, gate=None):
+                              dtype=torch.float32, endpoint=None, gate=None, fuse=None):
         """Allocate and reset a waveform slot pool (uvad_window_wav_slots_reset): window_slots_open for the SincNet PyanNet, samples of
-        dtype torch.float32 or torch.int16 (read as q / 32768).  endpoint: _slots_endpoint; gate (needs endpoint): _slots_gate."""
+        dtype torch.float32 or torch.int16 (read as q / 32768).  endpoint: _slots_endpoint; gate (needs endpoint): _slots_gate; fuse:
+        _slots_fuse."""
         if dtype not in (torch.float32, torch.int16):
             raise ValueError(f"dtype must be torch.float32 or torch.int16, got {dtype}")
         J, R = self.wav_window_geometry()
@@ -854,7 +897,7 @@ class VadRuntime:
                  "in": torch.empty((B, chunk), dtype=dtype, device=self.device),
                  "flags": torch.zeros(B, dtype=torch.uint8, device=self.device),
                  "graphs": 0 if graphs else None, "graph": None, "weights_gen": getattr(self, "_weights_gen", 0)}, endpoint, gate,
-                (J, 0, R - J))
+                (J, 0, R - J), fuse)
 
     def wav_window_slots_step(self, st, pcm_chunk: "torch.Tensor", start=None, end=None):
         """window_slots_step for a waveform slot pool: pcm_chunk (B, chunk) of the dtype the pool was opened with."""
@@ -1211,13 +1254,14 @@ class VadRuntime:
             ct["S"] = int(S)
             return ct["table"][:mc], ct["row_first"], ct["total"]
 
-    def cuts_gather(self, src: "torch.Tensor", cuts, which: str = "samples", ld_out=None, rows=None):
+    def cuts_gather(self, src: "torch.Tensor", cuts, which: str = "samples", ld_out=None, rows=None, table=None):
         """The audio (which="samples": src (B, S) int16 or f32) or the feature frames (which="frames": src (B, T, F) f32) of the cuts the
         last cuts_table on the state `cuts` listed -> (batch (max_cuts, ld_out[, F]) of src's type, lengths (max_cuts,) int32): row i <
         total holds the cut's first min(n, ld_out) units, then zeros; later rows are left as they are.  ld_out defaults to
         uvad_cuts_max_samples rounded up to 8 (samples) or the longest possible cut in frames; rows (default max_cuts) bounds the
         batch's rows: the batch is rows x ld_out units of memory whatever the labels hold, so a caller who knows the total (cuts_read)
-        or an upper bound passes it, here or as cuts_open's max_cuts."""
+        or an upper bound passes it, here or as cuts_open's max_cuts.  table: another table of the same cuts to gather by (fuse_pick's,
+        whose rows are the picked channels' rows of src); default: the state's own."""
         ct = cuts
         if ct.get("table") is None:
             raise RuntimeError("cuts_gather needs a state on which cuts_table has run")
@@ -1246,7 +1290,7 @@ class VadRuntime:
                 ct["out"][key] = torch.zeros((max(mc, 1), ld_out) + tailshape, dtype=src.dtype, device=self.device)
             out = ct["out"][key]
             self._check(self.lib.uvad_cuts_gather(self.ctx, src.data_ptr(), row_stride, unit, _lib.CUTS_SAMPLES if which == "samples" else _lib.CUTS_FRAMES,
-                                                  ct["table"].data_ptr(), ct["total"].data_ptr(), mc, out.data_ptr(), ld_out,
+                                                  (ct["table"] if table is None else table).data_ptr(), ct["total"].data_ptr(), mc, out.data_ptr(), ld_out,
                                                   ct["out_len"].data_ptr(), self._stream()))
             ct["_keep_src"] = src
             return out[:mc], ct["out_len"][:mc]
@@ -1350,6 +1394,120 @@ class VadRuntime:
             return {"pairs_per_cut": [pairs[min(int(first[i]), stored):min(int(first[i + 1]), stored)].tolist() for i in range(m)],
                     "total_pairs": total, "stored_pairs": stored, "item_cuts": jn["item_cuts"][:, :jn["max_iv"]].cpu().numpy().copy(),
                     "audit": {"rows": named[:-1], "pooled": named[-1]}, "audit_words": words}
+
+    # ------------------------------------------------------------------ channel fusion (uvad_fuse_*)
+    FUSE_MODES = {"max": _lib.FUSE_MAX, "mean": _lib.FUSE_MEAN, "vote": _lib.FUSE_VOTE}
+    FUSE_STAT_NAMES = ("valid", "speech", "agree", "best")     # the four uint64 words per member slot of d_stats, in order
+
+    def _fuse_configure(self, st):
+        """Make `st` the context's fusion configuration (one per context: the last fuse_open, or the state a call names)."""
+        if getattr(self, "_fuse_current", None) is st:
+            return
+        first, members, w = st["first"], st["members"], st["weights"]
+        self._check(self.lib.uvad_fuse_configure(self.ctx, C.byref(st["cfg"]), first.ctypes.data, members.ctypes.data,
+                                                 w.ctypes.data if w is not None else None, st["G"]))
+        self._fuse_current = st
+
+    def fuse_open(self, groups, **cfg):
+        """The configuration and the buffers of the fusion calls below.  groups: one list of input rows per recording (rows need not be
+        contiguous and may appear in several groups); **cfg: mode "max" / "mean" / "vote", threshold, decide, weights, as
+        postprocess.fuse_config, which validates them.  The configuration is uploaded into the context (uvad_fuse_configure); the
+        context holds one, so a call on another state re-configures first.  Buffers are sized by the first call with a shape; after that
+        the calls allocate nothing and can be captured.  st["stats"] (N, 4) int64 accumulates over calls until fuse_reset_stats."""
+        from .postprocess import fuse_config
+        q = fuse_config(groups=groups, **cfg)
+        first = np.zeros(len(q["groups"]) + 1, np.int32)
+        first[1:] = np.cumsum([len(g) for g in q["groups"]])
+        members = np.ascontiguousarray(np.concatenate([np.asarray(g, np.int32) for g in q["groups"]]))
+        w = None if q["weights"] is None else np.ascontiguousarray(np.concatenate([np.asarray(v, np.float32) for v in q["weights"]]))
+        st = {"cfg": _lib.FuseCfg(self.FUSE_MODES[q["mode"]], float(q["threshold"]), float(q["decide"])), "config": q,
+              "groups": q["groups"], "first": first, "members": members, "weights": w, "G": len(q["groups"]), "N": int(first[-1]),
+              "fused": None, "glens": None, "labels": None, "best": None, "flags": None, "ws": None}
+        with torch.cuda.device(self.device):
+            st["stats"] = torch.zeros((st["N"], _lib.FUSE_STATS_WORDS), dtype=torch.int64, device=self.device)
+            self._fuse_configure(st)
+        return st
+
+    def fuse_reset_stats(self, state):
+        state["stats"].zero_()
+
+    def _fuse_buffers(self, st, T: int, labels: bool, best: bool, flags: bool):
+        G = st["G"]
+        if st["fused"] is None or tuple(st["fused"].shape) != (G, T):
+            st["fused"] = torch.zeros((G, T), dtype=torch.float32, device=self.device)
+            st["glens"] = torch.zeros(G, dtype=torch.int32, device=self.device)
+            st["labels"] = st["best"] = None
+        if labels and st["labels"] is None:
+            st["labels"] = torch.zeros((G, T), dtype=torch.uint8, device=self.device)
+        if best and st["best"] is None:
+            st["best"] = torch.zeros((G, T), dtype=torch.uint8, device=self.device)
+        if flags and st["flags"] is None:
+            st["flags"] = torch.zeros(G, dtype=torch.uint8, device=self.device)
+
+    def _fuse_enqueue(self, st, in_ptr, ld_in, B, T, lens_ptr, flags_ptr, labels: bool, best: bool, stats: bool = True):
+        return self.lib.uvad_fuse(self.ctx, in_ptr, ld_in, B, T, lens_ptr, flags_ptr, st["fused"].data_ptr(), st["fused"].shape[1],
+                                  st["glens"].data_ptr(), st["flags"].data_ptr() if flags_ptr is not None else None,
+                                  st["labels"].data_ptr() if labels else None, T, st["best"].data_ptr() if best else None, T,
+                                  st["stats"].data_ptr() if stats else None, st["ws"].data_ptr(), st["ws"].numel(), self._stream())
+
+    def fuse(self, probs: "torch.Tensor", lengths=None, state=None, labels: bool = True, best: bool = True, **cfg):
+        """probs (B, T) f32 on the GPU, one row per channel (row-strided views are used as they are; logits do as well), lengths (B,)
+        valid frames per row (a device tensor is read on the device).  state: one of fuse_open; without it one is opened from **cfg
+        (groups=...).  -> (fused (G, T) f32, glens (G,) int32, labels (G, T) uint8 or None, best (G, T) uint8 or None, stats (N, 4) int64
+        {valid, speech, agree, best} per member slot, accumulated over the calls on the state), on the device and overwritten by the next
+        call on the state.  Columns at or past a group's length keep what they held (zero in a fresh state).  fuse_read gives the stats
+        on the host."""
+        st = state if state is not None else self.fuse_open(**cfg)
+        with torch.cuda.device(self.device):
+            if not torch.is_tensor(probs) or probs.device != self.device:
+                raise RuntimeError(f"probs must be a tensor on {self.device}")
+            probs = self._rows_2d(probs, torch.float32, "probs")
+            B, T = probs.shape
+            if B <= int(st["members"].max()):
+                raise ValueError(f"probs has {B} rows, the groups name row {int(st['members'].max())}")
+            n = None if lengths is None else self._dev_lens(lengths, B, T, torch.int32, "lengths (frames)")
+            self._fuse_configure(st)
+            self._fuse_buffers(st, T, labels, best, False)
+            need = int(self.lib.uvad_fuse_ws_bytes(self.ctx, B, T))
+            if st["ws"] is None or st["ws"].numel() < need:
+                st["ws"] = torch.zeros(max(need, 16), dtype=torch.uint8, device=self.device)
+            self._check(self._fuse_enqueue(st, probs.data_ptr(), probs.stride(0) if B > 1 else max(probs.stride(0), T), B, T,
+                                           n.data_ptr() if n is not None else None, None, labels, best))
+            st["_keep"] = (probs, n)   # the launch reads them after this call returns
+            return st["fused"], st["glens"], st["labels"] if labels else None, st["best"] if best else None, st["stats"]
+
+    def fuse_pick(self, best: "torch.Tensor", cuts, state=None):
+        """The channel of each cut (uvad_fuse_pick): best (G, T) uint8 as fuse wrote it, cuts a state of cuts_open on which cuts_table
+        has run on the fused labels.  -> (table (max_cuts, 8) int32, the cut table with each row replaced by the picked member's input
+        row -- pass it to cuts_gather(..., table=) with the (B, S) audio rows --, picks (max_cuts,) int32, the position within the
+        group; -1 for a cut whose row is no group), on the device, kept on the state and overwritten by the next call."""
+        ct = cuts
+        if ct.get("table") is None:
+            raise RuntimeError("fuse_pick needs a state on which cuts_table has run")
+        with torch.cuda.device(self.device):
+            if not torch.is_tensor(best) or best.device != self.device:
+                raise RuntimeError(f"best must be a tensor on {self.device}")
+            best = self._rows_2d(best, torch.uint8, "best")
+            if state is not None:
+                self._fuse_configure(state)
+            mc = ct["max_cuts"]
+            if ct.get("pick_table") is None or ct["pick_table"].shape[0] != max(mc, 1):
+                ct["pick_table"] = torch.zeros((max(mc, 1), 8), dtype=torch.int32, device=self.device)
+                ct["pick"] = torch.zeros(max(mc, 1), dtype=torch.int32, device=self.device)
+            self._check(self.lib.uvad_fuse_pick(self.ctx, best.data_ptr(), best.stride(0) if best.shape[0] > 1 else max(best.stride(0), best.shape[1]),
+                                                ct["table"].data_ptr() if mc else None, ct["total"].data_ptr(), mc,
+                                                ct["pick_table"].data_ptr(), ct["pick"].data_ptr(), self._stream()))
+            ct["_keep_best"] = best
+            return ct["pick_table"][:mc], ct["pick"][:mc]
+
+    def fuse_read(self, state):
+        """The counters accumulated on the state, copied to the host (synchronises): per group a list with one dict {valid, speech,
+        agree, best} per member, in slot order."""
+        with torch.cuda.device(self.device):
+            words = state["stats"].cpu().numpy()
+        first = state["first"]
+        return [[{name: int(words[j, k]) for k, name in enumerate(self.FUSE_STAT_NAMES)} for j in range(first[g], first[g + 1])]
+                for g in range(state["G"])]
 
     # ------------------------------------------------------------------ hysteresis decisions with minimum durations (uvad_binarize)
     def binarize_open(self, onset: float = 0.5, offset=None, min_on: int = 0, min_off: int = 0, pad_on: int = 0, pad_off: int = 0, max_iv=None):

@@ -103,7 +103,7 @@ def _wav_recordings(path: str, channels: str, rt, sample_rate: int = 16000):
     except (wave.Error, EOFError):
         plain = False
     if plain:
-        return [{"id": rid + ("-ch0" if channels == "all" else ""), "pcm": read_wav_int16(path, sample_rate)}]
+        return [{"id": rid + ("-ch0" if channels == "all" else ""), "pcm": read_wav_int16(path, sample_rate), "file": rid, "channel": 0}]
     raw, (encoding, nch, rate) = read_audio(path)
     ig = getattr(rt, "_ingest", None) or {}
     if (ig.get("encoding"), ig.get("channels"), ig.get("sample_rate")) != (encoding, nch, rate):   # files of one kind configure once
@@ -112,8 +112,8 @@ def _wav_recordings(path: str, channels: str, rt, sample_rate: int = 16000):
     # and each batch is uploaded again -- one extra round trip per file, kept so that both kinds of recording share one batching path
     rows = rt.ingest(torch.from_numpy(raw[None]).to(rt.device)).cpu().numpy()
     if channels == "first":
-        return [{"id": rid, "pcm": rows[0]}]
-    return [{"id": f"{rid}-ch{c}", "pcm": rows[c]} for c in range(nch)]
+        return [{"id": rid, "pcm": rows[0], "file": rid, "channel": 0}]
+    return [{"id": f"{rid}-ch{c}", "pcm": rows[c], "file": rid, "channel": c} for c in range(nch)]
 
 
 def _resolve_device(name: str) -> torch.device:
@@ -213,7 +213,8 @@ def _join_items(source, rec_ids, nsamp, frames, sincnet, shift, sr):
     return iv, np.asarray([len(r) for r in rows], np.int32), [[it[2] if len(it) > 2 else None for it in r] for r in rows]
 
 
-def _attach_cuts(results, recs, dev_labels, rt, cuts, sincnet, frame_shift, device, max_samples, sr=16000, supervisions=None, alignments=None):
+def _attach_cuts(results, recs, dev_labels, rt, cuts, sincnet, frame_shift, device, max_samples, sr=16000, supervisions=None, alignments=None,
+                 dev_best=None):
     """predict_vad(cuts=...): the tail of the reference's get_new_cuts on the device.  results[i], recs[i] and dev_labels[i] (the
     recording's whole-row labels, a 1-D tensor on the GPU, or None when it has no frame) belong together.  Recordings are grouped within
     the max_duration budget; a group is one uvad_cuts_table call on its padded label rows, and its table is the only thing that crosses
@@ -222,9 +223,13 @@ def _attach_cuts(results, recs, dev_labels, rt, cuts, sincnet, frame_shift, devi
     With supervisions and / or alignments ({recording_id: path or [(start_s, end_s, text)]}) each group also runs uvad_cuts_join on its
     table, on the device -- supervisions by overlap, an alignment's words by containment -- and every cut becomes a dict {"start", "end",
     "first_sample", "n_samples", "supervisions": indices into the recording's list, "text"} (with alignments also "words", whose text
-    replaces the supervisions' for a recording that has an alignment), every result gains "audit": the reference's seven counters for that recording (postprocess.join_report prints them)."""
+    replaces the supervisions' for a recording that has an alignment), every result gains "audit": the reference's seven counters for that recording (postprocess.join_report prints them).
+    With dev_best (predict_vad(fuse=...): per result the best-channel row uvad_fuse wrote, on the GPU; recs[i]["channels"] the audio of
+    every channel) one uvad_fuse_pick on each group's table names the channel of each cut, the audio written is gathered from that
+    channel's row, and every cut is a dict with "channel"."""
     from .postprocess import cut_transcripts
     join = supervisions is not None or alignments is not None
+    fused = dev_best is not None
     unknown = set(cuts) - set(CUTS_DEFAULTS)
     if unknown:
         raise ValueError(f"unknown cuts option(s) {sorted(unknown)} (known: {sorted(CUTS_DEFAULTS)})")
@@ -251,6 +256,15 @@ def _attach_cuts(results, recs, dev_labels, rt, cuts, sincnet, frame_shift, devi
         ct = rt.cuts_open(**cfg)
         rt.cuts_table(lab, lengths=frames, nsamp=nsamp, S=S, cuts=ct)
         tab = rt.cuts_read(ct)
+        picks = ptab = None
+        if fused:   # the channel of each cut: one more launch on the table where it lies; the group's channels are rows base .. base + C
+            base = np.concatenate([[0], np.cumsum([len(recs[i]["channels"]) for i in idx])]).astype(int)
+            best = torch.zeros((len(idx), T), dtype=torch.uint8, device=device)
+            for r, i in enumerate(idx):
+                best[r, :dev_best[i].numel()] = dev_best[i]
+            fz = rt.fuse_open([list(range(base[r], base[r + 1])) for r in range(len(idx))])
+            ptab, pk = rt.fuse_pick(best, ct, state=fz)
+            picks = pk[:len(tab)].cpu().numpy()
         joined = {}
         for name, source, mode in (("supervisions", supervisions, "overlap"), ("words", alignments, "inside")):
             if source is not None:   # one more launch on the table where it lies; the pair lists and eight counters a row cross to the host
@@ -259,20 +273,24 @@ def _attach_cuts(results, recs, dev_labels, rt, cuts, sincnet, frame_shift, devi
                 joined[name] = (rt.cuts_join_read(ct), texts, [recs[i]["id"] in source for i in idx])
         batch = lens = None
         if opt["write_dir"] and len(tab):
-            mixed = len({recs[i]["pcm"].dtype for i in idx}) > 1
-            i16 = not mixed and recs[idx[0]]["pcm"].dtype == np.int16
-            x = torch.zeros((len(idx), S), dtype=torch.int16 if i16 else torch.float32, device=device)
-            for r, i in enumerate(idx):
-                row = torch.from_numpy(np.array(recs[i]["pcm"])).to(device)
-                x[r, :nsamp[r]] = row.float() / 32768.0 if mixed and row.dtype == torch.int16 else row
-            batch, lens = rt.cuts_gather(x, ct, "samples", ld_out=-(-max(int(tab["n_samples"].max()), 1) // 8) * 8, rows=len(tab))
+            audio = [(r, pcm) for r, i in enumerate(idx) for pcm in (recs[i]["channels"] if fused else [recs[i]["pcm"]])]   # (row of idx, samples)
+            mixed = len({pcm.dtype for _, pcm in audio}) > 1
+            i16 = not mixed and audio[0][1].dtype == np.int16
+            x = torch.zeros((len(audio), S), dtype=torch.int16 if i16 else torch.float32, device=device)
+            for k, (r, pcm) in enumerate(audio):
+                row = torch.from_numpy(np.array(pcm)).to(device)
+                x[k, :nsamp[r]] = row.float() / 32768.0 if mixed and row.dtype == torch.int16 else row
+            batch, lens = rt.cuts_gather(x, ct, "samples", ld_out=-(-max(int(tab["n_samples"].max()), 1) // 8) * 8, rows=len(tab), table=ptab)
             batch, lens = batch.cpu().numpy(), lens.cpu().numpy()
         for k, c in enumerate(tab):
             res = results[idx[int(c["row"])]]
             f, nf = int(c["first_frame"]), int(c["n_frames"])
             entry = (round(f * shift, 6), round((f + nf) * shift, 6), int(c["first_sample"]), int(c["n_samples"]))
-            if join:
+            if join or fused:
                 entry = dict(zip(("start", "end", "first_sample", "n_samples"), entry))
+            if fused:
+                entry["channel"] = int(picks[k])
+            if join:
                 for name, (read, texts, listed) in joined.items():
                     entry[name] = read["pairs_per_cut"][k]
                     if "text" not in entry or listed[int(c["row"])]:   # the words supply the text of a recording that has an alignment
@@ -335,7 +353,8 @@ def sliding_geometry(rt, sincnet: bool, window_seconds: float, hop_seconds: floa
     return W, Hf
 
 
-def _predict_sliding(recs, rt, sincnet, kwargs, window_s, hop_s, frame_shift, med_window, device, sr=16000, dev_labels=None, binarize=None):
+def _predict_sliding(recs, rt, sincnet, kwargs, window_s, hop_s, frame_shift, med_window, device, sr=16000, dev_labels=None, binarize=None,
+                     dev_probs=None):
     """predict_vad with hop_seconds: whole recordings as ragged [R][S_max] batches within the max_duration budget, overlapping windows
     aggregated on the device (uvad_sliding_forward[_wav][_i16]), then the lens median filter and run-length kernels on the frame counts
     the call returned.  Every recording is copied into its row of the device batch by itself: nothing is stacked on the host."""
@@ -374,7 +393,52 @@ def _predict_sliding(recs, rt, sincnet, kwargs, window_s, hop_s, frame_shift, me
                           "probs": probs[r, :fr[r]].cpu().numpy(), "intervals": ivs[r]}
             if dev_labels is not None:
                 dev_labels[i] = lab[r, :fr[r]]
+            if dev_probs is not None:
+                dev_probs[i] = probs[r, :fr[r]]
     return results
+
+
+def _fuse_recordings(results, recs, dev_probs, rt, fuse, binarize, sincnet, frame_shift, med_window, device, sr=16000):
+    """predict_vad(fuse=...): the channel rows of each file put back together on the device.  results[i], recs[i] and dev_probs[i] (the
+    channel's probabilities, a 1-D tensor on the GPU, or None when it has no frame) belong together; recs carry "file" and "channel".
+    One uvad_fuse over all channel rows, one group per file; then the decision on the fused rows as the ragged route decides a whole
+    row: uvad_binarize with binarize=, else the lens median filter and the run walk.  -> (results, recs, dev_labels, dev_best), one
+    entry per file: the result has the id without -chK, "probs" the fused row, "channels" and "channel_stats" (per channel {valid,
+    speech, agree, best} frames); recs[i]["channels"] holds every channel's audio for the cuts."""
+    files = []
+    for i, r in enumerate(recs):
+        if not files or files[-1][0] != r["file"]:
+            files.append((r["file"], []))
+        files[-1][1].append(i)
+    frames = [0 if p is None else int(p.numel()) for p in dev_probs]
+    T = max(max(frames), 1)
+    x = torch.zeros((len(recs), T), dtype=torch.float32, device=device)
+    for i, p in enumerate(dev_probs):
+        if frames[i]:
+            x[i, :frames[i]] = p
+    st = rt.fuse_open([idx for _, idx in files], **{k: v for k, v in fuse.items() if k in ("mode", "threshold", "decide")})
+    fused, glens, _, best, _ = rt.fuse(x, lengths=frames, state=st, labels=False)
+    gl = glens.cpu().tolist()
+    stats = rt.fuse_read(st)
+    nsamp = [max(len(recs[i]["pcm"]) for i in idx) for _, idx in files]
+    if binarize is not None:
+        lab, ivs = _binarize_post(rt, binarize, fused, gl, [n / sr for n in nsamp], sincnet, frame_shift)
+    else:
+        lab = median_filter(fused, window=med_window, runtime=rt, lengths=gl)
+        if sincnet:
+            ivs = [sincnet_labels_to_intervals(lab[g, :gl[g]], nsamp[g] / sr, runtime=rt) if gl[g] else [] for g in range(len(files))]
+        else:
+            ivs = labels_to_intervals_batch(lab, frame_shift, runtime=rt, lengths=gl)
+    out, new_recs, dev_labels, dev_best = [], [], [], []
+    for g, (name, idx) in enumerate(files):
+        L = gl[g]
+        out.append({"recording_id": name, "num_frames": L, "labels": lab[g, :L].cpu().numpy().astype(np.uint8), "probs": fused[g, :L].cpu().numpy(),
+                    "intervals": ivs[g], "channels": len(idx),
+                    "channel_stats": [dict(stats[g][k], channel=recs[i]["channel"]) for k, i in enumerate(idx)]})
+        new_recs.append({"id": name, "pcm": recs[idx[0]]["pcm"], "channels": [recs[i]["pcm"] for i in idx]})
+        dev_labels.append(lab[g, :L] if L else None)
+        dev_best.append(best[g, :L])
+    return out, new_recs, dev_labels, dev_best
 
 
 def predict_vad(**kwargs):
@@ -441,14 +505,29 @@ def predict_vad(**kwargs):
     supervisions, alignments = kwargs.get("supervisions"), kwargs.get("alignments")
     if (supervisions is not None or alignments is not None) and cuts is None:
         raise ValueError("supervisions / alignments are joined with the cuts: pass cuts= as well")
+    fuse = kwargs.get("fuse")   # None: one result per channel row, as ever; a dict (postprocess.fuse_config's mode / threshold / decide): one per file
+    dev_probs = None
+    if fuse is not None:
+        from .postprocess import fuse_config
+        if src["kind"] != "wav" or src.get("channels", "first") != "all":
+            raise ValueError("fuse puts the channels of each file together: it needs input kind 'wav' with channels = 'all'")
+        if set(fuse) - {"mode", "threshold", "decide"}:
+            raise ValueError(f"unknown fuse option(s) {sorted(set(fuse) - {'mode', 'threshold', 'decide'})} (known: mode, threshold, decide; the groups are the files)")
+        fuse = fuse_config(**fuse)
+        dev_probs = [None] * len(recs)
+    dev_best = None
     hop_s = kwargs.get("hop_seconds")
     if hop_s is not None:   # overlapping windows of window_seconds every hop_seconds, aggregated on the device; None: the cuts below, unchanged
         if window_s is None:
             raise ValueError("hop_seconds needs window_seconds (the window the model was trained on)")
-        results = _predict_sliding(recs, net.runtime(device), sincnet, kwargs, window_s, hop_s, frame_shift, med_window, device, sr, dev_labels, binarize)
+        results = _predict_sliding(recs, net.runtime(device), sincnet, kwargs, window_s, hop_s, frame_shift, med_window, device, sr, dev_labels, binarize,
+                                   dev_probs)
+        if fuse is not None:
+            results, recs, dev_labels, dev_best = _fuse_recordings(results, recs, dev_probs, net.runtime(device), fuse, binarize, sincnet, frame_shift,
+                                                                   med_window, device, sr)
         if cuts is not None:
             _attach_cuts(results, recs, dev_labels, net.runtime(device), cuts, sincnet, frame_shift, device, int(kwargs["max_duration"] * sr), sr,
-                         supervisions, alignments)
+                         supervisions, alignments, dev_best)
         return _write_results(results, kwargs)
 
     # ---- batches: pieces of equal length together, at most max_duration seconds of audio per batch; with ragged_batches (whole
@@ -571,6 +650,8 @@ def predict_vad(**kwargs):
                             "probs": piece_probs[j].cpu().numpy(), "intervals": intervals})
             if dev_labels is not None:
                 dev_labels[ri] = labels
+            if dev_probs is not None:
+                dev_probs[ri] = piece_probs[j]
             continue
         probs = torch.cat([piece_probs[j] for j in mine])
         duration = len(r["pcm"]) / sr
@@ -613,8 +694,13 @@ def predict_vad(**kwargs):
                         "probs": probs.cpu().numpy(), "intervals": intervals})
         if dev_labels is not None:
             dev_labels[ri] = labels
+        if dev_probs is not None:
+            dev_probs[ri] = probs
+    if fuse is not None:
+        results, recs, dev_labels, dev_best = _fuse_recordings(results, recs, dev_probs, rt, fuse, binarize, sincnet, frame_shift, med_window, device, sr)
     if cuts is not None:
-        _attach_cuts(results, recs, dev_labels, rt, cuts, sincnet, frame_shift, device, int(kwargs["max_duration"] * sr), sr, supervisions, alignments)
+        _attach_cuts(results, recs, dev_labels, rt, cuts, sincnet, frame_shift, device, int(kwargs["max_duration"] * sr), sr, supervisions, alignments,
+                     dev_best)
     return _write_results(results, kwargs)
 
 
@@ -642,7 +728,7 @@ def test_vad(**kwargs):
     src = kwargs["input"]
     if src.get("kind") != "wav" or len(src.get("labels", ())) != len(src["paths"]):
         raise ValueError('test_vad needs input = {"kind": "wav", "paths": [...], "labels": [one label file per path]}')
-    if src.get("channels", "first") != "first":
+    if src.get("channels", "first") != "first" and kwargs.get("fuse") is None:   # with fuse= the channels are one recording again
         raise ValueError("test_vad scores one recording per file (channels = 'first')")
     sincnet = kwargs["feature_extractor"] == "sincnet"
     results = predict_vad(**kwargs)                        # sorted by recording id
