@@ -1018,6 +1018,73 @@ int uvad_gate_step(uvad_ctx *, const void *d_chunk, int chunk, const uint8_t *d_
                    const uint8_t *d_flags, int B, void *d_state, size_t state_bytes, void *d_out, int64_t ld_out, uvad_gate_seg *d_seg,
                    int max_seg, int32_t *d_seg_counts, void *stream);
 
+/* ---- Live speech gate for fused groups: each cut from its best channel, per step, on the device ------------------------------------------------
+ * The streaming counterpart of uvad_cuts_table (on the fused labels) + uvad_fuse_pick + uvad_cuts_gather(UVAD_CUTS_SAMPLES), as
+ * uvad_gate_step is of the table + gather: it stands behind uvad_fuse and an endpointer over the groups and emits, per group and step, the
+ * speech audio of the group's cuts, each cut taken WHOLE from one member channel.  It replaces the host round trip a multi-microphone
+ * caller otherwise pays behind a fused pool (copy events and best bytes out, keep a PCM history per channel, slice there), and nothing in
+ * the reference (its multi-channel corpora are fused offline: see uvad_fuse).
+ *   Groups: those of the context's uvad_fuse_configure: G groups, N member slots; slot j reads row h_members[j] of d_chunk [B][chunk].
+ *     Position p of group g is slot h_group_first[g] + p.  Reset writes G, N and decide_frames into the state's header; a step against a
+ *     state whose G / N differ from the context's configuration returns UVAD_E_STATE.  As for uvad_fuse, a failed upload keeps the
+ *     validated configuration: every argument refusal below still answers, and reset / step then return UVAD_E_HIP.
+ *   Inputs per step: d_chunk [B][chunk] units, the pool's input buffer; d_best [G][ld_best] with d_best_counts [G]: this step's uvad_fuse
+ *     d_best and d_glens (the first clamp(count, 0, ld_best) bytes of row g are the group's next best bytes); d_labels [G][ld_lab] with
+ *     d_lab_counts [G]: the endpointer's finalised labels, as uvad_gate_step takes them; d_gflags [G] (or NULL: no flags): the group's
+ *     session flags, uvad_fuse's OR-ed d_flags_out, with UVAD_SLOT_START / UVAD_SLOT_END as in uvad_gate_step; d_rflags [B] (or NULL: no
+ *     check): the pool's per-row flag bytes, for the lockstep check below.  The chunk rows, best row, label row and counts of an idle
+ *     group, columns past a count and rows no group names are never read (NaN or junk there changes no output byte).
+ *   The rule: the mode machine, pad, max_len, the END flush, SHORT, LOST, the record order and the n / n_stored / offset semantics are
+ *     uvad_gate_step's, unchanged, on the group's labels; min_len must be 0.  What is new is the channel and when a piece first speaks:
+ *     choice    a piece [f, f + k) -- one uvad_cut -- takes its audio from the member position with the most frames t in
+ *               [f, f + min(k, D)), D = decide_frames >= 1, at which best[g][t] equals that position; ties go to the lowest position; no
+ *               votes: position 0.  This is uvad_fuse_pick's rule on the cut truncated to its first D frames.  A frame at or past the
+ *               best bytes received, or one that has left the best ring, votes for nobody (a best byte at or above the group's size too);
+ *     deferral  a piece delivers nothing until its choice is final: until the end of the first step after which g - f >= D, with g the
+ *               frames known to lie inside the interval (uvad_gate_step's step 3), or the step in which the piece closes.  Its first
+ *               record then carries its whole backlog from max(f hop - lead, 0); later records continue it as uvad_gate_step's do.  Each
+ *               piece a max_len split makes chooses for itself.
+ *     Because the choice reads frames below f + D only, and a record is made only when those are known, the choice -- and with it every
+ *     byte -- does not depend on how the session is cut into steps: a session's fragments concatenated per cut are byte-identical to the
+ *     cuts of uvad_cuts_table on the fused labels, each gathered from the audio row of the member the truncated pick names.  With
+ *     max_len > 0 and D >= max_len no cut is longer than D and that is uvad_cuts_table -> uvad_fuse_pick -> uvad_cuts_gather; with D = 1
+ *     nothing is deferred and the records and sample ranges are uvad_gate_step's on the same labels.  (DESIGN.md 3.23 proves all three.)
+ *   Preconditions for "no UVAD_GATE_LOST, every frame votes" with the sizes below (both hold behind a fused pool): after every step
+ *     F >= floor(A / hop) - lag_frames (uvad_gate_step's), and F <= Fb <= floor(A / hop), with A the samples, F the labels and Fb the best
+ *     bytes the session has received.
+ *   State: one PCM ring of `history` units per member slot (a row that sits in several groups is kept once per slot) and one best ring of
+ *     `best_history` bytes per group, each rounded up to 16 bytes, behind a 256-byte header and 96 bytes per group.
+ *     uvad_gate_group_history = chunk + (lag_frames + pad + D) hop + lead (uvad_gate_history at D = 1) and uvad_gate_group_best_history =
+ *     ceil(chunk / hop) + lag_frames + pad + D are sizes at which, under the preconditions, no sample is lost and every frame of a choice
+ *     window is still in its ring: a piece first delivered in a step has f >= F_before - pad - D + 1.  uvad_gate_group_max_out =
+ *     uvad_gate_max_out + D hop (the one deferred piece adds its backlog) is an ld_out that never truncates; uvad_gate_max_seg holds as it
+ *     is (deferral only removes records).  The three helpers return -1 on a bad argument, uvad_gate_group_state_bytes 0 (also before
+ *     uvad_fuse_configure).
+ *   Outputs: d_out [G][ld_out], d_seg [G][max_seg] and d_seg_counts [G] exactly as uvad_gate_step's with B = G.  Bits 8 .. 15 of
+ *     uvad_gate_seg.flags hold the chosen member position, UVAD_GATE_CHANNEL(flags), the same on every record of a cut.
+ *   Lockstep: a group's members must be stepped together.  With d_rflags, a group whose members' bytes differ in a step is out of
+ *     lockstep: from that step until the session's END every record carries UVAD_GATE_UNSYNC.  The gate otherwise acts on d_gflags as given.
+ *   One launch of one workgroup per group per step; it allocates nothing, never synchronises and uses no atomics; its grid depends on the
+ *   configuration alone, so a graph captured around a step -- alone or in a pool's capture behind the endpointer -- replays for later ones.
+ *   Refusals (UVAD_E_ARG, nothing enqueued, uvad_last_error names the word): uvad_gate_reset's checks on the cfg (min_len != 0 among them),
+ *   unit_bytes and history; decide_frames outside [1, 2^24] (the largest max_len uvad_cuts_table accepts); best_history < 1 or above
+ *   2^31 - 1; chunk < 1 or > 2^24; ld_lab, ld_best, ld_out or max_seg < 0; NULL d_chunk / d_state / d_seg_counts; NULL d_labels or
+ *   d_lab_counts with ld_lab > 0; NULL d_best or d_best_counts with ld_best > 0; d_out NULL with ld_out > 0; d_seg NULL with max_seg > 0;
+ *   B not above the largest configured member index; history below chunk (step); state_bytes below uvad_gate_group_state_bytes.
+ *   UVAD_E_STATE: any call before uvad_fuse_configure; a step on a state never reset, or reset under another G / N. */
+#define UVAD_GATE_UNSYNC 16
+#define UVAD_GATE_CHANNEL(flags) (((flags) >> 8) & 0xff)
+int64_t uvad_gate_group_history(const uvad_cuts_cfg *, int lag_frames, int chunk, int decide_frames);
+int uvad_gate_group_best_history(const uvad_cuts_cfg *, int lag_frames, int chunk, int decide_frames);
+int64_t uvad_gate_group_max_out(const uvad_cuts_cfg *, int ld_lab, int chunk, int decide_frames);
+size_t uvad_gate_group_state_bytes(const uvad_ctx *, const uvad_cuts_cfg *, int unit_bytes, int64_t history, int best_history);
+int uvad_gate_group_reset(uvad_ctx *, void *d_state, size_t state_bytes, const uvad_cuts_cfg *, int unit_bytes, int64_t history,
+                          int best_history, int decide_frames, void *stream);
+int uvad_gate_group_step(uvad_ctx *, const void *d_chunk, int chunk, int B, const uint8_t *d_best, int ld_best, const int32_t *d_best_counts,
+                         const uint8_t *d_labels, int ld_lab, const int32_t *d_lab_counts, const uint8_t *d_gflags, const uint8_t *d_rflags,
+                         void *d_state, size_t state_bytes, void *d_out, int64_t ld_out, uvad_gate_seg *d_seg, int max_seg,
+                         int32_t *d_seg_counts, void *stream);
+
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;
  *   1  (default) f32-accurate on the f16 matrix cores: weights scaled by a power of two and split on the host into THREE

@@ -79,6 +79,7 @@ class BinarizeCfg(C.Structure):  # uvad_binarize_cfg: thresholds and frame count
 
 
 GATE_FIRST, GATE_LAST, GATE_LOST, GATE_SHORT = 1, 2, 4, 8     # uvad_gate_seg.flags
+GATE_UNSYNC = 16                                              # ... of uvad_gate_group_step: the group's members left lockstep
 
 
 class GateSeg(C.Structure):      # uvad_gate_seg: one record of a gate step (32 bytes)
@@ -220,6 +221,14 @@ SIGNATURES = {
     "uvad_gate_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(CutsCfg), C.c_int, C.c_int64, C.c_void_p]),
     "uvad_gate_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "uvad_gate_group_history": (C.c_int64, [C.POINTER(CutsCfg), C.c_int, C.c_int, C.c_int]),
+    "uvad_gate_group_best_history": (C.c_int, [C.POINTER(CutsCfg), C.c_int, C.c_int, C.c_int]),
+    "uvad_gate_group_max_out": (C.c_int64, [C.POINTER(CutsCfg), C.c_int, C.c_int, C.c_int]),
+    "uvad_gate_group_state_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(CutsCfg), C.c_int, C.c_int64, C.c_int]),
+    "uvad_gate_group_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(CutsCfg), C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "uvad_gate_group_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_void_p]),
     "uvad_classify_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_forward_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -264,7 +273,7 @@ _lib = None
 
 def bind(lib):
     """Declare every prototype of SIGNATURES on `lib`.  The ABI number did not move when entries were appended (the ingest stage among
-    them, the endpointer, the scoring stage, the speech cuts, the hysteresis decisions, the hysteresis endpointer, the speech gate, the cut-supervision join and the channel fusion after it), so a library built from an older tree passes the version check: a symbol it lacks is a loud error here, by name."""
+    them, the endpointer, the scoring stage, the speech cuts, the hysteresis decisions, the hysteresis endpointer, the speech gate, the cut-supervision join, the channel fusion and the group gate after it), so a library built from an older tree passes the version check: a symbol it lacks is a loud error here, by name."""
     for name, (res, args) in SIGNATURES.items():
         try:
             fn = getattr(lib, name)

@@ -103,6 +103,8 @@ struct EndpointPool { int B = 0, kernel = 0, pad = 0; float threshold = 0.5f; };
 struct EndpointHystPool { int B = 0, lag = 0; };
 // a speech gate state (uvad_gate_*): what reset fixed (the device header holds the same)
 struct GatePool { int B = 0, unit_bytes = 0, history = 0; };
+// a group gate state (uvad_gate_group_*): what reset fixed, G and N of the fusion configuration it was reset under among it
+struct GateGroupPool { int G = 0, N = 0, unit_bytes = 0, history = 0, best_history = 0; };
 // a scoring state (uvad_score_*): the configuration's n_points and bins at its reset (the device header holds the same)
 struct ScoreState { int n_points = 0, bins = 0; };
 
@@ -114,6 +116,7 @@ struct uvad_ctx {
     std::map<void *, EndpointPool> endpoints;   // ... and of the endpointer states (uvad_endpoint_*)
     std::map<void *, EndpointHystPool> endpoint_hysts;   // ... and of the hysteresis endpointer states (uvad_endpoint_hyst_*)
     std::map<void *, GatePool> gates;           // ... and of the speech gate states (uvad_gate_*)
+    std::map<void *, GateGroupPool> gate_groups;   // ... and of the group gate states (uvad_gate_group_*)
     std::map<void *, ScoreState> scores;        // ... and of the scoring states (uvad_score_*)
     bool has_score = false;                     // uvad_score_configure: operating points, collar, bins, segment (0 replaced by the default)
     uvad_score_cfg sq{};
@@ -3483,6 +3486,104 @@ int uvad_gate_step(uvad_ctx *c, const void *d_chunk, int chunk, const uint8_t *d
     a.seg_counts = d_seg_counts;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, launch_gate_step(a, g.unit_bytes, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+// ---- the live speech gate for fused groups (gate_group.hip) ------------------------------------------------------------------------------------
+static bool gate_group_args_ok(const uvad_cuts_cfg *q, int lag_frames, int chunk, int decide) {
+    return !gate_cfg_error(q) && lag_frames >= 0 && chunk >= 1 && chunk <= GATE_MAX_CHUNK && decide >= 1 && decide <= CUTS_MAX_LEN;
+}
+static const char *gate_group_size_error(int unit_bytes, int64_t history, int64_t best_history) {
+    if (const char *w = gate_size_error(1, unit_bytes, history)) return w;
+    if (best_history < 1 || best_history > 0x7fffffffll) return "best_history must lie in [1, 2^31 - 1] frames";
+    return nullptr;
+}
+
+int64_t uvad_gate_group_history(const uvad_cuts_cfg *q, int lag_frames, int chunk, int decide) {
+    if (!gate_group_args_ok(q, lag_frames, chunk, decide)) return -1;
+    return (int64_t)chunk + ((int64_t)lag_frames + q->pad + decide) * q->hop + q->lead;   // below 2^63, as uvad_gate_history
+}
+
+int uvad_gate_group_best_history(const uvad_cuts_cfg *q, int lag_frames, int chunk, int decide) {
+    if (!gate_group_args_ok(q, lag_frames, chunk, decide)) return -1;
+    const int64_t v = ((int64_t)chunk + q->hop - 1) / q->hop + lag_frames + q->pad + decide;
+    return v > 0x7fffffffll ? -1 : (int)v;
+}
+
+int64_t uvad_gate_group_max_out(const uvad_cuts_cfg *q, int ld_lab, int chunk, int decide) {
+    if (gate_cfg_error(q) || decide < 1 || decide > CUTS_MAX_LEN) return -1;
+    const int64_t base = uvad_gate_max_out(q, ld_lab, chunk, chunk);   // it does not depend on the history, which is only checked
+    if (base < 0) return -1;
+    const int64_t extra = (int64_t)decide * q->hop;                    // below 2^55
+    return base > INT64_MAX - extra ? INT64_MAX : base + extra;
+}
+
+size_t uvad_gate_group_state_bytes(const uvad_ctx *c, const uvad_cuts_cfg *q, int unit_bytes, int64_t history, int best_history) {
+    if (!c || !c->has_fuse || gate_cfg_error(q) || gate_group_size_error(unit_bytes, history, best_history)) return 0;
+    return gate_group_state_bytes(c->fz_G, c->fz_N, unit_bytes, history, best_history);
+}
+
+int uvad_gate_group_reset(uvad_ctx *c, void *d_state, size_t state_bytes, const uvad_cuts_cfg *q, int unit_bytes, int64_t history,
+                          int best_history, int decide, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!c->has_fuse) return fail(c, UVAD_E_STATE, "uvad_gate_group_reset: uvad_fuse_configure has not been called");
+    if (const char *w = gate_cfg_error(q)) return fail(c, UVAD_E_ARG, std::string("uvad_gate_group_reset: ") + w);
+    if (const char *w = gate_group_size_error(unit_bytes, history, best_history)) return fail(c, UVAD_E_ARG, std::string("uvad_gate_group_reset: ") + w);
+    if (decide < 1 || decide > CUTS_MAX_LEN) return fail(c, UVAD_E_ARG, "uvad_gate_group_reset: decide_frames must lie in [1, 2^24] frames");
+    if (!d_state) return fail(c, UVAD_E_ARG, "uvad_gate_group_reset: d_state is NULL");
+    const size_t need = gate_group_state_bytes(c->fz_G, c->fz_N, unit_bytes, history, best_history);
+    if (state_bytes < need) return fail(c, UVAD_E_ARG, "uvad_gate_group_reset: state_bytes too small: need " + std::to_string(need) + " bytes");
+    if (!c->fz_on_device)
+        return fail(c, UVAD_E_HIP, "uvad_gate_group_reset: the configuration is not on the device (uvad_fuse_configure's upload failed)");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_gate_group_reset(d_state, c->fz_G, c->fz_N, cuts_cfg_of(q), unit_bytes, (int)history, best_history, decide, (hipStream_t)stream));
+    GateGroupPool g;
+    g.G = c->fz_G; g.N = c->fz_N; g.unit_bytes = unit_bytes; g.history = (int)history; g.best_history = best_history;
+    c->gate_groups[d_state] = g;
+    return UVAD_OK;
+}
+
+int uvad_gate_group_step(uvad_ctx *c, const void *d_chunk, int chunk, int B, const uint8_t *d_best, int ld_best, const int32_t *d_best_counts,
+                         const uint8_t *d_labels, int ld_lab, const int32_t *d_lab_counts, const uint8_t *d_gflags, const uint8_t *d_rflags,
+                         void *d_state, size_t state_bytes, void *d_out, int64_t ld_out, uvad_gate_seg *d_seg, int max_seg,
+                         int32_t *d_seg_counts, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!c->has_fuse) return fail(c, UVAD_E_STATE, "uvad_gate_group_step: uvad_fuse_configure has not been called");
+    if (B <= c->fz_max_member)
+        return fail(c, UVAD_E_ARG, "uvad_gate_group_step: B must be above the largest configured member index (" + std::to_string(c->fz_max_member) + ")");
+    if (chunk < 1 || chunk > GATE_MAX_CHUNK) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: chunk must lie in [1, 2^24] samples");
+    if (ld_lab < 0) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: ld_lab must be >= 0");
+    if (ld_best < 0) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: ld_best must be >= 0");
+    if (ld_out < 0) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: ld_out must be >= 0");
+    if (max_seg < 0) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: max_seg must be >= 0");
+    if (!d_chunk) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_chunk is NULL");
+    if (!d_state) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_state is NULL");
+    if (!d_seg_counts) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_seg_counts is NULL");
+    if (ld_lab > 0 && !d_labels) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_labels is NULL with ld_lab > 0");
+    if (ld_lab > 0 && !d_lab_counts) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_lab_counts is NULL with ld_lab > 0");
+    if (ld_best > 0 && !d_best) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_best is NULL with ld_best > 0");
+    if (ld_best > 0 && !d_best_counts) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_best_counts is NULL with ld_best > 0");
+    if (ld_out > 0 && !d_out) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_out is NULL with ld_out > 0");
+    if (max_seg > 0 && !d_seg) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_seg is NULL with max_seg > 0");
+    auto it = c->gate_groups.find(d_state);
+    if (it == c->gate_groups.end()) return fail(c, UVAD_E_STATE, "uvad_gate_group_step: call uvad_gate_group_reset on this state first");
+    const GateGroupPool &g = it->second;
+    if (g.G != c->fz_G || g.N != c->fz_N)
+        return fail(c, UVAD_E_STATE, "uvad_gate_group_step: the state was reset under a configuration of G = " + std::to_string(g.G) + ", N = " +
+                                         std::to_string(g.N));
+    if (g.history < chunk) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: history " + std::to_string(g.history) + " is below chunk");
+    const size_t need = gate_group_state_bytes(g.G, g.N, g.unit_bytes, g.history, g.best_history);
+    if (state_bytes < need) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: state_bytes too small: need " + std::to_string(need) + " bytes");
+    if (!c->fz_on_device)
+        return fail(c, UVAD_E_HIP, "uvad_gate_group_step: the configuration is not on the device (uvad_fuse_configure's upload failed)");
+    GateGroupArgs a{};
+    a.first = c->d_fz; a.members = c->d_fz + c->fz_G + 1; a.G = c->fz_G; a.N = c->fz_N;
+    a.chunk = d_chunk; a.chunk_n = chunk; a.B = B; a.best = d_best; a.ld_best = ld_best; a.best_counts = d_best_counts;
+    a.labels = d_labels; a.ld_lab = ld_lab; a.lab_counts = d_lab_counts; a.gflags = d_gflags; a.rflags = d_rflags;
+    a.state = d_state; a.out = d_out; a.ld_out = ld_out; a.seg = reinterpret_cast<GateSeg *>(d_seg); a.max_seg = max_seg;
+    a.seg_counts = d_seg_counts;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_gate_group_step(a, g.unit_bytes, (hipStream_t)stream));
     return UVAD_OK;
 }
 

@@ -690,4 +690,45 @@ constexpr size_t gate_state_bytes(int B, int unit_bytes, long long history) {
 hipError_t launch_gate_reset(void *state, int B, const CutsCfgInt &q, int unit_bytes, int history, hipStream_t s);
 hipError_t launch_gate_step(const GateArgs &a, int unit_bytes, hipStream_t s);   // unit_bytes: the reset's, it picks the copy's granule
 
+// ---- gate_group.hip: the live speech gate for fused groups (uvad_gate_group_*, include/uvad.h): each cut from the channel that heard it best ----
+// The state is a header (what reset fixed: G and N of the fusion configuration, the uvad_cuts_cfg, the unit size, the two ring lengths and
+// the decision horizon), one GateGroupSlot per group, one ring of `best_history` bytes per group, then one ring of `history` units per
+// MEMBER SLOT (a row that sits in several groups is kept once per slot); every ring is rounded up to 16 bytes.  The rings of a group's
+// members share the group's write position: its members receive the same chunk count every step.
+constexpr unsigned GATE_GROUP_MAGIC = 0x55564747u;    // "UVGG"
+constexpr int GATE_GROUP_THREADS = 256;               // one workgroup per group
+constexpr int GATE_GROUP_UNSYNC = 16;                 // UVAD_GATE_UNSYNC
+struct GateGroupHeader {
+    unsigned magic; int G, N; CutsCfgInt q; int unit_bytes, history, best_history, decide, reserved0;
+    long long ring_bytes, best_bytes; int reserved[46];
+};                    // 256 bytes
+struct GateGroupSlot {
+    long long A;      // samples of the session so far (of every member)
+    long long sent;   // samples of the current piece delivered so far
+    long long Fb;     // `best` bytes of the session so far
+    int F, c, pf, idx, mode;   // as GateSlot
+    int started;      // 1 once the current piece has a record, which is when its channel was chosen
+    int live;
+    int wp;           // the PCM rings' write position, 0 .. history - 1; it runs on across sessions
+    int bwp;          // the best ring's write position, 0 .. best_history - 1; it runs on across sessions
+    int ch;           // started: the member position the current piece takes its audio from
+    int unsync;       // 1 from the step in which the members' flag bytes differed to the session's END
+    int reserved[7];
+};                    // 96 bytes
+struct GateGroupArgs {
+    const int *first, *members; int G, N;             // the fusion configuration on the device
+    const void *chunk; int chunk_n, B;
+    const uint8_t *best; int ld_best; const int *best_counts;
+    const uint8_t *labels; int ld_lab; const int *lab_counts; const uint8_t *gflags, *rflags;
+    void *state; void *out; long long ld_out; GateSeg *seg; int max_seg; int *seg_counts;
+};
+constexpr size_t gate_group_best_bytes(long long best_history) { return ((size_t)best_history + 15) / 16 * 16; }
+constexpr size_t gate_group_state_bytes(int G, int N, int unit_bytes, long long history, long long best_history) {
+    return sizeof(GateGroupHeader) + (size_t)G * (sizeof(GateGroupSlot) + gate_group_best_bytes(best_history)) +
+           (size_t)N * gate_ring_bytes(unit_bytes, history);
+}
+hipError_t launch_gate_group_reset(void *state, int G, int N, const CutsCfgInt &q, int unit_bytes, int history, int best_history, int decide,
+                                   hipStream_t s);
+hipError_t launch_gate_group_step(const GateGroupArgs &a, int unit_bytes, hipStream_t s);
+
 }  // namespace uvad

@@ -477,3 +477,24 @@ def fuse_config(mode="max", threshold=0.5, decide=None, groups=None, weights=Non
                 raise ValueError(f"the fuse weights of group {i} sum to 0")
         out["weights"] = ws
     return out
+
+
+GROUP_GATE_KEYS = ("decide_frames", "pad", "max_len", "hop", "lead", "tail", "lag_frames", "history", "best_history", "ld_out", "max_seg")
+
+
+def group_gate_config(group_gate, fuse=None, endpoint=None) -> dict:
+    """A validated `group_gate=` of the slot pools (VadRuntime.window_slots_open): a dict with decide_frames (required, 1 .. 2^24: the
+    frames of a cut that choose its channel) and any of pad, max_len, hop, lead, tail, lag_frames, history, best_history, ld_out,
+    max_seg.  The group gate stands behind the fusion and an endpointer, so it needs fuse= and endpoint=."""
+    if not isinstance(group_gate, dict):
+        raise ValueError(f"group_gate must be a dict with decide_frames, got {group_gate!r}")
+    if fuse is None or endpoint is None:
+        raise ValueError("group_gate needs fuse= and endpoint=: it reads the fusion's best bytes and the labels an endpointer finalises")
+    extra = set(group_gate) - set(GROUP_GATE_KEYS)
+    if extra:
+        raise ValueError(f"unknown group_gate parameters {sorted(extra)} {GROUP_GATE_KEYS}")
+    D = group_gate.get("decide_frames")
+    if isinstance(D, bool) or not isinstance(D, (int, np.integer)) or not 1 <= D <= 1 << 24:
+        raise ValueError(f"group_gate needs decide_frames, an integer in [1, 2^24], got {D!r}")
+    out = {k: int(v) for k, v in group_gate.items() if v is not None}
+    return out

@@ -727,6 +727,10 @@ class VadRuntime:
                 r = step(ep, p_ptr, c_ptr, f_ptr)
             if r == 0 and st.get("gate") is not None:   # ... and the gate behind it: the pool's chunk, the endpointer's labels, the same flags
                 r = self._gate_enqueue(st["gate"], src.data_ptr(), ep["labels"].data_ptr(), ep["lab_counts"].data_ptr(), fp)
+            if r == 0 and st.get("group_gate") is not None:   # ... or the group gate: the pool's chunk, the fusion's best bytes, group lengths
+                # and OR-ed flags, the endpointer's labels, and the rows' own flag bytes for the lockstep check
+                r = self._gate_group_enqueue(st["group_gate"], src.data_ptr(), B, fz["best"].data_ptr(), fz["best"].shape[1], fz["glens"].data_ptr(),
+                                             ep["labels"].data_ptr(), ep["lab_counts"].data_ptr(), f_ptr, fp)
             return r
 
         if st["graphs"] is None:
@@ -759,8 +763,8 @@ class VadRuntime:
         the fused rows, the group counts and the OR-ed flags.  st["fuse"] holds fused / glens / best / flags, overwritten by the next
         step, and stats, accumulated over the steps (fuse_read).  The members of a group must be stepped in lockstep: the same START /
         END flags and so the same counts every step -- which holds for the channels of one stream through ingest_step.  Opening or using
-        another fusion state on this runtime re-configures the context: the pool configures it back at its next step.  Not built: gate=
-        behind a fused pool (the gate would need a channel choice per fragment)."""
+        another fusion state on this runtime re-configures the context: the pool configures it back at its next step.  gate= behind a
+        fused pool is refused (the mono gate has no channel choice per fragment): group_gate= (_slots_group_gate) is the gate of a fused pool."""
         if fuse is None:
             return None
         if gate is not None:
@@ -779,7 +783,7 @@ class VadRuntime:
         fz["ws"] = torch.zeros(max(need, 16), dtype=torch.uint8, device=self.device)
         return fz
 
-    def _slots_endpoint(self, st, endpoint, gate=None, geometry=None, fuse=None):
+    def _slots_endpoint(self, st, endpoint, gate=None, geometry=None, fuse=None, group_gate=None):
         """endpoint: None, {"kernel", "pad", "threshold"} (any subset) for the median endpointer (endpoint_open), or {"onset", "offset",
         "min_on", "min_off", "pad_on", "pad_off"} (any non-empty subset; binarize_config's dict as it is) for the hysteresis endpointer
         (endpoint_hyst_open).  The pool gets a probabilities buffer and an endpointer over its B slots whose step is enqueued right behind
@@ -807,7 +811,28 @@ class VadRuntime:
                                                                                   **endpoint)
         if gate is not None:
             st["gate"] = self._slots_gate(st, dict(gate), geometry)
+        if group_gate is not None:
+            st["group_gate"] = self._slots_group_gate(st, group_gate, geometry)
         return st
+
+    def _slots_group_gate(self, st, group_gate, geometry):
+        """group_gate: {"decide_frames": D, ...} with any of _slots_gate's keys and best_history (postprocess.group_gate_config).  The gate
+        of a fused pool (gate_group_open): per group and step the speech audio of the group's cuts, each cut whole from the member that
+        won most of its first D frames.  hop / lead / tail default to the pool's geometry, lag_frames as _slots_gate computes it, the two
+        histories to the derived ones.  Its step is enqueued behind the endpointer's -- inside the one capture under graphs=True -- on
+        the pool's input buffer, the fusion's best bytes, group lengths and OR-ed flags, the endpointer's labels and counts, and the
+        pool's flag bytes (the lockstep check).  st["group_gate"] holds out / seg / seg_counts, overwritten by the next step
+        (gate_group_collect reads them)."""
+        from .postprocess import group_gate_config
+        q = group_gate_config(group_gate, st.get("fuse"), st.get("endpoint"))
+        hop, lead, tail = geometry
+        ep = st["endpoint"]
+        ep_lag = ep["lag"] if "lag" in ep else ep["kernel"] // 2
+        q.setdefault("hop", hop)
+        q.setdefault("lead", lead)
+        q.setdefault("tail", tail)
+        lag = q.pop("lag_frames", st["lookahead"] + ep_lag + -(-tail // hop))
+        return self.gate_group_open(st["fuse"], st["chunk"], ep["labels"].shape[1], st["in"].dtype, lag, q.pop("decide_frames"), **q)
 
     def _slots_gate(self, st, gate, geometry):
         """gate: {} or any of pad, max_len, hop, lead, tail, lag_frames, history, ld_out, max_seg (gate_open's).  geometry = (hop, lead,
@@ -828,11 +853,15 @@ class VadRuntime:
         return self.gate_open(st["B"], st["chunk"], ep["labels"].shape[1], st["in"].dtype, lag, **gate)
 
     def window_slots_open(self, B: int, chunk: int, window: int = 500, lookahead: int = 0, graphs: bool = False, endpoint=None, gate=None,
-                          fuse=None):
+                          fuse=None, group_gate=None):
         """Allocate and reset a log-mel slot pool (uvad_window_slots_reset): B slots stepping `chunk` samples at a time, each holding at
         most one session, windows of `window` frames, frames emitted `lookahead` frames behind the newest complete one (the END step
         flushes them).  graphs: capture the first step into a hipGraph and replay it for every later step.  endpoint: _slots_endpoint;
-        gate (needs endpoint): _slots_gate; fuse: _slots_fuse (the endpointer then serves the groups, not the slots)."""
+        gate (needs endpoint): _slots_gate; fuse: _slots_fuse (the endpointer then serves the groups, not the slots); group_gate (needs
+        fuse and endpoint): _slots_group_gate."""
+        if group_gate is not None:
+            from .postprocess import group_gate_config
+            group_gate_config(group_gate, fuse, endpoint)                    # refused before anything is allocated
         window_slots_plan([], chunk, window, lookahead, self._fb_c.frame_len, self._fb_c.frame_shift)   # the limits, before allocating
         n_left = (self._fb_c.frame_len - self._fb_c.frame_shift) // 2
         with torch.cuda.device(self.device):
@@ -850,7 +879,7 @@ class VadRuntime:
                  "in": torch.empty((B, chunk), dtype=torch.float32, device=self.device),
                  "flags": torch.zeros(B, dtype=torch.uint8, device=self.device),
                  "graphs": 0 if graphs else None, "graph": None, "weights_gen": getattr(self, "_weights_gen", 0)}, endpoint, gate,
-                (self._fb_c.frame_shift, n_left, self._fb_c.frame_len - self._fb_c.frame_shift - n_left), fuse)
+                (self._fb_c.frame_shift, n_left, self._fb_c.frame_len - self._fb_c.frame_shift - n_left), fuse, group_gate)
 
     def window_slots_step(self, st, pcm_chunk: "torch.Tensor", start=None, end=None):
         """pcm_chunk (B, chunk) f32 on the GPU; start / end: slots whose session starts with this chunk / ends after it (bool masks or
@@ -872,10 +901,13 @@ class VadRuntime:
             return feats, tw
 
     def wav_window_slots_open(self, B: int, chunk: int, window: int = 293, lookahead: int = 0, graphs: bool = False,
-                              dtype=torch.float32, endpoint=None, gate=None, fuse=None):
+                              dtype=torch.float32, endpoint=None, gate=None, fuse=None, group_gate=None):
         """Allocate and reset a waveform slot pool (uvad_window_wav_slots_reset): window_slots_open for the SincNet PyanNet, samples of
         dtype torch.float32 or torch.int16 (read as q / 32768).  endpoint: _slots_endpoint; gate (needs endpoint): _slots_gate; fuse:
-        _slots_fuse."""
+        _slots_fuse; group_gate (needs fuse and endpoint): _slots_group_gate."""
+        if group_gate is not None:
+            from .postprocess import group_gate_config
+            group_gate_config(group_gate, fuse, endpoint)                    # refused before anything is allocated
         if dtype not in (torch.float32, torch.int16):
             raise ValueError(f"dtype must be torch.float32 or torch.int16, got {dtype}")
         J, R = self.wav_window_geometry()
@@ -897,7 +929,7 @@ class VadRuntime:
                  "in": torch.empty((B, chunk), dtype=dtype, device=self.device),
                  "flags": torch.zeros(B, dtype=torch.uint8, device=self.device),
                  "graphs": 0 if graphs else None, "graph": None, "weights_gen": getattr(self, "_weights_gen", 0)}, endpoint, gate,
-                (J, 0, R - J), fuse)
+                (J, 0, R - J), fuse, group_gate)
 
     def wav_window_slots_step(self, st, pcm_chunk: "torch.Tensor", start=None, end=None):
         """window_slots_step for a waveform slot pool: pcm_chunk (B, chunk) of the dtype the pool was opened with."""
@@ -1088,6 +1120,117 @@ class VadRuntime:
                 ns = int(r[7])
                 out.append((b, int(r[0]), int(r[1]), int(r[2]), int(r[3]), g["out"][b, off:off + ns]))
                 off += ns
+        return out
+
+    # ------------------------------------------------------------------ live speech gate for fused groups (uvad_gate_group_*)
+    def gate_group_open(self, fuse_state, chunk: int, ld_lab: int, dtype, lag_frames: int, decide_frames: int, history=None, best_history=None,
+                        ld_out=None, max_seg=None, **cuts_cfg):
+        """Allocate and reset a group gate over the G groups of `fuse_state` (fuse_open's): the streaming cuts_table + fuse_pick +
+        cuts_gather.  Every step takes the (B, chunk) block of samples of `dtype` the group members' rows sit in, the step's best bytes and
+        up to ld_lab finalised labels per group, and emits each group's speech audio, each cut whole from the member that won most of its
+        first `decide_frames` frames.  **cuts_cfg, lag_frames as gate_open; history / best_history default to uvad_gate_group_history /
+        uvad_gate_group_best_history, ld_out / max_seg to uvad_gate_group_max_out / uvad_gate_max_seg, which never truncate."""
+        if dtype not in (torch.float32, torch.int16):
+            raise ValueError(f"dtype must be torch.float32 or torch.int16, got {dtype}")
+        q = dict(pad=0, max_len=0, min_len=0, hop=160, lead=0, tail=240)
+        extra = set(cuts_cfg) - set(q)
+        if extra:
+            raise ValueError(f"unknown gate parameters {sorted(extra)} (pad, max_len, hop, lead, tail)")
+        q.update(cuts_cfg)
+        cfg = _lib.CutsCfg(*(int(q[k]) for k in ("pad", "max_len", "min_len", "hop", "lead", "tail")))
+        unit = 2 if dtype == torch.int16 else 4
+        chunk, ld_lab, lag_frames, D = int(chunk), int(ld_lab), int(lag_frames), int(decide_frames)
+        if history is None:
+            history = self.lib.uvad_gate_group_history(C.byref(cfg), lag_frames, chunk, D)
+        if best_history is None:
+            best_history = self.lib.uvad_gate_group_best_history(C.byref(cfg), lag_frames, chunk, D)
+        history, best_history = int(history), int(best_history)
+        with torch.cuda.device(self.device):
+            self._fuse_configure(fuse_state)
+            ok = 1 <= history < 2 ** 31 and 1 <= best_history < 2 ** 31
+            nbytes = int(self.lib.uvad_gate_group_state_bytes(self.ctx, C.byref(cfg), unit, history, best_history)) if ok else 0
+            auto_out = int(self.lib.uvad_gate_group_max_out(C.byref(cfg), ld_lab, chunk, D))
+            auto_seg = int(self.lib.uvad_gate_max_seg(C.byref(cfg), ld_lab))
+            if nbytes == 0 or auto_out < 0 or auto_seg < 0 or history < chunk:
+                raise ValueError(f"bad group gate configuration: chunk {chunk} (1 .. 2^24), ld_lab {ld_lab} (>= 0), lag_frames {lag_frames} (>= 0), "
+                                 f"decide_frames {D} (1 .. 2^24), history {history} (chunk .. 2^31 - 1), best_history {best_history} (1 .. 2^31 - 1), "
+                                 f"pad {q['pad']} (0 .. 2^20), max_len {q['max_len']} (0 .. 2^24), min_len {q['min_len']} (0), hop {q['hop']} (>= 1), "
+                                 f"lead {q['lead']} and tail {q['tail']} (>= 0)")
+            ld_out = auto_out if ld_out is None else int(ld_out)
+            max_seg = auto_seg if max_seg is None else int(max_seg)
+            if ld_out < 0 or max_seg < 0:
+                raise ValueError("ld_out and max_seg must be >= 0")
+            G = fuse_state["G"]
+            state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._check(self.lib.uvad_gate_group_reset(self.ctx, state.data_ptr(), nbytes, C.byref(cfg), unit, history, best_history, D,
+                                                       self._stream()))
+            return {"state": state, "fuse": fuse_state, "G": G, "B": int(fuse_state["members"].max()) + 1, "chunk": chunk, "ld_lab": ld_lab,
+                    "dtype": dtype, "cfg": cfg, "history": history, "best_history": best_history, "decide_frames": D, "lag_frames": lag_frames,
+                    "ld_out": ld_out, "max_seg": max_seg,
+                    "out": torch.zeros((G, max(ld_out, 1)), dtype=dtype, device=self.device),
+                    "seg": torch.zeros((G, max(max_seg, 1), 8), dtype=torch.int32, device=self.device),
+                    "seg_counts": torch.zeros(G, dtype=torch.int32, device=self.device)}
+
+    def _gate_group_enqueue(self, g, chunk_ptr, B, best_ptr, ld_best, best_counts_ptr, labels_ptr, lab_counts_ptr, gflags_ptr, rflags_ptr):
+        return self.lib.uvad_gate_group_step(self.ctx, chunk_ptr, g["chunk"], B, best_ptr, ld_best, best_counts_ptr, labels_ptr, g["ld_lab"],
+                                             lab_counts_ptr, gflags_ptr, rflags_ptr, g["state"].data_ptr(), g["state"].numel(),
+                                             g["out"].data_ptr() if g["ld_out"] else None, g["ld_out"],
+                                             g["seg"].data_ptr() if g["max_seg"] else None, g["max_seg"], g["seg_counts"].data_ptr(), self._stream())
+
+    def gate_group_step(self, g, chunk: "torch.Tensor", best, best_counts, labels, lab_counts, start=None, end=None, row_flags=None):
+        """chunk (B, chunk) of the gate's dtype, B above the largest member row; best (G, ld_best) uint8 and best_counts (G,) int32: the
+        step's fuse best bytes and group lengths (None, None: none); labels (G, ld_lab) uint8 and lab_counts (G,) int32 (None, None with
+        ld_lab = 0); start / end: the GROUPS whose session starts with / ends after this step, as window_slots_step's; row_flags (B,) uint8
+        on the GPU: the rows' flag bytes for the lockstep check, or None.  -> (out (G, ld_out), seg (G, max_seg, 8) int32 -- uvad_gate_seg
+        rows, the member position in bits 8 .. 15 of flags --, seg_counts (G,) int32), on the device and overwritten by the next step."""
+        G = g["G"]
+        with torch.cuda.device(self.device):
+            if not torch.is_tensor(chunk) or chunk.device != self.device or chunk.dtype != g["dtype"] or chunk.dim() != 2 or \
+                    chunk.shape[1] != g["chunk"] or chunk.shape[0] < g["B"]:
+                raise ValueError(f"chunk must be a (>= {g['B']}, {g['chunk']}) {g['dtype']} tensor on {self.device}")
+            chunk = chunk.contiguous()
+
+            def pair(x, n, what, ld):
+                if x is None and n is None and not ld:
+                    return None, None, 0
+                if not torch.is_tensor(x) or x.device != self.device or x.dtype != torch.uint8 or x.dim() != 2 or x.shape[0] != G or \
+                        (ld is not None and x.shape[1] != ld):
+                    raise ValueError(f"{what} must be a ({G}, {ld if ld is not None else 'ld'}) uint8 tensor on {self.device}")
+                if not torch.is_tensor(n) or n.device != self.device or n.dtype != torch.int32 or tuple(n.shape) != (G,):
+                    raise ValueError(f"{what}' counts must be an int32 tensor of shape ({G},) on {self.device}")
+                x, n = x.contiguous(), n.contiguous()
+                return x, n, x.shape[1]
+
+            best, best_counts, ld_best = pair(best, best_counts, "best", None)
+            labels, lab_counts, _ = pair(labels, lab_counts, "labels", g["ld_lab"])
+            if row_flags is not None and (not torch.is_tensor(row_flags) or row_flags.device != self.device or row_flags.dtype != torch.uint8 or
+                                          tuple(row_flags.shape) != (chunk.shape[0],)):
+                raise ValueError(f"row_flags must be a ({chunk.shape[0]},) uint8 tensor on {self.device}")
+            flags = self._slot_flags(G, start, end)
+            self._fuse_configure(g["fuse"])
+            ptr = lambda t: t.data_ptr() if t is not None else None
+            self._check(self._gate_group_enqueue(g, chunk.data_ptr(), chunk.shape[0], ptr(best), ld_best, ptr(best_counts), ptr(labels),
+                                                 ptr(lab_counts), ptr(flags), ptr(row_flags)))
+            return g["out"], g["seg"], g["seg_counts"]
+
+    def gate_group_collect(self, g):
+        """The records of the last step on the host -> per group a list of dicts {"index", "flags", "first_frame", "n_frames", "offset", "n",
+        "channel" (the member position), "row" (its input row), "fragment" (a view of the n_stored samples in g["out"], on the device,
+        overwritten by the next step)}.  One synchronising copy of the records and counts."""
+        with torch.cuda.device(self.device):
+            counts = g["seg_counts"].cpu().numpy()
+            seg = g["seg"].cpu().numpy()
+        groups = g["fuse"]["groups"]
+        out = []
+        for b in range(g["G"]):
+            off, recs = 0, []
+            for r in seg[b, :min(int(counts[b]), g["max_seg"])]:
+                ns, ch = int(r[7]), (int(r[1]) >> 8) & 0xff
+                recs.append({"index": int(r[0]), "flags": int(r[1]) & 0xff, "first_frame": int(r[2]), "n_frames": int(r[3]),
+                             "offset": int(r[4]) & 0xffffffff | int(r[5]) << 32, "n": int(r[6]), "channel": ch, "row": int(groups[b][ch]),
+                             "fragment": g["out"][b, off:off + ns]})
+                off += ns
+            out.append(recs)
         return out
 
     # ------------------------------------------------------------------ scoring against reference labels (uvad_score_*)
