@@ -15,6 +15,8 @@ tests/test_gpu_range_fallback.py (test infrastructure only).
                       rows in W_ih (encoding_dim = 4: feature g drives gate g of every unit), dyadic per-unit biases.
   transparent cell    (product_*) i / o biases +40 and f bias -40 make sigma(i) = sigma(o) = 1 in f32 and the carry < 1e-17, so the
                       LSTM tap is tanh(tanh(z)) of the matrix product z under test.
+  ws_*                the library's launch-size rule for the weight-stationary projection kernel and for time chunks, restated (the
+                      runtime has no getter for "which projection kernel ran": tests pick shapes the rule provably admits).
 """
 import numpy as np
 
@@ -209,19 +211,22 @@ def transparent_biases(H):
     return b.reshape(4 * H)
 
 
-def projection_operands(F, B, T, seed, n_tiny=6):
-    """The input projection on operands at the bottom of the f16 range.  -> (x (B, T, F) f32, w_g (H = 128, F) f32: the g rows of W_ih).
+def projection_operands(F, B, T, seed, n_tiny=6, H=128):
+    """The input projection on operands at the bottom of the f16 range.  -> (x (B, T, F) f32, w_g (H, F) f32: the g rows of W_ih).
       columns 0 .. n_tiny - 1   features with |x| in [2^-24, 2^-14) (f16-subnormal hi planes) under weights in [2^4, 2^10)
-      the other columns         features in [2^-6, 2^2) under weights in [2^-10, 2^-7), four columns at 2^-20 x the matrix maximum
-    The caller checks |z| <= 0.25 and R <= 4 on what comes out."""
+      the other columns         features in [2^-6, 2^2) under weights in [2^-10 - s, 2^-7 - s), four columns at 2^-20 - s x the matrix
+                                maximum; s = round(log2(max(F, 64) / 64)) octaves (0 up to F = 90, 1 at F = 128, 2 at F = 256) keep the
+                                sum of F - n_tiny such terms where it is at F = 64
+    The caller checks |z| <= 0.25 and R <= 4 on what comes out (tests/test_gpu_projection_forms.py does for every shape it uses).  The
+    draws for H = 128, F < 91 are what they were before H and s existed."""
     rng = np.random.default_rng(seed)
-    H = 128
+    s = int(round(np.log2(max(F, 64) / 64.0)))
     x = wide_range(rng, (B, T, F), -6, 2)
     x[..., :n_tiny] = wide_range(rng, (B, T, n_tiny), -24, -14)
-    w = wide_range(rng, (H, F), -10, -7)
+    w = wide_range(rng, (H, F), -10 - s, -7 - s)
     w[:, :n_tiny] = wide_range(rng, (H, n_tiny), 4, 10)
     w[0, 0] = np.float32(1023.5)                 # the matrix maximum: just below 2^10
-    w[:, n_tiny:n_tiny + 4] = wide_range(rng, (H, 4), -10, -9)   # 2^-20 x the maximum
+    w[:, n_tiny:n_tiny + 4] = wide_range(rng, (H, 4), -10 - s, -9 - s)   # 2^-20 - s x the maximum
     return x, w
 
 
@@ -284,6 +289,51 @@ def product_bound(R, K, mode):
       f32          the accumulation term only
       + 4 x 2^-23  the cell (two gate functions and two products, lstm_reference's bound at c_{t-1} = 0)"""
     return R * product_rel(K, mode) + 4 * EPS
+
+
+# ------------------------------------------------------------------------------------------------ the launch-size rule, restated
+# csrc/gemm_f16p_ws.hip (gemm_f16p_ws_supported) and csrc/uvad_api.hip (classify_impl): a projection of M = 4 ceil(B / 4) T rows onto
+# N = 4 H D gate columns with K accumulated terms (the layer's input width in whole 32s) runs the weight-stationary kernel in modes
+# f16p / f16p3 iff K is 64, 96, 128 or 256, N is 1 .. 8 whole 128-column tiles and ceil(M / 128) * (N / 128) >= 2 * CUs.
+WS_K = (64, 96, 128, 256)
+
+
+def ws_padded_k(width):
+    return (width + 31) // 32 * 32
+
+
+def ws_rows(B, T):
+    return 4 * ((B + 3) // 4) * T
+
+
+def ws_nt(H, D):
+    assert (4 * H * D) % 128 == 0, (H, D)
+    return 4 * H * D // 128
+
+
+def ws_selected(rows, nt, K, cus):
+    return K in WS_K and 1 <= nt <= 8 and (rows + 127) // 128 * nt >= 2 * cus
+
+
+def ws_min_rows(nt, cus):
+    """The smallest row count the rule admits at nt column tiles."""
+    return (-(-2 * cus // nt) - 1) * 128 + 1
+
+
+def ws_batch(nt, T, cus, above=1.05):
+    """The smallest B = 1 (mod 4) -- a partial 4-sequence tile -- whose row count is at least `above` x the rule's threshold: 5 % above
+    it plus at most one 4-sequence tile of 4 T rows, whatever the CU count."""
+    tiles = int(np.ceil(above * ws_min_rows(nt, cus) / (4.0 * T)))
+    return 4 * tiles - 3
+
+
+def ws_chunks_used(rows, nt, n, cus):
+    """uvad_set_time_chunks(n >= 2) is a ceiling: the count is lowered until floor(mt / n) * nt >= 2 * CUs (every chunk's projection is
+    still a launch the weight-stationary kernel takes); 1 = unchunked."""
+    mt = (rows + 127) // 128
+    while n > 1 and (mt // n) * nt < 2 * cus:
+        n -= 1
+    return n
 
 
 # ------------------------------------------------------------------------------------------------ correctly rounded quotients
@@ -392,13 +442,18 @@ def head_weights(K1, seed, H=128):
 
 def head_reference(y, w, slope, mode):
     """The head in float64 on the tapped LSTM output y (B, T, K1) -> (logits, bound) (B, T).  Every layer's own error is
-    R_layer x product_rel(K, mode), R_layer = sum |w| |a| + |b|; leaky_relu (|slope| <= 1) passes an error on no larger, and the next
-    layer weighs it by |W|."""
+    R_layer x product_rel(K, mode), R_layer = sum |w| |a| + |b|.  leaky_relu is piecewise linear and continuous with slopes 1 and
+    `slope`, so an error that enters it leaves it multiplied by at most max(1, |slope|) (exactly 1.0 for |slope| <= 1: the bound is then
+    numerically what it was without the factor), and the next layer weighs it by |W|."""
     a, e = y.astype(np.float64), 0.0
+    lip = max(1.0, abs(float(slope)))
     for wk, bk in (("linear.0.weight", "linear.0.bias"), ("linear.1.weight", "linear.1.bias"), ("classifier.weight", "classifier.bias")):
         W, b = w[wk].astype(np.float64), w[bk].astype(np.float64)
         z = a @ W.T + b
         R = np.abs(a) @ np.abs(W).T + np.abs(b)
         e = (e @ np.abs(W).T if np.ndim(e) else 0.0) + R * product_rel(W.shape[1], mode)
-        a = z if wk.startswith("classifier") else np.where(z >= 0, z, slope * z)
+        if wk.startswith("classifier"):
+            a = z
+        else:
+            a, e = np.where(z >= 0, z, slope * z), e * lip
     return a[..., 0], e[..., 0]

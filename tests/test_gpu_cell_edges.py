@@ -8,7 +8,10 @@
   containment      one NaN / +Inf in one sequence changes no bit of any other sequence in the kernels that share sequences inside
                    matrix-core tiles, is non-finite exactly where torch's CPU LSTM is, and leaves nothing behind in the workspace
   bottom of f16    the input projection on features whose hi plane is an f16 subnormal and on a weight matrix spanning 20 octaves,
-                   read through a transparent cell, in every GEMM mode and both projection kernels
+                   read through a transparent cell, in every GEMM mode and both projection kernels (every column-tile count and K of
+                   the weight-stationary one: tests/test_gpu_projection_forms.py)
+  head             wide-range feed-forward / classifier weights against a float64 head on the tapped LSTM output: both input widths
+                   of head_fused_kernel, row counts with more 64-row tiles than CUs, leaky_relu slopes from -0.5 to 1.5
 The GPU tests carry the gpu mark one by one: the float32 restatement test runs without a GPU.
 """
 import numpy as np
@@ -343,6 +346,43 @@ def test_recurrent_product_keeps_tiny_states_and_wide_range_weights(tile):
         assert r <= 1.0, (tile, mode, r)
 
 
+def _head_runtime(K1, slope):
+    """One-layer H = 128 model (two directions: K1 = 256, one: K1 = 128), seeded LSTM x2, wide-range head weights, the classifier's
+    leaky_relu slope as given -> (runtime, head weights)."""
+    import uvad_amd
+    from uvad_amd.synth import seed_weights
+    dev = torch.device("cuda:0")
+    m = uvad_amd.PyanNet2(lstm={"num_layers": 1, "bidirectional": K1 == 256}, encoding_dim=64)
+    m.build()
+    seed_weights(m, 11, 2.0)
+    hw = cr.head_weights(K1, seed=5)
+    sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    sd.update({k: torch.from_numpy(v) for k, v in hw.items()})
+    rt = uvad_amd.VadRuntime(dev, model={"encoding_dim": 64, "lstm": m.hparams.lstm, "linear": m.hparams.linear, "leaky_slope": slope})
+    rt.load_state_dict(sd)
+    return rt, hw
+
+
+def _check_head(rt, hw, K1, B, T, slope):
+    x = (torch.randn(B, T, 64, generator=torch.Generator().manual_seed(4)) * 2.0 - 3.0).to(torch.device("cuda:0"))
+    for mode in ("f16p_stream", "f16p", "f16p3", "f32"):
+        rt.set_gemm_mode(mode)
+        # the output tensors of a call are fresh allocations, which the caching allocator serves from the blocks the previous mode's
+        # outputs were in: fill blocks of that size with NaN first, so that a row tile the head leaves unwritten is not finite
+        # instead of holding the previous mode's (nearly equal) logits
+        junk = [torch.full((B, T), float("nan"), device=x.device) for _ in range(2)]
+        torch.cuda.synchronize()
+        del junk
+        lg, _, y = _run(rt, x)
+        assert y.shape == (B, T, K1)
+        ref, bound = cr.head_reference(y, hw, slope, mode)
+        assert np.isfinite(lg).all() and np.abs(ref).max() > 0.05
+        r = float((np.abs(lg.astype(np.float64) - ref) / bound).max())
+        print(f"head K1 {K1}, B {B}, T {T}, slope {slope:g}, {mode}: worst err / bound {r:.4f} (worst |err| {float(np.abs(lg - ref).max()):.1e}, "
+              f"bound there >= {float(bound.min()):.1e})")
+        assert r <= 1.0, (K1, B, T, slope, mode, r)
+
+
 @gpu
 @pytest.mark.parametrize("B,T", [(5, 7), (33, 256)])
 def test_head_on_wide_range_weights_against_a_float64_head_on_the_tapped_lstm_output(B, T):
@@ -350,24 +390,39 @@ def test_head_on_wide_range_weights_against_a_float64_head_on_the_tapped_lstm_ou
     reads in the split modes).  By the library's rule (head_fused_supported: two 128-unit layers, any row count) modes f16p / f16p3 run
     head_fused at both sizes, f16p_stream the per-layer split kernels, f32 the exact ones; the runtime has no getter for the head path,
     so the modes are what selects it here."""
-    import uvad_amd
-    from uvad_amd.synth import seed_weights
-    dev = torch.device("cuda:0")
-    m = uvad_amd.PyanNet2(lstm={"num_layers": 1}, encoding_dim=64)
-    m.build()
-    seed_weights(m, 11, 2.0)
-    hw = cr.head_weights(256, seed=5)
-    sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
-    sd.update({k: torch.from_numpy(v) for k, v in hw.items()})
-    m.load_state_dict(sd)
-    m = m.to(dev).eval()
-    rt = m.runtime(dev)
-    x = (torch.randn(B, T, 64, generator=torch.Generator().manual_seed(4)) * 2.0 - 3.0).to(dev)
-    for mode in ("f16p_stream", "f16p", "f16p3", "f32"):
-        rt.set_gemm_mode(mode)
-        lg, _, y = _run(rt, x)
-        ref, bound = cr.head_reference(y, hw, 0.01, mode)
-        assert np.isfinite(lg).all() and np.abs(ref).max() > 0.05
-        r = float((np.abs(lg.astype(np.float64) - ref) / bound).max())
-        print(f"head B {B}, T {T}, {mode}: worst err / bound {r:.4f} (worst |err| {float(np.abs(lg - ref).max()):.1e}, bound there >= {float(bound.min()):.1e})")
-        assert r <= 1.0, (B, T, mode, r)
+    rt, hw = _head_runtime(256, 0.01)
+    _check_head(rt, hw, 256, B, T, 0.01)
+    rt.close()
+
+
+HEAD_SLOPES = (0.01, -0.5, 0.0, 1.0, 1.5)
+HEAD_T_MANY = 300
+
+
+def _head_sizes(cus):
+    """(B, T): one partial 64-row tile; six 64-row tiles and a partial one (12 x 37 = 444 rows); 144 tiles; and at least 1.2 x as many
+    64-row tiles as CUs (65 x 300 on 256 CUs), so that workgroups of head_fused_kernel run the drawn-ahead tile loop."""
+    tiles4 = -(-(12 * cus * 64) // (10 * 4 * HEAD_T_MANY))
+    return {"5x7": (5, 7), "9x37": (9, 37), "33x256": (33, 256), "more_tiles_than_cus": (4 * tiles4 - 3, HEAD_T_MANY)}
+
+
+@gpu
+@pytest.mark.parametrize("size", ["5x7", "9x37", "33x256", "more_tiles_than_cus"])
+@pytest.mark.parametrize("K1", [128, 256])
+def test_fused_head_at_both_input_widths_row_counts_past_the_cu_count_and_other_slopes(K1, size):
+    """The test above at K1 = 128 too (one direction: head_fused_kernel<4, 4> and <4, 3>), at row counts with a partial last 64-row tile
+    and with more 64-row tiles than CUs (a workgroup then draws a second tile), and at leaky_relu slopes 0.01, -0.5, 0, 1 and 1.5 in all
+    four GEMM modes.  The bound is cell_ref.head_reference's: an error entering a leaky_relu leaves it times max(1, |slope|); nothing
+    is fitted.  (The static range guard of csrc/uvad_api.hip scales its activation bound by the same factor; these weights stay far
+    inside the f16 range, so every split mode runs its split kernels.)"""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    B, T = _head_sizes(cus)[size]
+    mt = -(-4 * ((B + 3) // 4) * T // 64)
+    if size == "more_tiles_than_cus":
+        assert mt >= 1.2 * cus and B % 4 == 1, (B, T, mt, cus)
+    else:
+        assert mt < cus, (mt, cus)
+    for slope in HEAD_SLOPES:
+        rt, hw = _head_runtime(K1, slope)
+        _check_head(rt, hw, K1, B, T, slope)
+        rt.close()

@@ -303,10 +303,62 @@ def test_large_launch_kernels_reproduce_the_reference_goldens(tile, name):
     rt.set_recurrent_tile(0)
 
 
+# Two-layer models on the weight-stationary projection at other column-tile counts nt = 4 H D / 128; layer 1 reads the A planes the
+# recurrence wrote (K = H D).  (F, lstm): nt and K per layer in the comments; the batch comes from the launch-size rule.
+WS_TWO_LAYER = [(64, {"hidden_size": 96, "num_layers": 2, "bidirectional": False}),    # nt 3, K 64 then 96
+                (64, {"hidden_size": 32, "num_layers": 2}),                            # nt 2, K 64 / 64
+                (80, {"hidden_size": 48, "num_layers": 2}),                            # nt 3, K 96 / 96
+                (128, {"hidden_size": 256, "num_layers": 2, "bidirectional": False}),  # nt 8, K 128 then 256, generic recurrence
+                (64, {"hidden_size": 96, "num_layers": 2})]                            # nt 6 at layer 0, K = 192 at layer 1: weight-stationary, then tile-streaming, in one call
+
+
+def _ws_two_layer_batch(F, lstm, T):
+    """B = 1 (mod 4) with 4 ceil(B / 4) T rows at least 5 % above the threshold of the library's rule (cell_ref.ws_*) on this device;
+    asserts which layers the rule sends to the weight-stationary kernel."""
+    import cell_ref as cr
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    H, D = lstm["hidden_size"], 2 if lstm.get("bidirectional", True) else 1
+    nt = cr.ws_nt(H, D)
+    B = cr.ws_batch(nt, T, cus)
+    rows = cr.ws_rows(B, T)
+    ws = [cr.ws_selected(rows, nt, K, cus) for K in (cr.ws_padded_k(F), cr.ws_padded_k(H * D))]
+    assert ws == [True, H * D in cr.WS_K], f"F {F}, {lstm}: {B} x {T} no longer reaches the weight-stationary kernel on {cus} CUs: {ws}"
+    print(f"F={F} {lstm}: nt {nt}, B {B} x T {T} = {rows} rows on {cus} CUs, weight-stationary per layer {ws}")
+    return B
+
+
+@pytest.mark.parametrize("F,lstm", WS_TWO_LAYER)
+def test_two_layer_models_on_the_weight_stationary_projection_vs_float64_oracle(F, lstm):
+    """The shapes the bit-identity test below adds, with weights x2 (the contractive network the 1e-4 claim holds for): logits and
+    probabilities of 8 sequences -- the first, the last and six spread over other row tiles -- against the float64 oracle."""
+    import uvad_amd
+    from uvad_amd.synth import seed_weights
+    from oracle import c_oracle as co
+    dev = torch.device("cuda:0")
+    T = 255
+    B = _ws_two_layer_batch(F, lstm, T)
+    m = uvad_amd.PyanNet2(lstm=lstm, encoding_dim=F)
+    m.build()
+    seed_weights(m, 77, 2.0)
+    m = m.to(dev).eval()
+    feats = torch.randn(B, T, F, generator=torch.Generator().manual_seed(5)) * 2.0 - 3.0
+    logits, probs = m.forward_logits(feats.to(dev))
+    idx = sorted({0, B - 1} | {int(i) for i in np.linspace(0, B - 1, 8).round()})
+    assert len(idx) == 8 and len({i // 4 for i in idx}) == 8          # eight 4-sequence tiles: 4 T rows each, so eight different 128-row tiles
+    sd = {k: v.cpu().numpy() for k, v in m.state_dict().items()}
+    mc = co.ModelCfg(F, lstm["hidden_size"], 2, int(lstm.get("bidirectional", True)), 128, 2, 0.01)
+    want, wantp = co.classify(sd, mc, feats[idx].numpy())
+    err = float(np.abs(logits[idx].cpu().numpy() - want).max())
+    perr = float(np.abs(probs[idx].cpu().numpy() - wantp).max())
+    print(f"F={F} {lstm} B={B}: sequences {idx}: logit err {err:.2e}, prob err {perr:.2e}")
+    assert np.isfinite(logits.cpu().numpy()).all() and err < LOGIT_TOL and perr < LOGIT_TOL
+
+
 @pytest.mark.parametrize("F,lstm,B,T", [(64, None, 256, 1000),                       # cfg 2: K = 64 and K = 256, N = 1024
                                         (80, None, 37, 611),                         # K = 96 (F = 80 padded), ragged row count
                                         (64, {"hidden_size": 64}, 61, 509),          # K = 128, N = 512
-                                        (60, {"bidirectional": False}, 130, 300)])   # K = 64 / 128, N = 512, one direction
+                                        (60, {"bidirectional": False}, 130, 300)]    # K = 64 / 128, N = 512, one direction
+                         + [(F, lstm, None, 255) for F, lstm in WS_TWO_LAYER])             # other tile counts, layers >= 1: B from the launch-size rule
 def test_weight_stationary_projection_is_bit_identical_to_the_streaming_kernel(F, lstm, B, T):
     """gemm_f16p_ws_kernel (weights in registers, persistent workgroups pulling row tiles from a queue) and head_fused_kernel (both
     feed-forward layers + classifier in one launch) issue the same MFMA products in the same order per accumulator as
@@ -316,6 +368,8 @@ def test_weight_stationary_projection_is_bit_identical_to_the_streaming_kernel(F
     import uvad_amd
     from uvad_amd.synth import seed_weights
     dev = torch.device("cuda:0")
+    if B is None:
+        B = _ws_two_layer_batch(F, lstm, T)
     m = uvad_amd.PyanNet2(lstm=lstm, encoding_dim=F)
     m.build()
     seed_weights(m, 1234, 4.0)
@@ -333,7 +387,9 @@ def test_weight_stationary_projection_is_bit_identical_to_the_streaming_kernel(F
     for rep in range(3):
         got, gp = rt.classify(feats)
         y, z = rt.taps()
-        assert torch.equal(y, y_want) and torch.equal(z, z_want)          # LSTM output (fed by the projections) and feed-forward output: same bits
+        # LSTM output (fed by the projections) and feed-forward output: same bits
+        assert torch.equal(y, y_want), (rep, f"{int((y != y_want).sum())} of {y.numel()} LSTM outputs differ, by up to {float((y - y_want).abs().max()):.2e}")
+        assert torch.equal(z, z_want), (rep, f"{int((z != z_want).sum())} feed-forward outputs differ, by up to {float((z - z_want).abs().max()):.2e}")
         # the logits: bit-identical where the head runs as three kernels; where head_fused_kernel runs (two 128-unit layers, large
         # launch) its 128-term classifier sum is ordered differently: equal to f32 rounding, and the same bits run after run
         err = float((got - want).abs().max())
@@ -360,7 +416,8 @@ def test_weight_stationary_projection_is_bit_identical_to_the_streaming_kernel(F
                                         (80, None, 37, 611),                         # K = 96, rows that straddle sequence tiles everywhere
                                         (64, {"hidden_size": 64}, 61, 509),          # N = 512 (lowered to one chunk by the launch-size rule)
                                         (64, {"hidden_size": 64}, 256, 1000),        # N = 512 large enough to STAY chunked: lstm_rec_kernel<64, ...> with carried state
-                                        (60, {"bidirectional": False}, 130, 300)])   # one direction
+                                        (60, {"bidirectional": False}, 130, 300),    # one direction
+                                        (64, {"hidden_size": 64, "bidirectional": False}, 256, 512)])   # N = 256: lists of ONE direction over two column tiles, side-stream grid of 192
 def test_time_chunked_layers_are_bit_identical_to_one_launch_per_layer(F, lstm, B, T):
     """uvad_set_time_chunks: a layer cut into n time chunks -- the projection of chunk i + 1 (weight-stationary GEMM over the row tiles
     that chunk needs first) on the library's side stream beside the 4-sequence recurrence of chunk i (carried state) on the caller's --
@@ -393,10 +450,20 @@ def test_time_chunked_layers_are_bit_identical_to_one_launch_per_layer(F, lstm, 
         assert torch.equal(y, y_want) and torch.equal(z, z_want), (n, used)
         ran.append((n, used))
     print(f"F={F} B={B} T={T}: (requested, used) chunks {ran}")
-    # (a forced count is a ceiling: the library lowers it until every chunk's projection is still a launch the weight-stationary
-    #  kernel takes -- the 61 x 509 case runs unchunked)
+    # (a forced count n is a ceiling: the library lowers it until every chunk's projection is still a launch the weight-stationary
+    #  kernel takes, i.e. to the largest n' <= n with floor(mt / n') * nt >= 2 * CUs (cell_ref.ws_chunks_used) -- on 256 CUs the
+    #  61 x 509 case runs unchunked, the 256 x 1000 cases run all 8 and the 256 x 512 x (N = 256) case runs 4 for 7 and 8)
+    import cell_ref as cr
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    hp = dict(uvad_amd.PyanNet2.LSTM_DEFAULTS, **(lstm or {}))
+    nt = cr.ws_nt(hp["hidden_size"], 2 if hp["bidirectional"] else 1)
+    for n, used in ran:
+        if n >= 2:
+            assert used == cr.ws_chunks_used(cr.ws_rows(B, T), nt, n, cus), (n, used, nt, cus, "no concurrent side stream?")
     if B * T >= 128 * 1000:
-        assert dict(ran)[0] > 1 and dict(ran)[8] == 8, "the chunked schedule never ran (no concurrent side stream?)"
+        assert dict(ran)[0] > 1 and dict(ran)[8] == cr.ws_chunks_used(cr.ws_rows(B, T), nt, 8, cus) > 1, "the chunked schedule never ran"
+    if cus == 256 and B * T >= 128 * 1000:
+        assert [dict(ran)[n] for n in (2, 3, 7, 8)] == ([2, 3, 4, 4] if nt == 2 else [2, 3, 7, 8])
     # captured into a hipGraph on a side stream of the caller's (after an eager call there: the stream pair is probed outside captures)
     rt.set_time_chunks(4)
     side = torch.cuda.Stream(device=dev)
