@@ -416,6 +416,39 @@ int uvad_window_slots_reset(uvad_ctx *, void *d_state, int B, int chunk, int win
 int uvad_window_slots_step(uvad_ctx *, const float *d_pcm_chunk, const uint8_t *d_flags, int B, int chunk, void *d_state,
                            float *d_logits, float *d_probs, int ld_out, int32_t *d_counts, void *d_workspace, size_t ws_bytes, void *stream);
 int uvad_window_slots_features(uvad_ctx *, const void *d_state, int B, float *d_feats, int32_t *d_tw, void *stream);
+/* The causal stream's slot pool: uvad_stream_step for feeds that start and end independently, still ONE launch per step.  The contract
+ * is that of the window slot pools above with lookahead 0 -- flags, idle slots, outputs, d_counts, enqueue only -- and the step has
+ * uvad_window_slots_step's argument list, so whatever runs behind a window pool (fusion, endpointers, gates) runs behind this one.
+ *   Flags: after uvad_stream_slots_reset every slot is idle.  UVAD_SLOT_START drops whatever the slot held and starts a session with this
+ *   chunk as its first samples (zero (h, c) in every layer, the first chunk reflected on the left); UVAD_SLOT_END makes the slot idle
+ *   from the next step on; both bits: a one-chunk session; END on an idle slot does nothing.  An idle slot's chunk row is never read, its
+ *   state is not written, and d_counts[b] = 0.
+ *   A session's frames are, bit for bit, those of a B = 1 uvad_stream_step stream reset at the session's start and fed the same chunks;
+ *   frame t is emitted in the step in which its last sample arrives.  The END step emits what its chunk completes and nothing more:
+ *   streams are open-ended, there is NO right-edge reflection and no flush (as uvad_stream_step; there is no lookahead to flush).
+ *   Row b of d_logits / d_probs [B][ld_out] (either may be NULL, not both) gets its n_b frames in columns 0 .. n_b - 1 and d_counts[b]
+ *   (DEVICE int32 [B], required) = n_b; nothing else is written.  ld_out < kmax = uvad_stream_slots_kmax(ctx, chunk) = ceil(chunk /
+ *   frame_shift) is UVAD_E_ARG and nothing is enqueued.  A NaN / Inf sample poisons its own session only (as uvad_stream_step), until the
+ *   slot's next START.
+ *   Enqueue only: the step never allocates, frees or synchronises.  Every per-slot quantity -- the active bit, samples since the
+ *   session's start (int64), frames, the PCM tail (updated in place), whether this is the first chunk -- is read and written on the
+ *   device, so two steps with the same (B, chunk) and buffers enqueue identical work: one captured graph replays for every later step.
+ *   There is no peek / advance.  Steps return UVAD_OK, not a count.
+ *   Scope, fixed at reset: the pool exists where uvad_stream_step is one launch -- a causal model with hidden_size 128, 64 or 80 features,
+ *   1 .. 8 layers, at most 4 feed-forward layers of 128 -> 128 units; kmax <= 4, i.e. chunks up to 4 frame shifts (40 ms at the
+ *   reference geometry); the feature stage (4 rows of frame_len + chunk samples, the mel image, the transform scratch) within 120 KiB
+ *   of LDS; chunk >= (frame_len - frame_shift) / 2, since any step can be a session's first; snip_edges = 0.  Reset refuses anything
+ *   else with UVAD_E_UNSUPPORTED (model, framing) or UVAD_E_ARG (chunk) and a uvad_last_error text that names the limit; there is no
+ *   fallback: other models stream in lockstep groups (uvad_stream_step) or behind the window pools.
+ *   Other refusals as the window pools': another B or chunk than the reset's: UVAD_E_ARG; a state never reset, or missing tables /
+ *   weights: UVAD_E_STATE; a workspace below uvad_stream_slots_workspace_bytes: UVAD_E_WORKSPACE (the step needs no scratch memory; the
+ *   size is a token one that keeps the pools' calling convention).  A refused call leaves the state as it was. */
+int uvad_stream_slots_kmax(const uvad_ctx *, int chunk);
+size_t uvad_stream_slots_state_bytes(const uvad_ctx *, int B);
+size_t uvad_stream_slots_workspace_bytes(const uvad_ctx *, int B, int chunk);
+int uvad_stream_slots_reset(uvad_ctx *, void *d_state, int B, int chunk, void *stream);
+int uvad_stream_slots_step(uvad_ctx *, const float *d_pcm_chunk, const uint8_t *d_flags, int B, int chunk, void *d_state,
+                           float *d_logits, float *d_probs, int ld_out, int32_t *d_counts, void *d_workspace, size_t ws_bytes, void *stream);
 /* the same for the waveform model; the sample type (f32, or int16 read as q / 32768) is fixed at reset as in uvad_window_wav_reset */
 size_t uvad_window_wav_slots_state_bytes(const uvad_ctx *, int B, int window, int is_i16);
 size_t uvad_window_wav_slots_workspace_bytes(const uvad_ctx *, int B, int chunk, int window);

@@ -160,6 +160,12 @@ SIGNATURES = {
     "uvad_window_wav_slots_step_i16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_window_wav_slots_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uvad_stream_slots_kmax": (C.c_int, [C.c_void_p, C.c_int]),
+    "uvad_stream_slots_state_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "uvad_stream_slots_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "uvad_stream_slots_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "uvad_stream_slots_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_sliding_configure": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "uvad_sliding_count": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "uvad_sliding_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int]),

@@ -257,6 +257,212 @@ __global__ __launch_bounds__(WAVES * 64) void lstm_stack_kernel(LstmStackArgs a)
     }
 }
 
+// ---- the slot form (uvad_stream_slots_step): the one-launch step above for a POOL of slots, each holding its own session.  What the
+// host bakes into LstmStackArgs for a lockstep group -- T, the offset of the first new frame, the first-chunk reflection, the tail's
+// ping-pong parity -- is per slot here and read from the device (LstmStackSlotsArgs: active, n, e), so every step of a pool enqueues
+// the same launch.  A workgroup still owns its 4 slots from PCM to probability and waits for no other workgroup:
+//   plan      one lane per slot: flags and counters -> live / first / k_b / offset_b (stream_plan's arithmetic, uvad_api.hip, 64-bit),
+//             counts[b] = k_b and the counters' next values.  (Nothing below reads a counter from memory again, so they are committed
+//             here, END's cleared active bit included.)
+//   features  the whole image [tail | chunk] of a slot in LDS first (the START reflection included), then the next tail written IN
+//             PLACE from LDS -- a ping-pong's parity would be a host counter; wave (row j, pair p) transforms frames 2p, 2p + 1 of ITS
+//             row's k_j: a frame's bits depend on whether it had a partner, and this keeps them those of the slot's B = 1 stream.
+//   layers    run for t < kt = the tile's largest k_b (workgroup-uniform: the barriers stay legal); a lane whose sequence has
+//             t >= k_b keeps c, h and its hbuf row by SELECT -- what xbuf holds for that (t, sequence) is arbitrary, possibly
+//             non-finite, and the 4x4x1 MFMA keeps a sequence's column to itself.  START lanes take zero state instead of loading it;
+//             (h, c) and the tail are written for live slots only; idle slots' chunk rows are never read.
+template <int KIN0>
+__global__ __launch_bounds__(WAVES * 64) void lstm_stack_slots_kernel(LstmStackSlotsArgs q) {
+    constexpr int TMAX = LSTM_STACK_TMAX;
+    constexpr int HR = KIN0 == 64 ? 4 : 2;
+    __shared__ __attribute__((aligned(16))) float xbuf[TMAX][SEQ_TILE][HS];
+    __shared__ __attribute__((aligned(16))) float hbuf[2][SEQ_TILE][HS];
+    __shared__ int s_k[SEQ_TILE], s_off[SEQ_TILE], s_live[SEQ_TILE], s_first[SEQ_TILE];
+    extern __shared__ __attribute__((aligned(16))) float fbs[];
+
+    const LstmStackArgs &a = q.st;
+    const FbankArgs &f = a.fb;
+    const int tile = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int jb = lane & 3;
+    const int blk = lane >> 2;
+    const int unit = wave * 16 + blk;
+    const int L = f.frame_len, sh = f.frame_shift, F = KIN0, n_left = (L - sh) / 2, CH = q.chunk_len;
+
+    // ---- plan
+    if (tid < SEQ_TILE) {
+        const int b = tile * SEQ_TILE + tid;
+        int live = 0, first = 0, k = 0, off = 0;
+        if (b < a.B) {
+            const int fl = q.flags ? q.flags[b] : 0;
+            long long n_prev = 0, e_prev = 0;
+            if (fl & 1) live = 1;   // START: whatever the slot held is dropped
+            else if (q.active[b]) { live = 1; n_prev = q.n[b]; e_prev = q.e[b]; }
+            if (live) {
+                first = n_prev == 0;
+                // frame t spans [t sh - n_left, t sh - n_left + L): complete once n >= t sh - n_left + L (stream_plan)
+                const long long n = n_prev + CH;
+                const long long f_hi = n + n_left - L >= 0 ? (n + n_left - L) / sh : -1;
+                long long kk = f_hi - (e_prev - 1);
+                kk = kk < 0 ? 0 : (kk > q.kmax ? q.kmax : kk);   // (<= ceil(chunk / shift) = kmax by the arithmetic)
+                const long long o = e_prev * sh - n_left - (n_prev - L);   // the first new frame inside [tail (L samples) | chunk]
+                if (kk > 0 && (o < 0 || o + (kk - 1) * sh > CH)) kk = 0;    // (never by the arithmetic: no frame leaves the image)
+                k = (int)kk;
+                off = k > 0 ? (int)o : 0;
+                q.n[b] = n;
+                q.e[b] = e_prev + k;
+                q.active[b] = (fl & 2) ? 0 : 1;   // END: idle from the next step on
+            }
+            q.counts[b] = k;
+        }
+        s_live[tid] = live; s_first[tid] = first; s_k[tid] = k; s_off[tid] = off;
+    }
+    __syncthreads();
+    if (!(s_live[0] | s_live[1] | s_live[2] | s_live[3])) return;   // workgroup-uniform: an all-idle tile has written its zero counts
+    int kt_v = s_k[0];
+#pragma unroll
+    for (int j = 1; j < SEQ_TILE; ++j) kt_v = s_k[j] > kt_v ? s_k[j] : kt_v;
+    const int kt = __builtin_amdgcn_readfirstlane(kt_v);
+
+    // ---- feature stage: images, next tails, frame pairs
+    const int tot = L + CH, img_ld = (tot + 3) & ~3;
+    const int mel_quads = f.tab.mel_stride / 4, melw_n = (int)mel_image_floats(f.tab.mel_stride, F);
+    float *img = fbs, *melw = img + SEQ_TILE * img_ld, *scr = melw + melw_n;
+    for (int j = 0; j < SEQ_TILE; ++j) {
+        const bool lv = s_live[j] != 0, fr = s_first[j] != 0;
+        const size_t b = (size_t)(tile * SEQ_TILE + j);
+        const float *crow = q.chunk + b * CH, *trow = q.tail + b * L;
+        for (int p = tid; p < tot; p += WAVES * 64) {
+            float v = 0.0f;   // (an idle slot's row: zeros, its chunk row is not read)
+            if (lv) {
+                if (p >= L) v = crow[p - L];
+                else if (fr) {   // the session's first chunk mirrors its head, edge sample included (fbank.hip vs_abs)
+                    const int m = L - p;
+                    v = (m <= n_left && m - 1 < CH) ? crow[m - 1] : 0.0f;
+                } else v = trow[p];
+            }
+            img[j * img_ld + p] = v;
+        }
+    }
+    for (int i = tid; i < melw_n; i += WAVES * 64) melw[i] = f.tab.mel_wt[i];
+    fbp::PairConsts kc;
+    fbp::load_pair_consts(kc, f.tab, reinterpret_cast<const float2 *>(f.tab.tw512), lane, L, F);
+    __syncthreads();
+    for (int j = 0; j < SEQ_TILE; ++j) {   // the tail the slot's next step starts from: the image's last L samples
+        if (!s_live[j]) continue;
+        float *trow = q.tail + (size_t)(tile * SEQ_TILE + j) * L;
+        for (int p = tid; p < L; p += WAVES * 64) trow[p] = img[j * img_ld + CH + p];
+    }
+    const int kb = s_k[jb];
+    const bool live_b = s_live[jb] != 0, load_b = live_b && !s_first[jb];
+    const unsigned so = (unsigned)((tile * SEQ_TILE + jb) * H + unit);
+    if (kt == 0) {   // no slot of the tile completes a frame: a session that starts here still starts from zero state
+        if (live_b && !load_b)
+            for (int l = 0; l < a.n_layers; ++l) {
+                const size_t lo = (size_t)l * a.layer_stride + so;
+                a.h[lo] = 0.0f;
+                a.c[lo] = 0.0f;
+            }
+        return;
+    }
+    {
+        const int j = wave >> 1, fa = 2 * (wave & 1);
+        const int kj = __builtin_amdgcn_readfirstlane(s_k[j]);
+        const bool floor_normal = f.log_floor >= 1.17549435e-38f;
+        if (fa < kj) {   // wave-uniform, decided by the wave's own row
+            const bool has_b = fa + 1 < kj;
+            const float *x0 = img + j * img_ld + s_off[j];
+            float *zr = scr + (size_t)wave * (2 * fbp::ZB_ELEMS), *zi = zr + fbp::ZB_ELEMS;
+            fbp::fbank_pair(x0 + fa * sh, x0 + (has_b ? fa + 1 : fa) * sh, has_b, kc, zr, zi, melw, mel_quads, f.tab.nyquist != 0,
+                            (F + 63) / 64, F, L, f.preemph, f.remove_dc != 0, 1.0f / (float)L, lane, [&](int m, float ea, float eb) {
+                                if (m < F) {
+                                    xbuf[fa][j][m] = fbp::log_floored(ea, f.log_floor, floor_normal);
+                                    if (has_b) xbuf[fa + 1][j][m] = fbp::log_floored(eb, f.log_floor, floor_normal);
+                                }
+                            });
+        }
+    }
+
+    // ---- the layers, as lstm_stack_kernel's, for t < kt
+    float w[H];
+    for (int l = 0; l < a.n_layers; ++l) {
+        const float4 b4 = *reinterpret_cast<const float4 *>(a.bias[l] + unit * 4);
+        const f32x4 bias = {b4.x, b4.y, b4.z, b4.w};
+        f32x4 gq[TMAX];
+        if (l == 0) {
+            load_image<KIN0 / 4>(w, a.wih[0], wave, lane);
+            __syncthreads();   // the features are in LDS
+#pragma unroll
+            for (int t = 0; t < TMAX; ++t)
+                if (t < kt) gq[t] = chain<KIN0 / 4, HR>(w, &xbuf[t][jb][0], bias);
+        } else {
+            load_image<H / 4>(w, a.wih[l], wave, lane);
+#pragma unroll
+            for (int t = 0; t < TMAX; ++t)
+                if (t < kt) gq[t] = chain<H / 4, HR>(w, &xbuf[t][jb][0], bias);
+        }
+        load_image<H / 4>(w, a.whh[l], wave, lane);
+        const size_t lo = (size_t)l * a.layer_stride + so;
+        float c = 0.0f, hlast = 0.0f;
+        if (load_b) {
+            c = a.c[lo];
+            hlast = a.h[lo];
+        }
+        hbuf[0][jb][unit] = hlast;
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < TMAX; ++t) {
+            if (t < kt) {
+                float cn = c;
+                const float hn = lstm_cell(chain<H / 4, HR>(w, &hbuf[t & 1][jb][0], gq[t]), cn);
+                const bool on = t < kb;   // past the sequence's own frames: state and hbuf row kept by select
+                c = on ? cn : c;
+                hlast = on ? hn : hlast;
+                hbuf[(t + 1) & 1][jb][unit] = hlast;
+                xbuf[t][jb][unit] = hlast;   // the next layer's (or the head's) input; read for t < k_b only
+                __syncthreads();
+            }
+        }
+        if (live_b) {
+            a.h[lo] = hlast;
+            a.c[lo] = c;
+        }
+    }
+
+    // ---- the head, as lstm_stack_kernel's; only columns t < k_b of live rows leave
+    for (int j = 0; j < a.n_lin; ++j) {
+        f32x4 z[TMAX];
+        if (wave < 2) {
+            load_image<H / 4>(w, a.lin_w[j], wave, lane);
+            const float4 b4 = *reinterpret_cast<const float4 *>(a.lin_b[j] + unit * 4);
+#pragma unroll
+            for (int t = 0; t < TMAX; ++t)
+                if (t < kt) {
+                    z[t] = chain<H / 4, HR>(w, &xbuf[t][jb][0], f32x4{b4.x, b4.y, b4.z, b4.w});
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) z[t][e] = z[t][e] >= 0.f ? z[t][e] : a.slope * z[t][e];
+                }
+        }
+        __syncthreads();
+        if (wave < 2) {
+#pragma unroll
+            for (int t = 0; t < TMAX; ++t)
+                if (t < kt) *reinterpret_cast<float4 *>(&xbuf[t][jb][unit * 4]) = make_float4(z[t][0], z[t][1], z[t][2], z[t][3]);
+        }
+        __syncthreads();
+    }
+    if (tid < kt * SEQ_TILE) {
+        const int t = tid / SEQ_TILE, j = tid % SEQ_TILE, b = tile * SEQ_TILE + j;
+        float acc = a.cls_b[0];
+        for (int k = 0; k < H; ++k) acc = __builtin_fmaf(a.cls_w[k], xbuf[t][j][k], acc);
+        if (t < s_k[j]) {   // (k_j > 0 only for a live slot b < B)
+            if (a.logits) a.logits[(size_t)b * a.ld_out + t] = acc;
+            if (a.probs) a.probs[(size_t)b * a.ld_out + t] = 1.0f / (1.0f + expf(-acc));
+        }
+    }
+}
+
 }  // namespace
 
 size_t lstm_image_elems(int K) { return (size_t)4 * H * K; }
@@ -329,6 +535,41 @@ hipError_t launch_lstm_stack(const LstmStackArgs &a, hipStream_t s) {
         default: return hipErrorInvalidValue;
     }
 #undef UVAD_STACK_LAUNCH
+    return hipGetLastError();
+}
+
+// the slot form's rows are whole images [tail | chunk] of frame_len + chunk samples (any of a step's frames can start anywhere in them)
+size_t lstm_stack_slots_lds_bytes(const FbankArgs &fb, int chunk) {
+    if (!fb.tab.mel_wt || !fb.tab.tw512 || chunk < 1 || fb.n_mels > 128) return 0;
+    const size_t tot = (size_t)fb.frame_len + chunk, img_ld = (tot + 3) & ~(size_t)3;
+    const size_t melw = mel_image_floats(fb.tab.mel_stride, fb.n_mels);
+    const size_t bytes = (SEQ_TILE * img_ld + melw + (size_t)WAVES * 2 * fbp::ZB_ELEMS) * sizeof(float);
+    return bytes <= 120 * 1024 ? bytes : 0;
+}
+
+hipError_t launch_lstm_stack_slots(const LstmStackSlotsArgs &q, hipStream_t s) {
+    const LstmStackArgs &a = q.st;
+    if (a.tiles <= 0 || a.B <= 0 || a.tiles != (a.B + SEQ_TILE - 1) / SEQ_TILE) return hipErrorInvalidValue;
+    if (!lstm_stack_supported(H, 1, a.kin0, q.kmax, a.n_layers) || !a.h || !a.c) return hipErrorInvalidValue;
+    if (!q.chunk || !q.n || !q.e || !q.active || !q.tail || !q.counts || q.chunk_len < 1) return hipErrorInvalidValue;
+    if ((!a.logits && !a.probs) || a.n_lin < 0 || a.n_lin > LSTM_STACK_MAX_LIN || !a.cls_w || !a.cls_b || a.ld_out < q.kmax) return hipErrorInvalidValue;
+    if ((long long)a.tiles * SEQ_TILE * (a.ld_out > H ? a.ld_out : H) >= (1LL << 31)) return hipErrorInvalidValue;   // 32-bit offsets in the kernel
+    const size_t lds = lstm_stack_slots_lds_bytes(a.fb, q.chunk_len);
+    if (!lds || a.fb.n_mels != a.kin0) return hipErrorInvalidValue;
+    const dim3 grid(a.tiles), block(WAVES * 64);
+#define UVAD_STACK_SLOTS_LAUNCH(K_)                                                                                                        \
+    if (lds > 40 * 1024) {                                                                                                                 \
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(lstm_stack_slots_kernel<K_>),                              \
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                    \
+        if (e != hipSuccess) return e;                                                                                                     \
+    }                                                                                                                                      \
+    hipLaunchKernelGGL((lstm_stack_slots_kernel<K_>), grid, block, lds, s, q);
+    switch (a.kin0) {
+        case 64: UVAD_STACK_SLOTS_LAUNCH(64) break;
+        case 80: UVAD_STACK_SLOTS_LAUNCH(80) break;
+        default: return hipErrorInvalidValue;
+    }
+#undef UVAD_STACK_SLOTS_LAUNCH
     return hipGetLastError();
 }
 

@@ -113,6 +113,7 @@ struct uvad_ctx {
     std::map<void *, WindowGroup> windows;      // ... and of the windowed stream groups (uvad_window_*)
     std::map<void *, WavWindowGroup> wav_windows;   // ... and of the waveform model's windowed stream groups (uvad_window_wav_*)
     std::map<void *, SlotPool> slot_pools, wav_slot_pools;   // ... and of the slot pools of both window families (uvad_window_*slots_*)
+    std::map<void *, SlotPool> stream_slot_pools;   // ... and of the causal stream's slot pools (uvad_stream_slots_*): B and chunk
     std::map<void *, EndpointPool> endpoints;   // ... and of the endpointer states (uvad_endpoint_*)
     std::map<void *, EndpointHystPool> endpoint_hysts;   // ... and of the hysteresis endpointer states (uvad_endpoint_hyst_*)
     std::map<void *, GatePool> gates;           // ... and of the speech gate states (uvad_gate_*)
@@ -2436,6 +2437,133 @@ int uvad_window_wav_slots_features(uvad_ctx *c, const void *d_state, int B, floa
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemcpyAsync(d_feats, st + SL.off_feats, (size_t)B * g.W * c->sc.c3 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     HIPCHK(c, hipMemcpyAsync(d_tw, ctr.tw_last, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+// ---- the causal stream's slot pool (lstm_stack.hip, the slot form) ------------------------------------------------------------------
+// One launch per step, and nothing of a step on the host: the pool exists where the one-launch step of uvad_stream_step exists (feature
+// stage, every layer and the head in lstm_stack_kernel), and reset refuses everything else -- the per-layer paths take one T per launch
+// from host counters and stay with the lockstep groups.
+// state (256-aligned blocks): tail [B][frame_len] f32 (in place) | h [layers][Bpad][128] | c likewise | n [B] int64 | e [B] int64 |
+//                             active [B] int32.  The workspace is not used (a token size keeps the calling convention of the pools).
+extern "C++" {
+namespace {
+struct StreamSlotsLayout { size_t off_tail = 0, off_h = 0, off_c = 0, off_n = 0, off_e = 0, off_active = 0, layer_stride = 0, total = 0; };
+StreamSlotsLayout stream_slots_layout(const uvad_ctx *c, int B) {
+    StreamSlotsLayout L;
+    const size_t Bpad = (size_t)(B + SEQ_TILE - 1) / SEQ_TILE * SEQ_TILE;
+    size_t o = 0;
+    L.off_tail = o; o += align_up((size_t)B * c->fb.frame_len * sizeof(float));
+    L.layer_stride = align_up(Bpad * c->mc.hidden * sizeof(float));
+    L.off_h = o; o += L.layer_stride * c->mc.num_layers;
+    L.off_c = o; o += L.layer_stride * c->mc.num_layers;
+    L.off_n = o; o += align_up((size_t)B * sizeof(long long));
+    L.off_e = o; o += align_up((size_t)B * sizeof(long long));
+    L.off_active = o; o += align_up((size_t)B * sizeof(int));
+    L.total = o;
+    return L;
+}
+constexpr size_t STREAM_SLOTS_WS_BYTES = 256;
+int stream_slots_kmax(const uvad_ctx *c, int chunk) { return (chunk + c->fb.frame_shift - 1) / c->fb.frame_shift; }
+}  // namespace
+}  // extern "C++"
+
+int uvad_stream_slots_kmax(const uvad_ctx *c, int chunk) {
+    if (!c || !c->has_fb || chunk <= 0) return UVAD_E_ARG;
+    return stream_slots_kmax(c, chunk);
+}
+
+size_t uvad_stream_slots_state_bytes(const uvad_ctx *c, int B) {
+    if (!c || !c->has_fb || !c->has_model || B <= 0) return 0;
+    return stream_slots_layout(c, B).total;
+}
+
+size_t uvad_stream_slots_workspace_bytes(const uvad_ctx *c, int B, int chunk) {
+    if (!c || !c->has_fb || !c->has_model || B <= 0 || chunk <= 0) return 0;
+    return STREAM_SLOTS_WS_BYTES;
+}
+
+int uvad_stream_slots_reset(uvad_ctx *c, void *d_state, int B, int chunk, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    const std::string who = "uvad_stream_slots_reset: ";
+    if (!d_state || B <= 0 || chunk <= 0) return fail(c, UVAD_E_ARG, who + "bad argument");
+    if (!c->has_fb || !c->has_model) return fail(c, UVAD_E_STATE, who + "needs both a fbank and a model configuration");
+    const uvad_model_cfg &m = c->mc;
+    if (m.bidirectional) return fail(c, UVAD_E_UNSUPPORTED, who + "needs a causal model (lstm.bidirectional = False)");
+    if (c->fb.snip_edges) return fail(c, UVAD_E_UNSUPPORTED, who + "the centred (snip_edges = 0) framing only");
+    if (c->fb.n_mels != m.in_dim) return fail(c, UVAD_E_ARG, who + "n_mels != encoding_dim");
+    if (m.hidden != 128 || (m.in_dim != 64 && m.in_dim != 80) || m.num_layers < 1 || m.num_layers > LSTM_STACK_MAX_LAYERS)
+        return fail(c, UVAD_E_UNSUPPORTED, who + "the one-launch step needs hidden_size 128, 64 or 80 features and 1 .. " +
+                                               std::to_string(LSTM_STACK_MAX_LAYERS) + " layers (got " + std::to_string(m.hidden) + ", " +
+                                               std::to_string(m.in_dim) + ", " + std::to_string(m.num_layers) +
+                                               "); other models stream in lockstep groups (uvad_stream_step)");
+    if (m.lin_layers > LSTM_STACK_MAX_LIN || (m.lin_layers > 0 && m.lin_hidden != 128))
+        return fail(c, UVAD_E_UNSUPPORTED, who + "the in-launch head needs at most " + std::to_string(LSTM_STACK_MAX_LIN) +
+                                               " feed-forward layers, each 128 -> 128 (got " + std::to_string(m.lin_layers) + " of " +
+                                               std::to_string(m.lin_hidden) + " units)");
+    const int n_left = (c->fb.frame_len - c->fb.frame_shift) / 2, kmax = stream_slots_kmax(c, chunk);
+    if (chunk < n_left)
+        return fail(c, UVAD_E_ARG, who + "every step can be a session's first: chunk must hold at least (frame_len - shift) / 2 = " +
+                                       std::to_string(n_left) + " samples");
+    if (kmax > LSTM_STACK_TMAX)
+        return fail(c, UVAD_E_ARG, who + "a step completes up to ceil(chunk / frame_shift) = " + std::to_string(kmax) + " frames, the one-launch step takes " +
+                                       std::to_string(LSTM_STACK_TMAX) + ": chunk <= " + std::to_string(LSTM_STACK_TMAX * c->fb.frame_shift) + " samples");
+    if (!c->finalized || !c->tables_set) return fail(c, UVAD_E_STATE, who + "context not ready (tables / weights)");
+    if (!stream_uses_stack(c, kmax) || !stream_head_in_stack(c))
+        return fail(c, UVAD_E_UNSUPPORTED, who + "the weights have no one-launch form (lstm_stack.hip)");
+    if (!lstm_stack_slots_lds_bytes(fbank_cfg_args(c), chunk))
+        return fail(c, UVAD_E_UNSUPPORTED, who + "the feature stage (4 rows of frame_len + chunk samples, the mel image, the transform scratch) "
+                                               "exceeds the 120 KiB of LDS beside the stack");
+    if ((int64_t)B * std::max(c->fb.frame_len, 128) * m.num_layers >= ((int64_t)1 << 31))
+        return fail(c, UVAD_E_ARG, who + "B too large");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemsetAsync(d_state, 0, stream_slots_layout(c, B).total, (hipStream_t)stream));
+    SlotPool g;
+    g.B = B; g.chunk = chunk;
+    c->stream_slot_pools[d_state] = g;
+    return UVAD_OK;
+}
+
+int uvad_stream_slots_step(uvad_ctx *c, const float *d_pcm_chunk, const uint8_t *d_flags, int B, int chunk, void *d_state, float *d_logits,
+                           float *d_probs, int ld_out, int32_t *d_counts, void *ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    const std::string who = "uvad_stream_slots_step: ";
+    if (!d_pcm_chunk || !d_state || (!d_logits && !d_probs) || !d_counts || !ws || B <= 0 || chunk <= 0) return fail(c, UVAD_E_ARG, who + "bad argument");
+    if (!c->finalized || !c->has_fb || !c->tables_set) return fail(c, UVAD_E_STATE, who + "context not ready (tables / weights)");
+    auto it = c->stream_slot_pools.find(d_state);
+    if (it == c->stream_slot_pools.end()) return fail(c, UVAD_E_STATE, who + "call uvad_stream_slots_reset on this state first");
+    const SlotPool &g = it->second;
+    if (B != g.B) return fail(c, UVAD_E_ARG, who + "B differs from the one the state was reset with");
+    if (chunk != g.chunk) return fail(c, UVAD_E_ARG, who + "chunk differs from the one the state was reset with");
+    const int kmax = stream_slots_kmax(c, chunk);
+    if (ld_out < kmax) return fail(c, UVAD_E_ARG, who + "ld_out must be at least ceil(chunk / frame_shift) = " + std::to_string(kmax));
+    if (ws_bytes < STREAM_SLOTS_WS_BYTES)
+        return fail(c, UVAD_E_WORKSPACE, "stream slot pool workspace too small: need " + std::to_string(STREAM_SLOTS_WS_BYTES) + " bytes");
+    // (weights loaded since the reset: the scope is checked again, nothing is enqueued outside it)
+    if (c->mc.bidirectional || !stream_uses_stack(c, kmax) || !stream_head_in_stack(c))
+        return fail(c, UVAD_E_UNSUPPORTED, who + "the model has no one-launch step");
+    const uvad_model_cfg &m = c->mc;
+    const PackedWeights &W = *c->packed;
+    const StreamSlotsLayout S = stream_slots_layout(c, B);
+    char *st = reinterpret_cast<char *>(d_state);
+    HIPCHK(c, hipSetDevice(c->device));
+    LstmStackSlotsArgs q{};
+    LstmStackArgs &a = q.st;
+    a.kin0 = m.in_dim; a.n_layers = m.num_layers;
+    for (int k = 0; k < m.num_layers; ++k) { a.wih[k] = W.layers[k].w_ih_img; a.whh[k] = W.layers[k].w_hh; a.bias[k] = W.layers[k].bias; }
+    a.h = reinterpret_cast<float *>(st + S.off_h); a.c = reinterpret_cast<float *>(st + S.off_c); a.layer_stride = S.layer_stride / sizeof(float);
+    a.tiles = (B + SEQ_TILE - 1) / SEQ_TILE; a.B = B;
+    for (int j = 0; j < m.lin_layers; ++j) { a.lin_w[j] = W.lin_w_img[j]; a.lin_b[j] = W.lin_b[j]; }
+    a.n_lin = m.lin_layers; a.cls_w = W.cls_w; a.cls_b = W.cls_b; a.slope = m.leaky_slope;
+    a.logits = d_logits; a.probs = d_probs; a.ld_out = ld_out;
+    a.fb = fbank_cfg_args(c); a.fb_on = 1;
+    q.chunk = d_pcm_chunk; q.chunk_len = chunk; q.flags = d_flags; q.kmax = kmax;
+    q.n = reinterpret_cast<long long *>(st + S.off_n); q.e = reinterpret_cast<long long *>(st + S.off_e);
+    q.active = reinterpret_cast<int *>(st + S.off_active);
+    q.tail = reinterpret_cast<float *>(st + S.off_tail);
+    q.counts = d_counts;
+    HIPCHK(c, launch_lstm_stack_slots(q, (hipStream_t)stream));
+    c->rec_tile_used = 4;
     return UVAD_OK;
 }
 

@@ -367,6 +367,21 @@ struct LstmStackArgs {
 size_t lstm_stack_fb_lds_bytes(const FbankArgs &fb, int T);
 bool lstm_stack_supported(int hidden, int dirs, int in_dim, int T, int n_layers);
 hipError_t launch_lstm_stack(const LstmStackArgs &a, hipStream_t s);
+// The slot form (uvad_stream_slots_step): the same launch for a pool of B slots with a session each.  st as for a one-launch step with
+// the head and the feature stage inside (weights, h / c, head, logits and / or probs, ld_out, tiles, B; fb: the front-end configuration
+// and tables only) -- st.T, st.feats, st.Y*, st.fb.vs_* are not read: every slot's T, offset and first-chunk status come from the flag
+// bytes and the counters below, on the device.
+struct LstmStackSlotsArgs {
+    LstmStackArgs st;
+    const float *chunk; int chunk_len;            // this step's samples [B][chunk_len]; an idle slot's row is never read
+    const uint8_t *flags;                         // [B] UVAD_SLOT_START | UVAD_SLOT_END, or nullptr
+    int kmax;                                     // ceil(chunk_len / frame_shift) <= LSTM_STACK_TMAX
+    long long *n, *e; int *active;                // per slot: samples and frames since the session's start, whether it holds a session
+    float *tail;                                  // [B][frame_len]: the last frame_len samples of each session, updated in place
+    int *counts;                                  // [B] frames emitted this step (0 for an idle slot)
+};
+size_t lstm_stack_slots_lds_bytes(const FbankArgs &fb, int chunk);   // dynamic LDS of the slot form (0 if it cannot run)
+hipError_t launch_lstm_stack_slots(const LstmStackSlotsArgs &a, hipStream_t s);
 size_t lstm_image_elems(int K);
 void pack_lstm_image(const float *w /*[4 * 128][K], torch row order*/, int K, float *out);
 size_t fc_image_elems();                                                   // a 128 x 128 feed-forward matrix as a register image

@@ -141,6 +141,33 @@ def wav_window_slots_plan(flags, chunk: int, window: int, lookahead: int = 0, J:
     return _slots_plan(flags, (lambda n: 0 if n < R else (n - R) // J + 1, chunk), window, lookahead)
 
 
+STREAM_SLOTS_KMAX = 4       # LSTM_STACK_TMAX (csrc/uvad_internal.h): the frames a one-launch step takes
+
+
+def stream_slots_kmax(chunk: int, frame_shift: int = 160) -> int:
+    """The most frames a step of a causal stream's slot pool completes, and the least ld_out it accepts: ceil(chunk / frame_shift)
+    (uvad_stream_slots_kmax)."""
+    return -(-chunk // frame_shift)
+
+
+def stream_slots_plan(flags, chunk: int, frame_len: int = 400, frame_shift: int = 160):
+    """The frames each step of a causal stream's slot pool (uvad_stream_slots_step, include/uvad.h) emits, in closed form.  flags: per
+    step, one flag per slot (bit 0 UVAD_SLOT_START, bit 1 UVAD_SLOT_END).  -> per step, per slot (session, emit_lo, emit_hi, frames) as
+    window_slots_plan with lookahead 0: a frame is emitted in the step in which its last sample arrives, and the END step emits what its
+    chunk completes and nothing more."""
+    n_left = (frame_len - frame_shift) // 2
+    if chunk < n_left:
+        raise ValueError(f"every step can be a session's first: chunk must hold at least (frame_len - shift) / 2 = {n_left} samples")
+    if stream_slots_kmax(chunk, frame_shift) > STREAM_SLOTS_KMAX:
+        raise ValueError(f"a step completes up to ceil(chunk / frame_shift) = {stream_slots_kmax(chunk, frame_shift)} frames, the one-launch "
+                         f"step takes {STREAM_SLOTS_KMAX}: chunk <= {STREAM_SLOTS_KMAX * frame_shift} samples")
+
+    def frames(n):
+        return (n + n_left - frame_len) // frame_shift + 1 if n + n_left - frame_len >= 0 else 0
+
+    return _slots_plan(flags, (frames, chunk), 1, 0)
+
+
 def sliding_count(frames: int, window: int, hop: int) -> int:
     """Windows that cover a recording of `frames` frames (uvad_sliding_count, include/uvad.h): 0 for an empty one, 1 up to a window's
     length, else ceil((frames - window) / hop) + 1: window j starts at frame j * hop and holds min(window, frames - j * hop) frames."""
@@ -950,6 +977,45 @@ class VadRuntime:
             self._check(self.lib.uvad_window_wav_slots_features(self.ctx, st["state"].data_ptr(), st["B"], feats.data_ptr(), tw.data_ptr(),
                                                                 self._stream()))
             return feats, tw
+
+    # ------------------------------------------------------------------ the causal stream's slot pool (uvad_stream_slots_*)
+    def stream_slots_open(self, B: int, chunk: int, graphs: bool = False, endpoint=None, gate=None, fuse=None, group_gate=None):
+        """Allocate and reset a slot pool of the causal streaming step (uvad_stream_slots_reset): B slots stepping `chunk` samples at a
+        time, each holding at most one session, one launch per step.  The pool exists where stream_step is one launch (a causal model with
+        128 hidden units, 64 or 80 features, up to 8 layers, a 128-wide head; chunks of up to 4 frame shifts): anything else raises.
+        graphs: capture the first step into a hipGraph and replay it for every later step.  endpoint / gate / fuse / group_gate: as
+        window_slots_open, with lookahead 0.  The outputs are stream_slots_kmax(chunk) columns wide."""
+        if group_gate is not None:
+            from .postprocess import group_gate_config
+            group_gate_config(group_gate, fuse, endpoint)                    # refused before anything is allocated
+        stream_slots_plan([], chunk, self._fb_c.frame_len, self._fb_c.frame_shift)   # the limits, before allocating
+        n_left = (self._fb_c.frame_len - self._fb_c.frame_shift) // 2
+        with torch.cuda.device(self.device):
+            nbytes = int(self.lib.uvad_stream_slots_state_bytes(self.ctx, B))
+            if nbytes == 0:
+                raise RuntimeError("slot pools need a runtime built with both a FbankConfig and a model")
+            state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._check(self.lib.uvad_stream_slots_reset(self.ctx, state.data_ptr(), B, chunk, self._stream()))
+            ws = torch.empty(int(self.lib.uvad_stream_slots_workspace_bytes(self.ctx, B, chunk)), dtype=torch.uint8, device=self.device)
+            ld = stream_slots_kmax(chunk, self._fb_c.frame_shift)
+            return self._slots_endpoint(
+                {"state": state, "ws": ws, "B": B, "chunk": chunk, "lookahead": 0,
+                 "out": torch.empty((B, ld), dtype=torch.float32, device=self.device),
+                 "counts": torch.zeros(B, dtype=torch.int32, device=self.device),
+                 "in": torch.empty((B, chunk), dtype=torch.float32, device=self.device),
+                 "flags": torch.zeros(B, dtype=torch.uint8, device=self.device),
+                 "graphs": 0 if graphs else None, "graph": None, "weights_gen": getattr(self, "_weights_gen", 0)}, endpoint, gate,
+                (self._fb_c.frame_shift, n_left, self._fb_c.frame_len - self._fb_c.frame_shift - n_left), fuse, group_gate)
+
+    def stream_slots_step(self, st, pcm_chunk: "torch.Tensor", start=None, end=None):
+        """pcm_chunk (B, chunk) f32 on the GPU; start / end as window_slots_step.  -> (logits (B, kmax), counts int32 (B,)), both on the
+        device and overwritten by the next step: row b holds the counts[b] frames slot b completes with this chunk in its first columns
+        (stream_slots_plan says which).  There is no peek / advance: under graphs=True every step replays the one captured graph."""
+        with torch.cuda.device(self.device):
+            pcm_chunk = self._dev_f32(pcm_chunk, "pcm_chunk")
+            if tuple(pcm_chunk.shape) != (st["B"], st["chunk"]):
+                raise ValueError(f"expected a ({st['B']}, {st['chunk']}) chunk, got {tuple(pcm_chunk.shape)}")
+            return self._slots_step(st, pcm_chunk, start, end, self.lib.uvad_stream_slots_step)
 
     # ------------------------------------------------------------------ live endpointing (uvad_endpoint_*)
     def endpoint_open(self, B: int, ld_in: int, kernel: int = 25, pad: int = 0, threshold: float = 0.5, max_events=None):
