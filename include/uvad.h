@@ -1121,6 +1121,78 @@ int uvad_gate_group_step(uvad_ctx *, const void *d_chunk, int chunk, int B, cons
                          void *d_state, size_t state_bytes, void *d_out, int64_t ld_out, uvad_gate_seg *d_seg, int max_seg,
                          int32_t *d_seg_counts, void *stream);
 
+/* ---- Head fine-tuning on the device: loss gradient, backward pass, Adam ------------------------------------------------------------------
+ * The LSTM stack stays frozen; the feed-forward layers and the classifier learn from the last LSTM layer's output x0 [B][T][D0]
+ * (D0 = hidden x directions: what uvad_get_taps writes to d_lstm_out, which a caller may cache across epochs).  Replaces, for that
+ * slice of the model, VadModel.training_step / _common_step (src/engines/vad_engine.py:247-278: the head expression of
+ * PyanNet2.forward, F.leaky_relu(linear(x)) and sigmoid(classifier(x)), F.binary_cross_entropy with the mean over the frames present,
+ * src/utils/loss.py:56-89, and autograd's backward pass through them) and configure_optimizers (:280: torch.optim.Adam, no weight decay).
+ * Gradients into the LSTM stack or a SincNet front end, dropout, weight decay, schedules and DDP are not here; d_grad_x is where a
+ * backward pass through the LSTM stack would start.
+ *
+ * With s = leaky_slope, a_0 = x0, a_l = leaky_relu(a_{l-1} W_l^T + b_l, s) for l = 1 .. L, z = a_L . w_c + b_c, p = sigmoid(z), a frame
+ * (b, t) is valid iff t < len_b = clamp(d_lens[b], 0, T) (T when d_lens is NULL).  A valid frame with label y = (d_gt != 0) and weight w
+ * (d_fw, 1 when NULL) adds  w * -(y max(log p, -100) + (1 - y) max(log(1 - p), -100))  (f64, from the f32 p) to the loss sum and has
+ *   dz = w * ((p - y) * (q / max(q, 1e-12))),  q = p * (1 - p)
+ * every operation one f32 rounding in that order (autograd's gradient of BCE on sigmoid(z), saturation included: 0 where p rounds to 0
+ * or 1).  Frames past a length have dz = 0, add nothing, and are never read in d_x, d_gt, d_fw or d_dz.  A non-NULL d_dz [B][ld_dz]
+ * replaces the loss-derived dz (the caller's own loss): d_gt and d_fw are then ignored and may be NULL, and no loss is accumulated.
+ * The backward pass is d_L = (dz w_c) * leaky'(a_L), dW_l = sum_n d_l[n]^T a_{l-1}[n], db_l = sum_n d_l[n],
+ * d_{l-1} = (d_l W_l) * leaky'(a_{l-1}) with leaky' = 1 where the stored activation is > 0 and s elsewhere.
+ *
+ * uvad_head_train_grad runs the forward pass with the STATE's f32 master weights (not the context's packed ones), and ADDS the
+ *   gradients of the summed loss into the state's accumulator, the loss into its f64 sum and the valid frames into its count; any
+ *   number of calls (micro-batches) may precede a step.  d_probs [B][ld_p] (may be NULL) receives p at valid frames, columns past a
+ *   length are not written; d_grad_x [B][T][D0] (may be NULL) receives dL/dx0 of the summed loss and +0 at frames past a length.
+ *   After the call the workspace's first 16 bytes hold {double loss sum, uint64 valid frames} of THAT call.
+ *   All products run on the exact f32 matrix instruction (a k-ordered fma chain); the frames are reduced per segment of `segment` frames
+ *   (flat index b T + t) and the partials folded in segment order: no floating-point atomics, the same calls give the same bits.
+ * uvad_head_train_apply: one Adam step with g = accumulator / count, then the accumulator, loss sum and count are zeroed and t advances.
+ *   A zero count does nothing.  The bias corrections c_t = 1 - beta^t are kept in the state as f32 values advanced once per step,
+ *   c <- c beta + (1 - beta) from 0, so one captured graph serves every step (tests/head_train_ref.py restates the step operation by
+ *   operation).  The complement is kept, not the product beta^t: 1 - (f32 nearest 0.999)^t is 1.3e-5 off at every t.
+ * grad and apply allocate nothing, never synchronise and read lengths and counts from the device: any sequence of them can be captured
+ *   in one graph and replayed with new data.
+ * uvad_head_train_read copies out (device memory): which = UVAD_HEAD_TRAIN_MASTERS / _GRAD / _M / _V: the P floats of the trainable
+ *   tensors packed in state_dict order -- linear.0.weight [H][D0], linear.0.bias [H], linear.l.weight [H][H], linear.l.bias [H], ...,
+ *   classifier.weight [1][K_L], classifier.bias [1] (K_L = H, or D0 when lin_layers is 0), P = uvad_head_train_param_count;
+ *   which = UVAD_HEAD_TRAIN_SCALARS: UVAD_HEAD_TRAIN_SCALAR_WORDS 32-bit words: [0 .. 1] the accumulated loss sum (bits of a double, low
+ *   word first), [2 .. 3] the accumulated valid frames (uint64), [4 .. 5] t (uint64), [6] 1 - beta1^t, [7] 1 - beta2^t (f32).
+ * uvad_head_train_commit synchronises the device, then feeds the masters through uvad_set_weight + uvad_finalize: from then on
+ *   uvad_classify and every stream of THIS context serve the adapted head.  As for uvad_finalize: graphs captured earlier hold the old
+ *   weight buffers, which are freed here -- capture them again; contexts that shared the upload block keep the old weights.
+ * State: uvad_head_train_state_bytes (0 before configure).  Workspace: uvad_head_train_ws_bytes(ctx, B, T) (0 on a bad argument): the
+ *   kept activations lin_layers x B T x lin_hidden floats, two gradient buffers of B T x lin_hidden, ceil(B T / segment) x P partials.
+ * Served: D0 any multiple of 32 up to 2048; lin_layers 0 .. 4; lin_hidden a multiple of 32 in 32 .. 256; leaky_slope > 0 (the factor
+ *   leaky' is read from the sign of the stored activation).  uvad_head_train_configure returns UVAD_E_UNSUPPORTED for any other head
+ *   that uvad_create accepts.  PyanNet2 and PyanNet (SincNet front end) contexts alike.
+ * Refusals (nothing enqueued).  UVAD_E_ARG: NULL cfg / d_x / d_state / d_ws / d_out; both d_gt and d_dz NULL; lr not finite or <= 0;
+ *   beta1 / beta2 outside [0, 1) or not finite; eps not finite or <= 0; segment not 0 or a multiple of 32 in 32 .. 16384; B < 1; T < 1;
+ *   B T > 2^24 or more than 65535 segments; ld_gt / ld_fw / ld_dz / ld_p below T (for the pointers given); state_bytes or ws_bytes below the helpers; which outside
+ *   0 .. 4.  UVAD_E_STATE: a context without a model; no uvad_head_train_configure yet; a context that is not finalized (reset,
+ *   commit); a state that was never reset, or reset under another head shape.  UVAD_E_UNSUPPORTED: see above. */
+#define UVAD_HEAD_TRAIN_MASTERS 0
+#define UVAD_HEAD_TRAIN_GRAD 1
+#define UVAD_HEAD_TRAIN_M 2
+#define UVAD_HEAD_TRAIN_V 3
+#define UVAD_HEAD_TRAIN_SCALARS 4
+#define UVAD_HEAD_TRAIN_SCALAR_WORDS 8
+typedef struct {
+    float lr, beta1, beta2, eps;
+    int segment;                             /* frames per gradient partial, 0 = default (2048) */
+} uvad_head_train_cfg;
+int uvad_head_train_configure(uvad_ctx *, const uvad_head_train_cfg *);
+int64_t uvad_head_train_param_count(const uvad_ctx *);   /* P; 0 before uvad_head_train_configure */
+size_t uvad_head_train_state_bytes(const uvad_ctx *);
+size_t uvad_head_train_ws_bytes(const uvad_ctx *, int B, int T);
+int uvad_head_train_reset(uvad_ctx *, void *d_state, size_t state_bytes, void *stream);
+int uvad_head_train_grad(uvad_ctx *, const float *d_x, int B, int T, const int32_t *d_lens, const uint8_t *d_gt, int ld_gt,
+                         const float *d_fw, int ld_fw, const float *d_dz, int ld_dz, float *d_probs, int ld_p, float *d_grad_x,
+                         void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream);
+int uvad_head_train_apply(uvad_ctx *, void *d_state, size_t state_bytes, void *stream);
+int uvad_head_train_read(uvad_ctx *, const void *d_state, size_t state_bytes, int which, float *d_out, void *stream);
+int uvad_head_train_commit(uvad_ctx *, const void *d_state, size_t state_bytes);
+
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;
  *   1  (default) f32-accurate on the f16 matrix cores: weights scaled by a power of two and split on the host into THREE

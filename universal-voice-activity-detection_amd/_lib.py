@@ -51,6 +51,14 @@ class ScoreCfg(C.Structure):
 CUTS_SAMPLES, CUTS_FRAMES = 0, 1     # `which` of uvad_cuts_gather
 
 
+HEAD_TRAIN_MASTERS, HEAD_TRAIN_GRAD, HEAD_TRAIN_M, HEAD_TRAIN_V, HEAD_TRAIN_SCALARS = range(5)   # `which` of uvad_head_train_read
+HEAD_TRAIN_SCALAR_WORDS = 8      # 32-bit words of the scalar record (include/uvad.h gives the layout)
+
+
+class HeadTrainCfg(C.Structure):     # uvad_head_train_cfg (20 bytes)
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("segment", C.c_int)]
+
+
 class CutsCfg(C.Structure):
     _fields_ = [("pad", C.c_int), ("max_len", C.c_int), ("min_len", C.c_int), ("hop", C.c_int), ("lead", C.c_int), ("tail", C.c_int)]
 
@@ -197,6 +205,17 @@ SIGNATURES = {
     "uvad_score_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                   C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_score_totals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "uvad_head_train_configure": (C.c_int, [C.c_void_p, C.POINTER(HeadTrainCfg)]),
+    "uvad_head_train_param_count": (C.c_int64, [C.c_void_p]),
+    "uvad_head_train_state_bytes": (C.c_size_t, [C.c_void_p]),
+    "uvad_head_train_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "uvad_head_train_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_head_train_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                       C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                       C.c_void_p]),
+    "uvad_head_train_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_head_train_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "uvad_head_train_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "uvad_cuts_max_per_row": (C.c_int, [C.POINTER(CutsCfg), C.c_int]),
     "uvad_cuts_max_samples": (C.c_int64, [C.POINTER(CutsCfg), C.c_int64]),
     "uvad_cuts_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),

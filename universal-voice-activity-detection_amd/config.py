@@ -21,7 +21,7 @@ def load_config() -> ConfigDict:
     cfg = ConfigDict()
 
     cfg.task = "run"            # only "run" is in scope (reference: wer/download/prepare/... are data plumbing)
-    cfg.function = "predict"    # "predict" | "test" (scoring against label files: input.labels)
+    cfg.function = "predict"    # "predict" | "test" (scoring against label files: input.labels) | "adapt" (head fine-tuning on them)
 
     cfg.seed = 42
     cfg.device = "gpu"          # the HIP path needs a GPU; "cpu" raises (no fallback)
@@ -85,6 +85,13 @@ def load_config() -> ConfigDict:
     cfg.weights_seed = 1234     # used when load_checkpoint is False (no checkpoint ships with the reference)
     cfg.weights_scale = 4.0
 
+    # function == "adapt" (scripts.adapt_vad): the feed-forward layers and the classifier learn, the LSTM stack stays frozen
+    cfg.learning_rate = 1e-3
+    cfg.max_epochs = 10
+    cfg.check_val_every_n_epoch = 1
+    cfg.accumulate_grad_batches = 1
+    cfg.adapted_checkpoint_path = ""    # "" = experiments_dir/adapted.ckpt
+
     cfg.predict_output_dir = os.environ.get("UVAD_PREDICT_DIR", "")   # "" = do not write files
     cfg.window_type = "povey"   # lhotse default; BASELINE cfg 2 uses "hamming"
 
@@ -94,6 +101,8 @@ def load_config() -> ConfigDict:
     cfg.input.paths = []              # wav files when kind == "wav": 16 kHz 16-bit as they are; other rates, G.711 (A-law / mu-law) and
                                       # multi-channel files through the ingest stage (decode, channels to rows, resampling to 16 kHz)
     cfg.input.labels = []             # function == "test": one label file per path, `start<TAB>end<TAB>LABEL` lines (get_audacity_labels)
+    cfg.input.val_paths = []          # function == "adapt": held-out wav files and their label files (empty: the training files)
+    cfg.input.val_labels = []
     cfg.input.channels = "first"      # "first": channel 0 only (the reference's to_mono(mono_downmix=False)[0]); "all": every channel a
                                       # recording of its own, "-ch<N>" appended to its id
     cfg.input.num_utterances = 1

@@ -121,6 +121,10 @@ struct uvad_ctx {
     std::map<void *, ScoreState> scores;        // ... and of the scoring states (uvad_score_*)
     bool has_score = false;                     // uvad_score_configure: operating points, collar, bins, segment (0 replaced by the default)
     uvad_score_cfg sq{};
+    std::map<void *, int> head_trains;          // ... and of the head fine-tuning states (uvad_head_train_*): the parameter count at reset
+    bool has_ht = false;                        // uvad_head_train_configure: the optimiser (segment 0 replaced by the default) and the head's shape
+    uvad_head_train_cfg hq{};
+    HeadTrainShape hts{};
     int device = 0, n_cu = 256;
     bool has_fb = false, has_model = false, finalized = false, tables_set = false;
     uvad_fbank_cfg fb{};
@@ -3180,6 +3184,146 @@ int uvad_score_totals(uvad_ctx *c, const void *d_state, size_t state_bytes, uint
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, launch_score_totals(d_state, reinterpret_cast<unsigned long long *>(d_out), (hipStream_t)stream));
     return UVAD_OK;
+}
+
+// ---- head fine-tuning (head_train.hip) ----------------------------------------------------------------------------------------------------
+int uvad_head_train_configure(uvad_ctx *c, const uvad_head_train_cfg *q) {
+    if (!c) return UVAD_E_ARG;
+    if (!q) return fail(c, UVAD_E_ARG, "uvad_head_train_configure: bad argument");
+    if (!std::isfinite(q->lr) || !(q->lr > 0.0f)) return fail(c, UVAD_E_ARG, "uvad_head_train_configure: lr must be finite and positive");
+    if (!std::isfinite(q->beta1) || q->beta1 < 0.0f || !(q->beta1 < 1.0f)) return fail(c, UVAD_E_ARG, "uvad_head_train_configure: beta1 must lie in [0, 1)");
+    if (!std::isfinite(q->beta2) || q->beta2 < 0.0f || !(q->beta2 < 1.0f)) return fail(c, UVAD_E_ARG, "uvad_head_train_configure: beta2 must lie in [0, 1)");
+    if (!std::isfinite(q->eps) || !(q->eps > 0.0f)) return fail(c, UVAD_E_ARG, "uvad_head_train_configure: eps must be finite and positive");
+    if (q->segment != 0 && (q->segment < HT_MIN_SEGMENT || q->segment > HT_MAX_SEGMENT || q->segment % 32))
+        return fail(c, UVAD_E_ARG, "uvad_head_train_configure: segment must be 0 or a multiple of 32 in [32, 16384] frames");
+    if (!c->has_model) return fail(c, UVAD_E_STATE, "uvad_head_train_configure: context was created without a model configuration");
+    const uvad_model_cfg &m = c->mc;
+    const int D0 = m.hidden * (m.bidirectional ? 2 : 1);
+    if (D0 % 32 || D0 > HT_MAX_D0) return fail(c, UVAD_E_UNSUPPORTED, "uvad_head_train_configure: hidden x directions must be a multiple of 32, at most 2048");
+    if (m.lin_layers > HT_MAX_LAYERS) return fail(c, UVAD_E_UNSUPPORTED, "uvad_head_train_configure: at most 4 feed-forward layers");
+    if (m.lin_layers > 0 && (m.lin_hidden < 32 || m.lin_hidden > HT_MAX_HIDDEN || m.lin_hidden % 32))
+        return fail(c, UVAD_E_UNSUPPORTED, "uvad_head_train_configure: lin_hidden must be a multiple of 32 in [32, 256]");
+    if (m.lin_layers > 0 && !(m.leaky_slope > 0.0f))
+        return fail(c, UVAD_E_UNSUPPORTED, "uvad_head_train_configure: leaky_slope must be positive (the backward pass reads leaky' from the activation's sign)");
+    c->hq = *q;
+    if (c->hq.segment == 0) c->hq.segment = HT_DEFAULT_SEGMENT;
+    c->hts = head_train_shape(D0, m.lin_layers > 0 ? m.lin_hidden : 0, m.lin_layers, m.leaky_slope);
+    c->has_ht = true;
+    return UVAD_OK;
+}
+
+int64_t uvad_head_train_param_count(const uvad_ctx *c) { return c && c->has_ht ? (int64_t)c->hts.P : 0; }
+size_t uvad_head_train_state_bytes(const uvad_ctx *c) { return c && c->has_ht ? head_train_state_bytes(c->hts) : 0; }
+
+size_t uvad_head_train_ws_bytes(const uvad_ctx *c, int B, int T) {
+    if (!c || !c->has_ht || B < 1 || T < 1 || (long long)B * T > HT_MAX_FRAMES) return 0;
+    return head_train_ws(c->hts, (long long)B * T, c->hq.segment).total;
+}
+
+// the checks every call on a state shares; `reset`: the call that makes the state known
+static int head_train_state_check(uvad_ctx *c, const char *fn, const void *d_state, size_t state_bytes, bool reset) {
+    const std::string f(fn);
+    if (!d_state) return fail(c, UVAD_E_ARG, f + ": bad argument");
+    if (!c->has_ht) return fail(c, UVAD_E_STATE, f + ": call uvad_head_train_configure first");
+    const size_t need = head_train_state_bytes(c->hts);
+    if (state_bytes < need) return fail(c, UVAD_E_ARG, f + ": state too small: need " + std::to_string(need) + " bytes");
+    if (reset) return UVAD_OK;
+    auto it = c->head_trains.find(const_cast<void *>(d_state));
+    if (it == c->head_trains.end()) return fail(c, UVAD_E_STATE, f + ": call uvad_head_train_reset on this state first");
+    if (it->second != c->hts.P) return fail(c, UVAD_E_STATE, f + ": the state was reset under another head shape");
+    return UVAD_OK;
+}
+
+int uvad_head_train_reset(uvad_ctx *c, void *d_state, size_t state_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (int r = head_train_state_check(c, "uvad_head_train_reset", d_state, state_bytes, true)) return r;
+    if (!c->finalized) return fail(c, UVAD_E_STATE, "uvad_head_train_reset: call uvad_finalize first");
+    const HeadTrainShape &q = c->hts;
+    const PackedWeights &W = *c->packed;
+    HeadTrainInit in{};
+    for (int l = 0; l < q.L; ++l) { in.w[l] = W.lin_w[l]; in.b[l] = W.lin_b[l]; in.ldw[l] = gemm_padded_k(l ? q.H : q.D0); }
+    in.w[q.L] = W.cls_w; in.b[q.L] = W.cls_b; in.ldw[q.L] = q.L ? q.H : q.D0;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_head_train_reset(q, in, d_state, (hipStream_t)stream));
+    c->head_trains[d_state] = q.P;
+    return UVAD_OK;
+}
+
+int uvad_head_train_grad(uvad_ctx *c, const float *d_x, int B, int T, const int32_t *d_lens, const uint8_t *d_gt, int ld_gt,
+                         const float *d_fw, int ld_fw, const float *d_dz, int ld_dz, float *d_probs, int ld_p, float *d_grad_x,
+                         void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_x || !d_state || !d_ws || B < 1 || T < 1) return fail(c, UVAD_E_ARG, "uvad_head_train_grad: bad argument");
+    if ((long long)B * T > HT_MAX_FRAMES) return fail(c, UVAD_E_ARG, "uvad_head_train_grad: B x T above 2^24 frames");
+    if (!d_dz && !d_gt) return fail(c, UVAD_E_ARG, "uvad_head_train_grad: labels (d_gt) or a gradient (d_dz) must be given");
+    if (c->has_ht && ((long long)B * T + c->hq.segment - 1) / c->hq.segment > 65535)
+        return fail(c, UVAD_E_ARG, "uvad_head_train_grad: more than 65535 segments: B x T / segment too large");
+    if ((d_dz && ld_dz < T) || (!d_dz && ld_gt < T) || (!d_dz && d_fw && ld_fw < T) || (d_probs && ld_p < T))
+        return fail(c, UVAD_E_ARG, "uvad_head_train_grad: ld_gt, ld_fw, ld_dz and ld_p must be at least T");
+    if (int r = head_train_state_check(c, "uvad_head_train_grad", d_state, state_bytes, true)) return r;   // configured, and the state's size
+    const size_t need = head_train_ws(c->hts, (long long)B * T, c->hq.segment).total;
+    if (ws_bytes < need) return fail(c, UVAD_E_ARG, "uvad_head_train_grad: workspace too small: need " + std::to_string(need) + " bytes");
+    if (int r = head_train_state_check(c, "uvad_head_train_grad", d_state, state_bytes, false)) return r;  // ... and that it was reset
+    HeadTrainGradArgs a{};
+    a.x = d_x; a.B = B; a.T = T; a.lens = d_lens;
+    a.gt = d_dz ? nullptr : d_gt; a.ld_gt = ld_gt; a.fw = d_dz ? nullptr : d_fw; a.ld_fw = ld_fw; a.dz_in = d_dz; a.ld_dz = ld_dz;
+    a.probs = d_probs; a.ld_p = ld_p; a.grad_x = d_grad_x;
+    a.state = d_state; a.ws = d_ws; a.seg = c->hq.segment;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_head_train_grad(c->hts, a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_head_train_apply(uvad_ctx *c, void *d_state, size_t state_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (int r = head_train_state_check(c, "uvad_head_train_apply", d_state, state_bytes, false)) return r;
+    const uvad_head_train_cfg &q = c->hq;
+    // 1 - beta as torch hands it to lerp_ / addcmul_: the difference taken in f64 from the double the caller wrote (0.999, not the f32
+    // next to it, whose complement is 1.3e-5 off) -- the shortest decimal that rounds to the f32 given -- and rounded to f32 once
+    auto one_minus = [](float b) {
+        char buf[32];
+        double d = (double)b;
+        for (int p = 1; p <= 9; ++p) {
+            std::snprintf(buf, sizeof buf, "%.*g", p, (double)b);
+            d = std::strtod(buf, nullptr);
+            if ((float)d == b) break;
+        }
+        return (float)(1.0 - d);
+    };
+    const HeadTrainAdam o{q.lr, q.beta1, q.beta2, q.eps, one_minus(q.beta1), one_minus(q.beta2)};
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_head_train_apply(c->hts, o, d_state, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_head_train_read(uvad_ctx *c, const void *d_state, size_t state_bytes, int which, float *d_out, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_out || which < 0 || which > UVAD_HEAD_TRAIN_SCALARS) return fail(c, UVAD_E_ARG, "uvad_head_train_read: bad argument");
+    if (int r = head_train_state_check(c, "uvad_head_train_read", d_state, state_bytes, false)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_head_train_read(c->hts, d_state, which, d_out, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_head_train_commit(uvad_ctx *c, const void *d_state, size_t state_bytes) {
+    if (!c) return UVAD_E_ARG;
+    if (int r = head_train_state_check(c, "uvad_head_train_commit", d_state, state_bytes, false)) return r;
+    if (!c->finalized) return fail(c, UVAD_E_STATE, "uvad_head_train_commit: call uvad_finalize first");
+    const HeadTrainShape &q = c->hts;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());   // every enqueued grad / apply has landed
+    std::vector<float> w((size_t)q.P);
+    HIPCHK(c, hipMemcpy(w.data(), reinterpret_cast<const char *>(d_state) + sizeof(HeadTrainHeader), w.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int l = 0; l <= q.L; ++l) {
+        const bool cls = l == q.L;
+        const int K = cls ? (q.L ? q.H : q.D0) : (l ? q.H : q.D0), rows = cls ? 1 : q.H;
+        const std::string name = cls ? std::string("classifier") : "linear." + std::to_string(l);
+        const int64_t wshape[2] = {rows, K}, bshape[1] = {rows};
+        int r;
+        if ((r = uvad_set_weight(c, (name + ".weight").c_str(), w.data() + q.off_w[l], wshape, 2))) return r;
+        if ((r = uvad_set_weight(c, (name + ".bias").c_str(), w.data() + q.off_b[l], bshape, 1))) return r;
+    }
+    return uvad_finalize(c);
 }
 
 // ---- speech cuts (cuts.hip) --------------------------------------------------------------------------------------------------------------

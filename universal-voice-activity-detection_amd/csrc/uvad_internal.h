@@ -746,4 +746,48 @@ hipError_t launch_gate_group_reset(void *state, int G, int N, const CutsCfgInt &
                                    hipStream_t s);
 hipError_t launch_gate_group_step(const GateGroupArgs &a, int unit_bytes, hipStream_t s);
 
+// ---- head_train.hip: fine-tuning of the head (uvad_head_train_*, include/uvad.h): forward with kept activations, loss gradient, backward, Adam ----
+// Frames are flat, n = b T + t.  The trainable tensors are packed in state_dict order (linear.l.weight [H][K_l], linear.l.bias [H], ...,
+// classifier.weight [K_L], classifier.bias [1]; K_1 = D0, K_l = H after), P floats, padded to Pp = a multiple of 64.
+// State: HeadTrainHeader (256 bytes) | masters [Pp] | gradient accumulator [Pp] | m [Pp] | v [Pp].
+// Workspace: HeadTrainWsHead (256 bytes) | valid [N] bytes | dz [N] | activations [L][N][H] | two gradient buffers [N][H] (L > 0) |
+//            gradient partials [nseg][Pp] | loss partials [ceil(N / 256)] doubles; every part 256-byte aligned.
+constexpr int HT_MAX_LAYERS = 4, HT_MAX_HIDDEN = 256, HT_MAX_D0 = 2048;
+constexpr int HT_MIN_SEGMENT = 32, HT_MAX_SEGMENT = 1 << 14, HT_DEFAULT_SEGMENT = 2048;
+constexpr int HT_MAX_FRAMES = 1 << 24;               // B x T: flat frame arithmetic stays in int32
+constexpr int HT_LOSS_BLOCK = 256;                   // frames per loss partial
+constexpr unsigned HT_MAGIC = 0x55564854u;           // "UVHT"
+constexpr int HT_SCALAR_WORDS = 8;                   // UVAD_HEAD_TRAIN_SCALAR_WORDS
+struct HeadTrainShape {
+    int D0, H, L, P, Pp;
+    int off_w[HT_MAX_LAYERS + 1], off_b[HT_MAX_LAYERS + 1];   // entry L: the classifier
+    float slope;
+};
+struct HeadTrainHeader {
+    unsigned magic; int D0, H, L, P, pad0;
+    double loss; unsigned long long frames, t;       // accumulated since the last step: loss sum, valid frames; steps taken
+    // the bias corrections 1 - beta1^t, 1 - beta2^t, advanced once per step as c <- c beta + (1 - beta) from 0: one captured graph serves
+    // every step, and the value keeps f32 relative accuracy.  (The running PRODUCT beta^t of the f32 nearest to 0.999 is 1.3e-8 off per
+    // factor, which 1 - beta^t magnifies to 1.3e-5 at every t: the loss of a 20-step run then drifts 1e-3 from torch's, not 1e-6.)
+    float bc1, bc2;
+    int reserved[50];
+};                                                   // 256 bytes
+struct HeadTrainWsHead { double loss; unsigned long long frames; int reserved[60]; };   // of the last uvad_head_train_grad
+struct HeadTrainWs { size_t off_valid, off_dz, off_act, off_d[2], off_part, off_loss, total; int N, nseg; };
+struct HeadTrainGradArgs {
+    const float *x; int B, T; const int *lens;
+    const uint8_t *gt; int ld_gt; const float *fw; int ld_fw; const float *dz_in; int ld_dz;
+    float *probs; int ld_p; float *grad_x;
+    void *state; void *ws; int seg;
+};
+struct HeadTrainAdam { float lr, b1, b2, eps, omb1, omb2; };
+struct HeadTrainInit { const float *w[HT_MAX_LAYERS + 1], *b[HT_MAX_LAYERS + 1]; int ldw[HT_MAX_LAYERS + 1]; };   // the context's device copies
+HeadTrainShape head_train_shape(int D0, int H, int L, float slope);
+size_t head_train_state_bytes(const HeadTrainShape &q);
+HeadTrainWs head_train_ws(const HeadTrainShape &q, long long N, int seg);
+hipError_t launch_head_train_reset(const HeadTrainShape &q, const HeadTrainInit &in, void *state, hipStream_t s);
+hipError_t launch_head_train_grad(const HeadTrainShape &q, const HeadTrainGradArgs &a, hipStream_t s);
+hipError_t launch_head_train_apply(const HeadTrainShape &q, const HeadTrainAdam &o, void *state, hipStream_t s);
+hipError_t launch_head_train_read(const HeadTrainShape &q, const void *state, int which, float *out, hipStream_t s);
+
 }  // namespace uvad

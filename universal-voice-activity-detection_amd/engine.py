@@ -3,7 +3,8 @@ inference and scoring surface: constructor arguments, ``.model`` / ``.model_name
 ``predict_step``, ``test_step``, ``validation_step``, ``_common_step`` and ``load_from_checkpoint``
 keep their names, argument meaning and return shapes; what the reference logs through torchmetrics
 is accumulated on the device (``uvad_score_*``) and read with ``test_metrics`` / ``validation_metrics``.
-Training (``training_step``, Adam) is outside the accelerated path and raises."""
+``adapt_head_step`` / ``adapt_head_commit`` fine-tune the head on the device (``uvad_head_train_*``); full training
+(``training_step``, ``configure_optimizers``: back-propagation through the LSTM stack) is outside the accelerated path and raises."""
 import torch
 import torch.nn as nn
 
@@ -114,7 +115,52 @@ class VadModel(nn.Module):
     def validation_metrics(self, reset: bool = True) -> dict:
         return self._metrics("val", reset)
 
-    # -- training is out of scope --------------------------------------------------------------
+    # -- head adaptation: the feed-forward layers and the classifier learn, the LSTM stack stays frozen (uvad_head_train_*) ----------
+    def lstm_out(self, batch) -> torch.Tensor:
+        """The frozen encoder's output (batch, frames, hidden x directions) for batch["inputs"]: what adapt_head_step trains on, and what
+        a caller may cache across epochs as batch["lstm_out"]."""
+        x = batch["inputs"]
+        rt = self.model.runtime(x.device)
+        if self.model_name == "PyanNet":
+            x = rt.sincnet(x[:, 0, :] if x.dim() == 3 else x)
+        rt.classify(x, want_logits=False, lengths=batch.get("lengths"))
+        return rt.taps(lin=False)[0]
+
+    def adapt_head_step(self, batch, batch_idx=0, accumulate: int = 1):
+        """One micro-batch of head fine-tuning: batch["inputs"] through the frozen encoder (or batch["lstm_out"], cached taps, in its
+        place), binary cross-entropy against batch["is_voice"] over the frames inside batch["lengths"] (optional), the gradients of
+        linear.* and classifier.* accumulated on the device; every `accumulate` calls one Adam step (lr = self.learning_rate).
+        Returns the batch's mean loss as a 0-d tensor on the device without synchronising, as test_step does."""
+        y = batch.get("is_voice")
+        if y is None:
+            raise ValueError('adapt_head_step needs batch["is_voice"]')
+        x = batch["lstm_out"] if batch.get("lstm_out") is not None else self.lstm_out(batch)
+        rt = self.model.runtime(x.device)
+        held = getattr(self, "_adapt", None)
+        if held is None or held[0] is not rt:
+            held = self._adapt = [rt, rt.head_train_open(lr=self.learning_rate), 0]
+        gt = (y.to(x.device) != 0).to(torch.uint8).reshape(x.shape[:2])
+        rt.head_train_grad(held[1], x, gt, lengths=batch.get("lengths"))
+        held[2] += 1
+        if held[2] % max(1, int(accumulate)) == 0:
+            rt.head_train_apply(held[1])
+        return rt.head_train_batch_loss(held[1])
+
+    def adapt_head_commit(self):
+        """Serve the adapted head from now on (uvad_head_train_commit) and write it into self.model's parameters, so that state_dict()
+        and torch.save give the adapted checkpoint.  Synchronises."""
+        held = getattr(self, "_adapt", None)
+        if held is None:
+            raise RuntimeError("no adapt_head_step has run yet")
+        rt, h = held[0], held[1]
+        rt.head_train_commit(h)
+        params = dict(self.model.named_parameters())
+        with torch.no_grad():
+            for key, t in rt.head_train_state_dict(h).items():
+                params[key].copy_(t.to(params[key].device))
+        self.model._rt_stamp = self.model._stamp(rt.device)   # the runtime already holds these very tensors: no second upload
+
+    # -- full training is out of scope -----------------------------------------------------------
     def training_step(self, *a, **k):
         raise NotImplementedError("training is outside the accelerated inference path (SURVEY.md section 2, rows 6/12)")
 

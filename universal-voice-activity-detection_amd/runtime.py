@@ -1299,6 +1299,111 @@ class VadRuntime:
             out.append(recs)
         return out
 
+    # ------------------------------------------------------------------ head fine-tuning (uvad_head_train_*)
+    def head_train_keys(self):
+        """[(torch key, shape)] of the trainable tensors in the packed order of uvad_head_train_read (state_dict order)."""
+        m = self._mc_c
+        k = m.hidden * (2 if m.bidirectional else 1)
+        out = []
+        for l in range(m.lin_layers):
+            out += [(f"linear.{l}.weight", (m.lin_hidden, k)), (f"linear.{l}.bias", (m.lin_hidden,))]
+            k = m.lin_hidden
+        return out + [("classifier.weight", (1, k)), ("classifier.bias", (1,))]
+
+    def head_train_open(self, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, segment: int = 0):
+        """Allocate and reset a fine-tuning state for the head (uvad_head_train_reset): f32 master copies of linear.* / classifier.* as
+        finalized, Adam moments, the gradient accumulator.  The LSTM stack stays frozen.  segment: frames per gradient partial (0 = the
+        library's default).  The handle owns the state and the workspace."""
+        cfg = _lib.HeadTrainCfg(float(lr), float(betas[0]), float(betas[1]), float(eps), int(segment))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_head_train_configure(self.ctx, C.byref(cfg)))
+            P = int(self.lib.uvad_head_train_param_count(self.ctx))
+            h = {"cfg": cfg, "P": P, "state": torch.empty(int(self.lib.uvad_head_train_state_bytes(self.ctx)), dtype=torch.uint8, device=self.device),
+                 "ws": None, "out": torch.zeros(max(P, _lib.HEAD_TRAIN_SCALAR_WORDS), dtype=torch.float32, device=self.device)}
+            self._check(self.lib.uvad_head_train_reset(self.ctx, h["state"].data_ptr(), h["state"].numel(), self._stream()))
+            return h
+
+    def head_train_grad(self, h, x: "torch.Tensor", labels=None, lengths=None, weights=None, dz=None, want_probs: bool = False,
+                        want_grad_x: bool = False):
+        """One micro-batch (uvad_head_train_grad): x (B, T, hidden x directions) f32 LSTM output on the GPU (taps(lin=False)[0], which may be
+        cached), labels (B, T) uint8, lengths (B,) valid frames per row, weights (B, T) f32 frame weights, or dz (B, T) f32 in place of
+        the loss gradient (labels and weights are then not read).  Adds the gradients, the loss sum and the frame count into the state;
+        no copy to the host and no synchronisation, so once the workspace has the batch shape's size the call can be captured.
+        -> (probs (B, T) | None, grad_x (B, T, D0) | None); head_train_batch_loss gives the call's mean loss."""
+        with torch.cuda.device(self.device):
+            x = self._dev_f32(x, "x")
+            B, T, D0 = x.shape
+            if D0 != self._mc_c.hidden * (2 if self._mc_c.bidirectional else 1):
+                raise ValueError(f"x has {D0} columns, the LSTM output has {self._mc_c.hidden * (2 if self._mc_c.bidirectional else 1)}")
+            if dz is None and labels is None:
+                raise ValueError("labels or dz must be given")
+            ptr = lambda t: (t.data_ptr(), t.stride(0)) if t is not None else (None, 0)
+            for t, dt, name in ((labels, torch.uint8, "labels"), (weights, torch.float32, "weights"), (dz, torch.float32, "dz")):
+                if t is not None:
+                    if not torch.is_tensor(t) or t.device != self.device or tuple(t.shape) != (B, T):
+                        raise ValueError(f"{name} must be a ({B}, {T}) tensor on {self.device}")
+                    self._rows_2d(t, dt, name)
+            n = None if lengths is None else self._dev_lens(lengths, B, T, torch.int32, "lengths (frames)")
+            self._check(self.lib.uvad_head_train_configure(self.ctx, C.byref(h["cfg"])))   # host only: the context serves any number of handles
+            need = int(self.lib.uvad_head_train_ws_bytes(self.ctx, B, T))
+            if h["ws"] is None or h["ws"].numel() < need:
+                h["ws"] = torch.zeros(need, dtype=torch.uint8, device=self.device)
+            probs = torch.zeros((B, T), dtype=torch.float32, device=self.device) if want_probs else None
+            grad_x = torch.empty((B, T, D0), dtype=torch.float32, device=self.device) if want_grad_x else None
+            self._check(self.lib.uvad_head_train_grad(self.ctx, x.data_ptr(), B, T, n.data_ptr() if n is not None else None,
+                                                      *ptr(labels), *ptr(weights), *ptr(dz), *ptr(probs),
+                                                      grad_x.data_ptr() if grad_x is not None else None,
+                                                      h["state"].data_ptr(), h["state"].numel(), h["ws"].data_ptr(), h["ws"].numel(), self._stream()))
+            h["_keep"] = (x, labels, weights, dz, n)   # the launches read them after this call returns
+            return probs, grad_x
+
+    def head_train_batch_loss(self, h) -> "torch.Tensor":
+        """The most recent head_train_grad's mean loss over its valid frames, a 0-d f64 tensor on the device (no synchronisation)."""
+        head = h["ws"][:16]
+        return head[:8].view(torch.float64)[0] / head[8:].view(torch.int64)[0].to(torch.float64)
+
+    def head_train_apply(self, h):
+        """One Adam step from the accumulated gradients divided by the accumulated frame count (uvad_head_train_apply)."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_head_train_configure(self.ctx, C.byref(h["cfg"])))
+            self._check(self.lib.uvad_head_train_apply(self.ctx, h["state"].data_ptr(), h["state"].numel(), self._stream()))
+
+    def _head_train_block(self, h, which: int) -> np.ndarray:
+        self._check(self.lib.uvad_head_train_read(self.ctx, h["state"].data_ptr(), h["state"].numel(), which, h["out"].data_ptr(), self._stream()))
+        return h["out"].cpu().numpy().copy()
+
+    def head_train_read(self, h) -> dict:
+        """Copy the state to the host (synchronises) -> {"weights", "grad", "m", "v": {torch key: tensor}, "loss" (accumulated sum),
+        "frames", "step", "bias_correction1", "bias_correction2" (1 - beta^step)}."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_head_train_configure(self.ctx, C.byref(h["cfg"])))
+            out = {}
+            for name, which in (("weights", _lib.HEAD_TRAIN_MASTERS), ("grad", _lib.HEAD_TRAIN_GRAD), ("m", _lib.HEAD_TRAIN_M), ("v", _lib.HEAD_TRAIN_V)):
+                flat, off, d = self._head_train_block(h, which), 0, {}
+                for key, shape in self.head_train_keys():
+                    cnt = int(np.prod(shape))
+                    d[key] = torch.from_numpy(flat[off:off + cnt].reshape(shape).copy())
+                    off += cnt
+                out[name] = d
+            w = self._head_train_block(h, _lib.HEAD_TRAIN_SCALARS)[:_lib.HEAD_TRAIN_SCALAR_WORDS]
+        out["loss"] = float(w[0:2].view(np.float64)[0])
+        out["frames"] = int(w[2:4].view(np.uint64)[0])
+        out["step"] = int(w[4:6].view(np.uint64)[0])
+        out["bias_correction1"], out["bias_correction2"] = float(w[6]), float(w[7])
+        return out
+
+    def head_train_state_dict(self, h) -> dict:
+        """The adapted head tensors keyed by torch key, ready to merge into a checkpoint (synchronises)."""
+        return self.head_train_read(h)["weights"]
+
+    def head_train_commit(self, h):
+        """Make this runtime serve the adapted head (uvad_head_train_commit: synchronises, re-finalizes).  Graphs captured before are
+        stale, as after load_state_dict."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_head_train_configure(self.ctx, C.byref(h["cfg"])))
+            self._check(self.lib.uvad_head_train_commit(self.ctx, h["state"].data_ptr(), h["state"].numel()))
+            self._weights_gen = getattr(self, "_weights_gen", 0) + 1
+
     # ------------------------------------------------------------------ scoring against reference labels (uvad_score_*)
     def score_open(self, points=((0.5, 25),), collar: int = 0, bins: int = 256, segment: int = 0):
         """Allocate and reset a scoring state (uvad_score_reset): points [(threshold, odd median kernel)], 1 .. 8 of them; collar frames

@@ -774,3 +774,84 @@ def test_vad(**kwargs):
           f"Missed Detection Rate: {out['missed_detection']}")
     print(f"EER: {out['det']['eer']} at threshold {out['det']['eer_threshold']}; best threshold {out['det']['best_threshold']}")
     return out
+
+
+def adapt_vad(**kwargs):
+    """Head fine-tuning on wav files and label files in test_vad's formats (``function == "adapt"``): what the reference's training run
+    (src/scripts/train.py with VadModel.training_step / configure_optimizers) does for the head alone.  ``input = {"kind": "wav", "paths":
+    [...], "labels": [...], "val_paths": [...], "val_labels": [...]}``; without the held-out files the training files are validated on.
+    Every recording is one batch of its own: its encoder output is computed once and cached (the LSTM stack is frozen), then
+    ``max_epochs`` epochs of VadModel.adapt_head_step run over the cached taps (``accumulate_grad_batches`` calls per Adam step, lr =
+    ``learning_rate``); every ``check_val_every_n_epoch`` epochs the head is committed and validation_step runs on the held-out files.
+    Saves a Lightning-style checkpoint {"state_dict" (``model.`` keys), "epoch", "global_step"} to ``adapted_checkpoint_path`` (default:
+    experiments_dir/adapted.ckpt) and returns {"train_loss": [per epoch], "val_loss": [(epoch, loss)], "val_metrics", "checkpoint_path"}."""
+    from .postprocess import read_label_file, supervision_frames
+    src = kwargs["input"]
+    if src.get("kind") != "wav" or not src.get("paths") or len(src.get("labels", ())) != len(src["paths"]):
+        raise ValueError('adapt_vad needs input = {"kind": "wav", "paths": [...], "labels": [one label file per path]}')
+    val_paths, val_labels = list(src.get("val_paths") or src["paths"]), list(src.get("val_labels") or src["labels"])
+    if len(val_paths) != len(val_labels):
+        raise ValueError("adapt_vad needs one label file per held-out path")
+    if kwargs["feature_extractor"] not in ("fbank", "sincnet"):
+        raise NotImplementedError("feature_extractor must be 'fbank' or 'sincnet'")
+    sincnet = kwargs["feature_extractor"] == "sincnet"
+    torch.manual_seed(kwargs["seed"])
+    device = _resolve_device(kwargs["device"])
+    model_dict, sr = dict(kwargs["model_dict"]), 16000
+    lr = float(kwargs.get("learning_rate", 1e-3))
+    if kwargs["load_checkpoint"]:
+        model = VadModel.load_from_checkpoint(checkpoint_path=kwargs["checkpoint_path"], model_name=kwargs["model_name"], model_dict=model_dict,
+                                              learning_rate=lr)
+    else:
+        model = VadModel(model_name=kwargs["model_name"], model_dict=model_dict, learning_rate=lr)
+        seed_weights(model.model, kwargs.get("weights_seed", 1234), kwargs.get("weights_scale", 4.0))
+    model = model.to(device).eval()
+    net = model.model
+    if not sincnet:
+        net.attach_fbank(FbankConfig(sampling_rate=sr, num_filters=net.encoding_dim, window_type=kwargs.get("window_type", "povey"),
+                                     frame_shift=kwargs["frame_shift"], device="cuda"))
+    rt = net.runtime(device)
+
+    def batch_of(path, label_path, cache):
+        pcm = torch.from_numpy(_wav_recordings(path, "first", rt, sr)[0]["pcm"]).to(device)[None]
+        inputs = pcm if sincnet else rt.fbank(pcm)                  # (1, samples) for PyanNet, as _common_step takes them; (1, T, F) log-mel
+        b = {"inputs": inputs}
+        if cache:
+            b["lstm_out"] = model.lstm_out(b).clone()
+        T = b["lstm_out"].shape[1] if cache else (net.num_frames(pcm.shape[1]) if sincnet else inputs.shape[1])
+        table = supervision_frames(read_label_file(label_path), pcm.shape[1] / float(sr), frame_shift=kwargs["frame_shift"],
+                                   geometry="sincnet" if sincnet else "fbank", num_frames=T)
+        iv = np.zeros((1, max(len(table), 1), 2), np.int32)
+        iv[0, :len(table)] = table
+        b["is_voice"] = rt.intervals_to_labels(iv, [len(table)], T)
+        return b
+
+    train = [batch_of(p, l, True) for p, l in zip(src["paths"], src["labels"])]
+    held = [batch_of(p, l, False) for p, l in zip(val_paths, val_labels)]
+    epochs, every = int(kwargs.get("max_epochs", 10)), max(1, int(kwargs.get("check_val_every_n_epoch", 1)))
+    accumulate = max(1, int(kwargs.get("accumulate_grad_batches", 1)))
+    out = {"train_loss": [], "val_loss": [], "val_metrics": None}
+
+    def validate(epoch):
+        if epoch:                                                 # validation_step runs the context's head: serve the adapted one
+            model.adapt_head_commit()
+        for i, b in enumerate(held):
+            model.validation_step(b, i)
+        out["val_metrics"] = model.validation_metrics(reset=True)
+        out["val_loss"].append((epoch, out["val_metrics"]["val_loss"]))
+        print(f"epoch {epoch}: val_loss {out['val_metrics']['val_loss']:.6f}")
+
+    validate(0)
+    step = 0
+    for epoch in range(1, epochs + 1):
+        losses = [model.adapt_head_step(b, i, accumulate=accumulate) for i, b in enumerate(train)]
+        step += len(train)
+        out["train_loss"].append(float(torch.stack(losses).mean()))
+        if epoch % every == 0 or epoch == epochs:
+            validate(epoch)
+    path = kwargs.get("adapted_checkpoint_path") or os.path.join(kwargs.get("experiments_dir", "."), "adapted.ckpt")
+    if os.path.dirname(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+    torch.save({"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "epoch": epochs, "global_step": step // accumulate}, path)
+    out["checkpoint_path"] = path
+    return out
