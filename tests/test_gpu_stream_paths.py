@@ -71,6 +71,10 @@ CASES = {
     "E-f40-c320": cfg("E", 320, F=40),
     "E-h64-c320": cfg("E", 320, hidden=64),
     "E-l9-c320": cfg("E", 320, layers=9),
+    # ---- E on the generic recurrence (hidden not 128 / 64): (h, c) updated in place by lstm_rec_any_kernel, two passes / three passes / 32 units
+    "E-h288-c320": cfg("E", 320, hidden=288, layers=2, lin=(100, 2)),
+    "E-h544-c480-f32": cfg("E", 480, hidden=544, layers=2, mode="f32"),
+    "E-h32-c160": cfg("E", 160, hidden=32, layers=3, lin=(36, 2)),
     # ---- mixed sessions: the two kernels take turns on one (h, c) block and one PCM tail
     "mixed-AE-c700": cfg("AE", 700, seconds=1.5),
     "mixed-AE-f80-c700": cfg("AE", 700, F=80, window="hamming", seconds=1.5),
