@@ -38,7 +38,7 @@ def test_endpoint_entries_in_header_binding_and_export_list(built):
     mk = open(os.path.join(ROOT, "universal-voice-activity-detection_amd", "csrc", "Makefile")).read()
     assert re.search(r"^SRCS :=.*\bendpoint\.hip\b", mk, re.M)
     kernel = open(os.path.join(ROOT, "universal-voice-activity-detection_amd", "csrc", "endpoint.hip")).read()
-    assert "endpoint_reset_kernel" in kernel and "endpoint_step_kernel" in kernel and "asm" not in kernel
+    assert "launch_state_reset(state, header_words(h)" in kernel and "endpoint_step_kernel" in kernel and "asm" not in kernel
 
 
 def test_cfg_struct_matches_the_header(built):

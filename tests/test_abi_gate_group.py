@@ -56,7 +56,7 @@ def test_entries_in_header_binding_and_export_list(built):
     mk = open(os.path.join(ROOT, "universal-voice-activity-detection_amd", "csrc", "Makefile")).read()
     assert re.search(r"^SRCS :=.*\bgate_group\.hip\b", mk, re.M)
     kernel = open(os.path.join(ROOT, "universal-voice-activity-detection_amd", "csrc", "gate_group.hip")).read()
-    assert "gate_group_reset_kernel" in kernel and "gate_group_step_kernel" in kernel
+    assert "launch_state_reset(state, header_words(h)" in kernel and "gate_group_step_kernel" in kernel   # the reset is state_reset.hip's
     assert "asm" not in kernel and "atomic" not in re.sub(r"//.*", "", kernel)      # no inline assembly; no atomics in the code
     assert "__ballot" in kernel and "__popcll" in kernel
     assert kernel.count("hipLaunchKernelGGL(gate_group_step_kernel") == 2           # one launch per step: the int16 or the f32 form

@@ -3,7 +3,8 @@ post-processing context: every step's out / seg / seg_counts bytes against the s
 are filled with a canary before every step: nothing is written beside the records and fragments); ended sessions against the device chain
 uvad_fuse -> uvad_cuts_table -> uvad_fuse_pick -> uvad_cuts_gather at D >= max_len and against the numpy definition at D = 1 and 3; the
 hand-made cases; NaN and junk wherever nothing may be read; max_seg and ld_out overflow; the rings at their bound and below it; UNSYNC;
-determinism; one captured graph replayed for every later step; and the refusals that need a reset state.  hop 4, lead 3, tail 3, sessions
+determinism; one captured graph replayed for every later step; one-member groups at D = 1 against the mono gate on the device; and the
+refusals that need a reset state.  hop 4, lead 3, tail 3, sessions
 of at most 120 frames, G = 4 groups over B = 8 rows: one member, two, three (sharing a row with the pair) and 70."""
 import ctypes as C
 
@@ -13,7 +14,9 @@ import torch
 
 import fuse_ref as fr
 import gate_group_ref as gg
+import gate_ref as gr
 import test_gate_group_ref as tr
+import test_gate_ref as tg
 
 pytestmark = pytest.mark.gpu
 
@@ -419,3 +422,89 @@ def test_collect_and_device_refusals(rt):
     with pytest.raises(ValueError, match="bad group gate configuration"):
         rt.gate_group_open(fz, 6, 8, torch.int16, 2, 0, **dict(zip(KEYS, CFG)))
     torch.cuda.synchronize()
+
+
+def _mono_script(rng, rows, chunk, dtype, steps, hop, tail, hold):
+    """Step inputs both gates take: per row, sessions that start and end on the row's own draws; a frame's label arrives once its samples
+    and the tail have, up to `hold` frames later, and the END step hands over the rest.  Idle rows and columns past a count hold junk."""
+    ld_lab = chunk // hop + hold + 2
+    x = rng.integers(-30000, 30000, (steps, rows, chunk)).astype(dtype) if np.dtype(dtype).kind == "i" else \
+        rng.uniform(-1.0, 1.0, (steps, rows, chunk)).astype(dtype)
+    labels = rng.integers(0, 256, (steps, rows, ld_lab)).astype(np.uint8)
+    counts = rng.integers(-3, ld_lab + 4, (steps, rows)).astype(np.int32)
+    flags = np.zeros((steps, rows), np.uint8)
+    for b in range(rows):
+        s = int(rng.integers(0, 3))
+        while s < steps:
+            n_steps = min(int(rng.integers(1, 14)), steps - s)
+            lab, d = tg.random_labels(rng, n_steps * chunk // hop + 1), 0
+            for i in range(n_steps):
+                last = i == n_steps - 1
+                avail = max(((i + 1) * chunk - tail) // hop, 0)
+                d1 = avail if last else max(d, avail - int(rng.integers(0, hold + 1)))
+                assert d1 - d <= ld_lab
+                labels[s + i, b, :d1 - d], counts[s + i, b] = lab[d:d1], d1 - d
+                flags[s + i, b] = (gg.START if i == 0 else 0) | (gg.END if last else 0)
+                d = d1
+            s += n_steps + int(rng.integers(0, 3))
+    return x, labels, counts, flags, ld_lab
+
+
+def _both_gates(rt, cfg, x, labels, counts, flags, ld_lab, lag, hist, ld_out, max_seg):
+    """The same steps through the mono gate (one slot per row) and the group gate (one one-member group per row, decide_frames = 1, no row
+    flags) -> per step the two (out, seg, seg_counts), every buffer pre-filled with the canary."""
+    steps, rows, chunk = x.shape
+    dt, kw = TORCH[x.dtype], dict(zip(KEYS, cfg))
+    mono = rt.gate_open(rows, chunk, ld_lab, dt, lag, history=hist, ld_out=ld_out, max_seg=max_seg, **kw)
+    grp = rt.gate_group_open(rt.fuse_open([[r] for r in range(rows)]), chunk, ld_lab, dt, lag, 1, history=hist, ld_out=ld_out, max_seg=max_seg, **kw)
+    assert mono["history"] == grp["history"] and mono["out"].shape == grp["out"].shape and mono["seg"].shape == grp["seg"].shape
+    dx, dl, dc, df = (torch.from_numpy(v).to(DEV) for v in (x, labels, counts, flags))
+    best = torch.zeros((rows, ld_lab), dtype=torch.uint8, device=DEV)       # one member: position 0 wins every frame
+    got = []
+    for s in range(steps):
+        for g in (mono, grp):
+            g["out"].view(torch.uint8).fill_(CANARY)
+            g["seg"].view(torch.uint8).fill_(CANARY)
+            g["seg_counts"].fill_(-7)
+        start, end = (df[s] & 1).bool(), (df[s] & 2).bool()
+        rt.gate_step(mono, dx[s], dl[s], dc[s], start=start, end=end)
+        rt.gate_group_step(grp, dx[s], best, dc[s], dl[s], dc[s], start=start, end=end)
+        got.append([v.clone() for g in (mono, grp) for v in (g["out"], g["seg"], g["seg_counts"])])
+    torch.cuda.synchronize()
+    return [[v.cpu().numpy() for v in row] for row in got], mono
+
+
+def test_one_member_groups_at_decide_1_are_the_mono_gate(rt):
+    """With one member and decide_frames = 1 nothing is deferred and the channel bits are 0: step by step the group gate's counts, records
+    and output bytes are the mono gate's on the same rows (the two slot layouts differ: outputs only).  The two restatements agree byte
+    for byte under this setting; the mono one runs here for its trace, so that the comparison cannot pass on empty sessions."""
+    hop, lead, tail, hold, rows, steps = 2, 1, 3, 3, 4, 40
+    lag = hold + -(-tail // hop)
+    runs = [(chunk, dtype, pad, W, 1, None, None) for chunk in (6, 10) for dtype in (np.int16, np.float32) for pad in (0, 2) for W in (0, 3)]
+    runs += [(6, np.int16, 2, 3, 2, None, None), (10, np.float32, 2, 3, 1, 3, 2)]       # the history halved; ld_out cut to a third, max_seg = 2
+    runs += [(10, np.int16, 2, 0, 1, 8, None)]                                          # long pieces into an eighth of ld_out: fragments are cut
+    trace, n_rec, lost, cut, dropped = set(), 0, 0, 0, 0
+    for i, (chunk, dtype, pad, W, shrink, out_div, max_seg) in enumerate(runs):
+        cfg = (pad, W, 0, hop, lead, tail)
+        x, labels, counts, flags, ld_lab = _mono_script(np.random.default_rng(500 + i), rows, chunk, dtype, steps, hop, tail, hold)
+        hist = max(gr.history(cfg, lag, chunk) // shrink, chunk)
+        assert gg.history(cfg, lag, chunk, 1) == gr.history(cfg, lag, chunk)
+        ld_out = gr.max_out(cfg, ld_lab, chunk) // (out_div or 1)
+        ms = gr.max_seg(cfg, ld_lab) if max_seg is None else max_seg
+        got, mono = _both_gates(rt, cfg, x, labels, counts, flags, ld_lab, lag, hist, ld_out, ms)
+        ref, slots = gr.simulate(cfg, hist, x, labels, counts, flags, ld_out, ms)
+        trace |= set().union(*(sl.trace for sl in slots))
+        for s, (o1, s1, c1, o2, s2, c2) in enumerate(got):
+            assert c1.tolist() == c2.tolist() == [count for _, _, count in ref[s]], (i, s)
+            assert s1.tobytes() == s2.tobytes(), (i, s)
+            assert o1.tobytes() == o2.tobytes(), (i, s)
+            seg = s1.view(gr.SEG_DTYPE).reshape(rows, -1)
+            for b in range(rows):
+                k = min(int(c1[b]), ms)
+                n_rec += k
+                lost += int((seg[b, :k]["flags"] & gr.LOST != 0).sum())
+                cut += int((seg[b, :k]["n_stored"] < seg[b, :k]["n"]).sum())
+                dropped += int(c1[b]) - k
+                assert not (seg[b, :k]["flags"] >> 4).any()                 # neither UNSYNC nor a channel
+    print(f"{len(runs)} configurations: {n_rec} records, {lost} LOST, {cut} truncated, {dropped} dropped, met {sorted(trace)}")
+    assert {"split", "rejoin", "ring wrap"} <= trace and n_rec > 400 and lost > 0 and cut > 0 and dropped > 0

@@ -9,7 +9,7 @@
 // count of a frame is rank(i + h + 1) - rank(i - h): two LDS reads and two popcounts per label, whatever the kernel size.  The labels of
 // 64 frames come back as one ballot word and the interval machine walks it with count-trailing-zeros jumps, wave-uniform: it moves only
 // at a label change or when a pending run's 2 P frames of silence are complete.
-//   endpoint_reset_kernel   the header (magic, B, kernel, pad, threshold) and every slot empty
+//   launch_endpoint_reset   the header (magic, B, kernel, pad, threshold) by field name and every slot empty, through launch_state_reset
 //   endpoint_step_kernel    the step above; writes the slot back and the step's events / counts / active byte / labels
 // Plain global loads and stores only; a slot whose count is 0 and whose flags are 0 rewrites its own state unchanged.
 #include <climits>
@@ -21,19 +21,6 @@ namespace uvad {
 namespace {
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-__global__ __launch_bounds__(256) void endpoint_reset_kernel(unsigned *state, int B, int kernel, int pad, float threshold) {
-    const long long n = (long long)((sizeof(EndpointHeader) + (size_t)B * sizeof(EndpointSlot)) / sizeof(unsigned));
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        unsigned v = 0u;
-        if (i == 0) v = EP_MAGIC;
-        else if (i == 1) v = (unsigned)B;
-        else if (i == 2) v = (unsigned)kernel;
-        else if (i == 3) v = (unsigned)pad;
-        else if (i == 4) v = __builtin_bit_cast(unsigned, threshold);
-        state[i] = v;
-    }
-}
 
 // cap_words: the 64-bit words of X the launch's LDS holds (the prefix array of cap_words + 1 ints follows them)
 __global__ __launch_bounds__(64) void endpoint_step_kernel(EndpointArgs a, int cap_words) {
@@ -184,11 +171,9 @@ size_t endpoint_state_bytes(int B) { return sizeof(EndpointHeader) + (size_t)B *
 
 hipError_t launch_endpoint_reset(void *state, int B, int kernel, int pad, float threshold, hipStream_t s) {
     if (!state || B <= 0) return hipErrorInvalidValue;
-    const long long n = (long long)(endpoint_state_bytes(B) / sizeof(unsigned));
-    const long long g = (n + 255) / 256;
-    hipLaunchKernelGGL(endpoint_reset_kernel, dim3((unsigned)(g > 1024 ? 1024 : g)), dim3(256), 0, s, reinterpret_cast<unsigned *>(state), B, kernel,
-                       pad, threshold);
-    return hipGetLastError();
+    EndpointHeader h{};
+    h.magic = EP_MAGIC; h.B = B; h.kernel = kernel; h.pad = pad; h.threshold = threshold;
+    return launch_state_reset(state, header_words(h), (long long)(endpoint_state_bytes(B) / sizeof(unsigned)), s);
 }
 
 hipError_t launch_endpoint_step(const EndpointArgs &a, int kernel, hipStream_t s) {

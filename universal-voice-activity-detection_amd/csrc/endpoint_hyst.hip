@@ -18,7 +18,7 @@
 // Labels: what a step finalises is a few constant segments -- zeros while idle (up to m - pad_on), ones while a confirmed interval runs,
 // [lo, hi) at once when a candidate is confirmed or dropped -- and the frontier only moves forward, so before every frame the walk stops
 // at, and once after the last, the lanes fill [F, new F) with one value.
-//   endpoint_hyst_reset_kernel   the header (magic, B, the uvad_binarize_cfg) and every slot empty
+//   launch_endpoint_hyst_reset   the header (magic, B, the uvad_binarize_cfg) by field name and every slot empty, through launch_state_reset
 //   endpoint_hyst_step_kernel    the step above; writes the slot back and the step's events / counts / active byte / labels
 // No LDS, no atomics, plain global loads and stores; a slot whose count is 0 and whose flags are 0 rewrites its own state unchanged.
 #include <climits>
@@ -32,22 +32,6 @@ static_assert(sizeof(EndpointHystHeader) == 256 && sizeof(EndpointHystSlot) == 3
 namespace {
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-__global__ __launch_bounds__(256) void endpoint_hyst_reset_kernel(unsigned *state, int B, BinCfgInt q) {
-    const long long n = (long long)((sizeof(EndpointHystHeader) + (size_t)B * sizeof(EndpointHystSlot)) / sizeof(unsigned));
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        unsigned v = 0u;
-        if (i == 0) v = EPH_MAGIC;
-        else if (i == 1) v = (unsigned)B;
-        else if (i == 2) v = __builtin_bit_cast(unsigned, q.onset);
-        else if (i == 3) v = __builtin_bit_cast(unsigned, q.offset);
-        else if (i == 4) v = (unsigned)q.min_on;
-        else if (i == 5) v = (unsigned)q.min_off;
-        else if (i == 6) v = (unsigned)q.pad_on;
-        else if (i == 7) v = (unsigned)q.pad_off;
-        state[i] = v;
-    }
-}
 
 __global__ __launch_bounds__(64) void endpoint_hyst_step_kernel(EndpointArgs a) {
     const EndpointHystHeader *hd = reinterpret_cast<const EndpointHystHeader *>(a.state);
@@ -201,10 +185,9 @@ size_t endpoint_hyst_state_bytes(int B) { return sizeof(EndpointHystHeader) + (s
 
 hipError_t launch_endpoint_hyst_reset(void *state, int B, const BinCfgInt &q, hipStream_t s) {
     if (!state || B <= 0) return hipErrorInvalidValue;
-    const long long n = (long long)(endpoint_hyst_state_bytes(B) / sizeof(unsigned));
-    const long long g = (n + 255) / 256;
-    hipLaunchKernelGGL(endpoint_hyst_reset_kernel, dim3((unsigned)(g > 1024 ? 1024 : g)), dim3(256), 0, s, reinterpret_cast<unsigned *>(state), B, q);
-    return hipGetLastError();
+    EndpointHystHeader h{};
+    h.magic = EPH_MAGIC; h.B = B; h.q = q;
+    return launch_state_reset(state, header_words(h), (long long)(endpoint_hyst_state_bytes(B) / sizeof(unsigned)), s);
 }
 
 hipError_t launch_endpoint_hyst_step(const EndpointArgs &a, hipStream_t s) {

@@ -3689,6 +3689,30 @@ static int64_t gate_max_seg(const uvad_cuts_cfg *q, int ld_lab) {
     return 2 * I + 1 + (q->max_len ? ((int64_t)ld_lab + 2 * (int64_t)q->pad * I) / q->max_len : 0);   // below 2^54
 }
 
+// the argument checks uvad_gate_step and uvad_gate_group_step share, in the order both report them: the chunk's range, the signs of the
+// leading dimensions and of max_seg, then the NULL pairs.  fn: the entry point's name, which every message starts with.  The mono gate has
+// no best bytes: it passes ld_best = 0, so that their checks never fire.  -> UVAD_OK, or what fail() returned
+static int gate_step_args_error(uvad_ctx *c, const char *fn, int chunk, int ld_lab, int ld_best, int64_t ld_out, int max_seg, const void *d_chunk,
+                                const void *d_state, const void *d_seg_counts, const void *d_labels, const void *d_lab_counts, const void *d_best,
+                                const void *d_best_counts, const void *d_out, const void *d_seg) {
+    const char *w = nullptr;
+    if (chunk < 1 || chunk > GATE_MAX_CHUNK) w = "chunk must lie in [1, 2^24] samples";
+    else if (ld_lab < 0) w = "ld_lab must be >= 0";
+    else if (ld_best < 0) w = "ld_best must be >= 0";
+    else if (ld_out < 0) w = "ld_out must be >= 0";
+    else if (max_seg < 0) w = "max_seg must be >= 0";
+    else if (!d_chunk) w = "d_chunk is NULL";
+    else if (!d_state) w = "d_state is NULL";
+    else if (!d_seg_counts) w = "d_seg_counts is NULL";
+    else if (ld_lab > 0 && !d_labels) w = "d_labels is NULL with ld_lab > 0";
+    else if (ld_lab > 0 && !d_lab_counts) w = "d_lab_counts is NULL with ld_lab > 0";
+    else if (ld_best > 0 && !d_best) w = "d_best is NULL with ld_best > 0";
+    else if (ld_best > 0 && !d_best_counts) w = "d_best_counts is NULL with ld_best > 0";
+    else if (ld_out > 0 && !d_out) w = "d_out is NULL with ld_out > 0";
+    else if (max_seg > 0 && !d_seg) w = "d_seg is NULL with max_seg > 0";
+    return w ? fail(c, UVAD_E_ARG, std::string(fn) + ": " + w) : UVAD_OK;
+}
+
 int64_t uvad_gate_history(const uvad_cuts_cfg *q, int lag_frames, int chunk) {
     if (gate_cfg_error(q) || lag_frames < 0 || chunk < 1 || chunk > GATE_MAX_CHUNK) return -1;
     return (int64_t)chunk + ((int64_t)lag_frames + q->pad + 1) * q->hop + q->lead;   // below 2^63: (2^31 + 2^20 + 1) 2^31 + 2^31 + 2^24
@@ -3734,17 +3758,9 @@ int uvad_gate_step(uvad_ctx *c, const void *d_chunk, int chunk, const uint8_t *d
                    int max_seg, int32_t *d_seg_counts, void *stream) {
     if (!c) return UVAD_E_ARG;
     if (B < 1) return fail(c, UVAD_E_ARG, "uvad_gate_step: B must be >= 1");
-    if (chunk < 1 || chunk > GATE_MAX_CHUNK) return fail(c, UVAD_E_ARG, "uvad_gate_step: chunk must lie in [1, 2^24] samples");
-    if (ld_lab < 0) return fail(c, UVAD_E_ARG, "uvad_gate_step: ld_lab must be >= 0");
-    if (ld_out < 0) return fail(c, UVAD_E_ARG, "uvad_gate_step: ld_out must be >= 0");
-    if (max_seg < 0) return fail(c, UVAD_E_ARG, "uvad_gate_step: max_seg must be >= 0");
-    if (!d_chunk) return fail(c, UVAD_E_ARG, "uvad_gate_step: d_chunk is NULL");
-    if (!d_state) return fail(c, UVAD_E_ARG, "uvad_gate_step: d_state is NULL");
-    if (!d_seg_counts) return fail(c, UVAD_E_ARG, "uvad_gate_step: d_seg_counts is NULL");
-    if (ld_lab > 0 && !d_labels) return fail(c, UVAD_E_ARG, "uvad_gate_step: d_labels is NULL with ld_lab > 0");
-    if (ld_lab > 0 && !d_lab_counts) return fail(c, UVAD_E_ARG, "uvad_gate_step: d_lab_counts is NULL with ld_lab > 0");
-    if (ld_out > 0 && !d_out) return fail(c, UVAD_E_ARG, "uvad_gate_step: d_out is NULL with ld_out > 0");
-    if (max_seg > 0 && !d_seg) return fail(c, UVAD_E_ARG, "uvad_gate_step: d_seg is NULL with max_seg > 0");
+    if (const int e = gate_step_args_error(c, "uvad_gate_step", chunk, ld_lab, 0, ld_out, max_seg, d_chunk, d_state, d_seg_counts, d_labels, d_lab_counts,
+                                           nullptr, nullptr, d_out, d_seg))
+        return e;
     auto it = c->gates.find(d_state);
     if (it == c->gates.end()) return fail(c, UVAD_E_STATE, "uvad_gate_step: call uvad_gate_reset on this state first");
     const GatePool &g = it->second;
@@ -3823,20 +3839,9 @@ int uvad_gate_group_step(uvad_ctx *c, const void *d_chunk, int chunk, int B, con
     if (!c->has_fuse) return fail(c, UVAD_E_STATE, "uvad_gate_group_step: uvad_fuse_configure has not been called");
     if (B <= c->fz_max_member)
         return fail(c, UVAD_E_ARG, "uvad_gate_group_step: B must be above the largest configured member index (" + std::to_string(c->fz_max_member) + ")");
-    if (chunk < 1 || chunk > GATE_MAX_CHUNK) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: chunk must lie in [1, 2^24] samples");
-    if (ld_lab < 0) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: ld_lab must be >= 0");
-    if (ld_best < 0) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: ld_best must be >= 0");
-    if (ld_out < 0) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: ld_out must be >= 0");
-    if (max_seg < 0) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: max_seg must be >= 0");
-    if (!d_chunk) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_chunk is NULL");
-    if (!d_state) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_state is NULL");
-    if (!d_seg_counts) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_seg_counts is NULL");
-    if (ld_lab > 0 && !d_labels) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_labels is NULL with ld_lab > 0");
-    if (ld_lab > 0 && !d_lab_counts) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_lab_counts is NULL with ld_lab > 0");
-    if (ld_best > 0 && !d_best) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_best is NULL with ld_best > 0");
-    if (ld_best > 0 && !d_best_counts) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_best_counts is NULL with ld_best > 0");
-    if (ld_out > 0 && !d_out) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_out is NULL with ld_out > 0");
-    if (max_seg > 0 && !d_seg) return fail(c, UVAD_E_ARG, "uvad_gate_group_step: d_seg is NULL with max_seg > 0");
+    if (const int e = gate_step_args_error(c, "uvad_gate_group_step", chunk, ld_lab, ld_best, ld_out, max_seg, d_chunk, d_state, d_seg_counts, d_labels,
+                                           d_lab_counts, d_best, d_best_counts, d_out, d_seg))
+        return e;
     auto it = c->gate_groups.find(d_state);
     if (it == c->gate_groups.end()) return fail(c, UVAD_E_STATE, "uvad_gate_group_step: call uvad_gate_group_reset on this state first");
     const GateGroupPool &g = it->second;

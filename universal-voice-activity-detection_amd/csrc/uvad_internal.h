@@ -510,6 +510,19 @@ struct IngestArgs {
 };
 hipError_t launch_ingest(const IngestArgs &a, hipStream_t s);
 
+// ---- state_reset.hip: the one reset of the device states that are a 256-byte header followed by slots that start as zeros ------------------
+// (EndpointHeader, EndpointHystHeader, GateHeader, GateGroupHeader).  A launcher fills its header struct by field name -- the struct the
+// step kernel reads by field name -- and hands it over as 64 words in the kernel's arguments; the kernel writes word i of the header for
+// i < 64 and zero for the n_words - 64 words of the slots.  What follows the slots (the gates' rings) is not touched.
+struct HeaderWords { unsigned w[64]; };
+template <class H> inline HeaderWords header_words(const H &h) {
+    static_assert(sizeof(H) == 256 && sizeof(HeaderWords) == 256 && std::is_trivially_copyable<H>::value, "a state header is 256 bytes of plain words");
+    HeaderWords o;
+    __builtin_memcpy(&o, &h, sizeof(o));
+    return o;
+}
+hipError_t launch_state_reset(void *state, const HeaderWords &h, long long n_words, hipStream_t s);
+
 // ---- endpoint.hip: the live endpointer (uvad_endpoint_*, include/uvad.h): streaming median, runs and the padded merge, one slot per feed ----
 // The state is a header (what reset fixed: B and the configuration, so a step carries none) followed by one EndpointSlot per slot.
 // hist[0 .. n), n = ceil(2 h / 64), holds the thresholded frames before the slot's frame m as a bit string that ENDS at the top bit of
@@ -677,7 +690,7 @@ hipError_t launch_endpoint_hyst_step(const EndpointArgs &a, hipStream_t s);
 // per slot, then one ring of `history` units per slot, each rounded up to 16 bytes so that every ring starts as aligned as the state does.
 constexpr unsigned GATE_MAGIC = 0x55564754u;          // "UVGT"
 constexpr int GATE_MAX_CHUNK = 1 << 24;
-constexpr int GATE_THREADS = 256;                     // one workgroup per slot
+constexpr int GATE_THREADS = 256;                     // one workgroup per slot, and per group of the group gate
 constexpr int GATE_LAB_TILE = 1024;                   // labels staged in LDS per round of the walk
 struct GateHeader { unsigned magic; int B; CutsCfgInt q; int unit_bytes, history; long long ring_bytes; int reserved[52]; };   // 256 bytes
 struct GateSlot {
@@ -711,7 +724,6 @@ hipError_t launch_gate_step(const GateArgs &a, int unit_bytes, hipStream_t s);  
 // MEMBER SLOT (a row that sits in several groups is kept once per slot); every ring is rounded up to 16 bytes.  The rings of a group's
 // members share the group's write position: its members receive the same chunk count every step.
 constexpr unsigned GATE_GROUP_MAGIC = 0x55564747u;    // "UVGG"
-constexpr int GATE_GROUP_THREADS = 256;               // one workgroup per group
 constexpr int GATE_GROUP_UNSYNC = 16;                 // UVAD_GATE_UNSYNC
 struct GateGroupHeader {
     unsigned magic; int G, N; CutsCfgInt q; int unit_bytes, history, best_history, decide, reserved0;

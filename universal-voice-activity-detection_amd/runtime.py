@@ -1107,13 +1107,9 @@ class VadRuntime:
         return self._endpoint_run(ep, self._endpoint_hyst_enqueue, probs, counts, start, end)
 
     # ------------------------------------------------------------------ live speech gate (uvad_gate_*)
-    def gate_open(self, B: int, chunk: int, ld_lab: int, dtype, lag_frames: int, history=None, ld_out=None, max_seg=None, **cuts_cfg):
-        """Allocate and reset a speech gate of B slots (uvad_gate_reset): the streaming cuts_table + cuts_gather.  Every step takes a
-        (B, chunk) block of samples of `dtype` (torch.int16 or torch.float32) and up to ld_lab finalised labels per slot and emits each
-        slot's speech audio as fragments with records.  **cuts_cfg: pad, max_len, hop, lead, tail as cuts_open (min_len must be 0).
-        lag_frames: how far the label frontier may trail floor(samples / hop) after a step; it sizes the history ring
-        (uvad_gate_history) unless `history` samples are given.  ld_out / max_seg default to uvad_gate_max_out / uvad_gate_max_seg, which
-        never truncate."""
+    @staticmethod
+    def _gate_cfg(dtype, cuts_cfg):
+        """What gate_open and gate_group_open make of dtype and **cuts_cfg -> (the parameters with their defaults, the CutsCfg, the unit size)."""
         if dtype not in (torch.float32, torch.int16):
             raise ValueError(f"dtype must be torch.float32 or torch.int16, got {dtype}")
         q = dict(pad=0, max_len=0, min_len=0, hop=160, lead=0, tail=240)
@@ -1122,7 +1118,29 @@ class VadRuntime:
             raise ValueError(f"unknown gate parameters {sorted(extra)} (pad, max_len, hop, lead, tail)")
         q.update(cuts_cfg)
         cfg = _lib.CutsCfg(*(int(q[k]) for k in ("pad", "max_len", "min_len", "hop", "lead", "tail")))
-        unit = 2 if dtype == torch.int16 else 4
+        return q, cfg, 2 if dtype == torch.int16 else 4
+
+    def _gate_pair(self, x, n, what, ld, rows):
+        """A gate step's (bytes, counts) input pair: x (rows, ld) uint8 (ld None: any width) and n (rows,) int32 on the GPU, or None, None
+        where there is nothing to pass (ld None or 0) -> (x, n, columns of x), contiguous."""
+        if x is None and n is None and not ld:
+            return None, None, 0
+        if not torch.is_tensor(x) or x.device != self.device or x.dtype != torch.uint8 or x.dim() != 2 or x.shape[0] != rows or \
+                (ld is not None and x.shape[1] != ld):
+            raise ValueError(f"{what} must be a ({rows}, {ld if ld is not None else 'ld'}) uint8 tensor on {self.device}")
+        if not torch.is_tensor(n) or n.device != self.device or n.dtype != torch.int32 or tuple(n.shape) != (rows,):
+            raise ValueError(f"{what}' counts must be an int32 tensor of shape ({rows},) on {self.device}")
+        x, n = x.contiguous(), n.contiguous()
+        return x, n, x.shape[1]
+
+    def gate_open(self, B: int, chunk: int, ld_lab: int, dtype, lag_frames: int, history=None, ld_out=None, max_seg=None, **cuts_cfg):
+        """Allocate and reset a speech gate of B slots (uvad_gate_reset): the streaming cuts_table + cuts_gather.  Every step takes a
+        (B, chunk) block of samples of `dtype` (torch.int16 or torch.float32) and up to ld_lab finalised labels per slot and emits each
+        slot's speech audio as fragments with records.  **cuts_cfg: pad, max_len, hop, lead, tail as cuts_open (min_len must be 0).
+        lag_frames: how far the label frontier may trail floor(samples / hop) after a step; it sizes the history ring
+        (uvad_gate_history) unless `history` samples are given.  ld_out / max_seg default to uvad_gate_max_out / uvad_gate_max_seg, which
+        never truncate."""
+        q, cfg, unit = self._gate_cfg(dtype, cuts_cfg)
         if history is None:
             history = int(self.lib.uvad_gate_history(C.byref(cfg), int(lag_frames), int(chunk)))
         history = int(history)
@@ -1160,14 +1178,8 @@ class VadRuntime:
                 raise ValueError(f"chunk must be a ({g['B']}, {g['chunk']}) {g['dtype']} tensor on {self.device}")
             chunk = chunk.contiguous()
             lp = cp = None
-            if g["ld_lab"]:
-                if not torch.is_tensor(labels) or labels.device != self.device or labels.dtype != torch.uint8 or \
-                        tuple(labels.shape) != (g["B"], g["ld_lab"]):
-                    raise ValueError(f"labels must be a ({g['B']}, {g['ld_lab']}) uint8 tensor on {self.device}")
-                if not torch.is_tensor(lab_counts) or lab_counts.device != self.device or lab_counts.dtype != torch.int32 or \
-                        tuple(lab_counts.shape) != (g["B"],):
-                    raise ValueError(f"lab_counts must be an int32 tensor of shape ({g['B']},) on {self.device}")
-                labels, lab_counts = labels.contiguous(), lab_counts.contiguous()
+            if g["ld_lab"]:                                                    # with ld_lab = 0 whatever is passed is not looked at
+                labels, lab_counts, _ = self._gate_pair(labels, lab_counts, "labels", g["ld_lab"], g["B"])
                 lp, cp = labels.data_ptr(), lab_counts.data_ptr()
             flags = self._slot_flags(g["B"], start, end)
             self._check(self._gate_enqueue(g, chunk.data_ptr(), lp, cp, flags.data_ptr() if flags is not None else None))
@@ -1196,15 +1208,7 @@ class VadRuntime:
         up to ld_lab finalised labels per group, and emits each group's speech audio, each cut whole from the member that won most of its
         first `decide_frames` frames.  **cuts_cfg, lag_frames as gate_open; history / best_history default to uvad_gate_group_history /
         uvad_gate_group_best_history, ld_out / max_seg to uvad_gate_group_max_out / uvad_gate_max_seg, which never truncate."""
-        if dtype not in (torch.float32, torch.int16):
-            raise ValueError(f"dtype must be torch.float32 or torch.int16, got {dtype}")
-        q = dict(pad=0, max_len=0, min_len=0, hop=160, lead=0, tail=240)
-        extra = set(cuts_cfg) - set(q)
-        if extra:
-            raise ValueError(f"unknown gate parameters {sorted(extra)} (pad, max_len, hop, lead, tail)")
-        q.update(cuts_cfg)
-        cfg = _lib.CutsCfg(*(int(q[k]) for k in ("pad", "max_len", "min_len", "hop", "lead", "tail")))
-        unit = 2 if dtype == torch.int16 else 4
+        q, cfg, unit = self._gate_cfg(dtype, cuts_cfg)
         chunk, ld_lab, lag_frames, D = int(chunk), int(ld_lab), int(lag_frames), int(decide_frames)
         if history is None:
             history = self.lib.uvad_gate_group_history(C.byref(cfg), lag_frames, chunk, D)
@@ -1255,20 +1259,8 @@ class VadRuntime:
                     chunk.shape[1] != g["chunk"] or chunk.shape[0] < g["B"]:
                 raise ValueError(f"chunk must be a (>= {g['B']}, {g['chunk']}) {g['dtype']} tensor on {self.device}")
             chunk = chunk.contiguous()
-
-            def pair(x, n, what, ld):
-                if x is None and n is None and not ld:
-                    return None, None, 0
-                if not torch.is_tensor(x) or x.device != self.device or x.dtype != torch.uint8 or x.dim() != 2 or x.shape[0] != G or \
-                        (ld is not None and x.shape[1] != ld):
-                    raise ValueError(f"{what} must be a ({G}, {ld if ld is not None else 'ld'}) uint8 tensor on {self.device}")
-                if not torch.is_tensor(n) or n.device != self.device or n.dtype != torch.int32 or tuple(n.shape) != (G,):
-                    raise ValueError(f"{what}' counts must be an int32 tensor of shape ({G},) on {self.device}")
-                x, n = x.contiguous(), n.contiguous()
-                return x, n, x.shape[1]
-
-            best, best_counts, ld_best = pair(best, best_counts, "best", None)
-            labels, lab_counts, _ = pair(labels, lab_counts, "labels", g["ld_lab"])
+            best, best_counts, ld_best = self._gate_pair(best, best_counts, "best", None, G)
+            labels, lab_counts, _ = self._gate_pair(labels, lab_counts, "labels", g["ld_lab"], G)
             if row_flags is not None and (not torch.is_tensor(row_flags) or row_flags.device != self.device or row_flags.dtype != torch.uint8 or
                                           tuple(row_flags.shape) != (chunk.shape[0],)):
                 raise ValueError(f"row_flags must be a ({chunk.shape[0]},) uint8 tensor on {self.device}")
