@@ -1127,8 +1127,8 @@ int uvad_gate_group_step(uvad_ctx *, const void *d_chunk, int chunk, int B, cons
  * slice of the model, VadModel.training_step / _common_step (src/engines/vad_engine.py:247-278: the head expression of
  * PyanNet2.forward, F.leaky_relu(linear(x)) and sigmoid(classifier(x)), F.binary_cross_entropy with the mean over the frames present,
  * src/utils/loss.py:56-89, and autograd's backward pass through them) and configure_optimizers (:280: torch.optim.Adam, no weight decay).
- * Gradients into the LSTM stack or a SincNet front end, dropout, weight decay, schedules and DDP are not here; d_grad_x is where a
- * backward pass through the LSTM stack would start.
+ * Gradients into a SincNet front end, dropout, weight decay, schedules and DDP are not here; d_grad_x is where the backward pass through
+ * the LSTM stack starts (uvad_lstm_train_backward below takes it as d_dy).
  *
  * With s = leaky_slope, a_0 = x0, a_l = leaky_relu(a_{l-1} W_l^T + b_l, s) for l = 1 .. L, z = a_L . w_c + b_c, p = sigmoid(z), a frame
  * (b, t) is valid iff t < len_b = clamp(d_lens[b], 0, T) (T when d_lens is NULL).  A valid frame with label y = (d_gt != 0) and weight w
@@ -1192,6 +1192,61 @@ int uvad_head_train_grad(uvad_ctx *, const float *d_x, int B, int T, const int32
 int uvad_head_train_apply(uvad_ctx *, void *d_state, size_t state_bytes, void *stream);
 int uvad_head_train_read(uvad_ctx *, const void *d_state, size_t state_bytes, int which, float *d_out, void *stream);
 int uvad_head_train_commit(uvad_ctx *, const void *d_state, size_t state_bytes);
+
+/* ---- LSTM training on the device: forward with kept activations, backpropagation through time, Adam ---------------------------------------
+ * Layers first_layer .. num_layers - 1 of the context's LSTM stack learn; the layers below stay frozen and run through the inference
+ * kernels as before (their output, or the features themselves when first_layer is 0, is this block's input and may be cached across
+ * epochs).  Together with uvad_head_train_* this is VadModel.training_step / configure_optimizers (src/engines/vad_engine.py:247-281)
+ * for everything above the front end: nn.LSTM on pack_padded_sequence rows, autograd's backward pass through it, torch.optim.Adam.
+ * Gradients into a SincNet front end, dropout, weight decay, schedules and DDP are not here.
+ *
+ * d_x_in [B][T][Din] is the dense f32 input of layer first_layer (Din = in_dim when first_layer is 0, else hidden x directions);
+ * d_y [B][T][hidden x directions] the top layer's output computed with the STATE's f32 master weights: what uvad_head_train_grad takes as
+ * d_x; d_dy the head's d_grad_x (the gradient of the summed loss); d_grad_in [B][T][Din] (may be NULL) dL/dx_in.  len_b =
+ * clamp(d_lens[b], 0, T) (T when d_lens is NULL).  d_y and d_grad_in are +0 at frames past a length, and such frames are never read in
+ * d_x_in or d_dy.
+ * Forward, per layer and direction: nn.LSTM's cell -- gate order i, f, g, o, zero initial state, the backward direction starting at
+ *   len_b - 1 -- keeping i, f, g, o after their nonlinearities, c_t and h_{t-1} in the workspace, whose header records B and T.
+ * Backward, per step in reverse time for each direction, with dh = dy_t + dh_rec:  do = dh tanh(c_t);
+ *   dc = dh o (1 - tanh^2 c_t) + dc_rec;  di = dc g, dg = dc i, df = dc c_{t-1};  dpre = {di i (1 - i), df f (1 - f), dg (1 - g^2),
+ *   do o (1 - o)};  dc_rec <- dc f;  dh_rec <- dpre W_hh.  dW_ih = sum dpre^T x, dW_hh = sum dpre^T h_prev (the previous step's h in that
+ *   direction's own order, +0 at its first step), db_ih = db_hh = sum dpre (the same bits), d_in = dpre W_ih summed over the directions:
+ *   the next lower trainable layer's dy, and at first_layer d_grad_in.  The gradients are ADDED into the state's accumulator and the call's
+ *   valid frames into its count, so that uvad_lstm_train_apply divides by the count uvad_head_train_apply divides by.  The kernels check
+ *   the workspace header on the device: a backward call whose (B, T) is not that of the forward call that filled the workspace writes nothing.
+ *   All time-parallel products run on the head's exact f32 tile kernel, per segment of `segment` frames folded in segment order; the
+ *   recurrences sum in a fixed order: no floating-point atomics, the same calls give the same bits.
+ * uvad_lstm_train_apply, _read and _commit mean what the head's mean (the same Adam step, restated in tests/head_train_ref.py; `which` is
+ *   UVAD_HEAD_TRAIN_MASTERS / _GRAD / _M / _V / _SCALARS).  The P = uvad_lstm_train_param_count floats are packed in state_dict order,
+ *   per layer k = first_layer .., forward then _reverse: lstm.weight_ih_l{k} [4 hidden][in], weight_hh_l{k} [4 hidden][hidden],
+ *   bias_ih_l{k}, bias_hh_l{k} [4 hidden]; bias_ih and bias_hh are separate Adam tensors.  Commit synchronises the device, then feeds the
+ *   masters through uvad_set_weight + uvad_finalize, with the consequences uvad_head_train_commit names.
+ * uvad_lstm_train_reset copies the masters from the context's host tensors: it synchronises the stream and is not for graph capture.
+ *   forward, backward and apply allocate nothing and never synchronise: forward -> uvad_head_train_grad -> backward -> both applies can
+ *   be captured as one graph and replayed with new data.
+ * Served: hidden 64 or 128; one or two directions; Din a multiple of 4 up to 2048; up to 8 trainable layers; B T <= 2^24; segment as the
+ *   head's.  uvad_lstm_train_configure returns UVAD_E_UNSUPPORTED for anything else.
+ * Refusals (nothing enqueued).  UVAD_E_ARG: NULL cfg / d_x_in / d_y / d_dy / d_state / d_ws / d_out; d_state or d_ws not 16-byte aligned
+ *   (forward, backward); lr, beta1, beta2, eps, segment as the head's; first_layer outside [0, num_layers); B < 1; T < 1; B T > 2^24 or more than 65535 segments; state_bytes or ws_bytes below
+ *   the helpers; which outside 0 .. 4.  UVAD_E_STATE: a context without a model; no uvad_lstm_train_configure yet; a context that is not
+ *   finalized (reset, commit); a state that was never reset, or reset under another shape. */
+typedef struct {
+    float lr, beta1, beta2, eps;
+    int segment;                             /* frames per gradient partial, 0 = default (2048) */
+    int first_layer;                         /* layers first_layer .. num_layers - 1 learn */
+} uvad_lstm_train_cfg;
+int uvad_lstm_train_configure(uvad_ctx *, const uvad_lstm_train_cfg *);
+int64_t uvad_lstm_train_param_count(const uvad_ctx *);   /* P; 0 before uvad_lstm_train_configure */
+size_t uvad_lstm_train_state_bytes(const uvad_ctx *);
+size_t uvad_lstm_train_ws_bytes(const uvad_ctx *, int B, int T);
+int uvad_lstm_train_reset(uvad_ctx *, void *d_state, size_t state_bytes, void *stream);
+int uvad_lstm_train_forward(uvad_ctx *, const float *d_x_in, int B, int T, const int32_t *d_lens, float *d_y, void *d_state,
+                            size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream);
+int uvad_lstm_train_backward(uvad_ctx *, const float *d_x_in, const float *d_dy, int B, int T, const int32_t *d_lens, float *d_grad_in,
+                             void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream);
+int uvad_lstm_train_apply(uvad_ctx *, void *d_state, size_t state_bytes, void *stream);
+int uvad_lstm_train_read(uvad_ctx *, const void *d_state, size_t state_bytes, int which, float *d_out, void *stream);
+int uvad_lstm_train_commit(uvad_ctx *, const void *d_state, size_t state_bytes);
 
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;

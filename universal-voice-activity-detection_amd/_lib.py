@@ -59,6 +59,10 @@ class HeadTrainCfg(C.Structure):     # uvad_head_train_cfg (20 bytes)
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("segment", C.c_int)]
 
 
+class LstmTrainCfg(C.Structure):     # uvad_lstm_train_cfg (24 bytes)
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("segment", C.c_int), ("first_layer", C.c_int)]
+
+
 class CutsCfg(C.Structure):
     _fields_ = [("pad", C.c_int), ("max_len", C.c_int), ("min_len", C.c_int), ("hop", C.c_int), ("lead", C.c_int), ("tail", C.c_int)]
 
@@ -216,6 +220,18 @@ SIGNATURES = {
     "uvad_head_train_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_head_train_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     "uvad_head_train_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "uvad_lstm_train_configure": (C.c_int, [C.c_void_p, C.POINTER(LstmTrainCfg)]),
+    "uvad_lstm_train_param_count": (C.c_int64, [C.c_void_p]),
+    "uvad_lstm_train_state_bytes": (C.c_size_t, [C.c_void_p]),
+    "uvad_lstm_train_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "uvad_lstm_train_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_lstm_train_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.c_size_t, C.c_void_p]),
+    "uvad_lstm_train_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_lstm_train_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_lstm_train_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "uvad_lstm_train_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "uvad_cuts_max_per_row": (C.c_int, [C.POINTER(CutsCfg), C.c_int]),
     "uvad_cuts_max_samples": (C.c_int64, [C.POINTER(CutsCfg), C.c_int64]),
     "uvad_cuts_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),

@@ -91,6 +91,7 @@ def load_config() -> ConfigDict:
     cfg.check_val_every_n_epoch = 1
     cfg.accumulate_grad_batches = 1
     cfg.adapted_checkpoint_path = ""    # "" = experiments_dir/adapted.ckpt
+    cfg.adapt_lstm_layers = 0           # top LSTM layers that learn with the head (VadModel.adapt_step); 0 = the head alone, as before
 
     cfg.predict_output_dir = os.environ.get("UVAD_PREDICT_DIR", "")   # "" = do not write files
     cfg.window_type = "povey"   # lhotse default; BASELINE cfg 2 uses "hamming"

@@ -125,6 +125,10 @@ struct uvad_ctx {
     bool has_ht = false;                        // uvad_head_train_configure: the optimiser (segment 0 replaced by the default) and the head's shape
     uvad_head_train_cfg hq{};
     HeadTrainShape hts{};
+    std::map<void *, int> lstm_trains;          // ... and of the LSTM training states (uvad_lstm_train_*): the parameter count at reset
+    bool has_lt = false;                        // uvad_lstm_train_configure: the optimiser, first_layer and the packed shape of the trainable layers
+    uvad_lstm_train_cfg lq{};
+    LstmTrainShape lts{};
     int device = 0, n_cu = 256;
     bool has_fb = false, has_model = false, finalized = false, tables_set = false;
     uvad_fbank_cfg fb{};
@@ -3187,6 +3191,22 @@ int uvad_score_totals(uvad_ctx *c, const void *d_state, size_t state_bytes, uint
 }
 
 // ---- head fine-tuning (head_train.hip) ----------------------------------------------------------------------------------------------------
+// The optimiser's constants.  1 - beta as torch hands it to lerp_ / addcmul_: the difference taken in f64 from the double the caller wrote
+// (0.999, not the f32 next to it, whose complement is 1.3e-5 off) -- the shortest decimal that rounds to the f32 given -- and rounded to f32 once
+static HeadTrainAdam adam_of(float lr, float beta1, float beta2, float eps) {
+    auto one_minus = [](float b) {
+        char buf[32];
+        double d = (double)b;
+        for (int p = 1; p <= 9; ++p) {
+            std::snprintf(buf, sizeof buf, "%.*g", p, (double)b);
+            d = std::strtod(buf, nullptr);
+            if ((float)d == b) break;
+        }
+        return (float)(1.0 - d);
+    };
+    return HeadTrainAdam{lr, beta1, beta2, eps, one_minus(beta1), one_minus(beta2)};
+}
+
 int uvad_head_train_configure(uvad_ctx *c, const uvad_head_train_cfg *q) {
     if (!c) return UVAD_E_ARG;
     if (!q) return fail(c, UVAD_E_ARG, "uvad_head_train_configure: bad argument");
@@ -3278,19 +3298,7 @@ int uvad_head_train_apply(uvad_ctx *c, void *d_state, size_t state_bytes, void *
     if (!c) return UVAD_E_ARG;
     if (int r = head_train_state_check(c, "uvad_head_train_apply", d_state, state_bytes, false)) return r;
     const uvad_head_train_cfg &q = c->hq;
-    // 1 - beta as torch hands it to lerp_ / addcmul_: the difference taken in f64 from the double the caller wrote (0.999, not the f32
-    // next to it, whose complement is 1.3e-5 off) -- the shortest decimal that rounds to the f32 given -- and rounded to f32 once
-    auto one_minus = [](float b) {
-        char buf[32];
-        double d = (double)b;
-        for (int p = 1; p <= 9; ++p) {
-            std::snprintf(buf, sizeof buf, "%.*g", p, (double)b);
-            d = std::strtod(buf, nullptr);
-            if ((float)d == b) break;
-        }
-        return (float)(1.0 - d);
-    };
-    const HeadTrainAdam o{q.lr, q.beta1, q.beta2, q.eps, one_minus(q.beta1), one_minus(q.beta2)};
+    const HeadTrainAdam o = adam_of(q.lr, q.beta1, q.beta2, q.eps);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, launch_head_train_apply(c->hts, o, d_state, (hipStream_t)stream));
     return UVAD_OK;
@@ -3323,6 +3331,157 @@ int uvad_head_train_commit(uvad_ctx *c, const void *d_state, size_t state_bytes)
         if ((r = uvad_set_weight(c, (name + ".weight").c_str(), w.data() + q.off_w[l], wshape, 2))) return r;
         if ((r = uvad_set_weight(c, (name + ".bias").c_str(), w.data() + q.off_b[l], bshape, 1))) return r;
     }
+    return uvad_finalize(c);
+}
+
+// ---- LSTM training (lstm_train.hip) ---------------------------------------------------------------------------------------------------------
+int uvad_lstm_train_configure(uvad_ctx *c, const uvad_lstm_train_cfg *q) {
+    if (!c) return UVAD_E_ARG;
+    if (!q) return fail(c, UVAD_E_ARG, "uvad_lstm_train_configure: bad argument");
+    if (!std::isfinite(q->lr) || !(q->lr > 0.0f)) return fail(c, UVAD_E_ARG, "uvad_lstm_train_configure: lr must be finite and positive");
+    if (!std::isfinite(q->beta1) || q->beta1 < 0.0f || !(q->beta1 < 1.0f)) return fail(c, UVAD_E_ARG, "uvad_lstm_train_configure: beta1 must lie in [0, 1)");
+    if (!std::isfinite(q->beta2) || q->beta2 < 0.0f || !(q->beta2 < 1.0f)) return fail(c, UVAD_E_ARG, "uvad_lstm_train_configure: beta2 must lie in [0, 1)");
+    if (!std::isfinite(q->eps) || !(q->eps > 0.0f)) return fail(c, UVAD_E_ARG, "uvad_lstm_train_configure: eps must be finite and positive");
+    if (q->segment != 0 && (q->segment < HT_MIN_SEGMENT || q->segment > HT_MAX_SEGMENT || q->segment % 32))
+        return fail(c, UVAD_E_ARG, "uvad_lstm_train_configure: segment must be 0 or a multiple of 32 in [32, 16384] frames");
+    if (!c->has_model) return fail(c, UVAD_E_STATE, "uvad_lstm_train_configure: context was created without a model configuration");
+    const uvad_model_cfg &m = c->mc;
+    if (q->first_layer < 0 || q->first_layer >= m.num_layers)
+        return fail(c, UVAD_E_ARG, "uvad_lstm_train_configure: first_layer must lie in [0, num_layers)");
+    if (m.hidden != 64 && m.hidden != 128) return fail(c, UVAD_E_UNSUPPORTED, "uvad_lstm_train_configure: hidden must be 64 or 128");
+    if (m.num_layers - q->first_layer > LT_MAX_LAYERS) return fail(c, UVAD_E_UNSUPPORTED, "uvad_lstm_train_configure: at most 8 trainable layers");
+    const int dirs = m.bidirectional ? 2 : 1;
+    const int Din = q->first_layer == 0 ? m.in_dim : m.hidden * dirs;
+    if (Din < 4 || Din % 4 || Din > LT_MAX_DIN)
+        return fail(c, UVAD_E_UNSUPPORTED, "uvad_lstm_train_configure: the input width of first_layer must be a multiple of 4, at most 2048");
+    c->lq = *q;
+    if (c->lq.segment == 0) c->lq.segment = HT_DEFAULT_SEGMENT;
+    c->lts = lstm_train_shape(Din, m.hidden, dirs, m.num_layers, q->first_layer);
+    c->has_lt = true;
+    return UVAD_OK;
+}
+
+int64_t uvad_lstm_train_param_count(const uvad_ctx *c) { return c && c->has_lt ? (int64_t)c->lts.P : 0; }
+size_t uvad_lstm_train_state_bytes(const uvad_ctx *c) { return c && c->has_lt ? lstm_train_state_bytes(c->lts) : 0; }
+
+size_t uvad_lstm_train_ws_bytes(const uvad_ctx *c, int B, int T) {
+    if (!c || !c->has_lt || B < 1 || T < 1 || (long long)B * T > HT_MAX_FRAMES) return 0;
+    return lstm_train_ws(c->lts, (long long)B * T, c->lq.segment).total;
+}
+
+static int lstm_train_state_check(uvad_ctx *c, const char *fn, const void *d_state, size_t state_bytes, bool reset) {
+    const std::string f(fn);
+    if (!d_state) return fail(c, UVAD_E_ARG, f + ": bad argument");
+    if (!c->has_lt) return fail(c, UVAD_E_STATE, f + ": call uvad_lstm_train_configure first");
+    const size_t need = lstm_train_state_bytes(c->lts);
+    if (state_bytes < need) return fail(c, UVAD_E_ARG, f + ": state too small: need " + std::to_string(need) + " bytes");
+    if (reset) return UVAD_OK;
+    auto it = c->lstm_trains.find(const_cast<void *>(d_state));
+    if (it == c->lstm_trains.end()) return fail(c, UVAD_E_STATE, f + ": call uvad_lstm_train_reset on this state first");
+    if (it->second != c->lts.P) return fail(c, UVAD_E_STATE, f + ": the state was reset under another shape");
+    return UVAD_OK;
+}
+
+// the torch key of a trainable tensor: which = 0 .. 3 (weight_ih, weight_hh, bias_ih, bias_hh)
+static std::string lstm_train_key(int layer, int dir, int which) {
+    const char *const names[4] = {"weight_ih", "weight_hh", "bias_ih", "bias_hh"};
+    return std::string("lstm.") + names[which] + "_l" + std::to_string(layer) + (dir ? "_reverse" : "");
+}
+
+int uvad_lstm_train_reset(uvad_ctx *c, void *d_state, size_t state_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (int r = lstm_train_state_check(c, "uvad_lstm_train_reset", d_state, state_bytes, true)) return r;
+    if (!c->finalized) return fail(c, UVAD_E_STATE, "uvad_lstm_train_reset: call uvad_finalize first");
+    const LstmTrainShape &q = c->lts;
+    std::vector<float> w((size_t)q.P);
+    for (int li = 0; li < q.nl; ++li)
+        for (int d = 0; d < q.dirs; ++d)
+            for (int k = 0; k < 4; ++k) {
+                const std::string key = lstm_train_key(q.first_layer + li, d, k);
+                auto it = c->host_w.find(key);
+                const size_t n = (size_t)4 * q.H * (k == 0 ? q.in[li] : k == 1 ? q.H : 1);
+                if (it == c->host_w.end() || it->second.data.size() != n) return fail(c, UVAD_E_STATE, "uvad_lstm_train_reset: missing LSTM tensor " + key);
+                std::memcpy(w.data() + q.off[li][d][k], it->second.data.data(), n * sizeof(float));
+            }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));   // the masters come from the host tensors: a blocking copy, then the rest on the stream
+    HIPCHK(c, hipMemcpy(reinterpret_cast<char *>(d_state) + sizeof(HeadTrainHeader), w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(c, launch_lstm_train_reset(q, d_state, (hipStream_t)stream));
+    c->lstm_trains[d_state] = q.P;
+    return UVAD_OK;
+}
+
+// the checks forward and backward share, in the head's order: arguments, configuration and sizes, then that the state was reset
+static int lstm_train_call_check(uvad_ctx *c, const char *fn, const void *d_x, const void *d_other, int B, int T, void *d_state, size_t state_bytes,
+                                 void *d_ws, size_t ws_bytes) {
+    const std::string f(fn);
+    if (!d_x || !d_other || !d_state || !d_ws || B < 1 || T < 1) return fail(c, UVAD_E_ARG, f + ": bad argument");
+    if (reinterpret_cast<uintptr_t>(d_state) % 16 || reinterpret_cast<uintptr_t>(d_ws) % 16)
+        return fail(c, UVAD_E_ARG, f + ": d_state and d_ws must be 16-byte aligned");
+    if ((long long)B * T > HT_MAX_FRAMES) return fail(c, UVAD_E_ARG, f + ": B x T above 2^24 frames");
+    if (c->has_lt && ((long long)B * T + c->lq.segment - 1) / c->lq.segment > 65535)
+        return fail(c, UVAD_E_ARG, f + ": more than 65535 segments: B x T / segment too large");
+    if (int r = lstm_train_state_check(c, fn, d_state, state_bytes, true)) return r;
+    const size_t need = lstm_train_ws(c->lts, (long long)B * T, c->lq.segment).total;
+    if (ws_bytes < need) return fail(c, UVAD_E_ARG, f + ": workspace too small: need " + std::to_string(need) + " bytes");
+    return lstm_train_state_check(c, fn, d_state, state_bytes, false);
+}
+
+int uvad_lstm_train_forward(uvad_ctx *c, const float *d_x_in, int B, int T, const int32_t *d_lens, float *d_y, void *d_state, size_t state_bytes,
+                            void *d_ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (int r = lstm_train_call_check(c, "uvad_lstm_train_forward", d_x_in, d_y, B, T, d_state, state_bytes, d_ws, ws_bytes)) return r;
+    LstmTrainArgs a{};
+    a.x = d_x_in; a.B = B; a.T = T; a.lens = d_lens; a.y = d_y; a.state = d_state; a.ws = d_ws; a.seg = c->lq.segment;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_lstm_train_forward(c->lts, a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_lstm_train_backward(uvad_ctx *c, const float *d_x_in, const float *d_dy, int B, int T, const int32_t *d_lens, float *d_grad_in,
+                             void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (int r = lstm_train_call_check(c, "uvad_lstm_train_backward", d_x_in, d_dy, B, T, d_state, state_bytes, d_ws, ws_bytes)) return r;
+    LstmTrainArgs a{};
+    a.x = d_x_in; a.dy = d_dy; a.B = B; a.T = T; a.lens = d_lens; a.grad_in = d_grad_in; a.state = d_state; a.ws = d_ws; a.seg = c->lq.segment;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_lstm_train_backward(c->lts, a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_lstm_train_apply(uvad_ctx *c, void *d_state, size_t state_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (int r = lstm_train_state_check(c, "uvad_lstm_train_apply", d_state, state_bytes, false)) return r;
+    const uvad_lstm_train_cfg &q = c->lq;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_lstm_train_apply(c->lts, adam_of(q.lr, q.beta1, q.beta2, q.eps), d_state, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_lstm_train_read(uvad_ctx *c, const void *d_state, size_t state_bytes, int which, float *d_out, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_out || which < 0 || which > UVAD_HEAD_TRAIN_SCALARS) return fail(c, UVAD_E_ARG, "uvad_lstm_train_read: bad argument");
+    if (int r = lstm_train_state_check(c, "uvad_lstm_train_read", d_state, state_bytes, false)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_lstm_train_read(c->lts, d_state, which, d_out, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_lstm_train_commit(uvad_ctx *c, const void *d_state, size_t state_bytes) {
+    if (!c) return UVAD_E_ARG;
+    if (int r = lstm_train_state_check(c, "uvad_lstm_train_commit", d_state, state_bytes, false)) return r;
+    if (!c->finalized) return fail(c, UVAD_E_STATE, "uvad_lstm_train_commit: call uvad_finalize first");
+    const LstmTrainShape q = c->lts;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());   // every enqueued backward / apply has landed
+    std::vector<float> w((size_t)q.P);
+    HIPCHK(c, hipMemcpy(w.data(), reinterpret_cast<const char *>(d_state) + sizeof(HeadTrainHeader), w.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int li = 0; li < q.nl; ++li)
+        for (int d = 0; d < q.dirs; ++d)
+            for (int k = 0; k < 4; ++k) {
+                const int64_t shape[2] = {4 * q.H, k == 0 ? q.in[li] : q.H};
+                if (int r = uvad_set_weight(c, lstm_train_key(q.first_layer + li, d, k).c_str(), w.data() + q.off[li][d][k], shape, k < 2 ? 2 : 1)) return r;
+            }
     return uvad_finalize(c);
 }
 

@@ -802,4 +802,42 @@ hipError_t launch_head_train_grad(const HeadTrainShape &q, const HeadTrainGradAr
 hipError_t launch_head_train_apply(const HeadTrainShape &q, const HeadTrainAdam &o, void *state, hipStream_t s);
 hipError_t launch_head_train_read(const HeadTrainShape &q, const void *state, int which, float *out, hipStream_t s);
 
+// ---- lstm_train.hip: training of the top LSTM layers (uvad_lstm_train_*, include/uvad.h): forward with kept activations, BPTT, Adam ----
+// Layers first_layer .. num_layers - 1 learn; nl of them, layer index li = 0 .. nl - 1 from the bottom.  Frames are flat, n = b T + t, N = B T.
+// The trainable tensors are packed in state_dict order -- per layer, forward then _reverse: weight_ih [4H][in], weight_hh [4H][H],
+// bias_ih [4H], bias_hh [4H] (in = Din for li = 0, H x dirs above) -- P floats, padded to Pp = a multiple of 64.
+// State: HeadTrainHeader with LT_MAGIC (256 bytes) | masters [Pp] | gradient accumulator [Pp] | m [Pp] | v [Pp]: the head's layout, so the
+//        fold, Adam and read kernels of ht_kernels.h serve both.
+// Workspace: LstmTrainWsHead (256 bytes: magic, B, T) | HeadTrainWsHead (the fold's record of the last backward) | valid [N] bytes |
+//            b_ih + b_hh [nl][dirs][4H] | per layer: gates [dirs][N][4H] (pre-activations, then i f g o, then dpre), c [dirs][N][H],
+//            h_prev [dirs][N][H], and below the top layer its output h [N][H dirs] | two gradient buffers [N][H dirs] (nl > 1) |
+//            gradient partials [nseg][Pp]; every part 256-byte aligned.
+constexpr int LT_MAX_LAYERS = 8, LT_MAX_DIN = 2048;
+constexpr unsigned LT_MAGIC = 0x55564C54u;           // "UVLT": the state
+constexpr int LT_WS_MAGIC = 0x4C545753;              // "LTWS": a workspace whose kept activations belong to (B, T)
+struct LstmTrainShape {
+    int Din, H, dirs, nl, first_layer, P, Pp;
+    int in[LT_MAX_LAYERS];                           // input width of layer li
+    int off[LT_MAX_LAYERS][2][4];                    // weight_ih, weight_hh, bias_ih, bias_hh of (li, direction)
+};
+struct LstmTrainWsHead { int magic, B, T; int reserved[61]; };   // written by the forward call, checked by every backward kernel
+struct LstmTrainWs {
+    size_t off_fold, off_valid, off_bsum, off_gates[LT_MAX_LAYERS], off_c[LT_MAX_LAYERS], off_hprev[LT_MAX_LAYERS], off_h[LT_MAX_LAYERS], off_d[2],
+        off_part, total;
+    int N, nseg;
+};
+struct LstmTrainArgs {
+    const float *x; const float *dy; int B, T; const int *lens;
+    float *y; float *grad_in;
+    void *state; void *ws; int seg;
+};
+LstmTrainShape lstm_train_shape(int Din, int H, int dirs, int num_layers, int first_layer);
+size_t lstm_train_state_bytes(const LstmTrainShape &q);
+LstmTrainWs lstm_train_ws(const LstmTrainShape &q, long long N, int seg);
+hipError_t launch_lstm_train_reset(const LstmTrainShape &q, void *state, hipStream_t s);   // masters are copied in by the caller
+hipError_t launch_lstm_train_forward(const LstmTrainShape &q, const LstmTrainArgs &a, hipStream_t s);
+hipError_t launch_lstm_train_backward(const LstmTrainShape &q, const LstmTrainArgs &a, hipStream_t s);
+hipError_t launch_lstm_train_apply(const LstmTrainShape &q, const HeadTrainAdam &o, void *state, hipStream_t s);
+hipError_t launch_lstm_train_read(const LstmTrainShape &q, const void *state, int which, float *out, hipStream_t s);
+
 }  // namespace uvad

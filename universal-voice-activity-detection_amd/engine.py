@@ -3,8 +3,9 @@ inference and scoring surface: constructor arguments, ``.model`` / ``.model_name
 ``predict_step``, ``test_step``, ``validation_step``, ``_common_step`` and ``load_from_checkpoint``
 keep their names, argument meaning and return shapes; what the reference logs through torchmetrics
 is accumulated on the device (``uvad_score_*``) and read with ``test_metrics`` / ``validation_metrics``.
-``adapt_head_step`` / ``adapt_head_commit`` fine-tune the head on the device (``uvad_head_train_*``); full training
-(``training_step``, ``configure_optimizers``: back-propagation through the LSTM stack) is outside the accelerated path and raises."""
+``adapt_head_step`` / ``adapt_head_commit`` fine-tune the head on the device (``uvad_head_train_*``); ``adapt_step`` /
+``adapt_commit`` let the top LSTM layers learn with it (``uvad_lstm_train_*``).  ``training_step`` and ``configure_optimizers``
+themselves (gradients into a SincNet front end, dropout, DDP) are outside the accelerated path and raise."""
 import torch
 import torch.nn as nn
 
@@ -157,6 +158,59 @@ class VadModel(nn.Module):
         params = dict(self.model.named_parameters())
         with torch.no_grad():
             for key, t in rt.head_train_state_dict(h).items():
+                params[key].copy_(t.to(params[key].device))
+        self.model._rt_stamp = self.model._stamp(rt.device)   # the runtime already holds these very tensors: no second upload
+
+    # -- adaptation of the head AND the top LSTM layers (uvad_head_train_* + uvad_lstm_train_*) -------------------------------------
+    def lstm_in(self, batch, lstm_layers: int = 1) -> torch.Tensor:
+        """The frozen prefix's output for batch["inputs"]: the input of the lowest learning LSTM layer (the features themselves, or the
+        SincNet output, when every layer learns).  What adapt_step trains on, and what a caller may cache as batch["lstm_in"]."""
+        x = batch["inputs"]
+        rt = self.model.runtime(x.device)
+        if self.model_name == "PyanNet":
+            x = rt.sincnet(x[:, 0, :] if x.dim() == 3 else x)
+        return rt.lstm_train_input(x, lengths=batch.get("lengths"), layers=lstm_layers)
+
+    def adapt_step(self, batch, batch_idx=0, accumulate: int = 1, lstm_layers: int = 1):
+        """One micro-batch in which the head and the top `lstm_layers` LSTM layers learn: batch["lstm_in"] (the cached frozen prefix) or
+        batch["inputs"] through it, the learning layers' forward pass with kept activations, the head's loss and backward pass as
+        adapt_head_step's, backpropagation through time from its input gradient; every `accumulate` calls one Adam step on both
+        states (lr = self.learning_rate).  Returns the batch's mean loss as a 0-d tensor on the device without synchronising."""
+        y = batch.get("is_voice")
+        if y is None:
+            raise ValueError('adapt_step needs batch["is_voice"]')
+        x = batch["lstm_in"] if batch.get("lstm_in") is not None else self.lstm_in(batch, lstm_layers)
+        rt = self.model.runtime(x.device)
+        held = getattr(self, "_adapt_full", None)
+        if held is None or held[0] is not rt or held[2]["layers"] != int(lstm_layers):
+            held = self._adapt_full = [rt, rt.head_train_open(lr=self.learning_rate), rt.lstm_train_open(layers=lstm_layers, lr=self.learning_rate), 0]
+        hh, hl = held[1], held[2]
+        lengths = batch.get("lengths")
+        gt = (y.to(x.device) != 0).to(torch.uint8).reshape(x.shape[:2])
+        out = rt.lstm_train_forward(hl, x, lengths=lengths)
+        _, gx = rt.head_train_grad(hh, out, gt, lengths=lengths, want_grad_x=True)
+        rt.lstm_train_backward(hl, x, gx, lengths=lengths)
+        held[3] += 1
+        if held[3] % max(1, int(accumulate)) == 0:
+            rt.head_train_apply(hh)
+            rt.lstm_train_apply(hl)
+        return rt.head_train_batch_loss(hh)
+
+    def adapt_commit(self):
+        """Serve the adapted head and LSTM layers from now on (uvad_lstm_train_commit + uvad_head_train_commit) and write them into
+        self.model's parameters, so that state_dict() and torch.save give the adapted checkpoint.  Synchronises."""
+        held = getattr(self, "_adapt_full", None)
+        if held is None:
+            raise RuntimeError("no adapt_step has run yet")
+        rt, hh, hl = held[0], held[1], held[2]
+        rt.lstm_train_commit(hl)
+        rt.head_train_commit(hh)
+        params = dict(self.model.named_parameters())
+        with torch.no_grad():
+            for key, t in list(rt.head_train_state_dict(hh).items()) + list(rt.lstm_train_state_dict(hl).items()):
+                if key not in params:   # the ModuleList-of-LSTMs variant: lstm.{k}.weight_ih_l0[_reverse]
+                    name, k = key[len("lstm."):].split("_l", 1)
+                    key = f"lstm.{k.replace('_reverse', '')}.{name}_l0" + ("_reverse" if k.endswith("_reverse") else "")
                 params[key].copy_(t.to(params[key].device))
         self.model._rt_stamp = self.model._stamp(rt.device)   # the runtime already holds these very tensors: no second upload
 

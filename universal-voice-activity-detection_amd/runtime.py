@@ -2,6 +2,7 @@
 used only as device-memory containers whose ``data_ptr()`` is handed to the C ABI together with
 torch's current HIP stream.  Every method fails loudly if libuvad.so or the GPU is missing."""
 import ctypes as C
+import re
 from typing import Dict, Optional
 
 import numpy as np
@@ -257,7 +258,14 @@ class VadRuntime:
             self._check(self.lib.uvad_set_weight(self.ctx, k.encode(), a.ctypes.data, shape, a.ndim))
         self._check(self.lib.uvad_finalize(self.ctx))
         self._finalized = True
+        self._loaded_sd = dict(sd)       # references, not copies: lstm_train_input builds the frozen prefix's sibling context from them
+        self._drop_lstm_prefix()
         self._weights_gen = getattr(self, "_weights_gen", 0) + 1   # uvad_finalize re-allocates every weight buffer: graphs captured before are stale
+
+    def _drop_lstm_prefix(self):
+        for rt in getattr(self, "_lstm_prefix", {}).values():
+            rt.close()
+        self._lstm_prefix = {}
 
     # ------------------------------------------------------------------ helpers
     def _check(self, code):
@@ -1396,6 +1404,145 @@ class VadRuntime:
             self._check(self.lib.uvad_head_train_commit(self.ctx, h["state"].data_ptr(), h["state"].numel()))
             self._weights_gen = getattr(self, "_weights_gen", 0) + 1
 
+    # ------------------------------------------------------------------ LSTM training (uvad_lstm_train_*)
+    def _lstm_train_shape(self, first_layer: int):
+        m = self._mc_c
+        dirs = 2 if m.bidirectional else 1
+        return (m.in_dim if first_layer == 0 else m.hidden * dirs), m.hidden, dirs, m.num_layers, first_layer
+
+    def lstm_train_keys(self, layers: int = 1):
+        """[(torch key, shape)] of the trainable tensors of the top `layers` LSTM layers in the packed order of uvad_lstm_train_read
+        (state_dict order: per layer, forward then _reverse, weight_ih, weight_hh, bias_ih, bias_hh)."""
+        Din, H, dirs, L, first = self._lstm_train_shape(self._mc_c.num_layers - int(layers))
+        out = []
+        for k in range(first, L):
+            K = Din if k == first else H * dirs
+            for d in range(dirs):
+                suf = f"_l{k}" + ("_reverse" if d else "")
+                out += [(f"lstm.weight_ih{suf}", (4 * H, K)), (f"lstm.weight_hh{suf}", (4 * H, H)), (f"lstm.bias_ih{suf}", (4 * H,)),
+                        (f"lstm.bias_hh{suf}", (4 * H,))]
+        return out
+
+    def lstm_train_open(self, layers: int = 1, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, segment: int = 0):
+        """Allocate and reset a training state for the top `layers` layers of the LSTM stack (uvad_lstm_train_reset): f32 master copies of
+        their tensors as loaded, Adam moments, the gradient accumulator; first_layer = num_layers - layers, the layers below stay frozen.
+        The handle owns the state and the workspace."""
+        layers = int(layers)
+        if not 1 <= layers <= self._mc_c.num_layers:
+            raise ValueError(f"layers must lie in 1 .. {self._mc_c.num_layers}")
+        cfg = _lib.LstmTrainCfg(float(lr), float(betas[0]), float(betas[1]), float(eps), int(segment), self._mc_c.num_layers - layers)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_lstm_train_configure(self.ctx, C.byref(cfg)))
+            P = int(self.lib.uvad_lstm_train_param_count(self.ctx))
+            h = {"cfg": cfg, "P": P, "layers": layers, "first_layer": cfg.first_layer, "ws": None, "bt": None,
+                 "state": torch.empty(int(self.lib.uvad_lstm_train_state_bytes(self.ctx)), dtype=torch.uint8, device=self.device),
+                 "out": torch.zeros(max(P, _lib.HEAD_TRAIN_SCALAR_WORDS), dtype=torch.float32, device=self.device)}
+            self._check(self.lib.uvad_lstm_train_reset(self.ctx, h["state"].data_ptr(), h["state"].numel(), self._stream()))
+            return h
+
+    def lstm_train_input(self, x: "torch.Tensor", lengths=None, layers: int = 1) -> "torch.Tensor":
+        """The input of layer first_layer = num_layers - layers for the features x (B, T, encoding_dim): the frozen prefix's output, which a
+        caller caches across epochs.  x itself when every layer learns; otherwise the LSTM tap of a sibling context holding a
+        first_layer-layer copy of the model as loaded (classify + taps).  Host code only."""
+        first = self._mc_c.num_layers - int(layers)
+        if first == 0:
+            return self._dev_f32(x, "x")
+        sib = self._lstm_prefix.get(first)
+        if sib is None:
+            top = re.compile(r"(?:^|\.)lstm\.(?:(\d+)\.)?\w+_l(\d+)(?:_reverse)?$")
+
+            def frozen(key):
+                m = top.search(key)
+                return m is None or int(m.group(1) if m.group(1) is not None else m.group(2)) < first
+            rt = VadRuntime(self.device, model=dict(self.model_cfg, lstm=dict(self.model_cfg["lstm"], num_layers=first)))
+            rt.load_state_dict({k: v for k, v in self._loaded_sd.items() if frozen(k) and ".sincnet." not in k and not k.startswith("sincnet.")})
+            sib = self._lstm_prefix[first] = rt
+        sib.classify(x, want_logits=True, want_probs=False, lengths=lengths)
+        return sib.taps(lin=False)[0]
+
+    def _lstm_train_ws(self, h, B: int, T: int):
+        self._check(self.lib.uvad_lstm_train_configure(self.ctx, C.byref(h["cfg"])))   # host only: the context serves any number of handles
+        need = int(self.lib.uvad_lstm_train_ws_bytes(self.ctx, B, T))
+        if h["ws"] is None or h["ws"].numel() < need:
+            h["ws"] = torch.zeros(need, dtype=torch.uint8, device=self.device)
+
+    def lstm_train_forward(self, h, x_in: "torch.Tensor", lengths=None) -> "torch.Tensor":
+        """The trainable layers' forward pass with the state's master weights (uvad_lstm_train_forward), keeping the activations in the
+        handle's workspace: x_in (B, T, Din) from lstm_train_input -> y (B, T, hidden x directions), what head_train_grad takes as x.
+        No copy to the host and no synchronisation."""
+        with torch.cuda.device(self.device):
+            x_in = self._dev_f32(x_in, "x_in")
+            B, T, Din = x_in.shape
+            want = self._lstm_train_shape(h["first_layer"])[0]
+            if Din != want:
+                raise ValueError(f"x_in has {Din} columns, layer {h['first_layer']} takes {want}")
+            n = None if lengths is None else self._dev_lens(lengths, B, T, torch.int32, "lengths (frames)")
+            self._lstm_train_ws(h, B, T)
+            y = torch.empty((B, T, self._mc_c.hidden * (2 if self._mc_c.bidirectional else 1)), dtype=torch.float32, device=self.device)
+            self._check(self.lib.uvad_lstm_train_forward(self.ctx, x_in.data_ptr(), B, T, n.data_ptr() if n is not None else None, y.data_ptr(),
+                                                         h["state"].data_ptr(), h["state"].numel(), h["ws"].data_ptr(), h["ws"].numel(), self._stream()))
+            h["_keep"] = (x_in, n, y)
+            return y
+
+    def lstm_train_backward(self, h, x_in: "torch.Tensor", dy: "torch.Tensor", lengths=None, want_grad_in: bool = False):
+        """Backpropagation through time from dy (B, T, hidden x directions), head_train_grad's grad_x, through the activations the last
+        lstm_train_forward of this handle kept (uvad_lstm_train_backward): adds the gradients and the frame count into the state.
+        -> grad_in (B, T, Din) | None."""
+        with torch.cuda.device(self.device):
+            x_in, dy = self._dev_f32(x_in, "x_in"), self._dev_f32(dy, "dy")
+            B, T, _ = x_in.shape
+            if tuple(dy.shape) != (B, T, self._mc_c.hidden * (2 if self._mc_c.bidirectional else 1)):
+                raise ValueError(f"dy has shape {tuple(dy.shape)}")
+            n = None if lengths is None else self._dev_lens(lengths, B, T, torch.int32, "lengths (frames)")
+            self._lstm_train_ws(h, B, T)
+            g = torch.empty_like(x_in) if want_grad_in else None
+            self._check(self.lib.uvad_lstm_train_backward(self.ctx, x_in.data_ptr(), dy.data_ptr(), B, T, n.data_ptr() if n is not None else None,
+                                                          g.data_ptr() if g is not None else None, h["state"].data_ptr(), h["state"].numel(),
+                                                          h["ws"].data_ptr(), h["ws"].numel(), self._stream()))
+            h["_keep_b"] = (x_in, dy, n, g)
+            return g
+
+    def lstm_train_apply(self, h):
+        """One Adam step from the accumulated gradients divided by the accumulated frame count (uvad_lstm_train_apply)."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_lstm_train_configure(self.ctx, C.byref(h["cfg"])))
+            self._check(self.lib.uvad_lstm_train_apply(self.ctx, h["state"].data_ptr(), h["state"].numel(), self._stream()))
+
+    def _lstm_train_block(self, h, which: int) -> np.ndarray:
+        self._check(self.lib.uvad_lstm_train_read(self.ctx, h["state"].data_ptr(), h["state"].numel(), which, h["out"].data_ptr(), self._stream()))
+        return h["out"].cpu().numpy().copy()
+
+    def lstm_train_read(self, h) -> dict:
+        """Copy the state to the host (synchronises) -> {"weights", "grad", "m", "v": {torch key: tensor}, "frames", "step",
+        "bias_correction1", "bias_correction2" (1 - beta^step)}."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_lstm_train_configure(self.ctx, C.byref(h["cfg"])))
+            out = {}
+            for name, which in (("weights", _lib.HEAD_TRAIN_MASTERS), ("grad", _lib.HEAD_TRAIN_GRAD), ("m", _lib.HEAD_TRAIN_M), ("v", _lib.HEAD_TRAIN_V)):
+                flat, off, d = self._lstm_train_block(h, which), 0, {}
+                for key, shape in self.lstm_train_keys(h["layers"]):
+                    cnt = int(np.prod(shape))
+                    d[key] = torch.from_numpy(flat[off:off + cnt].reshape(shape).copy())
+                    off += cnt
+                out[name] = d
+            w = self._lstm_train_block(h, _lib.HEAD_TRAIN_SCALARS)[:_lib.HEAD_TRAIN_SCALAR_WORDS]
+        out["frames"] = int(w[2:4].view(np.uint64)[0])
+        out["step"] = int(w[4:6].view(np.uint64)[0])
+        out["bias_correction1"], out["bias_correction2"] = float(w[6]), float(w[7])
+        return out
+
+    def lstm_train_state_dict(self, h) -> dict:
+        """The adapted LSTM tensors keyed by torch key, ready to merge into a checkpoint (synchronises)."""
+        return self.lstm_train_read(h)["weights"]
+
+    def lstm_train_commit(self, h):
+        """Make this runtime serve the adapted layers (uvad_lstm_train_commit: synchronises, re-finalizes).  Graphs captured before are
+        stale, as after load_state_dict; the frozen prefix's sibling context is untouched."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_lstm_train_configure(self.ctx, C.byref(h["cfg"])))
+            self._check(self.lib.uvad_lstm_train_commit(self.ctx, h["state"].data_ptr(), h["state"].numel()))
+            self._weights_gen = getattr(self, "_weights_gen", 0) + 1
+
     # ------------------------------------------------------------------ scoring against reference labels (uvad_score_*)
     def score_open(self, points=((0.5, 25),), collar: int = 0, bins: int = 256, segment: int = 0):
         """Allocate and reset a scoring state (uvad_score_reset): points [(threshold, odd median kernel)], 1 .. 8 of them; collar frames
@@ -2189,6 +2336,7 @@ class VadRuntime:
 
     # ------------------------------------------------------------------ teardown
     def close(self):
+        self._drop_lstm_prefix()
         if getattr(self, "ctx", None) is not None and self.ctx:
             self.lib.uvad_destroy(self.ctx)
             self.ctx = C.c_void_p()

@@ -784,7 +784,9 @@ def adapt_vad(**kwargs):
     ``max_epochs`` epochs of VadModel.adapt_head_step run over the cached taps (``accumulate_grad_batches`` calls per Adam step, lr =
     ``learning_rate``); every ``check_val_every_n_epoch`` epochs the head is committed and validation_step runs on the held-out files.
     Saves a Lightning-style checkpoint {"state_dict" (``model.`` keys), "epoch", "global_step"} to ``adapted_checkpoint_path`` (default:
-    experiments_dir/adapted.ckpt) and returns {"train_loss": [per epoch], "val_loss": [(epoch, loss)], "val_metrics", "checkpoint_path"}."""
+    experiments_dir/adapted.ckpt) and returns {"train_loss": [per epoch], "val_loss": [(epoch, loss)], "val_metrics", "checkpoint_path"}.
+    ``adapt_lstm_layers`` > 0: that many top LSTM layers learn as well (VadModel.adapt_step / adapt_commit); what is cached per recording
+    is then the frozen prefix's output, the input of the lowest learning layer."""
     from .postprocess import read_label_file, supervision_frames
     src = kwargs["input"]
     if src.get("kind") != "wav" or not src.get("paths") or len(src.get("labels", ())) != len(src["paths"]):
@@ -799,6 +801,7 @@ def adapt_vad(**kwargs):
     device = _resolve_device(kwargs["device"])
     model_dict, sr = dict(kwargs["model_dict"]), 16000
     lr = float(kwargs.get("learning_rate", 1e-3))
+    lstm_layers = int(kwargs.get("adapt_lstm_layers", 0) or 0)
     if kwargs["load_checkpoint"]:
         model = VadModel.load_from_checkpoint(checkpoint_path=kwargs["checkpoint_path"], model_name=kwargs["model_name"], model_dict=model_dict,
                                               learning_rate=lr)
@@ -816,9 +819,10 @@ def adapt_vad(**kwargs):
         pcm = torch.from_numpy(_wav_recordings(path, "first", rt, sr)[0]["pcm"]).to(device)[None]
         inputs = pcm if sincnet else rt.fbank(pcm)                  # (1, samples) for PyanNet, as _common_step takes them; (1, T, F) log-mel
         b = {"inputs": inputs}
+        key = "lstm_in" if lstm_layers else "lstm_out"
         if cache:
-            b["lstm_out"] = model.lstm_out(b).clone()
-        T = b["lstm_out"].shape[1] if cache else (net.num_frames(pcm.shape[1]) if sincnet else inputs.shape[1])
+            b[key] = (model.lstm_in(b, lstm_layers) if lstm_layers else model.lstm_out(b)).clone()
+        T = b[key].shape[1] if cache else (net.num_frames(pcm.shape[1]) if sincnet else inputs.shape[1])
         table = supervision_frames(read_label_file(label_path), pcm.shape[1] / float(sr), frame_shift=kwargs["frame_shift"],
                                    geometry="sincnet" if sincnet else "fbank", num_frames=T)
         iv = np.zeros((1, max(len(table), 1), 2), np.int32)
@@ -834,7 +838,7 @@ def adapt_vad(**kwargs):
 
     def validate(epoch):
         if epoch:                                                 # validation_step runs the context's head: serve the adapted one
-            model.adapt_head_commit()
+            model.adapt_commit() if lstm_layers else model.adapt_head_commit()
         for i, b in enumerate(held):
             model.validation_step(b, i)
         out["val_metrics"] = model.validation_metrics(reset=True)
@@ -844,7 +848,10 @@ def adapt_vad(**kwargs):
     validate(0)
     step = 0
     for epoch in range(1, epochs + 1):
-        losses = [model.adapt_head_step(b, i, accumulate=accumulate) for i, b in enumerate(train)]
+        if lstm_layers:
+            losses = [model.adapt_step(b, i, accumulate=accumulate, lstm_layers=lstm_layers) for i, b in enumerate(train)]
+        else:
+            losses = [model.adapt_head_step(b, i, accumulate=accumulate) for i, b in enumerate(train)]
         step += len(train)
         out["train_loss"].append(float(torch.stack(losses).mean()))
         if epoch % every == 0 or epoch == epochs:
