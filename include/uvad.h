@@ -1127,7 +1127,8 @@ int uvad_gate_group_step(uvad_ctx *, const void *d_chunk, int chunk, int B, cons
  * slice of the model, VadModel.training_step / _common_step (src/engines/vad_engine.py:247-278: the head expression of
  * PyanNet2.forward, F.leaky_relu(linear(x)) and sigmoid(classifier(x)), F.binary_cross_entropy with the mean over the frames present,
  * src/utils/loss.py:56-89, and autograd's backward pass through them) and configure_optimizers (:280: torch.optim.Adam, no weight decay).
- * Gradients into a SincNet front end, dropout, weight decay, schedules and DDP are not here; d_grad_x is where the backward pass through
+ * Gradients into a SincNet front end, weight decay, schedules and DDP are not here (dropout between LSTM layers is a stage of
+ * uvad_lstm_train_*, below; the head has none in the reference either); d_grad_x is where the backward pass through
  * the LSTM stack starts (uvad_lstm_train_backward below takes it as d_dy).
  *
  * With s = leaky_slope, a_0 = x0, a_l = leaky_relu(a_{l-1} W_l^T + b_l, s) for l = 1 .. L, z = a_L . w_c + b_c, p = sigmoid(z), a frame
@@ -1198,7 +1199,8 @@ int uvad_head_train_commit(uvad_ctx *, const void *d_state, size_t state_bytes);
  * kernels as before (their output, or the features themselves when first_layer is 0, is this block's input and may be cached across
  * epochs).  Together with uvad_head_train_* this is VadModel.training_step / configure_optimizers (src/engines/vad_engine.py:247-281)
  * for everything above the front end: nn.LSTM on pack_padded_sequence rows, autograd's backward pass through it, torch.optim.Adam.
- * Gradients into a SincNet front end, dropout, weight decay, schedules and DDP are not here.
+ * Gradients into a SincNet front end, weight decay, schedules and DDP are not here.  Dropout between the trainable layers is
+ * (uvad_lstm_train_set_dropout, defined below); the frozen prefix runs in eval mode.
  *
  * d_x_in [B][T][Din] is the dense f32 input of layer first_layer (Din = in_dim when first_layer is 0, else hidden x directions);
  * d_y [B][T][hidden x directions] the top layer's output computed with the STATE's f32 master weights: what uvad_head_train_grad takes as
@@ -1229,7 +1231,37 @@ int uvad_head_train_commit(uvad_ctx *, const void *d_state, size_t state_bytes);
  * Refusals (nothing enqueued).  UVAD_E_ARG: NULL cfg / d_x_in / d_y / d_dy / d_state / d_ws / d_out; d_state or d_ws not 16-byte aligned
  *   (forward, backward); lr, beta1, beta2, eps, segment as the head's; first_layer outside [0, num_layers); B < 1; T < 1; B T > 2^24 or more than 65535 segments; state_bytes or ws_bytes below
  *   the helpers; which outside 0 .. 4.  UVAD_E_STATE: a context without a model; no uvad_lstm_train_configure yet; a context that is not
- *   finalized (reset, commit); a state that was never reset, or reset under another shape. */
+ *   finalized (reset, commit); a state that was never reset, or reset under another shape.
+ *
+ * Dropout between the trainable layers: nn.LSTM(dropout = p) in training mode.  uvad_lstm_train_set_dropout(ctx, p, seed) sets what every
+ *   later uvad_lstm_train_forward of the context applies; a new context has p = 0, and uvad_lstm_train_configure leaves the setting
+ *   alone.  With p = 0 forward and backward launch the kernels they launched before this stage existed and write nothing into the state.
+ *   The mask is a pure function of its coordinates, never stored; forward and backward each regenerate it.
+ *   Generator: Philox4x32-10 (Salmon et al., the Random123 definition): multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9,
+ *     0xBB67AE85, ten rounds, the key bumped after each round.  counter (0,0,0,0), key (0,0) gives 6627e8d5 e169c58d bc57ac4c 9b00dbd8.
+ *   Coordinates, for the output of absolute layer k at frame n = b T + t and column j in [0, hidden x directions):
+ *     counter = (n, (k << 16) | (j >> 2), draw_lo, draw_hi), key = (seed_lo, seed_hi); the element uses output word j & 3, so one call
+ *     serves four adjacent columns.
+ *   Decision: thr = (uint32) floor((double)p 2^32) (p = 0.5: 0x80000000; f32 0.3: 1288490240), scale = 1.0f / (1.0f - p) in IEEE f32;
+ *     the element is kept iff word >= thr; a kept value is fl(v scale), one f32 rounding; a dropped value is +0, chosen by a select, so
+ *     a NaN or -0 at a dropped position comes out +0.
+ *   Where: forward, the input of trainable layer k + 1 is the masked, scaled output of layer k for first_layer <= k < num_layers - 1;
+ *     backward, the dy of layer k is the masked, scaled d_in of layer k + 1 with the same mask.  d_y (the top layer's output) and
+ *     d_x_in are never dropped.  Frames past a length stay +0.
+ *   Draw ordinal: a 64-bit count at byte 56 of the state (zeroed by reset).  A forward call with thr > 0 takes draw = the count and
+ *     advances it by one, on the device, in a single thread of its first kernel, and records the call's values in the workspace header:
+ *     draw u64 at byte 16, thr u32 at byte 24, scale f32 at byte 28, seed u64 at byte 32.  A forward call with thr == 0 leaves the count
+ *     alone and writes only thr = 0 at byte 24.  thr, scale and seed are launch arguments of the forward call, so a captured graph holds
+ *     them, and every replay draws a fresh mask.  The backward call takes all four values from the workspace header only: a setting
+ *     changed to another p > 0 or seed between forward and backward does not break the pair, and micro-batches within one step get
+ *     different masks.  (The host enqueues the backward stage when the context's p is above 0 or its last forward call's was; switching
+ *     to p = 0 AND running a p = 0 forward call on another workspace in between is the one order that loses a pending backward's mask.)
+ *   uvad_lstm_train_set_dropout refuses with UVAD_E_ARG: NULL context; p not finite, < 0 or >= 1; UVAD_E_STATE: a context without a
+ *     model; no uvad_lstm_train_configure yet.  uvad_lstm_train_ws_bytes and _state_bytes do not depend on the setting.
+ * uvad_dropout_apply is the same mask function as a stand-alone call without a context: d_out [rows][cols] = keep ? d_x scale : +0, with
+ *   frame n = the row and k = layer; in place when d_out == d_x.  For input dropout on cached features, and to pin the mask bit for
+ *   bit.  UVAD_E_ARG: a NULL pointer; pointers not 16-byte aligned; cols not a multiple of 4 in [4, 2048]; rows outside [1, 2^24]; layer
+ *   outside [0, 65535]; p not finite, < 0 or >= 1. */
 typedef struct {
     float lr, beta1, beta2, eps;
     int segment;                             /* frames per gradient partial, 0 = default (2048) */
@@ -1247,6 +1279,8 @@ int uvad_lstm_train_backward(uvad_ctx *, const float *d_x_in, const float *d_dy,
 int uvad_lstm_train_apply(uvad_ctx *, void *d_state, size_t state_bytes, void *stream);
 int uvad_lstm_train_read(uvad_ctx *, const void *d_state, size_t state_bytes, int which, float *d_out, void *stream);
 int uvad_lstm_train_commit(uvad_ctx *, const void *d_state, size_t state_bytes);
+int uvad_lstm_train_set_dropout(uvad_ctx *, float p, uint64_t seed);
+int uvad_dropout_apply(const float *d_x, float *d_out, int64_t rows, int cols, int layer, uint64_t draw, float p, uint64_t seed, void *stream);
 
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;

@@ -1,12 +1,13 @@
 """Entry point with the reference's shape (main.py:12-55): ``main(load_config())`` dispatches on
-``config.task`` / ``config.function``.  The inference path, scoring against label files and fine-tuning of the head ("adapt") are in
-scope; every other task of the reference (corpus download / preparation, full training) raises with a pointer to SURVEY.md."""
+``config.task`` / ``config.function``.  The inference path, scoring against label files, fine-tuning ("adapt") and training a PyanNet2
+from initialisation ("train") are in scope; every other task of the reference (corpus download / preparation) raises with a pointer to
+SURVEY.md."""
 import faulthandler
 
 faulthandler.enable()
 
 from config.config import load_config  # noqa: E402
-from src.scripts import adapt_vad, predict_vad, test_vad    # noqa: E402
+from src.scripts import adapt_vad, predict_vad, test_vad, train_vad    # noqa: E402
 
 
 def main(config):
@@ -17,7 +18,9 @@ def main(config):
             return test_vad(**config)
         if config.function == "adapt":
             return adapt_vad(**config)
-        raise NotImplementedError(f"function={config.function!r}: only 'predict', 'test' and 'adapt' are on the accelerated path")
+        if config.function == "train":
+            return train_vad(**config)
+        raise NotImplementedError(f"function={config.function!r}: only 'predict', 'test', 'adapt' and 'train' are on the accelerated path")
     raise NotImplementedError(f"task={config.task!r}: data preparation tasks are out of scope (SURVEY.md section 2)")
 
 

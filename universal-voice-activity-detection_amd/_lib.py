@@ -232,6 +232,8 @@ SIGNATURES = {
     "uvad_lstm_train_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_lstm_train_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     "uvad_lstm_train_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "uvad_lstm_train_set_dropout": (C.c_int, [C.c_void_p, C.c_float, C.c_uint64]),
+    "uvad_dropout_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_uint64, C.c_float, C.c_uint64, C.c_void_p]),
     "uvad_cuts_max_per_row": (C.c_int, [C.POINTER(CutsCfg), C.c_int]),
     "uvad_cuts_max_samples": (C.c_int64, [C.POINTER(CutsCfg), C.c_int64]),
     "uvad_cuts_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),

@@ -21,7 +21,8 @@ def load_config() -> ConfigDict:
     cfg = ConfigDict()
 
     cfg.task = "run"            # only "run" is in scope (reference: wer/download/prepare/... are data plumbing)
-    cfg.function = "predict"    # "predict" | "test" (scoring against label files: input.labels) | "adapt" (head fine-tuning on them)
+    cfg.function = "predict"    # "predict" | "test" (scoring against label files: input.labels) | "adapt" (head fine-tuning on them) |
+                                # "train" (scripts.train_vad: every LSTM layer and the head learn from torch's initialisation)
 
     cfg.seed = 42
     cfg.device = "gpu"          # the HIP path needs a GPU; "cpu" raises (no fallback)
@@ -46,6 +47,7 @@ def load_config() -> ConfigDict:
     cfg.max_duration = 400      # seconds of audio per batch, as the reference's sampler
     # cut geometry of the reference's recipes (src/datasets/ami/utils.py:107,163): 5 s windows, tails of <= 3 s dropped, features
     # padded to the window; window_seconds = None runs whole recordings in one pass instead (not what the reference does)
+    # function == "train" cuts its cached features into rows of window_seconds too, every tail kept as a shorter row with its length
     cfg.window_seconds = 5.0
     cfg.min_window_seconds = 3.0
     # with window_seconds = None: recordings of different lengths share a batch (sorted by length, padded size within max_duration),

@@ -22,6 +22,12 @@
 //                         is how bias_ih and bias_hh receive the same bits
 //   ht_gemm_kernel<1>     d_in = dpre W_ih, the second direction added to the first: the next lower layer's dy, or d_grad_in
 //   ht_fold_kernel, ht_adam_kernel, ht_read_kernel   as the head's
+// Dropout between the trainable layers (uvad_lstm_train_set_dropout; the mask is defined in include/uvad.h) is a stage of its own:
+//   lt_dropout_kernel     out = keep ? x scale : +0, one thread per group of four columns of one frame: one Philox4x32-10 call, one 16-byte
+//                         load, one 16-byte store.  In place over h[li] after layer li's forward recurrence and over the gradient buffer
+//                         before layer li's backward recurrence, with draw / thr / scale / seed read from the workspace header, where
+//                         lt_prep_kernel recorded them when it took the draw ordinal from the state.  With the setting off the host
+//                         launches none of it and lt_prep_kernel writes only thr = 0 into that record.
 // No floating-point atomics: the same calls give the same bits.  Every backward kernel checks the workspace header on the device and does
 // nothing under a mismatch.  Contraction is off (ht_kernels.h and the Makefile's flag); the fused multiply-adds below are explicit.
 #include "ht_kernels.h"
@@ -29,6 +35,9 @@
 namespace uvad {
 
 static_assert(sizeof(LstmTrainWsHead) == 256, "workspace layout");
+static_assert(offsetof(HeadTrainHeader, draws) == 56, "the draw ordinal of include/uvad.h");
+static_assert(offsetof(LstmTrainWsHead, draw) == 16 && offsetof(LstmTrainWsHead, thr) == 24 && offsetof(LstmTrainWsHead, scale) == 28 &&
+              offsetof(LstmTrainWsHead, seed) == 32, "the dropout record of include/uvad.h");
 
 namespace {
 
@@ -68,8 +77,8 @@ struct LtRec {
 
 __device__ __forceinline__ int lt_len(const LtRec &a, int b) { return b < a.B ? ht_row_len(a.lens, b, a.T) : 0; }
 
-__global__ __launch_bounds__(256) void lt_prep_kernel(LstmTrainShape q, const void *state, const int *lens, int B, int T, uint8_t *valid, float *bsum,
-                                                      LstmTrainWsHead *head) {
+__global__ __launch_bounds__(256) void lt_prep_kernel(LstmTrainShape q, void *state, const int *lens, int B, int T, uint8_t *valid, float *bsum,
+                                                      LstmTrainWsHead *head, unsigned thr, float scale, unsigned long long seed) {
     if (!ht_state_ok(state, LT_MAGIC, q.P)) return;
     const float *master = reinterpret_cast<const float *>(reinterpret_cast<const HeadTrainHeader *>(state) + 1);
     const int N = B * T, G = 4 * q.H;
@@ -82,7 +91,61 @@ __global__ __launch_bounds__(256) void lt_prep_kernel(LstmTrainShape q, const vo
         const int ld = j / G, r = j - ld * G, li = ld / q.dirs, d = ld - li * q.dirs;
         bsum[j] = master[q.off[li][d][2] + r] + master[q.off[li][d][3] + r];
     }
-    if (gtid == 0) { head->magic = LT_WS_MAGIC; head->B = B; head->T = T; }
+    if (gtid == 0) {
+        head->magic = LT_WS_MAGIC; head->B = B; head->T = T;
+        head->thr = thr;                                 // 0: this forward call drops nothing, whatever an earlier one left here
+        if (thr > 0) {                                   // take the draw ordinal and advance it: the one writer of the count
+            HeadTrainHeader *hd = reinterpret_cast<HeadTrainHeader *>(state);
+            const unsigned long long draw = hd->draws;
+            hd->draws = draw + 1;
+            head->draw = draw; head->scale = scale; head->seed = seed;
+        }
+    }
+}
+
+// Philox4x32-10 (Salmon et al., Random123): ten rounds, the key bumped after each round
+__device__ __forceinline__ uint4 lt_philox(uint4 c, unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
+        c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return c;
+}
+
+// head != nullptr: the record of the workspace header (thr == 0 there: nothing to do), under the state's magic and the guard;
+// head == nullptr: the stand-alone call, everything in the arguments
+struct LtDrop {
+    const float *x; float *out; long long groups; int cq, layer;   // groups = rows x cq, cq = cols / 4
+    const LstmTrainWsHead *head; const void *state; int P; HtGuard guard;
+    unsigned long long draw, seed; unsigned thr; float scale;
+};
+
+__global__ __launch_bounds__(256) void lt_dropout_kernel(LtDrop a) {
+    unsigned long long draw = a.draw, seed = a.seed;
+    unsigned thr = a.thr;
+    float scale = a.scale;
+    if (a.head) {
+        if (!ht_state_ok(a.state, LT_MAGIC, a.P) || !ht_guard_ok(a.guard)) return;
+        thr = a.head->thr;
+        if (thr == 0) return;
+        draw = a.head->draw; scale = a.head->scale; seed = a.head->seed;
+    }
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= a.groups) return;
+    const long long n = g / a.cq;
+    const unsigned jq = (unsigned)(g - n * a.cq);
+    const uint4 r = lt_philox(make_uint4((unsigned)n, ((unsigned)a.layer << 16) | jq, (unsigned)draw, (unsigned)(draw >> 32)), (unsigned)seed,
+                              (unsigned)(seed >> 32));
+    const float4 v = reinterpret_cast<const float4 *>(a.x)[g];
+    float4 o;   // selects, not products: a NaN or -0 at a dropped position comes out +0
+    o.x = r.x >= thr ? v.x * scale : 0.0f;
+    o.y = r.y >= thr ? v.y * scale : 0.0f;
+    o.z = r.z >= thr ? v.z * scale : 0.0f;
+    o.w = r.w >= thr ? v.w * scale : 0.0f;
+    reinterpret_cast<float4 *>(a.out)[g] = o;
 }
 
 template <int H>
@@ -324,6 +387,14 @@ bool lt_args_ok(const LstmTrainShape &q, const LstmTrainArgs &a) {
     return a.x && a.state && a.ws && a.B > 0 && a.T > 0 && (long long)a.B * a.T <= HT_MAX_FRAMES && a.seg >= HT_MIN_SEGMENT &&
            a.seg <= HT_MAX_SEGMENT && a.seg % 32 == 0 && (q.H == 64 || q.H == 128) && q.nl >= 1 && q.nl <= LT_MAX_LAYERS;
 }
+// the in-place stage over the output of trainable layer li, or over the gradient with respect to it: a buffer [N][H dirs]
+hipError_t lt_launch_drop(const LstmTrainShape &q, const LstmTrainArgs &a, const LtBufs &b, float *buf, int li, const HtGuard &guard, hipStream_t s) {
+    LtDrop d{};
+    d.x = buf; d.out = buf; d.cq = q.H * q.dirs / 4; d.groups = (long long)a.B * a.T * d.cq; d.layer = q.first_layer + li;
+    d.head = b.head; d.state = a.state; d.P = q.P; d.guard = guard;
+    hipLaunchKernelGGL(lt_dropout_kernel, dim3((unsigned)((d.groups + 255) / 256)), dim3(256), 0, s, d);
+    return hipGetLastError();
+}
 unsigned lt_tiles(int M, int Nc) { return (unsigned)(((M + HT_TM - 1) / HT_TM) * ((Nc + HT_TN - 1) / HT_TN)); }
 
 template <typename K>
@@ -395,7 +466,8 @@ hipError_t launch_lstm_train_forward(const LstmTrainShape &q, const LstmTrainArg
     {
         const int work = N > q.nl * D * 4 * H ? N : q.nl * D * 4 * H;
         const unsigned blocks = (unsigned)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096);
-        hipLaunchKernelGGL(lt_prep_kernel, dim3(blocks), dim3(256), 0, s, q, a.state, a.lens, a.B, a.T, b.valid, b.bsum, b.head);
+        hipLaunchKernelGGL(lt_prep_kernel, dim3(blocks), dim3(256), 0, s, q, a.state, a.lens, a.B, a.T, b.valid, b.bsum, b.head, a.thr, a.scale,
+                           a.seed);
         LT_LAUNCHED();
     }
     for (int li = 0; li < q.nl; ++li) {
@@ -418,6 +490,10 @@ hipError_t launch_lstm_train_forward(const LstmTrainShape &q, const LstmTrainArg
         r.lens = a.lens; r.B = a.B; r.T = a.T;
         e = lt_launch_rec(lt_fwd_kernel<64>, lt_fwd_kernel<128>, H, a.B, D, r, s);
         if (e != hipSuccess) return e;
+        if (a.thr > 0 && li + 1 < q.nl) {   // the next layer's projection and its dW_ih both take the dropped value; h_prev is kept apart
+            e = lt_launch_drop(q, a, b, b.h[li], li, HtGuard{}, s);
+            if (e != hipSuccess) return e;
+        }
     }
     return hipSuccess;
 }
@@ -438,6 +514,10 @@ hipError_t launch_lstm_train_backward(const LstmTrainShape &q, const LstmTrainAr
         r.gates = b.gates[li]; r.c = b.c[li]; r.hprev = b.hprev[li];
         r.dy = li + 1 == q.nl ? a.dy : b.dbuf[li & 1]; r.ldy = H * D;
         r.lens = a.lens; r.B = a.B; r.T = a.T; r.guard = guard;
+        if (a.drop && li + 1 < q.nl) {   // dy of layer li = the masked, scaled d_in of layer li + 1: the forward call's mask, from the header
+            e = lt_launch_drop(q, a, b, b.dbuf[li & 1], li, guard, s);
+            if (e != hipSuccess) return e;
+        }
         e = lt_launch_rec(lt_bwd_kernel<64>, lt_bwd_kernel<128>, H, a.B, D, r, s);
         if (e != hipSuccess) return e;
         float *d_in = li > 0 ? b.dbuf[(li - 1) & 1] : a.grad_in;
@@ -469,6 +549,19 @@ hipError_t launch_lstm_train_backward(const LstmTrainShape &q, const LstmTrainAr
     return hipSuccess;
 }
 #undef LT_LAUNCHED
+
+unsigned lstm_dropout_threshold(float p) { return (unsigned)__builtin_floor((double)p * 4294967296.0); }
+
+hipError_t launch_dropout_apply(const float *x, float *out, long long rows, int cols, int layer, unsigned long long draw, unsigned thr, float scale,
+                                unsigned long long seed, hipStream_t s) {
+    if (!x || !out || rows < 1 || rows > HT_MAX_FRAMES || cols < 4 || cols % 4 || cols > LT_DROP_MAX_COLS || layer < 0 || layer > LT_DROP_MAX_LAYER)
+        return hipErrorInvalidValue;
+    LtDrop d{};
+    d.x = x; d.out = out; d.cq = cols / 4; d.groups = rows * d.cq; d.layer = layer;
+    d.draw = draw; d.seed = seed; d.thr = thr; d.scale = scale;
+    hipLaunchKernelGGL(lt_dropout_kernel, dim3((unsigned)((d.groups + 255) / 256)), dim3(256), 0, s, d);
+    return hipGetLastError();
+}
 
 hipError_t launch_lstm_train_apply(const LstmTrainShape &q, const HeadTrainAdam &o, void *state, hipStream_t s) {
     if (!state) return hipErrorInvalidValue;

@@ -129,6 +129,8 @@ struct uvad_ctx {
     bool has_lt = false;                        // uvad_lstm_train_configure: the optimiser, first_layer and the packed shape of the trainable layers
     uvad_lstm_train_cfg lq{};
     LstmTrainShape lts{};
+    unsigned lt_thr = 0; float lt_scale = 1.0f; uint64_t lt_seed = 0;   // uvad_lstm_train_set_dropout: what the forward call launches with (thr == 0: off)
+    bool lt_dropped = false;                    // the last forward call of this context ran with thr > 0
     int device = 0, n_cu = 256;
     bool has_fb = false, has_model = false, finalized = false, tables_set = false;
     uvad_fbank_cfg fb{};
@@ -3361,6 +3363,26 @@ int uvad_lstm_train_configure(uvad_ctx *c, const uvad_lstm_train_cfg *q) {
     return UVAD_OK;
 }
 
+int uvad_lstm_train_set_dropout(uvad_ctx *c, float p, uint64_t seed) {
+    if (!c) return UVAD_E_ARG;
+    if (!std::isfinite(p) || p < 0.0f || !(p < 1.0f)) return fail(c, UVAD_E_ARG, "uvad_lstm_train_set_dropout: p must lie in [0, 1)");
+    if (!c->has_model) return fail(c, UVAD_E_STATE, "uvad_lstm_train_set_dropout: context was created without a model configuration");
+    if (!c->has_lt) return fail(c, UVAD_E_STATE, "uvad_lstm_train_set_dropout: call uvad_lstm_train_configure first");
+    c->lt_thr = lstm_dropout_threshold(p);
+    c->lt_scale = 1.0f / (1.0f - p);
+    c->lt_seed = seed;
+    return UVAD_OK;
+}
+
+int uvad_dropout_apply(const float *d_x, float *d_out, int64_t rows, int cols, int layer, uint64_t draw, float p, uint64_t seed, void *stream) {
+    if (!d_x || !d_out || rows < 1 || rows > HT_MAX_FRAMES || cols < 4 || cols % 4 || cols > LT_DROP_MAX_COLS || layer < 0 ||
+        layer > LT_DROP_MAX_LAYER || !std::isfinite(p) || p < 0.0f || !(p < 1.0f) || reinterpret_cast<uintptr_t>(d_x) % 16 ||
+        reinterpret_cast<uintptr_t>(d_out) % 16)
+        return UVAD_E_ARG;
+    return launch_dropout_apply(d_x, d_out, rows, cols, layer, draw, lstm_dropout_threshold(p), 1.0f / (1.0f - p), seed, (hipStream_t)stream) ==
+                   hipSuccess ? UVAD_OK : UVAD_E_HIP;
+}
+
 int64_t uvad_lstm_train_param_count(const uvad_ctx *c) { return c && c->has_lt ? (int64_t)c->lts.P : 0; }
 size_t uvad_lstm_train_state_bytes(const uvad_ctx *c) { return c && c->has_lt ? lstm_train_state_bytes(c->lts) : 0; }
 
@@ -3433,6 +3455,8 @@ int uvad_lstm_train_forward(uvad_ctx *c, const float *d_x_in, int B, int T, cons
     if (int r = lstm_train_call_check(c, "uvad_lstm_train_forward", d_x_in, d_y, B, T, d_state, state_bytes, d_ws, ws_bytes)) return r;
     LstmTrainArgs a{};
     a.x = d_x_in; a.B = B; a.T = T; a.lens = d_lens; a.y = d_y; a.state = d_state; a.ws = d_ws; a.seg = c->lq.segment;
+    a.thr = c->lt_thr; a.scale = c->lt_scale; a.seed = c->lt_seed;
+    c->lt_dropped = a.thr > 0;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, launch_lstm_train_forward(c->lts, a, (hipStream_t)stream));
     return UVAD_OK;
@@ -3444,6 +3468,7 @@ int uvad_lstm_train_backward(uvad_ctx *c, const float *d_x_in, const float *d_dy
     if (int r = lstm_train_call_check(c, "uvad_lstm_train_backward", d_x_in, d_dy, B, T, d_state, state_bytes, d_ws, ws_bytes)) return r;
     LstmTrainArgs a{};
     a.x = d_x_in; a.dy = d_dy; a.B = B; a.T = T; a.lens = d_lens; a.grad_in = d_grad_in; a.state = d_state; a.ws = d_ws; a.seg = c->lq.segment;
+    a.drop = c->lt_thr > 0 || c->lt_dropped;   // the masks themselves come from the workspace header; off and never on: today's launches
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, launch_lstm_train_backward(c->lts, a, (hipStream_t)stream));
     return UVAD_OK;

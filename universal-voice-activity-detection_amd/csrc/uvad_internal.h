@@ -782,7 +782,8 @@ struct HeadTrainHeader {
     // every step, and the value keeps f32 relative accuracy.  (The running PRODUCT beta^t of the f32 nearest to 0.999 is 1.3e-8 off per
     // factor, which 1 - beta^t magnifies to 1.3e-5 at every t: the loss of a 20-step run then drifts 1e-3 from torch's, not 1e-6.)
     float bc1, bc2;
-    int reserved[50];
+    unsigned long long draws;                        // byte 56, LSTM training states only: dropout masks drawn so far (the draw ordinal)
+    int reserved[48];
 };                                                   // 256 bytes
 struct HeadTrainWsHead { double loss; unsigned long long frames; int reserved[60]; };   // of the last uvad_head_train_grad
 struct HeadTrainWs { size_t off_valid, off_dz, off_act, off_d[2], off_part, off_loss, total; int N, nseg; };
@@ -820,7 +821,13 @@ struct LstmTrainShape {
     int in[LT_MAX_LAYERS];                           // input width of layer li
     int off[LT_MAX_LAYERS][2][4];                    // weight_ih, weight_hh, bias_ih, bias_hh of (li, direction)
 };
-struct LstmTrainWsHead { int magic, B, T; int reserved[61]; };   // written by the forward call, checked by every backward kernel
+// written by the forward call, checked by every backward kernel.  draw .. seed (bytes 16 .. 39) are the dropout record of that forward
+// call: the backward call's masks come from here alone; thr == 0 means that forward call dropped nothing.
+struct LstmTrainWsHead {
+    int magic, B, T, pad0;
+    unsigned long long draw; unsigned thr; float scale; unsigned long long seed;
+    int reserved[54];
+};
 struct LstmTrainWs {
     size_t off_fold, off_valid, off_bsum, off_gates[LT_MAX_LAYERS], off_c[LT_MAX_LAYERS], off_hprev[LT_MAX_LAYERS], off_h[LT_MAX_LAYERS], off_d[2],
         off_part, total;
@@ -830,6 +837,8 @@ struct LstmTrainArgs {
     const float *x; const float *dy; int B, T; const int *lens;
     float *y; float *grad_in;
     void *state; void *ws; int seg;
+    unsigned thr; float scale; unsigned long long seed;   // forward: the dropout setting (thr == 0: off, today's launches)
+    bool drop;                                       // backward: launch the dropout stage (it reads the workspace header's record)
 };
 LstmTrainShape lstm_train_shape(int Din, int H, int dirs, int num_layers, int first_layer);
 size_t lstm_train_state_bytes(const LstmTrainShape &q);
@@ -839,5 +848,10 @@ hipError_t launch_lstm_train_forward(const LstmTrainShape &q, const LstmTrainArg
 hipError_t launch_lstm_train_backward(const LstmTrainShape &q, const LstmTrainArgs &a, hipStream_t s);
 hipError_t launch_lstm_train_apply(const LstmTrainShape &q, const HeadTrainAdam &o, void *state, hipStream_t s);
 hipError_t launch_lstm_train_read(const LstmTrainShape &q, const void *state, int which, float *out, hipStream_t s);
+// the dropout mask of include/uvad.h as a stand-alone pass: out = keep ? x scale : +0 over [rows][cols]; in place when out == x
+constexpr int LT_DROP_MAX_COLS = 2048, LT_DROP_MAX_LAYER = 65535;
+unsigned lstm_dropout_threshold(float p);            // floor((double)p 2^32)
+hipError_t launch_dropout_apply(const float *x, float *out, long long rows, int cols, int layer, unsigned long long draw, unsigned thr, float scale,
+                                unsigned long long seed, hipStream_t s);
 
 }  // namespace uvad

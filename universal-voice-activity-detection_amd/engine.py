@@ -4,8 +4,10 @@ inference and scoring surface: constructor arguments, ``.model`` / ``.model_name
 keep their names, argument meaning and return shapes; what the reference logs through torchmetrics
 is accumulated on the device (``uvad_score_*``) and read with ``test_metrics`` / ``validation_metrics``.
 ``adapt_head_step`` / ``adapt_head_commit`` fine-tune the head on the device (``uvad_head_train_*``); ``adapt_step`` /
-``adapt_commit`` let the top LSTM layers learn with it (``uvad_lstm_train_*``).  ``training_step`` and ``configure_optimizers``
-themselves (gradients into a SincNet front end, dropout, DDP) are outside the accelerated path and raise."""
+``adapt_commit`` let the top LSTM layers learn with it (``uvad_lstm_train_*``); ``train_step`` / ``train_commit`` are the reference's
+training step for a PyanNet2: every LSTM layer and the head learn, with nn.LSTM's dropout between the layers drawn on the device.
+``training_step`` and ``configure_optimizers`` themselves (Lightning's hooks; gradients into a SincNet front end, DDP) are outside the
+accelerated path and raise."""
 import torch
 import torch.nn as nn
 
@@ -171,20 +173,27 @@ class VadModel(nn.Module):
             x = rt.sincnet(x[:, 0, :] if x.dim() == 3 else x)
         return rt.lstm_train_input(x, lengths=batch.get("lengths"), layers=lstm_layers)
 
-    def adapt_step(self, batch, batch_idx=0, accumulate: int = 1, lstm_layers: int = 1):
+    def adapt_step(self, batch, batch_idx=0, accumulate: int = 1, lstm_layers: int = 1, dropout=None, seed: int = 0):
         """One micro-batch in which the head and the top `lstm_layers` LSTM layers learn: batch["lstm_in"] (the cached frozen prefix) or
         batch["inputs"] through it, the learning layers' forward pass with kept activations, the head's loss and backward pass as
         adapt_head_step's, backpropagation through time from its input gradient; every `accumulate` calls one Adam step on both
-        states (lr = self.learning_rate).  Returns the batch's mean loss as a 0-d tensor on the device without synchronising."""
+        states (lr = self.learning_rate).  dropout: nn.LSTM's dropout between the learning layers, a fresh mask per call (None: none,
+        the frozen prefix never has any); seed: the masks' seed.  Returns the batch's mean loss as a 0-d tensor on the device without
+        synchronising."""
         y = batch.get("is_voice")
         if y is None:
             raise ValueError('adapt_step needs batch["is_voice"]')
+        dropout = 0.0 if dropout is None else float(dropout)
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError("dropout must lie in [0, 1)")
         x = batch["lstm_in"] if batch.get("lstm_in") is not None else self.lstm_in(batch, lstm_layers)
         rt = self.model.runtime(x.device)
         held = getattr(self, "_adapt_full", None)
         if held is None or held[0] is not rt or held[2]["layers"] != int(lstm_layers):
-            held = self._adapt_full = [rt, rt.head_train_open(lr=self.learning_rate), rt.lstm_train_open(layers=lstm_layers, lr=self.learning_rate), 0]
+            held = self._adapt_full = [rt, rt.head_train_open(lr=self.learning_rate),
+                                       rt.lstm_train_open(layers=lstm_layers, lr=self.learning_rate, dropout=dropout, seed=seed), 0]
         hh, hl = held[1], held[2]
+        hl["dropout"], hl["seed"] = dropout, int(seed) & 0xFFFFFFFFFFFFFFFF      # the handle re-asserts them before every call
         lengths = batch.get("lengths")
         gt = (y.to(x.device) != 0).to(torch.uint8).reshape(x.shape[:2])
         out = rt.lstm_train_forward(hl, x, lengths=lengths)
@@ -214,7 +223,20 @@ class VadModel(nn.Module):
                 params[key].copy_(t.to(params[key].device))
         self.model._rt_stamp = self.model._stamp(rt.device)   # the runtime already holds these very tensors: no second upload
 
-    # -- full training is out of scope -----------------------------------------------------------
+    # -- training from initialisation: every LSTM layer and the head learn (PyanNet2) -----------------------------------------------
+    def train_step(self, batch, batch_idx=0, accumulate: int = 1):
+        """The reference's training_step for a PyanNet2 on the device: adapt_step with every LSTM layer learning, the model's configured
+        dropout between the layers (self.model.train_dropout) and the masks seeded from torch.initial_seed()."""
+        if self.model_name == "PyanNet":
+            raise NotImplementedError("train_step needs the gradients into the SincNet front end, which are not on the device: PyanNet2 only")
+        return self.adapt_step(batch, batch_idx, accumulate=accumulate, lstm_layers=self.model.hparams.lstm["num_layers"],
+                               dropout=self.model.train_dropout, seed=torch.initial_seed())
+
+    def train_commit(self):
+        """adapt_commit: serve the trained tensors and write them into self.model's parameters."""
+        self.adapt_commit()
+
+    # -- Lightning's own hooks stay outside the accelerated path -----------------------------------
     def training_step(self, *a, **k):
         raise NotImplementedError("training is outside the accelerated inference path (SURVEY.md section 2, rows 6/12)")
 

@@ -42,6 +42,8 @@ class PyanNet2(nn.Module):
         self.hparams = HParams(lstm=lstm_hp, linear=linear_hp)
         self.encoding_dim = encoding_dim
         self.sample_rate, self.num_channels = sample_rate, num_channels
+        # the configured inter-layer dropout: what VadModel.train_step hands to uvad_lstm_train_set_dropout (inference never applies it)
+        self.train_dropout = float(lstm_hp["dropout"])
 
         width = lstm_hp["hidden_size"] * (2 if lstm_hp["bidirectional"] else 1)
         kw = {k: v for k, v in lstm_hp.items() if k != "monolithic"}

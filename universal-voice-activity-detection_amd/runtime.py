@@ -1423,18 +1423,25 @@ class VadRuntime:
                         (f"lstm.bias_hh{suf}", (4 * H,))]
         return out
 
-    def lstm_train_open(self, layers: int = 1, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, segment: int = 0):
+    def lstm_train_open(self, layers: int = 1, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, segment: int = 0,
+                        dropout: float = 0.0, seed: int = 0):
         """Allocate and reset a training state for the top `layers` layers of the LSTM stack (uvad_lstm_train_reset): f32 master copies of
         their tensors as loaded, Adam moments, the gradient accumulator; first_layer = num_layers - layers, the layers below stay frozen.
-        The handle owns the state and the workspace."""
+        dropout, seed: nn.LSTM's dropout between the learning layers (uvad_lstm_train_set_dropout; 0 = none, the kernels of a run without
+        it).  The handle owns the state and the workspace."""
+        dropout = float(dropout)
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError("dropout must lie in [0, 1)")
         layers = int(layers)
         if not 1 <= layers <= self._mc_c.num_layers:
             raise ValueError(f"layers must lie in 1 .. {self._mc_c.num_layers}")
         cfg = _lib.LstmTrainCfg(float(lr), float(betas[0]), float(betas[1]), float(eps), int(segment), self._mc_c.num_layers - layers)
         with torch.cuda.device(self.device):
             self._check(self.lib.uvad_lstm_train_configure(self.ctx, C.byref(cfg)))
+            self._check(self.lib.uvad_lstm_train_set_dropout(self.ctx, dropout, int(seed) & 0xFFFFFFFFFFFFFFFF))
             P = int(self.lib.uvad_lstm_train_param_count(self.ctx))
             h = {"cfg": cfg, "P": P, "layers": layers, "first_layer": cfg.first_layer, "ws": None, "bt": None,
+                 "dropout": dropout, "seed": int(seed) & 0xFFFFFFFFFFFFFFFF,
                  "state": torch.empty(int(self.lib.uvad_lstm_train_state_bytes(self.ctx)), dtype=torch.uint8, device=self.device),
                  "out": torch.zeros(max(P, _lib.HEAD_TRAIN_SCALAR_WORDS), dtype=torch.float32, device=self.device)}
             self._check(self.lib.uvad_lstm_train_reset(self.ctx, h["state"].data_ptr(), h["state"].numel(), self._stream()))
@@ -1460,8 +1467,31 @@ class VadRuntime:
         sib.classify(x, want_logits=True, want_probs=False, lengths=lengths)
         return sib.taps(lin=False)[0]
 
+    def _lstm_train_configure(self, h):
+        """The handle's configuration and dropout setting on the context (host only: the context serves any number of handles)."""
+        self._check(self.lib.uvad_lstm_train_configure(self.ctx, C.byref(h["cfg"])))
+        self._check(self.lib.uvad_lstm_train_set_dropout(self.ctx, h.get("dropout", 0.0), h.get("seed", 0)))
+
+    def lstm_train_draws(self, h) -> int:
+        """How many dropout masks the handle's forward calls have drawn: the 64-bit count at byte 56 of the state (synchronises)."""
+        return int(h["state"][56:64].cpu().numpy().view(np.uint64)[0])
+
+    def dropout_apply(self, x: "torch.Tensor", layer: int, draw: int, p: float, seed: int, out=None) -> "torch.Tensor":
+        """The mask of uvad_lstm_train_set_dropout as a stand-alone pass (uvad_dropout_apply): x (..., cols) f32 on the GPU, rows = every
+        leading dimension flattened (the mask's frame index), cols a multiple of 4 up to 2048 -> keep ? x / (1 - p) : +0.  out: a tensor of
+        x's shape to write (x itself: in place); None allocates one.  For input dropout on cached features."""
+        with torch.cuda.device(self.device):
+            x = self._dev_f32(x, "x")
+            if out is None:
+                out = torch.empty_like(x)
+            if not (torch.is_tensor(out) and out.device == x.device and out.dtype == torch.float32 and out.shape == x.shape and out.is_contiguous()):
+                raise ValueError("out must be a contiguous f32 tensor of x's shape on x's device")
+            self._check(self.lib.uvad_dropout_apply(x.data_ptr(), out.data_ptr(), x.numel() // x.shape[-1], x.shape[-1], int(layer),
+                                                    int(draw) & 0xFFFFFFFFFFFFFFFF, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, self._stream()))
+            return out
+
     def _lstm_train_ws(self, h, B: int, T: int):
-        self._check(self.lib.uvad_lstm_train_configure(self.ctx, C.byref(h["cfg"])))   # host only: the context serves any number of handles
+        self._lstm_train_configure(h)
         need = int(self.lib.uvad_lstm_train_ws_bytes(self.ctx, B, T))
         if h["ws"] is None or h["ws"].numel() < need:
             h["ws"] = torch.zeros(need, dtype=torch.uint8, device=self.device)
@@ -1505,7 +1535,7 @@ class VadRuntime:
     def lstm_train_apply(self, h):
         """One Adam step from the accumulated gradients divided by the accumulated frame count (uvad_lstm_train_apply)."""
         with torch.cuda.device(self.device):
-            self._check(self.lib.uvad_lstm_train_configure(self.ctx, C.byref(h["cfg"])))
+            self._lstm_train_configure(h)
             self._check(self.lib.uvad_lstm_train_apply(self.ctx, h["state"].data_ptr(), h["state"].numel(), self._stream()))
 
     def _lstm_train_block(self, h, which: int) -> np.ndarray:
@@ -1516,7 +1546,7 @@ class VadRuntime:
         """Copy the state to the host (synchronises) -> {"weights", "grad", "m", "v": {torch key: tensor}, "frames", "step",
         "bias_correction1", "bias_correction2" (1 - beta^step)}."""
         with torch.cuda.device(self.device):
-            self._check(self.lib.uvad_lstm_train_configure(self.ctx, C.byref(h["cfg"])))
+            self._lstm_train_configure(h)
             out = {}
             for name, which in (("weights", _lib.HEAD_TRAIN_MASTERS), ("grad", _lib.HEAD_TRAIN_GRAD), ("m", _lib.HEAD_TRAIN_M), ("v", _lib.HEAD_TRAIN_V)):
                 flat, off, d = self._lstm_train_block(h, which), 0, {}
@@ -1539,7 +1569,7 @@ class VadRuntime:
         """Make this runtime serve the adapted layers (uvad_lstm_train_commit: synchronises, re-finalizes).  Graphs captured before are
         stale, as after load_state_dict; the frozen prefix's sibling context is untouched."""
         with torch.cuda.device(self.device):
-            self._check(self.lib.uvad_lstm_train_configure(self.ctx, C.byref(h["cfg"])))
+            self._lstm_train_configure(h)
             self._check(self.lib.uvad_lstm_train_commit(self.ctx, h["state"].data_ptr(), h["state"].numel()))
             self._weights_gen = getattr(self, "_weights_gen", 0) + 1
 

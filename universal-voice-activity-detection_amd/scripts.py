@@ -862,3 +862,96 @@ def adapt_vad(**kwargs):
     torch.save({"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "epoch": epochs, "global_step": step // accumulate}, path)
     out["checkpoint_path"] = path
     return out
+
+
+def train_vad(**kwargs):
+    """Training from initialisation on wav files and label files in adapt_vad's ``input`` format (``function == "train"``): the
+    accelerated form of the reference's src/scripts/train.py for ``feature_extractor = "fbank"``.  The PyanNet2 is built under
+    ``torch.manual_seed(seed)`` -- torch's own initialisation, not seed_weights -- or loaded from ``checkpoint_path`` when
+    ``load_checkpoint`` is set.  The log-mel features of every recording are computed once and cached, cut into windows of
+    ``window_seconds`` (default 5.0; every tail is kept as a shorter row with its length), and batched up to ``max_duration`` seconds per
+    batch; the window order is shuffled each epoch by a ``torch.Generator`` seeded with ``seed + epoch``.  Every batch is one
+    VadModel.train_step: all LSTM layers and the head learn, with the dropout of ``model_dict["lstm"]["dropout"]`` (the reference's 0.5
+    by default) between the LSTM layers, ``accumulate_grad_batches`` calls per Adam step, lr = ``learning_rate``.  Every
+    ``check_val_every_n_epoch`` epochs (and after the last) the tensors are committed and validation_step runs on the held-out
+    recordings (``input.val_paths``; the training files without them).  Saves a Lightning-style checkpoint {"state_dict" (``model.``
+    keys), "epoch", "global_step"} to experiments_dir/checkpoint-epoch=NN.ckpt and returns {"train_loss": [per epoch], "val_loss":
+    [(epoch, loss)], "val_metrics", "checkpoint_path", "global_step"}."""
+    from .postprocess import read_label_file, supervision_frames
+    src = kwargs["input"]
+    if src.get("kind") != "wav" or not src.get("paths") or len(src.get("labels", ())) != len(src["paths"]):
+        raise ValueError('train_vad needs input = {"kind": "wav", "paths": [...], "labels": [one label file per path]}')
+    val_paths, val_labels = list(src.get("val_paths") or src["paths"]), list(src.get("val_labels") or src["labels"])
+    if len(val_paths) != len(val_labels):
+        raise ValueError("train_vad needs one label file per held-out path")
+    if kwargs["feature_extractor"] != "fbank" or kwargs["model_name"] != "PyanNet2":
+        raise NotImplementedError("train_vad trains a PyanNet2 on log-mel features (feature_extractor = 'fbank'): the gradients into the "
+                                  "SincNet front end are not on the device")
+    seed, sr = int(kwargs["seed"]), 16000
+    torch.manual_seed(seed)
+    device = _resolve_device(kwargs["device"])
+    lr = float(kwargs.get("learning_rate", 1e-3))
+    if kwargs["load_checkpoint"]:
+        model = VadModel.load_from_checkpoint(checkpoint_path=kwargs["checkpoint_path"], model_name="PyanNet2", model_dict=dict(kwargs["model_dict"]),
+                                              learning_rate=lr)
+    else:
+        model = VadModel(model_name="PyanNet2", model_dict=dict(kwargs["model_dict"]), learning_rate=lr)
+    model = model.to(device).eval()      # the torch modules serve inference only; training runs in uvad_lstm_train_* / uvad_head_train_*
+    net = model.model
+    net.attach_fbank(FbankConfig(sampling_rate=sr, num_filters=net.encoding_dim, window_type=kwargs.get("window_type", "povey"),
+                                 frame_shift=kwargs["frame_shift"], device="cuda"))
+    rt = net.runtime(device)
+
+    def recording(path, label_path):
+        pcm = torch.from_numpy(_wav_recordings(path, "first", rt, sr)[0]["pcm"]).to(device)[None]
+        feats = rt.fbank(pcm).clone()                                 # (1, T, F) log-mel, cached across the epochs
+        T = feats.shape[1]
+        table = supervision_frames(read_label_file(label_path), pcm.shape[1] / float(sr), frame_shift=kwargs["frame_shift"], geometry="fbank",
+                                   num_frames=T)
+        iv = np.zeros((1, max(len(table), 1), 2), np.int32)
+        iv[0, :len(table)] = table
+        return {"inputs": feats, "is_voice": rt.intervals_to_labels(iv, [len(table)], T).clone()}
+
+    train = [recording(p, l) for p, l in zip(src["paths"], src["labels"])]
+    held = train if (val_paths, val_labels) == (list(src["paths"]), list(src["labels"])) else [recording(p, l) for p, l in zip(val_paths, val_labels)]
+    window_s = float(kwargs.get("window_seconds") or 5.0)
+    W = max(1, int(round(window_s / kwargs["frame_shift"])))
+    windows = [(r, s, min(W, b["inputs"].shape[1] - s)) for r, b in enumerate(train) for s in range(0, b["inputs"].shape[1], W)]
+    rows = max(1, int(float(kwargs["max_duration"]) / window_s))
+    epochs, every = int(kwargs.get("max_epochs", 10)), max(1, int(kwargs.get("check_val_every_n_epoch", 1)))
+    accumulate = max(1, int(kwargs.get("accumulate_grad_batches", 1)))
+    out = {"train_loss": [], "val_loss": [], "val_metrics": None}
+
+    def batch_of(picks):
+        """Rows of W frames, zero past each row's length (never read)."""
+        x = torch.zeros((len(picks), W, net.encoding_dim), dtype=torch.float32, device=device)
+        y = torch.zeros((len(picks), W), dtype=torch.uint8, device=device)
+        for i, (r, s, n) in enumerate(picks):
+            x[i, :n], y[i, :n] = train[r]["inputs"][0, s:s + n], train[r]["is_voice"][0, s:s + n]
+        return {"inputs": x, "is_voice": y, "lengths": [n for _, _, n in picks]}
+
+    def validate(epoch):
+        model.train_commit()                                          # validation_step runs the context's tensors: serve the trained ones
+        for i, b in enumerate(held):
+            model.validation_step(b, i)
+        out["val_metrics"] = model.validation_metrics(reset=True)
+        out["val_loss"].append((epoch, out["val_metrics"]["val_loss"]))
+        print(f"epoch {epoch}: val_loss {out['val_metrics']['val_loss']:.6f}")
+
+    step = 0
+    for epoch in range(1, epochs + 1):
+        order = torch.randperm(len(windows), generator=torch.Generator().manual_seed(seed + epoch)).tolist()
+        losses = []
+        for i in range(0, len(order), rows):
+            losses.append(model.train_step(batch_of([windows[k] for k in order[i:i + rows]]), step, accumulate=accumulate))
+            step += 1
+        out["train_loss"].append(float(torch.stack(losses).mean()))
+        print(f"epoch {epoch}: train_loss {out['train_loss'][-1]:.6f}")
+        if epoch % every == 0 or epoch == epochs:
+            validate(epoch)
+    path = os.path.join(kwargs.get("experiments_dir", "."), f"checkpoint-epoch={epochs:02d}.ckpt")
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    out["global_step"] = step // accumulate
+    torch.save({"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "epoch": epochs, "global_step": out["global_step"]}, path)
+    out["checkpoint_path"] = path
+    return out
