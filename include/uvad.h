@@ -1127,7 +1127,7 @@ int uvad_gate_group_step(uvad_ctx *, const void *d_chunk, int chunk, int B, cons
  * slice of the model, VadModel.training_step / _common_step (src/engines/vad_engine.py:247-278: the head expression of
  * PyanNet2.forward, F.leaky_relu(linear(x)) and sigmoid(classifier(x)), F.binary_cross_entropy with the mean over the frames present,
  * src/utils/loss.py:56-89, and autograd's backward pass through them) and configure_optimizers (:280: torch.optim.Adam, no weight decay).
- * Gradients into a SincNet front end, weight decay, schedules and DDP are not here (dropout between LSTM layers is a stage of
+ * Weight decay, schedules and DDP are not here; gradients into a SincNet front end are uvad_sincnet_train_*, below (dropout between LSTM layers is a stage of
  * uvad_lstm_train_*, below; the head has none in the reference either); d_grad_x is where the backward pass through
  * the LSTM stack starts (uvad_lstm_train_backward below takes it as d_dy).
  *
@@ -1199,7 +1199,7 @@ int uvad_head_train_commit(uvad_ctx *, const void *d_state, size_t state_bytes);
  * kernels as before (their output, or the features themselves when first_layer is 0, is this block's input and may be cached across
  * epochs).  Together with uvad_head_train_* this is VadModel.training_step / configure_optimizers (src/engines/vad_engine.py:247-281)
  * for everything above the front end: nn.LSTM on pack_padded_sequence rows, autograd's backward pass through it, torch.optim.Adam.
- * Gradients into a SincNet front end, weight decay, schedules and DDP are not here.  Dropout between the trainable layers is
+ * Weight decay, schedules and DDP are not here; d_grad_in of a PyanNet is what uvad_sincnet_train_backward takes.  Dropout between the trainable layers is
  * (uvad_lstm_train_set_dropout, defined below); the frozen prefix runs in eval mode.
  *
  * d_x_in [B][T][Din] is the dense f32 input of layer first_layer (Din = in_dim when first_layer is 0, else hidden x directions);
@@ -1281,6 +1281,80 @@ int uvad_lstm_train_read(uvad_ctx *, const void *d_state, size_t state_bytes, in
 int uvad_lstm_train_commit(uvad_ctx *, const void *d_state, size_t state_bytes);
 int uvad_lstm_train_set_dropout(uvad_ctx *, float p, uint64_t seed);
 int uvad_dropout_apply(const float *d_x, float *d_out, int64_t rows, int cols, int layer, uint64_t draw, float p, uint64_t seed, void *stream);
+
+/* ---- SincNet training on the device: forward with kept activations, the backward pass, Adam ----------------------------------------------
+ * The front end of PyanNet (src/models/blocks/sincnet.py:33-103) learns: with uvad_lstm_train_* and uvad_head_train_* this is
+ * VadModel.training_step / configure_optimizers for the waveform model.  d_dfeats is what uvad_lstm_train_backward writes as d_grad_in:
+ * the gradient of the SUMMED loss with respect to d_feats.  Dense batches only: B rows of the same S samples, T =
+ * uvad_sincnet_num_frames(S); per-row sample counts (uvad_sincnet_lens) are not trained.
+ *
+ * Stage s = 0, 1, 2 has L_s conv positions and Lp_s = L_s / 3 pooled positions; the 0 .. 2 conv positions past 3 Lp_s take part in nothing.
+ * Forward, from the STATE's f32 masters (not the context's packed weights):
+ *   the bank F [n_filters][kernel_size] from low_hz_ / band_hz_ as ParamSincFB.filters() defines it (sample rate 16000, min_low_hz =
+ *     min_band_hz = 50; low = 50 + |low_hz_|, high = clamp(low + 50 + |band_hz_|, 50, 8000), band = high - low; cos filter c and sin filter
+ *     c + n_filters / 2 share parameter c), evaluated in double from the f32 masters and the module's f32 buffers window_ / n_, rounded
+ *     once to f32.  It lives in the state behind the Adam block, and commit serves a bank built by this very kernel;
+ *   per row the biased variance over the S samples and eps, xn = g xhat + b0 (g, b0 = wav_norm1d.weight, .bias);
+ *   u = conv(a_in) (+ bias for s >= 1), for s = 0 u <- |u|;  p[l] = max(u[3 l .. 3 l + 2]), the LOWEST index winning a tie;
+ *   mean and rstd = 1 / sqrt(var + eps) per (b, c) over l < Lp_s (biased);  xhat = (p - mean) rstd, z = gamma xhat + beta, a_out = leaky_relu(z).
+ *   Kept in the workspace: p; one byte per pooled element (bits 0 .. 1 the winner's index, stage 0 also bits 2 .. 3: 1 the winning conv
+ *   output was > 0, 2 it was < 0, 0 it was +-0); mean, rstd; the row statistics.  a_out and xhat are recomputed; the pre-pool conv output is
+ *   not kept.  The workspace header records (B, S) and a magic word (xor the high word of S).  d_feats [B][T][c3] is the last a_out.
+ * Backward, stages 2 down to first_stage:  dz = d_a_out (z > 0 ? 1 : slope);  d gamma_c = sum_{b,l} dz xhat, d beta_c = sum_{b,l} dz;
+ *   dxhat = dz gamma;  dp = rstd (dxhat - mean_l(dxhat) - xhat mean_l(dxhat xhat));  du[3 l + winner] = dp, 0 at the other two positions
+ *   and past 3 Lp_s; stage 0 multiplies by the kept sign, sign(+-0) = 0 as torch.abs's gradient.  Stages 1, 2: dbias_co = sum du,
+ *   dW[co][ci][k] = sum_{b,t} du[co][t] a_in[ci][t + k], d_a_in[ci][j] = sum_{co,k} du[co][j - k] W[co][ci][k] (the next lower stage's d_a_out).
+ *   Stage 0 (no gradient for the waveform):  G[c][k] = sum_{b,t} du[c][t] xhat[b][stride t + k], D[c] = sum_{b,t} du[c][t], then
+ *   dF = g G + b0 D, dg = sum_{c,k} F G, db0 = sum_c D[c] sum_k F[c][k], and d low_hz_, d band_hz_ by the chain rule through filters() in
+ *   double: torch.abs's sign(0) = 0, torch.clamp passes a gradient only where min <= v <= max.
+ *   The weight-gradient contractions run in the PLAIN form: k over the conv positions t < 3 Lp_s of every row (flat b 3 Lp_s + t), du formed
+ *   from dp and the winner byte while staging, per segment of `segment` positions folded in segment order.  All contractions are exact f32
+ *   on v_mfma_f32_32x32x2_f32; the per-(b, c) sums run in double, lanes folded in a fixed order.  No floating-point atomics: the same calls
+ *   give the same bits.  The gradients are ADDED into the state's accumulator and the call's B T frames into its count, the count the head
+ *   and the LSTM divide by.  Every backward kernel checks the workspace header on the device: under a (B, S) that is not the forward
+ *   call's it writes nothing.
+ * Stages first_stage .. 2 learn, in the sense of the LSTM's first_layer.  Stage 0 owns wav_norm1d.*, conv1d.0.filterbank.{low_hz_,
+ *   band_hz_} and norm1d.0.*; stage s >= 1 owns conv1d.s.* and norm1d.s.*.  Frozen stages run in the training forward with the state's copy
+ *   of their tensors (a frozen stage 0: the same bank from the band edges when the context has them, so d_feats do not depend on
+ *   first_stage; else the bank given as sincnet.conv1d.0.filters); they get no gradient and the backward walk stops above.
+ *   The P floats are packed in state_dict order restricted to the learning tensors: wav_norm1d.weight, .bias; conv1d.0.filterbank.low_hz_,
+ *   band_hz_; conv1d.1.weight, .bias; conv1d.2.weight, .bias; norm1d.0.weight, .bias; norm1d.1.*; norm1d.2.*.  P = 42602 / 42360 / 18180
+ *   for first_stage 0 / 1 / 2 on the reference geometry.
+ * apply and read are the head's (torch.optim.Adam, no weight decay; tests/head_train_ref.py); which = UVAD_SINCNET_TRAIN_FILTERS reads the
+ *   n_filters x kernel_size bank of the last forward call.
+ * reset copies the masters from the context's host tensors and synchronises: not for graph capture.  The band edges arrive through
+ *   uvad_set_weight as sincnet.conv1d.0.filterbank.low_hz_ / .band_hz_ ([n_filters / 2][1] or [n_filters / 2]); they are optional for
+ *   inference, and reset with stage 0 learning and no band edges returns UVAD_E_STATE.  sincnet.conv1d.0.filterbank.window_ / .n_
+ *   ([kernel_size / 2], the module's buffers) are taken when given and restated on the host otherwise.
+ * commit synchronises, rebuilds the state's bank from the masters as they stand (so the bank served matches the committed band edges, also
+ *   right after an apply; the one write a commit makes to the state), feeds the masters through uvad_set_weight and that bank as
+ *   sincnet.conv1d.0.filters, then calls uvad_finalize, with the consequences uvad_head_train_commit names.
+ * forward, backward and apply allocate nothing and never synchronise: a whole step can be captured as one graph.
+ * Served: the geometries uvad_sincnet_configure accepts with leaky_slope <= 1 (stage 0 learning: kernel_size odd); 1 <= B <= 65535; S with
+ *   at least one frame; B L_0 <= 2^31 - 1; at most 65535 segments.  Otherwise uvad_sincnet_train_configure returns UVAD_E_UNSUPPORTED.
+ * Refusals (nothing enqueued).  UVAD_E_ARG: NULL cfg / d_wav / d_feats / d_dfeats / d_state / d_ws / d_out; d_state or d_ws not 16-byte
+ *   aligned (forward, backward); lr, beta1, beta2, eps, segment as the head's; first_stage outside [0, 2]; B or S out of range, S without a
+ *   frame; state_bytes or ws_bytes below the helpers; which outside 0 .. 5.  UVAD_E_STATE: a context without a model or without a SincNet
+ *   stage; no uvad_sincnet_train_configure yet; a context that is not finalized (reset, commit); a state never reset, or reset under another
+ *   shape. */
+#define UVAD_SINCNET_TRAIN_FILTERS 5
+typedef struct {
+    float lr, beta1, beta2, eps;
+    int segment;                             /* conv positions per gradient partial, 0 = default (2048) */
+    int first_stage;                         /* stages first_stage .. 2 learn */
+} uvad_sincnet_train_cfg;
+int uvad_sincnet_train_configure(uvad_ctx *, const uvad_sincnet_train_cfg *);
+int64_t uvad_sincnet_train_param_count(const uvad_ctx *);   /* P; 0 before uvad_sincnet_train_configure */
+size_t uvad_sincnet_train_state_bytes(const uvad_ctx *);
+size_t uvad_sincnet_train_ws_bytes(const uvad_ctx *, int B, int64_t S);
+int uvad_sincnet_train_reset(uvad_ctx *, void *d_state, size_t state_bytes, void *stream);
+int uvad_sincnet_train_forward(uvad_ctx *, const float *d_wav, int B, int64_t S, float *d_feats, void *d_state, size_t state_bytes,
+                               void *d_ws, size_t ws_bytes, void *stream);
+int uvad_sincnet_train_backward(uvad_ctx *, const float *d_wav, const float *d_dfeats, int B, int64_t S, void *d_state, size_t state_bytes,
+                                void *d_ws, size_t ws_bytes, void *stream);
+int uvad_sincnet_train_apply(uvad_ctx *, void *d_state, size_t state_bytes, void *stream);
+int uvad_sincnet_train_read(uvad_ctx *, const void *d_state, size_t state_bytes, int which, float *d_out, void *stream);
+int uvad_sincnet_train_commit(uvad_ctx *, const void *d_state, size_t state_bytes);
 
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;

@@ -1,6 +1,6 @@
 """Entry point with the reference's shape (main.py:12-55): ``main(load_config())`` dispatches on
 ``config.task`` / ``config.function``.  The inference path, scoring against label files, fine-tuning ("adapt") and training a PyanNet2
-from initialisation ("train") are in scope; every other task of the reference (corpus download / preparation) raises with a pointer to
+or a PyanNet from initialisation ("train") are in scope; every other task of the reference (corpus download / preparation) raises with a pointer to
 SURVEY.md."""
 import faulthandler
 

@@ -63,6 +63,13 @@ class LstmTrainCfg(C.Structure):     # uvad_lstm_train_cfg (24 bytes)
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("segment", C.c_int), ("first_layer", C.c_int)]
 
 
+class SincNetTrainCfg(C.Structure):  # uvad_sincnet_train_cfg (24 bytes)
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("segment", C.c_int), ("first_stage", C.c_int)]
+
+
+SINCNET_TRAIN_FILTERS = 5        # `which` of uvad_sincnet_train_read: the bank of the last forward call
+
+
 class CutsCfg(C.Structure):
     _fields_ = [("pad", C.c_int), ("max_len", C.c_int), ("min_len", C.c_int), ("hop", C.c_int), ("lead", C.c_int), ("tail", C.c_int)]
 
@@ -234,6 +241,18 @@ SIGNATURES = {
     "uvad_lstm_train_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "uvad_lstm_train_set_dropout": (C.c_int, [C.c_void_p, C.c_float, C.c_uint64]),
     "uvad_dropout_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_uint64, C.c_float, C.c_uint64, C.c_void_p]),
+    "uvad_sincnet_train_configure": (C.c_int, [C.c_void_p, C.POINTER(SincNetTrainCfg)]),
+    "uvad_sincnet_train_param_count": (C.c_int64, [C.c_void_p]),
+    "uvad_sincnet_train_state_bytes": (C.c_size_t, [C.c_void_p]),
+    "uvad_sincnet_train_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int64]),
+    "uvad_sincnet_train_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_sincnet_train_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                             C.c_void_p]),
+    "uvad_sincnet_train_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                              C.c_void_p]),
+    "uvad_sincnet_train_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_sincnet_train_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "uvad_sincnet_train_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "uvad_cuts_max_per_row": (C.c_int, [C.POINTER(CutsCfg), C.c_int]),
     "uvad_cuts_max_samples": (C.c_int64, [C.POINTER(CutsCfg), C.c_int64]),
     "uvad_cuts_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),

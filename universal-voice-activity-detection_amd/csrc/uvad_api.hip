@@ -131,6 +131,10 @@ struct uvad_ctx {
     LstmTrainShape lts{};
     unsigned lt_thr = 0; float lt_scale = 1.0f; uint64_t lt_seed = 0;   // uvad_lstm_train_set_dropout: what the forward call launches with (thr == 0: off)
     bool lt_dropped = false;                    // the last forward call of this context ran with thr > 0
+    std::map<void *, int> sinc_trains;          // ... and of the SincNet training states (uvad_sincnet_train_*): first_stage at reset, + 256 with band edges
+    bool has_snt = false;                       // uvad_sincnet_train_configure: the optimiser, first_stage and the packed shape of the front end
+    uvad_sincnet_train_cfg snq{};
+    SincTrainShape snts{};
     int device = 0, n_cu = 256;
     bool has_fb = false, has_model = false, finalized = false, tables_set = false;
     uvad_fbank_cfg fb{};
@@ -3507,6 +3511,208 @@ int uvad_lstm_train_commit(uvad_ctx *c, const void *d_state, size_t state_bytes)
                 const int64_t shape[2] = {4 * q.H, k == 0 ? q.in[li] : q.H};
                 if (int r = uvad_set_weight(c, lstm_train_key(q.first_layer + li, d, k).c_str(), w.data() + q.off[li][d][k], shape, k < 2 ? 2 : 1)) return r;
             }
+    return uvad_finalize(c);
+}
+
+// ---- SincNet training (sincnet_train.hip) ----------------------------------------------------------------------------------------------------
+int uvad_sincnet_train_configure(uvad_ctx *c, const uvad_sincnet_train_cfg *q) {
+    if (!c) return UVAD_E_ARG;
+    if (!q) return fail(c, UVAD_E_ARG, "uvad_sincnet_train_configure: bad argument");
+    if (!std::isfinite(q->lr) || !(q->lr > 0.0f)) return fail(c, UVAD_E_ARG, "uvad_sincnet_train_configure: lr must be finite and positive");
+    if (!std::isfinite(q->beta1) || q->beta1 < 0.0f || !(q->beta1 < 1.0f)) return fail(c, UVAD_E_ARG, "uvad_sincnet_train_configure: beta1 must lie in [0, 1)");
+    if (!std::isfinite(q->beta2) || q->beta2 < 0.0f || !(q->beta2 < 1.0f)) return fail(c, UVAD_E_ARG, "uvad_sincnet_train_configure: beta2 must lie in [0, 1)");
+    if (!std::isfinite(q->eps) || !(q->eps > 0.0f)) return fail(c, UVAD_E_ARG, "uvad_sincnet_train_configure: eps must be finite and positive");
+    if (q->segment != 0 && (q->segment < HT_MIN_SEGMENT || q->segment > HT_MAX_SEGMENT || q->segment % 32))
+        return fail(c, UVAD_E_ARG, "uvad_sincnet_train_configure: segment must be 0 or a multiple of 32 in [32, 16384] positions");
+    if (q->first_stage < 0 || q->first_stage > 2) return fail(c, UVAD_E_ARG, "uvad_sincnet_train_configure: first_stage must lie in [0, 2]");
+    if (!c->has_model) return fail(c, UVAD_E_STATE, "uvad_sincnet_train_configure: context was created without a model configuration");
+    if (!c->has_sinc) return fail(c, UVAD_E_STATE, "uvad_sincnet_train_configure: the context has no SincNet stage (uvad_sincnet_configure)");
+    const uvad_sincnet_cfg &sc = c->sc;
+    if (!(sc.leaky_slope <= 1.0f)) return fail(c, UVAD_E_UNSUPPORTED, "uvad_sincnet_train_configure: leaky_slope must be <= 1");
+    if (q->first_stage == 0 && !(sc.kernel_size & 1))
+        return fail(c, UVAD_E_UNSUPPORTED, "uvad_sincnet_train_configure: a learning sinc bank needs an odd kernel_size");
+    c->snq = *q;
+    if (c->snq.segment == 0) c->snq.segment = HT_DEFAULT_SEGMENT;
+    c->snts = sinc_train_shape(sc.n_filters, sc.kernel_size, sc.stride, sc.c2, sc.k2, sc.c3, sc.k3, sc.leaky_slope, sc.eps, q->first_stage);
+    c->has_snt = true;
+    return UVAD_OK;
+}
+
+int64_t uvad_sincnet_train_param_count(const uvad_ctx *c) { return c && c->has_snt ? (int64_t)c->snts.P : 0; }
+size_t uvad_sincnet_train_state_bytes(const uvad_ctx *c) { return c && c->has_snt ? sinc_train_state_bytes(c->snts) : 0; }
+
+// nullptr: (B, S) is served; else the word uvad_last_error names
+static const char *sinc_train_shape_error(const uvad_ctx *c, int B, int64_t S, SincTrainGeo *geo_out) {
+    if (B < 1 || B > SNT_MAX_B) return "B must lie in [1, 65535]";
+    if (S < 1) return "S must be >= 1";
+    const SincTrainGeo geo = sinc_train_geo(c->snts, S);
+    if (!geo.ok) return "S too short for one output frame";
+    if ((long long)B * geo.L[0] > 0x7fffffffLL) return "B x L_0 above 2^31 - 1 conv positions";
+    if (((long long)B * 3 * geo.Lp[c->snts.first_stage] + c->snq.segment - 1) / c->snq.segment > 65535)
+        return "more than 65535 segments: B x 3 Lp / segment too large";
+    if (geo_out) *geo_out = geo;
+    return nullptr;
+}
+
+size_t uvad_sincnet_train_ws_bytes(const uvad_ctx *c, int B, int64_t S) {
+    SincTrainGeo geo;
+    if (!c || !c->has_snt || sinc_train_shape_error(c, B, S, &geo)) return 0;
+    return sinc_train_ws(c->snts, geo, B, c->snq.segment).total;
+}
+
+static int sinc_train_state_check(uvad_ctx *c, const char *fn, const void *d_state, size_t state_bytes, bool reset) {
+    const std::string f(fn);
+    if (!d_state) return fail(c, UVAD_E_ARG, f + ": bad argument");
+    if (!c->has_snt) return fail(c, UVAD_E_STATE, f + ": call uvad_sincnet_train_configure first");
+    const size_t need = sinc_train_state_bytes(c->snts);
+    if (state_bytes < need) return fail(c, UVAD_E_ARG, f + ": state too small: need " + std::to_string(need) + " bytes");
+    if (reset) return UVAD_OK;
+    auto it = c->sinc_trains.find(const_cast<void *>(d_state));
+    if (it == c->sinc_trains.end()) return fail(c, UVAD_E_STATE, f + ": call uvad_sincnet_train_reset on this state first");
+    if ((it->second & 255) != c->snts.first_stage) return fail(c, UVAD_E_STATE, f + ": the state was reset under another shape");
+    return UVAD_OK;
+}
+
+// the torch key and shape of tensor t (SNT_T_* order)
+static std::string sinc_train_key(int t) {
+    static const char *const names[SNT_TENSORS] = {"wav_norm1d.weight", "wav_norm1d.bias", "conv1d.0.filterbank.low_hz_", "conv1d.0.filterbank.band_hz_",
+                                                   "conv1d.1.weight", "conv1d.1.bias", "conv1d.2.weight", "conv1d.2.bias", "norm1d.0.weight",
+                                                   "norm1d.0.bias", "norm1d.1.weight", "norm1d.1.bias", "norm1d.2.weight", "norm1d.2.bias"};
+    return std::string("sincnet.") + names[t];
+}
+static int sinc_train_tensor_shape(const SincTrainShape &q, int t, int64_t shape[3]) {
+    if (t == SNT_T_LOW || t == SNT_T_BAND) { shape[0] = q.NF / 2; shape[1] = 1; return 2; }
+    if (t == SNT_T_CONV || t == SNT_T_CONV + 2) {
+        const int s = t == SNT_T_CONV ? 1 : 2;
+        shape[0] = q.Cout[s]; shape[1] = q.Cin[s]; shape[2] = q.Kw[s];
+        return 3;
+    }
+    shape[0] = q.cnt[t];
+    return 1;
+}
+
+int uvad_sincnet_train_reset(uvad_ctx *c, void *d_state, size_t state_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (int r = sinc_train_state_check(c, "uvad_sincnet_train_reset", d_state, state_bytes, true)) return r;
+    if (!c->finalized) return fail(c, UVAD_E_STATE, "uvad_sincnet_train_reset: call uvad_finalize first");
+    const SincTrainShape &q = c->snts;
+    auto get = [&](const std::string &k) -> const HostTensor * {
+        auto it = c->host_w.find(k);
+        return it == c->host_w.end() ? nullptr : &it->second;
+    };
+    const size_t words = (sinc_train_state_bytes(q) - sizeof(HeadTrainHeader)) / sizeof(float);
+    std::vector<float> img(words, 0.0f);
+    for (int t = 0; t < SNT_TENSORS; ++t) {
+        const HostTensor *h = get(sinc_train_key(t));
+        const bool edge = t == SNT_T_LOW || t == SNT_T_BAND;
+        if (!h && edge && q.first_stage > 0) continue;   // a frozen bank runs from sincnet.conv1d.0.filters
+        if (!h || h->data.size() != (size_t)q.cnt[t]) return fail(c, UVAD_E_STATE, "uvad_sincnet_train_reset: missing SincNet tensor " + sinc_train_key(t));
+        std::memcpy(img.data() + q.off_fullblock + q.off_full[t], h->data.data(), h->data.size() * sizeof(float));
+        if (q.off_master[t] >= 0) std::memcpy(img.data() + q.off_master[t], h->data.data(), h->data.size() * sizeof(float));
+    }
+    const bool edges = get(sinc_train_key(SNT_T_LOW)) && get(sinc_train_key(SNT_T_BAND)) && (q.KS & 1);
+    if (const HostTensor *f = get("sincnet.conv1d.0.filters")) {
+        if (f->data.size() != (size_t)q.NF * q.KS) return fail(c, UVAD_E_STATE, "uvad_sincnet_train_reset: misshaped sincnet.conv1d.0.filters");
+        std::memcpy(img.data() + q.off_bank, f->data.data(), f->data.size() * sizeof(float));
+    } else if (!edges) {
+        return fail(c, UVAD_E_STATE, "uvad_sincnet_train_reset: missing SincNet tensor sincnet.conv1d.0.filters");
+    }
+    const int half = q.KS / 2;
+    const HostTensor *hw = get("sincnet.conv1d.0.filterbank.window_"), *hn = get("sincnet.conv1d.0.filterbank.n_");
+    for (int i = 0; i < half; ++i) {   // ParamSincFB's buffers: np.hamming(kernel_size)[:half] as f32, 2 pi (i - half) / 16000 in f32
+        img[q.off_win + i] = hw && hw->data.size() == (size_t)half ? hw->data[i] : (float)(0.54 - 0.46 * std::cos(2.0 * M_PI * i / (double)(q.KS - 1)));
+        img[q.off_n + i] = hn && hn->data.size() == (size_t)half ? hn->data[i] : (float)(2.0 * M_PI) * ((float)(i - half) / 16000.0f);
+    }
+    HeadTrainHeader h{};
+    h.magic = SNT_MAGIC; h.D0 = q.first_stage; h.H = q.NF; h.L = q.KS; h.P = q.P;
+    h.pad0 = edges ? 1 : 0;   // the forward call materialises the bank from the band edges
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));   // the state comes from the host tensors: blocking copies
+    HIPCHK(c, hipMemcpy(reinterpret_cast<char *>(d_state) + sizeof(HeadTrainHeader), img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_state, &h, sizeof h, hipMemcpyHostToDevice));
+    c->sinc_trains[d_state] = q.first_stage | (edges ? 256 : 0);
+    return UVAD_OK;
+}
+
+// the checks forward and backward share: arguments, configuration, shape and sizes, then that the state was reset
+static int sinc_train_call_check(uvad_ctx *c, const char *fn, const void *d_wav, const void *d_other, int B, int64_t S, void *d_state, size_t state_bytes,
+                                 void *d_ws, size_t ws_bytes) {
+    const std::string f(fn);
+    if (!d_wav || !d_other || !d_state || !d_ws || B < 1 || S < 1) return fail(c, UVAD_E_ARG, f + ": bad argument");
+    if (reinterpret_cast<uintptr_t>(d_state) % 16 || reinterpret_cast<uintptr_t>(d_ws) % 16)
+        return fail(c, UVAD_E_ARG, f + ": d_state and d_ws must be 16-byte aligned");
+    if (int r = sinc_train_state_check(c, fn, d_state, state_bytes, true)) return r;
+    SincTrainGeo geo;
+    if (const char *w = sinc_train_shape_error(c, B, S, &geo)) return fail(c, UVAD_E_ARG, f + ": " + w);
+    const size_t need = sinc_train_ws(c->snts, geo, B, c->snq.segment).total;
+    if (ws_bytes < need) return fail(c, UVAD_E_ARG, f + ": workspace too small: need " + std::to_string(need) + " bytes");
+    return sinc_train_state_check(c, fn, d_state, state_bytes, false);
+}
+
+int uvad_sincnet_train_forward(uvad_ctx *c, const float *d_wav, int B, int64_t S, float *d_feats, void *d_state, size_t state_bytes, void *d_ws,
+                               size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (int r = sinc_train_call_check(c, "uvad_sincnet_train_forward", d_wav, d_feats, B, S, d_state, state_bytes, d_ws, ws_bytes)) return r;
+    SincTrainArgs a{};
+    a.wav = d_wav; a.B = B; a.S = S; a.feats = d_feats; a.state = d_state; a.ws = d_ws; a.seg = c->snq.segment;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_sinc_train_forward(c->snts, a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_sincnet_train_backward(uvad_ctx *c, const float *d_wav, const float *d_dfeats, int B, int64_t S, void *d_state, size_t state_bytes,
+                                void *d_ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (int r = sinc_train_call_check(c, "uvad_sincnet_train_backward", d_wav, d_dfeats, B, S, d_state, state_bytes, d_ws, ws_bytes)) return r;
+    SincTrainArgs a{};
+    a.wav = d_wav; a.dfeats = d_dfeats; a.B = B; a.S = S; a.state = d_state; a.ws = d_ws; a.seg = c->snq.segment;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_sinc_train_backward(c->snts, a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_sincnet_train_apply(uvad_ctx *c, void *d_state, size_t state_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (int r = sinc_train_state_check(c, "uvad_sincnet_train_apply", d_state, state_bytes, false)) return r;
+    const uvad_sincnet_train_cfg &q = c->snq;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_sinc_train_apply(c->snts, adam_of(q.lr, q.beta1, q.beta2, q.eps), d_state, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_sincnet_train_read(uvad_ctx *c, const void *d_state, size_t state_bytes, int which, float *d_out, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_out || which < 0 || which > UVAD_SINCNET_TRAIN_FILTERS) return fail(c, UVAD_E_ARG, "uvad_sincnet_train_read: bad argument");
+    if (int r = sinc_train_state_check(c, "uvad_sincnet_train_read", d_state, state_bytes, false)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_sinc_train_read(c->snts, d_state, which, d_out, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_sincnet_train_commit(uvad_ctx *c, const void *d_state, size_t state_bytes) {
+    if (!c) return UVAD_E_ARG;
+    if (int r = sinc_train_state_check(c, "uvad_sincnet_train_commit", d_state, state_bytes, false)) return r;
+    if (!c->finalized) return fail(c, UVAD_E_STATE, "uvad_sincnet_train_commit: call uvad_finalize first");
+    const SincTrainShape q = c->snts;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());   // every enqueued backward / apply has landed
+    const bool edges = (c->sinc_trains[const_cast<void *>(d_state)] & 256) != 0;
+    if (edges) {   // the bank of the masters as they stand after the last apply: what is served matches the committed band edges
+        HIPCHK(c, launch_sinc_train_bank(q, const_cast<void *>(d_state), nullptr));
+        HIPCHK(c, hipDeviceSynchronize());
+    }
+    std::vector<float> w((size_t)q.off_bank + q.bankp);
+    HIPCHK(c, hipMemcpy(w.data(), reinterpret_cast<const char *>(d_state) + sizeof(HeadTrainHeader), w.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int t = 0; t < SNT_TENSORS; ++t) {
+        if (q.off_master[t] < 0) continue;
+        int64_t shape[3];
+        const int nd = sinc_train_tensor_shape(q, t, shape);
+        if (int r = uvad_set_weight(c, sinc_train_key(t).c_str(), w.data() + q.off_master[t], shape, nd)) return r;
+    }
+    if (edges) {   // learning or frozen
+        const int64_t shape[3] = {q.NF, 1, q.KS};
+        if (int r = uvad_set_weight(c, "sincnet.conv1d.0.filters", w.data() + q.off_bank, shape, 3)) return r;
+    }
     return uvad_finalize(c);
 }
 

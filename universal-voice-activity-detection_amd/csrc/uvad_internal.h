@@ -854,4 +854,47 @@ unsigned lstm_dropout_threshold(float p);            // floor((double)p 2^32)
 hipError_t launch_dropout_apply(const float *x, float *out, long long rows, int cols, int layer, unsigned long long draw, unsigned thr, float scale,
                                 unsigned long long seed, hipStream_t s);
 
+// ---- sincnet_train.hip: training of the SincNet front end (uvad_sincnet_train_*, include/uvad.h): forward with kept activations, backward, Adam ----
+// Stages first_stage .. 2 learn.  The 14 tensors in state_dict order (SNT_T_*): wav_norm1d.weight, .bias, conv1d.0.filterbank.low_hz_, band_hz_
+// (stage 0), conv1d.1.weight, .bias (stage 1), conv1d.2.weight, .bias (stage 2), norm1d.s.weight, .bias (stage s); the learning ones packed in
+// that order are the P floats of the Adam block, padded to Pp = a multiple of 64.
+// State: HeadTrainHeader with SNT_MAGIC (256 bytes) | masters [Pp] | gradient accumulator [Pp] | m [Pp] | v [Pp] (the head's layout: the fold,
+//        Adam and read kernels of ht_kernels.h serve it) | the bank [n_filters][kernel_size] the last forward call ran (padded to 64 floats) |
+//        all 14 tensors as reset found them, in order (the frozen stages run from here; padded) | window_ [kernel_size / 2] | n_ [kernel_size / 2]
+//        (each padded to 64 floats).
+// Workspace: SincTrainWsHead (256 bytes: magic ^ high word of S, B, S) | HeadTrainWsHead (the fold's record) | row statistics [B][4] | per stage:
+//            pooled values [B][Cout][Lp], winner bytes [B][Cout][Lp], mean / rstd [B][Cout][2], and for a learning stage the gradient buffer
+//            [B][Cout][Lp] (d_a_out, then dp in place) | the rows' shares of d gamma / d beta [B][max Cout][2] | gradient partials [nseg][Pp] |
+//            stage 0 learning: its partials of G and D [nseg][GS] and their fold [GS], GS = n_filters (kernel_size + 1) padded to 64; every part
+//            256-byte aligned.  nseg = ceil(B 3 Lp_first_stage / segment): the segments run over the flat conv positions of the lowest learning stage.
+constexpr unsigned SNT_MAGIC = 0x5556534Eu;          // "UVSN": the state
+constexpr int SNT_WS_MAGIC = 0x534E5753;             // "SNWS": a workspace whose kept activations belong to (B, S)
+constexpr int SNT_TENSORS = 14, SNT_T_WAV = 0, SNT_T_LOW = 2, SNT_T_BAND = 3, SNT_T_CONV = 4, SNT_T_NORM = 8;
+constexpr int SNT_MAX_B = 65535;                     // rows are a grid dimension
+struct SincTrainShape {
+    int first_stage, P, Pp, Pfull, Pfullp;
+    int NF, KS, stride;
+    int Cin[3], Cout[3], Kw[3];
+    int cnt[SNT_TENSORS], stage_of[SNT_TENSORS], off_full[SNT_TENSORS], off_master[SNT_TENSORS];   // off_master: -1 for a frozen tensor
+    int bankp, halfp, off_bank, off_fullblock, off_win, off_n;   // in floats behind the header
+    float slope, eps;
+};
+struct SincTrainGeo { long long Lin[3], L[3], Lp[3]; bool ok; };   // ok: at least one frame
+struct SincTrainWsHead { int magic, B, S_lo, S_hi; int reserved[60]; };
+struct SincTrainWs { size_t off_fold, off_wstat, off_p[3], off_idx[3], off_stat[3], off_g[3], off_nb, off_part, off_partG, off_Gf, total; int nseg, GS; };
+struct SincTrainArgs {
+    const float *wav; const float *dfeats; int B; long long S;
+    float *feats;
+    void *state; void *ws; int seg;
+};
+SincTrainShape sinc_train_shape(int n_filters, int kernel_size, int stride, int c2, int k2, int c3, int k3, float slope, float eps, int first_stage);
+size_t sinc_train_state_bytes(const SincTrainShape &q);
+SincTrainGeo sinc_train_geo(const SincTrainShape &q, long long S);
+SincTrainWs sinc_train_ws(const SincTrainShape &q, const SincTrainGeo &geo, int B, int seg);
+hipError_t launch_sinc_train_forward(const SincTrainShape &q, const SincTrainArgs &a, hipStream_t s);
+hipError_t launch_sinc_train_backward(const SincTrainShape &q, const SincTrainArgs &a, hipStream_t s);
+hipError_t launch_sinc_train_bank(const SincTrainShape &q, void *state, hipStream_t s);   // the bank from the masters as they stand
+hipError_t launch_sinc_train_apply(const SincTrainShape &q, const HeadTrainAdam &o, void *state, hipStream_t s);
+hipError_t launch_sinc_train_read(const SincTrainShape &q, const void *state, int which, float *out, hipStream_t s);   // which 5: the bank
+
 }  // namespace uvad

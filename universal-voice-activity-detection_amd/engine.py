@@ -5,9 +5,9 @@ keep their names, argument meaning and return shapes; what the reference logs th
 is accumulated on the device (``uvad_score_*``) and read with ``test_metrics`` / ``validation_metrics``.
 ``adapt_head_step`` / ``adapt_head_commit`` fine-tune the head on the device (``uvad_head_train_*``); ``adapt_step`` /
 ``adapt_commit`` let the top LSTM layers learn with it (``uvad_lstm_train_*``); ``train_step`` / ``train_commit`` are the reference's
-training step for a PyanNet2: every LSTM layer and the head learn, with nn.LSTM's dropout between the layers drawn on the device.
-``training_step`` and ``configure_optimizers`` themselves (Lightning's hooks; gradients into a SincNet front end, DDP) are outside the
-accelerated path and raise."""
+training step: every LSTM layer and the head learn, with nn.LSTM's dropout between the layers drawn on the device, and for a PyanNet the
+SincNet front end learns from the raw waveform (``uvad_sincnet_train_*``).
+``training_step`` and ``configure_optimizers`` themselves (Lightning's hooks; DDP) are outside the accelerated path and raise."""
 import torch
 import torch.nn as nn
 
@@ -173,24 +173,64 @@ class VadModel(nn.Module):
             x = rt.sincnet(x[:, 0, :] if x.dim() == 3 else x)
         return rt.lstm_train_input(x, lengths=batch.get("lengths"), layers=lstm_layers)
 
-    def adapt_step(self, batch, batch_idx=0, accumulate: int = 1, lstm_layers: int = 1, dropout=None, seed: int = 0):
+    _NO_SINCNET_LENGTHS = ("the SincNet front end normalises over whole rows (wav_norm1d and every instance norm), so per-row lengths are "
+                           "not trained: batches of one length only")
+
+    def _sincnet_step(self, batch, accumulate, sincnet_stages, dropout, seed):
+        """adapt_step with the top `sincnet_stages` SincNet stages learning: the waveform through sincnet_train_forward, every LSTM layer
+        and the head above it, and the LSTM's input gradient back through the front end."""
+        if batch.get("lengths") is not None:
+            raise NotImplementedError(self._NO_SINCNET_LENGTHS)
+        if self.model_name != "PyanNet":
+            raise ValueError("sincnet_stages needs a PyanNet")
+        stages = int(sincnet_stages)
+        if not 1 <= stages <= 3:
+            raise ValueError("sincnet_stages must lie in 0 .. 3")
+        y = batch["is_voice"]
+        wav = batch["inputs"]
+        layers = self.model.hparams.lstm["num_layers"]       # the gradient reaches the front end only through every layer
+        rt = self.model.runtime(wav.device)
+        held = getattr(self, "_adapt_full", None)
+        if held is None or held[0] is not rt or held[2]["layers"] != layers or len(held) < 5 or held[4]["first_stage"] != 3 - stages:
+            held = self._adapt_full = [rt, rt.head_train_open(lr=self.learning_rate),
+                                       rt.lstm_train_open(layers=layers, lr=self.learning_rate, dropout=dropout, seed=seed), 0,
+                                       rt.sincnet_train_open(first_stage=3 - stages, lr=self.learning_rate)]
+        hh, hl, hs = held[1], held[2], held[4]
+        hl["dropout"], hl["seed"] = dropout, int(seed) & 0xFFFFFFFFFFFFFFFF
+        feats = rt.sincnet_train_forward(hs, wav)
+        gt = (y.to(feats.device) != 0).to(torch.uint8).reshape(feats.shape[:2])
+        out = rt.lstm_train_forward(hl, feats)
+        _, gx = rt.head_train_grad(hh, out, gt, want_grad_x=True)
+        gin = rt.lstm_train_backward(hl, feats, gx, want_grad_in=True)
+        rt.sincnet_train_backward(hs, wav, gin)
+        held[3] += 1
+        if held[3] % max(1, int(accumulate)) == 0:
+            rt.head_train_apply(hh)
+            rt.lstm_train_apply(hl)
+            rt.sincnet_train_apply(hs)
+        return rt.head_train_batch_loss(hh)
+
+    def adapt_step(self, batch, batch_idx=0, accumulate: int = 1, lstm_layers: int = 1, dropout=None, seed: int = 0, sincnet_stages: int = 0):
         """One micro-batch in which the head and the top `lstm_layers` LSTM layers learn: batch["lstm_in"] (the cached frozen prefix) or
         batch["inputs"] through it, the learning layers' forward pass with kept activations, the head's loss and backward pass as
         adapt_head_step's, backpropagation through time from its input gradient; every `accumulate` calls one Adam step on both
         states (lr = self.learning_rate).  dropout: nn.LSTM's dropout between the learning layers, a fresh mask per call (None: none,
-        the frozen prefix never has any); seed: the masks' seed.  Returns the batch's mean loss as a 0-d tensor on the device without
-        synchronising."""
+        the frozen prefix never has any); seed: the masks' seed.  sincnet_stages = k > 0 (PyanNet): the top k stages of the SincNet front
+        end learn too, from the waveform batch["inputs"] (B, 1, S) or (B, S) -- every LSTM layer then learns, whatever lstm_layers says,
+        and batch["lengths"] must be None.  Returns the batch's mean loss as a 0-d tensor on the device without synchronising."""
         y = batch.get("is_voice")
         if y is None:
             raise ValueError('adapt_step needs batch["is_voice"]')
         dropout = 0.0 if dropout is None else float(dropout)
         if not 0.0 <= dropout < 1.0:
             raise ValueError("dropout must lie in [0, 1)")
+        if int(sincnet_stages) != 0:
+            return self._sincnet_step(batch, accumulate, sincnet_stages, dropout, seed)
         x = batch["lstm_in"] if batch.get("lstm_in") is not None else self.lstm_in(batch, lstm_layers)
         rt = self.model.runtime(x.device)
         held = getattr(self, "_adapt_full", None)
-        if held is None or held[0] is not rt or held[2]["layers"] != int(lstm_layers):
-            held = self._adapt_full = [rt, rt.head_train_open(lr=self.learning_rate),
+        if held is None or held[0] is not rt or held[2]["layers"] != int(lstm_layers) or len(held) > 4:   # (a SincNet handle of an earlier
+            held = self._adapt_full = [rt, rt.head_train_open(lr=self.learning_rate),                      # sincnet_stages > 0 step: start anew)
                                        rt.lstm_train_open(layers=lstm_layers, lr=self.learning_rate, dropout=dropout, seed=seed), 0]
         hh, hl = held[1], held[2]
         hl["dropout"], hl["seed"] = dropout, int(seed) & 0xFFFFFFFFFFFFFFFF      # the handle re-asserts them before every call
@@ -212,11 +252,16 @@ class VadModel(nn.Module):
         if held is None:
             raise RuntimeError("no adapt_step has run yet")
         rt, hh, hl = held[0], held[1], held[2]
+        hs = held[4] if len(held) > 4 else None
+        front = {}
+        if hs is not None:                                   # the front end first: each commit re-finalizes with what is set so far
+            rt.sincnet_train_commit(hs)
+            front = rt.sincnet_train_state_dict(hs)          # low_hz_ and band_hz_ among them
         rt.lstm_train_commit(hl)
         rt.head_train_commit(hh)
         params = dict(self.model.named_parameters())
         with torch.no_grad():
-            for key, t in list(rt.head_train_state_dict(hh).items()) + list(rt.lstm_train_state_dict(hl).items()):
+            for key, t in list(rt.head_train_state_dict(hh).items()) + list(rt.lstm_train_state_dict(hl).items()) + list(front.items()):
                 if key not in params:   # the ModuleList-of-LSTMs variant: lstm.{k}.weight_ih_l0[_reverse]
                     name, k = key[len("lstm."):].split("_l", 1)
                     key = f"lstm.{k.replace('_reverse', '')}.{name}_l0" + ("_reverse" if k.endswith("_reverse") else "")
@@ -225,12 +270,14 @@ class VadModel(nn.Module):
 
     # -- training from initialisation: every LSTM layer and the head learn (PyanNet2) -----------------------------------------------
     def train_step(self, batch, batch_idx=0, accumulate: int = 1):
-        """The reference's training_step for a PyanNet2 on the device: adapt_step with every LSTM layer learning, the model's configured
-        dropout between the layers (self.model.train_dropout) and the masks seeded from torch.initial_seed()."""
-        if self.model_name == "PyanNet":
-            raise NotImplementedError("train_step needs the gradients into the SincNet front end, which are not on the device: PyanNet2 only")
+        """The reference's training_step on the device: adapt_step with every LSTM layer learning, the model's configured dropout between
+        the layers (self.model.train_dropout) and the masks seeded from torch.initial_seed().  A PyanNet takes the waveform batch
+        (B, 1, S) or (B, S) and its whole SincNet front end learns with the rest; its batch must not carry lengths."""
+        if self.model_name == "PyanNet" and batch.get("lengths") is not None:    # before the model or the device is touched
+            raise NotImplementedError("train_step: " + self._NO_SINCNET_LENGTHS)
         return self.adapt_step(batch, batch_idx, accumulate=accumulate, lstm_layers=self.model.hparams.lstm["num_layers"],
-                               dropout=self.model.train_dropout, seed=torch.initial_seed())
+                               dropout=self.model.train_dropout, seed=torch.initial_seed(),
+                               sincnet_stages=3 if self.model_name == "PyanNet" else 0)
 
     def train_commit(self):
         """adapt_commit: serve the trained tensors and write them into self.model's parameters."""

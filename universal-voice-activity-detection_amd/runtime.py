@@ -251,8 +251,9 @@ class VadRuntime:
     def load_state_dict(self, sd: Dict[str, "torch.Tensor"]):
         """torch-keyed tensors (CPU or GPU; a Lightning ``model.`` prefix is accepted)."""
         for k, v in sd.items():
-            if ".filterbank." in k:
-                continue   # band edges / buffers of ParamSincFB: the materialised bank is sent as "...conv1d.0.filters"
+            if ".filterbank." in k and k.rsplit(".", 1)[1] not in ("low_hz_", "band_hz_", "window_", "n_"):
+                continue   # inference runs the materialised bank, sent as "...conv1d.0.filters"; the band edges and the two buffers are
+                           # what uvad_sincnet_train_reset builds the learning bank from
             a = np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy() if torch.is_tensor(v) else v, np.float32)
             shape = (C.c_int64 * a.ndim)(*a.shape)
             self._check(self.lib.uvad_set_weight(self.ctx, k.encode(), a.ctypes.data, shape, a.ndim))
@@ -1571,6 +1572,130 @@ class VadRuntime:
         with torch.cuda.device(self.device):
             self._lstm_train_configure(h)
             self._check(self.lib.uvad_lstm_train_commit(self.ctx, h["state"].data_ptr(), h["state"].numel()))
+            self._weights_gen = getattr(self, "_weights_gen", 0) + 1
+
+    # ------------------------------------------------------------------ SincNet training (uvad_sincnet_train_*)
+    def sincnet_train_keys(self, first_stage: int = 0):
+        """[(torch key, shape)] of the learning tensors of stages first_stage .. 2 in the packed order of uvad_sincnet_train_read
+        (state_dict order), with the model's ``sincnet.`` prefix."""
+        q = self._sn_c
+        nf, c2, c3 = q.n_filters, q.c2, q.c3
+        every = [(0, "wav_norm1d.weight", (1,)), (0, "wav_norm1d.bias", (1,)), (0, "conv1d.0.filterbank.low_hz_", (nf // 2, 1)),
+                 (0, "conv1d.0.filterbank.band_hz_", (nf // 2, 1)), (1, "conv1d.1.weight", (c2, nf, q.k2)), (1, "conv1d.1.bias", (c2,)),
+                 (2, "conv1d.2.weight", (c3, c2, q.k3)), (2, "conv1d.2.bias", (c3,)), (0, "norm1d.0.weight", (nf,)), (0, "norm1d.0.bias", (nf,)),
+                 (1, "norm1d.1.weight", (c2,)), (1, "norm1d.1.bias", (c2,)), (2, "norm1d.2.weight", (c3,)), (2, "norm1d.2.bias", (c3,))]
+        return [("sincnet." + k, shape) for stage, k, shape in every if stage >= int(first_stage)]
+
+    def sincnet_train_open(self, first_stage: int = 0, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, segment: int = 0):
+        """Allocate and reset a training state for stages first_stage .. 2 of the SincNet front end (uvad_sincnet_train_reset): f32 master
+        copies of their tensors as loaded (the band edges of the sinc bank among them), Adam moments, the gradient accumulator, the bank.
+        segment: conv positions per gradient partial (0 = the library's default).  The handle owns the state and the workspace."""
+        if self._sn_c is None:
+            raise RuntimeError("this runtime has no SincNet stage")
+        first_stage = int(first_stage)
+        if not 0 <= first_stage <= 2:
+            raise ValueError("first_stage must lie in 0 .. 2")
+        cfg = _lib.SincNetTrainCfg(float(lr), float(betas[0]), float(betas[1]), float(eps), int(segment), first_stage)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_sincnet_train_configure(self.ctx, C.byref(cfg)))
+            P = int(self.lib.uvad_sincnet_train_param_count(self.ctx))
+            h = {"cfg": cfg, "P": P, "first_stage": first_stage, "ws": None,
+                 "state": torch.empty(int(self.lib.uvad_sincnet_train_state_bytes(self.ctx)), dtype=torch.uint8, device=self.device),
+                 "out": torch.zeros(max(P, _lib.HEAD_TRAIN_SCALAR_WORDS, self._sn_c.n_filters * self._sn_c.kernel_size), dtype=torch.float32,
+                                    device=self.device)}
+            self._check(self.lib.uvad_sincnet_train_reset(self.ctx, h["state"].data_ptr(), h["state"].numel(), self._stream()))
+            return h
+
+    def _sincnet_train_wav(self, wav: "torch.Tensor") -> "torch.Tensor":
+        wav = self._dev_f32(wav, "wav")
+        if wav.dim() == 3:
+            if wav.shape[1] != 1:
+                raise ValueError(f"Only single channel is supported. You have {wav.shape[1]}")
+            wav = wav[:, 0, :].contiguous()
+        if wav.dim() != 2:
+            raise ValueError("wav must be (B, S) or (B, 1, S)")
+        return wav
+
+    def _sincnet_train_ws(self, h, B: int, S: int):
+        self._check(self.lib.uvad_sincnet_train_configure(self.ctx, C.byref(h["cfg"])))   # host only: the context serves any number of handles
+        need = int(self.lib.uvad_sincnet_train_ws_bytes(self.ctx, B, S))
+        if need == 0:
+            raise ValueError(f"uvad_sincnet_train does not serve B = {B}, S = {S} (at least one frame; B x L_0 <= 2^31 - 1; <= 65535 segments)")
+        if h["ws"] is None or h["ws"].numel() < need:
+            h["ws"] = torch.zeros(need, dtype=torch.uint8, device=self.device)
+
+    def sincnet_train_forward(self, h, wav: "torch.Tensor") -> "torch.Tensor":
+        """The front end's forward pass with the state's master weights (uvad_sincnet_train_forward), keeping the activations in the
+        handle's workspace: wav (B, S) or (B, 1, S) f32 on the GPU -> feats (B, T, c3), what lstm_train_forward takes as x_in.  No copy
+        to the host and no synchronisation."""
+        with torch.cuda.device(self.device):
+            wav = self._sincnet_train_wav(wav)
+            B, S = wav.shape
+            self._sincnet_train_ws(h, B, S)
+            T = int(self.lib.uvad_sincnet_num_frames(self.ctx, S))
+            feats = torch.empty((B, T, self._sn_c.c3), dtype=torch.float32, device=self.device)
+            self._check(self.lib.uvad_sincnet_train_forward(self.ctx, wav.data_ptr(), B, S, feats.data_ptr(), h["state"].data_ptr(), h["state"].numel(),
+                                                            h["ws"].data_ptr(), h["ws"].numel(), self._stream()))
+            h["_keep"] = (wav, feats)
+            return feats
+
+    def sincnet_train_backward(self, h, wav: "torch.Tensor", dfeats: "torch.Tensor"):
+        """The backward pass from dfeats (B, T, c3), lstm_train_backward's grad_in (the gradient of the summed loss), through the
+        activations the last sincnet_train_forward of this handle kept (uvad_sincnet_train_backward): adds the gradients and the B T
+        frames into the state."""
+        with torch.cuda.device(self.device):
+            wav, dfeats = self._sincnet_train_wav(wav), self._dev_f32(dfeats, "dfeats")
+            B, S = wav.shape
+            T = int(self.lib.uvad_sincnet_num_frames(self.ctx, S))
+            if tuple(dfeats.shape) != (B, T, self._sn_c.c3):
+                raise ValueError(f"dfeats has shape {tuple(dfeats.shape)}, expected {(B, T, self._sn_c.c3)}")
+            self._sincnet_train_ws(h, B, S)
+            self._check(self.lib.uvad_sincnet_train_backward(self.ctx, wav.data_ptr(), dfeats.data_ptr(), B, S, h["state"].data_ptr(),
+                                                             h["state"].numel(), h["ws"].data_ptr(), h["ws"].numel(), self._stream()))
+            h["_keep_b"] = (wav, dfeats)
+
+    def sincnet_train_apply(self, h):
+        """One Adam step from the accumulated gradients divided by the accumulated frame count (uvad_sincnet_train_apply)."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_sincnet_train_configure(self.ctx, C.byref(h["cfg"])))
+            self._check(self.lib.uvad_sincnet_train_apply(self.ctx, h["state"].data_ptr(), h["state"].numel(), self._stream()))
+
+    def _sincnet_train_block(self, h, which: int) -> np.ndarray:
+        self._check(self.lib.uvad_sincnet_train_read(self.ctx, h["state"].data_ptr(), h["state"].numel(), which, h["out"].data_ptr(), self._stream()))
+        return h["out"].cpu().numpy().copy()
+
+    def sincnet_train_read(self, h) -> dict:
+        """Copy the state to the host (synchronises) -> {"weights", "grad", "m", "v": {torch key: tensor}, "filters" (the bank of the last
+        forward call, (n_filters, kernel_size)), "frames", "step", "bias_correction1", "bias_correction2" (1 - beta^step)}."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_sincnet_train_configure(self.ctx, C.byref(h["cfg"])))
+            out = {}
+            for name, which in (("weights", _lib.HEAD_TRAIN_MASTERS), ("grad", _lib.HEAD_TRAIN_GRAD), ("m", _lib.HEAD_TRAIN_M), ("v", _lib.HEAD_TRAIN_V)):
+                flat, off, d = self._sincnet_train_block(h, which), 0, {}
+                for key, shape in self.sincnet_train_keys(h["first_stage"]):
+                    cnt = int(np.prod(shape))
+                    d[key] = torch.from_numpy(flat[off:off + cnt].reshape(shape).copy())
+                    off += cnt
+                out[name] = d
+            nf, ks = self._sn_c.n_filters, self._sn_c.kernel_size
+            out["filters"] = torch.from_numpy(self._sincnet_train_block(h, _lib.SINCNET_TRAIN_FILTERS)[:nf * ks].reshape(nf, ks).copy())
+            w = self._sincnet_train_block(h, _lib.HEAD_TRAIN_SCALARS)[:_lib.HEAD_TRAIN_SCALAR_WORDS]
+        out["frames"] = int(w[2:4].view(np.uint64)[0])
+        out["step"] = int(w[4:6].view(np.uint64)[0])
+        out["bias_correction1"], out["bias_correction2"] = float(w[6]), float(w[7])
+        return out
+
+    def sincnet_train_state_dict(self, h) -> dict:
+        """The adapted SincNet tensors keyed by torch key (reference names, ``sincnet.`` prefix), ready to merge into a checkpoint
+        (synchronises)."""
+        return self.sincnet_train_read(h)["weights"]
+
+    def sincnet_train_commit(self, h):
+        """Make this runtime serve the adapted front end (uvad_sincnet_train_commit: synchronises, re-finalizes; the bank served is the one
+        the last forward call ran).  Graphs captured before are stale, as after load_state_dict."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_sincnet_train_configure(self.ctx, C.byref(h["cfg"])))
+            self._check(self.lib.uvad_sincnet_train_commit(self.ctx, h["state"].data_ptr(), h["state"].numel()))
             self._weights_gen = getattr(self, "_weights_gen", 0) + 1
 
     # ------------------------------------------------------------------ scoring against reference labels (uvad_score_*)

@@ -864,9 +864,89 @@ def adapt_vad(**kwargs):
     return out
 
 
+def _train_vad_sincnet(kwargs, src, val_paths, val_labels, model, rt, device, seed, sr):
+    """train_vad for the waveform PyanNet: each recording's waveform is cached on the device and cut into windows of ``window_seconds``;
+    a window's labels are its own supervisions_feature_mask (supervision_frames, geometry "sincnet", over the window's own frames).
+    The front end normalises over whole rows, so a batch holds rows of ONE length: full windows together, tails in batches of their
+    own; a tail shorter than the receptive field (991 samples) has no frame and is skipped.  Shuffle, validation and the checkpoint are
+    train_vad's."""
+    from .postprocess import read_label_file, supervision_frames
+    net = model.model
+
+    def labels_of(items, t0, n):
+        """(1, T) labels of the n samples from t0 seconds on, from the recording's intervals."""
+        T, dur = net.num_frames(n), n / float(sr)
+        own = [(a - t0, b - t0) for a, b in items if b - t0 > 0 and a - t0 < dur]
+        table = supervision_frames(own, dur, geometry="sincnet", num_frames=T)
+        iv = np.zeros((1, max(len(table), 1), 2), np.int32)
+        iv[0, :len(table)] = table
+        return rt.intervals_to_labels(iv, [len(table)], T).clone()
+
+    def recording(path, label_path):
+        pcm = torch.from_numpy(np.array(_wav_recordings(path, "first", rt, sr)[0]["pcm"])).to(device)[None].float()
+        if net.num_frames(pcm.shape[1]) < 1:
+            raise ValueError(f"{path}: shorter than the receptive field (991 samples)")
+        items = read_label_file(label_path)
+        return {"inputs": pcm, "is_voice": labels_of(items, 0.0, pcm.shape[1]), "items": items}
+
+    train = [recording(p, l) for p, l in zip(src["paths"], src["labels"])]
+    held = train if (val_paths, val_labels) == (list(src["paths"]), list(src["labels"])) else [recording(p, l) for p, l in zip(val_paths, val_labels)]
+    window_s = float(kwargs.get("window_seconds") or 5.0)
+    Wn = max(991, int(round(window_s * sr)))
+    windows, skipped = [], 0
+    for r, b in enumerate(train):
+        S = b["inputs"].shape[1]
+        for s0 in range(0, S, Wn):
+            n = min(Wn, S - s0)
+            if net.num_frames(n) < 1:
+                skipped += 1
+                continue
+            windows.append((r, s0, n, labels_of(b["items"], s0 / float(sr), n)))
+    if skipped:
+        print(f"train_vad: {skipped} tail window(s) shorter than the receptive field (991 samples) skipped")
+    rows = max(1, int(float(kwargs["max_duration"]) / window_s))
+    epochs, every = int(kwargs.get("max_epochs", 10)), max(1, int(kwargs.get("check_val_every_n_epoch", 1)))
+    accumulate = max(1, int(kwargs.get("accumulate_grad_batches", 1)))
+    out = {"train_loss": [], "val_loss": [], "val_metrics": None}
+
+    def validate(epoch):
+        model.train_commit()
+        for i, b in enumerate(held):
+            model.validation_step({"inputs": b["inputs"], "is_voice": b["is_voice"]}, i)
+        out["val_metrics"] = model.validation_metrics(reset=True)
+        out["val_loss"].append((epoch, out["val_metrics"]["val_loss"]))
+        print(f"epoch {epoch}: val_loss {out['val_metrics']['val_loss']:.6f}")
+
+    step = 0
+    for epoch in range(1, epochs + 1):
+        order = torch.randperm(len(windows), generator=torch.Generator().manual_seed(seed + epoch)).tolist()
+        by_len = {}
+        for k in order:                                               # rows of one length per batch, in the shuffled order
+            by_len.setdefault(windows[k][2], []).append(k)
+        losses = []
+        for n, ks in by_len.items():
+            for i in range(0, len(ks), rows):
+                picks = [windows[k] for k in ks[i:i + rows]]
+                x = torch.stack([train[r]["inputs"][0, s0:s0 + n] for r, s0, _, _ in picks])
+                y = torch.cat([lab for _, _, _, lab in picks])
+                losses.append(model.train_step({"inputs": x, "is_voice": y}, step, accumulate=accumulate))
+                step += 1
+        out["train_loss"].append(float(torch.stack(losses).mean()))
+        print(f"epoch {epoch}: train_loss {out['train_loss'][-1]:.6f}")
+        if epoch % every == 0 or epoch == epochs:
+            validate(epoch)
+    path = os.path.join(kwargs.get("experiments_dir", "."), f"checkpoint-epoch={epochs:02d}.ckpt")
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    out["global_step"] = step // accumulate
+    torch.save({"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "epoch": epochs, "global_step": out["global_step"]}, path)
+    out["checkpoint_path"] = path
+    return out
+
+
 def train_vad(**kwargs):
     """Training from initialisation on wav files and label files in adapt_vad's ``input`` format (``function == "train"``): the
-    accelerated form of the reference's src/scripts/train.py for ``feature_extractor = "fbank"``.  The PyanNet2 is built under
+    accelerated form of the reference's src/scripts/train.py for ``feature_extractor = "fbank"`` (PyanNet2, below) and
+    ``feature_extractor = "sincnet"`` with ``model_name = "PyanNet"`` (_train_vad_sincnet: waveform windows).  The PyanNet2 is built under
     ``torch.manual_seed(seed)`` -- torch's own initialisation, not seed_weights -- or loaded from ``checkpoint_path`` when
     ``load_checkpoint`` is set.  The log-mel features of every recording are computed once and cached, cut into windows of
     ``window_seconds`` (default 5.0; every tail is kept as a shorter row with its length), and batched up to ``max_duration`` seconds per
@@ -884,23 +964,27 @@ def train_vad(**kwargs):
     val_paths, val_labels = list(src.get("val_paths") or src["paths"]), list(src.get("val_labels") or src["labels"])
     if len(val_paths) != len(val_labels):
         raise ValueError("train_vad needs one label file per held-out path")
-    if kwargs["feature_extractor"] != "fbank" or kwargs["model_name"] != "PyanNet2":
-        raise NotImplementedError("train_vad trains a PyanNet2 on log-mel features (feature_extractor = 'fbank'): the gradients into the "
-                                  "SincNet front end are not on the device")
+    if (kwargs["feature_extractor"], kwargs["model_name"]) not in (("fbank", "PyanNet2"), ("sincnet", "PyanNet")):
+        raise NotImplementedError("train_vad trains a PyanNet2 on log-mel features (feature_extractor = 'fbank') or a PyanNet on the raw "
+                                  "waveform (feature_extractor = 'sincnet')")
+    sincnet = kwargs["feature_extractor"] == "sincnet"
     seed, sr = int(kwargs["seed"]), 16000
     torch.manual_seed(seed)
     device = _resolve_device(kwargs["device"])
     lr = float(kwargs.get("learning_rate", 1e-3))
     if kwargs["load_checkpoint"]:
-        model = VadModel.load_from_checkpoint(checkpoint_path=kwargs["checkpoint_path"], model_name="PyanNet2", model_dict=dict(kwargs["model_dict"]),
-                                              learning_rate=lr)
+        model = VadModel.load_from_checkpoint(checkpoint_path=kwargs["checkpoint_path"], model_name=kwargs["model_name"],
+                                              model_dict=dict(kwargs["model_dict"]), learning_rate=lr)
     else:
-        model = VadModel(model_name="PyanNet2", model_dict=dict(kwargs["model_dict"]), learning_rate=lr)
-    model = model.to(device).eval()      # the torch modules serve inference only; training runs in uvad_lstm_train_* / uvad_head_train_*
+        model = VadModel(model_name=kwargs["model_name"], model_dict=dict(kwargs["model_dict"]), learning_rate=lr)
+    model = model.to(device).eval()      # the torch modules serve inference only; training runs in uvad_*_train_*
     net = model.model
-    net.attach_fbank(FbankConfig(sampling_rate=sr, num_filters=net.encoding_dim, window_type=kwargs.get("window_type", "povey"),
-                                 frame_shift=kwargs["frame_shift"], device="cuda"))
+    if not sincnet:
+        net.attach_fbank(FbankConfig(sampling_rate=sr, num_filters=net.encoding_dim, window_type=kwargs.get("window_type", "povey"),
+                                     frame_shift=kwargs["frame_shift"], device="cuda"))
     rt = net.runtime(device)
+    if sincnet:
+        return _train_vad_sincnet(kwargs, src, val_paths, val_labels, model, rt, device, seed, sr)
 
     def recording(path, label_path):
         pcm = torch.from_numpy(_wav_recordings(path, "first", rt, sr)[0]["pcm"]).to(device)[None]
