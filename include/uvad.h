@@ -1356,6 +1356,76 @@ int uvad_sincnet_train_apply(uvad_ctx *, void *d_state, size_t state_bytes, void
 int uvad_sincnet_train_read(uvad_ctx *, const void *d_state, size_t state_bytes, int which, float *d_out, void *stream);
 int uvad_sincnet_train_commit(uvad_ctx *, const void *d_state, size_t state_bytes);
 
+/* ---- Noise mixing of training batches on the device -----------------------------------------------------------------------------------------
+ * Every training recipe of the reference runs cuts.mix(noise_cuts, snr = (10, 20), mix_prob = 0.5, preserve_id = "left") on its training
+ * phase (src/datasets/<corpus>/utils.py, enable_musan), once, on the host, before the features are stored.  Here the mix is a stage in front of uvad_fbank_lens /
+ * uvad_sincnet_train_forward and is drawn anew for every batch: the draws come from the generator of the dropout stage above, the draw
+ * ordinal lives on the device, so one captured graph draws a fresh mix per replay.  Not here: parity with lhotse itself, random start
+ * offsets inside a clip, reverberation, speed perturbation.
+ *
+ * Noise bank: one caller-owned device buffer d_bank of f32 samples, n_clips clips back to back; h_clip_first [n_clips + 1] (host, int64)
+ *   are the clips' first samples, h_clip_first[0] = 0, every clip at least 1 sample.  The state keeps the pointer: the bank must stay where
+ *   it is and unchanged while the state is in use.
+ * Configuration: mix_prob in [0, 1]; snr_steps = Q >= 1 and the host table h_amp [Q] of doubles, the noise-to-speech AMPLITUDE ratios (the
+ *   caller computes them: 10^(-(lo + (hi - lo) (q + 0.5) / Q) / 20) for Q steps over lo .. hi dB; no transcendental function runs on the
+ *   device); max_seg in [1, UVAD_MIX_MAX_SEG]; seed.
+ * Batch: d_in [B][S], fmt UVAD_INGEST_F32 or UVAD_INGEST_I16 (read as q / 32768, as uvad_sincnet_i16); len_b = clamp(d_nsamp[b], 0, S) as
+ *   uvad_fbank_lens takes it (S when d_nsamp is NULL); d_out [B][S] f32, for f32 input d_out == d_in is allowed (in place).
+ *
+ * Energy: E(x, n) = (sum_i (double)x_i (double)x_i) / n over the n valid samples, 0 for n = 0; every product is exact in double.  The
+ *   ORDER of the sum is a function of (samples, n) alone -- not of B, S, the grid or neighbouring rows: lane t = (i / 4) mod 1024 adds the
+ *   squares of its samples in increasing i, starting from +0 (1024 lanes; samples 4 t .. 4 t + 3, then 4096 + 4 t .. and so on); then within
+ *   each run of 64 lanes lane t += lane t + o for o = 32, 16, 8, 4, 2, 1; then the 16 run sums w_j += w_{j + o} for o = 8, 4, 2, 1; w_0 is
+ *   divided by (double)n, one correctly rounded division.  No floating-point atomics.  A clip's energy is over the WHOLE clip (as lhotse's
+ *   AudioMixer takes it before truncation), computed by uvad_mix_reset in the same order.
+ * Draws: Philox4x32-10 exactly as the dropout block above defines it, counter = (row b, segment k, draw_lo, draw_hi), key = (seed_lo,
+ *   seed_hi); row b is the row's index in the batch (uvad_mix_apply: row0 + b), as a 32-bit word.
+ *     segment 0, word 0: the row is mixed iff (uint64)w0 < floor(mix_prob 2^32), a 64-bit compare: 1.0 always mixes, 0.0 never does;
+ *     segment 0, word 1: q = (w1 Q) >> 32, one SNR per row, as in lhotse;
+ *     segment k, word 2: clip = (w2 n_clips) >> 32;   word 3 is reserved.
+ * Plan: segments are laid end to end from sample 0; segment k covers min(clip length, len_b - offset) samples, from the clip's first sample.
+ *   Drawing stops when the row is covered or after max_seg segments; what is left stays clean.
+ *   gain_k = (float)(amp[q] sqrt(E_row / E_clip)): the division and the square root correctly rounded double operations, the product one
+ *   double rounding, then one rounding to f32; +0 when E_clip == 0 or E_row == 0.  A row of length 0, or one not mixed, has no segments.
+ * Output: out = fl32(x + fl32(gain noise)) inside a segment: two f32 roundings, no fused multiply-add.  Samples outside every segment, and
+ *   whole unmixed rows, are the input's f32 value bit for bit (a NaN passes through).  Samples past a row's length are +0 and are never read.
+ * Draw ordinal: a 64-bit count at byte 56 of the state (zeroed by reset).  uvad_mix_step takes draw = the count and advances it by one, on
+ *   the device, in a single thread of its first kernel, whatever mix_prob is: a replayed graph draws anew and micro-batches differ.
+ * Plan record: d_plan (may be NULL) [B][UVAD_MIX_PLAN_HEAD + UVAD_MIX_SEG_WORDS max_seg] int32: {mixed (0 / 1: the draw's decision), q,
+ *   nseg, 0}, then per segment {clip, dst offset, count, gain (the f32's bits)}; slots past nseg are zeros.  For logging and the tests.
+ * State (uvad_mix_state_bytes; it does not depend on the bank's size): a 256-byte header {u32 magic, i32 n_clips, Q, max_seg; byte 16 u64
+ *   floor(mix_prob 2^32); byte 24 u64 seed; byte 32 i64 samples in the bank; byte 56 u64 draw ordinal} | clip_first [n_clips + 1] int64 |
+ *   clip energies [n_clips] f64 | amp [Q] f64, every part padded to 256 bytes.
+ * Workspace (uvad_mix_ws_bytes(B, max_seg)): 256-byte header {byte 0 u64 the call's draw, byte 8 i64 row0} | row energies [B] f64 (from
+ *   byte 256) | the plan [B][...] as above, every part padded to 256 bytes.
+ * uvad_mix_reset uploads the tables, computes every clip's energy on the device and zeroes the draw ordinal; it synchronises the stream and
+ *   is not for graph capture.  uvad_mix_step allocates nothing, never synchronises and can be captured.  uvad_mix_apply is the same step
+ *   with the draw and the first row's index given and no state update: the same arguments give the same bytes, and row b of a batch equals
+ *   a one-row call with row0 = b.  The three share every kernel.
+ * Refusals (nothing enqueued).  UVAD_E_ARG: NULL ctx / cfg / h_amp / d_bank / h_clip_first / d_in / d_out / d_state / d_ws; d_state or
+ *   d_ws not 16-byte aligned, d_bank / d_in / d_out / d_plan not aligned to their element; mix_prob outside [0, 1] or not finite; Q < 1 or > 2^24; an
+ *   amplitude not finite or negative; max_seg outside [1, 64]; n_clips < 1; h_clip_first[0] != 0, an empty clip or a non-monotone table;
+ *   B < 1; S < 1 or S > 2^31 - 1; state_bytes / ws_bytes below the helpers; an unknown fmt; int16 input with d_out == d_in.
+ *   UVAD_E_STATE: a state that was never reset.  The size helpers return 0 on a bad argument. */
+#define UVAD_MIX_MAX_SEG 64
+#define UVAD_MIX_PLAN_HEAD 4
+#define UVAD_MIX_SEG_WORDS 4
+typedef struct {
+    float mix_prob;          /* the share of rows that get noise, [0, 1] */
+    int snr_steps;           /* Q: entries of h_amp */
+    const double *h_amp;     /* host: noise-to-speech amplitude ratio of SNR step q */
+    int max_seg;             /* noise clips laid end to end per row, at most */
+    uint64_t seed;
+} uvad_mix_cfg;
+size_t uvad_mix_state_bytes(const uvad_mix_cfg *, int n_clips);
+size_t uvad_mix_ws_bytes(int B, int max_seg);
+int uvad_mix_reset(uvad_ctx *, void *d_state, size_t state_bytes, const uvad_mix_cfg *, const float *d_bank, const int64_t *h_clip_first,
+                   int n_clips, void *stream);
+int uvad_mix_step(uvad_ctx *, const void *d_in, int fmt, int B, int64_t S, const int64_t *d_nsamp, float *d_out, int32_t *d_plan,
+                  void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream);
+int uvad_mix_apply(uvad_ctx *, const void *d_in, int fmt, int B, int64_t S, const int64_t *d_nsamp, float *d_out, int32_t *d_plan,
+                   int64_t row0, uint64_t draw, void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream);
+
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;
  *   1  (default) f32-accurate on the f16 matrix cores: weights scaled by a power of two and split on the host into THREE

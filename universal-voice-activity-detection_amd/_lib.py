@@ -70,6 +70,14 @@ class SincNetTrainCfg(C.Structure):  # uvad_sincnet_train_cfg (24 bytes)
 SINCNET_TRAIN_FILTERS = 5        # `which` of uvad_sincnet_train_read: the bank of the last forward call
 
 
+INGEST_F32, INGEST_I16 = 0, 1    # `fmt` of uvad_mix_step / uvad_mix_apply (UVAD_INGEST_*)
+MIX_MAX_SEG, MIX_PLAN_HEAD, MIX_SEG_WORDS = 64, 4, 4     # the plan record of uvad_mix_step: int32 words per row = head + seg words x max_seg
+
+
+class MixCfg(C.Structure):       # uvad_mix_cfg (32 bytes)
+    _fields_ = [("mix_prob", C.c_float), ("snr_steps", C.c_int), ("h_amp", C.POINTER(C.c_double)), ("max_seg", C.c_int), ("seed", C.c_uint64)]
+
+
 class CutsCfg(C.Structure):
     _fields_ = [("pad", C.c_int), ("max_len", C.c_int), ("min_len", C.c_int), ("hop", C.c_int), ("lead", C.c_int), ("tail", C.c_int)]
 
@@ -253,6 +261,13 @@ SIGNATURES = {
     "uvad_sincnet_train_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_sincnet_train_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     "uvad_sincnet_train_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "uvad_mix_state_bytes": (C.c_size_t, [C.POINTER(MixCfg), C.c_int]),
+    "uvad_mix_ws_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "uvad_mix_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(MixCfg), C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
+    "uvad_mix_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_mix_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64,
+                                 C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_cuts_max_per_row": (C.c_int, [C.POINTER(CutsCfg), C.c_int]),
     "uvad_cuts_max_samples": (C.c_int64, [C.POINTER(CutsCfg), C.c_int64]),
     "uvad_cuts_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),

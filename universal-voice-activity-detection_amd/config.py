@@ -95,6 +95,16 @@ def load_config() -> ConfigDict:
     cfg.adapted_checkpoint_path = ""    # "" = experiments_dir/adapted.ckpt
     cfg.adapt_lstm_layers = 0           # top LSTM layers that learn with the head (VadModel.adapt_step); 0 = the head alone, as before
 
+    # function == "train": noise augmentation of the training phase, drawn anew for every batch on the device (uvad_mix_step; validation is
+    # never mixed).  noise = {"paths": [wav files], "snr": (10, 20), "mix_prob": 0.5} or None.  The reference's keys give the same:
+    # enable_musan (its default) with musan.paths, the noise recordings -- an empty list (no corpus ships) trains on clean audio
+    cfg.noise = None
+    cfg.enable_musan = True
+    cfg.musan = ConfigDict()
+    cfg.musan.paths = []
+    cfg.musan.snr = (10, 20)
+    cfg.musan.mix_prob = 0.5
+
     cfg.predict_output_dir = os.environ.get("UVAD_PREDICT_DIR", "")   # "" = do not write files
     cfg.window_type = "povey"   # lhotse default; BASELINE cfg 2 uses "hamming"
 

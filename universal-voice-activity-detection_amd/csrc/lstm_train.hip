@@ -31,6 +31,7 @@
 // No floating-point atomics: the same calls give the same bits.  Every backward kernel checks the workspace header on the device and does
 // nothing under a mismatch.  Contraction is off (ht_kernels.h and the Makefile's flag); the fused multiply-adds below are explicit.
 #include "ht_kernels.h"
+#include "philox.h"
 
 namespace uvad {
 
@@ -103,17 +104,7 @@ __global__ __launch_bounds__(256) void lt_prep_kernel(LstmTrainShape q, void *st
     }
 }
 
-// Philox4x32-10 (Salmon et al., Random123): ten rounds, the key bumped after each round
-__device__ __forceinline__ uint4 lt_philox(uint4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-        c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return c;
-}
+// lt_philox: Philox4x32-10, philox.h (shared with mix.hip)
 
 // head != nullptr: the record of the workspace header (thr == 0 there: nothing to do), under the state's magic and the guard;
 // head == nullptr: the stand-alone call, everything in the arguments

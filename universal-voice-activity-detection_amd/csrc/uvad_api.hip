@@ -107,6 +107,8 @@ struct GatePool { int B = 0, unit_bytes = 0, history = 0; };
 struct GateGroupPool { int G = 0, N = 0, unit_bytes = 0, history = 0, best_history = 0; };
 // a scoring state (uvad_score_*): the configuration's n_points and bins at its reset (the device header holds the same)
 struct ScoreState { int n_points = 0, bins = 0; };
+// a noise-mix state (uvad_mix_*): the caller's bank and what reset fixed (the device header holds the same)
+struct MixState { const float *bank = nullptr; int n_clips = 0, Q = 0, max_seg = 0; };
 
 struct uvad_ctx {
     std::map<void *, StreamCounters> streams;   // host mirror of the lock-step stream groups, keyed by d_state
@@ -135,6 +137,7 @@ struct uvad_ctx {
     bool has_snt = false;                       // uvad_sincnet_train_configure: the optimiser, first_stage and the packed shape of the front end
     uvad_sincnet_train_cfg snq{};
     SincTrainShape snts{};
+    std::map<void *, MixState> mixes;           // ... and of the noise-mix states (uvad_mix_*)
     int device = 0, n_cu = 256;
     bool has_fb = false, has_model = false, finalized = false, tables_set = false;
     uvad_fbank_cfg fb{};
@@ -3714,6 +3717,103 @@ int uvad_sincnet_train_commit(uvad_ctx *c, const void *d_state, size_t state_byt
         if (int r = uvad_set_weight(c, "sincnet.conv1d.0.filters", w.data() + q.off_bank, shape, 3)) return r;
     }
     return uvad_finalize(c);
+}
+
+// ---- noise mixing of training batches (mix.hip) ------------------------------------------------------------------------------------------
+// nullptr: the configuration is in range; else the word uvad_last_error names
+static const char *mix_cfg_error(const uvad_mix_cfg *q) {
+    if (!q) return "cfg is NULL";
+    if (!std::isfinite(q->mix_prob) || q->mix_prob < 0.0f || q->mix_prob > 1.0f) return "mix_prob must lie in [0, 1]";
+    if (q->snr_steps < 1 || q->snr_steps > (1 << 24)) return "snr_steps must lie in [1, 2^24]";
+    if (!q->h_amp) return "h_amp is NULL";
+    for (int i = 0; i < q->snr_steps; ++i)
+        if (!std::isfinite(q->h_amp[i]) || q->h_amp[i] < 0.0) return "every amplitude must be finite and >= 0";
+    if (q->max_seg < 1 || q->max_seg > MIX_MAX_SEG) return "max_seg must lie in [1, 64]";
+    return nullptr;
+}
+
+size_t uvad_mix_state_bytes(const uvad_mix_cfg *q, int n_clips) {
+    if (mix_cfg_error(q) || n_clips < 1) return 0;
+    return mix_layout(n_clips, q->snr_steps).total;
+}
+
+size_t uvad_mix_ws_bytes(int B, int max_seg) {
+    if (B < 1 || max_seg < 1 || max_seg > MIX_MAX_SEG) return 0;
+    return mix_ws(B, max_seg).total;
+}
+
+int uvad_mix_reset(uvad_ctx *c, void *d_state, size_t state_bytes, const uvad_mix_cfg *q, const float *d_bank, const int64_t *h_clip_first,
+                   int n_clips, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_state || !d_bank || !h_clip_first) return fail(c, UVAD_E_ARG, "uvad_mix_reset: bad argument");
+    if (const char *e = mix_cfg_error(q)) return fail(c, UVAD_E_ARG, std::string("uvad_mix_reset: ") + e);
+    if (n_clips < 1) return fail(c, UVAD_E_ARG, "uvad_mix_reset: n_clips must be at least 1");
+    if (reinterpret_cast<uintptr_t>(d_state) % 16) return fail(c, UVAD_E_ARG, "uvad_mix_reset: d_state must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_bank) % 4) return fail(c, UVAD_E_ARG, "uvad_mix_reset: d_bank must be 4-byte aligned");
+    if (h_clip_first[0] != 0) return fail(c, UVAD_E_ARG, "uvad_mix_reset: h_clip_first[0] must be 0");
+    for (int i = 0; i < n_clips; ++i)
+        if (h_clip_first[i + 1] <= h_clip_first[i])
+            return fail(c, UVAD_E_ARG, "uvad_mix_reset: h_clip_first must increase: clip " + std::to_string(i) + " is empty");
+    const MixLayout l = mix_layout(n_clips, q->snr_steps);
+    if (state_bytes < l.total) return fail(c, UVAD_E_ARG, "uvad_mix_reset: state too small: need " + std::to_string(l.total) + " bytes");
+    std::vector<char> host(l.total, 0);
+    MixHeader h{};
+    h.magic = MIX_MAGIC; h.n_clips = n_clips; h.Q = q->snr_steps; h.max_seg = q->max_seg;
+    h.thr = (unsigned long long)__builtin_floor((double)q->mix_prob * 4294967296.0);
+    h.seed = q->seed; h.bank_total = h_clip_first[n_clips]; h.draws = 0;
+    std::memcpy(host.data(), &h, sizeof(h));
+    std::memcpy(host.data() + l.off_first, h_clip_first, ((size_t)n_clips + 1) * 8);
+    std::memcpy(host.data() + l.off_amp, q->h_amp, (size_t)q->snr_steps * 8);
+    c->mixes.erase(d_state);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));      // what the stream still does to this state comes first
+    HIPCHK(c, hipMemcpy(d_state, host.data(), host.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, launch_mix_clip_energies(d_bank, d_state, n_clips, q->snr_steps, (hipStream_t)stream));
+    HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));
+    MixState g;
+    g.bank = d_bank; g.n_clips = n_clips; g.Q = q->snr_steps; g.max_seg = q->max_seg;
+    c->mixes[d_state] = g;
+    return UVAD_OK;
+}
+
+static int mix_call(uvad_ctx *c, const char *fn, const void *d_in, int fmt, int B, int64_t S, const int64_t *d_nsamp, float *d_out, int32_t *d_plan,
+                    bool take, int64_t row0, uint64_t draw, void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    const std::string f(fn);
+    if (!d_in || !d_out || !d_state || !d_ws) return fail(c, UVAD_E_ARG, f + ": bad argument");
+    if (fmt != UVAD_INGEST_F32 && fmt != UVAD_INGEST_I16) return fail(c, UVAD_E_ARG, f + ": fmt must be UVAD_INGEST_F32 or UVAD_INGEST_I16");
+    if (B < 1) return fail(c, UVAD_E_ARG, f + ": B must be at least 1");
+    if (S < 1 || S > MIX_MAX_S) return fail(c, UVAD_E_ARG, f + ": S must lie in [1, 2^31 - 1]");
+    if (reinterpret_cast<uintptr_t>(d_state) % 16 || reinterpret_cast<uintptr_t>(d_ws) % 16)
+        return fail(c, UVAD_E_ARG, f + ": d_state and d_ws must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_in) % (fmt == UVAD_INGEST_F32 ? 4 : 2) || reinterpret_cast<uintptr_t>(d_out) % 4 ||
+        reinterpret_cast<uintptr_t>(d_plan) % 4 || reinterpret_cast<uintptr_t>(d_nsamp) % 8)
+        return fail(c, UVAD_E_ARG, f + ": d_in, d_out, d_plan and d_nsamp must be aligned to their element");
+    if (fmt == UVAD_INGEST_I16 && d_in == static_cast<const void *>(d_out)) return fail(c, UVAD_E_ARG, f + ": int16 input cannot be mixed in place");
+    auto it = c->mixes.find(d_state);
+    if (it == c->mixes.end()) return fail(c, UVAD_E_STATE, f + ": call uvad_mix_reset on this state first");
+    const MixState &g = it->second;
+    const size_t need_state = mix_layout(g.n_clips, g.Q).total, need_ws = mix_ws(B, g.max_seg).total;
+    if (state_bytes < need_state) return fail(c, UVAD_E_ARG, f + ": state too small: need " + std::to_string(need_state) + " bytes");
+    if (ws_bytes < need_ws) return fail(c, UVAD_E_ARG, f + ": workspace too small: need " + std::to_string(need_ws) + " bytes");
+    MixArgs a{};
+    a.in = d_in; a.fmt = fmt; a.B = B; a.S = S; a.nsamp = reinterpret_cast<const long long *>(d_nsamp);
+    a.out = d_out; a.plan = d_plan; a.bank = g.bank; a.state = d_state; a.ws = d_ws;
+    a.n_clips = g.n_clips; a.Q = g.Q; a.max_seg = g.max_seg;
+    a.take = take; a.draw = draw; a.row0 = row0;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_mix(a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_mix_step(uvad_ctx *c, const void *d_in, int fmt, int B, int64_t S, const int64_t *d_nsamp, float *d_out, int32_t *d_plan, void *d_state,
+                  size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream) {
+    return mix_call(c, "uvad_mix_step", d_in, fmt, B, S, d_nsamp, d_out, d_plan, true, 0, 0, d_state, state_bytes, d_ws, ws_bytes, stream);
+}
+
+int uvad_mix_apply(uvad_ctx *c, const void *d_in, int fmt, int B, int64_t S, const int64_t *d_nsamp, float *d_out, int32_t *d_plan, int64_t row0,
+                   uint64_t draw, void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream) {
+    return mix_call(c, "uvad_mix_apply", d_in, fmt, B, S, d_nsamp, d_out, d_plan, false, row0, draw, d_state, state_bytes, d_ws, ws_bytes, stream);
 }
 
 // ---- speech cuts (cuts.hip) --------------------------------------------------------------------------------------------------------------

@@ -897,4 +897,37 @@ hipError_t launch_sinc_train_bank(const SincTrainShape &q, void *state, hipStrea
 hipError_t launch_sinc_train_apply(const SincTrainShape &q, const HeadTrainAdam &o, void *state, hipStream_t s);
 hipError_t launch_sinc_train_read(const SincTrainShape &q, const void *state, int which, float *out, hipStream_t s);   // which 5: the bank
 
+// ---- mix.hip: noise mixing for training batches (uvad_mix_*, include/uvad.h): row energies, the plan of every row, the mix pass ----
+// State: MixHeader (256 bytes) | clip_first [n_clips + 1] int64 | clip energies [n_clips] f64 | amp [Q] f64; every part 256-byte aligned.
+// Workspace: MixWsHead (256 bytes: the call's draw and first row index) | row energies [B] f64 | the plan [B][4 + 4 max_seg] int32; every part
+//            256-byte aligned.  The plan row is the record of include/uvad.h; the mix pass reads it from here, d_plan is a copy.
+constexpr unsigned MIX_MAGIC = 0x55564D58u;          // "UVMX"
+constexpr int MIX_MAX_SEG = 64;                      // UVAD_MIX_MAX_SEG
+constexpr int MIX_PLAN_HEAD = 4, MIX_SEG_WORDS = 4;  // words of a plan row: {mixed, q, nseg, 0}, then {clip, dst offset, count, gain bits} per segment
+constexpr int MIX_LANES = 1024, MIX_CHUNK = 4 * MIX_LANES;   // the energy order of include/uvad.h: lanes per row, samples per pass of the lanes
+constexpr long long MIX_MAX_S = 2147483647LL;        // offsets and counts of the plan are int32
+struct MixHeader {
+    unsigned magic; int n_clips, Q, max_seg;
+    unsigned long long thr;                          // byte 16: floor(mix_prob 2^32), 0 .. 2^32
+    unsigned long long seed;                         // byte 24
+    long long bank_total;                            // byte 32: samples of the bank = clip_first[n_clips]
+    int reserved0[4];
+    unsigned long long draws;                        // byte 56: steps drawn so far (the draw ordinal), where the training states keep theirs
+    int reserved[48];
+};                                                   // 256 bytes
+struct MixWsHead { unsigned long long draw; long long row0; int reserved[60]; };   // 256 bytes: what the call's first kernel recorded
+struct MixLayout { size_t off_first, off_energy, off_amp, total; };               // the state
+struct MixWs { size_t off_energy, off_plan, total; int plan_words; };             // the workspace
+struct MixArgs {
+    const void *in; int fmt; int B; long long S; const long long *nsamp;
+    float *out; int *plan;                           // plan: the caller's copy, may be null
+    const float *bank; void *state; void *ws;
+    int n_clips, Q, max_seg;
+    bool take; unsigned long long draw; long long row0;   // take: the draw is the state's ordinal, which advances; else `draw`
+};
+MixLayout mix_layout(int n_clips, int Q);
+MixWs mix_ws(int B, int max_seg);
+hipError_t launch_mix_clip_energies(const float *bank, void *state, int n_clips, int Q, hipStream_t s);
+hipError_t launch_mix(const MixArgs &a, hipStream_t s);
+
 }  // namespace uvad

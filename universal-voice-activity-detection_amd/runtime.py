@@ -1491,6 +1491,95 @@ class VadRuntime:
                                                     int(draw) & 0xFFFFFFFFFFFFFFFF, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, self._stream()))
             return out
 
+    # ------------------------------------------------------------------ noise mixing of training batches (uvad_mix_*)
+    @staticmethod
+    def mix_amp_table(snr, snr_steps: int) -> np.ndarray:
+        """The noise-to-speech amplitude ratios of snr_steps SNR steps over snr = (lo, hi) dB (a number: that one SNR)."""
+        lo, hi = (float(snr), float(snr)) if np.isscalar(snr) else (float(snr[0]), float(snr[1]))
+        Q = int(snr_steps)
+        if Q < 1:
+            raise ValueError("snr_steps must be at least 1")
+        return np.array([10 ** (-(lo + (hi - lo) * (q + 0.5) / Q) / 20) for q in range(Q)], np.float64)
+
+    def mix_open(self, bank, clip_lengths, snr=(10, 20), mix_prob: float = 0.5, snr_steps: int = 1024, max_seg: int = 8, seed: int = 0):
+        """Allocate and reset a noise-mix state (uvad_mix_reset).  bank: the noise clips back to back, a 1-D f32 tensor (moved to this
+        device; the handle keeps it alive), clip_lengths: samples per clip.  snr (lo, hi) dB, mix_prob, max_seg and seed as
+        include/uvad.h; the amplitude table is mix_amp_table(snr, snr_steps).  The clip energies are computed on the device here."""
+        lens = [int(v) for v in clip_lengths]
+        if not lens or min(lens) < 1:
+            raise ValueError("every noise clip needs at least 1 sample")
+        if not 0.0 <= float(mix_prob) <= 1.0:
+            raise ValueError("mix_prob must lie in [0, 1]")
+        if not 1 <= int(max_seg) <= _lib.MIX_MAX_SEG:
+            raise ValueError(f"max_seg must lie in [1, {_lib.MIX_MAX_SEG}]")
+        first = np.zeros(len(lens) + 1, np.int64)
+        first[1:] = np.cumsum(lens)
+        amp = self.mix_amp_table(snr, snr_steps)
+        with torch.cuda.device(self.device):
+            bank = torch.as_tensor(bank, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
+            if bank.numel() != int(first[-1]):
+                raise ValueError(f"bank holds {bank.numel()} samples, the clip lengths add up to {int(first[-1])}")
+            cfg = _lib.MixCfg(float(mix_prob), len(amp), amp.ctypes.data_as(C.POINTER(C.c_double)), int(max_seg), int(seed) & 0xFFFFFFFFFFFFFFFF)
+            st = {"cfg": cfg, "amp": amp, "bank": bank, "first": first, "n_clips": len(lens), "max_seg": int(max_seg),
+                  "plan_words": _lib.MIX_PLAN_HEAD + _lib.MIX_SEG_WORDS * int(max_seg), "ws": None,
+                  "state": torch.zeros(int(self.lib.uvad_mix_state_bytes(C.byref(cfg), len(lens))), dtype=torch.uint8, device=self.device)}
+            self._check(self.lib.uvad_mix_reset(self.ctx, st["state"].data_ptr(), st["state"].numel(), C.byref(cfg), bank.data_ptr(),
+                                                first.ctypes.data_as(C.POINTER(C.c_int64)), len(lens), self._stream()))
+            return st
+
+    def mix_draws(self, st) -> int:
+        """How many steps the state has drawn: the 64-bit count at byte 56 (synchronises)."""
+        return int(st["state"][56:64].cpu().numpy().view(np.uint64)[0])
+
+    def mix_clip_energies(self, st) -> np.ndarray:
+        """The clips' energies as uvad_mix_reset computed them (synchronises)."""
+        off = 256 + (8 * (st["n_clips"] + 1) + 255) // 256 * 256
+        return st["state"][off:off + 8 * st["n_clips"]].cpu().numpy().view(np.float64).copy()
+
+    def mix_row_energies(self, st, B: int) -> np.ndarray:
+        """The row energies of the state's last step (synchronises)."""
+        return st["ws"][256:256 + 8 * B].cpu().numpy().view(np.float64).copy()
+
+    def mix_step(self, st, pcm: "torch.Tensor", nsamp=None, out=None, plan=False, draw=None, row0: int = 0):
+        """pcm (B, S) f32 or int16 on the GPU -> the batch with noise mixed in, (B, S) f32 (uvad_mix_step: a fresh draw per call).
+        nsamp: samples per row (B,), as fbank's lengths; out: the f32 tensor to write (pcm itself: in place; None allocates one);
+        plan: True also returns the plan record (B, 4 + 4 max_seg) int32, or pass the tensor to write.  draw: an explicit draw ordinal
+        (uvad_mix_apply: no state update), with row0 the index the first row draws under.  After the first call with a batch size
+        nothing is allocated when out (and plan) are given: the call can be captured."""
+        with torch.cuda.device(self.device):
+            i16 = pcm.dtype == torch.int16
+            if i16:
+                if pcm.device != self.device:
+                    raise RuntimeError(f"pcm must be on {self.device}")
+                pcm = pcm.contiguous()
+            else:
+                pcm = self._dev_f32(pcm, "pcm")
+            B, S = pcm.shape
+            if out is None:
+                out = torch.empty((B, S), dtype=torch.float32, device=self.device)
+            if not (torch.is_tensor(out) and out.device == self.device and out.dtype == torch.float32 and tuple(out.shape) == (B, S) and
+                    out.is_contiguous()):
+                raise ValueError("out must be a contiguous f32 tensor of pcm's shape on pcm's device")
+            if plan is True:
+                plan = torch.zeros((B, st["plan_words"]), dtype=torch.int32, device=self.device)
+            elif plan is False:
+                plan = None
+            elif not (torch.is_tensor(plan) and plan.device == self.device and plan.dtype == torch.int32 and
+                      tuple(plan.shape) == (B, st["plan_words"]) and plan.is_contiguous()):
+                raise ValueError(f"plan must be a contiguous int32 tensor of shape ({B}, {st['plan_words']}) on pcm's device")
+            n = None if nsamp is None else self._dev_lens(nsamp, B, S, torch.int64, "nsamp (samples)")
+            need = int(self.lib.uvad_mix_ws_bytes(B, st["max_seg"]))
+            if st["ws"] is None or st["ws"].numel() < need:
+                st["ws"] = torch.zeros(need, dtype=torch.uint8, device=self.device)
+            head = (self.ctx, pcm.data_ptr(), _lib.INGEST_I16 if i16 else _lib.INGEST_F32, B, S, None if n is None else n.data_ptr(),
+                    out.data_ptr(), None if plan is None else plan.data_ptr())
+            tail = (st["state"].data_ptr(), st["state"].numel(), st["ws"].data_ptr(), st["ws"].numel(), self._stream())
+            if draw is None:
+                self._check(self.lib.uvad_mix_step(*head, *tail))
+            else:
+                self._check(self.lib.uvad_mix_apply(*head, int(row0), int(draw) & 0xFFFFFFFFFFFFFFFF, *tail))
+            return out if plan is None else (out, plan)
+
     def _lstm_train_ws(self, h, B: int, T: int):
         self._lstm_train_configure(h)
         need = int(self.lib.uvad_lstm_train_ws_bytes(self.ctx, B, T))

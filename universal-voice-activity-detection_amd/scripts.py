@@ -864,14 +864,40 @@ def adapt_vad(**kwargs):
     return out
 
 
+def _open_noise(kwargs, rt, seed, sr=16000):
+    """train_vad's noise augmentation -> a mix state (VadRuntime.mix_open) or None.  ``noise`` = {"paths": [wav files], "snr": (10, 20),
+    "mix_prob": 0.5, "snr_steps": 1024, "max_seg": 8, "seed": the run's}: what every training recipe of the reference does to its training
+    phase (cuts.mix(noise_cuts, snr=(10, 20), mix_prob=0.5), src/datasets/*/utils.py), redrawn here for every batch on the device
+    (uvad_mix_step).  Without ``noise``, ``enable_musan`` with ``musan["paths"]`` gives the same.  The files are read through
+    _wav_recordings, so other sample rates pass through the ingest stage.  mix_prob = 0 needs no files: the stage runs and changes
+    nothing."""
+    noise = kwargs.get("noise")
+    if noise is None and kwargs.get("enable_musan") and (kwargs.get("musan") or {}).get("paths"):
+        noise = dict(kwargs["musan"])
+    if noise is None:
+        return None
+    paths, mix_prob = list(noise.get("paths") or ()), float(noise.get("mix_prob", 0.5))
+    if not paths and mix_prob != 0.0:
+        raise ValueError('train_vad: noise needs "paths", a list of wav files')
+    clips = [np.zeros(1, np.float32)] if not paths else []
+    for p in paths:
+        pcm = np.asarray(_wav_recordings(p, "first", rt, sr)[0]["pcm"])
+        clips.append(pcm.astype(np.float32) * np.float32(1.0 / 32768.0) if pcm.dtype == np.int16 else pcm.astype(np.float32))
+        if len(clips[-1]) < 1:
+            raise ValueError(f"{p}: an empty noise file")
+    return rt.mix_open(np.concatenate(clips), [len(c) for c in clips], snr=noise.get("snr", (10, 20)), mix_prob=mix_prob,
+                       snr_steps=int(noise.get("snr_steps", 1024)), max_seg=int(noise.get("max_seg", 8)), seed=int(noise.get("seed", seed)))
+
+
 def _train_vad_sincnet(kwargs, src, val_paths, val_labels, model, rt, device, seed, sr):
     """train_vad for the waveform PyanNet: each recording's waveform is cached on the device and cut into windows of ``window_seconds``;
     a window's labels are its own supervisions_feature_mask (supervision_frames, geometry "sincnet", over the window's own frames).
     The front end normalises over whole rows, so a batch holds rows of ONE length: full windows together, tails in batches of their
     own; a tail shorter than the receptive field (991 samples) has no frame and is skipped.  Shuffle, validation and the checkpoint are
-    train_vad's."""
+    train_vad's.  With ``noise`` every stacked batch is mixed on the device before its train_step; validation never is."""
     from .postprocess import read_label_file, supervision_frames
     net = model.model
+    mix = _open_noise(kwargs, rt, seed, sr)
 
     def labels_of(items, t0, n):
         """(1, T) labels of the n samples from t0 seconds on, from the recording's intervals."""
@@ -929,6 +955,8 @@ def _train_vad_sincnet(kwargs, src, val_paths, val_labels, model, rt, device, se
                 picks = [windows[k] for k in ks[i:i + rows]]
                 x = torch.stack([train[r]["inputs"][0, s0:s0 + n] for r, s0, _, _ in picks])
                 y = torch.cat([lab for _, _, _, lab in picks])
+                if mix is not None:
+                    rt.mix_step(mix, x, out=x)                        # a fresh draw per batch, in place
                 losses.append(model.train_step({"inputs": x, "is_voice": y}, step, accumulate=accumulate))
                 step += 1
         out["train_loss"].append(float(torch.stack(losses).mean()))
@@ -952,7 +980,9 @@ def train_vad(**kwargs):
     ``window_seconds`` (default 5.0; every tail is kept as a shorter row with its length), and batched up to ``max_duration`` seconds per
     batch; the window order is shuffled each epoch by a ``torch.Generator`` seeded with ``seed + epoch``.  Every batch is one
     VadModel.train_step: all LSTM layers and the head learn, with the dropout of ``model_dict["lstm"]["dropout"]`` (the reference's 0.5
-    by default) between the LSTM layers, ``accumulate_grad_batches`` calls per Adam step, lr = ``learning_rate``.  Every
+    by default) between the LSTM layers, ``accumulate_grad_batches`` calls per Adam step, lr = ``learning_rate``.  With ``noise``
+    (_open_noise) the PCM is cached instead of the features, windows are cut in samples, and every batch is mixed with noise on the
+    device and framed with its rows' own lengths; ``noise = None`` launches what a run without the option launches.  Every
     ``check_val_every_n_epoch`` epochs (and after the last) the tensors are committed and validation_step runs on the held-out
     recordings (``input.val_paths``; the training files without them).  Saves a Lightning-style checkpoint {"state_dict" (``model.``
     keys), "epoch", "global_step"} to experiments_dir/checkpoint-epoch=NN.ckpt and returns {"train_loss": [per epoch], "val_loss":
@@ -996,23 +1026,62 @@ def train_vad(**kwargs):
         iv[0, :len(table)] = table
         return {"inputs": feats, "is_voice": rt.intervals_to_labels(iv, [len(table)], T).clone()}
 
-    train = [recording(p, l) for p, l in zip(src["paths"], src["labels"])]
-    held = train if (val_paths, val_labels) == (list(src["paths"]), list(src["labels"])) else [recording(p, l) for p, l in zip(val_paths, val_labels)]
+    mix = _open_noise(kwargs, rt, seed, sr)
     window_s = float(kwargs.get("window_seconds") or 5.0)
-    W = max(1, int(round(window_s / kwargs["frame_shift"])))
-    windows = [(r, s, min(W, b["inputs"].shape[1] - s)) for r, b in enumerate(train) for s in range(0, b["inputs"].shape[1], W)]
     rows = max(1, int(float(kwargs["max_duration"]) / window_s))
     epochs, every = int(kwargs.get("max_epochs", 10)), max(1, int(kwargs.get("check_val_every_n_epoch", 1)))
     accumulate = max(1, int(kwargs.get("accumulate_grad_batches", 1)))
     out = {"train_loss": [], "val_loss": [], "val_metrics": None}
+    if mix is None:
+        train = [recording(p, l) for p, l in zip(src["paths"], src["labels"])]
+        held = train if (val_paths, val_labels) == (list(src["paths"]), list(src["labels"])) else [recording(p, l) for p, l in zip(val_paths, val_labels)]
+        W = max(1, int(round(window_s / kwargs["frame_shift"])))
+        windows = [(r, s, min(W, b["inputs"].shape[1] - s)) for r, b in enumerate(train) for s in range(0, b["inputs"].shape[1], W)]
 
-    def batch_of(picks):
-        """Rows of W frames, zero past each row's length (never read)."""
-        x = torch.zeros((len(picks), W, net.encoding_dim), dtype=torch.float32, device=device)
-        y = torch.zeros((len(picks), W), dtype=torch.uint8, device=device)
-        for i, (r, s, n) in enumerate(picks):
-            x[i, :n], y[i, :n] = train[r]["inputs"][0, s:s + n], train[r]["is_voice"][0, s:s + n]
-        return {"inputs": x, "is_voice": y, "lengths": [n for _, _, n in picks]}
+        def batch_of(picks):
+            """Rows of W frames, zero past each row's length (never read)."""
+            x = torch.zeros((len(picks), W, net.encoding_dim), dtype=torch.float32, device=device)
+            y = torch.zeros((len(picks), W), dtype=torch.uint8, device=device)
+            for i, (r, s, n) in enumerate(picks):
+                x[i, :n], y[i, :n] = train[r]["inputs"][0, s:s + n], train[r]["is_voice"][0, s:s + n]
+            return {"inputs": x, "is_voice": y, "lengths": [n for _, _, n in picks]}
+    else:
+        # noise: the PCM is cached instead of the features, windows are cut in samples, and every batch is mixed (a fresh draw), then
+        # framed with its rows' own lengths; a window's labels are computed over its own frames, as _train_vad_sincnet does
+        def waveform(path, label_path):
+            pcm = np.asarray(_wav_recordings(path, "first", rt, sr)[0]["pcm"])
+            pcm = pcm.astype(np.float32) * np.float32(1.0 / 32768.0) if pcm.dtype == np.int16 else pcm.astype(np.float32)
+            return {"pcm": torch.from_numpy(pcm).to(device), "items": read_label_file(label_path)}
+
+        def labels_of(items, t0, n, T):
+            dur = n / float(sr)
+            own = [(a - t0, b - t0) for a, b in items if b - t0 > 0 and a - t0 < dur]
+            table = supervision_frames(own, dur, frame_shift=kwargs["frame_shift"], geometry="fbank", num_frames=T)
+            iv = np.zeros((1, max(len(table), 1), 2), np.int32)
+            iv[0, :len(table)] = table
+            return rt.intervals_to_labels(iv, [len(table)], T).clone()
+
+        train = [waveform(p, l) for p, l in zip(src["paths"], src["labels"])]
+        held = [recording(p, l) for p, l in zip(val_paths, val_labels)]      # validation is never mixed
+        Wn = max(1, int(round(window_s * sr)))
+        W = rt.num_frames(Wn)
+        windows = []
+        for r, b in enumerate(train):
+            for s0 in range(0, b["pcm"].shape[0], Wn):
+                n = min(Wn, b["pcm"].shape[0] - s0)
+                T = rt.num_frames(n)
+                if T >= 1:                                            # a tail without a frame is skipped
+                    windows.append((r, s0, n, T, labels_of(b["items"], s0 / float(sr), n, T)))
+
+        def batch_of(picks):
+            """Rows of Wn samples, mixed on the device, then their log-mel features with each row's own length."""
+            x = torch.zeros((len(picks), Wn), dtype=torch.float32, device=device)
+            y = torch.zeros((len(picks), W), dtype=torch.uint8, device=device)
+            for i, (r, s0, n, T, lab) in enumerate(picks):
+                x[i, :n], y[i, :T] = train[r]["pcm"][s0:s0 + n], lab[0, :T]
+            nsamp = [n for _, _, n, _, _ in picks]
+            rt.mix_step(mix, x, nsamp=nsamp, out=x)
+            return {"inputs": rt.fbank(x, lengths=nsamp), "is_voice": y, "lengths": [T for _, _, _, T, _ in picks]}
 
     def validate(epoch):
         model.train_commit()                                          # validation_step runs the context's tensors: serve the trained ones
