@@ -1127,7 +1127,8 @@ int uvad_gate_group_step(uvad_ctx *, const void *d_chunk, int chunk, int B, cons
  * slice of the model, VadModel.training_step / _common_step (src/engines/vad_engine.py:247-278: the head expression of
  * PyanNet2.forward, F.leaky_relu(linear(x)) and sigmoid(classifier(x)), F.binary_cross_entropy with the mean over the frames present,
  * src/utils/loss.py:56-89, and autograd's backward pass through them) and configure_optimizers (:280: torch.optim.Adam, no weight decay).
- * Weight decay, schedules and DDP are not here; gradients into a SincNet front end are uvad_sincnet_train_*, below (dropout between LSTM layers is a stage of
+ * Gradient clipping, weight decay, learning-rate schedules and the skip of a non-finite step are uvad_optim_step, below (it replaces the
+ * _apply calls); DDP is not here.  Gradients into a SincNet front end are uvad_sincnet_train_*, below (dropout between LSTM layers is a stage of
  * uvad_lstm_train_*, below; the head has none in the reference either); d_grad_x is where the backward pass through
  * the LSTM stack starts (uvad_lstm_train_backward below takes it as d_dy).
  *
@@ -1199,7 +1200,7 @@ int uvad_head_train_commit(uvad_ctx *, const void *d_state, size_t state_bytes);
  * kernels as before (their output, or the features themselves when first_layer is 0, is this block's input and may be cached across
  * epochs).  Together with uvad_head_train_* this is VadModel.training_step / configure_optimizers (src/engines/vad_engine.py:247-281)
  * for everything above the front end: nn.LSTM on pack_padded_sequence rows, autograd's backward pass through it, torch.optim.Adam.
- * Weight decay, schedules and DDP are not here; d_grad_in of a PyanNet is what uvad_sincnet_train_backward takes.  Dropout between the trainable layers is
+ * Clipping, weight decay and schedules are uvad_optim_step, below; DDP is not here; d_grad_in of a PyanNet is what uvad_sincnet_train_backward takes.  Dropout between the trainable layers is
  * (uvad_lstm_train_set_dropout, defined below); the frozen prefix runs in eval mode.
  *
  * d_x_in [B][T][Din] is the dense f32 input of layer first_layer (Din = in_dim when first_layer is 0, else hidden x directions);
@@ -1223,6 +1224,8 @@ int uvad_head_train_commit(uvad_ctx *, const void *d_state, size_t state_bytes);
  *   per layer k = first_layer .., forward then _reverse: lstm.weight_ih_l{k} [4 hidden][in], weight_hh_l{k} [4 hidden][hidden],
  *   bias_ih_l{k}, bias_hh_l{k} [4 hidden]; bias_ih and bias_hh are separate Adam tensors.  Commit synchronises the device, then feeds the
  *   masters through uvad_set_weight + uvad_finalize, with the consequences uvad_head_train_commit names.
+ *   An LSTM state's scalar record has UVAD_LSTM_TRAIN_SCALAR_WORDS = 10 words: the head's eight, then [8 .. 9] the dropout draw ordinal
+ *   (uint64, low word first); d_out must hold ten words for which = UVAD_HEAD_TRAIN_SCALARS.
  * uvad_lstm_train_reset copies the masters from the context's host tensors: it synchronises the stream and is not for graph capture.
  *   forward, backward and apply allocate nothing and never synchronise: forward -> uvad_head_train_grad -> backward -> both applies can
  *   be captured as one graph and replayed with new data.
@@ -1267,6 +1270,7 @@ typedef struct {
     int segment;                             /* frames per gradient partial, 0 = default (2048) */
     int first_layer;                         /* layers first_layer .. num_layers - 1 learn */
 } uvad_lstm_train_cfg;
+#define UVAD_LSTM_TRAIN_SCALAR_WORDS 10
 int uvad_lstm_train_configure(uvad_ctx *, const uvad_lstm_train_cfg *);
 int64_t uvad_lstm_train_param_count(const uvad_ctx *);   /* P; 0 before uvad_lstm_train_configure */
 size_t uvad_lstm_train_state_bytes(const uvad_ctx *);
@@ -1320,7 +1324,8 @@ int uvad_dropout_apply(const float *d_x, float *d_out, int64_t rows, int cols, i
  *   The P floats are packed in state_dict order restricted to the learning tensors: wav_norm1d.weight, .bias; conv1d.0.filterbank.low_hz_,
  *   band_hz_; conv1d.1.weight, .bias; conv1d.2.weight, .bias; norm1d.0.weight, .bias; norm1d.1.*; norm1d.2.*.  P = 42602 / 42360 / 18180
  *   for first_stage 0 / 1 / 2 on the reference geometry.
- * apply and read are the head's (torch.optim.Adam, no weight decay; tests/head_train_ref.py); which = UVAD_SINCNET_TRAIN_FILTERS reads the
+ * apply and read are the head's (torch.optim.Adam, no weight decay -- clipping, decay and schedules are uvad_optim_step, below;
+ *   tests/head_train_ref.py); which = UVAD_SINCNET_TRAIN_FILTERS reads the
  *   n_filters x kernel_size bank of the last forward call.
  * reset copies the masters from the context's host tensors and synchronises: not for graph capture.  The band edges arrive through
  *   uvad_set_weight as sincnet.conv1d.0.filterbank.low_hz_ / .band_hz_ ([n_filters / 2][1] or [n_filters / 2]); they are optional for
@@ -1355,6 +1360,67 @@ int uvad_sincnet_train_backward(uvad_ctx *, const float *d_wav, const float *d_d
 int uvad_sincnet_train_apply(uvad_ctx *, void *d_state, size_t state_bytes, void *stream);
 int uvad_sincnet_train_read(uvad_ctx *, const void *d_state, size_t state_bytes, int which, float *d_out, void *stream);
 int uvad_sincnet_train_commit(uvad_ctx *, const void *d_state, size_t state_bytes);
+
+/* ---- The joint optimizer step on the device: gradient clipping, weight decay, learning-rate table, skipped steps, resume -----------------
+ * uvad_optim_step replaces the _apply calls of the training states it is given (head, LSTM, SincNet; any may be NULL, not all): what
+ * torch.nn.utils.clip_grad_norm_ over ALL parameters, torch.optim.Adam(weight_decay=) or AdamW, an lr scheduler stepped once per
+ * optimizer step, and Lightning's skipped step (the reference's _common_step returns None on a NaN loss, src/engines/vad_engine.py:275) do
+ * around configure_optimizers.  Like grad and apply it allocates nothing and never synchronises, and it reads every count and the step
+ * index from the device: forward -> head grad -> backward(s) -> uvad_optim_step is one graph that replays for every step.  DDP is not here.
+ *
+ * A state TAKES PART iff it is given, its header carries its family's magic word and parameter count, and its frame count is not 0.  A
+ *   state that does not take part adds nothing to the norm and nothing in it is written; when no state takes part nothing is written at all.
+ * Step, every operation one f32 rounding in this order, no fused multiply-add (tests/optim_ref.py restates it):
+ *   g_j = fl(acc_j / (float)frames) per parameter of a state that takes part;
+ *   S = sum (double)g_j (double)g_j (each product exact).  Order: the parameters of a state in chunks of 4096; within a chunk lane l of 256
+ *     adds elements l, l + 256, ..., l + 3840 in that order from +0, then lane l += lane l + o for o = 128, 64, ..., 1; the chunk sums are
+ *     added in chunk order into one running sum, the states in the order head, LSTM, SincNet.  No atomics: the same calls give the same bits.
+ *   norm = (float)sqrt(S);  coef = max_norm > 0 ? fminf(1, max_norm / (norm + 1e-6f)) : 1  (clip_grad_norm_'s expression);
+ *   lr_t = table[min(t, n_lr - 1)], t the optim state's count of applied steps: any schedule is an uploaded table, the device only indexes
+ *     (the idiom of uvad_mix's amplitude table), so it is bit-defined; uvad_optim_set_lr_table rewrites it between steps without re-capture;
+ *   skip_nonfinite and S not finite: every participating state's accumulator, loss sum and frame count are zeroed, the optim state's
+ *     `skipped` advances, and no master, m, v, t, bc1 or bc2 of any state changes, nor the optim state's t;
+ *   otherwise, with lr_k = fl(lr_t lr_scale[k]) for family k:  g = fl(g coef);  weight_decay > 0, L2: g = fl(g + fl(wd w));  AdamW:
+ *     w = fl(w fl(1 - fl(lr_k wd)));  then uvad_head_train_apply's update with lr_k and the header update of apply (t, bc1, bc2 advance, the
+ *     sums are zeroed), and the optim state's t advances once.  Mixing _apply and uvad_optim_step on one state is well defined.
+ *   With max_norm = 0, weight_decay = 0, lr_scale = 1 and a one-entry table holding the family's lr (and its betas and eps) the step leaves
+ *   the bytes the three _apply calls leave.
+ * uvad_optim_reset uploads the configuration and the table, zeroes t and skipped; it synchronises the stream and is not for graph capture, nor
+ *   is uvad_optim_set_lr_table (n_lr at most the reset's).  1 - beta is formed as the families' configure forms it.
+ * uvad_optim_read copies UVAD_OPTIM_RECORD_WORDS 32-bit words to d_out (device memory): [0] norm, [1] coef (0 for a skipped step), [2] lr_t
+ *   of the last step that had a participant (f32), [3] bit k set: family k (0 head, 1 LSTM, 2 SincNet) took part, [4 .. 5] t, [6 .. 7] skipped
+ *   (uint64, low word first).  uvad_optim_write puts such a record (device memory) back.
+ * uvad_head_train_write / uvad_lstm_train_write / uvad_sincnet_train_write mirror the _read calls, d_in in device memory: which =
+ *   UVAD_HEAD_TRAIN_MASTERS / _M / _V copy P floats in; UVAD_HEAD_TRAIN_SCALARS takes the family's scalar record and restores t, 1 - beta1^t,
+ *   1 - beta2^t, and for an LSTM state the draw ordinal (the accumulated loss and frame words are ignored: a write belongs between steps,
+ *   and _GRAD is refused).  A state written from what was read is indistinguishable from the one that was read.
+ * State: uvad_optim_state_bytes(n_lr) = a 256-byte header | the table, padded to 64 floats (0 for n_lr outside [1, 2^24]).  Workspace:
+ *   uvad_optim_ws_bytes(ctx): one double per 4096 parameters of every family the context has configured, padded to 256 bytes.
+ * Refusals (nothing enqueued).  UVAD_E_ARG: NULL cfg, table, optim state, workspace, d_in or d_out; n_lr < 1 or above 2^24 or above the
+ *   reset's; a table entry not finite or <= 0; beta1 / beta2 outside [0, 1); eps not finite or <= 0; max_norm or weight_decay negative or
+ *   not finite; an lr_scale not finite or < 0; all three states NULL; byte counts below the helpers; which outside MASTERS, M, V, SCALARS.
+ *   UVAD_E_STATE: a family whose state is given but which is not configured; a family or optim state never reset, or reset under another
+ *   shape.  On the device a state or optim state whose magic word or shape does not match makes the kernels write nothing. */
+#define UVAD_OPTIM_RECORD_WORDS 8
+typedef struct {
+    float beta1, beta2, eps;
+    float max_norm;                          /* 0 = no clipping */
+    float weight_decay;                      /* 0 = none */
+    int decoupled;                           /* 0: L2 into the gradient (Adam(weight_decay=)); 1: AdamW */
+    int skip_nonfinite;                      /* 1: a step whose squared norm is not finite is skipped */
+    float lr_scale[3];                       /* head, LSTM, SincNet: lr_k = fl(lr_t * scale) */
+} uvad_optim_cfg;
+size_t uvad_optim_state_bytes(int n_lr);
+size_t uvad_optim_ws_bytes(const uvad_ctx *);
+int uvad_optim_reset(uvad_ctx *, void *d_state, size_t state_bytes, const uvad_optim_cfg *, const float *h_lr_table, int n_lr, void *stream);
+int uvad_optim_set_lr_table(uvad_ctx *, void *d_state, size_t state_bytes, const float *h_lr_table, int n_lr, void *stream);
+int uvad_optim_step(uvad_ctx *, void *d_head_state, size_t head_bytes, void *d_lstm_state, size_t lstm_bytes, void *d_sincnet_state,
+                    size_t sincnet_bytes, void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream);
+int uvad_optim_read(uvad_ctx *, const void *d_state, size_t state_bytes, void *d_out, void *stream);
+int uvad_optim_write(uvad_ctx *, void *d_state, size_t state_bytes, const void *d_in, void *stream);
+int uvad_head_train_write(uvad_ctx *, void *d_state, size_t state_bytes, int which, const float *d_in, void *stream);
+int uvad_lstm_train_write(uvad_ctx *, void *d_state, size_t state_bytes, int which, const float *d_in, void *stream);
+int uvad_sincnet_train_write(uvad_ctx *, void *d_state, size_t state_bytes, int which, const float *d_in, void *stream);
 
 /* ---- Noise mixing of training batches on the device -----------------------------------------------------------------------------------------
  * Every training recipe of the reference runs cuts.mix(noise_cuts, snr = (10, 20), mix_prob = 0.5, preserve_id = "left") on its training

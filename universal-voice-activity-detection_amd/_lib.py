@@ -70,6 +70,15 @@ class SincNetTrainCfg(C.Structure):  # uvad_sincnet_train_cfg (24 bytes)
 SINCNET_TRAIN_FILTERS = 5        # `which` of uvad_sincnet_train_read: the bank of the last forward call
 
 
+LSTM_TRAIN_SCALAR_WORDS = 10     # an LSTM state's scalar record: the head's eight words, then the dropout draw ordinal (uint64)
+OPTIM_RECORD_WORDS = 8           # 32-bit words of uvad_optim_read's record: norm, coef, lr_t, took-part bits, t (u64), skipped (u64)
+
+
+class OptimCfg(C.Structure):     # uvad_optim_cfg (40 bytes)
+    _fields_ = [("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("max_norm", C.c_float), ("weight_decay", C.c_float),
+                ("decoupled", C.c_int), ("skip_nonfinite", C.c_int), ("lr_scale", C.c_float * 3)]
+
+
 INGEST_F32, INGEST_I16 = 0, 1    # `fmt` of uvad_mix_step / uvad_mix_apply (UVAD_INGEST_*)
 MIX_MAX_SEG, MIX_PLAN_HEAD, MIX_SEG_WORDS = 64, 4, 4     # the plan record of uvad_mix_step: int32 words per row = head + seg words x max_seg
 
@@ -261,6 +270,17 @@ SIGNATURES = {
     "uvad_sincnet_train_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_sincnet_train_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     "uvad_sincnet_train_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "uvad_optim_state_bytes": (C.c_size_t, [C.c_int]),
+    "uvad_optim_ws_bytes": (C.c_size_t, [C.c_void_p]),
+    "uvad_optim_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(OptimCfg), C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    "uvad_optim_set_lr_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    "uvad_optim_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                  C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_optim_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "uvad_optim_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "uvad_head_train_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "uvad_lstm_train_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "uvad_sincnet_train_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     "uvad_mix_state_bytes": (C.c_size_t, [C.POINTER(MixCfg), C.c_int]),
     "uvad_mix_ws_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "uvad_mix_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(MixCfg), C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),

@@ -105,6 +105,19 @@ def load_config() -> ConfigDict:
     cfg.musan.snr = (10, 20)
     cfg.musan.mix_prob = 0.5
 
+    # function == "train" / "adapt" with adapt_lstm_layers: the joint optimizer step (uvad_optim_step).  All at their defaults: every state
+    # takes its own plain Adam step, as before.  gradient_clip_val: the global gradient norm is clipped to it (0 = off); weight_decay with
+    # adamw (False: L2 into the gradient, torch.optim.Adam(weight_decay=); True: AdamW); lr_schedule: None or {"name": "constant" | "warmup" |
+    # "linear" | "cosine" | "step", ...} (scripts.lr_schedule_table); skip_nonfinite: a step whose gradient norm is not finite is skipped.
+    # stop_after_epoch: end the run after that epoch with its checkpoint (0 = run to max_epochs); the same configuration with
+    # load_checkpoint then continues it.
+    cfg.gradient_clip_val = 0.0
+    cfg.weight_decay = 0.0
+    cfg.adamw = False
+    cfg.lr_schedule = None
+    cfg.skip_nonfinite = False
+    cfg.stop_after_epoch = 0
+
     cfg.predict_output_dir = os.environ.get("UVAD_PREDICT_DIR", "")   # "" = do not write files
     cfg.window_type = "povey"   # lhotse default; BASELINE cfg 2 uses "hamming"
 

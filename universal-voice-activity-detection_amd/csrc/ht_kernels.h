@@ -220,9 +220,10 @@ __global__ __launch_bounds__(256) void ht_read_kernel(const void *state, unsigne
     const HeadTrainHeader *hd = reinterpret_cast<const HeadTrainHeader *>(state);
     const bool ok = ht_state_ok(state, magic, P);
     if (which == UVAD_HEAD_TRAIN_SCALARS) {
-        if (blockIdx.x == 0 && threadIdx.x < HT_SCALAR_WORDS) {
+        // an LSTM state's record carries two more words, [8 .. 9]: the dropout draw ordinal (UVAD_LSTM_TRAIN_SCALAR_WORDS)
+        if (blockIdx.x == 0 && threadIdx.x < (magic == LT_MAGIC ? LT_SCALAR_WORDS : HT_SCALAR_WORDS)) {
             const int i = threadIdx.x;
-            const unsigned long long q = i < 2 ? (unsigned long long)__double_as_longlong(hd->loss) : i < 4 ? hd->frames : hd->t;
+            const unsigned long long q = i < 2 ? (unsigned long long)__double_as_longlong(hd->loss) : i < 4 ? hd->frames : i < 8 ? hd->t : hd->draws;
             const unsigned word = i == 6 ? __float_as_uint(hd->bc1) : i == 7 ? __float_as_uint(hd->bc2) : (unsigned)(i & 1 ? q >> 32 : q);
             reinterpret_cast<unsigned *>(out)[i] = ok ? word : 0u;
         }

@@ -138,6 +138,7 @@ struct uvad_ctx {
     uvad_sincnet_train_cfg snq{};
     SincTrainShape snts{};
     std::map<void *, MixState> mixes;           // ... and of the noise-mix states (uvad_mix_*)
+    std::map<void *, int> optims;               // ... and of the optimizer states (uvad_optim_*): n_lr at reset
     int device = 0, n_cu = 256;
     bool has_fb = false, has_model = false, finalized = false, tables_set = false;
     uvad_fbank_cfg fb{};
@@ -3717,6 +3718,169 @@ int uvad_sincnet_train_commit(uvad_ctx *c, const void *d_state, size_t state_byt
         if (int r = uvad_set_weight(c, "sincnet.conv1d.0.filters", w.data() + q.off_bank, shape, 3)) return r;
     }
     return uvad_finalize(c);
+}
+
+// ---- the joint optimizer step and the _write calls (optim.hip) ------------------------------------------------------------------------------
+// nullptr: the configuration and the table are in range; else the word uvad_last_error names
+static const char *optim_table_error(const float *h_lr_table, int n_lr) {
+    if (!h_lr_table) return "h_lr_table is NULL";
+    if (n_lr < 1 || n_lr > OPT_MAX_LR) return "n_lr must lie in [1, 2^24]";
+    for (int i = 0; i < n_lr; ++i)
+        if (!std::isfinite(h_lr_table[i]) || !(h_lr_table[i] > 0.0f)) return "every lr table entry must be finite and positive";
+    return nullptr;
+}
+static const char *optim_cfg_error(const uvad_optim_cfg *q) {
+    if (!q) return "cfg is NULL";
+    if (!std::isfinite(q->beta1) || q->beta1 < 0.0f || !(q->beta1 < 1.0f)) return "beta1 must lie in [0, 1)";
+    if (!std::isfinite(q->beta2) || q->beta2 < 0.0f || !(q->beta2 < 1.0f)) return "beta2 must lie in [0, 1)";
+    if (!std::isfinite(q->eps) || !(q->eps > 0.0f)) return "eps must be finite and positive";
+    if (!std::isfinite(q->max_norm) || q->max_norm < 0.0f) return "max_norm must be finite and >= 0";
+    if (!std::isfinite(q->weight_decay) || q->weight_decay < 0.0f) return "weight_decay must be finite and >= 0";
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(q->lr_scale[k]) || q->lr_scale[k] < 0.0f) return "every lr_scale must be finite and >= 0";
+    return nullptr;
+}
+
+size_t uvad_optim_state_bytes(int n_lr) { return n_lr < 1 || n_lr > OPT_MAX_LR ? 0 : optim_state_bytes(n_lr); }
+
+size_t uvad_optim_ws_bytes(const uvad_ctx *c) {
+    if (!c) return 0;
+    const int chunks = (c->has_ht ? optim_chunks(c->hts.P) : 0) + (c->has_lt ? optim_chunks(c->lts.P) : 0) + (c->has_snt ? optim_chunks(c->snts.P) : 0);
+    return chunks ? optim_ws_bytes(chunks) : 0;
+}
+
+int uvad_optim_reset(uvad_ctx *c, void *d_state, size_t state_bytes, const uvad_optim_cfg *q, const float *h_lr_table, int n_lr, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_state) return fail(c, UVAD_E_ARG, "uvad_optim_reset: bad argument");
+    if (const char *e = optim_cfg_error(q)) return fail(c, UVAD_E_ARG, std::string("uvad_optim_reset: ") + e);
+    if (const char *e = optim_table_error(h_lr_table, n_lr)) return fail(c, UVAD_E_ARG, std::string("uvad_optim_reset: ") + e);
+    if (reinterpret_cast<uintptr_t>(d_state) % 16) return fail(c, UVAD_E_ARG, "uvad_optim_reset: d_state must be 16-byte aligned");
+    const size_t need = optim_state_bytes(n_lr);
+    if (state_bytes < need) return fail(c, UVAD_E_ARG, "uvad_optim_reset: state too small: need " + std::to_string(need) + " bytes");
+    const HeadTrainAdam o = adam_of(1.0f, q->beta1, q->beta2, q->eps);
+    std::vector<char> host(need, 0);
+    OptimHeader h{};
+    h.magic = OPT_MAGIC; h.cap = n_lr; h.n = n_lr; h.decoupled = q->decoupled ? 1 : 0; h.skip_nonfinite = q->skip_nonfinite ? 1 : 0;
+    h.b1 = o.b1; h.b2 = o.b2; h.eps = o.eps; h.omb1 = o.omb1; h.omb2 = o.omb2; h.max_norm = q->max_norm; h.wd = q->weight_decay;
+    for (int k = 0; k < 3; ++k) h.lr_scale[k] = q->lr_scale[k];
+    std::memcpy(host.data(), &h, sizeof h);
+    std::memcpy(host.data() + sizeof h, h_lr_table, (size_t)n_lr * sizeof(float));
+    c->optims.erase(d_state);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));      // what the stream still does to this state comes first
+    HIPCHK(c, hipMemcpy(d_state, host.data(), host.size(), hipMemcpyHostToDevice));
+    c->optims[d_state] = n_lr;
+    return UVAD_OK;
+}
+
+// the checks every call on a reset optim state shares -> its n_lr at reset through *cap
+static int optim_state_check(uvad_ctx *c, const char *fn, const void *d_state, size_t state_bytes, int *cap) {
+    const std::string f(fn);
+    if (!d_state) return fail(c, UVAD_E_ARG, f + ": bad argument");
+    auto it = c->optims.find(const_cast<void *>(d_state));
+    if (it == c->optims.end()) return fail(c, UVAD_E_STATE, f + ": call uvad_optim_reset on this state first");
+    const size_t need = optim_state_bytes(it->second);
+    if (state_bytes < need) return fail(c, UVAD_E_ARG, f + ": state too small: need " + std::to_string(need) + " bytes");
+    *cap = it->second;
+    return UVAD_OK;
+}
+
+int uvad_optim_set_lr_table(uvad_ctx *c, void *d_state, size_t state_bytes, const float *h_lr_table, int n_lr, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_state) return fail(c, UVAD_E_ARG, "uvad_optim_set_lr_table: bad argument");
+    if (const char *e = optim_table_error(h_lr_table, n_lr)) return fail(c, UVAD_E_ARG, std::string("uvad_optim_set_lr_table: ") + e);
+    int cap = 0;
+    if (int r = optim_state_check(c, "uvad_optim_set_lr_table", d_state, state_bytes, &cap)) return r;
+    if (n_lr > cap) return fail(c, UVAD_E_ARG, "uvad_optim_set_lr_table: n_lr above the " + std::to_string(cap) + " entries of uvad_optim_reset");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));      // the steps enqueued so far read the old table
+    HIPCHK(c, hipMemcpy(reinterpret_cast<char *>(d_state) + sizeof(OptimHeader), h_lr_table, (size_t)n_lr * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(c, launch_optim_set_n(d_state, cap, n_lr, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_optim_step(uvad_ctx *c, void *d_head_state, size_t head_bytes, void *d_lstm_state, size_t lstm_bytes, void *d_sincnet_state,
+                    size_t sincnet_bytes, void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_state || !d_ws) return fail(c, UVAD_E_ARG, "uvad_optim_step: bad argument");
+    if (!d_head_state && !d_lstm_state && !d_sincnet_state) return fail(c, UVAD_E_ARG, "uvad_optim_step: at least one training state must be given");
+    if (reinterpret_cast<uintptr_t>(d_ws) % 8) return fail(c, UVAD_E_ARG, "uvad_optim_step: d_ws must be 8-byte aligned");
+    if (d_head_state)
+        if (int r = head_train_state_check(c, "uvad_optim_step", d_head_state, head_bytes, true)) return r;    // configured, and the state's size
+    if (d_lstm_state)
+        if (int r = lstm_train_state_check(c, "uvad_optim_step", d_lstm_state, lstm_bytes, true)) return r;
+    if (d_sincnet_state)
+        if (int r = sinc_train_state_check(c, "uvad_optim_step", d_sincnet_state, sincnet_bytes, true)) return r;
+    int cap = 0;
+    if (int r = optim_state_check(c, "uvad_optim_step", d_state, state_bytes, &cap)) return r;
+    OptimFamily fam[3] = {};
+    if (d_head_state) fam[0] = OptimFamily{d_head_state, HT_MAGIC, c->hts.P, c->hts.Pp};
+    if (d_lstm_state) fam[1] = OptimFamily{d_lstm_state, LT_MAGIC, c->lts.P, c->lts.Pp};
+    if (d_sincnet_state) fam[2] = OptimFamily{d_sincnet_state, SNT_MAGIC, c->snts.P, c->snts.Pp};
+    int chunks = 0;
+    for (int k = 0; k < 3; ++k) chunks += fam[k].state ? optim_chunks(fam[k].P) : 0;
+    const size_t need = optim_ws_bytes(chunks);
+    if (ws_bytes < need) return fail(c, UVAD_E_ARG, "uvad_optim_step: workspace too small: need " + std::to_string(need) + " bytes");
+    if (d_head_state)
+        if (int r = head_train_state_check(c, "uvad_optim_step", d_head_state, head_bytes, false)) return r;   // ... and that it was reset
+    if (d_lstm_state)
+        if (int r = lstm_train_state_check(c, "uvad_optim_step", d_lstm_state, lstm_bytes, false)) return r;
+    if (d_sincnet_state)
+        if (int r = sinc_train_state_check(c, "uvad_optim_step", d_sincnet_state, sincnet_bytes, false)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_optim_step(fam, d_state, cap, reinterpret_cast<double *>(d_ws), (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_optim_read(uvad_ctx *c, const void *d_state, size_t state_bytes, void *d_out, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_out) return fail(c, UVAD_E_ARG, "uvad_optim_read: bad argument");
+    int cap = 0;
+    if (int r = optim_state_check(c, "uvad_optim_read", d_state, state_bytes, &cap)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_optim_read(d_state, cap, reinterpret_cast<unsigned *>(d_out), (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_optim_write(uvad_ctx *c, void *d_state, size_t state_bytes, const void *d_in, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_in) return fail(c, UVAD_E_ARG, "uvad_optim_write: bad argument");
+    int cap = 0;
+    if (int r = optim_state_check(c, "uvad_optim_write", d_state, state_bytes, &cap)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_optim_write(d_state, cap, reinterpret_cast<const unsigned *>(d_in), (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+static bool train_write_which_ok(int which) {
+    return which == UVAD_HEAD_TRAIN_MASTERS || which == UVAD_HEAD_TRAIN_M || which == UVAD_HEAD_TRAIN_V || which == UVAD_HEAD_TRAIN_SCALARS;
+}
+
+int uvad_head_train_write(uvad_ctx *c, void *d_state, size_t state_bytes, int which, const float *d_in, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_in || !train_write_which_ok(which)) return fail(c, UVAD_E_ARG, "uvad_head_train_write: bad argument");
+    if (int r = head_train_state_check(c, "uvad_head_train_write", d_state, state_bytes, false)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_train_write(d_state, HT_MAGIC, c->hts.P, c->hts.Pp, which, d_in, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_lstm_train_write(uvad_ctx *c, void *d_state, size_t state_bytes, int which, const float *d_in, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_in || !train_write_which_ok(which)) return fail(c, UVAD_E_ARG, "uvad_lstm_train_write: bad argument");
+    if (int r = lstm_train_state_check(c, "uvad_lstm_train_write", d_state, state_bytes, false)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_train_write(d_state, LT_MAGIC, c->lts.P, c->lts.Pp, which, d_in, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_sincnet_train_write(uvad_ctx *c, void *d_state, size_t state_bytes, int which, const float *d_in, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_in || !train_write_which_ok(which)) return fail(c, UVAD_E_ARG, "uvad_sincnet_train_write: bad argument");
+    if (int r = sinc_train_state_check(c, "uvad_sincnet_train_write", d_state, state_bytes, false)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_train_write(d_state, SNT_MAGIC, c->snts.P, c->snts.Pp, which, d_in, (hipStream_t)stream));
+    return UVAD_OK;
 }
 
 // ---- noise mixing of training batches (mix.hip) ------------------------------------------------------------------------------------------

@@ -816,6 +816,7 @@ hipError_t launch_head_train_read(const HeadTrainShape &q, const void *state, in
 constexpr int LT_MAX_LAYERS = 8, LT_MAX_DIN = 2048;
 constexpr unsigned LT_MAGIC = 0x55564C54u;           // "UVLT": the state
 constexpr int LT_WS_MAGIC = 0x4C545753;              // "LTWS": a workspace whose kept activations belong to (B, T)
+constexpr int LT_SCALAR_WORDS = 10;                  // UVAD_LSTM_TRAIN_SCALAR_WORDS: the head's eight, then the draw ordinal
 struct LstmTrainShape {
     int Din, H, dirs, nl, first_layer, P, Pp;
     int in[LT_MAX_LAYERS];                           // input width of layer li
@@ -896,6 +897,35 @@ hipError_t launch_sinc_train_backward(const SincTrainShape &q, const SincTrainAr
 hipError_t launch_sinc_train_bank(const SincTrainShape &q, void *state, hipStream_t s);   // the bank from the masters as they stand
 hipError_t launch_sinc_train_apply(const SincTrainShape &q, const HeadTrainAdam &o, void *state, hipStream_t s);
 hipError_t launch_sinc_train_read(const SincTrainShape &q, const void *state, int which, float *out, hipStream_t s);   // which 5: the bank
+
+// ---- optim.hip: the joint optimizer step over the three training states (uvad_optim_*, include/uvad.h), and the _write calls of the families ----
+// State: OptimHeader (256 bytes) | the learning-rate table [cap] f32, padded to 64 floats.  cap is the n_lr of uvad_optim_reset (the shape the
+// kernels check beside the magic word), n <= cap the entries in use.
+// Workspace: one double per chunk of OPT_CHUNK parameters, the chunks of the head first, then the LSTM's, then SincNet's; padded to 256 bytes.
+constexpr unsigned OPT_MAGIC = 0x55564F50u;          // "UVOP"
+constexpr int OPT_CHUNK = 4096;                      // parameters per sum-of-squares partial: 256 lanes x 16 passes
+constexpr int OPT_RECORD_WORDS = 8;                  // UVAD_OPTIM_RECORD_WORDS
+constexpr int OPT_MAX_LR = 1 << 24;
+struct OptimHeader {
+    unsigned magic; int cap, n, decoupled, skip_nonfinite;
+    float b1, b2, eps, omb1, omb2, max_norm, wd;     // byte 20
+    float lr_scale[3];                               // byte 48
+    int pad0;
+    unsigned long long t, skipped;                   // byte 64, 72: steps applied, steps skipped
+    float norm, coef, lr_t; unsigned mask;           // byte 80: the record of the last step; mask bit k: family k took part
+    int skip;                                        // byte 96: the step in flight is skipped (written by the fold, read by the update and the commit)
+    int reserved[39];
+};                                                   // 256 bytes
+struct OptimFamily { void *state; unsigned magic; int P, Pp; };   // state == nullptr: the family is absent
+inline int optim_chunks(int P) { return (P + OPT_CHUNK - 1) / OPT_CHUNK; }
+inline size_t optim_state_bytes(int n_lr) { return sizeof(OptimHeader) + (size_t)((n_lr + 63) / 64 * 64) * sizeof(float); }
+inline size_t optim_ws_bytes(int chunks) { return ((size_t)chunks * sizeof(double) + 255) / 256 * 256; }
+hipError_t launch_optim_step(const OptimFamily fam[3], void *opt, int cap, double *part, hipStream_t s);
+hipError_t launch_optim_set_n(void *opt, int cap, int n, hipStream_t s);
+hipError_t launch_optim_read(const void *opt, int cap, unsigned *out, hipStream_t s);
+hipError_t launch_optim_write(void *opt, int cap, const unsigned *in, hipStream_t s);
+// MASTERS / M / V: P floats into that block; SCALARS: t, bc1, bc2 from the words of the family's scalar record (an LSTM state: the draw ordinal too)
+hipError_t launch_train_write(void *state, unsigned magic, int P, int Pp, int which, const float *in, hipStream_t s);
 
 // ---- mix.hip: noise mixing for training batches (uvad_mix_*, include/uvad.h): row energies, the plan of every row, the mix pass ----
 // State: MixHeader (256 bytes) | clip_first [n_clips + 1] int64 | clip energies [n_clips] f64 | amp [Q] f64; every part 256-byte aligned.

@@ -176,7 +176,61 @@ class VadModel(nn.Module):
     _NO_SINCNET_LENGTHS = ("the SincNet front end normalises over whole rows (wav_norm1d and every instance norm), so per-row lengths are "
                            "not trained: batches of one length only")
 
-    def _sincnet_step(self, batch, accumulate, sincnet_stages, dropout, seed):
+    def _optim_of(self, rt, optim):
+        """optim= of adapt_step / train_step -> an optimizer handle: the state VadRuntime.optim_open returned as it is, or one opened (once)
+        from a dict of optim_open's options plus "lr_table" (default: the constant self.learning_rate)."""
+        if "state" in optim:
+            return optim
+        held = getattr(self, "_optim", None)
+        norm = {k: ([float(x) for x in v] if hasattr(v, "__len__") else v) for k, v in optim.items()}
+        if held is None or held[0] is not rt or held[1] != norm:
+            cfg = {k: v for k, v in optim.items() if k != "lr_table"}
+            table = optim.get("lr_table")
+            o = rt.optim_open(cfg, [self.learning_rate] if table is None else table)
+            held = self._optim = [rt, norm, o]
+            pending = getattr(self, "_pending_optimizer_state", None)
+            if pending is not None and pending.get("optim") is not None:
+                rt.optim_write(o, pending["optim"])
+        return held[2]
+
+    def _restore_pending(self, rt, hh, hl, hs=None):
+        """load_optimizer_state's tensors into handles that were just opened."""
+        st = getattr(self, "_pending_optimizer_state", None)
+        if st is None:
+            return
+        for h, key, write in ((hh, "head", rt.head_train_write), (hl, "lstm", rt.lstm_train_write), (hs, "sincnet", rt.sincnet_train_write)):
+            if h is not None and st.get(key) is not None:
+                write(h, st[key])
+
+    def optimizer_state(self) -> dict:
+        """Everything a resumed run needs beside the weights, as CPU tensors: per family ("head", "lstm", "sincnet" when it learns) the
+        masters, m, v and the scalar record (step, bias corrections, the LSTM's dropout draw ordinal), and "optim": the joint optimizer's
+        record (applied and skipped steps) when adapt_step / train_step ran with optim=.  Synchronises."""
+        held = getattr(self, "_adapt_full", None)
+        if held is None:
+            raise RuntimeError("no adapt_step has run yet")
+        rt = held[0]
+        pick = lambda r: {k: r[k] for k in ("weights", "m", "v", "scalars")}
+        out = {"head": pick(rt.head_train_read(held[1])), "lstm": pick(rt.lstm_train_read(held[2]))}
+        if len(held) > 4:
+            out["sincnet"] = pick(rt.sincnet_train_read(held[4]))
+        o = getattr(self, "_optim", None)
+        if o is not None and o[0] is rt:
+            out["optim"] = rt.optim_read(o[2])["record"]
+        return out
+
+    def load_optimizer_state(self, state: dict):
+        """Restore what optimizer_state returned: into the training handles when adapt_step / train_step already opened them, otherwise
+        into the handles the next such step opens (the handles take their shapes from that step's arguments)."""
+        self._pending_optimizer_state = state
+        held = getattr(self, "_adapt_full", None)
+        if held is not None:
+            self._restore_pending(held[0], held[1], held[2], held[4] if len(held) > 4 else None)
+            o = getattr(self, "_optim", None)
+            if o is not None and o[0] is held[0] and state.get("optim") is not None:
+                held[0].optim_write(o[2], state["optim"])
+
+    def _sincnet_step(self, batch, accumulate, sincnet_stages, dropout, seed, optim=None):
         """adapt_step with the top `sincnet_stages` SincNet stages learning: the waveform through sincnet_train_forward, every LSTM layer
         and the head above it, and the LSTM's input gradient back through the front end."""
         if batch.get("lengths") is not None:
@@ -195,6 +249,7 @@ class VadModel(nn.Module):
             held = self._adapt_full = [rt, rt.head_train_open(lr=self.learning_rate),
                                        rt.lstm_train_open(layers=layers, lr=self.learning_rate, dropout=dropout, seed=seed), 0,
                                        rt.sincnet_train_open(first_stage=3 - stages, lr=self.learning_rate)]
+            self._restore_pending(rt, held[1], held[2], held[4])
         hh, hl, hs = held[1], held[2], held[4]
         hl["dropout"], hl["seed"] = dropout, int(seed) & 0xFFFFFFFFFFFFFFFF
         feats = rt.sincnet_train_forward(hs, wav)
@@ -205,19 +260,26 @@ class VadModel(nn.Module):
         rt.sincnet_train_backward(hs, wav, gin)
         held[3] += 1
         if held[3] % max(1, int(accumulate)) == 0:
-            rt.head_train_apply(hh)
-            rt.lstm_train_apply(hl)
-            rt.sincnet_train_apply(hs)
+            if optim is not None:
+                rt.optim_step(self._optim_of(rt, optim), head=hh, lstm=hl, sincnet=hs)
+            else:
+                rt.head_train_apply(hh)
+                rt.lstm_train_apply(hl)
+                rt.sincnet_train_apply(hs)
         return rt.head_train_batch_loss(hh)
 
-    def adapt_step(self, batch, batch_idx=0, accumulate: int = 1, lstm_layers: int = 1, dropout=None, seed: int = 0, sincnet_stages: int = 0):
+    def adapt_step(self, batch, batch_idx=0, accumulate: int = 1, lstm_layers: int = 1, dropout=None, seed: int = 0, sincnet_stages: int = 0,
+                   optim=None):
         """One micro-batch in which the head and the top `lstm_layers` LSTM layers learn: batch["lstm_in"] (the cached frozen prefix) or
         batch["inputs"] through it, the learning layers' forward pass with kept activations, the head's loss and backward pass as
         adapt_head_step's, backpropagation through time from its input gradient; every `accumulate` calls one Adam step on both
         states (lr = self.learning_rate).  dropout: nn.LSTM's dropout between the learning layers, a fresh mask per call (None: none,
         the frozen prefix never has any); seed: the masks' seed.  sincnet_stages = k > 0 (PyanNet): the top k stages of the SincNet front
         end learn too, from the waveform batch["inputs"] (B, 1, S) or (B, S) -- every LSTM layer then learns, whatever lstm_layers says,
-        and batch["lengths"] must be None.  Returns the batch's mean loss as a 0-d tensor on the device without synchronising."""
+        and batch["lengths"] must be None.  optim: None -- every state takes its own plain Adam step (the _apply calls); a dict of
+        VadRuntime.optim_open's options (plus "lr_table"), or the state optim_open returned -- the step ends in ONE uvad_optim_step over
+        all learning states instead: the global gradient norm and its clipping, weight decay, the table's learning rate, a non-finite
+        step skipped.  Returns the batch's mean loss as a 0-d tensor on the device without synchronising."""
         y = batch.get("is_voice")
         if y is None:
             raise ValueError('adapt_step needs batch["is_voice"]')
@@ -225,13 +287,14 @@ class VadModel(nn.Module):
         if not 0.0 <= dropout < 1.0:
             raise ValueError("dropout must lie in [0, 1)")
         if int(sincnet_stages) != 0:
-            return self._sincnet_step(batch, accumulate, sincnet_stages, dropout, seed)
+            return self._sincnet_step(batch, accumulate, sincnet_stages, dropout, seed, optim)
         x = batch["lstm_in"] if batch.get("lstm_in") is not None else self.lstm_in(batch, lstm_layers)
         rt = self.model.runtime(x.device)
         held = getattr(self, "_adapt_full", None)
         if held is None or held[0] is not rt or held[2]["layers"] != int(lstm_layers) or len(held) > 4:   # (a SincNet handle of an earlier
             held = self._adapt_full = [rt, rt.head_train_open(lr=self.learning_rate),                      # sincnet_stages > 0 step: start anew)
                                        rt.lstm_train_open(layers=lstm_layers, lr=self.learning_rate, dropout=dropout, seed=seed), 0]
+            self._restore_pending(rt, held[1], held[2])
         hh, hl = held[1], held[2]
         hl["dropout"], hl["seed"] = dropout, int(seed) & 0xFFFFFFFFFFFFFFFF      # the handle re-asserts them before every call
         lengths = batch.get("lengths")
@@ -241,8 +304,11 @@ class VadModel(nn.Module):
         rt.lstm_train_backward(hl, x, gx, lengths=lengths)
         held[3] += 1
         if held[3] % max(1, int(accumulate)) == 0:
-            rt.head_train_apply(hh)
-            rt.lstm_train_apply(hl)
+            if optim is not None:
+                rt.optim_step(self._optim_of(rt, optim), head=hh, lstm=hl)
+            else:
+                rt.head_train_apply(hh)
+                rt.lstm_train_apply(hl)
         return rt.head_train_batch_loss(hh)
 
     def adapt_commit(self):
@@ -269,15 +335,15 @@ class VadModel(nn.Module):
         self.model._rt_stamp = self.model._stamp(rt.device)   # the runtime already holds these very tensors: no second upload
 
     # -- training from initialisation: every LSTM layer and the head learn (PyanNet2) -----------------------------------------------
-    def train_step(self, batch, batch_idx=0, accumulate: int = 1):
+    def train_step(self, batch, batch_idx=0, accumulate: int = 1, optim=None):
         """The reference's training_step on the device: adapt_step with every LSTM layer learning, the model's configured dropout between
         the layers (self.model.train_dropout) and the masks seeded from torch.initial_seed().  A PyanNet takes the waveform batch
-        (B, 1, S) or (B, S) and its whole SincNet front end learns with the rest; its batch must not carry lengths."""
+        (B, 1, S) or (B, S) and its whole SincNet front end learns with the rest; its batch must not carry lengths.  optim: adapt_step's."""
         if self.model_name == "PyanNet" and batch.get("lengths") is not None:    # before the model or the device is touched
             raise NotImplementedError("train_step: " + self._NO_SINCNET_LENGTHS)
         return self.adapt_step(batch, batch_idx, accumulate=accumulate, lstm_layers=self.model.hparams.lstm["num_layers"],
                                dropout=self.model.train_dropout, seed=torch.initial_seed(),
-                               sincnet_stages=3 if self.model_name == "PyanNet" else 0)
+                               sincnet_stages=3 if self.model_name == "PyanNet" else 0, optim=optim)
 
     def train_commit(self):
         """adapt_commit: serve the trained tensors and write them into self.model's parameters."""

@@ -1387,6 +1387,7 @@ class VadRuntime:
                     off += cnt
                 out[name] = d
             w = self._head_train_block(h, _lib.HEAD_TRAIN_SCALARS)[:_lib.HEAD_TRAIN_SCALAR_WORDS]
+        out["scalars"] = torch.from_numpy(w.view(np.int32).copy())   # the raw record: what head_train_write takes back
         out["loss"] = float(w[0:2].view(np.float64)[0])
         out["frames"] = int(w[2:4].view(np.uint64)[0])
         out["step"] = int(w[4:6].view(np.uint64)[0])
@@ -1444,7 +1445,7 @@ class VadRuntime:
             h = {"cfg": cfg, "P": P, "layers": layers, "first_layer": cfg.first_layer, "ws": None, "bt": None,
                  "dropout": dropout, "seed": int(seed) & 0xFFFFFFFFFFFFFFFF,
                  "state": torch.empty(int(self.lib.uvad_lstm_train_state_bytes(self.ctx)), dtype=torch.uint8, device=self.device),
-                 "out": torch.zeros(max(P, _lib.HEAD_TRAIN_SCALAR_WORDS), dtype=torch.float32, device=self.device)}
+                 "out": torch.zeros(max(P, _lib.LSTM_TRAIN_SCALAR_WORDS), dtype=torch.float32, device=self.device)}
             self._check(self.lib.uvad_lstm_train_reset(self.ctx, h["state"].data_ptr(), h["state"].numel(), self._stream()))
             return h
 
@@ -1634,7 +1635,7 @@ class VadRuntime:
 
     def lstm_train_read(self, h) -> dict:
         """Copy the state to the host (synchronises) -> {"weights", "grad", "m", "v": {torch key: tensor}, "frames", "step",
-        "bias_correction1", "bias_correction2" (1 - beta^step)}."""
+        "bias_correction1", "bias_correction2" (1 - beta^step), "draws" (the dropout draw ordinal), "scalars" (the raw record)}."""
         with torch.cuda.device(self.device):
             self._lstm_train_configure(h)
             out = {}
@@ -1645,7 +1646,9 @@ class VadRuntime:
                     d[key] = torch.from_numpy(flat[off:off + cnt].reshape(shape).copy())
                     off += cnt
                 out[name] = d
-            w = self._lstm_train_block(h, _lib.HEAD_TRAIN_SCALARS)[:_lib.HEAD_TRAIN_SCALAR_WORDS]
+            w = self._lstm_train_block(h, _lib.HEAD_TRAIN_SCALARS)[:_lib.LSTM_TRAIN_SCALAR_WORDS]
+        out["scalars"] = torch.from_numpy(w.view(np.int32).copy())   # the raw record: what lstm_train_write takes back
+        out["draws"] = int(w[8:10].view(np.uint64)[0])
         out["frames"] = int(w[2:4].view(np.uint64)[0])
         out["step"] = int(w[4:6].view(np.uint64)[0])
         out["bias_correction1"], out["bias_correction2"] = float(w[6]), float(w[7])
@@ -1769,6 +1772,7 @@ class VadRuntime:
             nf, ks = self._sn_c.n_filters, self._sn_c.kernel_size
             out["filters"] = torch.from_numpy(self._sincnet_train_block(h, _lib.SINCNET_TRAIN_FILTERS)[:nf * ks].reshape(nf, ks).copy())
             w = self._sincnet_train_block(h, _lib.HEAD_TRAIN_SCALARS)[:_lib.HEAD_TRAIN_SCALAR_WORDS]
+        out["scalars"] = torch.from_numpy(w.view(np.int32).copy())   # the raw record: what sincnet_train_write takes back
         out["frames"] = int(w[2:4].view(np.uint64)[0])
         out["step"] = int(w[4:6].view(np.uint64)[0])
         out["bias_correction1"], out["bias_correction2"] = float(w[6]), float(w[7])
@@ -1786,6 +1790,121 @@ class VadRuntime:
             self._check(self.lib.uvad_sincnet_train_configure(self.ctx, C.byref(h["cfg"])))
             self._check(self.lib.uvad_sincnet_train_commit(self.ctx, h["state"].data_ptr(), h["state"].numel()))
             self._weights_gen = getattr(self, "_weights_gen", 0) + 1
+
+    # ------------------------------------------------------------------ the joint optimizer step (uvad_optim_*) and the _write calls
+    def optim_open(self, cfg=None, lr_table=(1e-3,)):
+        """Allocate and reset an optimizer state (uvad_optim_reset).  cfg: {"betas": (0.9, 0.999), "eps": 1e-8, "max_norm": 0 (no
+        clipping), "weight_decay": 0, "adamw": False (L2 into the gradient; True: decoupled), "skip_nonfinite": False, "lr_scale": (1, 1, 1)
+        for head, LSTM, SincNet}.  lr_table: the learning rate of applied step t is lr_table[min(t, len - 1)], rounded to f32 here.  The
+        handle owns the state and the workspace."""
+        cfg = dict(cfg or {})
+        known = {"betas", "eps", "max_norm", "weight_decay", "adamw", "skip_nonfinite", "lr_scale"}
+        if set(cfg) - known:
+            raise ValueError(f"optim_open: unknown option(s) {sorted(set(cfg) - known)}")
+        betas, scale = cfg.get("betas", (0.9, 0.999)), tuple(cfg.get("lr_scale", (1.0, 1.0, 1.0)))
+        if len(scale) != 3:
+            raise ValueError("lr_scale needs three entries: head, LSTM, SincNet")
+        q = _lib.OptimCfg(float(betas[0]), float(betas[1]), float(cfg.get("eps", 1e-8)), float(cfg.get("max_norm", 0.0) or 0.0),
+                          float(cfg.get("weight_decay", 0.0) or 0.0), int(bool(cfg.get("adamw", False))), int(bool(cfg.get("skip_nonfinite", False))),
+                          (C.c_float * 3)(*[float(v) for v in scale]))
+        table = np.ascontiguousarray(np.asarray(lr_table, np.float64).reshape(-1).astype(np.float32))
+        with torch.cuda.device(self.device):
+            o = {"cfg": q, "n": int(table.size), "ws": None, "table": table,
+                 "state": torch.zeros(max(int(self.lib.uvad_optim_state_bytes(int(table.size))), 256), dtype=torch.uint8, device=self.device),
+                 "out": torch.zeros(_lib.OPTIM_RECORD_WORDS, dtype=torch.int32, device=self.device)}
+            self._check(self.lib.uvad_optim_reset(self.ctx, o["state"].data_ptr(), o["state"].numel(), C.byref(q),
+                                                  table.ctypes.data_as(C.POINTER(C.c_float)), int(table.size), self._stream()))
+            return o
+
+    def optim_set_lr(self, o, table):
+        """Rewrite the learning-rate table between steps (uvad_optim_set_lr_table): at most optim_open's entry count; a captured graph
+        picks the new values up on its next replay.  Synchronises the stream."""
+        table = np.ascontiguousarray(np.asarray(table, np.float64).reshape(-1).astype(np.float32))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_optim_set_lr_table(self.ctx, o["state"].data_ptr(), o["state"].numel(),
+                                                         table.ctypes.data_as(C.POINTER(C.c_float)), int(table.size), self._stream()))
+        o["table"] = table
+
+    def optim_step(self, o, head=None, lstm=None, sincnet=None):
+        """One joint step over the handles given (uvad_optim_step) in place of their _apply calls: the global gradient norm, clipping,
+        weight decay, the table's learning rate, Adam; no copy to the host and no synchronisation, so once the workspace exists the call
+        can be captured."""
+        if head is None and lstm is None and sincnet is None:
+            raise ValueError("optim_step needs at least one training handle")
+        with torch.cuda.device(self.device):
+            if head is not None:
+                self._check(self.lib.uvad_head_train_configure(self.ctx, C.byref(head["cfg"])))
+            if lstm is not None:
+                self._lstm_train_configure(lstm)
+            if sincnet is not None:
+                self._check(self.lib.uvad_sincnet_train_configure(self.ctx, C.byref(sincnet["cfg"])))
+            need = int(self.lib.uvad_optim_ws_bytes(self.ctx))
+            if o["ws"] is None or o["ws"].numel() < need:
+                o["ws"] = torch.zeros(need, dtype=torch.uint8, device=self.device)
+            arg = lambda h: (h["state"].data_ptr(), h["state"].numel()) if h is not None else (None, 0)
+            self._check(self.lib.uvad_optim_step(self.ctx, *arg(head), *arg(lstm), *arg(sincnet), o["state"].data_ptr(), o["state"].numel(),
+                                                 o["ws"].data_ptr(), o["ws"].numel(), self._stream()))
+
+    def optim_read(self, o) -> dict:
+        """The record of the last step and the counts (uvad_optim_read; synchronises) -> {"norm", "coef", "lr" (of the last step that had
+        a participant), "took_part": (head, LSTM, SincNet), "step" (applied steps), "skipped", "record": the raw words, an int32 tensor}."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_optim_read(self.ctx, o["state"].data_ptr(), o["state"].numel(), o["out"].data_ptr(), self._stream()))
+            w = o["out"].cpu().numpy().copy()
+        f, u = w.view(np.float32), w.view(np.uint32)
+        return {"norm": float(f[0]), "coef": float(f[1]), "lr": float(f[2]), "took_part": tuple(bool(int(u[3]) >> k & 1) for k in range(3)),
+                "step": int(u[4:6].view(np.uint64)[0]), "skipped": int(u[6:8].view(np.uint64)[0]), "record": torch.from_numpy(w)}
+
+    def optim_write(self, o, record):
+        """Put back what optim_read returned (its dict or its "record" tensor; uvad_optim_write): the counts and the last step's record."""
+        rec = record["record"] if isinstance(record, dict) else record
+        with torch.cuda.device(self.device):
+            src = torch.as_tensor(rec).to(torch.int32).reshape(-1)[:_lib.OPTIM_RECORD_WORDS].contiguous().to(self.device)
+            self._check(self.lib.uvad_optim_write(self.ctx, o["state"].data_ptr(), o["state"].numel(), src.data_ptr(), self._stream()))
+            o["_keep_w"] = src
+
+    def _train_write(self, h, fn, keys, st):
+        """The _write companion of a family's _read: st["weights"], st["m"], st["v"] ({torch key: tensor}) and st["scalars"] (the raw words)."""
+        keep = []
+        for name, which in (("weights", _lib.HEAD_TRAIN_MASTERS), ("m", _lib.HEAD_TRAIN_M), ("v", _lib.HEAD_TRAIN_V)):
+            if st.get(name) is None:
+                continue
+            parts = []
+            for key, shape in keys:
+                t = torch.as_tensor(st[name][key]).detach().to(torch.float32).cpu()
+                if tuple(t.shape) != tuple(shape):
+                    raise ValueError(f"{name}[{key}] has shape {tuple(t.shape)}, expected {tuple(shape)}")
+                parts.append(t.reshape(-1))
+            flat = torch.cat(parts).contiguous().to(self.device)
+            self._check(fn(self.ctx, h["state"].data_ptr(), h["state"].numel(), which, flat.data_ptr(), self._stream()))
+            keep.append(flat)
+        if st.get("scalars") is not None:
+            words = torch.zeros(_lib.LSTM_TRAIN_SCALAR_WORDS, dtype=torch.int32)
+            src = torch.as_tensor(st["scalars"]).to(torch.int32).reshape(-1)
+            words[:src.numel()] = src[:words.numel()]
+            words = words.to(self.device)
+            self._check(fn(self.ctx, h["state"].data_ptr(), h["state"].numel(), _lib.HEAD_TRAIN_SCALARS, words.data_ptr(), self._stream()))
+            keep.append(words)
+        h["_keep_w"] = keep          # the launches read them after this call returns
+
+    def head_train_write(self, h, st):
+        """Put back what head_train_read returned (uvad_head_train_write): masters, m, v, and from "scalars" the step and the bias
+        corrections.  The accumulated gradient, loss and frames are not written: a write belongs between steps."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_head_train_configure(self.ctx, C.byref(h["cfg"])))
+            self._train_write(h, self.lib.uvad_head_train_write, self.head_train_keys(), st)
+
+    def lstm_train_write(self, h, st):
+        """head_train_write for an LSTM handle (uvad_lstm_train_write); "scalars" carries the dropout draw ordinal as well."""
+        with torch.cuda.device(self.device):
+            self._lstm_train_configure(h)
+            self._train_write(h, self.lib.uvad_lstm_train_write, self.lstm_train_keys(h["layers"]), st)
+
+    def sincnet_train_write(self, h, st):
+        """head_train_write for a SincNet handle (uvad_sincnet_train_write); the bank is rebuilt from the masters by the next forward call."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.uvad_sincnet_train_configure(self.ctx, C.byref(h["cfg"])))
+            self._train_write(h, self.lib.uvad_sincnet_train_write, self.sincnet_train_keys(h["first_stage"]), st)
 
     # ------------------------------------------------------------------ scoring against reference labels (uvad_score_*)
     def score_open(self, points=((0.5, 25),), collar: int = 0, bins: int = 256, segment: int = 0):

@@ -786,7 +786,9 @@ def adapt_vad(**kwargs):
     Saves a Lightning-style checkpoint {"state_dict" (``model.`` keys), "epoch", "global_step"} to ``adapted_checkpoint_path`` (default:
     experiments_dir/adapted.ckpt) and returns {"train_loss": [per epoch], "val_loss": [(epoch, loss)], "val_metrics", "checkpoint_path"}.
     ``adapt_lstm_layers`` > 0: that many top LSTM layers learn as well (VadModel.adapt_step / adapt_commit); what is cached per recording
-    is then the frozen prefix's output, the input of the lowest learning layer."""
+    is then the frozen prefix's output, the input of the lowest learning layer.  With them, train_vad's optimizer options apply
+    (``gradient_clip_val``, ``weight_decay`` with ``adamw``, ``lr_schedule``, ``skip_nonfinite``: every step then ends in one
+    uvad_optim_step), and the checkpoint carries "optimizer_states"; continuing an interrupted run is train_vad's."""
     from .postprocess import read_label_file, supervision_frames
     src = kwargs["input"]
     if src.get("kind") != "wav" or not src.get("paths") or len(src.get("labels", ())) != len(src["paths"]):
@@ -845,11 +847,15 @@ def adapt_vad(**kwargs):
         out["val_loss"].append((epoch, out["val_metrics"]["val_loss"]))
         print(f"epoch {epoch}: val_loss {out['val_metrics']['val_loss']:.6f}")
 
+    optim = _optim_options(kwargs, lr, epochs * len(train) // accumulate)
+    if optim is not None and not lstm_layers:
+        raise ValueError("adapt_vad: gradient_clip_val, weight_decay, lr_schedule and skip_nonfinite need adapt_lstm_layers > 0 (the joint "
+                         "optimizer step runs in VadModel.adapt_step)")
     validate(0)
     step = 0
     for epoch in range(1, epochs + 1):
         if lstm_layers:
-            losses = [model.adapt_step(b, i, accumulate=accumulate, lstm_layers=lstm_layers) for i, b in enumerate(train)]
+            losses = [model.adapt_step(b, i, accumulate=accumulate, lstm_layers=lstm_layers, optim=optim) for i, b in enumerate(train)]
         else:
             losses = [model.adapt_head_step(b, i, accumulate=accumulate) for i, b in enumerate(train)]
         step += len(train)
@@ -859,9 +865,71 @@ def adapt_vad(**kwargs):
     path = kwargs.get("adapted_checkpoint_path") or os.path.join(kwargs.get("experiments_dir", "."), "adapted.ckpt")
     if os.path.dirname(path):
         os.makedirs(os.path.dirname(path), exist_ok=True)
-    torch.save({"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "epoch": epochs, "global_step": step // accumulate}, path)
+    blob = {"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "epoch": epochs, "global_step": step // accumulate}
+    if lstm_layers:
+        blob["optimizer_states"] = model.optimizer_state()
+    torch.save(blob, path)
     out["checkpoint_path"] = path
     return out
+
+
+def lr_schedule_table(schedule, base_lr: float, total_steps: int) -> np.ndarray:
+    """The learning rate of every optimizer step t = 0 .. total_steps - 1 as a float64 array (uvad_optim_reset rounds the entries to f32):
+    the table uvad_optim_step indexes with its count of applied steps.  schedule = None or {"name": ..., "warmup_steps": w (default 0), ...}:
+      "constant"  base_lr;
+      "warmup"    base_lr min(1, (t + 1) / w): torch's LambdaLR with that factor;
+      "linear"    the warmup, then base_lr (1 - (1 - end_factor) (t - w) / (total_steps - w)), end_factor default 0;
+      "cosine"    the warmup, then eta_min + (base_lr - eta_min) (1 + cos(pi (t - w) / (total_steps - w))) / 2: CosineAnnealingLR with
+                  T_max = total_steps - w, eta_min default 0;
+      "step"      the warmup times base_lr gamma^((t - w) // step_size): StepLR (gamma default 0.1).
+    Every entry must come out finite and positive."""
+    total = max(1, int(total_steps))
+    sched = dict(schedule or {"name": "constant"})
+    name, w = sched.get("name", "constant"), max(0, int(sched.get("warmup_steps", 0) or 0))
+    if name not in ("constant", "warmup", "linear", "cosine", "step"):
+        raise ValueError(f"lr_schedule: unknown name {name!r}")
+    if name == "warmup" and w < 1:
+        raise ValueError('lr_schedule "warmup" needs warmup_steps >= 1')
+    base, out = float(base_lr), np.empty(total, np.float64)
+    span = max(1, total - w)
+    for t in range(total):
+        if t < w:
+            out[t] = base * min(1.0, (t + 1) / w)
+        elif name in ("constant", "warmup"):
+            out[t] = base
+        elif name == "linear":
+            out[t] = base * (1.0 - (1.0 - float(sched.get("end_factor", 0.0))) * (t - w) / span)
+        elif name == "cosine":
+            lo = float(sched.get("eta_min", 0.0))
+            out[t] = lo + (base - lo) * (1.0 + math.cos(math.pi * (t - w) / span)) / 2.0
+        else:
+            out[t] = base * float(sched.get("gamma", 0.1)) ** ((t - w) // max(1, int(sched.get("step_size", 1))))
+    if not (np.isfinite(out).all() and (out.astype(np.float32) > 0).all()):
+        raise ValueError("lr_schedule: every learning rate must be finite and positive in f32")
+    return out
+
+
+def _optim_options(kwargs, lr: float, total_steps: int):
+    """train_vad / adapt_vad's optimizer options -> the optim= dict of VadModel.train_step, or None when none is set (the run then ends
+    every step in the _apply calls, as before the options existed)."""
+    clip, wd = float(kwargs.get("gradient_clip_val") or 0.0), float(kwargs.get("weight_decay") or 0.0)
+    sched, skip = kwargs.get("lr_schedule"), bool(kwargs.get("skip_nonfinite", False))
+    if clip == 0.0 and wd == 0.0 and sched is None and not skip:
+        return None
+    return {"max_norm": clip, "weight_decay": wd, "adamw": bool(kwargs.get("adamw", False)), "skip_nonfinite": skip,
+            "lr_table": [float(v) for v in lr_schedule_table(dict(sched) if sched is not None else None, lr, total_steps)]}
+
+
+def _resume_point(kwargs, model):
+    """With load_checkpoint and a checkpoint that carries "optimizer_states": hand them to the model (VadModel.load_optimizer_state) and
+    -> (its epoch, its global_step): training continues from there.  Otherwise (0, 0): the checkpoint gives the weights only."""
+    if not kwargs.get("load_checkpoint"):
+        return 0, 0
+    blob = torch.load(kwargs["checkpoint_path"], map_location="cpu", weights_only=True)
+    if not isinstance(blob, dict) or blob.get("optimizer_states") is None:
+        return 0, 0
+    model.load_optimizer_state(blob["optimizer_states"])
+    return int(blob.get("epoch", 0)), int(blob.get("global_step", 0))
 
 
 def _open_noise(kwargs, rt, seed, sr=16000):
@@ -887,6 +955,20 @@ def _open_noise(kwargs, rt, seed, sr=16000):
             raise ValueError(f"{p}: an empty noise file")
     return rt.mix_open(np.concatenate(clips), [len(c) for c in clips], snr=noise.get("snr", (10, 20)), mix_prob=mix_prob,
                        snr_steps=int(noise.get("snr_steps", 1024)), max_seg=int(noise.get("max_seg", 8)), seed=int(noise.get("seed", seed)))
+
+
+def _save_training_checkpoint(kwargs, model, out, epoch: int, global_step: int):
+    """train_vad's checkpoint: {"state_dict", "epoch", "global_step", "optimizer_states" (VadModel.optimizer_state: every family's masters,
+    m, v and scalars, and the joint optimizer's counts)} at experiments_dir/checkpoint-epoch=NN.ckpt -> out, completed."""
+    path = os.path.join(kwargs.get("experiments_dir", "."), f"checkpoint-epoch={epoch:02d}.ckpt")
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    out["global_step"] = global_step
+    blob = {"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "epoch": epoch, "global_step": global_step}
+    if getattr(model, "_adapt_full", None) is not None:
+        blob["optimizer_states"] = model.optimizer_state()
+    torch.save(blob, path)
+    out["checkpoint_path"] = path
+    return out
 
 
 def _train_vad_sincnet(kwargs, src, val_paths, val_labels, model, rt, device, seed, sr):
@@ -943,8 +1025,12 @@ def _train_vad_sincnet(kwargs, src, val_paths, val_labels, model, rt, device, se
         out["val_loss"].append((epoch, out["val_metrics"]["val_loss"]))
         print(f"epoch {epoch}: val_loss {out['val_metrics']['val_loss']:.6f}")
 
-    step = 0
-    for epoch in range(1, epochs + 1):
+    per_epoch = sum((sum(1 for w in windows if w[2] == n) + rows - 1) // rows for n in {w[2] for w in windows})
+    optim = _optim_options(kwargs, float(kwargs.get("learning_rate", 1e-3)), epochs * per_epoch // accumulate)
+    first, done = _resume_point(kwargs, model)
+    last = min(epochs, int(kwargs.get("stop_after_epoch") or epochs))
+    step = done * accumulate
+    for epoch in range(first + 1, last + 1):
         order = torch.randperm(len(windows), generator=torch.Generator().manual_seed(seed + epoch)).tolist()
         by_len = {}
         for k in order:                                               # rows of one length per batch, in the shuffled order
@@ -957,18 +1043,13 @@ def _train_vad_sincnet(kwargs, src, val_paths, val_labels, model, rt, device, se
                 y = torch.cat([lab for _, _, _, lab in picks])
                 if mix is not None:
                     rt.mix_step(mix, x, out=x)                        # a fresh draw per batch, in place
-                losses.append(model.train_step({"inputs": x, "is_voice": y}, step, accumulate=accumulate))
+                losses.append(model.train_step({"inputs": x, "is_voice": y}, step, accumulate=accumulate, optim=optim))
                 step += 1
         out["train_loss"].append(float(torch.stack(losses).mean()))
         print(f"epoch {epoch}: train_loss {out['train_loss'][-1]:.6f}")
-        if epoch % every == 0 or epoch == epochs:
+        if epoch % every == 0 or epoch == last:
             validate(epoch)
-    path = os.path.join(kwargs.get("experiments_dir", "."), f"checkpoint-epoch={epochs:02d}.ckpt")
-    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-    out["global_step"] = step // accumulate
-    torch.save({"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "epoch": epochs, "global_step": out["global_step"]}, path)
-    out["checkpoint_path"] = path
-    return out
+    return _save_training_checkpoint(kwargs, model, out, last, step // accumulate)
 
 
 def train_vad(**kwargs):
@@ -985,8 +1066,18 @@ def train_vad(**kwargs):
     device and framed with its rows' own lengths; ``noise = None`` launches what a run without the option launches.  Every
     ``check_val_every_n_epoch`` epochs (and after the last) the tensors are committed and validation_step runs on the held-out
     recordings (``input.val_paths``; the training files without them).  Saves a Lightning-style checkpoint {"state_dict" (``model.``
-    keys), "epoch", "global_step"} to experiments_dir/checkpoint-epoch=NN.ckpt and returns {"train_loss": [per epoch], "val_loss":
-    [(epoch, loss)], "val_metrics", "checkpoint_path", "global_step"}."""
+    keys), "epoch", "global_step", "optimizer_states"} to experiments_dir/checkpoint-epoch=NN.ckpt and returns {"train_loss": [per epoch],
+    "val_loss": [(epoch, loss)], "val_metrics", "checkpoint_path", "global_step"}.
+    Optimizer options (all off: every step ends in the three _apply calls and launches what it launched before they existed):
+    ``gradient_clip_val`` (the global gradient norm over every learning tensor is clipped to it), ``weight_decay`` with ``adamw`` (False:
+    L2 into the gradient; True: decoupled), ``lr_schedule`` (lr_schedule_table: a table over the run's epochs x batches // accumulate
+    optimizer steps, built here and indexed on the device) and ``skip_nonfinite``; with any of them every step ends in one
+    uvad_optim_step (VadModel.train_step's optim=).  ``stop_after_epoch`` ends the run early with that epoch's checkpoint.  With
+    ``load_checkpoint`` and a checkpoint that carries "optimizer_states" the run CONTINUES: moments, step counts, bias corrections, the
+    dropout draw ordinal and the optimizer's step index are restored and the epochs after the checkpoint's run, so that an interrupted
+    run and an uninterrupted one end in the same bytes (with accumulate_grad_batches > 1 a partly accumulated step at the interruption
+    is lost).  The noise mix's draw ordinal is not part of the checkpoint: a resumed run with ``noise`` draws other mixes than an
+    uninterrupted one."""
     from .postprocess import read_label_file, supervision_frames
     src = kwargs["input"]
     if src.get("kind") != "wav" or not src.get("paths") or len(src.get("labels", ())) != len(src["paths"]):
@@ -1091,20 +1182,18 @@ def train_vad(**kwargs):
         out["val_loss"].append((epoch, out["val_metrics"]["val_loss"]))
         print(f"epoch {epoch}: val_loss {out['val_metrics']['val_loss']:.6f}")
 
-    step = 0
-    for epoch in range(1, epochs + 1):
+    optim = _optim_options(kwargs, lr, epochs * ((len(windows) + rows - 1) // rows) // accumulate)
+    first, done = _resume_point(kwargs, model)
+    last = min(epochs, int(kwargs.get("stop_after_epoch") or epochs))
+    step = done * accumulate
+    for epoch in range(first + 1, last + 1):
         order = torch.randperm(len(windows), generator=torch.Generator().manual_seed(seed + epoch)).tolist()
         losses = []
         for i in range(0, len(order), rows):
-            losses.append(model.train_step(batch_of([windows[k] for k in order[i:i + rows]]), step, accumulate=accumulate))
+            losses.append(model.train_step(batch_of([windows[k] for k in order[i:i + rows]]), step, accumulate=accumulate, optim=optim))
             step += 1
         out["train_loss"].append(float(torch.stack(losses).mean()))
         print(f"epoch {epoch}: train_loss {out['train_loss'][-1]:.6f}")
-        if epoch % every == 0 or epoch == epochs:
+        if epoch % every == 0 or epoch == last:
             validate(epoch)
-    path = os.path.join(kwargs.get("experiments_dir", "."), f"checkpoint-epoch={epochs:02d}.ckpt")
-    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-    out["global_step"] = step // accumulate
-    torch.save({"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "epoch": epochs, "global_step": out["global_step"]}, path)
-    out["checkpoint_path"] = path
-    return out
+    return _save_training_checkpoint(kwargs, model, out, last, step // accumulate)
