@@ -159,7 +159,8 @@ def _poisoned(x, dy, valid):
 
 
 # (Din, H, dirs, B, T): every hidden size, direction count, Din (60 is no multiple of the GEMM's k chunk), B around the 4-sequence tile and T
-# around the prefetch depth; segment 32, so that with B T = 185 the segment boundaries fall inside rows
+# around the prefetch depth; segment 32, so that with B T = 185 the segment boundaries fall inside rows (the default segment, with several
+# k-chunks per segment and a ragged last one, T 500 and four layers: tests/test_gpu_train_reference_size.py)
 CONFIGS = [(4, 64, 1, 1, 1), (60, 64, 2, 4, 2), (80, 128, 1, 9, 5), (256, 128, 2, 5, 37), (80, 64, 2, 5, 37)]
 _SHARED = {}
 
@@ -310,13 +311,17 @@ def test_backward_on_a_workspace_of_another_shape_writes_nothing():
 
 
 # ------------------------------------------------------------------------------------------------ accuracy
-def _pooled_ratios(cases, layers, first):
-    """cases: [(params, x, dy, lens, kernel outputs {name: array})] -> {name: (kernel rms, kernel max, torch rms, torch max)} pooled."""
+def _pooled_ratios(cases, layers, first, refs=None):
+    """cases: [(params, x, dy, lens, kernel outputs {name: array})] -> {name: (kernel rms, kernel max, torch rms, torch max)} pooled.
+    refs: per case the (float64 restatement, torch f32) pair where the caller shares them; None: computed here."""
     pool = {}
-    for params, x, dy, lens, got, shape in cases:
+    for ci, (params, x, dy, lens, got, shape) in enumerate(cases):
         Din, H, dirs = shape[:3]
-        truth = R.forward_backward(params, x, dy, H, dirs, layers, first, lens)
-        cpu = R.torch_forward_backward(params, x, dy, H, dirs, layers, first, lens, dtype=torch.float32)
+        if refs is not None:
+            truth, cpu = refs[ci]
+        else:
+            truth = R.forward_backward(params, x, dy, H, dirs, layers, first, lens)
+            cpu = R.torch_forward_backward(params, x, dy, H, dirs, layers, first, lens, dtype=torch.float32)
         names = [("y", truth["y"], cpu["y"]), ("grad_in", truth["grad_in"], cpu["grad_in"])]
         names += [(k, truth["grads"][k], cpu["grads"][k]) for k in truth["grads"]]
         for k, t, c in names:
@@ -399,10 +404,10 @@ def test_apply_equals_the_f32_adam_restatement_bit_for_bit():
     assert bytes(tr.sbuf.cpu().numpy()) == before and tr.canaries_intact()
 
 
-def _torch_model(sd, Din, H, dtype):
-    """The seeded one-layer bidirectional model with the head 32 / 1 as torch modules on the CPU -> (parameters, forward(x, lens) -> p (B, T))."""
+def _torch_model(sd, Din, H, dtype, layers=1):
+    """The seeded bidirectional model of `layers` layers with the head 32 / 1 as torch modules on the CPU -> (parameters, forward(x, lens) -> p (B, T))."""
     from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence
-    lstm = torch.nn.LSTM(Din, H, 1, batch_first=True, bidirectional=True).to(dtype)
+    lstm = torch.nn.LSTM(Din, H, layers, batch_first=True, bidirectional=True).to(dtype)
     with torch.no_grad():
         for name, prm in lstm.named_parameters():
             prm.copy_(sd["lstm." + name].to(dtype))

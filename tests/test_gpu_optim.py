@@ -4,6 +4,8 @@ Chains, the smallest that still have several reduction chunks and a ragged tail:
              chunks, the second ragged), LSTM P = 174080 (42.5 chunks)
   "sincnet"  PyanNet (one bidirectional 64-unit layer, head 32 / 1), B 2, S 991 (one frame): all three families
   "head0"    a head without feed-forward layers on D0 = 64: P = 65, less than a chunk
+A family of more than 256 chunks, whose partials opt_fold_kernel takes through LDS in a second pass (256, 257 and the reference model's 342),
+lives in tests/test_gpu_train_reference_size.py, which builds its chains here through Chain's shape arguments.
 Cases: off is off, clipping, weight decay, the table and lr_scale, absent and idle states, a non-finite step, a captured graph, the device
 guards, the read / write round trip into a fresh context, and train_vad with every option and a resumed run."""
 import ctypes as C
@@ -38,13 +40,14 @@ def _flat(d):
 class Chain:
     """One of the three chains on a fresh runtime: handles, seeded batches, forward / backward, and either kind of step."""
 
-    def __init__(self, kind, dropout=0.0, lr=1e-3, rt=None):
-        self.kind, self.hl, self.hs, self.lens = kind, None, None, None
+    def __init__(self, kind, dropout=0.0, lr=1e-3, rt=None, Din=80, H=64, layers=2, B=3, T=19, lens=(19, 7, 1)):
+        """Din, H, layers, B, T, lens: the "lstm" chain's model and batch (the defaults are the chain of the module's docstring)."""
+        self.kind, self.hl, self.hs, self.lens, self.Din = kind, None, None, None, Din if kind == "lstm" else 64
         if kind == "lstm":
-            self.rt = rt or T0._runtime(80, 64, 2, 2)[0]
+            self.rt = rt or T0._runtime(Din, H, 2, layers)[0]
             self.hh = self.rt.head_train_open(lr=lr, segment=32)
-            self.hl = self.rt.lstm_train_open(layers=2, lr=lr, segment=32, dropout=dropout, seed=11)
-            self.B, self.T, self.lens = 3, 19, torch.tensor([19, 7, 1], dtype=torch.int32, device=_dev())
+            self.hl = self.rt.lstm_train_open(layers=layers, lr=lr, segment=32, dropout=dropout, seed=11)
+            self.B, self.T, self.lens = B, T, torch.tensor(list(lens), dtype=torch.int32, device=_dev())
         elif kind == "sincnet":
             self.rt = rt or T2._model(SR.make_case(2, 991, 1)[0]).runtime(_dev())
             self.hh = self.rt.head_train_open(lr=lr, segment=32)
@@ -64,7 +67,7 @@ class Chain:
         if self.kind == "sincnet":
             x = torch.from_numpy(SR.make_case(self.B, 991, 70 + k)[1].astype(F32)).to(_dev())
         else:
-            x = torch.from_numpy(rng.standard_normal((self.B, self.T, 80 if self.kind == "lstm" else 64)).astype(F32)).to(_dev())
+            x = torch.from_numpy(rng.standard_normal((self.B, self.T, self.Din)).astype(F32)).to(_dev())
         return x, gt
 
     def fb(self, k=None, dz=None, data=None):

@@ -12,8 +12,8 @@
 //   ht_gemm_kernel<0>     a_l = leaky_relu(a_{l-1} W_l^T + b_l), kept in the workspace
 //   ht_cls_kernel         z = a_L . w_c + b_c, p = sigmoid(z), the loss terms in f64 and dz, one wave per frame; a loss partial per 256 frames
 //   ht_dlast_kernel       d_L = (dz w_c) * leaky'(a_L), or for a head without feed-forward layers d_grad_x = dz w_c
-//   ht_gemm_kernel<2>     dW_l = sum_n d_l[n][o] a_{l-1}[n][i] and db_l = sum_n d_l[n][o] (32-frame chunk sums, added in order) over one segment of
-//                         frames: a partial in the workspace
+//   ht_gemm_kernel<2>     dW_l = sum_n d_l[n][o] a_{l-1}[n][i] and db_l = sum_n d_l[n][o] (both as 32-frame chunk sums, added in order) over one
+//                         segment of frames: a partial in the workspace
 //   ht_gemm_kernel<1>     d_{l-1} = (d_l W_l) * leaky'(a_{l-1}); the last one is d_grad_x (no factor, +0 past the lengths)
 //   ht_fold_kernel        the partials in segment order into the accumulator, the loss partials and the frame count into the state: no
 //                         floating-point atomics anywhere, the same calls give the same bits
