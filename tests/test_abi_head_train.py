@@ -49,8 +49,10 @@ def test_entries_in_header_binding_and_export_list(built):
     mk = open(os.path.join(csrc, "Makefile")).read()
     assert re.search(r"^SRCS :=.*\bhead_train\.hip\b", mk, re.M) and re.search(r"^FLAGS_head_train := .*-ffp-contract=off", mk, re.M)
     kernel = open(os.path.join(csrc, "head_train.hip")).read()
-    for k in ("ht_gemm_kernel", "ht_cls_kernel", "ht_fold_kernel", "ht_adam_kernel", "__builtin_amdgcn_mfma_f32_32x32x2f32", "fp contract(off)"):
+    for k in ("ht_gemm_kernel", "ht_cls_kernel", "ht_fold_kernel", "__builtin_amdgcn_mfma_f32_32x32x2f32", "fp contract(off)"):
         assert k in kernel
+    # Adam and the read-out work on the state's blocks alone: one launcher for every family (optim.hip), none of its own and no launch here
+    assert not re.search(r"\blaunch_\w+_train_(apply|read)\s*\(", kernel) and not re.search(r"hipLaunchKernelGGL\(\s*ht_adam_kernel", kernel)
     assert "asm" not in kernel and "atomic" not in re.sub(r"//.*", "", kernel)     # no atomics at all: the same calls give the same bits
 
 

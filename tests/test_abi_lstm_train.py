@@ -55,9 +55,11 @@ def test_entries_in_header_binding_and_export_list(built):
     assert re.search(r"^SRCS :=.*\blstm_train\.hip\b", mk, re.M) and re.search(r"^FLAGS_lstm_train := .*-ffp-contract=off", mk, re.M)
     assert re.search(r"^%\.o:.*\bht_kernels\.h\b", mk, re.M)
     kernel = open(os.path.join(csrc, "lstm_train.hip")).read()
-    for k in ("lt_fwd_kernel", "lt_bwd_kernel", "ht_gemm_kernel<0>", "ht_gemm_kernel<1>", "ht_gemm_kernel<2>", "ht_fold_kernel", "ht_adam_kernel",
+    for k in ("lt_fwd_kernel", "lt_bwd_kernel", "ht_gemm_kernel<0>", "ht_gemm_kernel<1>", "ht_gemm_kernel<2>", "ht_fold_kernel",
               "__builtin_amdgcn_mfma_f32_4x4x1f32", '#include "ht_kernels.h"'):
         assert k in kernel, k
+    # Adam and the read-out work on the state's blocks alone: one launcher for every family (optim.hip), none of its own and no launch here
+    assert not re.search(r"\blaunch_\w+_train_(apply|read)\s*\(", kernel) and not re.search(r"hipLaunchKernelGGL\(\s*ht_adam_kernel", kernel)
     assert "atomic" not in re.sub(r"//.*", "", kernel)                          # no atomics at all: the same calls give the same bits
     # one copy of the tile kernel: defined in the shared header, in neither file
     shared = open(os.path.join(csrc, "ht_kernels.h")).read()

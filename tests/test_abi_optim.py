@@ -56,8 +56,14 @@ def test_entries_in_header_binding_and_export_list(built):
     mk = open(os.path.join(csrc, "Makefile")).read()
     assert re.search(r"^SRCS :=.*\boptim\.hip\b", mk, re.M) and re.search(r"^FLAGS_optim := .*-ffp-contract=off", mk, re.M)
     kernel = open(os.path.join(csrc, "optim.hip")).read()
-    for k in ("opt_sumsq_kernel", "opt_fold_kernel", "opt_adam_kernel", "opt_commit_kernel", "ht_write_kernel", "ht_state_ok"):
+    for k in ("opt_sumsq_kernel", "opt_fold_kernel", "opt_adam_kernel", "opt_commit_kernel", "ht_adam_kernel", "ht_adam_commit_kernel", "ht_read_kernel",
+              "ht_write_kernel", "ht_state_ok"):
         assert k in kernel
+    # one launcher each for the three families' _apply, _read and _write: defined once under csrc/, and that is here
+    every = {fn: open(os.path.join(csrc, fn)).read() for fn in sorted(os.listdir(csrc)) if fn.endswith((".hip", ".h"))}
+    for name in ("launch_train_apply", "launch_train_read", "launch_train_write"):
+        define = re.compile(rf"hipError_t\s+{name}\s*\([^;{{]*\)\s*\{{")
+        assert sum(len(define.findall(txt)) for txt in every.values()) == 1 and define.search(kernel), name
     assert "asm" not in kernel and "atomic" not in re.sub(r"//.*", "", kernel)      # no atomics at all: the same calls give the same bits
 
 

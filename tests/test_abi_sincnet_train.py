@@ -57,8 +57,10 @@ def test_entries_in_header_binding_and_export_list(built):
     assert re.search(r"^SRCS :=.*\blstm_train\.hip sincnet_train\.hip\b", mk, re.M) and re.search(r"^FLAGS_sincnet_train := .*-ffp-contract=off", mk, re.M)
     kernel = open(os.path.join(csrc, "sincnet_train.hip")).read()
     for k in ("st_bank_kernel", "st_conv_kernel", "st_wgrad_kernel", "st_dgrad_kernel", "st_norm_bwd_kernel", "st_bank_bwd_kernel", "ht_fold_kernel",
-              "ht_adam_kernel", "ht_read_kernel", "__builtin_amdgcn_mfma_f32_32x32x2f32(", '#include "ht_kernels.h"'):
+              "__builtin_amdgcn_mfma_f32_32x32x2f32(", '#include "ht_kernels.h"'):
         assert k in kernel, k
+    # Adam and the read-out work on the state's blocks alone: one launcher for every family (optim.hip), none of its own and no launch here
+    assert not re.search(r"\blaunch_\w+_train_(apply|read)\s*\(", kernel) and not re.search(r"hipLaunchKernelGGL\(\s*(ht_adam_kernel|ht_read_kernel)", kernel)
     assert "atomic" not in re.sub(r"//.*", "", kernel)                          # no atomics at all: the same calls give the same bits
 
 

@@ -510,3 +510,77 @@ def test_train_vad_without_the_options_runs_the_apply_path_as_before(tmp_path, m
     c = torch.load(off["checkpoint_path"], weights_only=True)
     assert off["train_loss"] == one["train_loss"] and _same(c["state_dict"], a["state_dict"])
     assert _same({k: c["optimizer_states"][k] for k in ("head", "lstm")}, a["optimizer_states"])
+
+
+# ---------------------------------------------------------------- a state belongs to its family
+# The smallest shapes the configure calls accept: a PyanNet of one unidirectional 64-unit LSTM layer and a 32 / 1 head behind the SincNet
+# geometry of tests/test_gpu_sincnet_train.py; first_layer = the last layer, first_stage = 2; B = 2, S = 991 (one frame).
+_FAMILIES = ("head", "lstm", "sincnet")
+E_STATE = -3
+
+
+@pytest.fixture(scope="module")
+def family_handles():
+    import uvad_amd
+    from uvad_amd.synth import seed_weights
+    m = uvad_amd.PyanNet(lstm={"hidden_size": 64, "num_layers": 1, "bidirectional": False, "dropout": 0.0}, linear={"hidden_size": 32, "num_layers": 1})
+    m.build()
+    seed_weights(m, 3, 1.0)
+    sd = m.state_dict()
+    with torch.no_grad():
+        for k, v in SR.make_case(2, 991, 1)[0].items():
+            sd["sincnet." + k].copy_(torch.from_numpy(np.ascontiguousarray(v, F32)))
+    rt = m.runtime(_dev())
+    hs = {"head": rt.head_train_open(segment=32), "lstm": rt.lstm_train_open(layers=1, segment=32),
+          "sincnet": rt.sincnet_train_open(first_stage=2, segment=32)}
+    # every state in a buffer as large as the largest, so that the size a foreign family is told is true
+    big = max(h["state"].numel() for h in hs.values())
+    for f, h in hs.items():
+        h["state"] = torch.zeros(big, dtype=torch.uint8, device=_dev())
+        rt._train_configure(h)
+        rt._check(getattr(rt.lib, f"uvad_{f}_train_reset")(rt.ctx, h["state"].data_ptr(), big, None))
+    return rt, hs, m
+
+
+@gpu
+@pytest.mark.parametrize("a,b", [(a, b) for a in _FAMILIES for b in _FAMILIES if a != b])
+def test_a_state_of_one_family_is_refused_by_another(family_handles, a, b):
+    rt, hs, _ = family_handles
+    st, n = hs[a]["state"], hs[a]["state"].numel()
+    torch.cuda.synchronize()
+    before = st.clone()
+    rt._train_configure(hs[b])                                                   # b is configured, and n is large enough for it
+    assert n >= int(getattr(rt.lib, f"uvad_{b}_train_state_bytes")(rt.ctx))
+    out = torch.zeros(max(h["out"].numel() for h in hs.values()), dtype=torch.float32, device=_dev())
+    fn = lambda op: getattr(rt.lib, f"uvad_{b}_train_{op}")
+    calls = {"apply": lambda: fn("apply")(rt.ctx, st.data_ptr(), n, None), "read": lambda: fn("read")(rt.ctx, st.data_ptr(), n, 0, out.data_ptr(), None),
+             "write": lambda: fn("write")(rt.ctx, st.data_ptr(), n, 0, out.data_ptr(), None), "commit": lambda: fn("commit")(rt.ctx, st.data_ptr(), n)}
+    for name, call in calls.items():
+        assert call() == E_STATE, (name, rt.lib.uvad_last_error(rt.ctx))
+        assert rt.lib.uvad_last_error(rt.ctx).decode() == f"uvad_{b}_train_{name}: call uvad_{b}_train_reset on this state first", name
+    torch.cuda.synchronize()
+    assert torch.equal(st, before) and not out.any()
+
+
+@gpu
+def test_the_shared_apply_reaches_each_family_with_its_own_state(family_handles):
+    rt, hs, _ = family_handles
+    wav = torch.from_numpy(SR.make_case(2, 991, 71)[1].astype(F32)).to(_dev())
+    gt = torch.tensor([[1], [0]], dtype=torch.uint8, device=_dev())
+    feats = rt.sincnet_train_forward(hs["sincnet"], wav)
+    assert tuple(feats.shape) == (2, 1, 60)
+    y = rt.lstm_train_forward(hs["lstm"], feats)
+    _, gx = rt.head_train_grad(hs["head"], y, gt, want_grad_x=True)
+    rt.sincnet_train_backward(hs["sincnet"], wav, rt.lstm_train_backward(hs["lstm"], feats, gx, want_grad_in=True))
+    read = {"head": rt.head_train_read, "lstm": rt.lstm_train_read, "sincnet": rt.sincnet_train_read}
+    apply = {"head": rt.head_train_apply, "lstm": rt.lstm_train_apply, "sincnet": rt.sincnet_train_apply}
+    for f in _FAMILIES:
+        r0 = read[f](hs[f])
+        assert r0["step"] == 0 and r0["frames"] > 0 and np.abs(_flat(r0["grad"])).max() > 0, f
+        apply[f](hs[f])
+        r1 = read[f](hs[f])
+        assert r1["step"] == 1 and r1["frames"] == 0 and not _flat(r1["grad"]).any(), f
+        assert _flat(r1["weights"]).shape == _flat(r0["weights"]).shape == (hs[f]["P"],) and not np.array_equal(_flat(r1["weights"]), _flat(r0["weights"])), f
+        for g in _FAMILIES:                                                       # ... and nobody else's
+            if g != f:
+                assert read[g](hs[g])["step"] == (1 if _FAMILIES.index(g) < _FAMILIES.index(f) else 0), (f, g)

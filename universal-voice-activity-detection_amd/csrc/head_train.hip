@@ -17,12 +17,13 @@
 //   ht_gemm_kernel<1>     d_{l-1} = (d_l W_l) * leaky'(a_{l-1}); the last one is d_grad_x (no factor, +0 past the lengths)
 //   ht_fold_kernel        the partials in segment order into the accumulator, the loss partials and the frame count into the state: no
 //                         floating-point atomics anywhere, the same calls give the same bits
-//   ht_adam_kernel        one Adam step over every trainable tensor, each operation rounded once in the order of tests/head_train_ref.py
-//   ht_reset_kernel, ht_read_kernel   the state from the context's head tensors; a tensor block or the scalars, copied out
+//   ht_reset_kernel       the state from the context's head tensors
+// The Adam step, the read-out and the write work on the state's blocks alone and serve every family: launch_train_apply / _read / _write
+// of optim.hip.
 // Contraction is off in the whole file (#pragma clang fp contract(off) in ht_kernels.h and the Makefile's flag): the elementwise arithmetic
 // is restated operation by operation on the CPU, and the matrix instruction is not affected.
-// ht_valid_kernel, ht_gemm_kernel (its products are __builtin_amdgcn_mfma_f32_32x32x2f32), ht_fold_kernel, ht_adam_kernel and
-// ht_read_kernel live in ht_kernels.h, which lstm_train.hip (uvad_lstm_train_*: the backward pass d_grad_x starts) includes as well.
+// ht_valid_kernel, ht_gemm_kernel (its products are __builtin_amdgcn_mfma_f32_32x32x2f32) and ht_fold_kernel live in ht_kernels.h, which
+// lstm_train.hip (uvad_lstm_train_*: the backward pass d_grad_x starts) and sincnet_train.hip include as well.
 #include "ht_kernels.h"
 
 namespace uvad {
@@ -267,22 +268,6 @@ hipError_t launch_head_train_grad(const HeadTrainShape &q, const HeadTrainGradAr
     HT_LAUNCHED();
 #undef HT_LAUNCHED
     return hipSuccess;
-}
-
-hipError_t launch_head_train_apply(const HeadTrainShape &q, const HeadTrainAdam &o, void *state, hipStream_t s) {
-    if (!state) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(ht_adam_kernel, dim3((unsigned)((q.P + 255) / 256)), dim3(256), 0, s, state, HT_MAGIC, q.P, q.Pp, o);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ht_adam_commit_kernel, dim3(1), dim3(64), 0, s, state, HT_MAGIC, q.P, o);
-    return hipGetLastError();
-}
-
-hipError_t launch_head_train_read(const HeadTrainShape &q, const void *state, int which, float *out, hipStream_t s) {
-    if (!state || !out || which < 0 || which > UVAD_HEAD_TRAIN_SCALARS) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(ht_read_kernel, dim3(which == UVAD_HEAD_TRAIN_SCALARS ? 1u : (unsigned)((q.P + 255) / 256)), dim3(256), 0, s, state,
-                       HT_MAGIC, q.P, q.Pp, which, out);
-    return hipGetLastError();
 }
 
 }  // namespace uvad

@@ -1,10 +1,11 @@
-// ht_kernels.h -- the training kernels that head_train.hip (uvad_head_train_*) and lstm_train.hip (uvad_lstm_train_*) share: the valid
-// mask, the exact-f32 tile GEMM ht_gemm_kernel<MODE> on v_mfma_f32_32x32x2_f32 with its segment partials, the fold of the partials in
-// segment order, Adam, and the read-out.  One copy of the source; each file that includes it compiles its own instances (the kernels sit in
-// an unnamed namespace), under that file's flags -- both files build with contraction off.
-// A state is HeadTrainHeader | masters [Pp] | gradient accumulator [Pp] | m [Pp] | v [Pp] for both families; the header's magic word tells
-// them apart.  A kernel may also be handed a GUARD: three words somewhere in device memory (a workspace header) that must hold the values
-// the launcher expects, or the kernel does nothing.
+// ht_kernels.h -- the training kernels that head_train.hip (uvad_head_train_*), lstm_train.hip (uvad_lstm_train_*) and sincnet_train.hip
+// (uvad_sincnet_train_*) share: the valid mask, the exact-f32 tile GEMM ht_gemm_kernel<MODE> on v_mfma_f32_32x32x2_f32 with its segment
+// partials, and the fold of the partials in segment order.  One copy of the source; each file that includes it compiles its own instances of
+// the kernels it launches (they sit in an unnamed namespace), under that file's flags -- every includer builds with contraction off.
+// A state is HeadTrainHeader | masters [Pp] | gradient accumulator [Pp] | m [Pp] | v [Pp] for every family; the header's magic word tells
+// them apart.  The kernels that work on those blocks alone -- Adam, its commit, the read-out and the write -- are in optim.hip, once, behind
+// launch_train_apply / _read / _write.  A kernel may also be handed a GUARD: three words somewhere in device memory (a workspace header) that
+// must hold the values the launcher expects, or the kernel does nothing.
 #pragma once
 #include "uvad_internal.h"
 #include "../../include/uvad.h"
@@ -185,59 +186,6 @@ __global__ __launch_bounds__(256) void ht_fold_kernel(void *state, unsigned magi
         hd->loss += lsh[0];
         hd->frames += vsh[0];
     }
-}
-
-// torch.optim.Adam (no weight decay, no amsgrad) with the running bias corrections 1 - beta^t; every operation one rounding
-__global__ __launch_bounds__(256) void ht_adam_kernel(void *state, unsigned magic, int P, int Pp, HeadTrainAdam o) {
-    if (!ht_state_ok(state, magic, P)) return;
-    HeadTrainHeader *hd = reinterpret_cast<HeadTrainHeader *>(state);
-    const unsigned long long frames = hd->frames;
-    if (frames == 0ull) return;                                  // nothing accumulated: no step
-    float *w = reinterpret_cast<float *>(hd + 1), *acc = w + Pp, *m = acc + Pp, *v = m + Pp;
-    const float cnt = (float)frames;
-    const float bc1 = hd->bc1 * o.b1 + o.omb1, bc2 = hd->bc2 * o.b2 + o.omb2;   // 1 - beta^t, advanced: see HeadTrainHeader
-    const float step_size = o.lr / bc1;
-    const float bc2s = sqrtf(bc2);
-    const int j = (int)blockIdx.x * 256 + threadIdx.x;
-    if (j < P) {
-        const float g = acc[j] / cnt;
-        float mj = m[j], vj = v[j];
-        mj = mj + (g - mj) * o.omb1;                             // exp_avg.lerp_(grad, 1 - beta1)
-        vj = vj * o.b2 + (o.omb2 * g) * g;                       // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-        const float denom = sqrtf(vj) / bc2s + o.eps;
-        w[j] = w[j] - step_size * (mj / denom);                  // param.addcdiv_(exp_avg, denom, value = -step_size)
-        m[j] = mj;
-        v[j] = vj;
-        acc[j] = 0.0f;
-    }
-}
-// after every workgroup of ht_adam_kernel has read the header: the step counted, the running corrections advanced, the sums zeroed
-__global__ void ht_adam_commit_kernel(void *state, unsigned magic, int P, HeadTrainAdam o) {
-    if (!ht_state_ok(state, magic, P)) return;
-    HeadTrainHeader *hd = reinterpret_cast<HeadTrainHeader *>(state);
-    if (threadIdx.x != 0 || hd->frames == 0ull) return;
-    hd->bc1 = hd->bc1 * o.b1 + o.omb1;
-    hd->bc2 = hd->bc2 * o.b2 + o.omb2;
-    hd->t += 1ull;
-    hd->loss = 0.0;
-    hd->frames = 0ull;
-}
-
-__global__ __launch_bounds__(256) void ht_read_kernel(const void *state, unsigned magic, int P, int Pp, int which, float *out) {
-    const HeadTrainHeader *hd = reinterpret_cast<const HeadTrainHeader *>(state);
-    const bool ok = ht_state_ok(state, magic, P);
-    if (which == UVAD_HEAD_TRAIN_SCALARS) {
-        // an LSTM state's record carries two more words, [8 .. 9]: the dropout draw ordinal (UVAD_LSTM_TRAIN_SCALAR_WORDS)
-        if (blockIdx.x == 0 && threadIdx.x < (magic == LT_MAGIC ? LT_SCALAR_WORDS : HT_SCALAR_WORDS)) {
-            const int i = threadIdx.x;
-            const unsigned long long q = i < 2 ? (unsigned long long)__double_as_longlong(hd->loss) : i < 4 ? hd->frames : i < 8 ? hd->t : hd->draws;
-            const unsigned word = i == 6 ? __float_as_uint(hd->bc1) : i == 7 ? __float_as_uint(hd->bc2) : (unsigned)(i & 1 ? q >> 32 : q);
-            reinterpret_cast<unsigned *>(out)[i] = ok ? word : 0u;
-        }
-        return;
-    }
-    const float *src = reinterpret_cast<const float *>(hd + 1) + (size_t)which * Pp;
-    for (int j = (int)blockIdx.x * 256 + threadIdx.x; j < P; j += (int)gridDim.x * 256) out[j] = ok ? src[j] : 0.0f;
 }
 
 inline size_t ht_align(size_t v) { return (v + 255) / 256 * 256; }

@@ -21,7 +21,7 @@
 //   ht_gemm_kernel<2>     dW_ih = sum dpre^T x and dW_hh = sum dpre^T h_prev per segment of frames; the bias partial rides along in both, which
 //                         is how bias_ih and bias_hh receive the same bits
 //   ht_gemm_kernel<1>     d_in = dpre W_ih, the second direction added to the first: the next lower layer's dy, or d_grad_in
-//   ht_fold_kernel, ht_adam_kernel, ht_read_kernel   as the head's
+//   ht_fold_kernel        as the head's; Adam, the read-out and the write are launch_train_apply / _read / _write of optim.hip
 // Dropout between the trainable layers (uvad_lstm_train_set_dropout; the mask is defined in include/uvad.h) is a stage of its own:
 //   lt_dropout_kernel     out = keep ? x scale : +0, one thread per group of four columns of one frame: one Philox4x32-10 call, one 16-byte
 //                         load, one 16-byte store.  In place over h[li] after layer li's forward recurrence and over the gradient buffer
@@ -551,22 +551,6 @@ hipError_t launch_dropout_apply(const float *x, float *out, long long rows, int 
     d.x = x; d.out = out; d.cq = cols / 4; d.groups = rows * d.cq; d.layer = layer;
     d.draw = draw; d.seed = seed; d.thr = thr; d.scale = scale;
     hipLaunchKernelGGL(lt_dropout_kernel, dim3((unsigned)((d.groups + 255) / 256)), dim3(256), 0, s, d);
-    return hipGetLastError();
-}
-
-hipError_t launch_lstm_train_apply(const LstmTrainShape &q, const HeadTrainAdam &o, void *state, hipStream_t s) {
-    if (!state) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(ht_adam_kernel, dim3((unsigned)((q.P + 255) / 256)), dim3(256), 0, s, state, LT_MAGIC, q.P, q.Pp, o);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ht_adam_commit_kernel, dim3(1), dim3(64), 0, s, state, LT_MAGIC, q.P, o);
-    return hipGetLastError();
-}
-
-hipError_t launch_lstm_train_read(const LstmTrainShape &q, const void *state, int which, float *out, hipStream_t s) {
-    if (!state || !out || which < 0 || which > UVAD_HEAD_TRAIN_SCALARS) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(ht_read_kernel, dim3(which == UVAD_HEAD_TRAIN_SCALARS ? 1u : (unsigned)((q.P + 255) / 256)), dim3(256), 0, s, state,
-                       LT_MAGIC, q.P, q.Pp, which, out);
     return hipGetLastError();
 }
 

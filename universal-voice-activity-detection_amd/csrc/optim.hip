@@ -14,7 +14,8 @@
 // A state takes part iff it is given, its header carries its family's magic word and parameter count, and its frame count is not zero; every
 // kernel decides that from the headers alone, which only the commit changes.  No atomics: the same calls give the same bits.
 // Contraction is off in the whole file, as in head_train.hip: tests/optim_ref.py restates the step operation by operation.
-// The _write calls of the three families (launch_train_write) live here too: they put back what ht_read_kernel copied out.
+// The kernels on one state's blocks live here too, once for the three families: ht_adam_kernel + ht_adam_commit_kernel (launch_train_apply:
+// a family's own _apply), ht_read_kernel (launch_train_read) and ht_write_kernel (launch_train_write), keyed by a TrainBlock's magic word.
 #include "ht_kernels.h"
 
 namespace uvad {
@@ -193,6 +194,60 @@ __global__ void opt_write_kernel(void *opt, int cap, const unsigned *in) {
     oh->skip = 0;
 }
 
+// ---- the kernels on one state's blocks: every family's _apply, _read and _write (launch_train_*) ----
+// torch.optim.Adam (no weight decay, no amsgrad) with the running bias corrections 1 - beta^t; every operation one rounding
+__global__ __launch_bounds__(256) void ht_adam_kernel(void *state, unsigned magic, int P, int Pp, HeadTrainAdam o) {
+    if (!ht_state_ok(state, magic, P)) return;
+    HeadTrainHeader *hd = reinterpret_cast<HeadTrainHeader *>(state);
+    const unsigned long long frames = hd->frames;
+    if (frames == 0ull) return;                                  // nothing accumulated: no step
+    float *w = reinterpret_cast<float *>(hd + 1), *acc = w + Pp, *m = acc + Pp, *v = m + Pp;
+    const float cnt = (float)frames;
+    const float bc1 = hd->bc1 * o.b1 + o.omb1, bc2 = hd->bc2 * o.b2 + o.omb2;   // 1 - beta^t, advanced: see HeadTrainHeader
+    const float step_size = o.lr / bc1;
+    const float bc2s = sqrtf(bc2);
+    const int j = (int)blockIdx.x * 256 + threadIdx.x;
+    if (j < P) {
+        const float g = acc[j] / cnt;
+        float mj = m[j], vj = v[j];
+        mj = mj + (g - mj) * o.omb1;                             // exp_avg.lerp_(grad, 1 - beta1)
+        vj = vj * o.b2 + (o.omb2 * g) * g;                       // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
+        const float denom = sqrtf(vj) / bc2s + o.eps;
+        w[j] = w[j] - step_size * (mj / denom);                  // param.addcdiv_(exp_avg, denom, value = -step_size)
+        m[j] = mj;
+        v[j] = vj;
+        acc[j] = 0.0f;
+    }
+}
+// after every workgroup of ht_adam_kernel has read the header: the step counted, the running corrections advanced, the sums zeroed
+__global__ void ht_adam_commit_kernel(void *state, unsigned magic, int P, HeadTrainAdam o) {
+    if (!ht_state_ok(state, magic, P)) return;
+    HeadTrainHeader *hd = reinterpret_cast<HeadTrainHeader *>(state);
+    if (threadIdx.x != 0 || hd->frames == 0ull) return;
+    hd->bc1 = hd->bc1 * o.b1 + o.omb1;
+    hd->bc2 = hd->bc2 * o.b2 + o.omb2;
+    hd->t += 1ull;
+    hd->loss = 0.0;
+    hd->frames = 0ull;
+}
+
+__global__ __launch_bounds__(256) void ht_read_kernel(const void *state, unsigned magic, int P, int Pp, int which, float *out) {
+    const HeadTrainHeader *hd = reinterpret_cast<const HeadTrainHeader *>(state);
+    const bool ok = ht_state_ok(state, magic, P);
+    if (which == UVAD_HEAD_TRAIN_SCALARS) {
+        // an LSTM state's record carries two more words, [8 .. 9]: the dropout draw ordinal (UVAD_LSTM_TRAIN_SCALAR_WORDS)
+        if (blockIdx.x == 0 && threadIdx.x < (magic == LT_MAGIC ? LT_SCALAR_WORDS : HT_SCALAR_WORDS)) {
+            const int i = threadIdx.x;
+            const unsigned long long q = i < 2 ? (unsigned long long)__double_as_longlong(hd->loss) : i < 4 ? hd->frames : i < 8 ? hd->t : hd->draws;
+            const unsigned word = i == 6 ? __float_as_uint(hd->bc1) : i == 7 ? __float_as_uint(hd->bc2) : (unsigned)(i & 1 ? q >> 32 : q);
+            reinterpret_cast<unsigned *>(out)[i] = ok ? word : 0u;
+        }
+        return;
+    }
+    const float *src = reinterpret_cast<const float *>(hd + 1) + (size_t)which * Pp;
+    for (int j = (int)blockIdx.x * 256 + threadIdx.x; j < P; j += (int)gridDim.x * 256) out[j] = ok ? src[j] : 0.0f;
+}
+
 // what ht_read_kernel copied out, put back: a tensor block, or t, bc1, bc2 (and an LSTM state's draw ordinal) from the scalar record
 __global__ __launch_bounds__(256) void ht_write_kernel(void *state, unsigned magic, int P, int Pp, int which, const float *in) {
     if (!ht_state_ok(state, magic, P)) return;
@@ -212,7 +267,7 @@ __global__ __launch_bounds__(256) void ht_write_kernel(void *state, unsigned mag
 
 }  // namespace
 
-hipError_t launch_optim_step(const OptimFamily fam[3], void *opt, int cap, double *part, hipStream_t s) {
+hipError_t launch_optim_step(const TrainBlock fam[3], void *opt, int cap, double *part, hipStream_t s) {
     if (!opt || !part || cap < 1) return hipErrorInvalidValue;
     OptArgs a{};
     int chunks = 0, blocks = 0;
@@ -253,10 +308,26 @@ hipError_t launch_optim_write(void *opt, int cap, const unsigned *in, hipStream_
     return hipGetLastError();
 }
 
-hipError_t launch_train_write(void *state, unsigned magic, int P, int Pp, int which, const float *in, hipStream_t s) {
-    if (!state || !in || which < 0 || which > UVAD_HEAD_TRAIN_SCALARS || which == UVAD_HEAD_TRAIN_GRAD) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(ht_write_kernel, dim3(which == UVAD_HEAD_TRAIN_SCALARS ? 1u : (unsigned)((P + 255) / 256)), dim3(256), 0, s, state, magic, P, Pp,
-                       which, in);
+hipError_t launch_train_apply(const TrainBlock &b, const HeadTrainAdam &o, hipStream_t s) {
+    if (!b.state) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ht_adam_kernel, dim3((unsigned)((b.P + 255) / 256)), dim3(256), 0, s, b.state, b.magic, b.P, b.Pp, o);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ht_adam_commit_kernel, dim3(1), dim3(64), 0, s, b.state, b.magic, b.P, o);
+    return hipGetLastError();
+}
+
+hipError_t launch_train_read(const TrainBlock &b, int which, float *out, hipStream_t s) {
+    if (!b.state || !out || which < 0 || which > UVAD_HEAD_TRAIN_SCALARS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ht_read_kernel, dim3(which == UVAD_HEAD_TRAIN_SCALARS ? 1u : (unsigned)((b.P + 255) / 256)), dim3(256), 0, s,
+                       (const void *)b.state, b.magic, b.P, b.Pp, which, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_train_write(const TrainBlock &b, int which, const float *in, hipStream_t s) {
+    if (!b.state || !in || which < 0 || which > UVAD_HEAD_TRAIN_SCALARS || which == UVAD_HEAD_TRAIN_GRAD) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ht_write_kernel, dim3(which == UVAD_HEAD_TRAIN_SCALARS ? 1u : (unsigned)((b.P + 255) / 256)), dim3(256), 0, s, b.state, b.magic,
+                       b.P, b.Pp, which, in);
     return hipGetLastError();
 }
 

@@ -26,7 +26,7 @@
 //   st_dgrad_kernel       d_a_in[ci][j] = sum_{co, tap} du[co][j - tap] W[co][ci][tap]: m = in channel, n = position, k = (out channel, tap)
 //   st_gfold_kernel, st_bank_bwd_kernel   stage 0: G and D folded in segment order, dF = g G + b0 D, d g = sum F G, d b0 = sum_c D_c sum_k F_ck,
 //                         and d low_hz_ / d band_hz_ by the chain rule through filters() in double
-//   ht_fold_kernel, ht_adam_kernel, ht_read_kernel   as the head's
+//   ht_fold_kernel        as the head's; Adam, the read-out and the write are launch_train_apply / _read / _write of optim.hip
 // No floating-point atomics; every reduction has a fixed order, so the same calls give the same bits.  Every backward kernel checks the state's
 // and the workspace's headers on the device and writes nothing under a mismatch.  Contraction is off; the fused multiply-adds are explicit.
 #include "ht_kernels.h"
@@ -751,25 +751,12 @@ hipError_t launch_sinc_train_bank(const SincTrainShape &q, void *state, hipStrea
     return hipGetLastError();
 }
 
-hipError_t launch_sinc_train_apply(const SincTrainShape &q, const HeadTrainAdam &o, void *state, hipStream_t s) {
-    if (!state) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(ht_adam_kernel, dim3((unsigned)((q.P + 255) / 256)), dim3(256), 0, s, state, SNT_MAGIC, q.P, q.Pp, o);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ht_adam_commit_kernel, dim3(1), dim3(64), 0, s, state, SNT_MAGIC, q.P, o);
-    return hipGetLastError();
-}
-
-hipError_t launch_sinc_train_read(const SincTrainShape &q, const void *state, int which, float *out, hipStream_t s) {
-    if (!state || !out || which < 0 || which > UVAD_SINCNET_TRAIN_FILTERS) return hipErrorInvalidValue;
-    if (which == UVAD_SINCNET_TRAIN_FILTERS) {
-        const float *bank = reinterpret_cast<const float *>(reinterpret_cast<const char *>(state) + sizeof(HeadTrainHeader)) + q.off_bank;
-        const int n = q.NF * q.KS;
-        hipLaunchKernelGGL(st_copy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bank, out, n, state, q.P);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(ht_read_kernel, dim3(which == UVAD_HEAD_TRAIN_SCALARS ? 1u : (unsigned)((q.P + 255) / 256)), dim3(256), 0, s, state,
-                       SNT_MAGIC, q.P, q.Pp, which, out);
+// which = UVAD_SINCNET_TRAIN_FILTERS of uvad_sincnet_train_read: the bank of the last forward call (every other block: launch_train_read)
+hipError_t launch_sinc_train_read_bank(const SincTrainShape &q, const void *state, float *out, hipStream_t s) {
+    if (!state || !out) return hipErrorInvalidValue;
+    const float *bank = reinterpret_cast<const float *>(reinterpret_cast<const char *>(state) + sizeof(HeadTrainHeader)) + q.off_bank;
+    const int n = q.NF * q.KS;
+    hipLaunchKernelGGL(st_copy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bank, out, n, state, q.P);
     return hipGetLastError();
 }
 

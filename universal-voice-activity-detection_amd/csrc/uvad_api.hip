@@ -133,7 +133,7 @@ struct uvad_ctx {
     LstmTrainShape lts{};
     unsigned lt_thr = 0; float lt_scale = 1.0f; uint64_t lt_seed = 0;   // uvad_lstm_train_set_dropout: what the forward call launches with (thr == 0: off)
     bool lt_dropped = false;                    // the last forward call of this context ran with thr > 0
-    std::map<void *, int> sinc_trains;          // ... and of the SincNet training states (uvad_sincnet_train_*): first_stage at reset, + 256 with band edges
+    std::map<void *, int> sinc_trains;          // ... and of the SincNet training states (uvad_sincnet_train_*): first_stage at reset, | TRAIN_TAG_FLAG with band edges
     bool has_snt = false;                       // uvad_sincnet_train_configure: the optimiser, first_stage and the packed shape of the front end
     uvad_sincnet_train_cfg snq{};
     SincTrainShape snts{};
@@ -3217,15 +3217,103 @@ static HeadTrainAdam adam_of(float lr, float beta1, float beta2, float eps) {
     return HeadTrainAdam{lr, beta1, beta2, eps, one_minus(beta1), one_minus(beta2)};
 }
 
+// nullptr: in range; else the words uvad_last_error names.  The segment's words end where the caller names the unit (frames, positions).
+static const char *adam_cfg_error(float lr, float beta1, float beta2, float eps) {
+    if (!std::isfinite(lr) || !(lr > 0.0f)) return "lr must be finite and positive";
+    if (!std::isfinite(beta1) || beta1 < 0.0f || !(beta1 < 1.0f)) return "beta1 must lie in [0, 1)";
+    if (!std::isfinite(beta2) || beta2 < 0.0f || !(beta2 < 1.0f)) return "beta2 must lie in [0, 1)";
+    if (!std::isfinite(eps) || !(eps > 0.0f)) return "eps must be finite and positive";
+    return nullptr;
+}
+static const char *segment_error(int segment) {
+    if (segment != 0 && (segment < HT_MIN_SEGMENT || segment > HT_MAX_SEGMENT || segment % 32)) return "segment must be 0 or a multiple of 32 in [32, 16384] ";
+    return nullptr;
+}
+
+// ---- what the three training families share: one view of a family's configuration on the context, and the calls on a state's blocks ----
+constexpr int TRAIN_TAG_FLAG = 1 << 30;   // a bit a family may keep beside the tag in its map of reset states (SincNet: reset found band edges)
+struct TrainFamily {
+    const char *name;                          // "head", "lstm", "sincnet": the messages name uvad_<name>_train_*
+    bool configured;
+    size_t state_bytes;
+    unsigned magic; int P, Pp;                 // the TrainBlock of a state of this family
+    float lr, beta1, beta2, eps;
+    const std::map<void *, int> &resets;       // the states this family reset -> the tag then; the maps stay apart, so a state belongs to one family
+    int tag;                                   // what "reset under this shape" compares: P (head, LSTM), first_stage (SincNet)
+};
+static TrainFamily head_family(const uvad_ctx *c) {
+    return {"head", c->has_ht, uvad_head_train_state_bytes(c), HT_MAGIC, c->hts.P, c->hts.Pp, c->hq.lr, c->hq.beta1, c->hq.beta2, c->hq.eps,
+            c->head_trains, c->hts.P};
+}
+static TrainFamily lstm_family(const uvad_ctx *c) {
+    return {"lstm", c->has_lt, uvad_lstm_train_state_bytes(c), LT_MAGIC, c->lts.P, c->lts.Pp, c->lq.lr, c->lq.beta1, c->lq.beta2, c->lq.eps,
+            c->lstm_trains, c->lts.P};
+}
+static TrainFamily sinc_family(const uvad_ctx *c) {
+    return {"sincnet", c->has_snt, uvad_sincnet_train_state_bytes(c), SNT_MAGIC, c->snts.P, c->snts.Pp, c->snq.lr, c->snq.beta1, c->snq.beta2, c->snq.eps,
+            c->sinc_trains, c->snts.first_stage};
+}
+
+// the checks every call on a state shares, `fn` the public call refused; `reset`: the call that makes the state known
+static int train_state_check(uvad_ctx *c, const TrainFamily &v, const std::string &fn, const void *d_state, size_t state_bytes, bool reset) {
+    const std::string family = std::string("uvad_") + v.name + "_train_";
+    if (!d_state) return fail(c, UVAD_E_ARG, fn + ": bad argument");
+    if (!v.configured) return fail(c, UVAD_E_STATE, fn + ": call " + family + "configure first");
+    if (state_bytes < v.state_bytes) return fail(c, UVAD_E_ARG, fn + ": state too small: need " + std::to_string(v.state_bytes) + " bytes");
+    if (reset) return UVAD_OK;
+    auto it = v.resets.find(const_cast<void *>(d_state));
+    if (it == v.resets.end()) return fail(c, UVAD_E_STATE, fn + ": call " + family + "reset on this state first");
+    if ((it->second & ~TRAIN_TAG_FLAG) != v.tag) return fail(c, UVAD_E_STATE, fn + ": the state was reset under another shape");
+    return UVAD_OK;
+}
+
+static int train_apply(uvad_ctx *c, const TrainFamily &v, void *d_state, size_t state_bytes, void *stream) {
+    if (int r = train_state_check(c, v, std::string("uvad_") + v.name + "_train_apply", d_state, state_bytes, false)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_train_apply(TrainBlock{d_state, v.magic, v.P, v.Pp}, adam_of(v.lr, v.beta1, v.beta2, v.eps), (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+// which = MASTERS .. SCALARS; SincNet's bank (which 5) is its own entry's case
+static int train_read(uvad_ctx *c, const TrainFamily &v, const void *d_state, size_t state_bytes, int which, float *d_out, void *stream) {
+    const std::string fn = std::string("uvad_") + v.name + "_train_read";
+    if (!d_out || which < 0 || which > UVAD_HEAD_TRAIN_SCALARS) return fail(c, UVAD_E_ARG, fn + ": bad argument");
+    if (int r = train_state_check(c, v, fn, d_state, state_bytes, false)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_train_read(TrainBlock{const_cast<void *>(d_state), v.magic, v.P, v.Pp}, which, d_out, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+static int train_write(uvad_ctx *c, const TrainFamily &v, void *d_state, size_t state_bytes, int which, const float *d_in, void *stream) {
+    const std::string fn = std::string("uvad_") + v.name + "_train_write";
+    const bool which_ok = which == UVAD_HEAD_TRAIN_MASTERS || which == UVAD_HEAD_TRAIN_M || which == UVAD_HEAD_TRAIN_V || which == UVAD_HEAD_TRAIN_SCALARS;
+    if (!d_in || !which_ok) return fail(c, UVAD_E_ARG, fn + ": bad argument");
+    if (int r = train_state_check(c, v, fn, d_state, state_bytes, false)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_train_write(TrainBlock{d_state, v.magic, v.P, v.Pp}, which, d_in, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+// the shell of a family's _commit: the checks, every enqueued backward / apply landed, then `words` floats from behind the header on the host.
+// before_copy (SincNet: the bank rebuilt from the masters) runs between the two.
+static int train_commit_begin(uvad_ctx *c, const TrainFamily &v, const void *d_state, size_t state_bytes, size_t words, std::vector<float> &host,
+                              hipError_t (*before_copy)(uvad_ctx *, const void *) = nullptr) {
+    const std::string fn = std::string("uvad_") + v.name + "_train_commit";
+    if (int r = train_state_check(c, v, fn, d_state, state_bytes, false)) return r;
+    if (!c->finalized) return fail(c, UVAD_E_STATE, fn + ": call uvad_finalize first");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    if (before_copy) HIPCHK(c, before_copy(c, d_state));
+    host.resize(words);
+    HIPCHK(c, hipMemcpy(host.data(), reinterpret_cast<const char *>(d_state) + sizeof(HeadTrainHeader), words * sizeof(float), hipMemcpyDeviceToHost));
+    return UVAD_OK;
+}
+
 int uvad_head_train_configure(uvad_ctx *c, const uvad_head_train_cfg *q) {
     if (!c) return UVAD_E_ARG;
     if (!q) return fail(c, UVAD_E_ARG, "uvad_head_train_configure: bad argument");
-    if (!std::isfinite(q->lr) || !(q->lr > 0.0f)) return fail(c, UVAD_E_ARG, "uvad_head_train_configure: lr must be finite and positive");
-    if (!std::isfinite(q->beta1) || q->beta1 < 0.0f || !(q->beta1 < 1.0f)) return fail(c, UVAD_E_ARG, "uvad_head_train_configure: beta1 must lie in [0, 1)");
-    if (!std::isfinite(q->beta2) || q->beta2 < 0.0f || !(q->beta2 < 1.0f)) return fail(c, UVAD_E_ARG, "uvad_head_train_configure: beta2 must lie in [0, 1)");
-    if (!std::isfinite(q->eps) || !(q->eps > 0.0f)) return fail(c, UVAD_E_ARG, "uvad_head_train_configure: eps must be finite and positive");
-    if (q->segment != 0 && (q->segment < HT_MIN_SEGMENT || q->segment > HT_MAX_SEGMENT || q->segment % 32))
-        return fail(c, UVAD_E_ARG, "uvad_head_train_configure: segment must be 0 or a multiple of 32 in [32, 16384] frames");
+    if (const char *e = adam_cfg_error(q->lr, q->beta1, q->beta2, q->eps)) return fail(c, UVAD_E_ARG, std::string("uvad_head_train_configure: ") + e);
+    if (const char *e = segment_error(q->segment)) return fail(c, UVAD_E_ARG, std::string("uvad_head_train_configure: ") + e + "frames");
     if (!c->has_model) return fail(c, UVAD_E_STATE, "uvad_head_train_configure: context was created without a model configuration");
     const uvad_model_cfg &m = c->mc;
     const int D0 = m.hidden * (m.bidirectional ? 2 : 1);
@@ -3250,23 +3338,9 @@ size_t uvad_head_train_ws_bytes(const uvad_ctx *c, int B, int T) {
     return head_train_ws(c->hts, (long long)B * T, c->hq.segment).total;
 }
 
-// the checks every call on a state shares; `reset`: the call that makes the state known
-static int head_train_state_check(uvad_ctx *c, const char *fn, const void *d_state, size_t state_bytes, bool reset) {
-    const std::string f(fn);
-    if (!d_state) return fail(c, UVAD_E_ARG, f + ": bad argument");
-    if (!c->has_ht) return fail(c, UVAD_E_STATE, f + ": call uvad_head_train_configure first");
-    const size_t need = head_train_state_bytes(c->hts);
-    if (state_bytes < need) return fail(c, UVAD_E_ARG, f + ": state too small: need " + std::to_string(need) + " bytes");
-    if (reset) return UVAD_OK;
-    auto it = c->head_trains.find(const_cast<void *>(d_state));
-    if (it == c->head_trains.end()) return fail(c, UVAD_E_STATE, f + ": call uvad_head_train_reset on this state first");
-    if (it->second != c->hts.P) return fail(c, UVAD_E_STATE, f + ": the state was reset under another head shape");
-    return UVAD_OK;
-}
-
 int uvad_head_train_reset(uvad_ctx *c, void *d_state, size_t state_bytes, void *stream) {
     if (!c) return UVAD_E_ARG;
-    if (int r = head_train_state_check(c, "uvad_head_train_reset", d_state, state_bytes, true)) return r;
+    if (int r = train_state_check(c, head_family(c), "uvad_head_train_reset", d_state, state_bytes, true)) return r;
     if (!c->finalized) return fail(c, UVAD_E_STATE, "uvad_head_train_reset: call uvad_finalize first");
     const HeadTrainShape &q = c->hts;
     const PackedWeights &W = *c->packed;
@@ -3290,10 +3364,10 @@ int uvad_head_train_grad(uvad_ctx *c, const float *d_x, int B, int T, const int3
         return fail(c, UVAD_E_ARG, "uvad_head_train_grad: more than 65535 segments: B x T / segment too large");
     if ((d_dz && ld_dz < T) || (!d_dz && ld_gt < T) || (!d_dz && d_fw && ld_fw < T) || (d_probs && ld_p < T))
         return fail(c, UVAD_E_ARG, "uvad_head_train_grad: ld_gt, ld_fw, ld_dz and ld_p must be at least T");
-    if (int r = head_train_state_check(c, "uvad_head_train_grad", d_state, state_bytes, true)) return r;   // configured, and the state's size
+    if (int r = train_state_check(c, head_family(c), "uvad_head_train_grad", d_state, state_bytes, true)) return r;   // configured, and the state's size
     const size_t need = head_train_ws(c->hts, (long long)B * T, c->hq.segment).total;
     if (ws_bytes < need) return fail(c, UVAD_E_ARG, "uvad_head_train_grad: workspace too small: need " + std::to_string(need) + " bytes");
-    if (int r = head_train_state_check(c, "uvad_head_train_grad", d_state, state_bytes, false)) return r;  // ... and that it was reset
+    if (int r = train_state_check(c, head_family(c), "uvad_head_train_grad", d_state, state_bytes, false)) return r;  // ... and that it was reset
     HeadTrainGradArgs a{};
     a.x = d_x; a.B = B; a.T = T; a.lens = d_lens;
     a.gt = d_dz ? nullptr : d_gt; a.ld_gt = ld_gt; a.fw = d_dz ? nullptr : d_fw; a.ld_fw = ld_fw; a.dz_in = d_dz; a.ld_dz = ld_dz;
@@ -3305,33 +3379,18 @@ int uvad_head_train_grad(uvad_ctx *c, const float *d_x, int B, int T, const int3
 }
 
 int uvad_head_train_apply(uvad_ctx *c, void *d_state, size_t state_bytes, void *stream) {
-    if (!c) return UVAD_E_ARG;
-    if (int r = head_train_state_check(c, "uvad_head_train_apply", d_state, state_bytes, false)) return r;
-    const uvad_head_train_cfg &q = c->hq;
-    const HeadTrainAdam o = adam_of(q.lr, q.beta1, q.beta2, q.eps);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, launch_head_train_apply(c->hts, o, d_state, (hipStream_t)stream));
-    return UVAD_OK;
+    return c ? train_apply(c, head_family(c), d_state, state_bytes, stream) : UVAD_E_ARG;
 }
 
 int uvad_head_train_read(uvad_ctx *c, const void *d_state, size_t state_bytes, int which, float *d_out, void *stream) {
-    if (!c) return UVAD_E_ARG;
-    if (!d_out || which < 0 || which > UVAD_HEAD_TRAIN_SCALARS) return fail(c, UVAD_E_ARG, "uvad_head_train_read: bad argument");
-    if (int r = head_train_state_check(c, "uvad_head_train_read", d_state, state_bytes, false)) return r;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, launch_head_train_read(c->hts, d_state, which, d_out, (hipStream_t)stream));
-    return UVAD_OK;
+    return c ? train_read(c, head_family(c), d_state, state_bytes, which, d_out, stream) : UVAD_E_ARG;
 }
 
 int uvad_head_train_commit(uvad_ctx *c, const void *d_state, size_t state_bytes) {
     if (!c) return UVAD_E_ARG;
-    if (int r = head_train_state_check(c, "uvad_head_train_commit", d_state, state_bytes, false)) return r;
-    if (!c->finalized) return fail(c, UVAD_E_STATE, "uvad_head_train_commit: call uvad_finalize first");
     const HeadTrainShape &q = c->hts;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipDeviceSynchronize());   // every enqueued grad / apply has landed
-    std::vector<float> w((size_t)q.P);
-    HIPCHK(c, hipMemcpy(w.data(), reinterpret_cast<const char *>(d_state) + sizeof(HeadTrainHeader), w.size() * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<float> w;
+    if (int r = train_commit_begin(c, head_family(c), d_state, state_bytes, (size_t)q.P, w)) return r;
     for (int l = 0; l <= q.L; ++l) {
         const bool cls = l == q.L;
         const int K = cls ? (q.L ? q.H : q.D0) : (l ? q.H : q.D0), rows = cls ? 1 : q.H;
@@ -3348,12 +3407,8 @@ int uvad_head_train_commit(uvad_ctx *c, const void *d_state, size_t state_bytes)
 int uvad_lstm_train_configure(uvad_ctx *c, const uvad_lstm_train_cfg *q) {
     if (!c) return UVAD_E_ARG;
     if (!q) return fail(c, UVAD_E_ARG, "uvad_lstm_train_configure: bad argument");
-    if (!std::isfinite(q->lr) || !(q->lr > 0.0f)) return fail(c, UVAD_E_ARG, "uvad_lstm_train_configure: lr must be finite and positive");
-    if (!std::isfinite(q->beta1) || q->beta1 < 0.0f || !(q->beta1 < 1.0f)) return fail(c, UVAD_E_ARG, "uvad_lstm_train_configure: beta1 must lie in [0, 1)");
-    if (!std::isfinite(q->beta2) || q->beta2 < 0.0f || !(q->beta2 < 1.0f)) return fail(c, UVAD_E_ARG, "uvad_lstm_train_configure: beta2 must lie in [0, 1)");
-    if (!std::isfinite(q->eps) || !(q->eps > 0.0f)) return fail(c, UVAD_E_ARG, "uvad_lstm_train_configure: eps must be finite and positive");
-    if (q->segment != 0 && (q->segment < HT_MIN_SEGMENT || q->segment > HT_MAX_SEGMENT || q->segment % 32))
-        return fail(c, UVAD_E_ARG, "uvad_lstm_train_configure: segment must be 0 or a multiple of 32 in [32, 16384] frames");
+    if (const char *e = adam_cfg_error(q->lr, q->beta1, q->beta2, q->eps)) return fail(c, UVAD_E_ARG, std::string("uvad_lstm_train_configure: ") + e);
+    if (const char *e = segment_error(q->segment)) return fail(c, UVAD_E_ARG, std::string("uvad_lstm_train_configure: ") + e + "frames");
     if (!c->has_model) return fail(c, UVAD_E_STATE, "uvad_lstm_train_configure: context was created without a model configuration");
     const uvad_model_cfg &m = c->mc;
     if (q->first_layer < 0 || q->first_layer >= m.num_layers)
@@ -3399,19 +3454,6 @@ size_t uvad_lstm_train_ws_bytes(const uvad_ctx *c, int B, int T) {
     return lstm_train_ws(c->lts, (long long)B * T, c->lq.segment).total;
 }
 
-static int lstm_train_state_check(uvad_ctx *c, const char *fn, const void *d_state, size_t state_bytes, bool reset) {
-    const std::string f(fn);
-    if (!d_state) return fail(c, UVAD_E_ARG, f + ": bad argument");
-    if (!c->has_lt) return fail(c, UVAD_E_STATE, f + ": call uvad_lstm_train_configure first");
-    const size_t need = lstm_train_state_bytes(c->lts);
-    if (state_bytes < need) return fail(c, UVAD_E_ARG, f + ": state too small: need " + std::to_string(need) + " bytes");
-    if (reset) return UVAD_OK;
-    auto it = c->lstm_trains.find(const_cast<void *>(d_state));
-    if (it == c->lstm_trains.end()) return fail(c, UVAD_E_STATE, f + ": call uvad_lstm_train_reset on this state first");
-    if (it->second != c->lts.P) return fail(c, UVAD_E_STATE, f + ": the state was reset under another shape");
-    return UVAD_OK;
-}
-
 // the torch key of a trainable tensor: which = 0 .. 3 (weight_ih, weight_hh, bias_ih, bias_hh)
 static std::string lstm_train_key(int layer, int dir, int which) {
     const char *const names[4] = {"weight_ih", "weight_hh", "bias_ih", "bias_hh"};
@@ -3420,7 +3462,7 @@ static std::string lstm_train_key(int layer, int dir, int which) {
 
 int uvad_lstm_train_reset(uvad_ctx *c, void *d_state, size_t state_bytes, void *stream) {
     if (!c) return UVAD_E_ARG;
-    if (int r = lstm_train_state_check(c, "uvad_lstm_train_reset", d_state, state_bytes, true)) return r;
+    if (int r = train_state_check(c, lstm_family(c), "uvad_lstm_train_reset", d_state, state_bytes, true)) return r;
     if (!c->finalized) return fail(c, UVAD_E_STATE, "uvad_lstm_train_reset: call uvad_finalize first");
     const LstmTrainShape &q = c->lts;
     std::vector<float> w((size_t)q.P);
@@ -3451,10 +3493,10 @@ static int lstm_train_call_check(uvad_ctx *c, const char *fn, const void *d_x, c
     if ((long long)B * T > HT_MAX_FRAMES) return fail(c, UVAD_E_ARG, f + ": B x T above 2^24 frames");
     if (c->has_lt && ((long long)B * T + c->lq.segment - 1) / c->lq.segment > 65535)
         return fail(c, UVAD_E_ARG, f + ": more than 65535 segments: B x T / segment too large");
-    if (int r = lstm_train_state_check(c, fn, d_state, state_bytes, true)) return r;
+    if (int r = train_state_check(c, lstm_family(c), f, d_state, state_bytes, true)) return r;
     const size_t need = lstm_train_ws(c->lts, (long long)B * T, c->lq.segment).total;
     if (ws_bytes < need) return fail(c, UVAD_E_ARG, f + ": workspace too small: need " + std::to_string(need) + " bytes");
-    return lstm_train_state_check(c, fn, d_state, state_bytes, false);
+    return train_state_check(c, lstm_family(c), f, d_state, state_bytes, false);
 }
 
 int uvad_lstm_train_forward(uvad_ctx *c, const float *d_x_in, int B, int T, const int32_t *d_lens, float *d_y, void *d_state, size_t state_bytes,
@@ -3483,32 +3525,18 @@ int uvad_lstm_train_backward(uvad_ctx *c, const float *d_x_in, const float *d_dy
 }
 
 int uvad_lstm_train_apply(uvad_ctx *c, void *d_state, size_t state_bytes, void *stream) {
-    if (!c) return UVAD_E_ARG;
-    if (int r = lstm_train_state_check(c, "uvad_lstm_train_apply", d_state, state_bytes, false)) return r;
-    const uvad_lstm_train_cfg &q = c->lq;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, launch_lstm_train_apply(c->lts, adam_of(q.lr, q.beta1, q.beta2, q.eps), d_state, (hipStream_t)stream));
-    return UVAD_OK;
+    return c ? train_apply(c, lstm_family(c), d_state, state_bytes, stream) : UVAD_E_ARG;
 }
 
 int uvad_lstm_train_read(uvad_ctx *c, const void *d_state, size_t state_bytes, int which, float *d_out, void *stream) {
-    if (!c) return UVAD_E_ARG;
-    if (!d_out || which < 0 || which > UVAD_HEAD_TRAIN_SCALARS) return fail(c, UVAD_E_ARG, "uvad_lstm_train_read: bad argument");
-    if (int r = lstm_train_state_check(c, "uvad_lstm_train_read", d_state, state_bytes, false)) return r;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, launch_lstm_train_read(c->lts, d_state, which, d_out, (hipStream_t)stream));
-    return UVAD_OK;
+    return c ? train_read(c, lstm_family(c), d_state, state_bytes, which, d_out, stream) : UVAD_E_ARG;
 }
 
 int uvad_lstm_train_commit(uvad_ctx *c, const void *d_state, size_t state_bytes) {
     if (!c) return UVAD_E_ARG;
-    if (int r = lstm_train_state_check(c, "uvad_lstm_train_commit", d_state, state_bytes, false)) return r;
-    if (!c->finalized) return fail(c, UVAD_E_STATE, "uvad_lstm_train_commit: call uvad_finalize first");
     const LstmTrainShape q = c->lts;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipDeviceSynchronize());   // every enqueued backward / apply has landed
-    std::vector<float> w((size_t)q.P);
-    HIPCHK(c, hipMemcpy(w.data(), reinterpret_cast<const char *>(d_state) + sizeof(HeadTrainHeader), w.size() * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<float> w;
+    if (int r = train_commit_begin(c, lstm_family(c), d_state, state_bytes, (size_t)q.P, w)) return r;
     for (int li = 0; li < q.nl; ++li)
         for (int d = 0; d < q.dirs; ++d)
             for (int k = 0; k < 4; ++k) {
@@ -3522,12 +3550,8 @@ int uvad_lstm_train_commit(uvad_ctx *c, const void *d_state, size_t state_bytes)
 int uvad_sincnet_train_configure(uvad_ctx *c, const uvad_sincnet_train_cfg *q) {
     if (!c) return UVAD_E_ARG;
     if (!q) return fail(c, UVAD_E_ARG, "uvad_sincnet_train_configure: bad argument");
-    if (!std::isfinite(q->lr) || !(q->lr > 0.0f)) return fail(c, UVAD_E_ARG, "uvad_sincnet_train_configure: lr must be finite and positive");
-    if (!std::isfinite(q->beta1) || q->beta1 < 0.0f || !(q->beta1 < 1.0f)) return fail(c, UVAD_E_ARG, "uvad_sincnet_train_configure: beta1 must lie in [0, 1)");
-    if (!std::isfinite(q->beta2) || q->beta2 < 0.0f || !(q->beta2 < 1.0f)) return fail(c, UVAD_E_ARG, "uvad_sincnet_train_configure: beta2 must lie in [0, 1)");
-    if (!std::isfinite(q->eps) || !(q->eps > 0.0f)) return fail(c, UVAD_E_ARG, "uvad_sincnet_train_configure: eps must be finite and positive");
-    if (q->segment != 0 && (q->segment < HT_MIN_SEGMENT || q->segment > HT_MAX_SEGMENT || q->segment % 32))
-        return fail(c, UVAD_E_ARG, "uvad_sincnet_train_configure: segment must be 0 or a multiple of 32 in [32, 16384] positions");
+    if (const char *e = adam_cfg_error(q->lr, q->beta1, q->beta2, q->eps)) return fail(c, UVAD_E_ARG, std::string("uvad_sincnet_train_configure: ") + e);
+    if (const char *e = segment_error(q->segment)) return fail(c, UVAD_E_ARG, std::string("uvad_sincnet_train_configure: ") + e + "positions");
     if (q->first_stage < 0 || q->first_stage > 2) return fail(c, UVAD_E_ARG, "uvad_sincnet_train_configure: first_stage must lie in [0, 2]");
     if (!c->has_model) return fail(c, UVAD_E_STATE, "uvad_sincnet_train_configure: context was created without a model configuration");
     if (!c->has_sinc) return fail(c, UVAD_E_STATE, "uvad_sincnet_train_configure: the context has no SincNet stage (uvad_sincnet_configure)");
@@ -3564,19 +3588,6 @@ size_t uvad_sincnet_train_ws_bytes(const uvad_ctx *c, int B, int64_t S) {
     return sinc_train_ws(c->snts, geo, B, c->snq.segment).total;
 }
 
-static int sinc_train_state_check(uvad_ctx *c, const char *fn, const void *d_state, size_t state_bytes, bool reset) {
-    const std::string f(fn);
-    if (!d_state) return fail(c, UVAD_E_ARG, f + ": bad argument");
-    if (!c->has_snt) return fail(c, UVAD_E_STATE, f + ": call uvad_sincnet_train_configure first");
-    const size_t need = sinc_train_state_bytes(c->snts);
-    if (state_bytes < need) return fail(c, UVAD_E_ARG, f + ": state too small: need " + std::to_string(need) + " bytes");
-    if (reset) return UVAD_OK;
-    auto it = c->sinc_trains.find(const_cast<void *>(d_state));
-    if (it == c->sinc_trains.end()) return fail(c, UVAD_E_STATE, f + ": call uvad_sincnet_train_reset on this state first");
-    if ((it->second & 255) != c->snts.first_stage) return fail(c, UVAD_E_STATE, f + ": the state was reset under another shape");
-    return UVAD_OK;
-}
-
 // the torch key and shape of tensor t (SNT_T_* order)
 static std::string sinc_train_key(int t) {
     static const char *const names[SNT_TENSORS] = {"wav_norm1d.weight", "wav_norm1d.bias", "conv1d.0.filterbank.low_hz_", "conv1d.0.filterbank.band_hz_",
@@ -3597,7 +3608,7 @@ static int sinc_train_tensor_shape(const SincTrainShape &q, int t, int64_t shape
 
 int uvad_sincnet_train_reset(uvad_ctx *c, void *d_state, size_t state_bytes, void *stream) {
     if (!c) return UVAD_E_ARG;
-    if (int r = sinc_train_state_check(c, "uvad_sincnet_train_reset", d_state, state_bytes, true)) return r;
+    if (int r = train_state_check(c, sinc_family(c), "uvad_sincnet_train_reset", d_state, state_bytes, true)) return r;
     if (!c->finalized) return fail(c, UVAD_E_STATE, "uvad_sincnet_train_reset: call uvad_finalize first");
     const SincTrainShape &q = c->snts;
     auto get = [&](const std::string &k) -> const HostTensor * {
@@ -3634,7 +3645,7 @@ int uvad_sincnet_train_reset(uvad_ctx *c, void *d_state, size_t state_bytes, voi
     HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));   // the state comes from the host tensors: blocking copies
     HIPCHK(c, hipMemcpy(reinterpret_cast<char *>(d_state) + sizeof(HeadTrainHeader), img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(d_state, &h, sizeof h, hipMemcpyHostToDevice));
-    c->sinc_trains[d_state] = q.first_stage | (edges ? 256 : 0);
+    c->sinc_trains[d_state] = q.first_stage | (edges ? TRAIN_TAG_FLAG : 0);
     return UVAD_OK;
 }
 
@@ -3645,12 +3656,12 @@ static int sinc_train_call_check(uvad_ctx *c, const char *fn, const void *d_wav,
     if (!d_wav || !d_other || !d_state || !d_ws || B < 1 || S < 1) return fail(c, UVAD_E_ARG, f + ": bad argument");
     if (reinterpret_cast<uintptr_t>(d_state) % 16 || reinterpret_cast<uintptr_t>(d_ws) % 16)
         return fail(c, UVAD_E_ARG, f + ": d_state and d_ws must be 16-byte aligned");
-    if (int r = sinc_train_state_check(c, fn, d_state, state_bytes, true)) return r;
+    if (int r = train_state_check(c, sinc_family(c), f, d_state, state_bytes, true)) return r;
     SincTrainGeo geo;
     if (const char *w = sinc_train_shape_error(c, B, S, &geo)) return fail(c, UVAD_E_ARG, f + ": " + w);
     const size_t need = sinc_train_ws(c->snts, geo, B, c->snq.segment).total;
     if (ws_bytes < need) return fail(c, UVAD_E_ARG, f + ": workspace too small: need " + std::to_string(need) + " bytes");
-    return sinc_train_state_check(c, fn, d_state, state_bytes, false);
+    return train_state_check(c, sinc_family(c), f, d_state, state_bytes, false);
 }
 
 int uvad_sincnet_train_forward(uvad_ctx *c, const float *d_wav, int B, int64_t S, float *d_feats, void *d_state, size_t state_bytes, void *d_ws,
@@ -3676,37 +3687,31 @@ int uvad_sincnet_train_backward(uvad_ctx *c, const float *d_wav, const float *d_
 }
 
 int uvad_sincnet_train_apply(uvad_ctx *c, void *d_state, size_t state_bytes, void *stream) {
-    if (!c) return UVAD_E_ARG;
-    if (int r = sinc_train_state_check(c, "uvad_sincnet_train_apply", d_state, state_bytes, false)) return r;
-    const uvad_sincnet_train_cfg &q = c->snq;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, launch_sinc_train_apply(c->snts, adam_of(q.lr, q.beta1, q.beta2, q.eps), d_state, (hipStream_t)stream));
-    return UVAD_OK;
+    return c ? train_apply(c, sinc_family(c), d_state, state_bytes, stream) : UVAD_E_ARG;
 }
 
 int uvad_sincnet_train_read(uvad_ctx *c, const void *d_state, size_t state_bytes, int which, float *d_out, void *stream) {
     if (!c) return UVAD_E_ARG;
-    if (!d_out || which < 0 || which > UVAD_SINCNET_TRAIN_FILTERS) return fail(c, UVAD_E_ARG, "uvad_sincnet_train_read: bad argument");
-    if (int r = sinc_train_state_check(c, "uvad_sincnet_train_read", d_state, state_bytes, false)) return r;
+    if (which != UVAD_SINCNET_TRAIN_FILTERS) return train_read(c, sinc_family(c), d_state, state_bytes, which, d_out, stream);
+    if (!d_out) return fail(c, UVAD_E_ARG, "uvad_sincnet_train_read: bad argument");
+    if (int r = train_state_check(c, sinc_family(c), "uvad_sincnet_train_read", d_state, state_bytes, false)) return r;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, launch_sinc_train_read(c->snts, d_state, which, d_out, (hipStream_t)stream));
+    HIPCHK(c, launch_sinc_train_read_bank(c->snts, d_state, d_out, (hipStream_t)stream));
     return UVAD_OK;
 }
 
 int uvad_sincnet_train_commit(uvad_ctx *c, const void *d_state, size_t state_bytes) {
     if (!c) return UVAD_E_ARG;
-    if (int r = sinc_train_state_check(c, "uvad_sincnet_train_commit", d_state, state_bytes, false)) return r;
-    if (!c->finalized) return fail(c, UVAD_E_STATE, "uvad_sincnet_train_commit: call uvad_finalize first");
     const SincTrainShape q = c->snts;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipDeviceSynchronize());   // every enqueued backward / apply has landed
-    const bool edges = (c->sinc_trains[const_cast<void *>(d_state)] & 256) != 0;
-    if (edges) {   // the bank of the masters as they stand after the last apply: what is served matches the committed band edges
-        HIPCHK(c, launch_sinc_train_bank(q, const_cast<void *>(d_state), nullptr));
-        HIPCHK(c, hipDeviceSynchronize());
-    }
-    std::vector<float> w((size_t)q.off_bank + q.bankp);
-    HIPCHK(c, hipMemcpy(w.data(), reinterpret_cast<const char *>(d_state) + sizeof(HeadTrainHeader), w.size() * sizeof(float), hipMemcpyDeviceToHost));
+    // a state reset with band edges: the bank of the masters as they stand after the last apply, so that what is served matches the committed edges
+    auto bank = [](uvad_ctx *x, const void *st) -> hipError_t {
+        if (!(x->sinc_trains[const_cast<void *>(st)] & TRAIN_TAG_FLAG)) return hipSuccess;
+        const hipError_t e = launch_sinc_train_bank(x->snts, const_cast<void *>(st), nullptr);
+        return e != hipSuccess ? e : hipDeviceSynchronize();
+    };
+    std::vector<float> w;
+    if (int r = train_commit_begin(c, sinc_family(c), d_state, state_bytes, (size_t)q.off_bank + q.bankp, w, bank)) return r;
+    const bool edges = (c->sinc_trains[const_cast<void *>(d_state)] & TRAIN_TAG_FLAG) != 0;
     for (int t = 0; t < SNT_TENSORS; ++t) {
         if (q.off_master[t] < 0) continue;
         int64_t shape[3];
@@ -3731,9 +3736,7 @@ static const char *optim_table_error(const float *h_lr_table, int n_lr) {
 }
 static const char *optim_cfg_error(const uvad_optim_cfg *q) {
     if (!q) return "cfg is NULL";
-    if (!std::isfinite(q->beta1) || q->beta1 < 0.0f || !(q->beta1 < 1.0f)) return "beta1 must lie in [0, 1)";
-    if (!std::isfinite(q->beta2) || q->beta2 < 0.0f || !(q->beta2 < 1.0f)) return "beta2 must lie in [0, 1)";
-    if (!std::isfinite(q->eps) || !(q->eps > 0.0f)) return "eps must be finite and positive";
+    if (const char *e = adam_cfg_error(1.0f, q->beta1, q->beta2, q->eps)) return e;   // the learning rates are the table's
     if (!std::isfinite(q->max_norm) || q->max_norm < 0.0f) return "max_norm must be finite and >= 0";
     if (!std::isfinite(q->weight_decay) || q->weight_decay < 0.0f) return "weight_decay must be finite and >= 0";
     for (int k = 0; k < 3; ++k)
@@ -3745,7 +3748,8 @@ size_t uvad_optim_state_bytes(int n_lr) { return n_lr < 1 || n_lr > OPT_MAX_LR ?
 
 size_t uvad_optim_ws_bytes(const uvad_ctx *c) {
     if (!c) return 0;
-    const int chunks = (c->has_ht ? optim_chunks(c->hts.P) : 0) + (c->has_lt ? optim_chunks(c->lts.P) : 0) + (c->has_snt ? optim_chunks(c->snts.P) : 0);
+    int chunks = 0;
+    for (const TrainFamily &v : {head_family(c), lstm_family(c), sinc_family(c)}) chunks += v.configured ? optim_chunks(v.P) : 0;
     return chunks ? optim_ws_bytes(chunks) : 0;
 }
 
@@ -3805,28 +3809,24 @@ int uvad_optim_step(uvad_ctx *c, void *d_head_state, size_t head_bytes, void *d_
     if (!d_state || !d_ws) return fail(c, UVAD_E_ARG, "uvad_optim_step: bad argument");
     if (!d_head_state && !d_lstm_state && !d_sincnet_state) return fail(c, UVAD_E_ARG, "uvad_optim_step: at least one training state must be given");
     if (reinterpret_cast<uintptr_t>(d_ws) % 8) return fail(c, UVAD_E_ARG, "uvad_optim_step: d_ws must be 8-byte aligned");
-    if (d_head_state)
-        if (int r = head_train_state_check(c, "uvad_optim_step", d_head_state, head_bytes, true)) return r;    // configured, and the state's size
-    if (d_lstm_state)
-        if (int r = lstm_train_state_check(c, "uvad_optim_step", d_lstm_state, lstm_bytes, true)) return r;
-    if (d_sincnet_state)
-        if (int r = sinc_train_state_check(c, "uvad_optim_step", d_sincnet_state, sincnet_bytes, true)) return r;
+    void *const given[3] = {d_head_state, d_lstm_state, d_sincnet_state};
+    const size_t bytes[3] = {head_bytes, lstm_bytes, sincnet_bytes};
+    const TrainFamily family[3] = {head_family(c), lstm_family(c), sinc_family(c)};
+    TrainBlock fam[3] = {};
+    int chunks = 0;
+    for (int k = 0; k < 3; ++k) {   // a family whose state is given: configured, and the state's size
+        if (!given[k]) continue;
+        if (int r = train_state_check(c, family[k], "uvad_optim_step", given[k], bytes[k], true)) return r;
+        fam[k] = TrainBlock{given[k], family[k].magic, family[k].P, family[k].Pp};
+        chunks += optim_chunks(family[k].P);
+    }
     int cap = 0;
     if (int r = optim_state_check(c, "uvad_optim_step", d_state, state_bytes, &cap)) return r;
-    OptimFamily fam[3] = {};
-    if (d_head_state) fam[0] = OptimFamily{d_head_state, HT_MAGIC, c->hts.P, c->hts.Pp};
-    if (d_lstm_state) fam[1] = OptimFamily{d_lstm_state, LT_MAGIC, c->lts.P, c->lts.Pp};
-    if (d_sincnet_state) fam[2] = OptimFamily{d_sincnet_state, SNT_MAGIC, c->snts.P, c->snts.Pp};
-    int chunks = 0;
-    for (int k = 0; k < 3; ++k) chunks += fam[k].state ? optim_chunks(fam[k].P) : 0;
     const size_t need = optim_ws_bytes(chunks);
     if (ws_bytes < need) return fail(c, UVAD_E_ARG, "uvad_optim_step: workspace too small: need " + std::to_string(need) + " bytes");
-    if (d_head_state)
-        if (int r = head_train_state_check(c, "uvad_optim_step", d_head_state, head_bytes, false)) return r;   // ... and that it was reset
-    if (d_lstm_state)
-        if (int r = lstm_train_state_check(c, "uvad_optim_step", d_lstm_state, lstm_bytes, false)) return r;
-    if (d_sincnet_state)
-        if (int r = sinc_train_state_check(c, "uvad_optim_step", d_sincnet_state, sincnet_bytes, false)) return r;
+    for (int k = 0; k < 3; ++k)     // ... and that it was reset
+        if (given[k])
+            if (int r = train_state_check(c, family[k], "uvad_optim_step", given[k], bytes[k], false)) return r;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, launch_optim_step(fam, d_state, cap, reinterpret_cast<double *>(d_ws), (hipStream_t)stream));
     return UVAD_OK;
@@ -3852,35 +3852,14 @@ int uvad_optim_write(uvad_ctx *c, void *d_state, size_t state_bytes, const void 
     return UVAD_OK;
 }
 
-static bool train_write_which_ok(int which) {
-    return which == UVAD_HEAD_TRAIN_MASTERS || which == UVAD_HEAD_TRAIN_M || which == UVAD_HEAD_TRAIN_V || which == UVAD_HEAD_TRAIN_SCALARS;
-}
-
 int uvad_head_train_write(uvad_ctx *c, void *d_state, size_t state_bytes, int which, const float *d_in, void *stream) {
-    if (!c) return UVAD_E_ARG;
-    if (!d_in || !train_write_which_ok(which)) return fail(c, UVAD_E_ARG, "uvad_head_train_write: bad argument");
-    if (int r = head_train_state_check(c, "uvad_head_train_write", d_state, state_bytes, false)) return r;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, launch_train_write(d_state, HT_MAGIC, c->hts.P, c->hts.Pp, which, d_in, (hipStream_t)stream));
-    return UVAD_OK;
+    return c ? train_write(c, head_family(c), d_state, state_bytes, which, d_in, stream) : UVAD_E_ARG;
 }
-
 int uvad_lstm_train_write(uvad_ctx *c, void *d_state, size_t state_bytes, int which, const float *d_in, void *stream) {
-    if (!c) return UVAD_E_ARG;
-    if (!d_in || !train_write_which_ok(which)) return fail(c, UVAD_E_ARG, "uvad_lstm_train_write: bad argument");
-    if (int r = lstm_train_state_check(c, "uvad_lstm_train_write", d_state, state_bytes, false)) return r;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, launch_train_write(d_state, LT_MAGIC, c->lts.P, c->lts.Pp, which, d_in, (hipStream_t)stream));
-    return UVAD_OK;
+    return c ? train_write(c, lstm_family(c), d_state, state_bytes, which, d_in, stream) : UVAD_E_ARG;
 }
-
 int uvad_sincnet_train_write(uvad_ctx *c, void *d_state, size_t state_bytes, int which, const float *d_in, void *stream) {
-    if (!c) return UVAD_E_ARG;
-    if (!d_in || !train_write_which_ok(which)) return fail(c, UVAD_E_ARG, "uvad_sincnet_train_write: bad argument");
-    if (int r = sinc_train_state_check(c, "uvad_sincnet_train_write", d_state, state_bytes, false)) return r;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, launch_train_write(d_state, SNT_MAGIC, c->snts.P, c->snts.Pp, which, d_in, (hipStream_t)stream));
-    return UVAD_OK;
+    return c ? train_write(c, sinc_family(c), d_state, state_bytes, which, d_in, stream) : UVAD_E_ARG;
 }
 
 // ---- noise mixing of training batches (mix.hip) ------------------------------------------------------------------------------------------

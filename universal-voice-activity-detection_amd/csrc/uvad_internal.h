@@ -800,15 +800,21 @@ size_t head_train_state_bytes(const HeadTrainShape &q);
 HeadTrainWs head_train_ws(const HeadTrainShape &q, long long N, int seg);
 hipError_t launch_head_train_reset(const HeadTrainShape &q, const HeadTrainInit &in, void *state, hipStream_t s);
 hipError_t launch_head_train_grad(const HeadTrainShape &q, const HeadTrainGradArgs &a, hipStream_t s);
-hipError_t launch_head_train_apply(const HeadTrainShape &q, const HeadTrainAdam &o, void *state, hipStream_t s);
-hipError_t launch_head_train_read(const HeadTrainShape &q, const void *state, int which, float *out, hipStream_t s);
+// One training state of any family (head, LSTM, SincNet): the layout above under the family's magic word; state == nullptr: absent.  What works
+// on the blocks alone is launched once for all three, from optim.hip:
+//   apply  ht_adam_kernel, then the one-workgroup ht_adam_commit_kernel
+//   read   which = MASTERS / GRAD / M / V: the block's P floats; SCALARS: the family's scalar record
+//   write  MASTERS / M / V: P floats into that block; SCALARS: t, bc1, bc2 from the record's words (an LSTM state: the draw ordinal too)
+struct TrainBlock { void *state; unsigned magic; int P, Pp; };
+hipError_t launch_train_apply(const TrainBlock &b, const HeadTrainAdam &o, hipStream_t s);
+hipError_t launch_train_read(const TrainBlock &b, int which, float *out, hipStream_t s);
+hipError_t launch_train_write(const TrainBlock &b, int which, const float *in, hipStream_t s);
 
 // ---- lstm_train.hip: training of the top LSTM layers (uvad_lstm_train_*, include/uvad.h): forward with kept activations, BPTT, Adam ----
 // Layers first_layer .. num_layers - 1 learn; nl of them, layer index li = 0 .. nl - 1 from the bottom.  Frames are flat, n = b T + t, N = B T.
 // The trainable tensors are packed in state_dict order -- per layer, forward then _reverse: weight_ih [4H][in], weight_hh [4H][H],
 // bias_ih [4H], bias_hh [4H] (in = Din for li = 0, H x dirs above) -- P floats, padded to Pp = a multiple of 64.
-// State: HeadTrainHeader with LT_MAGIC (256 bytes) | masters [Pp] | gradient accumulator [Pp] | m [Pp] | v [Pp]: the head's layout, so the
-//        fold, Adam and read kernels of ht_kernels.h serve both.
+// State: HeadTrainHeader with LT_MAGIC (256 bytes) | masters [Pp] | gradient accumulator [Pp] | m [Pp] | v [Pp]: the head's layout (TrainBlock).
 // Workspace: LstmTrainWsHead (256 bytes: magic, B, T) | HeadTrainWsHead (the fold's record of the last backward) | valid [N] bytes |
 //            b_ih + b_hh [nl][dirs][4H] | per layer: gates [dirs][N][4H] (pre-activations, then i f g o, then dpre), c [dirs][N][H],
 //            h_prev [dirs][N][H], and below the top layer its output h [N][H dirs] | two gradient buffers [N][H dirs] (nl > 1) |
@@ -847,8 +853,6 @@ LstmTrainWs lstm_train_ws(const LstmTrainShape &q, long long N, int seg);
 hipError_t launch_lstm_train_reset(const LstmTrainShape &q, void *state, hipStream_t s);   // masters are copied in by the caller
 hipError_t launch_lstm_train_forward(const LstmTrainShape &q, const LstmTrainArgs &a, hipStream_t s);
 hipError_t launch_lstm_train_backward(const LstmTrainShape &q, const LstmTrainArgs &a, hipStream_t s);
-hipError_t launch_lstm_train_apply(const LstmTrainShape &q, const HeadTrainAdam &o, void *state, hipStream_t s);
-hipError_t launch_lstm_train_read(const LstmTrainShape &q, const void *state, int which, float *out, hipStream_t s);
 // the dropout mask of include/uvad.h as a stand-alone pass: out = keep ? x scale : +0 over [rows][cols]; in place when out == x
 constexpr int LT_DROP_MAX_COLS = 2048, LT_DROP_MAX_LAYER = 65535;
 unsigned lstm_dropout_threshold(float p);            // floor((double)p 2^32)
@@ -859,8 +863,8 @@ hipError_t launch_dropout_apply(const float *x, float *out, long long rows, int 
 // Stages first_stage .. 2 learn.  The 14 tensors in state_dict order (SNT_T_*): wav_norm1d.weight, .bias, conv1d.0.filterbank.low_hz_, band_hz_
 // (stage 0), conv1d.1.weight, .bias (stage 1), conv1d.2.weight, .bias (stage 2), norm1d.s.weight, .bias (stage s); the learning ones packed in
 // that order are the P floats of the Adam block, padded to Pp = a multiple of 64.
-// State: HeadTrainHeader with SNT_MAGIC (256 bytes) | masters [Pp] | gradient accumulator [Pp] | m [Pp] | v [Pp] (the head's layout: the fold,
-//        Adam and read kernels of ht_kernels.h serve it) | the bank [n_filters][kernel_size] the last forward call ran (padded to 64 floats) |
+// State: HeadTrainHeader with SNT_MAGIC (256 bytes) | masters [Pp] | gradient accumulator [Pp] | m [Pp] | v [Pp] (the head's layout: TrainBlock) |
+//        the bank [n_filters][kernel_size] the last forward call ran (padded to 64 floats) |
 //        all 14 tensors as reset found them, in order (the frozen stages run from here; padded) | window_ [kernel_size / 2] | n_ [kernel_size / 2]
 //        (each padded to 64 floats).
 // Workspace: SincTrainWsHead (256 bytes: magic ^ high word of S, B, S) | HeadTrainWsHead (the fold's record) | row statistics [B][4] | per stage:
@@ -895,10 +899,9 @@ SincTrainWs sinc_train_ws(const SincTrainShape &q, const SincTrainGeo &geo, int 
 hipError_t launch_sinc_train_forward(const SincTrainShape &q, const SincTrainArgs &a, hipStream_t s);
 hipError_t launch_sinc_train_backward(const SincTrainShape &q, const SincTrainArgs &a, hipStream_t s);
 hipError_t launch_sinc_train_bank(const SincTrainShape &q, void *state, hipStream_t s);   // the bank from the masters as they stand
-hipError_t launch_sinc_train_apply(const SincTrainShape &q, const HeadTrainAdam &o, void *state, hipStream_t s);
-hipError_t launch_sinc_train_read(const SincTrainShape &q, const void *state, int which, float *out, hipStream_t s);   // which 5: the bank
+hipError_t launch_sinc_train_read_bank(const SincTrainShape &q, const void *state, float *out, hipStream_t s);   // _read's which 5: the bank
 
-// ---- optim.hip: the joint optimizer step over the three training states (uvad_optim_*, include/uvad.h), and the _write calls of the families ----
+// ---- optim.hip: the joint optimizer step over the three training states (uvad_optim_*, include/uvad.h); the launch_train_* above live there too ----
 // State: OptimHeader (256 bytes) | the learning-rate table [cap] f32, padded to 64 floats.  cap is the n_lr of uvad_optim_reset (the shape the
 // kernels check beside the magic word), n <= cap the entries in use.
 // Workspace: one double per chunk of OPT_CHUNK parameters, the chunks of the head first, then the LSTM's, then SincNet's; padded to 256 bytes.
@@ -916,16 +919,13 @@ struct OptimHeader {
     int skip;                                        // byte 96: the step in flight is skipped (written by the fold, read by the update and the commit)
     int reserved[39];
 };                                                   // 256 bytes
-struct OptimFamily { void *state; unsigned magic; int P, Pp; };   // state == nullptr: the family is absent
 inline int optim_chunks(int P) { return (P + OPT_CHUNK - 1) / OPT_CHUNK; }
 inline size_t optim_state_bytes(int n_lr) { return sizeof(OptimHeader) + (size_t)((n_lr + 63) / 64 * 64) * sizeof(float); }
 inline size_t optim_ws_bytes(int chunks) { return ((size_t)chunks * sizeof(double) + 255) / 256 * 256; }
-hipError_t launch_optim_step(const OptimFamily fam[3], void *opt, int cap, double *part, hipStream_t s);
+hipError_t launch_optim_step(const TrainBlock fam[3], void *opt, int cap, double *part, hipStream_t s);
 hipError_t launch_optim_set_n(void *opt, int cap, int n, hipStream_t s);
 hipError_t launch_optim_read(const void *opt, int cap, unsigned *out, hipStream_t s);
 hipError_t launch_optim_write(void *opt, int cap, const unsigned *in, hipStream_t s);
-// MASTERS / M / V: P floats into that block; SCALARS: t, bc1, bc2 from the words of the family's scalar record (an LSTM state: the draw ordinal too)
-hipError_t launch_train_write(void *state, unsigned magic, int P, int Pp, int which, const float *in, hipStream_t s);
 
 // ---- mix.hip: noise mixing for training batches (uvad_mix_*, include/uvad.h): row energies, the plan of every row, the mix pass ----
 // State: MixHeader (256 bytes) | clip_first [n_clips + 1] int64 | clip energies [n_clips] f64 | amp [Q] f64; every part 256-byte aligned.

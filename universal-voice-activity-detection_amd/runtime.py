@@ -1300,6 +1300,63 @@ class VadRuntime:
             out.append(recs)
         return out
 
+    # ------------------------------------------------------------------ what the three training families share
+    # A handle carries its family, h["family"]: the library's entries are uvad_<family>_train_*; the record holds the packed key list of a
+    # handle and the words of the family's scalar record.
+    _TRAIN_FAMILIES = {"head": (lambda rt, h: rt.head_train_keys(), _lib.HEAD_TRAIN_SCALAR_WORDS),
+                       "lstm": (lambda rt, h: rt.lstm_train_keys(h["layers"]), _lib.LSTM_TRAIN_SCALAR_WORDS),
+                       "sincnet": (lambda rt, h: rt.sincnet_train_keys(h["first_stage"]), _lib.HEAD_TRAIN_SCALAR_WORDS)}
+    _TRAIN_BLOCKS = (("weights", _lib.HEAD_TRAIN_MASTERS), ("grad", _lib.HEAD_TRAIN_GRAD), ("m", _lib.HEAD_TRAIN_M), ("v", _lib.HEAD_TRAIN_V))
+
+    def _train_fn(self, h, op: str):
+        return getattr(self.lib, f"uvad_{h['family']}_train_{op}")
+
+    def _train_configure(self, h):
+        """The handle's configuration (an LSTM handle: its dropout setting too) on the context, before every call on the handle: host
+        only, the context serves any number of handles."""
+        self._check(self._train_fn(h, "configure")(self.ctx, C.byref(h["cfg"])))
+        if h["family"] == "lstm":
+            self._check(self.lib.uvad_lstm_train_set_dropout(self.ctx, h.get("dropout", 0.0), h.get("seed", 0)))
+
+    _lstm_train_configure = _train_configure   # the name the LSTM training tests call it by
+
+    def _train_apply(self, h):
+        with torch.cuda.device(self.device):
+            self._train_configure(h)
+            self._check(self._train_fn(h, "apply")(self.ctx, h["state"].data_ptr(), h["state"].numel(), self._stream()))
+
+    def _train_block(self, h, which: int) -> np.ndarray:
+        self._check(self._train_fn(h, "read")(self.ctx, h["state"].data_ptr(), h["state"].numel(), which, h["out"].data_ptr(), self._stream()))
+        return h["out"].cpu().numpy().copy()
+
+    def _train_read(self, h):
+        """Copy the state to the host (synchronises) -> ({"weights", "grad", "m", "v": {torch key: tensor}, "scalars" (the raw record: what
+        the family's _write takes back), "frames", "step", "bias_correction1", "bias_correction2" (1 - beta^step)}, the record's words);
+        the family adds what else its record or state holds."""
+        keys, words = self._TRAIN_FAMILIES[h["family"]]
+        with torch.cuda.device(self.device):
+            self._train_configure(h)
+            out = {}
+            for name, which in self._TRAIN_BLOCKS:
+                flat, off, d = self._train_block(h, which), 0, {}
+                for key, shape in keys(self, h):
+                    cnt = int(np.prod(shape))
+                    d[key] = torch.from_numpy(flat[off:off + cnt].reshape(shape).copy())
+                    off += cnt
+                out[name] = d
+            w = self._train_block(h, _lib.HEAD_TRAIN_SCALARS)[:words]
+        out["scalars"] = torch.from_numpy(w.view(np.int32).copy())
+        out["frames"] = int(w[2:4].view(np.uint64)[0])
+        out["step"] = int(w[4:6].view(np.uint64)[0])
+        out["bias_correction1"], out["bias_correction2"] = float(w[6]), float(w[7])
+        return out, w
+
+    def _train_commit(self, h):
+        with torch.cuda.device(self.device):
+            self._train_configure(h)
+            self._check(self._train_fn(h, "commit")(self.ctx, h["state"].data_ptr(), h["state"].numel()))
+            self._weights_gen = getattr(self, "_weights_gen", 0) + 1
+
     # ------------------------------------------------------------------ head fine-tuning (uvad_head_train_*)
     def head_train_keys(self):
         """[(torch key, shape)] of the trainable tensors in the packed order of uvad_head_train_read (state_dict order)."""
@@ -1319,7 +1376,7 @@ class VadRuntime:
         with torch.cuda.device(self.device):
             self._check(self.lib.uvad_head_train_configure(self.ctx, C.byref(cfg)))
             P = int(self.lib.uvad_head_train_param_count(self.ctx))
-            h = {"cfg": cfg, "P": P, "state": torch.empty(int(self.lib.uvad_head_train_state_bytes(self.ctx)), dtype=torch.uint8, device=self.device),
+            h = {"family": "head", "cfg": cfg, "P": P, "state": torch.empty(int(self.lib.uvad_head_train_state_bytes(self.ctx)), dtype=torch.uint8, device=self.device),
                  "ws": None, "out": torch.zeros(max(P, _lib.HEAD_TRAIN_SCALAR_WORDS), dtype=torch.float32, device=self.device)}
             self._check(self.lib.uvad_head_train_reset(self.ctx, h["state"].data_ptr(), h["state"].numel(), self._stream()))
             return h
@@ -1345,7 +1402,7 @@ class VadRuntime:
                         raise ValueError(f"{name} must be a ({B}, {T}) tensor on {self.device}")
                     self._rows_2d(t, dt, name)
             n = None if lengths is None else self._dev_lens(lengths, B, T, torch.int32, "lengths (frames)")
-            self._check(self.lib.uvad_head_train_configure(self.ctx, C.byref(h["cfg"])))   # host only: the context serves any number of handles
+            self._train_configure(h)
             need = int(self.lib.uvad_head_train_ws_bytes(self.ctx, B, T))
             if h["ws"] is None or h["ws"].numel() < need:
                 h["ws"] = torch.zeros(need, dtype=torch.uint8, device=self.device)
@@ -1365,33 +1422,13 @@ class VadRuntime:
 
     def head_train_apply(self, h):
         """One Adam step from the accumulated gradients divided by the accumulated frame count (uvad_head_train_apply)."""
-        with torch.cuda.device(self.device):
-            self._check(self.lib.uvad_head_train_configure(self.ctx, C.byref(h["cfg"])))
-            self._check(self.lib.uvad_head_train_apply(self.ctx, h["state"].data_ptr(), h["state"].numel(), self._stream()))
-
-    def _head_train_block(self, h, which: int) -> np.ndarray:
-        self._check(self.lib.uvad_head_train_read(self.ctx, h["state"].data_ptr(), h["state"].numel(), which, h["out"].data_ptr(), self._stream()))
-        return h["out"].cpu().numpy().copy()
+        self._train_apply(h)
 
     def head_train_read(self, h) -> dict:
         """Copy the state to the host (synchronises) -> {"weights", "grad", "m", "v": {torch key: tensor}, "loss" (accumulated sum),
-        "frames", "step", "bias_correction1", "bias_correction2" (1 - beta^step)}."""
-        with torch.cuda.device(self.device):
-            self._check(self.lib.uvad_head_train_configure(self.ctx, C.byref(h["cfg"])))
-            out = {}
-            for name, which in (("weights", _lib.HEAD_TRAIN_MASTERS), ("grad", _lib.HEAD_TRAIN_GRAD), ("m", _lib.HEAD_TRAIN_M), ("v", _lib.HEAD_TRAIN_V)):
-                flat, off, d = self._head_train_block(h, which), 0, {}
-                for key, shape in self.head_train_keys():
-                    cnt = int(np.prod(shape))
-                    d[key] = torch.from_numpy(flat[off:off + cnt].reshape(shape).copy())
-                    off += cnt
-                out[name] = d
-            w = self._head_train_block(h, _lib.HEAD_TRAIN_SCALARS)[:_lib.HEAD_TRAIN_SCALAR_WORDS]
-        out["scalars"] = torch.from_numpy(w.view(np.int32).copy())   # the raw record: what head_train_write takes back
+        "frames", "step", "bias_correction1", "bias_correction2" (1 - beta^step), "scalars" (the raw record)}."""
+        out, w = self._train_read(h)
         out["loss"] = float(w[0:2].view(np.float64)[0])
-        out["frames"] = int(w[2:4].view(np.uint64)[0])
-        out["step"] = int(w[4:6].view(np.uint64)[0])
-        out["bias_correction1"], out["bias_correction2"] = float(w[6]), float(w[7])
         return out
 
     def head_train_state_dict(self, h) -> dict:
@@ -1401,10 +1438,7 @@ class VadRuntime:
     def head_train_commit(self, h):
         """Make this runtime serve the adapted head (uvad_head_train_commit: synchronises, re-finalizes).  Graphs captured before are
         stale, as after load_state_dict."""
-        with torch.cuda.device(self.device):
-            self._check(self.lib.uvad_head_train_configure(self.ctx, C.byref(h["cfg"])))
-            self._check(self.lib.uvad_head_train_commit(self.ctx, h["state"].data_ptr(), h["state"].numel()))
-            self._weights_gen = getattr(self, "_weights_gen", 0) + 1
+        self._train_commit(h)
 
     # ------------------------------------------------------------------ LSTM training (uvad_lstm_train_*)
     def _lstm_train_shape(self, first_layer: int):
@@ -1442,7 +1476,7 @@ class VadRuntime:
             self._check(self.lib.uvad_lstm_train_configure(self.ctx, C.byref(cfg)))
             self._check(self.lib.uvad_lstm_train_set_dropout(self.ctx, dropout, int(seed) & 0xFFFFFFFFFFFFFFFF))
             P = int(self.lib.uvad_lstm_train_param_count(self.ctx))
-            h = {"cfg": cfg, "P": P, "layers": layers, "first_layer": cfg.first_layer, "ws": None, "bt": None,
+            h = {"family": "lstm", "cfg": cfg, "P": P, "layers": layers, "first_layer": cfg.first_layer, "ws": None, "bt": None,
                  "dropout": dropout, "seed": int(seed) & 0xFFFFFFFFFFFFFFFF,
                  "state": torch.empty(int(self.lib.uvad_lstm_train_state_bytes(self.ctx)), dtype=torch.uint8, device=self.device),
                  "out": torch.zeros(max(P, _lib.LSTM_TRAIN_SCALAR_WORDS), dtype=torch.float32, device=self.device)}
@@ -1468,11 +1502,6 @@ class VadRuntime:
             sib = self._lstm_prefix[first] = rt
         sib.classify(x, want_logits=True, want_probs=False, lengths=lengths)
         return sib.taps(lin=False)[0]
-
-    def _lstm_train_configure(self, h):
-        """The handle's configuration and dropout setting on the context (host only: the context serves any number of handles)."""
-        self._check(self.lib.uvad_lstm_train_configure(self.ctx, C.byref(h["cfg"])))
-        self._check(self.lib.uvad_lstm_train_set_dropout(self.ctx, h.get("dropout", 0.0), h.get("seed", 0)))
 
     def lstm_train_draws(self, h) -> int:
         """How many dropout masks the handle's forward calls have drawn: the 64-bit count at byte 56 of the state (synchronises)."""
@@ -1582,7 +1611,7 @@ class VadRuntime:
             return out if plan is None else (out, plan)
 
     def _lstm_train_ws(self, h, B: int, T: int):
-        self._lstm_train_configure(h)
+        self._train_configure(h)
         need = int(self.lib.uvad_lstm_train_ws_bytes(self.ctx, B, T))
         if h["ws"] is None or h["ws"].numel() < need:
             h["ws"] = torch.zeros(need, dtype=torch.uint8, device=self.device)
@@ -1625,33 +1654,13 @@ class VadRuntime:
 
     def lstm_train_apply(self, h):
         """One Adam step from the accumulated gradients divided by the accumulated frame count (uvad_lstm_train_apply)."""
-        with torch.cuda.device(self.device):
-            self._lstm_train_configure(h)
-            self._check(self.lib.uvad_lstm_train_apply(self.ctx, h["state"].data_ptr(), h["state"].numel(), self._stream()))
-
-    def _lstm_train_block(self, h, which: int) -> np.ndarray:
-        self._check(self.lib.uvad_lstm_train_read(self.ctx, h["state"].data_ptr(), h["state"].numel(), which, h["out"].data_ptr(), self._stream()))
-        return h["out"].cpu().numpy().copy()
+        self._train_apply(h)
 
     def lstm_train_read(self, h) -> dict:
         """Copy the state to the host (synchronises) -> {"weights", "grad", "m", "v": {torch key: tensor}, "frames", "step",
         "bias_correction1", "bias_correction2" (1 - beta^step), "draws" (the dropout draw ordinal), "scalars" (the raw record)}."""
-        with torch.cuda.device(self.device):
-            self._lstm_train_configure(h)
-            out = {}
-            for name, which in (("weights", _lib.HEAD_TRAIN_MASTERS), ("grad", _lib.HEAD_TRAIN_GRAD), ("m", _lib.HEAD_TRAIN_M), ("v", _lib.HEAD_TRAIN_V)):
-                flat, off, d = self._lstm_train_block(h, which), 0, {}
-                for key, shape in self.lstm_train_keys(h["layers"]):
-                    cnt = int(np.prod(shape))
-                    d[key] = torch.from_numpy(flat[off:off + cnt].reshape(shape).copy())
-                    off += cnt
-                out[name] = d
-            w = self._lstm_train_block(h, _lib.HEAD_TRAIN_SCALARS)[:_lib.LSTM_TRAIN_SCALAR_WORDS]
-        out["scalars"] = torch.from_numpy(w.view(np.int32).copy())   # the raw record: what lstm_train_write takes back
+        out, w = self._train_read(h)
         out["draws"] = int(w[8:10].view(np.uint64)[0])
-        out["frames"] = int(w[2:4].view(np.uint64)[0])
-        out["step"] = int(w[4:6].view(np.uint64)[0])
-        out["bias_correction1"], out["bias_correction2"] = float(w[6]), float(w[7])
         return out
 
     def lstm_train_state_dict(self, h) -> dict:
@@ -1661,10 +1670,7 @@ class VadRuntime:
     def lstm_train_commit(self, h):
         """Make this runtime serve the adapted layers (uvad_lstm_train_commit: synchronises, re-finalizes).  Graphs captured before are
         stale, as after load_state_dict; the frozen prefix's sibling context is untouched."""
-        with torch.cuda.device(self.device):
-            self._lstm_train_configure(h)
-            self._check(self.lib.uvad_lstm_train_commit(self.ctx, h["state"].data_ptr(), h["state"].numel()))
-            self._weights_gen = getattr(self, "_weights_gen", 0) + 1
+        self._train_commit(h)
 
     # ------------------------------------------------------------------ SincNet training (uvad_sincnet_train_*)
     def sincnet_train_keys(self, first_stage: int = 0):
@@ -1691,7 +1697,7 @@ class VadRuntime:
         with torch.cuda.device(self.device):
             self._check(self.lib.uvad_sincnet_train_configure(self.ctx, C.byref(cfg)))
             P = int(self.lib.uvad_sincnet_train_param_count(self.ctx))
-            h = {"cfg": cfg, "P": P, "first_stage": first_stage, "ws": None,
+            h = {"family": "sincnet", "cfg": cfg, "P": P, "first_stage": first_stage, "ws": None,
                  "state": torch.empty(int(self.lib.uvad_sincnet_train_state_bytes(self.ctx)), dtype=torch.uint8, device=self.device),
                  "out": torch.zeros(max(P, _lib.HEAD_TRAIN_SCALAR_WORDS, self._sn_c.n_filters * self._sn_c.kernel_size), dtype=torch.float32,
                                     device=self.device)}
@@ -1709,7 +1715,7 @@ class VadRuntime:
         return wav
 
     def _sincnet_train_ws(self, h, B: int, S: int):
-        self._check(self.lib.uvad_sincnet_train_configure(self.ctx, C.byref(h["cfg"])))   # host only: the context serves any number of handles
+        self._train_configure(h)
         need = int(self.lib.uvad_sincnet_train_ws_bytes(self.ctx, B, S))
         if need == 0:
             raise ValueError(f"uvad_sincnet_train does not serve B = {B}, S = {S} (at least one frame; B x L_0 <= 2^31 - 1; <= 65535 segments)")
@@ -1748,34 +1754,15 @@ class VadRuntime:
 
     def sincnet_train_apply(self, h):
         """One Adam step from the accumulated gradients divided by the accumulated frame count (uvad_sincnet_train_apply)."""
-        with torch.cuda.device(self.device):
-            self._check(self.lib.uvad_sincnet_train_configure(self.ctx, C.byref(h["cfg"])))
-            self._check(self.lib.uvad_sincnet_train_apply(self.ctx, h["state"].data_ptr(), h["state"].numel(), self._stream()))
-
-    def _sincnet_train_block(self, h, which: int) -> np.ndarray:
-        self._check(self.lib.uvad_sincnet_train_read(self.ctx, h["state"].data_ptr(), h["state"].numel(), which, h["out"].data_ptr(), self._stream()))
-        return h["out"].cpu().numpy().copy()
+        self._train_apply(h)
 
     def sincnet_train_read(self, h) -> dict:
         """Copy the state to the host (synchronises) -> {"weights", "grad", "m", "v": {torch key: tensor}, "filters" (the bank of the last
-        forward call, (n_filters, kernel_size)), "frames", "step", "bias_correction1", "bias_correction2" (1 - beta^step)}."""
-        with torch.cuda.device(self.device):
-            self._check(self.lib.uvad_sincnet_train_configure(self.ctx, C.byref(h["cfg"])))
-            out = {}
-            for name, which in (("weights", _lib.HEAD_TRAIN_MASTERS), ("grad", _lib.HEAD_TRAIN_GRAD), ("m", _lib.HEAD_TRAIN_M), ("v", _lib.HEAD_TRAIN_V)):
-                flat, off, d = self._sincnet_train_block(h, which), 0, {}
-                for key, shape in self.sincnet_train_keys(h["first_stage"]):
-                    cnt = int(np.prod(shape))
-                    d[key] = torch.from_numpy(flat[off:off + cnt].reshape(shape).copy())
-                    off += cnt
-                out[name] = d
-            nf, ks = self._sn_c.n_filters, self._sn_c.kernel_size
-            out["filters"] = torch.from_numpy(self._sincnet_train_block(h, _lib.SINCNET_TRAIN_FILTERS)[:nf * ks].reshape(nf, ks).copy())
-            w = self._sincnet_train_block(h, _lib.HEAD_TRAIN_SCALARS)[:_lib.HEAD_TRAIN_SCALAR_WORDS]
-        out["scalars"] = torch.from_numpy(w.view(np.int32).copy())   # the raw record: what sincnet_train_write takes back
-        out["frames"] = int(w[2:4].view(np.uint64)[0])
-        out["step"] = int(w[4:6].view(np.uint64)[0])
-        out["bias_correction1"], out["bias_correction2"] = float(w[6]), float(w[7])
+        forward call, (n_filters, kernel_size)), "frames", "step", "bias_correction1", "bias_correction2" (1 - beta^step), "scalars"}."""
+        out, _ = self._train_read(h)
+        nf, ks = self._sn_c.n_filters, self._sn_c.kernel_size
+        with torch.cuda.device(self.device):   # the context is still configured from h
+            out["filters"] = torch.from_numpy(self._train_block(h, _lib.SINCNET_TRAIN_FILTERS)[:nf * ks].reshape(nf, ks).copy())
         return out
 
     def sincnet_train_state_dict(self, h) -> dict:
@@ -1786,10 +1773,7 @@ class VadRuntime:
     def sincnet_train_commit(self, h):
         """Make this runtime serve the adapted front end (uvad_sincnet_train_commit: synchronises, re-finalizes; the bank served is the one
         the last forward call ran).  Graphs captured before are stale, as after load_state_dict."""
-        with torch.cuda.device(self.device):
-            self._check(self.lib.uvad_sincnet_train_configure(self.ctx, C.byref(h["cfg"])))
-            self._check(self.lib.uvad_sincnet_train_commit(self.ctx, h["state"].data_ptr(), h["state"].numel()))
-            self._weights_gen = getattr(self, "_weights_gen", 0) + 1
+        self._train_commit(h)
 
     # ------------------------------------------------------------------ the joint optimizer step (uvad_optim_*) and the _write calls
     def optim_open(self, cfg=None, lr_table=(1e-3,)):
@@ -1832,12 +1816,9 @@ class VadRuntime:
         if head is None and lstm is None and sincnet is None:
             raise ValueError("optim_step needs at least one training handle")
         with torch.cuda.device(self.device):
-            if head is not None:
-                self._check(self.lib.uvad_head_train_configure(self.ctx, C.byref(head["cfg"])))
-            if lstm is not None:
-                self._lstm_train_configure(lstm)
-            if sincnet is not None:
-                self._check(self.lib.uvad_sincnet_train_configure(self.ctx, C.byref(sincnet["cfg"])))
+            for h in (head, lstm, sincnet):
+                if h is not None:
+                    self._train_configure(h)
             need = int(self.lib.uvad_optim_ws_bytes(self.ctx))
             if o["ws"] is None or o["ws"].numel() < need:
                 o["ws"] = torch.zeros(need, dtype=torch.uint8, device=self.device)
@@ -1863,48 +1844,45 @@ class VadRuntime:
             self._check(self.lib.uvad_optim_write(self.ctx, o["state"].data_ptr(), o["state"].numel(), src.data_ptr(), self._stream()))
             o["_keep_w"] = src
 
-    def _train_write(self, h, fn, keys, st):
+    def _train_write(self, h, st):
         """The _write companion of a family's _read: st["weights"], st["m"], st["v"] ({torch key: tensor}) and st["scalars"] (the raw words)."""
-        keep = []
-        for name, which in (("weights", _lib.HEAD_TRAIN_MASTERS), ("m", _lib.HEAD_TRAIN_M), ("v", _lib.HEAD_TRAIN_V)):
-            if st.get(name) is None:
-                continue
-            parts = []
-            for key, shape in keys:
-                t = torch.as_tensor(st[name][key]).detach().to(torch.float32).cpu()
-                if tuple(t.shape) != tuple(shape):
-                    raise ValueError(f"{name}[{key}] has shape {tuple(t.shape)}, expected {tuple(shape)}")
-                parts.append(t.reshape(-1))
-            flat = torch.cat(parts).contiguous().to(self.device)
-            self._check(fn(self.ctx, h["state"].data_ptr(), h["state"].numel(), which, flat.data_ptr(), self._stream()))
-            keep.append(flat)
-        if st.get("scalars") is not None:
-            words = torch.zeros(_lib.LSTM_TRAIN_SCALAR_WORDS, dtype=torch.int32)
-            src = torch.as_tensor(st["scalars"]).to(torch.int32).reshape(-1)
-            words[:src.numel()] = src[:words.numel()]
-            words = words.to(self.device)
-            self._check(fn(self.ctx, h["state"].data_ptr(), h["state"].numel(), _lib.HEAD_TRAIN_SCALARS, words.data_ptr(), self._stream()))
-            keep.append(words)
-        h["_keep_w"] = keep          # the launches read them after this call returns
+        fn, keys = self._train_fn(h, "write"), self._TRAIN_FAMILIES[h["family"]][0](self, h)
+        with torch.cuda.device(self.device):
+            self._train_configure(h)
+            keep = []
+            for name, which in (("weights", _lib.HEAD_TRAIN_MASTERS), ("m", _lib.HEAD_TRAIN_M), ("v", _lib.HEAD_TRAIN_V)):
+                if st.get(name) is None:
+                    continue
+                parts = []
+                for key, shape in keys:
+                    t = torch.as_tensor(st[name][key]).detach().to(torch.float32).cpu()
+                    if tuple(t.shape) != tuple(shape):
+                        raise ValueError(f"{name}[{key}] has shape {tuple(t.shape)}, expected {tuple(shape)}")
+                    parts.append(t.reshape(-1))
+                flat = torch.cat(parts).contiguous().to(self.device)
+                self._check(fn(self.ctx, h["state"].data_ptr(), h["state"].numel(), which, flat.data_ptr(), self._stream()))
+                keep.append(flat)
+            if st.get("scalars") is not None:
+                words = torch.zeros(_lib.LSTM_TRAIN_SCALAR_WORDS, dtype=torch.int32)
+                src = torch.as_tensor(st["scalars"]).to(torch.int32).reshape(-1)
+                words[:src.numel()] = src[:words.numel()]
+                words = words.to(self.device)
+                self._check(fn(self.ctx, h["state"].data_ptr(), h["state"].numel(), _lib.HEAD_TRAIN_SCALARS, words.data_ptr(), self._stream()))
+                keep.append(words)
+            h["_keep_w"] = keep          # the launches read them after this call returns
 
     def head_train_write(self, h, st):
         """Put back what head_train_read returned (uvad_head_train_write): masters, m, v, and from "scalars" the step and the bias
         corrections.  The accumulated gradient, loss and frames are not written: a write belongs between steps."""
-        with torch.cuda.device(self.device):
-            self._check(self.lib.uvad_head_train_configure(self.ctx, C.byref(h["cfg"])))
-            self._train_write(h, self.lib.uvad_head_train_write, self.head_train_keys(), st)
+        self._train_write(h, st)
 
     def lstm_train_write(self, h, st):
         """head_train_write for an LSTM handle (uvad_lstm_train_write); "scalars" carries the dropout draw ordinal as well."""
-        with torch.cuda.device(self.device):
-            self._lstm_train_configure(h)
-            self._train_write(h, self.lib.uvad_lstm_train_write, self.lstm_train_keys(h["layers"]), st)
+        self._train_write(h, st)
 
     def sincnet_train_write(self, h, st):
         """head_train_write for a SincNet handle (uvad_sincnet_train_write); the bank is rebuilt from the masters by the next forward call."""
-        with torch.cuda.device(self.device):
-            self._check(self.lib.uvad_sincnet_train_configure(self.ctx, C.byref(h["cfg"])))
-            self._train_write(h, self.lib.uvad_sincnet_train_write, self.sincnet_train_keys(h["first_stage"]), st)
+        self._train_write(h, st)
 
     # ------------------------------------------------------------------ scoring against reference labels (uvad_score_*)
     def score_open(self, points=((0.5, 25),), collar: int = 0, bins: int = 256, segment: int = 0):
