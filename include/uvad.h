@@ -1427,7 +1427,7 @@ int uvad_sincnet_train_write(uvad_ctx *, void *d_state, size_t state_bytes, int 
  * phase (src/datasets/<corpus>/utils.py, enable_musan), once, on the host, before the features are stored.  Here the mix is a stage in front of uvad_fbank_lens /
  * uvad_sincnet_train_forward and is drawn anew for every batch: the draws come from the generator of the dropout stage above, the draw
  * ordinal lives on the device, so one captured graph draws a fresh mix per replay.  Not here: parity with lhotse itself, random start
- * offsets inside a clip, reverberation, speed perturbation.
+ * offsets inside a clip, speed perturbation (reverberation is the block behind this one).
  *
  * Noise bank: one caller-owned device buffer d_bank of f32 samples, n_clips clips back to back; h_clip_first [n_clips + 1] (host, int64)
  *   are the clips' first samples, h_clip_first[0] = 0, every clip at least 1 sample.  The state keeps the pointer: the bank must stay where
@@ -1491,6 +1491,84 @@ int uvad_mix_step(uvad_ctx *, const void *d_in, int fmt, int B, int64_t S, const
                   void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream);
 int uvad_mix_apply(uvad_ctx *, const void *d_in, int fmt, int B, int64_t S, const int64_t *d_nsamp, float *d_out, int32_t *d_plan,
                    int64_t row0, uint64_t draw, void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream);
+
+/* ---- Reverberation of training batches on the device ------------------------------------------------------------------------------------------
+ * More than a third of the corpora the reference trains and tests on are far-field or meeting-room audio (CHiME-6 mdm, DiPCo, AMI, DIHARD3,
+ * VoxConverse), and additive noise does not model a room.  This stage sits in front of uvad_mix_step (reverb, then noise, then uvad_fbank_lens /
+ * uvad_sincnet_train_forward): per batch and per row it either leaves the row alone or convolves it with one room impulse response (RIR) of a
+ * device-resident bank, what lhotse's reverb_rir does once on the host.  The draw is fresh per call and the draw ordinal lives on the device,
+ * so one captured graph of reverb -> mix -> front end -> train step replays with new draws.  Not here, and UNPINNED: parity with lhotse /
+ * torchaudio themselves (neither is available to the tests and the reference holds no fixture: the definition below is the contract);
+ * multi-channel responses; reverberating the noise bank; speed perturbation.
+ *
+ * Bank: one caller-owned device buffer d_rir of f32 taps, n_rirs responses back to back; h_rir_first [n_rirs + 1] (host, int64) are the
+ *   responses' first taps, h_rir_first[0] = 0, strictly increasing.  The state keeps the pointer: the bank must stay where it is and
+ *   unchanged while the state is in use.  Response r has K_r = its length, or min(length, max_taps) when max_taps > 0: a truncated tail
+ *   ("early reflections only" is a small max_taps).  K_r <= UVAD_REVERB_MAX_TAPS = 2^20 taps (65.5 s at 16 kHz); a longer response is
+ *   refused unless max_taps cuts it.  Taps and the samples of a drawn row are expected finite: the kernel multiplies the zeros around a row
+ *   and around a response like any other operand, so a NaN or Inf spreads further than the sum below says.
+ * Delay: uvad_reverb_reset computes, on the device, delay_r = the smallest k < K_r at which |h_r[k]| is largest (the direct path), and keeps
+ *   it in the state.  A NaN never wins the comparison (a response of NaNs has delay 0).
+ * Batch: d_in [B][S], fmt UVAD_INGEST_F32 or UVAD_INGEST_I16 (read as q / 32768); n_b = clamp(d_nsamp[b], 0, S) (S when d_nsamp is NULL);
+ *   d_out [B][S] f32.  d_out == d_in is refused: a row is read while it is written.
+ * Draws: Philox4x32-10 exactly as the dropout block above defines it, counter = (row0 + b, 0x52560000, draw_lo, draw_hi), key = (seed_lo,
+ *   seed_hi).  Word 1 of the counter differs from every segment index the mix stage uses (at most 63), so a mix state and a reverb state
+ *   under one seed stay independent.
+ *     word 0: the row is reverberated iff (uint64)w0 < floor(prob 2^32), a 64-bit compare: 1.0 always does, 0.0 never does;
+ *     word 1: r = (w1 n_rirs) >> 32;   words 2 and 3 are reserved.
+ * Convolution of a drawn row, with d = delay_r when align != 0 and d = 0 otherwise:
+ *     z[i] = sum_{k = 0}^{K_r - 1} h_r[k] x[i + d - k]   for 0 <= i < n_b,
+ *   x outside [0, n_b) is 0 and is never read.  The output has the row's own length (the tail is dropped, as lhotse does); with align the
+ *   direct path stays where it was, so frame labels stay valid.  Products are f32-exact (v_mfma_f32_32x32x2_f32, the arithmetic of the
+ *   training kernels; not the split-f16 planes).  Accumulation is in f32: ONE chain per output sample, starting from +0, over the taps in
+ *   increasing k (in front of k = 0 and behind k = K_r - 1 the chain holds products with zero taps, which change nothing).  The order is a
+ *   function of (K_r, i) alone, not of B, S, the grid or neighbouring rows.  No atomics: the same call gives the same bits.
+ *   UVAD_REVERB_TILE (output samples of a workgroup) and UVAD_REVERB_K_CHUNK (input offsets staged at a time) are the kernel's tile
+ *   constants, exported for the tests; no result depends on them.
+ * Normalisation (normalize != 0; lhotse's normalize_output): E_in = E(x, n_b) and E_out = E(z, n_b) over the f32 values of z, E exactly the
+ *   energy of the mix block above (the same double sum in the same order).  g = (float)sqrt(E_in / E_out): the division and the square
+ *   root correctly rounded double operations, then one rounding to f32; g = 1.0f when either energy is 0.  out = fl32(z g): one rounding,
+ *   no fused operation.  With normalize == 0, out = z.
+ * Rows not drawn are the input's f32 value bit for bit (a NaN payload and -0 pass through; int16: q / 32768).  Samples past a row's length
+ *   are +0 in d_out, in every row.
+ * Draw ordinal: a 64-bit count at byte 56 of the state (zeroed by reset).  uvad_reverb_step takes draw = the count and advances it by one, on
+ *   the device, in a single thread of its first kernel, whatever prob is.  uvad_reverb_apply takes draw and row0 as arguments and updates
+ *   nothing: row b of a batch equals a one-row apply with row0 = b, byte for byte.
+ * Plan record: d_plan (may be NULL) [B][UVAD_REVERB_PLAN_WORDS = 4] int32: {applied (0 / 1), r, d, the bits of g}; a row not drawn reads
+ *   {0, 0, 0, the bits of 1.0f}.  For logging and the tests.
+ * State (uvad_reverb_state_bytes; it does not depend on the bank's size): a 256-byte header {u32 magic, i32 n_rirs, normalize, align; byte 16
+ *   u64 floor(prob 2^32); byte 24 u64 seed; byte 32 i64 taps in the bank; byte 40 i32 max_taps; byte 56 u64 draw ordinal} | rir_first
+ *   [n_rirs + 1] int64 | K_r [n_rirs] int32 | delay_r [n_rirs] int32, every part padded to 256 bytes.
+ * Workspace (uvad_reverb_ws_bytes(B)): 256-byte header {byte 0 u64 the call's draw, byte 8 i64 row0} | the plan [B][4] as above, padded to
+ *   256 bytes.
+ * uvad_reverb_reset uploads the tables, computes the delays and zeroes the draw ordinal; it synchronises the stream and is not for graph
+ *   capture.  uvad_reverb_step and uvad_reverb_apply allocate nothing, never synchronise, read lengths and the ordinal on the device and can
+ *   be captured.  Their argument order is that of uvad_mix_step / uvad_mix_apply; uvad_reverb_ws_bytes has no second argument because the plan
+ *   row has a fixed width.
+ * Refusals (nothing enqueued).  UVAD_E_ARG: NULL ctx / cfg / d_rir / h_rir_first / d_in / d_out / d_state / d_ws; d_state or d_ws not
+ *   16-byte aligned, d_rir / d_in / d_out / d_plan not aligned to their element; prob outside [0, 1] or not finite; max_taps < 0; n_rirs < 1;
+ *   h_rir_first[0] != 0, an empty response or a non-monotone table, K_r > 2^20; B < 1; S < 1 or S > 2^31 - 1; B ceil(S / 4096) > 2^31 - 1;
+ *   state_bytes / ws_bytes below the helpers; an unknown fmt; d_out == d_in.
+ *   UVAD_E_STATE: a state that was never reset.  The size helpers return 0 on a bad argument. */
+#define UVAD_REVERB_PLAN_WORDS 4
+#define UVAD_REVERB_MAX_TAPS 1048576
+#define UVAD_REVERB_TILE 4096
+#define UVAD_REVERB_K_CHUNK 256
+typedef struct {
+    float prob;              /* the share of rows that are reverberated, [0, 1] */
+    int normalize;           /* != 0: scale the output to the input's energy */
+    int align;               /* != 0: keep the direct path where it was (d = delay_r) */
+    int max_taps;            /* > 0: use the first max_taps taps of every response; 0: all */
+    uint64_t seed;
+} uvad_reverb_cfg;
+size_t uvad_reverb_state_bytes(const uvad_reverb_cfg *, int n_rirs);
+size_t uvad_reverb_ws_bytes(int B);
+int uvad_reverb_reset(uvad_ctx *, void *d_state, size_t state_bytes, const uvad_reverb_cfg *, const float *d_rir, const int64_t *h_rir_first,
+                      int n_rirs, void *stream);
+int uvad_reverb_step(uvad_ctx *, const void *d_in, int fmt, int B, int64_t S, const int64_t *d_nsamp, float *d_out, int32_t *d_plan,
+                     void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream);
+int uvad_reverb_apply(uvad_ctx *, const void *d_in, int fmt, int B, int64_t S, const int64_t *d_nsamp, float *d_out, int32_t *d_plan,
+                      int64_t row0, uint64_t draw, void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream);
 
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;

@@ -79,12 +79,20 @@ class OptimCfg(C.Structure):     # uvad_optim_cfg (40 bytes)
                 ("decoupled", C.c_int), ("skip_nonfinite", C.c_int), ("lr_scale", C.c_float * 3)]
 
 
-INGEST_F32, INGEST_I16 = 0, 1    # `fmt` of uvad_mix_step / uvad_mix_apply (UVAD_INGEST_*)
+INGEST_F32, INGEST_I16 = 0, 1    # `fmt` of uvad_mix_step / uvad_mix_apply and uvad_reverb_step / uvad_reverb_apply (UVAD_INGEST_*)
 MIX_MAX_SEG, MIX_PLAN_HEAD, MIX_SEG_WORDS = 64, 4, 4     # the plan record of uvad_mix_step: int32 words per row = head + seg words x max_seg
 
 
 class MixCfg(C.Structure):       # uvad_mix_cfg (32 bytes)
     _fields_ = [("mix_prob", C.c_float), ("snr_steps", C.c_int), ("h_amp", C.POINTER(C.c_double)), ("max_seg", C.c_int), ("seed", C.c_uint64)]
+
+
+REVERB_PLAN_WORDS, REVERB_MAX_TAPS = 4, 1 << 20          # the plan record of uvad_reverb_step: {applied, r, d, gain bits}; taps per response at most
+REVERB_TILE, REVERB_K_CHUNK = 4096, 256                  # the convolution kernel's tile constants (UVAD_REVERB_TILE, UVAD_REVERB_K_CHUNK)
+
+
+class ReverbCfg(C.Structure):    # uvad_reverb_cfg (24 bytes)
+    _fields_ = [("prob", C.c_float), ("normalize", C.c_int), ("align", C.c_int), ("max_taps", C.c_int), ("seed", C.c_uint64)]
 
 
 class CutsCfg(C.Structure):
@@ -288,6 +296,13 @@ SIGNATURES = {
                                 C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_mix_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64,
                                  C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_reverb_state_bytes": (C.c_size_t, [C.POINTER(ReverbCfg), C.c_int]),
+    "uvad_reverb_ws_bytes": (C.c_size_t, [C.c_int]),
+    "uvad_reverb_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ReverbCfg), C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p]),
+    "uvad_reverb_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_reverb_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64,
+                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_cuts_max_per_row": (C.c_int, [C.POINTER(CutsCfg), C.c_int]),
     "uvad_cuts_max_samples": (C.c_int64, [C.POINTER(CutsCfg), C.c_int64]),
     "uvad_cuts_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),

@@ -104,6 +104,9 @@ def load_config() -> ConfigDict:
     cfg.musan.paths = []
     cfg.musan.snr = (10, 20)
     cfg.musan.mix_prob = 0.5
+    # ... and reverberation, in front of the noise (uvad_reverb_step): reverb = {"paths": [wav files, one room impulse response each],
+    # "prob": 0.5, "normalize": True, "align": True, "max_seconds": None} or None
+    cfg.reverb = None
 
     # function == "train" / "adapt" with adapt_lstm_layers: the joint optimizer step (uvad_optim_step).  All at their defaults: every state
     # takes its own plain Adam step, as before.  gradient_clip_val: the global gradient norm is clipped to it (0 = off); weight_decay with

@@ -2,7 +2,8 @@
 // mix_prob = 0.5) does to the training phase of every corpus recipe of the reference (src/datasets/*/utils.py), redrawn for every batch from
 // the Philox stream of the dropout stage (philox.h) instead of once on the host.  A step is three launches:
 //   mix_energy_kernel<fmt>   E = (sum (double)x (double)x) / n of every row, one workgroup of 1024 lanes per row in the fixed order of
-//                            include/uvad.h: lane t = (i / 4) mod 1024 adds its samples in increasing i, the lanes are folded by a tree.
+//                            include/uvad.h (energy_order.h, shared with reverb.hip): lane t = (i / 4) mod 1024 adds its samples in
+//                            increasing i, the lanes are folded by a tree.
 //                            16-byte loads where the row starts on a 16-byte boundary (8-byte for int16), guarded dword loads elsewhere and
 //                            in the group that holds the row's end; nothing at or past a length is read.  Its first thread takes the draw
 //                            ordinal from the state (uvad_mix_step) or the caller (uvad_mix_apply) and records it in the workspace header.
@@ -17,6 +18,7 @@
 //                            the bank, goes sample by sample.  In place (f32), tiles that keep the input's bits are skipped.
 // No floating-point atomics and no contraction (the Makefile's flag): the same call gives the same bits, and tests/mix_ref.py restates it.
 #include "../../include/uvad.h"
+#include "energy_order.h"
 #include "philox.h"
 #include "uvad_internal.h"
 
@@ -51,44 +53,6 @@ namespace {
 
 constexpr int MIX_TILE = 4096, MIX_PASS_THREADS = 256, MIX_PASS_BLOCKS = 8192;
 
-__device__ __forceinline__ long long mix_row_len(const long long *nsamp, long long b, long long S) {
-    if (!nsamp) return S;
-    const long long n = nsamp[b];
-    return n < 0 ? 0 : n > S ? S : n;
-}
-
-// samples i .. i + 3 of a row with n valid samples, as f32; an element at or past n is +0 and is not read.  vec: the row starts on a
-// 16-byte (f32) / 8-byte (int16) boundary, and i is a multiple of 4
-template <int FMT>
-__device__ __forceinline__ float4 mix_load4(const void *row, long long i, long long n, bool vec) {
-    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if constexpr (FMT == UVAD_INGEST_F32) {
-        const float *p = reinterpret_cast<const float *>(row) + i;
-        if (vec && i + 4 <= n) return *reinterpret_cast<const float4 *>(p);
-        if (i < n) v.x = p[0];
-        if (i + 1 < n) v.y = p[1];
-        if (i + 2 < n) v.z = p[2];
-        if (i + 3 < n) v.w = p[3];
-    } else {
-        constexpr float k = 1.0f / 32768.0f;
-        const short *p = reinterpret_cast<const short *>(row) + i;
-        if (vec && i + 4 <= n) {
-            const short4 q = *reinterpret_cast<const short4 *>(p);
-            return make_float4((float)q.x * k, (float)q.y * k, (float)q.z * k, (float)q.w * k);
-        }
-        if (i < n) v.x = (float)p[0] * k;
-        if (i + 1 < n) v.y = (float)p[1] * k;
-        if (i + 2 < n) v.z = (float)p[2] * k;
-        if (i + 3 < n) v.w = (float)p[3] * k;
-    }
-    return v;
-}
-
-template <int FMT>
-__device__ __forceinline__ bool mix_row_vec(const void *row) {
-    return (reinterpret_cast<uintptr_t>(row) & (FMT == UVAD_INGEST_F32 ? 15 : 7)) == 0;
-}
-
 // mode 0: the clips of the bank (rows = first[b] .. first[b + 1]); 1: a step (the state's ordinal, advanced); 2: apply (the caller's draw)
 struct MixEnergyArgs {
     const void *in; long long S; const long long *nsamp; const long long *first; double *energy;
@@ -113,30 +77,8 @@ __global__ __launch_bounds__(MIX_LANES) void mix_energy_kernel(MixEnergyArgs a) 
     else { base = b * a.S; n = mix_row_len(a.nsamp, b, a.S); }
     const void *row = FMT == UVAD_INGEST_F32 ? static_cast<const void *>(reinterpret_cast<const float *>(a.in) + base)
                                              : static_cast<const void *>(reinterpret_cast<const short *>(a.in) + base);
-    const bool vec = mix_row_vec<FMT>(row);
-    double acc = 0.0;
-    for (long long c0 = 0; c0 < n; c0 += 4LL * MIX_CHUNK) {     // four passes of the lanes in flight; the additions stay in index order
-        float4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = mix_load4<FMT>(row, c0 + (long long)u * MIX_CHUNK + 4 * t, n, vec);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {                           // a group past n is four +0: adding them changes no bit of a sum >= +0
-            acc += (double)v[u].x * (double)v[u].x;
-            acc += (double)v[u].y * (double)v[u].y;
-            acc += (double)v[u].z * (double)v[u].z;
-            acc += (double)v[u].w * (double)v[u].w;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);   // lanes t .. t + 63 of one wave: t += t + o
-    if ((t & 63) == 0) { s_lo[t >> 6] = __double2loint(acc); s_hi[t >> 6] = __double2hiint(acc); }
-    __syncthreads();
-    if (t < 64) {
-        double w = t < MIX_LANES / 64 ? __hiloint2double(s_hi[t], s_lo[t]) : 0.0;
-#pragma unroll
-        for (int o = MIX_LANES / 128; o > 0; o >>= 1) w += __shfl_down(w, o);   // the 16 wave sums: j += j + o
-        if (t == 0) a.energy[b] = n > 0 ? w / (double)n : 0.0;
-    }
+    const double w = mix_energy_sum<FMT>(row, n, s_lo, s_hi);     // energy_order.h: the order of include/uvad.h
+    if (t == 0) a.energy[b] = n > 0 ? w / (double)n : 0.0;
 }
 
 struct MixPlanArgs {

@@ -1,5 +1,6 @@
-// philox.h -- the one counter-based generator of the library: the dropout masks of lstm_train.hip and the noise-mix draws of mix.hip
-// (include/uvad.h defines both sets of coordinates; tests/lstm_dropout_ref.py restates the function).
+// philox.h -- the one counter-based generator of the library: the dropout masks of lstm_train.hip, the noise-mix draws of mix.hip and the
+// reverberation draws of reverb.hip
+// (include/uvad.h defines every set of coordinates; tests/lstm_dropout_ref.py restates the function).
 #pragma once
 #include <hip/hip_runtime.h>
 

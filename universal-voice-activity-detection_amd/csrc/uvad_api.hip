@@ -109,6 +109,8 @@ struct GateGroupPool { int G = 0, N = 0, unit_bytes = 0, history = 0, best_histo
 struct ScoreState { int n_points = 0, bins = 0; };
 // a noise-mix state (uvad_mix_*): the caller's bank and what reset fixed (the device header holds the same)
 struct MixState { const float *bank = nullptr; int n_clips = 0, Q = 0, max_seg = 0; };
+// a reverberation state (uvad_reverb_*): the same for the bank of impulse responses
+struct ReverbState { const float *bank = nullptr; int n_rirs = 0, normalize = 0; };
 
 struct uvad_ctx {
     std::map<void *, StreamCounters> streams;   // host mirror of the lock-step stream groups, keyed by d_state
@@ -138,6 +140,7 @@ struct uvad_ctx {
     uvad_sincnet_train_cfg snq{};
     SincTrainShape snts{};
     std::map<void *, MixState> mixes;           // ... and of the noise-mix states (uvad_mix_*)
+    std::map<void *, ReverbState> reverbs;      // ... and of the reverberation states (uvad_reverb_*)
     std::map<void *, int> optims;               // ... and of the optimizer states (uvad_optim_*): n_lr at reset
     int device = 0, n_cu = 256;
     bool has_fb = false, has_model = false, finalized = false, tables_set = false;
@@ -3957,6 +3960,106 @@ int uvad_mix_step(uvad_ctx *c, const void *d_in, int fmt, int B, int64_t S, cons
 int uvad_mix_apply(uvad_ctx *c, const void *d_in, int fmt, int B, int64_t S, const int64_t *d_nsamp, float *d_out, int32_t *d_plan, int64_t row0,
                    uint64_t draw, void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream) {
     return mix_call(c, "uvad_mix_apply", d_in, fmt, B, S, d_nsamp, d_out, d_plan, false, row0, draw, d_state, state_bytes, d_ws, ws_bytes, stream);
+}
+
+// ---- reverberation of training batches (reverb.hip) --------------------------------------------------------------------------------------
+// nullptr: the configuration is in range; else the word uvad_last_error names
+static const char *reverb_cfg_error(const uvad_reverb_cfg *q) {
+    if (!q) return "cfg is NULL";
+    if (!std::isfinite(q->prob) || q->prob < 0.0f || q->prob > 1.0f) return "prob must lie in [0, 1]";
+    if (q->max_taps < 0) return "max_taps must be >= 0";
+    return nullptr;
+}
+
+size_t uvad_reverb_state_bytes(const uvad_reverb_cfg *q, int n_rirs) {
+    if (reverb_cfg_error(q) || n_rirs < 1) return 0;
+    return reverb_layout(n_rirs).total;
+}
+
+size_t uvad_reverb_ws_bytes(int B) {
+    if (B < 1) return 0;
+    return reverb_ws_bytes(B);
+}
+
+int uvad_reverb_reset(uvad_ctx *c, void *d_state, size_t state_bytes, const uvad_reverb_cfg *q, const float *d_rir, const int64_t *h_rir_first,
+                      int n_rirs, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_state || !d_rir || !h_rir_first) return fail(c, UVAD_E_ARG, "uvad_reverb_reset: bad argument");
+    if (const char *e = reverb_cfg_error(q)) return fail(c, UVAD_E_ARG, std::string("uvad_reverb_reset: ") + e);
+    if (n_rirs < 1) return fail(c, UVAD_E_ARG, "uvad_reverb_reset: n_rirs must be at least 1");
+    if (reinterpret_cast<uintptr_t>(d_state) % 16) return fail(c, UVAD_E_ARG, "uvad_reverb_reset: d_state must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_rir) % 4) return fail(c, UVAD_E_ARG, "uvad_reverb_reset: d_rir must be 4-byte aligned");
+    if (h_rir_first[0] != 0) return fail(c, UVAD_E_ARG, "uvad_reverb_reset: h_rir_first[0] must be 0");
+    const ReverbLayout l = reverb_layout(n_rirs);
+    std::vector<char> host(l.total, 0);
+    int *taps = reinterpret_cast<int *>(host.data() + l.off_taps);
+    for (int i = 0; i < n_rirs; ++i) {
+        int64_t k = h_rir_first[i + 1] - h_rir_first[i];
+        if (k <= 0) return fail(c, UVAD_E_ARG, "uvad_reverb_reset: h_rir_first must increase: response " + std::to_string(i) + " is empty");
+        if (q->max_taps > 0) k = std::min<int64_t>(k, q->max_taps);
+        if (k > REVERB_MAX_TAPS)
+            return fail(c, UVAD_E_ARG, "uvad_reverb_reset: response " + std::to_string(i) + " has more than 2^20 taps: set max_taps");
+        taps[i] = (int)k;
+    }
+    if (state_bytes < l.total) return fail(c, UVAD_E_ARG, "uvad_reverb_reset: state too small: need " + std::to_string(l.total) + " bytes");
+    ReverbHeader h{};
+    h.magic = REVERB_MAGIC; h.n_rirs = n_rirs; h.normalize = q->normalize != 0; h.align = q->align != 0;
+    h.thr = (unsigned long long)__builtin_floor((double)q->prob * 4294967296.0);
+    h.seed = q->seed; h.bank_total = h_rir_first[n_rirs]; h.max_taps = q->max_taps; h.draws = 0;
+    std::memcpy(host.data(), &h, sizeof(h));
+    std::memcpy(host.data() + l.off_first, h_rir_first, ((size_t)n_rirs + 1) * 8);
+    c->reverbs.erase(d_state);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));      // what the stream still does to this state comes first
+    HIPCHK(c, hipMemcpy(d_state, host.data(), host.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, launch_reverb_delays(d_rir, d_state, n_rirs, (hipStream_t)stream));
+    HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));
+    ReverbState g;
+    g.bank = d_rir; g.n_rirs = n_rirs; g.normalize = h.normalize;
+    c->reverbs[d_state] = g;
+    return UVAD_OK;
+}
+
+static int reverb_call(uvad_ctx *c, const char *fn, const void *d_in, int fmt, int B, int64_t S, const int64_t *d_nsamp, float *d_out,
+                       int32_t *d_plan, bool take, int64_t row0, uint64_t draw, void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes,
+                       void *stream) {
+    if (!c) return UVAD_E_ARG;
+    const std::string f(fn);
+    if (!d_in || !d_out || !d_state || !d_ws) return fail(c, UVAD_E_ARG, f + ": bad argument");
+    if (fmt != UVAD_INGEST_F32 && fmt != UVAD_INGEST_I16) return fail(c, UVAD_E_ARG, f + ": fmt must be UVAD_INGEST_F32 or UVAD_INGEST_I16");
+    if (B < 1) return fail(c, UVAD_E_ARG, f + ": B must be at least 1");
+    if (S < 1 || S > MIX_MAX_S) return fail(c, UVAD_E_ARG, f + ": S must lie in [1, 2^31 - 1]");
+    if ((int64_t)B * ((S + REVERB_TILE - 1) / REVERB_TILE) > 2147483647LL) return fail(c, UVAD_E_ARG, f + ": B x ceil(S / 4096) must stay below 2^31");
+    if (reinterpret_cast<uintptr_t>(d_state) % 16 || reinterpret_cast<uintptr_t>(d_ws) % 16)
+        return fail(c, UVAD_E_ARG, f + ": d_state and d_ws must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_in) % (fmt == UVAD_INGEST_F32 ? 4 : 2) || reinterpret_cast<uintptr_t>(d_out) % 4 ||
+        reinterpret_cast<uintptr_t>(d_plan) % 4 || reinterpret_cast<uintptr_t>(d_nsamp) % 8)
+        return fail(c, UVAD_E_ARG, f + ": d_in, d_out, d_plan and d_nsamp must be aligned to their element");
+    if (d_in == static_cast<const void *>(d_out)) return fail(c, UVAD_E_ARG, f + ": d_out == d_in: a row is read while it is written");
+    auto it = c->reverbs.find(d_state);
+    if (it == c->reverbs.end()) return fail(c, UVAD_E_STATE, f + ": call uvad_reverb_reset on this state first");
+    const ReverbState &g = it->second;
+    const size_t need_state = reverb_layout(g.n_rirs).total, need_ws = reverb_ws_bytes(B);
+    if (state_bytes < need_state) return fail(c, UVAD_E_ARG, f + ": state too small: need " + std::to_string(need_state) + " bytes");
+    if (ws_bytes < need_ws) return fail(c, UVAD_E_ARG, f + ": workspace too small: need " + std::to_string(need_ws) + " bytes");
+    ReverbArgs a{};
+    a.in = d_in; a.fmt = fmt; a.B = B; a.S = S; a.nsamp = reinterpret_cast<const long long *>(d_nsamp);
+    a.out = d_out; a.plan = d_plan; a.bank = g.bank; a.state = d_state; a.ws = d_ws;
+    a.n_rirs = g.n_rirs; a.normalize = g.normalize;
+    a.take = take; a.draw = draw; a.row0 = row0;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_reverb(a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_reverb_step(uvad_ctx *c, const void *d_in, int fmt, int B, int64_t S, const int64_t *d_nsamp, float *d_out, int32_t *d_plan, void *d_state,
+                     size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream) {
+    return reverb_call(c, "uvad_reverb_step", d_in, fmt, B, S, d_nsamp, d_out, d_plan, true, 0, 0, d_state, state_bytes, d_ws, ws_bytes, stream);
+}
+
+int uvad_reverb_apply(uvad_ctx *c, const void *d_in, int fmt, int B, int64_t S, const int64_t *d_nsamp, float *d_out, int32_t *d_plan, int64_t row0,
+                      uint64_t draw, void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream) {
+    return reverb_call(c, "uvad_reverb_apply", d_in, fmt, B, S, d_nsamp, d_out, d_plan, false, row0, draw, d_state, state_bytes, d_ws, ws_bytes, stream);
 }
 
 // ---- speech cuts (cuts.hip) --------------------------------------------------------------------------------------------------------------

@@ -960,4 +960,34 @@ MixWs mix_ws(int B, int max_seg);
 hipError_t launch_mix_clip_energies(const float *bank, void *state, int n_clips, int Q, hipStream_t s);
 hipError_t launch_mix(const MixArgs &a, hipStream_t s);
 
+// ---- reverb.hip: reverberation of training batches (uvad_reverb_*, include/uvad.h): delays, the plan of every row, the convolution, gains ----
+// State: ReverbHeader (256 bytes) | rir_first [n_rirs + 1] int64 | taps K_r [n_rirs] int32 | delay_r [n_rirs] int32; every part 256-byte aligned.
+// Workspace: MixWsHead (256 bytes: the call's draw and first row index) | the plan [B][4] int32 (the record of include/uvad.h; d_plan is a copy).
+constexpr unsigned REVERB_MAGIC = 0x55565242u;       // "UVRB"
+constexpr int REVERB_PLAN_WORDS = 4;                 // UVAD_REVERB_PLAN_WORDS: {applied, r, d, gain bits}
+constexpr int REVERB_MAX_TAPS = 1 << 20;             // UVAD_REVERB_MAX_TAPS: K_r at most (65.5 s at 16 kHz)
+constexpr int REVERB_TILE = 4096;                    // UVAD_REVERB_TILE: output samples of one workgroup: 4 waves x 32 blocks x 32 phases
+constexpr int REVERB_KC = 256;                       // UVAD_REVERB_K_CHUNK: input offsets s staged in LDS at a time
+struct ReverbHeader {
+    unsigned magic; int n_rirs, normalize, align;
+    unsigned long long thr;                          // byte 16: floor(prob 2^32), 0 .. 2^32
+    unsigned long long seed;                         // byte 24
+    long long bank_total;                            // byte 32: taps in the bank = rir_first[n_rirs]
+    int max_taps, reserved0[3];                      // byte 40
+    unsigned long long draws;                        // byte 56: steps drawn so far (the draw ordinal), where the mix state keeps its own
+    int reserved[48];
+};                                                   // 256 bytes
+struct ReverbLayout { size_t off_first, off_taps, off_delay, total; };
+struct ReverbArgs {
+    const void *in; int fmt; int B; long long S; const long long *nsamp;
+    float *out; int *plan;                           // plan: the caller's copy, may be null
+    const float *bank; void *state; void *ws;
+    int n_rirs, normalize;
+    bool take; unsigned long long draw; long long row0;   // take: the draw is the state's ordinal, which advances; else `draw`
+};
+ReverbLayout reverb_layout(int n_rirs);
+size_t reverb_ws_bytes(int B);
+hipError_t launch_reverb_delays(const float *bank, void *state, int n_rirs, hipStream_t s);
+hipError_t launch_reverb(const ReverbArgs &a, hipStream_t s);
+
 }  // namespace uvad

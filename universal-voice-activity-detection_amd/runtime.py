@@ -1570,6 +1570,38 @@ class VadRuntime:
         """The row energies of the state's last step (synchronises)."""
         return st["ws"][256:256 + 8 * B].cpu().numpy().view(np.float64).copy()
 
+    def _augment_args(self, st, pcm, nsamp, out, plan, ws_bytes):
+        """What uvad_mix_step / uvad_reverb_step (and their _apply forms) share: the checked batch, the output and plan tensors, the
+        state's workspace grown to ws_bytes(B), and the argument lists in front of and behind (row0, draw).  -> (head, tail, out, plan)"""
+        i16 = pcm.dtype == torch.int16
+        if i16:
+            if pcm.device != self.device:
+                raise RuntimeError(f"pcm must be on {self.device}")
+            pcm = pcm.contiguous()
+        else:
+            pcm = self._dev_f32(pcm, "pcm")
+        B, S = pcm.shape
+        if out is None:
+            out = torch.empty((B, S), dtype=torch.float32, device=self.device)
+        if not (torch.is_tensor(out) and out.device == self.device and out.dtype == torch.float32 and tuple(out.shape) == (B, S) and
+                out.is_contiguous()):
+            raise ValueError("out must be a contiguous f32 tensor of pcm's shape on pcm's device")
+        if plan is True:
+            plan = torch.zeros((B, st["plan_words"]), dtype=torch.int32, device=self.device)
+        elif plan is False:
+            plan = None
+        elif not (torch.is_tensor(plan) and plan.device == self.device and plan.dtype == torch.int32 and
+                  tuple(plan.shape) == (B, st["plan_words"]) and plan.is_contiguous()):
+            raise ValueError(f"plan must be a contiguous int32 tensor of shape ({B}, {st['plan_words']}) on pcm's device")
+        n = None if nsamp is None else self._dev_lens(nsamp, B, S, torch.int64, "nsamp (samples)")
+        need = int(ws_bytes(B))
+        if st["ws"] is None or st["ws"].numel() < need:
+            st["ws"] = torch.zeros(need, dtype=torch.uint8, device=self.device)
+        head = (self.ctx, pcm.data_ptr(), _lib.INGEST_I16 if i16 else _lib.INGEST_F32, B, S, None if n is None else n.data_ptr(),
+                out.data_ptr(), None if plan is None else plan.data_ptr())
+        tail = (st["state"].data_ptr(), st["state"].numel(), st["ws"].data_ptr(), st["ws"].numel(), self._stream())
+        return head, tail, out, plan
+
     def mix_step(self, st, pcm: "torch.Tensor", nsamp=None, out=None, plan=False, draw=None, row0: int = 0):
         """pcm (B, S) f32 or int16 on the GPU -> the batch with noise mixed in, (B, S) f32 (uvad_mix_step: a fresh draw per call).
         nsamp: samples per row (B,), as fbank's lengths; out: the f32 tensor to write (pcm itself: in place; None allocates one);
@@ -1577,37 +1609,60 @@ class VadRuntime:
         (uvad_mix_apply: no state update), with row0 the index the first row draws under.  After the first call with a batch size
         nothing is allocated when out (and plan) are given: the call can be captured."""
         with torch.cuda.device(self.device):
-            i16 = pcm.dtype == torch.int16
-            if i16:
-                if pcm.device != self.device:
-                    raise RuntimeError(f"pcm must be on {self.device}")
-                pcm = pcm.contiguous()
-            else:
-                pcm = self._dev_f32(pcm, "pcm")
-            B, S = pcm.shape
-            if out is None:
-                out = torch.empty((B, S), dtype=torch.float32, device=self.device)
-            if not (torch.is_tensor(out) and out.device == self.device and out.dtype == torch.float32 and tuple(out.shape) == (B, S) and
-                    out.is_contiguous()):
-                raise ValueError("out must be a contiguous f32 tensor of pcm's shape on pcm's device")
-            if plan is True:
-                plan = torch.zeros((B, st["plan_words"]), dtype=torch.int32, device=self.device)
-            elif plan is False:
-                plan = None
-            elif not (torch.is_tensor(plan) and plan.device == self.device and plan.dtype == torch.int32 and
-                      tuple(plan.shape) == (B, st["plan_words"]) and plan.is_contiguous()):
-                raise ValueError(f"plan must be a contiguous int32 tensor of shape ({B}, {st['plan_words']}) on pcm's device")
-            n = None if nsamp is None else self._dev_lens(nsamp, B, S, torch.int64, "nsamp (samples)")
-            need = int(self.lib.uvad_mix_ws_bytes(B, st["max_seg"]))
-            if st["ws"] is None or st["ws"].numel() < need:
-                st["ws"] = torch.zeros(need, dtype=torch.uint8, device=self.device)
-            head = (self.ctx, pcm.data_ptr(), _lib.INGEST_I16 if i16 else _lib.INGEST_F32, B, S, None if n is None else n.data_ptr(),
-                    out.data_ptr(), None if plan is None else plan.data_ptr())
-            tail = (st["state"].data_ptr(), st["state"].numel(), st["ws"].data_ptr(), st["ws"].numel(), self._stream())
+            head, tail, out, plan = self._augment_args(st, pcm, nsamp, out, plan, lambda B: self.lib.uvad_mix_ws_bytes(B, st["max_seg"]))
             if draw is None:
                 self._check(self.lib.uvad_mix_step(*head, *tail))
             else:
                 self._check(self.lib.uvad_mix_apply(*head, int(row0), int(draw) & 0xFFFFFFFFFFFFFFFF, *tail))
+            return out if plan is None else (out, plan)
+
+    # ------------------------------------------------------------------ reverberation of training batches (uvad_reverb_*)
+    def reverb_open(self, bank, rir_lengths, prob: float = 0.5, normalize: bool = True, align: bool = True, max_taps: int = 0, seed: int = 0):
+        """Allocate and reset a reverberation state (uvad_reverb_reset).  bank: the room impulse responses back to back, a 1-D f32
+        tensor (moved to this device; the handle keeps it alive), rir_lengths: taps per response.  prob, normalize, align, max_taps
+        and seed as include/uvad.h.  The delays (direct paths) are computed on the device here."""
+        lens = [int(v) for v in rir_lengths]
+        if not lens or min(lens) < 1:
+            raise ValueError("every impulse response needs at least 1 tap")
+        if not 0.0 <= float(prob) <= 1.0:
+            raise ValueError("prob must lie in [0, 1]")
+        if int(max_taps) < 0:
+            raise ValueError("max_taps must be >= 0")
+        first = np.zeros(len(lens) + 1, np.int64)
+        first[1:] = np.cumsum(lens)
+        with torch.cuda.device(self.device):
+            bank = torch.as_tensor(bank, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
+            if bank.numel() != int(first[-1]):
+                raise ValueError(f"bank holds {bank.numel()} taps, the response lengths add up to {int(first[-1])}")
+            cfg = _lib.ReverbCfg(float(prob), int(bool(normalize)), int(bool(align)), int(max_taps), int(seed) & 0xFFFFFFFFFFFFFFFF)
+            st = {"cfg": cfg, "bank": bank, "first": first, "n_rirs": len(lens), "plan_words": _lib.REVERB_PLAN_WORDS, "ws": None,
+                  "state": torch.zeros(int(self.lib.uvad_reverb_state_bytes(C.byref(cfg), len(lens))), dtype=torch.uint8, device=self.device)}
+            self._check(self.lib.uvad_reverb_reset(self.ctx, st["state"].data_ptr(), st["state"].numel(), C.byref(cfg), bank.data_ptr(),
+                                                   first.ctypes.data_as(C.POINTER(C.c_int64)), len(lens), self._stream()))
+            return st
+
+    def reverb_draws(self, st) -> int:
+        """How many steps the state has drawn: the 64-bit count at byte 56 (synchronises)."""
+        return int(st["state"][56:64].cpu().numpy().view(np.uint64)[0])
+
+    def reverb_delays(self, st) -> np.ndarray:
+        """The responses' delays (direct paths) as uvad_reverb_reset computed them (synchronises)."""
+        pad = lambda v: (v + 255) // 256 * 256
+        off = 256 + pad(8 * (st["n_rirs"] + 1)) + pad(4 * st["n_rirs"])
+        return st["state"][off:off + 4 * st["n_rirs"]].cpu().numpy().view(np.int32).copy()
+
+    def reverb_step(self, st, pcm: "torch.Tensor", nsamp=None, out=None, plan=False, draw=None, row0: int = 0):
+        """pcm (B, S) f32 or int16 on the GPU -> the batch with the drawn rows reverberated, (B, S) f32 (uvad_reverb_step: a fresh draw
+        per call).  nsamp: samples per row (B,), as fbank's lengths; out: the f32 tensor to write (never pcm itself; None allocates
+        one); plan: True also returns the plan record (B, 4) int32, or pass the tensor to write.  draw: an explicit draw ordinal
+        (uvad_reverb_apply: no state update), with row0 the index the first row draws under.  After the first call with a batch size
+        nothing is allocated when out (and plan) are given: the call can be captured."""
+        with torch.cuda.device(self.device):
+            head, tail, out, plan = self._augment_args(st, pcm, nsamp, out, plan, self.lib.uvad_reverb_ws_bytes)
+            if draw is None:
+                self._check(self.lib.uvad_reverb_step(*head, *tail))
+            else:
+                self._check(self.lib.uvad_reverb_apply(*head, int(row0), int(draw) & 0xFFFFFFFFFFFFFFFF, *tail))
             return out if plan is None else (out, plan)
 
     def _lstm_train_ws(self, h, B: int, T: int):

@@ -932,6 +932,18 @@ def _resume_point(kwargs, model):
     return int(blob.get("epoch", 0)), int(blob.get("global_step", 0))
 
 
+def _wav_bank(paths, rt, sr, what):
+    """The first channel of every file as f32 (through _wav_recordings, so other sample rates pass through the ingest stage); without
+    files, one clip of one zero, for a stage that is switched off."""
+    clips = [np.zeros(1, np.float32)] if not paths else []
+    for p in paths:
+        pcm = np.asarray(_wav_recordings(p, "first", rt, sr)[0]["pcm"])
+        clips.append(pcm.astype(np.float32) * np.float32(1.0 / 32768.0) if pcm.dtype == np.int16 else pcm.astype(np.float32))
+        if len(clips[-1]) < 1:
+            raise ValueError(f"{p}: an empty {what} file")
+    return clips
+
+
 def _open_noise(kwargs, rt, seed, sr=16000):
     """train_vad's noise augmentation -> a mix state (VadRuntime.mix_open) or None.  ``noise`` = {"paths": [wav files], "snr": (10, 20),
     "mix_prob": 0.5, "snr_steps": 1024, "max_seg": 8, "seed": the run's}: what every training recipe of the reference does to its training
@@ -947,14 +959,37 @@ def _open_noise(kwargs, rt, seed, sr=16000):
     paths, mix_prob = list(noise.get("paths") or ()), float(noise.get("mix_prob", 0.5))
     if not paths and mix_prob != 0.0:
         raise ValueError('train_vad: noise needs "paths", a list of wav files')
-    clips = [np.zeros(1, np.float32)] if not paths else []
-    for p in paths:
-        pcm = np.asarray(_wav_recordings(p, "first", rt, sr)[0]["pcm"])
-        clips.append(pcm.astype(np.float32) * np.float32(1.0 / 32768.0) if pcm.dtype == np.int16 else pcm.astype(np.float32))
-        if len(clips[-1]) < 1:
-            raise ValueError(f"{p}: an empty noise file")
+    clips = _wav_bank(paths, rt, sr, "noise")
     return rt.mix_open(np.concatenate(clips), [len(c) for c in clips], snr=noise.get("snr", (10, 20)), mix_prob=mix_prob,
                        snr_steps=int(noise.get("snr_steps", 1024)), max_seg=int(noise.get("max_seg", 8)), seed=int(noise.get("seed", seed)))
+
+
+def _open_reverb(kwargs, rt, seed, sr=16000):
+    """train_vad's reverberation -> a reverb state (VadRuntime.reverb_open) or None.  ``reverb`` = {"paths": [wav files, one room impulse
+    response each], "prob": 0.5, "normalize": True, "align": True, "max_seconds": None (a number: only that much of every response),
+    "seed": the run's}: lhotse's reverb_rir, redrawn here for every batch on the device (uvad_reverb_step) in front of the noise mix.
+    prob = 0 needs no files: the stage runs and changes nothing."""
+    reverb = kwargs.get("reverb")
+    if reverb is None:
+        return None
+    paths, prob = list(reverb.get("paths") or ()), float(reverb.get("prob", 0.5))
+    if not paths and prob != 0.0:
+        raise ValueError('train_vad: reverb needs "paths", a list of wav files')
+    rirs = _wav_bank(paths, rt, sr, "impulse response")
+    max_seconds = reverb.get("max_seconds")
+    return rt.reverb_open(np.concatenate(rirs), [len(h) for h in rirs], prob=prob, normalize=bool(reverb.get("normalize", True)),
+                          align=bool(reverb.get("align", True)), max_taps=0 if max_seconds is None else max(1, int(round(float(max_seconds) * sr))),
+                          seed=int(reverb.get("seed", seed)))
+
+
+def _augment(rt, reverb, mix, x, nsamp=None):
+    """A stacked PCM batch through the augmentation chain, a fresh draw per batch: reverberation (into a new tensor: a row is read while
+    it is written), then noise (in place).  -> the augmented batch"""
+    if reverb is not None:
+        x = rt.reverb_step(reverb, x, nsamp=nsamp)
+    if mix is not None:
+        rt.mix_step(mix, x, nsamp=nsamp, out=x)
+    return x
 
 
 def _save_training_checkpoint(kwargs, model, out, epoch: int, global_step: int):
@@ -976,10 +1011,11 @@ def _train_vad_sincnet(kwargs, src, val_paths, val_labels, model, rt, device, se
     a window's labels are its own supervisions_feature_mask (supervision_frames, geometry "sincnet", over the window's own frames).
     The front end normalises over whole rows, so a batch holds rows of ONE length: full windows together, tails in batches of their
     own; a tail shorter than the receptive field (991 samples) has no frame and is skipped.  Shuffle, validation and the checkpoint are
-    train_vad's.  With ``noise`` every stacked batch is mixed on the device before its train_step; validation never is."""
+    train_vad's.  With ``reverb`` / ``noise`` every stacked batch is reverberated, then mixed, on the device before its train_step
+    (_augment); validation never is."""
     from .postprocess import read_label_file, supervision_frames
     net = model.model
-    mix = _open_noise(kwargs, rt, seed, sr)
+    mix, reverb = _open_noise(kwargs, rt, seed, sr), _open_reverb(kwargs, rt, seed, sr)
 
     def labels_of(items, t0, n):
         """(1, T) labels of the n samples from t0 seconds on, from the recording's intervals."""
@@ -1041,8 +1077,7 @@ def _train_vad_sincnet(kwargs, src, val_paths, val_labels, model, rt, device, se
                 picks = [windows[k] for k in ks[i:i + rows]]
                 x = torch.stack([train[r]["inputs"][0, s0:s0 + n] for r, s0, _, _ in picks])
                 y = torch.cat([lab for _, _, _, lab in picks])
-                if mix is not None:
-                    rt.mix_step(mix, x, out=x)                        # a fresh draw per batch, in place
+                x = _augment(rt, reverb, mix, x)                      # a fresh draw per batch
                 losses.append(model.train_step({"inputs": x, "is_voice": y}, step, accumulate=accumulate, optim=optim))
                 step += 1
         out["train_loss"].append(float(torch.stack(losses).mean()))
@@ -1063,7 +1098,8 @@ def train_vad(**kwargs):
     VadModel.train_step: all LSTM layers and the head learn, with the dropout of ``model_dict["lstm"]["dropout"]`` (the reference's 0.5
     by default) between the LSTM layers, ``accumulate_grad_batches`` calls per Adam step, lr = ``learning_rate``.  With ``noise``
     (_open_noise) the PCM is cached instead of the features, windows are cut in samples, and every batch is mixed with noise on the
-    device and framed with its rows' own lengths; ``noise = None`` launches what a run without the option launches.  Every
+    device and framed with its rows' own lengths; ``reverb`` (_open_reverb) takes the same branch and reverberates every batch in front of
+    the mix; ``noise = None`` and ``reverb = None`` launch what a run without the options launches.  Every
     ``check_val_every_n_epoch`` epochs (and after the last) the tensors are committed and validation_step runs on the held-out
     recordings (``input.val_paths``; the training files without them).  Saves a Lightning-style checkpoint {"state_dict" (``model.``
     keys), "epoch", "global_step", "optimizer_states"} to experiments_dir/checkpoint-epoch=NN.ckpt and returns {"train_loss": [per epoch],
@@ -1076,8 +1112,8 @@ def train_vad(**kwargs):
     ``load_checkpoint`` and a checkpoint that carries "optimizer_states" the run CONTINUES: moments, step counts, bias corrections, the
     dropout draw ordinal and the optimizer's step index are restored and the epochs after the checkpoint's run, so that an interrupted
     run and an uninterrupted one end in the same bytes (with accumulate_grad_batches > 1 a partly accumulated step at the interruption
-    is lost).  The noise mix's draw ordinal is not part of the checkpoint: a resumed run with ``noise`` draws other mixes than an
-    uninterrupted one."""
+    is lost).  The draw ordinals of the noise mix and the reverberation are not part of the checkpoint: a resumed run with ``noise``
+    or ``reverb`` draws others than an uninterrupted one."""
     from .postprocess import read_label_file, supervision_frames
     src = kwargs["input"]
     if src.get("kind") != "wav" or not src.get("paths") or len(src.get("labels", ())) != len(src["paths"]):
@@ -1117,13 +1153,13 @@ def train_vad(**kwargs):
         iv[0, :len(table)] = table
         return {"inputs": feats, "is_voice": rt.intervals_to_labels(iv, [len(table)], T).clone()}
 
-    mix = _open_noise(kwargs, rt, seed, sr)
+    mix, reverb = _open_noise(kwargs, rt, seed, sr), _open_reverb(kwargs, rt, seed, sr)
     window_s = float(kwargs.get("window_seconds") or 5.0)
     rows = max(1, int(float(kwargs["max_duration"]) / window_s))
     epochs, every = int(kwargs.get("max_epochs", 10)), max(1, int(kwargs.get("check_val_every_n_epoch", 1)))
     accumulate = max(1, int(kwargs.get("accumulate_grad_batches", 1)))
     out = {"train_loss": [], "val_loss": [], "val_metrics": None}
-    if mix is None:
+    if mix is None and reverb is None:
         train = [recording(p, l) for p, l in zip(src["paths"], src["labels"])]
         held = train if (val_paths, val_labels) == (list(src["paths"]), list(src["labels"])) else [recording(p, l) for p, l in zip(val_paths, val_labels)]
         W = max(1, int(round(window_s / kwargs["frame_shift"])))
@@ -1137,8 +1173,8 @@ def train_vad(**kwargs):
                 x[i, :n], y[i, :n] = train[r]["inputs"][0, s:s + n], train[r]["is_voice"][0, s:s + n]
             return {"inputs": x, "is_voice": y, "lengths": [n for _, _, n in picks]}
     else:
-        # noise: the PCM is cached instead of the features, windows are cut in samples, and every batch is mixed (a fresh draw), then
-        # framed with its rows' own lengths; a window's labels are computed over its own frames, as _train_vad_sincnet does
+        # noise / reverb: the PCM is cached instead of the features, windows are cut in samples, and every batch is augmented (a fresh
+        # draw), then framed with its rows' own lengths; a window's labels are computed over its own frames, as _train_vad_sincnet does
         def waveform(path, label_path):
             pcm = np.asarray(_wav_recordings(path, "first", rt, sr)[0]["pcm"])
             pcm = pcm.astype(np.float32) * np.float32(1.0 / 32768.0) if pcm.dtype == np.int16 else pcm.astype(np.float32)
@@ -1165,13 +1201,13 @@ def train_vad(**kwargs):
                     windows.append((r, s0, n, T, labels_of(b["items"], s0 / float(sr), n, T)))
 
         def batch_of(picks):
-            """Rows of Wn samples, mixed on the device, then their log-mel features with each row's own length."""
+            """Rows of Wn samples, augmented on the device, then their log-mel features with each row's own length."""
             x = torch.zeros((len(picks), Wn), dtype=torch.float32, device=device)
             y = torch.zeros((len(picks), W), dtype=torch.uint8, device=device)
             for i, (r, s0, n, T, lab) in enumerate(picks):
                 x[i, :n], y[i, :T] = train[r]["pcm"][s0:s0 + n], lab[0, :T]
             nsamp = [n for _, _, n, _, _ in picks]
-            rt.mix_step(mix, x, nsamp=nsamp, out=x)
+            x = _augment(rt, reverb, mix, x, nsamp)
             return {"inputs": rt.fbank(x, lengths=nsamp), "is_voice": y, "lengths": [T for _, _, _, T, _ in picks]}
 
     def validate(epoch):

@@ -6,6 +6,7 @@
 ``seed_weights``-- deterministic weights for a PyanNet2: uniform(-1/sqrt(fan), 1/sqrt(fan)) like
                    torch's default init, times ``scale`` (x4 makes the outputs span 0.03..0.99
                    instead of the ~0.506 flat line of the default init).
+``rir``         -- a seeded synthetic room impulse response for the reverberation stage's tests and tools (no RIR corpus ships).
 """
 import math
 
@@ -29,6 +30,20 @@ def synth_pcm(B: int, S: int, seed: int = 1000, sample_rate: int = 16000, first:
             x = x + 0.15 * env * sig
         out[i] = np.clip(x, -1.0, 1.0).astype(np.float32)
     return out
+
+
+def rir(taps: int, rt60_seconds: float, direct_at: int = 0, seed: int = 0, sample_rate: int = 16000) -> np.ndarray:
+    """``taps`` f32 taps: zeros in front of a unit direct path at tap ``direct_at``, behind it Gaussian noise of amplitude 0.5 that has
+    decayed by 60 dB after ``rt60_seconds`` (clipped below the direct path, so the direct path stays the largest tap)."""
+    if not 0 <= direct_at < taps:
+        raise ValueError("direct_at must lie inside the response")
+    rng = np.random.default_rng(seed)
+    t = np.arange(taps - direct_at, dtype=np.float64) / sample_rate
+    tail = np.clip(0.5 * rng.standard_normal(taps - direct_at) * 10.0 ** (-3.0 * t / max(float(rt60_seconds), 1e-6)), -0.95, 0.95)
+    h = np.zeros(taps, np.float32)
+    h[direct_at:] = tail.astype(np.float32)
+    h[direct_at] = 1.0
+    return h
 
 
 def synth_pcm_device(B: int, S: int, seed: int, device, first: int = 0) -> torch.Tensor:
