@@ -1630,6 +1630,22 @@ int uvad_set_recurrent_tile(uvad_ctx *, int sequences);
 int uvad_set_time_chunks(uvad_ctx *, int chunks);
 int uvad_get_time_chunks(const uvad_ctx *);
 int uvad_get_recurrent_tile(const uvad_ctx *);
+/* How many steps the caller keeps in flight at once, this context's included (one context and stream per step: ForwardPipeline).
+ * The large input projections (x_t W_ih^T, PyanNet2.py:169-172) and the fused head run as persistent grids of one workgroup per CU,
+ * and such a workgroup and a recurrence workgroup cannot share a CU (registers).  A grid over the whole chip keeps every CU until
+ * its last tile is done, so the recurrences that the other steps launch meanwhile wait for it and the steps fall into lockstep.
+ * With n > 1 the persistent grids of a call that is not time-chunked leave (n - 1) x rec_cus CUs free, rec_cus being the
+ * workgroups of this call's own recurrence launch (ceil(B / 16) x directions in the 16-sequence form, ceil(B / 4) x directions
+ * in the 4-sequence form): max(per, (CUs - reserve) / per x per) workgroups, per = 8 x (4 x hidden x directions / 128).  A
+ * reserve above half the CUs is not made: so many steps keep every CU taken anyway and smaller grids were measured to lose there
+ * (whole-chip grids again).  The tile queue hands every tile out once whatever the grid: outputs are bit-identical for every n.
+ *   1  (default) the call runs alone: grids over the whole chip;   n >= 1 accepted.
+ * uvad_get_projection_grid: the workgroups of the weight-stationary projection launches of the most recent uvad_classify /
+ * uvad_forward* call (0 = it launched none: small launches and the other GEMM modes run the tile-streaming kernels).
+ * Replaces nothing in the reference (its inference is one batch at a time, src/scripts/predict.py:98). */
+int uvad_set_concurrent_steps(uvad_ctx *, int n);
+int uvad_get_concurrent_steps(const uvad_ctx *);
+int uvad_get_projection_grid(const uvad_ctx *);
 /* 1 if the throughput form runs its fourth product (P2 x h, the residue plane of the exact three-way split of W_hh) on the 8-bit
  * matrix pipe (v_mfma_scale_f32_16x16x128_f8f6f4): decided by uvad_finalize, which checks that EVERY element of every layer's P2 plane is
  * exactly a bf8 (E5M2) number after one power-of-two shift, so the weights stay exact (the residue of two round-to-nearest f16

@@ -371,6 +371,9 @@ SIGNATURES = {
     "uvad_weights_shared_by": (C.c_int, [C.c_void_p]),
     "uvad_set_time_chunks": (C.c_int, [C.c_void_p, C.c_int]),
     "uvad_get_time_chunks": (C.c_int, [C.c_void_p]),
+    "uvad_set_concurrent_steps": (C.c_int, [C.c_void_p, C.c_int]),
+    "uvad_get_concurrent_steps": (C.c_int, [C.c_void_p]),
+    "uvad_get_projection_grid": (C.c_int, [C.c_void_p]),
     "uvad_recurrent_tile_for": (C.c_int, [C.c_void_p, C.c_int]),
     "uvad_streams_overlap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "uvad_set_timing": (C.c_int, [C.c_void_p, C.c_int]),

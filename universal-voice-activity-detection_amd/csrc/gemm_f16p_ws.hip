@@ -372,7 +372,7 @@ bool gemm_f16p_ws_supported(const GemmArgs &a, int n_cu) {
     return mt * (a.N / 128) >= 2L * (n_cu > 0 ? n_cu : 256);
 }
 
-hipError_t launch_gemm_f16p_ws(const GemmArgs &a, unsigned *counters, int n_cu, hipStream_t s) {
+hipError_t launch_gemm_f16p_ws(const GemmArgs &a, unsigned *counters, int n_cu, hipStream_t s, int *grid_used, int grid_cus) {
     if (!gemm_f16p_ws_supported(a, n_cu) || !counters || !a.Ah || !a.Al || !a.Wsplit16 || !a.C || a.ldw != a.K) return hipErrorInvalidValue;
     const int mt = (a.M + 127) / 128, nt = a.N / 128;
     if (a.ws_tiles) {
@@ -384,8 +384,9 @@ hipError_t launch_gemm_f16p_ws(const GemmArgs &a, unsigned *counters, int n_cu, 
     if (e != hipSuccess) return e;
     // one workgroup per CU; every (group, column tile) pair must own at least one workgroup: a multiple of 8 * nt
     const int per = GROUPS * nt;
-    int grid = (n_cu > 0 ? n_cu : 256) / per * per;
+    int grid = (grid_cus > 0 ? grid_cus : n_cu > 0 ? n_cu : 256) / per * per;
     if (grid < per) grid = per;
+    if (grid_used) *grid_used = grid;
     if (a.products != 0 && a.products != 3 && a.products != 4) return hipErrorInvalidValue;
     const bool three = a.products == 3;
 #define UVAD_WS_LAUNCH(NKB_)                                                                                                          \

@@ -170,6 +170,9 @@ struct uvad_ctx {
     // time-chunked layers (uvad_set_time_chunks): the projection of chunk i + 1 on a side stream beside the recurrence of chunk i
     int chunk_mode = 0;                    // 0 = automatic, 1 = off, n > 1 = n chunks wherever the chunked form can run
     int chunks_used = 0;                   // chunks of the most recent classify / forward (1 = not chunked)
+    // steps the caller keeps in flight on other contexts (uvad_set_concurrent_steps): sizes the persistent projection grids
+    int concurrent_steps = 1;
+    int proj_grid_used = 0;                // workgroups of the most recent call's weight-stationary projections (0 = it launched none)
     hipStream_t side = nullptr;            // the library's own stream for the chunk projections
     hipStream_t side_for = nullptr;        // the caller stream `side` was PROVEN concurrent with (nullptr: not yet probed / not concurrent)
     bool side_probed_for_null = false;     // (a null caller stream is a valid key: remember that it was probed)
@@ -1195,6 +1198,17 @@ static int auto_time_chunks(int T, int tiles, int D, int n_cu) {
     return std::min(6, T / 96);   // (lengths grow x 1.3 per chunk: six chunks of T = 1000 are 78 ... 290 frames)
 }
 
+// CUs a call's persistent projection grids may take when the caller keeps n steps in flight (uvad_set_concurrent_steps): what is left
+// after the other n - 1 steps each hold the CUs of one recurrence launch (rec_cus workgroups, one per CU).  At least 1 (the launcher
+// rounds to whole column-tile groups).  A reserve above SLOT_GRID_RESERVE_NUM / _DEN of the chip is not made: so many steps keep every
+// CU taken whatever the grids are, and a smaller grid then only makes each projection longer (profiles/slot_grid.json).
+constexpr long SLOT_GRID_RESERVE_NUM = 1, SLOT_GRID_RESERVE_DEN = 2;
+static int slot_grid_cus(int n_cu, int n, int rec_cus) {
+    const long reserve = (long)(n - 1) * rec_cus;
+    if (reserve * SLOT_GRID_RESERVE_DEN > (long)n_cu * SLOT_GRID_RESERVE_NUM) return n_cu;
+    return (int)std::max(1L, (long)n_cu - reserve);
+}
+
 // One run of the classifier (LSTM stack, feed-forward layers, head) on B sequences of T frames.  The options default to what uvad_classify
 // asks for; every caller names the ones it sets.
 struct ClassifyCall {
@@ -1310,6 +1324,18 @@ static int classify_impl(uvad_ctx *c, const ClassifyCall &rq) {
         }
     }
     c->chunks_used = NC;
+    c->proj_grid_used = 0;
+    // Steps in flight on other contexts (uvad_set_concurrent_steps(n), n > 1): a projection workgroup and a recurrence workgroup
+    // exclude each other on a CU (registers), and a persistent grid over the whole chip holds every CU until its last tile is done, so
+    // a recurrence that another step launches meanwhile cannot start one workgroup and the steps fall into lockstep.  The grid
+    // therefore leaves the other n - 1 steps the CUs of a recurrence launch like this call's own; the tile queue hands out the same
+    // tiles whatever the grid (same bits).  slot_grid_cus says where the cut stops paying.
+    int cu_proj = c->n_cu;
+    if (c->concurrent_steps > 1 && NC == 1 && !use_stack) {
+        const bool tile16 = !ss && H == 128 && W.layers[0].w_hh16_ok &&
+                            (c->rec_tile_mode ? c->rec_tile_mode : lstm_auto_tile(w.tiles, D, H, c->n_cu)) == 16;
+        cu_proj = slot_grid_cus(c->n_cu, c->concurrent_steps, (tile16 ? (w.tiles + 3) / 4 : w.tiles) * D);
+    }
     for (int k = 0; k < (use_stack ? 0 : m.num_layers); ++k) {
         const LayerDev &L = W.layers[k];
         GemmArgs g{};
@@ -1341,7 +1367,7 @@ static int classify_impl(uvad_ctx *c, const ClassifyCall &rq) {
                     GemmArgs gi = g;
                     gi.ws_tiles = plan->d_list; gi.ws_dirs = D;
                     for (int d = 0; d < D; ++d) { gi.ws_off[d] = plan->off[d][i]; gi.ws_len[d] = plan->len[d][i]; }
-                    HIPCHK(c, launch_gemm_f16p_ws(gi, ctr, cu_side, c->side));   // (chunk 0 too: on the whole chip it was 0.1 ms shorter and the layer's recurrences 0.3 ms longer)
+                    HIPCHK(c, launch_gemm_f16p_ws(gi, ctr, cu_side, c->side, &c->proj_grid_used));   // (chunk 0 too: on the whole chip it was 0.1 ms shorter and the layer's recurrences 0.3 ms longer)
                     HIPCHK(c, hipEventRecord(c->ev_chunk[i], c->side));
                 }
                 float *hst = reinterpret_cast<float *>(base + w.off_hc);
@@ -1363,7 +1389,7 @@ static int classify_impl(uvad_ctx *c, const ClassifyCall &rq) {
                 continue;
             }
             if (mode_is_ws(c) && gemm_f16p_ws_supported(g, c->n_cu))   // large launches: weights stay in registers, bit-identical gates
-                HIPCHK(c, launch_gemm_f16p_ws(g, reinterpret_cast<unsigned *>(base + w.off_ctr), c->n_cu, s));
+                HIPCHK(c, launch_gemm_f16p_ws(g, reinterpret_cast<unsigned *>(base + w.off_ctr), c->n_cu, s, &c->proj_grid_used, cu_proj));
             else
                 HIPCHK(c, launch_gemm_f16p(g, s));
             if (k == 0 && check_range) {   // the same projection by the exact kernel, run only if the flag is set
@@ -1409,7 +1435,8 @@ static int classify_impl(uvad_ctx *c, const ClassifyCall &rq) {
         h.logits = d_logits; h.probs = d_probs; h.tiles = w.tiles; h.T = T; h.B = B; h.ld_out = ld_out > 0 ? ld_out : T;
         h.counter = reinterpret_cast<unsigned *>(base + w.off_ctr);
         h.products = mode_products(c);
-        HIPCHK(c, launch_head_fused(h, c->n_cu, s));
+        // (its workgroups take a whole CU's registers as the projections' do: the same share of the chip, at least a quarter)
+        HIPCHK(c, launch_head_fused(h, std::max(c->n_cu / 4, cu_proj), s));
         if (lens) HIPCHK(c, launch_lens_fill(d_logits, d_probs, B, T, h.ld_out, lens, s));
         if (timing) {
             HIPCHK(c, hipEventRecord(c->ev[3], s));
@@ -4643,6 +4670,16 @@ int uvad_set_time_chunks(uvad_ctx *c, int chunks) {
 }
 
 int uvad_get_time_chunks(const uvad_ctx *c) { return c ? c->chunks_used : UVAD_E_ARG; }
+
+int uvad_set_concurrent_steps(uvad_ctx *c, int n) {
+    if (!c) return UVAD_E_ARG;
+    if (n < 1) return fail(c, UVAD_E_ARG, "concurrent steps must be 1 (this context's calls run alone) or more");
+    c->concurrent_steps = n;
+    return UVAD_OK;
+}
+
+int uvad_get_concurrent_steps(const uvad_ctx *c) { return c ? c->concurrent_steps : UVAD_E_ARG; }
+int uvad_get_projection_grid(const uvad_ctx *c) { return c ? c->proj_grid_used : UVAD_E_ARG; }
 
 int uvad_recurrent_tile_for(const uvad_ctx *c, int B) {
     if (!c || !c->has_model || B <= 0) return UVAD_E_ARG;

@@ -82,7 +82,9 @@ int gemm_f16p_padded_k(int K);   // gemm_f16p.hip: plane row width for a true wi
 // kernel; bit-identical output.  `counters` = gemm_f16p_ws_counter_bytes() of device memory (zeroed by the launcher on the stream).
 bool gemm_f16p_ws_supported(const GemmArgs &a, int n_cu);
 size_t gemm_f16p_ws_counter_bytes();
-hipError_t launch_gemm_f16p_ws(const GemmArgs &a, unsigned *counters, int n_cu, hipStream_t s);
+// grid_cus: CUs the persistent grid may take (0 = n_cu; rounded down to a multiple of 8 column-tile groups, at least one);
+// grid_used: the workgroups launched.
+hipError_t launch_gemm_f16p_ws(const GemmArgs &a, unsigned *counters, int n_cu, hipStream_t s, int *grid_used = nullptr, int grid_cus = 0);
 size_t weight_plane_elems(int N, int ldw);
 bool split_weights_f16x3(const float *w, int N, int ldw, unsigned short *out /*3 * weight_plane_elems*/, float *wscale);   // false: not representable
 // canonical f32 features [B][T][F] -> the same with frames t >= clamp(lens[b], 0, T) zero (never read): the operand of a lens classify

@@ -77,6 +77,7 @@ class ForwardPipeline:
                     # recurrence leaves idle); with several steps in flight those CUs belong to the other slots, and a slot's first
                     # submit would run the side-stream probe beside busy neighbours.  One launch per layer here.
                     r.set_time_chunks(1)
+                r.set_concurrent_steps(self.depth)   # the persistent grids leave the other slots' recurrences their CUs
             self.select_streams()
         except Exception:
             self.close()
@@ -136,6 +137,8 @@ class ForwardPipeline:
             raise ValueError(f"active depth {n} outside 1..{self.depth}")
         self._active = n
         self._k = 0
+        for r in self.runtimes:
+            r.set_concurrent_steps(n)
 
     def synchronize(self):
         for s in self.streams or []:

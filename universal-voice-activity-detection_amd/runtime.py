@@ -2677,6 +2677,18 @@ class VadRuntime:
         """What the most recent classify / forward ran (1 = not chunked)."""
         return int(self.lib.uvad_get_time_chunks(self.ctx))
 
+    def set_concurrent_steps(self, n: int):
+        """Steps the caller keeps in flight at once, this context's included (include/uvad.h): with n > 1 the persistent projection
+        and head grids leave the other steps' recurrences their CUs.  1 = the call runs alone (default); outputs are bit-identical."""
+        self._check(self.lib.uvad_set_concurrent_steps(self.ctx, int(n)))
+
+    def concurrent_steps(self) -> int:
+        return int(self.lib.uvad_get_concurrent_steps(self.ctx))
+
+    def projection_grid(self) -> int:
+        """Workgroups of the weight-stationary projection launches of the most recent classify / forward (0 = it launched none)."""
+        return int(self.lib.uvad_get_projection_grid(self.ctx))
+
     def der_counts(self, pred: "torch.Tensor", gt: "torch.Tensor") -> "torch.Tensor":
         """pred, gt (B, T) uint8 0/1 on the GPU -> (B, 2) int32 counts {false alarm, missed detection}."""
         with torch.cuda.device(self.device):
