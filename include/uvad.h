@@ -1570,6 +1570,107 @@ int uvad_reverb_step(uvad_ctx *, const void *d_in, int fmt, int B, int64_t S, co
 int uvad_reverb_apply(uvad_ctx *, const void *d_in, int fmt, int B, int64_t S, const int64_t *d_nsamp, float *d_out, int32_t *d_plan,
                       int64_t row0, uint64_t draw, void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream);
 
+/* ---- Training batches drawn on the device ------------------------------------------------------------------------------------------------------
+ * The first stage of the chain sampler -> reverb -> mix -> front end -> train step: it cuts a device-resident corpus into windows, walks a
+ * shuffled epoch order per dataset, multiplexes the datasets by weight, gathers the batch's samples and rasterises its frame labels.  It is the
+ * reference's cut_into_windows(duration).filter(duration > min) ... .pad(duration), SimpleCutSampler(shuffle, drop_last), CutSet.mux(weights)
+ * (data_module.py:140-151) and supervisions_feature_mask (custom_vad.py:41-75) as ONE definition that every draw follows; the cursors and the
+ * draw ordinal live on the device, so one captured graph replays with a new batch.  No atomics: the same call gives the same bytes.
+ * UNPINNED, and not claimed: parity with lhotse's samplers (their order comes from Python's random module; neither lhotse nor a fixture is
+ * available to the tests): the definition below is the contract, tests/sampler_ref.py restates it.
+ *
+ * Corpus (caller-owned; the state keeps the pointer, the buffer must stay where it is and unchanged while the state is in use): d_pcm, the
+ *   samples of R recordings back to back, fmt UVAD_INGEST_F32 or UVAD_INGEST_I16 (read as q / 32768); h_rec_first [R + 1] (host, int64) the
+ *   recordings' first samples, h_rec_first[0] = 0, every recording 1 .. 2^31 - 1 samples.  Supervisions: h_sup [n_sup][2] (host, int64)
+ *   {start, end} in samples of their own recording, h_sup_first [R + 1] (host, int32) each recording's range (h_sup_first[0] = 0, not
+ *   decreasing, h_sup_first[R] = n_sup; h_sup may be NULL when n_sup = 0).  Supervisions may be unsorted, overlapping, empty, negative or past
+ *   the end.  h_rec_set [R] (host, int32): each recording's dataset in 0 .. D - 1, 1 <= D <= UVAD_SAMPLER_MAX_SETS; h_weight [D] (host,
+ *   doubles) finite and > 0.  All host tables are copied by reset.
+ * Window table (built by uvad_sampler_reset on the host): recording r gives the windows {r, start = k W, n = min(W, len_r - k W)} for
+ *   k = 0, 1, ..; a window is kept iff n > min_keep, a strict comparison (the reference's `> 3`), 0 <= min_keep < W -- so every full window
+ *   is kept and only a recording's last, short one can go.  Windows are grouped by dataset, in recording order inside a dataset, in k order
+ *   inside a recording: dataset d owns the N_d windows first_d .. first_d + N_d - 1.  A dataset without a window is refused; at most
+ *   2^31 - 1 windows in all.  The table is stored per recording (kept windows of a recording are k = 0 .. K_r - 1): the state's size does not
+ *   depend on the corpus' length.
+ * Epoch order: the permutation is never stored.  perm(N, seed, d, e, p) for 0 <= p < N: 0 when N = 1; else k = max(8, bits(N - 1)) rounded
+ *   up to even (bits(v) = the position of v's highest set bit, plus one), half = k / 2, mask = 2^half - 1, and starting from x = p repeat,
+ *   until x < N (cycle walking over a bijection of [0, 2^k): the walk ends):
+ *     L = x >> half, R = x & mask; four rounds t = 0 .. 3 of (L, R) = (R, L ^ (F & mask)), F = word 0 of Philox4x32-10 (the dropout block's
+ *     generator) on counter (R | t << 16, 0x53500000 | d, e_lo, e_hi), key (seed_lo, seed_hi), R being the round's input; x = L << half | R.
+ *   shuffle == 0 makes perm the identity (validation).  Counter word 1 differs from the mix stage's segment indices (at most 63), the reverb
+ *   stage's 0x52560000 and every dropout layer word (layer << 16 | j >> 2 with layer below 0x5253): one seed serves all of them.  The minimum
+ *   k of 8 is part of the definition (smaller domains are visibly biased).
+ * A step of B rows.  Row b draws its dataset from Philox counter (row0 + b, 0x53440000, draw_lo, draw_hi), key (seed_lo, seed_hi): the first
+ *   d with (uint64)w0 < cum[d], cum[d] = floor(2^32 ((w_0 + .. + w_d) / sum)) in double, the sums taken left to right, sum = w_0 + .. +
+ *   w_{D - 1}, cum[D - 1] = 2^32 (D = 1: always 0).  Its position is c = cursor_d + (the rows b' < b of the same dataset); e = c / L_d,
+ *   p = c mod L_d, window = first_d + perm(N_d, seed, d, e, p).  L_d = N_d, except that drop_last != 0 needs D = 1 and uses
+ *   L = floor(N / batch) batch, batch being the cfg's: the step's B must equal it, N < batch is refused, and the last N - L windows of every
+ *   epoch's permutation are skipped (SimpleCutSampler(drop_last=True)).  After planning one thread adds every dataset's row count to its
+ *   cursor and 1 to the draw ordinal.  uvad_sampler_apply takes h_cursor [D] (host, int64, >= 0), draw and row0 as arguments and updates
+ *   nothing: row b of a batch equals a one-row apply with row0 = b and its own cursor, byte for byte.  The two calls share every kernel.
+ * Gather: d_out [B][ld_out >= W] f32: the window's n samples -- f32 bit for bit (a NaN payload and -0 pass through), int16 q / 32768 -- then
+ *   +0 up to W; columns [W, ld_out) are untouched.  d_nsamp [B] int64 = len_b = n, or W when pad != 0 (the reference's .pad(duration): the
+ *   waveform model's rows share a length).  16-byte stores from the first 16-byte boundary of the output row, 16-byte loads when the source
+ *   is aligned with them (the source offset of a window is arbitrary: recordings are packed back to back), element by element before and behind.
+ * Labels: d_labels [B][ld_gt >= T] uint8 and d_frames [B] int32, T = frames(W), T_b = frames(len_b), frames = uvad_num_frames for
+ *   UVAD_SAMPLER_FBANK and uvad_sincnet_num_frames for UVAD_SAMPLER_SINCNET (the context's configuration at reset).  A supervision {s, e} of
+ *   the window's recording is clipped to rs = max(s - start, 0), re = min(e - start, n), skipped when re <= rs, and sets the frames
+ *   [st, et) n [0, T_b) to 1:
+ *     FBANK    st = rs / hop, et = re / hop (integer division; hop = the context's frame shift in samples);
+ *     SINCNET  st = rs > 0 ? max(floordiv(rs - half, step), 0) : 0,  et = re < len_b ? max(floordiv(re - half, step), 0) : T_b
+ *              (half, step from the cfg; the reference's 496 and 270; custom_vad.py:41-75 with postprocess.supervision_frames' clamp).
+ *   Bytes [T_b, T) are 0, bytes [T, ld_gt) untouched.  The walk over a recording's supervisions is brute force.
+ * Plan record: d_plan (may be NULL) [B][UVAD_SAMPLER_PLAN_WORDS = 8] int32: {dataset, epoch (low word), position p, window, recording, start,
+ *   n, T_b}.
+ * State (uvad_sampler_state_bytes(cfg, R, n_sup, D)): a 256-byte header {u32 magic, i32 R, n_sup, D; byte 16 i64 W; byte 24 u64 seed; byte 32
+ *   i64 samples in the corpus; byte 40 i32 fmt, geometry; byte 48 i32 windows in all, batch; byte 56 u64 draw ordinal; byte 64 i32 shuffle,
+ *   drop_last, pad, half, step, hop, frame_len, snip_edges; byte 96 i32 the three kernel widths and the stride of the waveform front end; byte
+ *   112 i64 min_keep} | 64 dataset entries of 32 bytes {i64 cursor, i64 L_d, u64 cum[d], i32 first_d, i32 N_d} | the recordings in table order
+ *   [R] int32 | their first windows [R + 1] int32 | rec_first [R + 1] int64 | sup_first [R + 1] int32 | sup [n_sup][2] int64, every part
+ *   padded to 256 bytes.  Workspace (uvad_sampler_ws_bytes(B)): 256-byte header {byte 0 u64 the call's draw, byte 8 i64 row0} | the plan
+ *   [B][8] as above, padded to 256 bytes.
+ * uvad_sampler_reset builds the table, uploads it and zeroes the cursors and the ordinal; it synchronises the stream and is not for graph
+ *   capture.  uvad_sampler_step and uvad_sampler_apply allocate nothing, never synchronise and can be captured.  uvad_sampler_read writes the
+ *   record {draw ordinal, cursor_0 .. cursor_{D - 1}} (1 + D int64, device memory) and uvad_sampler_write sets it (a negative cursor is stored as 0; the convention of
+ *   uvad_optim_read / uvad_optim_write: device buffers, on the stream, no synchronisation): a resumed run continues to the bytes of an
+ *   uninterrupted one.
+ * Refusals (nothing enqueued, uvad_last_error names the word).  UVAD_E_ARG: NULL ctx / cfg / d_pcm / h_rec_first / h_sup_first / h_rec_set /
+ *   h_weight / d_out / d_nsamp / d_labels / d_frames / d_state / d_ws / h_cursor, NULL h_sup with n_sup > 0; d_state or d_ws not 16-byte aligned,
+ *   d_pcm / d_out / d_nsamp / d_frames / d_plan not aligned to their element; an unknown fmt; R < 1, n_sup < 0, D outside [1, 64];
+ *   h_rec_first[0] != 0, an empty recording, a non-monotone table or a recording above 2^31 - 1 samples; a bad h_sup_first; a dataset index out
+ *   of range, a dataset without windows; a weight not finite or <= 0; W < 1 or > 2^31 - 1; min_keep outside [0, W); drop_last with D > 1, with
+ *   batch < 1, with N < batch, or a step with another B; an unknown geometry, step < 1 or half < 0 (SINCNET); a window without a frame; B < 1;
+ *   ld_out < W or ld_gt < T; a negative cursor; state_bytes / ws_bytes below the helpers.
+ *   UVAD_E_STATE: a state that was never reset; the label geometry's configuration missing from the context (no feature configuration for
+ *   FBANK, no uvad_sincnet_configure for SINCNET).  The size helpers return 0 on a bad argument. */
+#define UVAD_SAMPLER_FBANK 0
+#define UVAD_SAMPLER_SINCNET 1
+#define UVAD_SAMPLER_PLAN_WORDS 8
+#define UVAD_SAMPLER_MAX_SETS 64
+typedef struct {
+    int64_t window;          /* W: samples of a window */
+    int64_t min_keep;        /* a window is kept iff it has MORE samples than this; [0, W) */
+    int geometry;            /* UVAD_SAMPLER_FBANK / UVAD_SAMPLER_SINCNET: which frame grid the labels are on */
+    int half, step;          /* SINCNET: the receptive field's half width and the frame step in samples (496, 270) */
+    int shuffle;             /* 0: table order (validation) */
+    int drop_last;           /* != 0: an epoch is floor(N / batch) batch windows (D = 1 only) */
+    int pad;                 /* != 0: d_nsamp = W for every row (short windows count as zero-padded) */
+    int batch;               /* the batch size drop_last refers to */
+    uint64_t seed;
+} uvad_sampler_cfg;
+size_t uvad_sampler_state_bytes(const uvad_sampler_cfg *, int R, int n_sup, int D);
+size_t uvad_sampler_ws_bytes(int B);
+int uvad_sampler_reset(uvad_ctx *, void *d_state, size_t state_bytes, const uvad_sampler_cfg *, const void *d_pcm, int fmt,
+                       const int64_t *h_rec_first, int R, const int64_t *h_sup, const int32_t *h_sup_first, int n_sup, const int32_t *h_rec_set,
+                       const double *h_weight, int D, void *stream);
+int uvad_sampler_step(uvad_ctx *, int B, float *d_out, int64_t ld_out, int64_t *d_nsamp, uint8_t *d_labels, int64_t ld_gt, int32_t *d_frames,
+                      int32_t *d_plan, void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream);
+int uvad_sampler_apply(uvad_ctx *, int B, float *d_out, int64_t ld_out, int64_t *d_nsamp, uint8_t *d_labels, int64_t ld_gt, int32_t *d_frames,
+                       int32_t *d_plan, const int64_t *h_cursor, int64_t row0, uint64_t draw, void *d_state, size_t state_bytes, void *d_ws,
+                       size_t ws_bytes, void *stream);
+int uvad_sampler_read(uvad_ctx *, const void *d_state, size_t state_bytes, int64_t *d_out, void *stream);
+int uvad_sampler_write(uvad_ctx *, void *d_state, size_t state_bytes, const int64_t *d_in, void *stream);
+
 /* Which kernel runs the time-parallel contractions (input projections, feed-forward layers):
  *   0  exact f32: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain, bit-compatible with f32 FMA arithmetic;
  *   1  (default) f32-accurate on the f16 matrix cores: weights scaled by a power of two and split on the host into THREE

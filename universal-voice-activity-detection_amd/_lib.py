@@ -95,6 +95,15 @@ class ReverbCfg(C.Structure):    # uvad_reverb_cfg (24 bytes)
     _fields_ = [("prob", C.c_float), ("normalize", C.c_int), ("align", C.c_int), ("max_taps", C.c_int), ("seed", C.c_uint64)]
 
 
+SAMPLER_FBANK, SAMPLER_SINCNET = 0, 1                     # uvad_sampler_cfg.geometry (UVAD_SAMPLER_*)
+SAMPLER_PLAN_WORDS, SAMPLER_MAX_SETS = 8, 64              # the plan record of uvad_sampler_step: {dataset, epoch, position, window, recording, start, n, T_b}
+
+
+class SamplerCfg(C.Structure):   # uvad_sampler_cfg (56 bytes)
+    _fields_ = [("window", C.c_int64), ("min_keep", C.c_int64), ("geometry", C.c_int), ("half", C.c_int), ("step", C.c_int), ("shuffle", C.c_int),
+                ("drop_last", C.c_int), ("pad", C.c_int), ("batch", C.c_int), ("seed", C.c_uint64)]
+
+
 class CutsCfg(C.Structure):
     _fields_ = [("pad", C.c_int), ("max_len", C.c_int), ("min_len", C.c_int), ("hop", C.c_int), ("lead", C.c_int), ("tail", C.c_int)]
 
@@ -303,6 +312,17 @@ SIGNATURES = {
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
     "uvad_reverb_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64,
                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_sampler_state_bytes": (C.c_size_t, [C.POINTER(SamplerCfg), C.c_int, C.c_int, C.c_int]),
+    "uvad_sampler_ws_bytes": (C.c_size_t, [C.c_int]),
+    "uvad_sampler_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SamplerCfg), C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int,
+                                     C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int,
+                                     C.c_void_p]),
+    "uvad_sampler_step": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_sampler_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.POINTER(C.c_int64), C.c_int64, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uvad_sampler_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "uvad_sampler_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "uvad_cuts_max_per_row": (C.c_int, [C.POINTER(CutsCfg), C.c_int]),
     "uvad_cuts_max_samples": (C.c_int64, [C.POINTER(CutsCfg), C.c_int64]),
     "uvad_cuts_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),

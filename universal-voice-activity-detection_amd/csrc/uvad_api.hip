@@ -111,6 +111,8 @@ struct ScoreState { int n_points = 0, bins = 0; };
 struct MixState { const float *bank = nullptr; int n_clips = 0, Q = 0, max_seg = 0; };
 // a reverberation state (uvad_reverb_*): the same for the bank of impulse responses
 struct ReverbState { const float *bank = nullptr; int n_rirs = 0, normalize = 0; };
+// a sampler state (uvad_sampler_*): the caller's corpus and what reset fixed (the device header holds the same)
+struct SamplerState { const void *pcm = nullptr; int fmt = 0, R = 0, n_sup = 0, D = 0, geometry = 0, drop_last = 0, batch = 0; int64_t W = 0, T = 0; };
 
 struct uvad_ctx {
     std::map<void *, StreamCounters> streams;   // host mirror of the lock-step stream groups, keyed by d_state
@@ -141,6 +143,7 @@ struct uvad_ctx {
     SincTrainShape snts{};
     std::map<void *, MixState> mixes;           // ... and of the noise-mix states (uvad_mix_*)
     std::map<void *, ReverbState> reverbs;      // ... and of the reverberation states (uvad_reverb_*)
+    std::map<void *, SamplerState> samplers;    // ... and of the sampler states (uvad_sampler_*)
     std::map<void *, int> optims;               // ... and of the optimizer states (uvad_optim_*): n_lr at reset
     int device = 0, n_cu = 256;
     bool has_fb = false, has_model = false, finalized = false, tables_set = false;
@@ -4087,6 +4090,155 @@ int uvad_reverb_step(uvad_ctx *c, const void *d_in, int fmt, int B, int64_t S, c
 int uvad_reverb_apply(uvad_ctx *c, const void *d_in, int fmt, int B, int64_t S, const int64_t *d_nsamp, float *d_out, int32_t *d_plan, int64_t row0,
                       uint64_t draw, void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream) {
     return reverb_call(c, "uvad_reverb_apply", d_in, fmt, B, S, d_nsamp, d_out, d_plan, false, row0, draw, d_state, state_bytes, d_ws, ws_bytes, stream);
+}
+
+// ---- training batches drawn on the device (sampler.hip) ----------------------------------------------------------------------------------
+// nullptr: the configuration is in range; else the word uvad_last_error names
+static const char *sampler_cfg_error(const uvad_sampler_cfg *q, int D) {
+    if (!q) return "cfg is NULL";
+    if (q->window < 1 || q->window > SAMPLER_MAX_LEN) return "window must lie in [1, 2^31 - 1]";
+    if (q->min_keep < 0 || q->min_keep >= q->window) return "min_keep must lie in [0, window)";
+    if (q->geometry != UVAD_SAMPLER_FBANK && q->geometry != UVAD_SAMPLER_SINCNET) return "geometry must be UVAD_SAMPLER_FBANK or UVAD_SAMPLER_SINCNET";
+    if (q->geometry == UVAD_SAMPLER_SINCNET && q->step < 1) return "step must be at least 1";
+    if (q->geometry == UVAD_SAMPLER_SINCNET && q->half < 0) return "half must be >= 0";
+    if (D < 1 || D > SAMPLER_MAX_SETS) return "D must lie in [1, 64]";
+    if (q->drop_last && D > 1) return "drop_last needs D = 1";
+    if (q->drop_last && q->batch < 1) return "drop_last needs batch >= 1";
+    return nullptr;
+}
+
+size_t uvad_sampler_state_bytes(const uvad_sampler_cfg *q, int R, int n_sup, int D) {
+    if (sampler_cfg_error(q, D) || R < 1 || n_sup < 0) return 0;
+    return sampler_layout(R, n_sup).total;
+}
+
+size_t uvad_sampler_ws_bytes(int B) {
+    if (B < 1) return 0;
+    return sampler_ws_bytes(B);
+}
+
+int uvad_sampler_reset(uvad_ctx *c, void *d_state, size_t state_bytes, const uvad_sampler_cfg *q, const void *d_pcm, int fmt,
+                       const int64_t *h_rec_first, int R, const int64_t *h_sup, const int32_t *h_sup_first, int n_sup, const int32_t *h_rec_set,
+                       const double *h_weight, int D, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_state || !d_pcm || !h_rec_first || !h_sup_first || !h_rec_set || !h_weight) return fail(c, UVAD_E_ARG, "uvad_sampler_reset: bad argument");
+    if (const char *e = sampler_cfg_error(q, D)) return fail(c, UVAD_E_ARG, std::string("uvad_sampler_reset: ") + e);
+    if (fmt != UVAD_INGEST_F32 && fmt != UVAD_INGEST_I16) return fail(c, UVAD_E_ARG, "uvad_sampler_reset: fmt must be UVAD_INGEST_F32 or UVAD_INGEST_I16");
+    if (R < 1) return fail(c, UVAD_E_ARG, "uvad_sampler_reset: R must be at least 1");
+    if (n_sup < 0 || (n_sup > 0 && !h_sup)) return fail(c, UVAD_E_ARG, "uvad_sampler_reset: n_sup must be >= 0 and h_sup given");
+    if (reinterpret_cast<uintptr_t>(d_state) % 16) return fail(c, UVAD_E_ARG, "uvad_sampler_reset: d_state must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_pcm) % (fmt == UVAD_INGEST_F32 ? 4 : 2)) return fail(c, UVAD_E_ARG, "uvad_sampler_reset: d_pcm must be aligned to its element");
+    const SamplerLayout l = sampler_layout(R, n_sup);
+    std::vector<char> host(l.total, 0);
+    SamplerTables t{};
+    t.q = q; t.fmt = fmt; t.rec_first = h_rec_first; t.R = R; t.sup = h_sup; t.sup_first = h_sup_first; t.n_sup = n_sup; t.rec_set = h_rec_set;
+    t.weight = h_weight; t.D = D;
+    if (const char *e = sampler_build(t, host.data())) return fail(c, UVAD_E_ARG, std::string("uvad_sampler_reset: ") + e);
+    if (state_bytes < l.total) return fail(c, UVAD_E_ARG, "uvad_sampler_reset: state too small: need " + std::to_string(l.total) + " bytes");
+    SamplerHeader *h = reinterpret_cast<SamplerHeader *>(host.data());
+    int64_t T;
+    if (q->geometry == UVAD_SAMPLER_FBANK) {
+        if (!c->has_fb) return fail(c, UVAD_E_STATE, "uvad_sampler_reset: UVAD_SAMPLER_FBANK needs a context with a feature configuration");
+        h->hop = c->fb.frame_shift; h->frame_len = c->fb.frame_len; h->snip = c->fb.snip_edges != 0;
+        T = uvad_num_frames(c, q->window);
+    } else {
+        if (!c->has_sinc) return fail(c, UVAD_E_STATE, "uvad_sampler_reset: UVAD_SAMPLER_SINCNET needs uvad_sincnet_configure");
+        h->kw[0] = c->sc.kernel_size; h->kw[1] = c->sc.k2; h->kw[2] = c->sc.k3; h->stride0 = c->sc.stride;
+        T = uvad_sincnet_num_frames(c, q->window);
+    }
+    if (T != sampler_frames(*h, q->window)) return fail(c, UVAD_E_STATE, "uvad_sampler_reset: internal: the frame count disagrees with the front end's");
+    if (T < 1) return fail(c, UVAD_E_ARG, "uvad_sampler_reset: a window of " + std::to_string(q->window) + " samples gives no frame");
+    c->samplers.erase(d_state);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));      // what the stream still does to this state comes first
+    HIPCHK(c, hipMemcpy(d_state, host.data(), host.size(), hipMemcpyHostToDevice));
+    SamplerState g;
+    g.pcm = d_pcm; g.fmt = fmt; g.R = R; g.n_sup = n_sup; g.D = D; g.geometry = q->geometry; g.drop_last = q->drop_last != 0; g.batch = q->batch;
+    g.W = q->window; g.T = T;
+    c->samplers[d_state] = g;
+    return UVAD_OK;
+}
+
+// the checks uvad_sampler_read / _write share with the step: a state that was reset, and large enough
+static int sampler_state_check(uvad_ctx *c, const std::string &f, const void *d_state, size_t state_bytes, const SamplerState **out) {
+    if (!d_state) return fail(c, UVAD_E_ARG, f + ": bad argument");
+    if (reinterpret_cast<uintptr_t>(d_state) % 16) return fail(c, UVAD_E_ARG, f + ": d_state must be 16-byte aligned");
+    auto it = c->samplers.find(const_cast<void *>(d_state));
+    if (it == c->samplers.end()) return fail(c, UVAD_E_STATE, f + ": call uvad_sampler_reset on this state first");
+    const size_t need = sampler_layout(it->second.R, it->second.n_sup).total;
+    if (state_bytes < need) return fail(c, UVAD_E_ARG, f + ": state too small: need " + std::to_string(need) + " bytes");
+    *out = &it->second;
+    return UVAD_OK;
+}
+
+static int sampler_call(uvad_ctx *c, const char *fn, int B, float *d_out, int64_t ld_out, int64_t *d_nsamp, uint8_t *d_labels, int64_t ld_gt,
+                        int32_t *d_frames, int32_t *d_plan, bool take, const int64_t *h_cursor, int64_t row0, uint64_t draw, void *d_state,
+                        size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    const std::string f(fn);
+    if (!d_out || !d_nsamp || !d_labels || !d_frames || !d_state || !d_ws || (!take && !h_cursor)) return fail(c, UVAD_E_ARG, f + ": bad argument");
+    if (B < 1) return fail(c, UVAD_E_ARG, f + ": B must be at least 1");
+    if (reinterpret_cast<uintptr_t>(d_state) % 16 || reinterpret_cast<uintptr_t>(d_ws) % 16)
+        return fail(c, UVAD_E_ARG, f + ": d_state and d_ws must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_out) % 4 || reinterpret_cast<uintptr_t>(d_nsamp) % 8 || reinterpret_cast<uintptr_t>(d_frames) % 4 ||
+        reinterpret_cast<uintptr_t>(d_plan) % 4)
+        return fail(c, UVAD_E_ARG, f + ": d_out, d_nsamp, d_frames and d_plan must be aligned to their element");
+    const SamplerState *gp = nullptr;
+    if (int r = sampler_state_check(c, f, d_state, state_bytes, &gp)) return r;
+    const SamplerState &g = *gp;
+    if (g.geometry == UVAD_SAMPLER_FBANK ? !c->has_fb : !c->has_sinc)
+        return fail(c, UVAD_E_STATE, f + ": the label geometry's configuration is missing from the context");
+    if (ld_out < g.W) return fail(c, UVAD_E_ARG, f + ": ld_out must be at least the window, " + std::to_string(g.W));
+    if (ld_gt < g.T) return fail(c, UVAD_E_ARG, f + ": ld_gt must be at least the window's frames, " + std::to_string(g.T));
+    if (g.drop_last && B != g.batch) return fail(c, UVAD_E_ARG, f + ": drop_last: B must be the configuration's batch, " + std::to_string(g.batch));
+    if ((int64_t)B * (g.W / 4096 + 1) > 2147483647LL) return fail(c, UVAD_E_ARG, f + ": B x ceil(window / 4096) must stay below 2^31");
+    const size_t need_ws = sampler_ws_bytes(B);
+    if (ws_bytes < need_ws) return fail(c, UVAD_E_ARG, f + ": workspace too small: need " + std::to_string(need_ws) + " bytes");
+    SamplerArgs a{};
+    a.B = B; a.out = d_out; a.ld_out = ld_out; a.nsamp = reinterpret_cast<long long *>(d_nsamp); a.labels = d_labels; a.ld_gt = ld_gt;
+    a.frames = d_frames; a.plan = d_plan; a.pcm = g.pcm; a.fmt = g.fmt; a.state = d_state; a.ws = d_ws; a.R = g.R; a.n_sup = g.n_sup; a.D = g.D;
+    a.W = g.W; a.T = g.T; a.take = take; a.draw = draw; a.row0 = row0;
+    if (!take)
+        for (int d = 0; d < g.D; ++d) {
+            if (h_cursor[d] < 0) return fail(c, UVAD_E_ARG, f + ": a cursor must be >= 0");
+            a.cursor[d] = h_cursor[d];
+        }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_sampler(a, (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_sampler_step(uvad_ctx *c, int B, float *d_out, int64_t ld_out, int64_t *d_nsamp, uint8_t *d_labels, int64_t ld_gt, int32_t *d_frames,
+                      int32_t *d_plan, void *d_state, size_t state_bytes, void *d_ws, size_t ws_bytes, void *stream) {
+    return sampler_call(c, "uvad_sampler_step", B, d_out, ld_out, d_nsamp, d_labels, ld_gt, d_frames, d_plan, true, nullptr, 0, 0, d_state, state_bytes,
+                        d_ws, ws_bytes, stream);
+}
+
+int uvad_sampler_apply(uvad_ctx *c, int B, float *d_out, int64_t ld_out, int64_t *d_nsamp, uint8_t *d_labels, int64_t ld_gt, int32_t *d_frames,
+                       int32_t *d_plan, const int64_t *h_cursor, int64_t row0, uint64_t draw, void *d_state, size_t state_bytes, void *d_ws,
+                       size_t ws_bytes, void *stream) {
+    return sampler_call(c, "uvad_sampler_apply", B, d_out, ld_out, d_nsamp, d_labels, ld_gt, d_frames, d_plan, false, h_cursor, row0, draw, d_state,
+                        state_bytes, d_ws, ws_bytes, stream);
+}
+
+int uvad_sampler_read(uvad_ctx *c, const void *d_state, size_t state_bytes, int64_t *d_out, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_out || reinterpret_cast<uintptr_t>(d_out) % 8) return fail(c, UVAD_E_ARG, "uvad_sampler_read: bad argument");
+    const SamplerState *g = nullptr;
+    if (int r = sampler_state_check(c, "uvad_sampler_read", d_state, state_bytes, &g)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_sampler_read(d_state, g->D, reinterpret_cast<long long *>(d_out), (hipStream_t)stream));
+    return UVAD_OK;
+}
+
+int uvad_sampler_write(uvad_ctx *c, void *d_state, size_t state_bytes, const int64_t *d_in, void *stream) {
+    if (!c) return UVAD_E_ARG;
+    if (!d_in || reinterpret_cast<uintptr_t>(d_in) % 8) return fail(c, UVAD_E_ARG, "uvad_sampler_write: bad argument");
+    const SamplerState *g = nullptr;
+    if (int r = sampler_state_check(c, "uvad_sampler_write", d_state, state_bytes, &g)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_sampler_write(d_state, g->D, reinterpret_cast<const long long *>(d_in), (hipStream_t)stream));
+    return UVAD_OK;
 }
 
 // ---- speech cuts (cuts.hip) --------------------------------------------------------------------------------------------------------------

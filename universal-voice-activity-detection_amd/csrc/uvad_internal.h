@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdint.h>
+#include "../../include/uvad.h"
 
 namespace uvad {
 
@@ -991,5 +992,60 @@ ReverbLayout reverb_layout(int n_rirs);
 size_t reverb_ws_bytes(int B);
 hipError_t launch_reverb_delays(const float *bank, void *state, int n_rirs, hipStream_t s);
 hipError_t launch_reverb(const ReverbArgs &a, hipStream_t s);
+
+// ---- sampler.hip: training batches drawn on the device (uvad_sampler_*, include/uvad.h): the window table, the plan of every row, the gather
+//      of the samples, the labels ----
+// State: SamplerHeader (256 bytes) | SamplerSet [SAMPLER_MAX_SETS] | slot_rec [R] int32 (the recordings in table order) | win_first [R + 1] int32
+//        (the first window of every slot) | rec_first [R + 1] int64 | sup_first [R + 1] int32 | sup [n_sup][2] int64; every part 256-byte aligned.
+// Workspace: MixWsHead (256 bytes: the call's draw and first row index) | the plan [B][8] int32 (the record of include/uvad.h; d_plan is a copy).
+constexpr unsigned SAMPLER_MAGIC = 0x55565350u;      // "UVSP"
+constexpr int SAMPLER_PLAN_WORDS = 8;                // UVAD_SAMPLER_PLAN_WORDS: {dataset, epoch, position, window, recording, start, n, T_b}
+constexpr int SAMPLER_MAX_SETS = 64;                 // UVAD_SAMPLER_MAX_SETS
+constexpr long long SAMPLER_MAX_LEN = 2147483647LL;  // samples of a recording, of a window, windows in all: plan words are int32
+struct SamplerHeader {
+    unsigned magic; int R, n_sup, D;
+    long long W;                                     // byte 16
+    unsigned long long seed;                         // byte 24
+    long long total;                                 // byte 32: samples of the corpus = rec_first[R]
+    int fmt, geometry;                               // byte 40
+    int n_windows, batch;                            // byte 48
+    unsigned long long draws;                        // byte 56: steps drawn so far (the draw ordinal), where the mix state keeps its own
+    int shuffle, drop_last, pad, half;               // byte 64
+    int step, hop, frame_len, snip;                  // byte 80: hop / frame_len / snip_edges: the log-mel front end's framing (FBANK)
+    int kw[3], stride0;                              // byte 96: the waveform front end's stages (SINCNET)
+    long long min_keep;                              // byte 112
+    int reserved[34];
+};                                                   // 256 bytes
+struct SamplerSet { long long cursor, L; unsigned long long cum; int first, N; };   // 32 bytes per dataset
+struct SamplerLayout { size_t off_sets, off_slot, off_win, off_first, off_supf, off_sup, total; };
+// frames of a row of n samples on the label grid of the header: uvad_num_frames / uvad_sincnet_num_frames (the floor chains of frames_of_kernel
+// and sinc_row_geometry_kernel), for the host and the device
+__host__ __device__ inline long long sampler_frames(const SamplerHeader &h, long long n) {
+    if (h.geometry == UVAD_SAMPLER_FBANK) return h.snip ? (n < h.frame_len ? 0 : 1 + (n - h.frame_len) / h.hop) : (n + h.hop / 2) / h.hop;
+    long long L = n;
+    for (int i = 0; i < 3; ++i) {
+        const long long lconv = L >= h.kw[i] ? (L - h.kw[i]) / (i == 0 ? h.stride0 : 1) + 1 : 0;
+        L = lconv / 3;
+    }
+    return L;
+}
+struct SamplerTables {                               // what uvad_sampler_reset is given on the host
+    const uvad_sampler_cfg *q; int fmt;
+    const int64_t *rec_first; int R; const int64_t *sup; const int32_t *sup_first; int n_sup; const int32_t *rec_set; const double *weight; int D;
+};
+struct SamplerArgs {
+    int B; float *out; long long ld_out; long long *nsamp; unsigned char *labels; long long ld_gt; int *frames; int *plan;   // plan: may be null
+    const void *pcm; int fmt; void *state; void *ws;
+    int R, n_sup, D; long long W, T;
+    bool take; unsigned long long draw; long long row0; long long cursor[SAMPLER_MAX_SETS];   // take: ordinal and cursors are the state's, which advance
+};
+SamplerLayout sampler_layout(int R, int n_sup);
+size_t sampler_ws_bytes(int B);
+// Validates the tables and fills `image` (sampler_layout(R, n_sup).total bytes; the header's geometry fields are the caller's, already in
+// image).  Returns nullptr, or the sentence uvad_last_error reports.  Host only, no HIP call.
+const char *sampler_build(const SamplerTables &t, char *image);
+hipError_t launch_sampler(const SamplerArgs &a, hipStream_t s);
+hipError_t launch_sampler_read(const void *state, int D, long long *out, hipStream_t s);
+hipError_t launch_sampler_write(void *state, int D, const long long *in, hipStream_t s);
 
 }  // namespace uvad

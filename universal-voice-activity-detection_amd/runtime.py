@@ -1665,6 +1665,118 @@ class VadRuntime:
                 self._check(self.lib.uvad_reverb_apply(*head, int(row0), int(draw) & 0xFFFFFFFFFFFFFFFF, *tail))
             return out if plan is None else (out, plan)
 
+    # ------------------------------------------------------------------ training batches drawn on the device (uvad_sampler_*)
+    def sampler_open(self, pcm, rec_lengths, supervisions, window: int, min_keep: int, geometry: str, half: int = 496, step: int = 270,
+                     datasets=None, weights=None, shuffle: bool = True, drop_last: bool = False, pad: bool = False, seed: int = 0,
+                     batch: int = 0):
+        """Allocate and reset a sampler state (uvad_sampler_reset).  pcm: the recordings back to back, a 1-D f32 or int16 tensor (moved to
+        this device; the handle keeps it alive); rec_lengths: samples per recording; supervisions: per recording, an (n, 2) table of
+        {start, end} in samples of that recording.  window, min_keep in samples; geometry "fbank" or "sincnet" (half, step: the
+        waveform grid's receptive-field half width and frame step); datasets: each recording's dataset index (None: one dataset),
+        weights: one per dataset; shuffle, drop_last (with batch, the batch size it refers to), pad and seed as include/uvad.h."""
+        lens = [int(v) for v in rec_lengths]
+        if not lens or min(lens) < 1:
+            raise ValueError("every recording needs at least 1 sample")
+        if geometry not in ("fbank", "sincnet"):
+            raise ValueError(f"unknown geometry {geometry!r} (fbank, sincnet)")
+        if len(supervisions) != len(lens):
+            raise ValueError(f"{len(supervisions)} supervision tables for {len(lens)} recordings")
+        R = len(lens)
+        first = np.zeros(R + 1, np.int64)
+        first[1:] = np.cumsum(lens)
+        tables = [np.asarray(s, np.int64).reshape(-1, 2) for s in supervisions]
+        sup_first = np.zeros(R + 1, np.int32)
+        sup_first[1:] = np.cumsum([len(t) for t in tables])
+        sup = np.ascontiguousarray(np.concatenate(tables) if tables else np.zeros((0, 2)), np.int64)
+        rec_set = np.zeros(R, np.int32) if datasets is None else np.ascontiguousarray(datasets, np.int32)
+        if rec_set.shape != (R,):
+            raise ValueError(f"datasets must name one dataset per recording ({R})")
+        w = np.ones(int(rec_set.max()) + 1, np.float64) if weights is None else np.ascontiguousarray(weights, np.float64).reshape(-1)
+        D = len(w)
+        with torch.cuda.device(self.device):
+            pcm = torch.as_tensor(pcm)
+            if pcm.dtype != torch.int16:
+                pcm = pcm.to(torch.float32)
+            pcm = pcm.reshape(-1).to(self.device).contiguous()
+            if pcm.numel() != int(first[-1]):
+                raise ValueError(f"pcm holds {pcm.numel()} samples, the recording lengths add up to {int(first[-1])}")
+            fmt = _lib.INGEST_I16 if pcm.dtype == torch.int16 else _lib.INGEST_F32
+            cfg = _lib.SamplerCfg(int(window), int(min_keep), _lib.SAMPLER_FBANK if geometry == "fbank" else _lib.SAMPLER_SINCNET, int(half),
+                                  int(step), int(bool(shuffle)), int(bool(drop_last)), int(bool(pad)), int(batch), int(seed) & 0xFFFFFFFFFFFFFFFF)
+            frames = self.lib.uvad_num_frames if geometry == "fbank" else self.lib.uvad_sincnet_num_frames
+            st = {"cfg": cfg, "pcm": pcm, "first": first, "R": R, "D": D, "W": int(window), "T": int(frames(self.ctx, int(window))), "ws": None,
+                  "plan_words": _lib.SAMPLER_PLAN_WORDS, "bufs": {},
+                  "state": torch.zeros(max(int(self.lib.uvad_sampler_state_bytes(C.byref(cfg), R, len(sup), D)), 256), dtype=torch.uint8,
+                                       device=self.device)}
+            self._check(self.lib.uvad_sampler_reset(
+                self.ctx, st["state"].data_ptr(), st["state"].numel(), C.byref(cfg), pcm.data_ptr(), fmt, first.ctypes.data_as(C.POINTER(C.c_int64)),
+                R, sup.ctypes.data_as(C.POINTER(C.c_int64)) if len(sup) else None, sup_first.ctypes.data_as(C.POINTER(C.c_int32)), len(sup),
+                rec_set.ctypes.data_as(C.POINTER(C.c_int32)), w.ctypes.data_as(C.POINTER(C.c_double)), D, self._stream()))
+            return st
+
+    def sampler_step(self, st, B: int, out=None, labels=None, plan=False, cursor=None, draw=None, row0: int = 0):
+        """One batch of B rows (uvad_sampler_step) -> dict(pcm (B, W) f32, nsamp (B,) int64, labels (B, T) uint8, frames (B,) int32, and
+        plan (B, 8) int32 when asked for).  out / labels: the tensors to write (row strides of at least W / T elements; None: the
+        handle's own per batch size, overwritten by the next step of that size); plan: True, or the tensor to write.  cursor and draw:
+        an explicit position (uvad_sampler_apply: no state update), with row0 the index the first row draws under.  After the first call
+        with a batch size nothing is allocated: the call can be captured."""
+        B = int(B)
+        with torch.cuda.device(self.device):
+            buf = st["bufs"].get(B)
+            if buf is None:
+                buf = st["bufs"][B] = {"pcm": torch.zeros((B, st["W"]), dtype=torch.float32, device=self.device),
+                                       "labels": torch.zeros((B, st["T"]), dtype=torch.uint8, device=self.device),
+                                       "nsamp": torch.zeros(B, dtype=torch.int64, device=self.device),
+                                       "frames": torch.zeros(B, dtype=torch.int32, device=self.device),
+                                       "plan": torch.zeros((B, _lib.SAMPLER_PLAN_WORDS), dtype=torch.int32, device=self.device)}
+            out = buf["pcm"] if out is None else out
+            labels = buf["labels"] if labels is None else labels
+            for t, dt, w, name in ((out, torch.float32, st["W"], "out"), (labels, torch.uint8, st["T"], "labels")):
+                if not (torch.is_tensor(t) and t.device == self.device and t.dtype == dt and t.dim() == 2 and t.shape[0] == B and t.shape[1] >= w and
+                        t.stride(1) == 1 and t.stride(0) >= t.shape[1]):
+                    raise ValueError(f"{name} must be a ({B}, >= {w}) {dt} tensor on {self.device} with unit column stride")
+            if plan is True:
+                plan = buf["plan"]
+            elif plan is False:
+                plan = None
+            elif not (torch.is_tensor(plan) and plan.device == self.device and plan.dtype == torch.int32 and
+                      tuple(plan.shape) == (B, _lib.SAMPLER_PLAN_WORDS) and plan.is_contiguous()):
+                raise ValueError(f"plan must be a contiguous int32 tensor of shape ({B}, {_lib.SAMPLER_PLAN_WORDS}) on {self.device}")
+            need = int(self.lib.uvad_sampler_ws_bytes(B))
+            if st["ws"] is None or st["ws"].numel() < need:
+                st["ws"] = torch.zeros(need, dtype=torch.uint8, device=self.device)
+            head = (self.ctx, B, out.data_ptr(), out.stride(0), buf["nsamp"].data_ptr(), labels.data_ptr(), labels.stride(0), buf["frames"].data_ptr(),
+                    None if plan is None else plan.data_ptr())
+            tail = (st["state"].data_ptr(), st["state"].numel(), st["ws"].data_ptr(), st["ws"].numel(), self._stream())
+            if cursor is None and draw is None:
+                self._check(self.lib.uvad_sampler_step(*head, *tail))
+            else:
+                if cursor is None or draw is None:
+                    raise ValueError("cursor and draw go together (uvad_sampler_apply)")
+                cur = np.ascontiguousarray(np.broadcast_to(np.asarray(cursor, np.int64), (st["D"],)))
+                self._check(self.lib.uvad_sampler_apply(*head, cur.ctypes.data_as(C.POINTER(C.c_int64)), int(row0), int(draw) & 0xFFFFFFFFFFFFFFFF, *tail))
+            res = {"pcm": out, "nsamp": buf["nsamp"], "labels": labels, "frames": buf["frames"]}
+            if plan is not None:
+                res["plan"] = plan
+            return res
+
+    def sampler_read(self, st) -> np.ndarray:
+        """The record {draw ordinal, cursor of every dataset} (1 + D int64) of uvad_sampler_read, on the host (synchronises)."""
+        with torch.cuda.device(self.device):
+            rec = torch.zeros(1 + st["D"], dtype=torch.int64, device=self.device)
+            self._check(self.lib.uvad_sampler_read(self.ctx, st["state"].data_ptr(), st["state"].numel(), rec.data_ptr(), self._stream()))
+            return rec.cpu().numpy()
+
+    def sampler_write(self, st, record):
+        """Set the record sampler_read returned (uvad_sampler_write): the next step continues where that state stood."""
+        rec = np.ascontiguousarray(record, np.int64).reshape(-1)
+        if rec.shape != (1 + st["D"],):
+            raise ValueError(f"the record holds 1 + D = {1 + st['D']} words")
+        with torch.cuda.device(self.device):
+            dev = torch.from_numpy(rec).to(self.device)
+            self._check(self.lib.uvad_sampler_write(self.ctx, st["state"].data_ptr(), st["state"].numel(), dev.data_ptr(), self._stream()))
+            torch.cuda.current_stream(self.device).synchronize()     # `dev` is freed on return
+
     def _lstm_train_ws(self, h, B: int, T: int):
         self._train_configure(h)
         need = int(self.lib.uvad_lstm_train_ws_bytes(self.ctx, B, T))

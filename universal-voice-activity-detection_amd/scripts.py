@@ -992,18 +992,109 @@ def _augment(rt, reverb, mix, x, nsamp=None):
     return x
 
 
-def _save_training_checkpoint(kwargs, model, out, epoch: int, global_step: int):
+def _save_training_checkpoint(kwargs, model, out, epoch: int, global_step: int, extra_states=None):
     """train_vad's checkpoint: {"state_dict", "epoch", "global_step", "optimizer_states" (VadModel.optimizer_state: every family's masters,
-    m, v and scalars, and the joint optimizer's counts)} at experiments_dir/checkpoint-epoch=NN.ckpt -> out, completed."""
+    m, v and scalars, and the joint optimizer's counts; extra_states, the device sampler's record, joins them)} at
+    experiments_dir/checkpoint-epoch=NN.ckpt -> out, completed."""
     path = os.path.join(kwargs.get("experiments_dir", "."), f"checkpoint-epoch={epoch:02d}.ckpt")
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     out["global_step"] = global_step
     blob = {"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "epoch": epoch, "global_step": global_step}
     if getattr(model, "_adapt_full", None) is not None:
         blob["optimizer_states"] = model.optimizer_state()
+        blob["optimizer_states"].update(extra_states or {})
     torch.save(blob, path)
     out["checkpoint_path"] = path
     return out
+
+
+def sampler_corpus(paths, labels, rt, sr=16000):
+    """Wav files and their label files -> what VadRuntime.sampler_open takes: (pcm back to back -- int16 when every file is, else f32 --,
+    samples per recording, per recording the (n, 2) supervision table in samples, rounded to the nearest sample)."""
+    from .postprocess import read_label_file
+    pcms = [np.asarray(_wav_recordings(p, "first", rt, sr)[0]["pcm"]) for p in paths]
+    if not all(x.dtype == np.int16 for x in pcms):
+        pcms = [x.astype(np.float32) * np.float32(1.0 / 32768.0) if x.dtype == np.int16 else x.astype(np.float32) for x in pcms]
+    sups = [np.array([(int(round(a * sr)), int(round(b * sr))) for a, b in read_label_file(l)], np.int64).reshape(-1, 2) for l in labels]
+    return np.concatenate(pcms), [len(x) for x in pcms], sups
+
+
+def _train_vad_device_sampler(kwargs, src, val_paths, val_labels, model, rt, device, seed, sr, sincnet):
+    """train_vad with ``device_sampler=True``, for both front ends: the recordings and their supervision tables are uploaded once
+    (sampler_corpus, VadRuntime.sampler_open) and every step is sampler_step -> _augment -> train_step; no batch is assembled on the host.
+    Windows of ``window_seconds``; a tail is kept when it is longer than ``min_keep_seconds`` (default: 3 / 5 of the window for the waveform
+    model, the reference's 3 s of 5 s, whose rows are zero-padded to the window, pad=True; for the log-mel model 0, raised to the longest
+    tail that still has no frame).  ``input["datasets"]`` names each recording's dataset and ``dataset_weights`` = {name: weight} multiplexes
+    them (the reference's dataset_weights; absent: one dataset).  An epoch is steps_per_epoch = (windows in all) // rows steps of
+    rows = max_duration / window_seconds rows.  The sampler's record {draw ordinal, cursors} joins "optimizer_states" in the checkpoint
+    (key "sampler"), so a resumed run draws the batches an uninterrupted one draws.  Validation walks the held-out recordings' windows in
+    table order through a second state (shuffle=False)."""
+    window_s = float(kwargs.get("window_seconds") or 5.0)
+    Wn = int(round(window_s * sr))
+    rows = max(1, int(float(kwargs["max_duration"]) / window_s))
+    keep_s = kwargs.get("min_keep_seconds")
+    keep = int(round((0.6 * window_s if sincnet else 0.0) * sr)) if keep_s is None else int(round(float(keep_s) * sr))
+    if not sincnet:
+        keep = max(keep, next(n for n in range(1, Wn + 1) if rt.num_frames(n) >= 1) - 1)      # every kept row has a frame
+    geometry = "sincnet" if sincnet else "fbank"
+    names = list(src.get("datasets") or ["all"] * len(src["paths"]))
+    if len(names) != len(src["paths"]):
+        raise ValueError('train_vad: input["datasets"] names one dataset per path')
+    order = sorted(set(names), key=names.index)
+    given = dict(kwargs.get("dataset_weights") or {})
+    if set(given) - set(order):
+        raise ValueError(f"train_vad: dataset_weights names unknown datasets {sorted(set(given) - set(order))}")
+    weights = [float(given.get(n, 1.0)) for n in order]
+
+    def open_state(paths, labels, **kw):
+        pcm, lens, sups = sampler_corpus(paths, labels, rt, sr)
+        st = rt.sampler_open(pcm, lens, sups, Wn, keep, geometry, pad=sincnet, seed=seed, **kw)
+        return st, sum(n // Wn + (n % Wn > keep) for n in lens)
+
+    st, n_windows = open_state(src["paths"], src["labels"], datasets=[order.index(n) for n in names], weights=weights, shuffle=True)
+    held, n_held = open_state(val_paths, val_labels, shuffle=False)
+    mix, reverb = _open_noise(kwargs, rt, seed, sr), _open_reverb(kwargs, rt, seed, sr)
+    steps_per_epoch = max(1, n_windows // rows)
+    epochs, every = int(kwargs.get("max_epochs", 10)), max(1, int(kwargs.get("check_val_every_n_epoch", 1)))
+    accumulate = max(1, int(kwargs.get("accumulate_grad_batches", 1)))
+    out = {"train_loss": [], "val_loss": [], "val_metrics": None, "steps_per_epoch": steps_per_epoch, "first_plan": None}
+
+    def batch_of(res, augment):
+        x = _augment(rt, reverb, mix, res["pcm"], res["nsamp"]) if augment else res["pcm"]
+        if sincnet:
+            return {"inputs": x, "is_voice": res["labels"]}
+        return {"inputs": rt.fbank(x, lengths=res["nsamp"]), "is_voice": res["labels"], "lengths": res["frames"]}
+
+    def validate(epoch):
+        model.train_commit()
+        for i, at in enumerate(range(0, n_held, rows)):               # table order from window 0, the last batch as short as it must be
+            model.validation_step(batch_of(rt.sampler_step(held, min(rows, n_held - at), cursor=[at], draw=i), False), i)
+        out["val_metrics"] = model.validation_metrics(reset=True)
+        out["val_loss"].append((epoch, out["val_metrics"]["val_loss"]))
+        print(f"epoch {epoch}: val_loss {out['val_metrics']['val_loss']:.6f}")
+
+    optim = _optim_options(kwargs, float(kwargs.get("learning_rate", 1e-3)), epochs * steps_per_epoch // accumulate)
+    first, done = _resume_point(kwargs, model)
+    if first or done:
+        record = torch.load(kwargs["checkpoint_path"], map_location="cpu", weights_only=True)["optimizer_states"].get("sampler")
+        if record is None:
+            raise ValueError("train_vad: the checkpoint was not written with device_sampler=True: it holds no sampler record")
+        rt.sampler_write(st, np.asarray(record, np.int64))
+    last = min(epochs, int(kwargs.get("stop_after_epoch") or epochs))
+    step = done * accumulate
+    for epoch in range(first + 1, last + 1):
+        losses = []
+        for _ in range(steps_per_epoch):
+            res = rt.sampler_step(st, rows, plan=out["first_plan"] is None)
+            if out["first_plan"] is None:
+                out["first_plan"] = res["plan"].cpu().numpy().copy()
+            losses.append(model.train_step(batch_of(res, True), step, accumulate=accumulate, optim=optim))
+            step += 1
+        out["train_loss"].append(float(torch.stack(losses).mean()))
+        print(f"epoch {epoch}: train_loss {out['train_loss'][-1]:.6f}")
+        if epoch % every == 0 or epoch == last:
+            validate(epoch)
+    return _save_training_checkpoint(kwargs, model, out, last, step // accumulate, {"sampler": [int(v) for v in rt.sampler_read(st)]})
 
 
 def _train_vad_sincnet(kwargs, src, val_paths, val_labels, model, rt, device, seed, sr):
@@ -1113,7 +1204,10 @@ def train_vad(**kwargs):
     dropout draw ordinal and the optimizer's step index are restored and the epochs after the checkpoint's run, so that an interrupted
     run and an uninterrupted one end in the same bytes (with accumulate_grad_batches > 1 a partly accumulated step at the interruption
     is lost).  The draw ordinals of the noise mix and the reverberation are not part of the checkpoint: a resumed run with ``noise``
-    or ``reverb`` draws others than an uninterrupted one."""
+    or ``reverb`` draws others than an uninterrupted one.
+    ``device_sampler=True`` (default False: everything above, launch for launch) draws the batches on the device instead
+    (_train_vad_device_sampler: uvad_sampler_step in front of the same augmentation and train_step, weighted datasets, the sampler's
+    record in the checkpoint); its window order is the sampler's own, not the torch.Generator's."""
     from .postprocess import read_label_file, supervision_frames
     src = kwargs["input"]
     if src.get("kind") != "wav" or not src.get("paths") or len(src.get("labels", ())) != len(src["paths"]):
@@ -1140,6 +1234,8 @@ def train_vad(**kwargs):
         net.attach_fbank(FbankConfig(sampling_rate=sr, num_filters=net.encoding_dim, window_type=kwargs.get("window_type", "povey"),
                                      frame_shift=kwargs["frame_shift"], device="cuda"))
     rt = net.runtime(device)
+    if kwargs.get("device_sampler"):
+        return _train_vad_device_sampler(kwargs, src, val_paths, val_labels, model, rt, device, seed, sr, sincnet)
     if sincnet:
         return _train_vad_sincnet(kwargs, src, val_paths, val_labels, model, rt, device, seed, sr)
 
